@@ -46,6 +46,7 @@ import json
 import os
 import sys
 import time
+import zlib
 
 import numpy as np
 
@@ -83,7 +84,18 @@ def parse_args():
                     help="N>1, quant: keep the TOTAL work fixed (the N = 1 dataset cut into N row ranges) instead of the "
                          "default: one dataset of N x the per-GPU size (per-GPU work fixed)")
     ap.add_argument("--weak", action="store_true", help="(the default at N>1; kept for old command lines)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, "
+                         "finite: NaN / inf written as -1e30 and told apart in DIR/<name>.nonfinite.npy; a fixed seeded row sample "
+                         "of the large arrays, at most 64 MB in all); --gpus 1 only")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs is not None and args.gpus != 1:
+        ap.error("--dump-outputs is supported with --gpus 1 only")
+    return args
 
 
 class Dist:
@@ -195,6 +207,10 @@ class QuantWorkload:
         if nnz is not None:
             self.d_col, self.nnz = d_col, nnz
         self.ctx.ps_dev(self.d_counts, self.d_row_ptr, self.d_col, None, self.d_ps)
+
+    def outputs(self):
+        """what a caller of the step receives: the clustering (row order, CSR lists) and the PS table"""
+        return [("row_of", self.d_row_of), ("row_ptr", self.d_row_ptr), ("col", self.d_col), ("ps", self.d_ps)]
 
     def describe(self):
         tag = "BASELINE config 2" if (self.n, self.s) == (1_000_000, 100) else \
@@ -346,6 +362,9 @@ class CompareWorkload:
         self.ctx.ranksum_dev(self.d_ps, self.d_g1, self.d_g2, self.out)
         self.ctx.bh_masked_dev(self.out["p"], self.out["tested"], self.d_q)     # BH over the tested rows, as the product does
 
+    def outputs(self):
+        return list(self.out.items()) + [("q", self.d_q)]
+
     def describe(self):
         return {"workload": f"compare_sample_sets {self.n} junctions, {self.g1.size} v {self.g2.size} (BASELINE config 3), "
                             f"rank-sum + BH", "junctions_per_gpu": self.n, "samples": self.s}
@@ -404,6 +423,9 @@ class PairwiseWorkload:
         self.ctx.ps_dev(self.d_counts, self.d_row_ptr, self.d_col, self.d_excl, None)
         self.ctx.fisher_pairs_dev(self.d_counts, self.d_excl, self.d_p)
         self.ctx.bh_columns_dev(self.d_p)
+
+    def outputs(self):
+        return [("p", self.d_p)]          # BH-corrected p-values, [junctions, pairs]
 
     def describe(self):
         return {"workload": f"pairwise {self.n} junctions x {self.s} samples per GPU = {self.pairs} pairs/junction "
@@ -483,6 +505,9 @@ class E2EWorkload(QuantWorkload):
             self.ctx.set_param("ps.quantize3", 0)
         self.ctx.ranksum_dev(self.d_ps, self.d_g1, self.d_g2, self.out)
         self.ctx.bh_masked_dev(self.out["p"], self.out["tested"], self.d_q)     # BH over the tested rows, as the product does
+
+    def outputs(self):
+        return super().outputs() + list(self.out.items()) + [("q", self.d_q)]
 
     def describe(self):
         return {"workload": f"quant + compare end to end, {self.n} junctions x {self.s} samples per GPU "
@@ -790,8 +815,67 @@ def reference_over_port(workload):
         return None
 
 
-def measure(ctx, wl, dist, steps, warmup, gpus, verify=True):
-    """warmup + timed steps of one workload -> (elapsed s [max over ranks], roofline dict, verify dict)"""
+DUMP_BUDGET = 60 << 20          # bytes of .npy data over all arrays of one dump (row indices included): under 64 MB
+DUMP_SEED = 20240917
+DUMP_NONFINITE = -1e30          # stands for NaN / +inf / -inf in a dumped float output (no output here reaches it)
+
+
+def dump_outputs(out_dir, outputs):
+    """Write device arrays as out_dir/<name>.npy: float32 stays float32, every other dtype becomes float64 (exact for
+    the integer outputs).  Every file holds finite numbers only.  In a float output a non-finite entry (PS of 0 / 0
+    is NaN, as in the reference) is written as DUMP_NONFINITE -- far from every value the outputs take, so an entry
+    that turns from NaN into a number changes <name>.npy itself -- and <name>.nonfinite.npy (float32, same shape,
+    written for every float output) says which it was: 0 finite, 1 NaN, 2 +inf, 3 -inf.
+    Budget: taken smallest array first, an array whose full size is at most half of the budget still left is
+    written whole; the others share what is left evenly and are cut to a sample of whole rows: runs of `run`
+    consecutive rows starting at seeded multiples of `run` that depend only on the name and the shape (so the last
+    n_rows % run rows are never in a sample), listed in <name>.rows.npy.  -> {name: rows written}"""
+    os.makedirs(out_dir, exist_ok=True)
+    plan = []
+    for i, (name, d) in enumerate(outputs):
+        out_dtype = np.float32 if d.dtype == np.float32 else np.float64
+        n_rows = d.shape[0] if d.shape else 1
+        row_elems = int(np.prod(d.shape[1:], dtype=np.int64))
+        # values and, for float outputs, the code of every entry
+        row_bytes = max(row_elems, 1) * (np.dtype(out_dtype).itemsize + (4 if d.dtype.kind == "f" else 0))
+        plan.append((n_rows * row_bytes, i, name, d, out_dtype, n_rows, row_elems, row_bytes))
+    plan.sort(key=lambda t: t[:2])
+    left, share, written = DUMP_BUDGET, None, {}
+    for j, (cost, _, name, d, out_dtype, n_rows, row_elems, row_bytes) in enumerate(plan):
+        if share is None and cost <= left // (2 if j + 1 < len(plan) else 1):
+            left -= cost
+            host = d.to_host().astype(out_dtype)
+            rows = None
+        else:
+            share = share or left // (len(plan) - j)            # the rest share what is left evenly
+            want = share // (row_bytes + 8)                     # (+ 8 B of row index per row)
+            if want < 1:
+                raise ValueError(f"--dump-outputs: one row of {name!r} ({row_bytes} B) exceeds its share of the budget")
+            run = max(1, min(256, want // 64))                  # about 64 runs of consecutive rows
+            k = want // run
+            rng = np.random.default_rng([DUMP_SEED, zlib.crc32(name.encode())])
+            starts = np.sort(rng.choice(n_rows // run, size=k, replace=False)) * run
+            host = np.empty((k * run,) + tuple(d.shape[1:]), out_dtype)
+            for i, a in enumerate(starts):
+                host[i * run:(i + 1) * run] = d.offset(int(a) * row_elems, (run,) + tuple(d.shape[1:])).to_host()
+            rows = (starts[:, None] + np.arange(run)[None, :]).ravel().astype(np.float64)
+        if d.dtype.kind == "f":
+            code = np.zeros(host.shape, np.float32)
+            code[np.isnan(host)] = 1
+            code[np.isposinf(host)] = 2
+            code[np.isneginf(host)] = 3
+            host = np.where(code != 0, out_dtype(DUMP_NONFINITE), host).astype(out_dtype)
+            np.save(os.path.join(out_dir, f"{name}.nonfinite.npy"), code)
+        np.save(os.path.join(out_dir, f"{name}.npy"), host)
+        if rows is not None:
+            np.save(os.path.join(out_dir, f"{name}.rows.npy"), rows)
+        written[name] = int(host.shape[0])
+    return written
+
+
+def measure(ctx, wl, dist, steps, warmup, gpus, verify=True, dump_dir=None):
+    """warmup + timed steps of one workload -> (elapsed s [max over ranks], roofline dict, verify dict, dump dict).
+    dump_dir: the last step's outputs are written there (dump_outputs) before anything else touches them."""
     for _ in range(warmup):
         wl.step()
     ctx.sync()
@@ -808,6 +892,7 @@ def measure(ctx, wl, dist, steps, warmup, gpus, verify=True):
     launches, kernel_ms = ctx.prof_query(wl.kernel)
     ctx.prof_enable(0)
     elapsed = dist.max(elapsed)
+    dumped = dump_outputs(dump_dir, wl.outputs()) if dump_dir else None
     avg_ms = kernel_ms / launches if launches else float("nan")
     achieved = wl.alg_bytes / (avg_ms * 1e-3) / 1e9 if launches else float("nan")
     traffic = traffic_from_profiles(wl.key, wl.n, wl.s)
@@ -888,7 +973,7 @@ def measure(ctx, wl, dist, steps, warmup, gpus, verify=True):
         except Exception as e:                       # the figure is a reference point, never a reason to fail the line
             roofline["copy_same_bytes_ms"] = None
             roofline["copy_error"] = str(e)[:120]
-    return elapsed, roofline, v
+    return elapsed, roofline, v, dumped
 
 
 # what "also" reports at N=1: (key, workload class, n, s, rows of the repeated host block, steps, CPU sample)
@@ -929,7 +1014,8 @@ def main():
         wl = WORKLOADS[args.workload](ctx, dist.rank, args.n, args.s)
     wl.key = args.workload
 
-    elapsed, roofline, verify = measure(ctx, wl, dist, args.steps, args.warmup, args.gpus, not args.no_verify)
+    elapsed, roofline, verify, dumped = measure(ctx, wl, dist, args.steps, args.warmup, args.gpus, not args.no_verify,
+                                                args.dump_outputs)
     failed = bool(verify and not verify["ok"])
 
     ps_allgather = None
@@ -998,6 +1084,8 @@ def main():
             (product_sharded and getattr(wl, "comm_note", "x") is None) else (0 if args.gpus > 1 else None),
             "device": info["name"].strip(), "gen_seconds": round(wl.gen_s, 1),
         }
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "rows": dumped}
 
     # ---- the other configurations, same measurement, a few steps each (1 GPU only: the driver's N=1 line)
     if args.gpus == 1 and not args.no_also and args.workload == "quant" and not args.n and not args.s:
@@ -1008,7 +1096,7 @@ def main():
             try:
                 w = WORKLOADS[kind](ctx, 0, n, s, block)
                 w.key = kind
-                el, rl, vf = measure(ctx, w, dist, steps, 5, 1, not args.no_verify)      # (enough steps for the clocks to settle)
+                el, rl, vf, _ = measure(ctx, w, dist, steps, 5, 1, not args.no_verify)      # (enough steps for the clocks to settle)
                 rec = {"metric": w.metric, "value": w.units * steps / el, "unit": w.unit, "steps": steps, "warmup": 5,
                        "ms_per_step": el / steps * 1e3, "dtype": w.dtype, "config": w.describe(), "roofline": rl,
                        "verify": vf, "gen_seconds": round(w.gen_s, 1)}
