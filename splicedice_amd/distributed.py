@@ -203,6 +203,15 @@ def _csr_host(sh):
     return rp, cl, nnz
 
 
+def _size_range_lists(e, d_j, d_row_of, d_rp):
+    """cluster a shard's range once synchronously at load time.  step() clusters it asynchronously, and an asynchronous
+    sdice_cluster_dev only sizes the context's list buffer at 16 entries per junction: a denser range would fail at the
+    next sync.  The synchronous call grows the buffer to the range's list total (it never shrinks) and reports invalid or
+    duplicate junctions here.  (A range that the fast path can only cluster synchronously -- a sort bucket overflow, e.g.
+    more than 16 384 junctions sharing one (chrom, left) -- still fails in step(); that is not handled here.)"""
+    e.cluster_dev(*d_j, d_row_of, d_rp, sync=True)
+
+
 class CompareShard:
     """One rank's part of quant -> compare_sample_sets, resident in HBM (device engines).
 
@@ -246,6 +255,7 @@ class CompareShard:
                 assert len(cr) == rows, (len(cr), rows)
                 self.d_j = [e.to_device(cr, np.int32), e.to_device(l, np.int32), e.to_device(r, np.int32), e.to_device(st, np.int8)]
                 self.d_row_of, self.d_rp = e.empty(rows, np.int32), e.empty(rows + 1, np.int64)
+                _size_range_lists(e, self.d_j, self.d_row_of, self.d_rp)
             else:
                 self.d_rp = e.to_device(rp, np.int64)
                 self.d_cl = e.to_device(cl if cl.size else np.zeros(1, np.int32), np.int32)
@@ -460,6 +470,7 @@ class PairwiseShard:
                 assert len(cr) == rows, (len(cr), rows)
                 self.d_j = [e.to_device(cr, np.int32), e.to_device(l, np.int32), e.to_device(r, np.int32), e.to_device(st, np.int8)]
                 self.d_row_of, self.d_rp = e.empty(rows, np.int32), e.empty(rows + 1, np.int64)
+                _size_range_lists(e, self.d_j, self.d_row_of, self.d_rp)
             else:
                 self.d_rp = e.to_device(rp, np.int64)
                 self.d_cl = e.to_device(cl if cl.size else np.zeros(1, np.int32), np.int32)
