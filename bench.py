@@ -33,13 +33,24 @@ ranks, the 128-byte RCCL id); the collectives are the library's own RCCL calls (
 The timed region is bracketed by barrier + device sync on both sides; rank 0 prints the
 max-over-ranks time.  "roofline" is for the dominant kernel, timed with HIP events on the
 library's stream inside the timed region (profiling mode 2 records only that kernel).
-"cpu_baseline" times the oracle's loop-for-loop restatement of the reference on a bounded
-sample, on rank 0 at N=1 only; it is a reported baseline, never the thing measured above.
+The big tables (the headline's included) are one seeded host block of 200 000 rows repeated down
+the device matrix, so that generation stays bounded.
 
-At N=1 the line also carries "also": the same measurement (value, roofline, cpu_baseline, verify) for
-BASELINE configs 2 (quant 1M x 100), 3, 4 (one GPU's shard) and 5 (one GPU's shard), a few steps each
-(--no-also skips them).  The big tables (the headline's included) are one seeded host block of 200 000 rows
-repeated down the device matrix, so that generation stays bounded.
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.
+Everything else the benchmark measures or checks runs with --full only (its "verify", "cpu_baseline",
+"allgather", "ps_allgather", "also" and the roofline figures that take launches of their own are null or
+absent without it):
+  verify        the last step's outputs against the oracle on a row sample; a failure makes the run exit 3
+                (--no-verify skips it)
+  cpu_baseline  the oracle's loop-for-loop restatement of the reference on a bounded sample, on rank 0 at
+                N=1 only, plus the same restatement over the host cores; a reported baseline, never the thing
+                measured above (--no-cpu-baseline skips it)
+  roofline      pcie (host <-> device rates of the workload's tables), copy_same_bytes_ms (a device copy of
+                the PS kernel's bytes), valu_f64 lane-step counts (one extra Fisher launch)
+  allgather, ps_allgather, config.collectives (N>1): the collectives timed after the loop
+  also          at N=1, quant at its default size: the same measurement (value, roofline, cpu_baseline,
+                verify) for BASELINE configs 2 (quant 1M x 100), 3, 4 and 5 (one GPU's shard and full size),
+                a few steps each (--no-also skips them)
 """
 import argparse
 import json
@@ -76,10 +87,13 @@ def parse_args():
     # (long names only: under torch.distributed.run a short "--n" is swallowed by the launcher's parser)
     ap.add_argument("--junctions", dest="n", type=int, default=0, help="junctions per GPU (default: the BASELINE config)")
     ap.add_argument("--samples", dest="s", type=int, default=0, help="samples (default: the BASELINE config)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also verify, time the CPU baselines, the extra roofline figures, the collectives and the "
+                         "configurations under 'also' (a plain run does the set-up, the steps and the line only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-sample", type=int, default=0, help="junctions in the CPU-baseline sample")
-    ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the extra configurations reported under 'also'")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the verification")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the extra configurations reported under 'also'")
     ap.add_argument("--strong", action="store_true",
                     help="N>1, quant: keep the TOTAL work fixed (the N = 1 dataset cut into N row ranges) instead of the "
                          "default: one dataset of N x the per-GPU size (per-GPU work fixed)")
@@ -644,7 +658,7 @@ class ShardedPairwiseWorkload:
                             f"all-to-all back",
                 "junctions_total": self.n_total, "rows_per_rank": [q["own_hi"] - q["own_lo"] for q in self.plan],
                 "samples": self.s, "collective": self.comm_note or "RCCL all-to-all (grouped send/recv), twice per step",
-                "collectives": self.shard.timed_collectives() if self.comm_note is None else None}
+                "collectives": self.shard.timed_collectives() if self.comm_note is None and self.full else None}
 
     def verify(self):
         """raw Fisher p-values of a few of the rank's rows against the oracle (the corrected matrix needs every rank's rows)"""
@@ -873,9 +887,11 @@ def dump_outputs(out_dir, outputs):
     return written
 
 
-def measure(ctx, wl, dist, steps, warmup, gpus, verify=True, dump_dir=None):
+def measure(ctx, wl, dist, steps, warmup, gpus, full=False, verify=False, dump_dir=None):
     """warmup + timed steps of one workload -> (elapsed s [max over ranks], roofline dict, verify dict, dump dict).
-    dump_dir: the last step's outputs are written there (dump_outputs) before anything else touches them."""
+    dump_dir: the last step's outputs are written there (dump_outputs) before anything else touches them.
+    full: also the roofline figures that take launches or copies of their own (after the timed steps and the dump);
+    verify: check the outputs against the oracle (None without it)."""
     for _ in range(warmup):
         wl.step()
     ctx.sync()
@@ -911,6 +927,8 @@ def measure(ctx, wl, dist, steps, warmup, gpus, verify=True, dump_dir=None):
         vf = {"peak": VALU_WAVE_INSTS_SPEC, "unit": "wave64 VALU instructions/s (all VALU, f64 and not)",
               "peak_assumes": "1024 SIMDs x 2.4 GHz / 4 cycles per wave64 instruction"}
         try:
+            if not full:
+                raise RuntimeError("lane-step counts are taken with --full only")
             if not all(hasattr(wl, a) for a in ("d_counts", "d_excl", "d_p")):
                 raise AttributeError("lane-step counts are taken on the unsharded workload (N = 1)")
             ctx.set_param("fisher.count_steps", 1)
@@ -940,7 +958,7 @@ def measure(ctx, wl, dist, steps, warmup, gpus, verify=True, dump_dir=None):
     if verify:
         ok, checked = wl.verify()
         v = {"ok": ok, "checked": checked}
-    if wl.key in ("quant", "e2e") and launches and hasattr(wl, "d_counts") and hasattr(wl, "d_ps") and hasattr(wl, "sample_counts"):
+    if full and wl.key in ("quant", "e2e") and launches and hasattr(wl, "d_counts") and hasattr(wl, "d_ps") and hasattr(wl, "sample_counts"):
         # host <-> device rates of this workload's tables (pageable numpy buffers, as the host entry points
         # of the C ABI receive them), measured apart from the timed region and never part of `value`
         try:
@@ -956,7 +974,7 @@ def measure(ctx, wl, dist, steps, warmup, gpus, verify=True, dump_dir=None):
                                         "reported beside the device-resident figures, never inside them"}
         except Exception as e:                       # noqa: BLE001
             roofline["pcie"] = {"error": str(e)[:120]}
-    if wl.key == "quant" and launches and hasattr(wl, "d_counts") and hasattr(wl, "d_ps"):
+    if full and wl.key == "quant" and launches and hasattr(wl, "d_counts") and hasattr(wl, "d_ps"):
         # what a device-to-device copy of the same byte volume (count table -> PS table) takes on THIS box, measured after
         # the timed region and the verification (it overwrites the PS table): the bandwidth ceiling the PS kernel can be held against besides the spec figure
         try:
@@ -989,8 +1007,9 @@ ALSO = [
 
 def main():
     args = parse_args()
+    cpu_baselines = args.full and args.gpus == 1 and not args.no_cpu_baseline
     all_cores = None
-    if args.gpus == 1 and not args.no_cpu_baseline:
+    if cpu_baselines:
         all_cores = cpu_baseline_all_cores(args.workload)
     # stdout carries exactly ONE line (the JSON): gloo / RCCL print banners on fd 1, so fd 1 is
     # pointed at stderr for the whole run and the JSON goes to a saved copy of the real stdout
@@ -1012,19 +1031,19 @@ def main():
         wl = (ShardedPairwiseWorkload if args.workload == "pairwise" else ShardedE2EWorkload)(ctx, dist, args.gpus, args.n, args.s)
     else:
         wl = WORKLOADS[args.workload](ctx, dist.rank, args.n, args.s)
-    wl.key = args.workload
+    wl.key, wl.full = args.workload, args.full
 
-    elapsed, roofline, verify, dumped = measure(ctx, wl, dist, args.steps, args.warmup, args.gpus, not args.no_verify,
-                                                args.dump_outputs)
+    elapsed, roofline, verify, dumped = measure(ctx, wl, dist, args.steps, args.warmup, args.gpus, args.full,
+                                                args.full and not args.no_verify, args.dump_outputs)
     failed = bool(verify and not verify["ok"])
 
     ps_allgather = None
-    if sharded:
+    if args.full and sharded:
         ps_allgather = wl.ps_allgather(dist)      # reported, never hidden: the timed steps above contain no collective
         dist.barrier()
 
     allgather = None
-    if args.gpus > 1 and not sharded and not product_sharded:
+    if args.full and args.gpus > 1 and not sharded and not product_sharded:
         # data-plane collective: RCCL all-gather of a per-junction result table (8 B per junction); every rank
         # goes through the same control-plane calls whatever fails where
         err = None
@@ -1063,7 +1082,7 @@ def main():
         dist.barrier()
 
     cpu = None
-    if dist.rank == 0 and args.gpus == 1 and not args.no_cpu_baseline:
+    if dist.rank == 0 and cpu_baselines:
         cpu = wl.cpu_baseline(args.cpu_sample)
         cpu["all_cores"] = all_cores
         cpu["real_reference_over_port"] = reference_over_port(args.workload)
@@ -1088,7 +1107,7 @@ def main():
             line["dump_outputs"] = {"dir": args.dump_outputs, "rows": dumped}
 
     # ---- the other configurations, same measurement, a few steps each (1 GPU only: the driver's N=1 line)
-    if args.gpus == 1 and not args.no_also and args.workload == "quant" and not args.n and not args.s:
+    if args.full and args.gpus == 1 and not args.no_also and args.workload == "quant" and not args.n and not args.s:
         del wl
         also = {}
         for key, kind, n, s, block, steps, cpu_sample in ALSO:
@@ -1096,11 +1115,11 @@ def main():
             try:
                 w = WORKLOADS[kind](ctx, 0, n, s, block)
                 w.key = kind
-                el, rl, vf, _ = measure(ctx, w, dist, steps, 5, 1, not args.no_verify)      # (enough steps for the clocks to settle)
+                el, rl, vf, _ = measure(ctx, w, dist, steps, 5, 1, True, not args.no_verify)      # (enough steps for the clocks to settle)
                 rec = {"metric": w.metric, "value": w.units * steps / el, "unit": w.unit, "steps": steps, "warmup": 5,
                        "ms_per_step": el / steps * 1e3, "dtype": w.dtype, "config": w.describe(), "roofline": rl,
                        "verify": vf, "gen_seconds": round(w.gen_s, 1)}
-                if not args.no_cpu_baseline and cpu_sample:
+                if cpu_baselines and cpu_sample:
                     rec["cpu_baseline"] = w.cpu_baseline(cpu_sample)
                     rec["cpu_baseline"]["real_reference_over_port"] = reference_over_port(kind)
                 failed = failed or bool(vf and not vf["ok"])

@@ -11,7 +11,7 @@ ONLY=${2:-}
 OUT=gpurun_out/prof_$R
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-COMMON="--no-cpu-baseline --no-verify --no-also"
+COMMON="--full --no-cpu-baseline --no-verify --no-also"   # (--full: the extra roofline figures the summaries quote)
 args_of() {   # workload -> bench.py arguments (>= 20 profiled launches after >= 20 warm-ups for the quant lines)
   case $1 in
     quant)    echo "--workload quant --steps 25 --warmup 20" ;;
