@@ -302,14 +302,12 @@ extern "C" int sdice_bh(sdice_ctx* ctx, int64_t m, const double* p, double* q) {
     SD_ARG(m >= 0, "negative size");
     if (m == 0) return SDICE_OK;
     SD_ARG(p && q, "NULL pointer");
-    double *dp = nullptr, *dq = nullptr;
-    int rc = sdice_dmalloc(ctx, m * 8, (void**)&dp);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, m * 8, (void**)&dq);
-    if (rc == SDICE_OK) rc = sdice_h2d(ctx, dp, p, m * 8);
-    if (rc == SDICE_OK) rc = sdice_bh_dev(ctx, m, dp, dq);
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, q, dq, m * 8);
-    sdice_dfree(ctx, dp); sdice_dfree(ctx, dq);
-    return rc;
+    HostStaging st(ctx);
+    double *dp, *dq;
+    SD_TRY(st.upload(&dp, p, m));
+    SD_TRY(st.alloc(&dq, m));
+    SD_TRY(sdice_bh_dev(ctx, m, dp, dq));
+    return st.download(q, dq, m);
 }
 
 // BH down each column of a row-major [n, cols] device table, in place.
@@ -414,11 +412,9 @@ extern "C" int sdice_bh_columns(sdice_ctx* ctx, int64_t n, int64_t cols, double*
     SD_ARG(n >= 0 && cols >= 0, "negative size");
     if (n == 0 || cols == 0) return SDICE_OK;
     SD_ARG(p_inout, "NULL pointer");
-    double* d_rm = nullptr;
-    int rc = sdice_dmalloc(ctx, n * cols * 8, (void**)&d_rm);
-    if (rc == SDICE_OK) rc = sdice_h2d(ctx, d_rm, p_inout, n * cols * 8);
-    if (rc == SDICE_OK) rc = sdice_bh_columns_dev(ctx, n, cols, d_rm);
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, p_inout, d_rm, n * cols * 8);
-    sdice_dfree(ctx, d_rm);
-    return rc;
+    HostStaging st(ctx);
+    double* d_rm;
+    SD_TRY(st.upload(&d_rm, p_inout, n * cols));
+    SD_TRY(sdice_bh_columns_dev(ctx, n, cols, d_rm));
+    return st.download(p_inout, d_rm, n * cols);
 }

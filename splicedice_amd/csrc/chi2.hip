@@ -103,18 +103,15 @@ extern "C" int sdice_chi2_pairs(sdice_ctx* ctx, int64_t n, int32_t s, const int3
     SD_ARG(incl && excl && p, "NULL pointer");
     for (int64_t i = 0; i < n * s; ++i) SD_ARG(incl[i] >= 0 && excl[i] >= 0, "counts must be non-negative");
     const int64_t n_pairs = (int64_t)s * (s - 1) / 2;
-    int32_t* di = nullptr;
-    int64_t *de = nullptr, *db = nullptr;
-    double* dp = nullptr;
-    int rc = sdice_dmalloc(ctx, n * s * 4, (void**)&di);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, n * s * 8, (void**)&de);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, n * n_pairs * 8, (void**)&dp);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, 8, (void**)&db);
-    if (rc == SDICE_OK) rc = sdice_h2d(ctx, di, incl, n * s * 4);
-    if (rc == SDICE_OK) rc = sdice_h2d(ctx, de, excl, n * s * 8);
-    if (rc == SDICE_OK) rc = sdice_chi2_pairs_dev(ctx, n, s, di, de, dp, db);
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, p, dp, n * n_pairs * 8);
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, n_bad, db, 8);
-    sdice_dfree(ctx, di); sdice_dfree(ctx, de); sdice_dfree(ctx, dp); sdice_dfree(ctx, db);
-    return rc;
+    HostStaging st(ctx);
+    int32_t* di;
+    int64_t *de, *db;
+    double* dp;
+    SD_TRY(st.upload(&di, incl, n * s));
+    SD_TRY(st.upload(&de, excl, n * s));
+    SD_TRY(st.alloc(&dp, n * n_pairs));
+    SD_TRY(st.alloc(&db, 1));
+    SD_TRY(sdice_chi2_pairs_dev(ctx, n, s, di, de, dp, db));
+    SD_TRY(st.download(p, dp, n * n_pairs));
+    return st.download(n_bad, db, 1);
 }

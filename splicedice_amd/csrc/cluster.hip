@@ -520,28 +520,23 @@ extern "C" int sdice_cluster(sdice_ctx* ctx, int64_t n, const int32_t* chrom_ran
     SD_ARG(row_ptr, "row_ptr is NULL");
     if (n == 0) { row_ptr[0] = 0; if (nnz) *nnz = 0; ctx->nnz = 0; return SDICE_OK; }
     SD_ARG(chrom_rank && left && right && strand && row_of, "NULL pointer");
-    int32_t *dc = nullptr, *dl = nullptr, *dr = nullptr, *drow = nullptr;
-    int8_t* ds = nullptr;
-    int64_t* drp = nullptr;
-    int rc = sdice_dmalloc(ctx, n * 4, (void**)&dc);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, n * 4, (void**)&dl);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, n * 4, (void**)&dr);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, n, (void**)&ds);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, n * 4, (void**)&drow);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, (n + 1) * 8, (void**)&drp);
-    if (rc == SDICE_OK) rc = sdice_h2d(ctx, dc, chrom_rank, n * 4);
-    if (rc == SDICE_OK) rc = sdice_h2d(ctx, dl, left, n * 4);
-    if (rc == SDICE_OK) rc = sdice_h2d(ctx, dr, right, n * 4);
-    if (rc == SDICE_OK) rc = sdice_h2d(ctx, ds, strand, n);
+    HostStaging st(ctx);
+    int32_t *dc, *dl, *dr, *drow;
+    int8_t* ds;
+    int64_t* drp;
+    SD_TRY(st.upload(&dc, chrom_rank, n));
+    SD_TRY(st.upload(&dl, left, n));
+    SD_TRY(st.upload(&dr, right, n));
+    SD_TRY(st.upload(&ds, strand, n));
+    SD_TRY(st.alloc(&drow, n));
+    SD_TRY(st.alloc(&drp, n + 1));
     int64_t z = 0;
-    if (rc == SDICE_OK) rc = sdice_cluster_dev(ctx, n, dc, dl, dr, ds, drow, drp, &z);
-    if (rc == SDICE_OK) rc = sd_cluster_check_nnz(ctx, z, true);        // (the caller is about to hold the list on the host)
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, row_of, drow, n * 4);
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, row_ptr, drp, (n + 1) * 8);
-    if (rc == SDICE_OK && nnz) *nnz = z;
-    sdice_dfree(ctx, dc); sdice_dfree(ctx, dl); sdice_dfree(ctx, dr); sdice_dfree(ctx, ds);
-    sdice_dfree(ctx, drow); sdice_dfree(ctx, drp);
-    return rc;
+    SD_TRY(sdice_cluster_dev(ctx, n, dc, dl, dr, ds, drow, drp, &z));
+    SD_TRY(sd_cluster_check_nnz(ctx, z, true));        // (the caller is about to hold the list on the host)
+    SD_TRY(st.download(row_of, drow, n));
+    SD_TRY(st.download(row_ptr, drp, n + 1));
+    if (nnz) *nnz = z;
+    return SDICE_OK;
 }
 
 extern "C" int sdice_cluster_col(sdice_ctx* ctx, int32_t* col, int64_t capacity) {

@@ -128,6 +128,42 @@ int sd_prof_drain(sdice_ctx* ctx);
 
 static inline int64_t sd_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Device copies of a host entry point's arguments, from sdice_dmalloc (256 B minimum: a count of 0 still yields a valid
+// buffer).  Not from ctx->arena, which the _dev callees reset.  Freed when the object goes out of scope, after the context
+// stream has drained; the results of those calls are ignored so that the error of the failure that ended the call stays.
+class HostStaging {
+  public:
+    explicit HostStaging(sdice_ctx* ctx) : ctx_(ctx) {}
+    ~HostStaging();
+    HostStaging(const HostStaging&) = delete;
+    HostStaging& operator=(const HostStaging&) = delete;
+
+    template <class T> int alloc(T** d, int64_t count) {
+        void* p = nullptr;
+        const int rc = sdice_dmalloc(ctx_, count * (int64_t)sizeof(T), &p);
+        if (p) bufs_.push_back(p);
+        *d = static_cast<T*>(p);
+        return rc;
+    }
+    // alloc + synchronous copy in
+    template <class T> int upload(T** d, const T* h, int64_t count) {
+        SD_TRY(alloc(d, count));
+        return sdice_h2d(ctx_, *d, h, count * (int64_t)sizeof(T));
+    }
+    // synchronous copy out
+    template <class T> int download(T* h, const T* d, int64_t count) {
+        return sdice_d2h(ctx_, h, d, count * (int64_t)sizeof(T));
+    }
+
+  private:
+    sdice_ctx* ctx_;
+    std::vector<void*> bufs_;
+};
+
+// Argument check of a host CSR neighbour list (n_out rows into n_rows): row_ptr starts at 0 and never decreases, every
+// col entry is in [0, n_rows).  Errors are prefixed with `who`.
+int sd_check_csr(const char* who, int64_t n_out, int64_t n_rows, const int64_t* row_ptr, const int32_t* col);
+
 // status of an asynchronous sdice_cluster_dev (synchronises when one is pending)
 int sd_cluster_resolve(sdice_ctx* ctx);
 // SDICE_ERR_NOMEM (message naming nnz) when a neighbour list of nnz entries exceeds param cluster.max_nnz or, when that

@@ -205,6 +205,12 @@ extern "C" int sdice_d2h(sdice_ctx* ctx, void* dst_host, const void* src_dev, in
     return SDICE_OK;
 }
 
+HostStaging::~HostStaging() {
+    if (bufs_.empty()) return;
+    (void)hipStreamSynchronize(ctx_->stream);
+    for (void* p : bufs_) (void)hipFree(p);
+}
+
 extern "C" int sdice_dmemset(sdice_ctx* ctx, void* dptr, int value, int64_t bytes) {
     SD_ARG(ctx && bytes >= 0, "bad arguments");
     if (bytes == 0) return SDICE_OK;

@@ -486,18 +486,15 @@ extern "C" int sdice_fisher_pairs(sdice_ctx* ctx, int64_t n, int32_t s, const in
     SD_ARG(incl && excl && p, "NULL pointer");
     for (int64_t i = 0; i < n * s; ++i) SD_ARG(incl[i] >= 0 && excl[i] >= 0, "counts must be non-negative");
     const int64_t n_pairs = (int64_t)s * (s - 1) / 2;
-    int32_t* di = nullptr;
-    int64_t* de = nullptr;
-    double* dp = nullptr;
-    int rc = sdice_dmalloc(ctx, n * s * 4, (void**)&di);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, n * s * 8, (void**)&de);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, n * n_pairs * 8, (void**)&dp);
-    if (rc == SDICE_OK) rc = sdice_h2d(ctx, di, incl, n * s * 4);
-    if (rc == SDICE_OK) rc = sdice_h2d(ctx, de, excl, n * s * 8);
-    if (rc == SDICE_OK) rc = sdice_fisher_pairs_dev(ctx, n, s, di, de, dp);
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, p, dp, n * n_pairs * 8);
-    sdice_dfree(ctx, di); sdice_dfree(ctx, de); sdice_dfree(ctx, dp);
-    return rc;
+    HostStaging st(ctx);
+    int32_t* di;
+    int64_t* de;
+    double* dp;
+    SD_TRY(st.upload(&di, incl, n * s));
+    SD_TRY(st.upload(&de, excl, n * s));
+    SD_TRY(st.alloc(&dp, n * n_pairs));
+    SD_TRY(sdice_fisher_pairs_dev(ctx, n, s, di, de, dp));
+    return st.download(p, dp, n * n_pairs);
 }
 
 extern "C" int sdice_fisher_tables(sdice_ctx* ctx, int64_t m, const int64_t* abcd, double* p) {
@@ -509,17 +506,12 @@ extern "C" int sdice_fisher_tables(sdice_ctx* ctx, int64_t m, const int64_t* abc
     SD_HIP(hipSetDevice(ctx->device));
     LfTable t;
     SD_TRY(get_lf_table(ctx, &t));
-    int64_t* dt = nullptr;
-    double* dp = nullptr;
-    int rc = sdice_dmalloc(ctx, m * 32, (void**)&dt);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, m * 8, (void**)&dp);
-    if (rc == SDICE_OK) rc = sdice_h2d(ctx, dt, abcd, m * 32);
-    if (rc == SDICE_OK) {
-        hipLaunchKernelGGL(fisher_tables_kernel, dim3((unsigned)sd_ceil_div(m, 256)), dim3(256), 0, ctx->stream, dt, m, dp,
-                           t);
-        if (hipGetLastError() != hipSuccess) { sdice_set_error("fisher_tables_kernel launch failed"); rc = SDICE_ERR_HIP; }
-    }
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, p, dp, m * 8);
-    sdice_dfree(ctx, dt); sdice_dfree(ctx, dp);
-    return rc;
+    HostStaging st(ctx);
+    int64_t* dt;
+    double* dp;
+    SD_TRY(st.upload(&dt, abcd, 4 * m));
+    SD_TRY(st.alloc(&dp, m));
+    SD_LAUNCH(ctx, "fisher_tables_kernel", fisher_tables_kernel, dim3((unsigned)sd_ceil_div(m, 256)), dim3(256), 0, dt, m,
+              dp, t);
+    return st.download(p, dp, m);
 }

@@ -883,6 +883,20 @@ extern "C" int sdice_ps_dev(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t*
     return launch_ps<1>(ctx, a, threads, lds_bytes, grid, d_excl != nullptr, d_ps != nullptr, q3, abl);
 }
 
+int sd_check_csr(const char* who, int64_t n_out, int64_t n_rows, const int64_t* row_ptr, const int32_t* col) {
+    const int64_t nnz = row_ptr[n_out];
+    const char* bad = nullptr;
+    if (row_ptr[0] != 0 || nnz < 0) bad = "row_ptr must start at 0 and be non-decreasing";
+    else if (nnz != 0 && !col) bad = "col is NULL";
+    for (int64_t i = 0; i < n_out && !bad; ++i)
+        if (row_ptr[i + 1] < row_ptr[i]) bad = "row_ptr must be non-decreasing";
+    for (int64_t k = 0; k < nnz && !bad; ++k)
+        if (col[k] < 0 || col[k] >= n_rows) bad = "col index out of range";
+    if (!bad) return SDICE_OK;
+    sdice_set_error("%s: %s", who, bad);
+    return SDICE_ERR_ARG;
+}
+
 extern "C" int sdice_ps(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* counts,
                         const int64_t* row_ptr, const int32_t* col, int64_t* excl, float* ps) {
     SD_ARG(ctx, "ctx is NULL");
@@ -890,51 +904,21 @@ extern "C" int sdice_ps(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* cou
     SD_ARG(excl || ps, "both outputs are NULL");
     if (n == 0 || s == 0) return SDICE_OK;
     SD_ARG(counts && row_ptr, "NULL input");
-    const int64_t nnz = row_ptr[n];
-    SD_ARG(row_ptr[0] == 0 && nnz >= 0, "row_ptr must start at 0 and be non-decreasing");
-    SD_ARG(nnz == 0 || col, "col is NULL");
-    for (int64_t i = 0; i < n; ++i) SD_ARG(row_ptr[i + 1] >= row_ptr[i], "row_ptr must be non-decreasing");
-    for (int64_t k = 0; k < nnz; ++k) SD_ARG(col[k] >= 0 && col[k] < n, "col index out of range");
-    SD_HIP(hipSetDevice(ctx->device));
-    const size_t cells = (size_t)n * (size_t)s;
-    int32_t *d_counts = nullptr, *d_col = nullptr;
-    int64_t *d_rp = nullptr, *d_excl = nullptr;
+    SD_TRY(sd_check_csr(__func__, n, n, row_ptr, col));
+    const int64_t cells = n * s;
+    HostStaging st(ctx);
+    int32_t *d_counts, *d_col;
+    int64_t *d_rp, *d_excl = nullptr;
     float* d_ps = nullptr;
-    int rc = SDICE_OK;
-    auto cleanup = [&]() {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (d_counts) (void)hipFree(d_counts);
-        if (d_col) (void)hipFree(d_col);
-        if (d_rp) (void)hipFree(d_rp);
-        if (d_excl) (void)hipFree(d_excl);
-        if (d_ps) (void)hipFree(d_ps);
-    };
-#define SD_STEP(expr)                                                    \
-    do {                                                                 \
-        hipError_t _e = (expr);                                          \
-        if (_e != hipSuccess) {                                          \
-            sdice_set_error("sdice_ps: %s -> %s", #expr, hipGetErrorString(_e)); \
-            cleanup();                                                   \
-            return SDICE_ERR_HIP;                                        \
-        }                                                                \
-    } while (0)
-    SD_STEP(hipMalloc((void**)&d_counts, cells * 4));
-    SD_STEP(hipMalloc((void**)&d_rp, (size_t)(n + 1) * 8));
-    SD_STEP(hipMalloc((void**)&d_col, nnz > 0 ? (size_t)nnz * 4 : 256));
-    if (excl) SD_STEP(hipMalloc((void**)&d_excl, cells * 8));
-    if (ps) SD_STEP(hipMalloc((void**)&d_ps, cells * 4));
-    SD_STEP(hipMemcpyAsync(d_counts, counts, cells * 4, hipMemcpyHostToDevice, ctx->stream));
-    SD_STEP(hipMemcpyAsync(d_rp, row_ptr, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (nnz > 0) SD_STEP(hipMemcpyAsync(d_col, col, (size_t)nnz * 4, hipMemcpyHostToDevice, ctx->stream));
-    rc = sdice_ps_dev(ctx, n, s, d_counts, d_rp, d_col, d_excl, d_ps);
-    if (rc == SDICE_OK) {
-        if (excl) SD_STEP(hipMemcpyAsync(excl, d_excl, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (ps) SD_STEP(hipMemcpyAsync(ps, d_ps, cells * 4, hipMemcpyDeviceToHost, ctx->stream));
-        SD_STEP(hipStreamSynchronize(ctx->stream));
-    }
-#undef SD_STEP
-    cleanup();
-    return rc;
+    SD_TRY(st.upload(&d_counts, counts, cells));
+    SD_TRY(st.upload(&d_rp, row_ptr, n + 1));
+    SD_TRY(st.upload(&d_col, col, row_ptr[n]));          // (nnz == 0: a valid empty buffer, never NULL)
+    if (excl) SD_TRY(st.alloc(&d_excl, cells));
+    if (ps) SD_TRY(st.alloc(&d_ps, cells));
+    SD_TRY(sdice_ps_dev(ctx, n, s, d_counts, d_rp, d_col, d_excl, d_ps));
+    if (excl) SD_TRY(st.download(excl, d_excl, cells));
+    if (ps) SD_TRY(st.download(ps, d_ps, cells));
+    return SDICE_OK;
 }
 
 extern "C" int sdice_quantize3_dev(sdice_ctx* ctx, int64_t n_elems, float* d_ps_inout) {
@@ -951,13 +935,11 @@ extern "C" int sdice_quantize3(sdice_ctx* ctx, int64_t n_elems, float* ps_inout)
     SD_ARG(ctx && n_elems >= 0, "bad arguments");
     if (n_elems == 0) return SDICE_OK;
     SD_ARG(ps_inout, "NULL pointer");
-    float* d = nullptr;
-    SD_TRY(sdice_dmalloc(ctx, n_elems * 4, (void**)&d));
-    int rc = sdice_h2d(ctx, d, ps_inout, n_elems * 4);
-    if (rc == SDICE_OK) rc = sdice_quantize3_dev(ctx, n_elems, d);
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, ps_inout, d, n_elems * 4);
-    sdice_dfree(ctx, d);
-    return rc;
+    HostStaging st(ctx);
+    float* d;
+    SD_TRY(st.upload(&d, ps_inout, n_elems));
+    SD_TRY(sdice_quantize3_dev(ctx, n_elems, d));
+    return st.download(ps_inout, d, n_elems);
 }
 
 extern "C" int sdice_mark_low_dev(sdice_ctx* ctx, int64_t n_elems, float* d_ps, const int64_t* d_low_idx,
@@ -977,15 +959,11 @@ extern "C" int sdice_mark_low(sdice_ctx* ctx, int64_t n_elems, float* ps, const 
     if (n_low == 0) return SDICE_OK;
     SD_ARG(ps && low_idx, "NULL pointer");
     for (int64_t i = 0; i < n_low; ++i) SD_ARG(low_idx[i] >= 0 && low_idx[i] < n_elems, "low index out of range");
-    float* d = nullptr;
-    int64_t* di = nullptr;
-    SD_TRY(sdice_dmalloc(ctx, n_elems * 4, (void**)&d));
-    int rc = sdice_dmalloc(ctx, n_low * 8, (void**)&di);
-    if (rc == SDICE_OK) rc = sdice_h2d(ctx, d, ps, n_elems * 4);
-    if (rc == SDICE_OK) rc = sdice_h2d(ctx, di, low_idx, n_low * 8);
-    if (rc == SDICE_OK) rc = sdice_mark_low_dev(ctx, n_elems, d, di, n_low);
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, ps, d, n_elems * 4);
-    sdice_dfree(ctx, d);
-    sdice_dfree(ctx, di);
-    return rc;
+    HostStaging st(ctx);
+    float* d;
+    int64_t* di;
+    SD_TRY(st.upload(&d, ps, n_elems));
+    SD_TRY(st.upload(&di, low_idx, n_low));
+    SD_TRY(sdice_mark_low_dev(ctx, n_elems, d, di, n_low));
+    return st.download(ps, d, n_elems);
 }

@@ -84,48 +84,17 @@ static int ps_f64_host(sdice_ctx* ctx, bool excl, int64_t n_out, int64_t n_rows,
     SD_ARG(n_out >= 0 && n_rows >= n_out && s >= 0, "need 0 <= n_out <= n_rows, s >= 0");
     if (n_out == 0 || s == 0) return SDICE_OK;
     SD_ARG(counts && row_ptr && ps, "NULL pointer");
-    const int64_t nnz = row_ptr[n_out];
-    SD_ARG(row_ptr[0] == 0 && nnz >= 0, "row_ptr must start at 0 and be non-decreasing");
-    SD_ARG(nnz == 0 || col, "col is NULL");
-    for (int64_t i = 0; i < n_out; ++i) SD_ARG(row_ptr[i + 1] >= row_ptr[i], "row_ptr must be non-decreasing");
-    for (int64_t k = 0; k < nnz; ++k) SD_ARG(col[k] >= 0 && col[k] < n_rows, "col index out of range");
-    SD_HIP(hipSetDevice(ctx->device));
-    const size_t in_bytes = (size_t)n_rows * (size_t)s * 8, out_bytes = (size_t)n_out * (size_t)s * 8;
-    double *d_counts = nullptr, *d_ps = nullptr;
-    int64_t* d_rp = nullptr;
-    int32_t* d_col = nullptr;
-    int rc = SDICE_OK;
-    auto cleanup = [&]() {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (d_counts) (void)hipFree(d_counts);
-        if (d_ps) (void)hipFree(d_ps);
-        if (d_rp) (void)hipFree(d_rp);
-        if (d_col) (void)hipFree(d_col);
-    };
-#define SD_STEP(expr)                                                        \
-    do {                                                                     \
-        hipError_t _e = (expr);                                              \
-        if (_e != hipSuccess) {                                              \
-            sdice_set_error("sdice_ps_f64: %s -> %s", #expr, hipGetErrorString(_e)); \
-            cleanup();                                                       \
-            return SDICE_ERR_HIP;                                            \
-        }                                                                    \
-    } while (0)
-    SD_STEP(hipMalloc((void**)&d_counts, in_bytes));
-    SD_STEP(hipMalloc((void**)&d_ps, out_bytes));
-    SD_STEP(hipMalloc((void**)&d_rp, (size_t)(n_out + 1) * 8));
-    SD_STEP(hipMalloc((void**)&d_col, nnz > 0 ? (size_t)nnz * 4 : 256));
-    SD_STEP(hipMemcpyAsync(d_counts, counts, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    SD_STEP(hipMemcpyAsync(d_rp, row_ptr, (size_t)(n_out + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (nnz > 0) SD_STEP(hipMemcpyAsync(d_col, col, (size_t)nnz * 4, hipMemcpyHostToDevice, ctx->stream));
-    rc = ps_f64_dev(ctx, excl, n_out, n_rows, s, d_counts, d_rp, d_col, d_ps);
-    if (rc == SDICE_OK) {
-        SD_STEP(hipMemcpyAsync(ps, d_ps, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-        SD_STEP(hipStreamSynchronize(ctx->stream));
-    }
-#undef SD_STEP
-    cleanup();
-    return rc;
+    SD_TRY(sd_check_csr(__func__, n_out, n_rows, row_ptr, col));
+    HostStaging st(ctx);
+    double *d_counts, *d_ps;
+    int64_t* d_rp;
+    int32_t* d_col;
+    SD_TRY(st.upload(&d_counts, counts, n_rows * s));
+    SD_TRY(st.alloc(&d_ps, n_out * s));
+    SD_TRY(st.upload(&d_rp, row_ptr, n_out + 1));
+    SD_TRY(st.upload(&d_col, col, row_ptr[n_out]));
+    SD_TRY(ps_f64_dev(ctx, excl, n_out, n_rows, s, d_counts, d_rp, d_col, d_ps));
+    return st.download(ps, d_ps, n_out * s);
 }
 
 extern "C" int sdice_ps_f64(sdice_ctx* ctx, int64_t n_out, int64_t n_rows, int32_t s, const double* counts,

@@ -1478,33 +1478,26 @@ extern "C" int sdice_ranksum(sdice_ctx* ctx, int64_t n, int32_t s, const float* 
     SD_ARG(tested && p && med1 && med2 && mean1 && mean2 && delta, "NULL output");
     for (int i = 0; i < n1; ++i) SD_ARG(g1[i] >= 0 && g1[i] < s, "g1 index out of range");
     for (int i = 0; i < n2; ++i) SD_ARG(g2[i] >= 0 && g2[i] < s, "g2 index out of range");
-    float* d_ps = nullptr;
-    int32_t *dg1 = nullptr, *dg2 = nullptr;
-    uint8_t* dt = nullptr;
-    double *dp = nullptr, *dz = nullptr;
-    float* df = nullptr;
-    int rc = sdice_dmalloc(ctx, n * s * 4, (void**)&d_ps);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, (int64_t)n1 * 4, (void**)&dg1);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, (int64_t)n2 * 4, (void**)&dg2);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, n, (void**)&dt);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, n * 8, (void**)&dp);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, n * 8, (void**)&dz);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, n * 4 * 5, (void**)&df);
-    if (rc == SDICE_OK) rc = sdice_h2d(ctx, d_ps, ps, n * s * 4);
-    if (rc == SDICE_OK && n1) rc = sdice_h2d(ctx, dg1, g1, (int64_t)n1 * 4);
-    if (rc == SDICE_OK && n2) rc = sdice_h2d(ctx, dg2, g2, (int64_t)n2 * 4);
-    if (rc == SDICE_OK)
-        rc = sdice_ranksum_dev(ctx, n, s, d_ps, dg1, n1, dg2, n2, dt, dp, dz, df, df + n, df + 2 * n, df + 3 * n,
-                               df + 4 * n);
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, tested, dt, n);
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, p, dp, n * 8);
-    if (rc == SDICE_OK && z) rc = sdice_d2h(ctx, z, dz, n * 8);
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, med1, df, n * 4);
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, med2, df + n, n * 4);
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, mean1, df + 2 * n, n * 4);
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, mean2, df + 3 * n, n * 4);
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, delta, df + 4 * n, n * 4);
-    sdice_dfree(ctx, d_ps); sdice_dfree(ctx, dg1); sdice_dfree(ctx, dg2); sdice_dfree(ctx, dt);
-    sdice_dfree(ctx, dp); sdice_dfree(ctx, dz); sdice_dfree(ctx, df);
-    return rc;
+    HostStaging st(ctx);
+    float *d_ps, *df;
+    int32_t *dg1, *dg2;
+    uint8_t* dt;
+    double *dp, *dz;
+    SD_TRY(st.upload(&d_ps, ps, n * s));
+    SD_TRY(st.upload(&dg1, g1, n1));
+    SD_TRY(st.upload(&dg2, g2, n2));
+    SD_TRY(st.alloc(&dt, n));
+    SD_TRY(st.alloc(&dp, n));
+    SD_TRY(st.alloc(&dz, n));
+    SD_TRY(st.alloc(&df, n * 5));      // med1, med2, mean1, mean2, delta
+    SD_TRY(sdice_ranksum_dev(ctx, n, s, d_ps, dg1, n1, dg2, n2, dt, dp, dz, df, df + n, df + 2 * n, df + 3 * n,
+                             df + 4 * n));
+    SD_TRY(st.download(tested, dt, n));
+    SD_TRY(st.download(p, dp, n));
+    if (z) SD_TRY(st.download(z, dz, n));
+    SD_TRY(st.download(med1, df, n));
+    SD_TRY(st.download(med2, df + n, n));
+    SD_TRY(st.download(mean1, df + 2 * n, n));
+    SD_TRY(st.download(mean2, df + 3 * n, n));
+    return st.download(delta, df + 4 * n, n);
 }

@@ -174,20 +174,16 @@ extern "C" int sdice_rowstats(sdice_ctx* ctx, int64_t n, int32_t s, const void* 
     SD_ARG(data && idx && mean && std_ && n_nan, "NULL pointer");
     for (int i = 0; i < k; ++i) SD_ARG(idx[i] >= 0 && idx[i] < s, "column index out of range");
     const int64_t w = dtype == 0 ? 4 : 8;
-    void *d_data = nullptr, *d_mean = nullptr, *d_std = nullptr;
-    int32_t *d_idx = nullptr, *d_nan = nullptr;
-    int rc = sdice_dmalloc(ctx, n * s * w, &d_data);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, (int64_t)(k > 0 ? k : 1) * 4, (void**)&d_idx);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, n * w, &d_mean);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, n * w, &d_std);
-    if (rc == SDICE_OK) rc = sdice_dmalloc(ctx, n * 4, (void**)&d_nan);
-    if (rc == SDICE_OK) rc = sdice_h2d(ctx, d_data, data, n * s * w);
-    if (rc == SDICE_OK && k) rc = sdice_h2d(ctx, d_idx, idx, (int64_t)k * 4);
-    if (rc == SDICE_OK) rc = sdice_rowstats_dev(ctx, n, s, d_data, dtype, d_idx, k, d_mean, d_std, d_nan);
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, mean, d_mean, n * w);
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, std_, d_std, n * w);
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, n_nan, d_nan, n * 4);
-    sdice_dfree(ctx, d_data); sdice_dfree(ctx, d_idx); sdice_dfree(ctx, d_mean); sdice_dfree(ctx, d_std);
-    sdice_dfree(ctx, d_nan);
-    return rc;
+    HostStaging st(ctx);
+    char *d_data, *d_mean, *d_std;
+    int32_t *d_idx, *d_nan;
+    SD_TRY(st.upload(&d_data, static_cast<const char*>(data), n * s * w));
+    SD_TRY(st.upload(&d_idx, idx, k));      // (k == 0 still stages a valid buffer; the _dev call rejects it)
+    SD_TRY(st.alloc(&d_mean, n * w));
+    SD_TRY(st.alloc(&d_std, n * w));
+    SD_TRY(st.alloc(&d_nan, n));
+    SD_TRY(sdice_rowstats_dev(ctx, n, s, d_data, dtype, d_idx, k, d_mean, d_std, d_nan));
+    SD_TRY(st.download(static_cast<char*>(mean), d_mean, n * w));
+    SD_TRY(st.download(static_cast<char*>(std_), d_std, n * w));
+    return st.download(n_nan, d_nan, n);
 }

@@ -70,19 +70,15 @@ extern "C" int sdice_similarity(sdice_ctx* ctx, int64_t n, int32_t s, const doub
     if (s == 0) return SDICE_OK;
     SD_ARG(scores && counts, "NULL output");
     SD_ARG(n == 0 || (ps && mid && sign), "NULL input");
-    double *d_ps = nullptr, *d_mid = nullptr;
-    int8_t* d_sign = nullptr;
-    int64_t* d_out = nullptr;
-    int rc = sdice_dmalloc(ctx, (int64_t)s * 16, (void**)&d_out);
-    if (rc == SDICE_OK && n) rc = sdice_dmalloc(ctx, n * s * 8, (void**)&d_ps);
-    if (rc == SDICE_OK && n) rc = sdice_dmalloc(ctx, n * 8, (void**)&d_mid);
-    if (rc == SDICE_OK && n) rc = sdice_dmalloc(ctx, n, (void**)&d_sign);
-    if (rc == SDICE_OK && n) rc = sdice_h2d(ctx, d_ps, ps, n * s * 8);
-    if (rc == SDICE_OK && n) rc = sdice_h2d(ctx, d_mid, mid, n * 8);
-    if (rc == SDICE_OK && n) rc = sdice_h2d(ctx, d_sign, sign, n);
-    if (rc == SDICE_OK) rc = sdice_similarity_dev(ctx, n, s, d_ps, d_mid, d_sign, d_out, d_out + s);
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, scores, d_out, (int64_t)s * 8);
-    if (rc == SDICE_OK) rc = sdice_d2h(ctx, counts, d_out + s, (int64_t)s * 8);
-    sdice_dfree(ctx, d_ps); sdice_dfree(ctx, d_mid); sdice_dfree(ctx, d_sign); sdice_dfree(ctx, d_out);
-    return rc;
+    HostStaging st(ctx);
+    double *d_ps, *d_mid;
+    int8_t* d_sign;
+    int64_t* d_out;                               // scores, then counts
+    SD_TRY(st.alloc(&d_out, (int64_t)s * 2));
+    SD_TRY(st.upload(&d_ps, ps, n * s));          // (n == 0: nothing is copied, so NULL inputs pass)
+    SD_TRY(st.upload(&d_mid, mid, n));
+    SD_TRY(st.upload(&d_sign, sign, n));
+    SD_TRY(sdice_similarity_dev(ctx, n, s, d_ps, d_mid, d_sign, d_out, d_out + s));
+    SD_TRY(st.download(scores, d_out, s));
+    return st.download(counts, d_out + s, s);
 }
