@@ -157,16 +157,13 @@ def compare_sharded(matrix, g1_idx, g2_idx, ctx, L):
     from . import distributed
     n = matrix.shape[0]
     lo, hi = L.row_block(n)
-    blocks = [L.row_block(n, r) for r in range(L.world)]
-    maxk = max(max(b - a for a, b in blocks), 1)
+    rows_of = [b - a for a, b in (L.row_block(n, r) for r in range(L.world))]
+    maxk = distributed.longest(rows_of)
     res = ctx.ranksum(np.ascontiguousarray(matrix[lo:hi]), g1_idx, g2_idx)
-    stats = {k: np.zeros(maxk, dt) for k, dt in zip(distributed.STAT_NAMES, distributed._STAT_DTYPES)}
-    for k in distributed.STAT_NAMES:
-        stats[k][: hi - lo] = res[k]
+    stats = {k: distributed.pad_rows(np.asarray(res[k], dt), maxk) for k, dt in zip(distributed.STAT_NAMES, distributed.STAT_DTYPES)}
     gathered = L.comm(ctx).allgather(distributed.pack_stats_host(stats, maxk))
     host = distributed.unpack_stats_host(gathered, maxk, L.world)
-    full = {k: np.concatenate([host[k][r * maxk: r * maxk + b - a] for r, (a, b) in enumerate(blocks)])
-            for k in ("tested", "p", "med1", "med2", "mean1", "mean2", "delta")}
+    full = {k: distributed.drop_padding(host[k], rows_of, maxk) for k in ("tested", "p", "med1", "med2", "mean1", "mean2", "delta")}
     keep = np.flatnonzero(full["tested"])
     out = {k: full[k][keep] for k in ("p", "med1", "med2", "mean1", "mean2", "delta")}
     out["corrected"] = ctx.bh(out["p"]) if (keep.size and L.root) else np.zeros(keep.size)

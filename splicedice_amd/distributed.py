@@ -22,19 +22,64 @@ BH on complete columns, all-to-all back.  `--multiple_test_correction all` (one 
 n x pairs matrix, pairwise_fisher.py:182-186) all-gathers the raw matrix (config 4: 32 GB, 26 ms of
 xGMI time) and every rank ranks it redundantly, keeping its own rows.
 
-Communicators implement rank, world, allgather(x), alltoall(x) for host arrays (GlooComm: the CPU
-tests of the N>1 logic; SingleComm) or device arrays (RcclComm; SingleComm).
+Communicators implement rank, world, allgather(x), alltoall(x), allsum(v) for host arrays (GlooComm: the CPU
+tests of the N>1 logic; SingleComm) or device arrays (RcclComm; SingleComm); _allgather / _alltoall hand
+the receive buffer to one that also has allgather_into / alltoall_into.
+
+_RowRange is a rank's rows on the device (plan geometry, counts, CSR or coordinates, every array it
+allocated); CompareShard and PairwiseShard add their buffers and step(); both *_sharded entry points start
+in _shard_inputs; pad_rows / drop_padding pad to the longest shard and back.
 """
 import numpy as np
 
 from . import shard
 
 STAT_NAMES = ("tested", "p", "z", "med1", "med2", "mean1", "mean2", "delta")
-_STAT_DTYPES = (np.uint8, np.float64, np.float64, np.float32, np.float32, np.float32, np.float32, np.float32)
+STAT_DTYPES = (np.uint8, np.float64, np.float64, np.float32, np.float32, np.float32, np.float32, np.float32)
 
 
 def _is_dev(x):
     return hasattr(x, "ptr") and hasattr(x, "to_host")
+
+
+def _allgather(comm, send, recv):
+    """all-gather into `recv` when there is one and the communicator takes it; otherwise the communicator allocates"""
+    if recv is not None and hasattr(comm, "allgather_into"):
+        return comm.allgather_into(send, recv)
+    return comm.allgather(send)
+
+
+def _alltoall(comm, send, recv, in_place=False):
+    """all-to-all into `recv` when there is one and the communicator takes it; otherwise the communicator allocates
+    the result -- except `in_place` (recv is a slice of a buffer that is read as a whole later): a communicator
+    without alltoall_into then leaves the blocks where they are, and they are copied across on the device."""
+    if recv is not None and hasattr(comm, "alltoall_into"):
+        return comm.alltoall_into(send, recv)
+    if in_place:
+        send.ctx.copy2d_dev(recv.ptr, send.nbytes, send.ptr, send.nbytes, send.nbytes, 1)
+        return recv
+    return comm.alltoall(send)
+
+
+def rows_per_rank(plan):
+    return [p["own_hi"] - p["own_lo"] for p in plan]
+
+
+def longest(rows_of):
+    """rows of the longest shard: every rank pads to it (at least 1: no collective is empty)"""
+    return max(max(rows_of), 1)
+
+
+def pad_rows(a, m, fill=0):
+    """a's rows, then `fill` up to m rows"""
+    out = np.full((m,) + a.shape[1:], fill, dtype=a.dtype)
+    out[: a.shape[0]] = a
+    return out
+
+
+def drop_padding(a, rows_of, m):
+    """rank blocks of m rows each -> the first rows_of[r] rows of every block, in rank order"""
+    return np.concatenate([a[r * m: r * m + k] for r, k in enumerate(rows_of)])
 
 
 class SingleComm:
@@ -139,7 +184,7 @@ def stat_layout(m):
     RCCL all-gather ... to reassemble the output tables"): name -> (byte offset, dtype); every vector starts at a
     multiple of 16 bytes.  -> (offsets, block bytes)"""
     off, at = {}, 0
-    for name, dt in zip(STAT_NAMES, _STAT_DTYPES):
+    for name, dt in zip(STAT_NAMES, STAT_DTYPES):
         off[name] = (at, np.dtype(dt))
         at += (m * np.dtype(dt).itemsize + 15) // 16 * 16
     return off, at
@@ -171,6 +216,32 @@ def _own_slice(counts_ext, n, part):
     raise ValueError(f"expected the {ehi - elo} count rows [{elo}, {ehi}) of this rank's shard, got {counts_ext.shape[0]}")
 
 
+def _shard_inputs(engine, comm, counts_ext, row_ptr, col, plan, junctions_ext, dev):
+    """what quant_compare_sharded and pairwise_sharded start from -> (n, plan, part, ext, rp, cl): the plan (made here
+    from the CSR unless given), this rank's part of it, its count rows and its local CSR -- cut out of (row_ptr, col),
+    or clustered here from junctions_ext by a host engine (`dev`: the caller takes the device path, where the shard
+    object clusters the range itself and rp = cl = None).  A rank without own rows gets counts_ext[:0] and no CSR."""
+    if junctions_ext is not None:
+        if plan is None:
+            raise ValueError("junctions_ext needs the plan it was cut by (shard.shard_plan_junctions)")
+        n = plan[-1]["own_hi"]
+    else:
+        n = row_ptr.size - 1
+        plan = plan or shard.shard_plan(row_ptr, col, comm.world)
+    part = plan[comm.rank]
+    if part["own_hi"] == part["own_lo"]:
+        return n, plan, part, counts_ext[:0], None, None
+    ext = np.ascontiguousarray(_own_slice(counts_ext, n, part))
+    rp = cl = None
+    if junctions_ext is None:
+        rp, cl = shard.local_csr(row_ptr, col, part)
+    elif not dev:
+        row_of, rp, cl = engine.cluster(*junctions_ext)             # the range alone; rows arrive in row order
+        if not np.array_equal(row_of, np.arange(len(row_of))):
+            raise ValueError("junctions_ext must be in output row order")
+    return n, plan, part, ext, rp, cl
+
+
 def _bh_masked_host(engine, p, tested):
     """host twin of sdice_bh_masked_dev for engines without device entry points (the CPU test double)"""
     keep = np.flatnonzero(tested if tested is not None else p >= 0)
@@ -183,36 +254,80 @@ def _bh_masked_host(engine, p, tested):
 def shard_stats(engine, counts_ext, rp, cl, first, k, g1, g2, pad_to=None):
     """(host engines: the CPU test double)  PS -> '.3f' quantise -> rank-sum for rows [first, first + k) of one shard
     (with its halo rows) -> dict name -> array of length pad_to (default k), zero beyond k."""
-    pad_to = k if pad_to is None else pad_to
-    out = {name: np.zeros(pad_to, dt) for name, dt in zip(STAT_NAMES, _STAT_DTYPES)}
+    r = dict.fromkeys(STAT_NAMES, ())
     if k:
         ps = engine.quantize3(engine.ps(counts_ext, rp, cl))   # the _allPS.tsv text round trip (SURVEY 0.5)
         r = engine.ranksum(ps[first: first + k], g1, g2)
-        for name in STAT_NAMES:
-            out[name][:k] = r[name]
-    return out
+    return {name: pad_rows(np.asarray(r[name], dt), k if pad_to is None else pad_to) for name, dt in zip(STAT_NAMES, STAT_DTYPES)}
 
 
-def _csr_host(sh):
-    """(row_ptr, col, nnz) of the rows [ext_lo, ext_hi) of a shard object as the device holds them (after a step)"""
-    rp = sh.d_rp.to_host()
-    nnz = int(rp[-1])
-    if sh.d_j is not None:
-        nnz, _ = sh.e.cluster_status()               # (resolves the asynchronous clustering: deferred errors surface here)
-    cl = sh.d_cl.offset(0, (nnz,)).to_host() if nnz else np.zeros(0, np.int32)
-    return rp, cl, nnz
+class _RowRange:
+    """One rank's row range on the device: the plan geometry (own rows [lo, hi), held rows from elo, k own rows, maxk =
+    the longest shard), the count rows, and EITHER the local CSR OR the coordinates of the rows [ext_lo, ext_hi), which
+    lists() then clusters itself.  Every array is allocated through empty() / to_device(), and free() releases exactly
+    those."""
+
+    def __init__(self, engine, comm, n, s, plan):
+        self.e, self.comm, self.n, self.s, self.plan = engine, comm, n, s, plan
+        part = plan[comm.rank]
+        self.lo, self.hi, self.elo = part["own_lo"], part["own_hi"], part["ext_lo"]
+        self.k = self.hi - self.lo
+        self.rows_of = rows_per_rank(plan)
+        self.maxk = longest(self.rows_of)
+        self.owned = []
+        self.d_counts = self.d_rp = self.d_cl = self.d_row_of = self.d_j = None
+
+    def empty(self, shape, dtype):
+        self.owned.append(self.e.empty(shape, dtype))
+        return self.owned[-1]
+
+    def to_device(self, host, dtype):
+        self.owned.append(self.e.to_device(host, dtype))
+        return self.owned[-1]
+
+    def load_rows(self, counts_ext, rp, cl, junctions):
+        """counts_ext: rows [ext_lo, ext_hi); either (rp, cl) -- the local CSR -- or junctions = (chrom_rank, left,
+        right, strand) of those rows in row order"""
+        self.d_counts = self.to_device(np.ascontiguousarray(counts_ext), np.int32)
+        rows = self.d_counts.shape[0]
+        if junctions is None:
+            self.d_rp = self.to_device(rp, np.int64)
+            self.d_cl = self.to_device(cl if cl.size else np.zeros(1, np.int32), np.int32)
+            return
+        assert len(junctions[0]) == rows, (len(junctions[0]), rows)
+        self.d_j = [self.to_device(x, dt) for x, dt in zip(junctions, (np.int32, np.int32, np.int32, np.int8))]
+        self.d_row_of, self.d_rp = self.empty(rows, np.int32), self.empty(rows + 1, np.int64)
+        # cluster the range once synchronously.  lists() clusters it asynchronously, and an asynchronous sdice_cluster_dev
+        # only sizes the context's list buffer at 16 entries per junction: a denser range would fail at the next sync.
+        # The synchronous call grows the buffer to the range's list total (it never shrinks) and reports invalid or
+        # duplicate junctions here.  (A range that the fast path can only cluster synchronously -- a sort bucket
+        # overflow, e.g. more than 16 384 junctions sharing one (chrom, left) -- still fails in step(); that is not
+        # handled here.)
+        self.e.cluster_dev(*self.d_j, self.d_row_of, self.d_rp, sync=True)
+
+    def lists(self):
+        """the neighbour lists of this step: the uploaded ones, or the rank's own range clustered now, enqueued without
+        a host round trip (a view of the context's list buffer: not owned, never freed here)"""
+        if self.d_j is not None:
+            self.d_cl, _ = self.e.cluster_dev(*self.d_j, self.d_row_of, self.d_rp, sync=False)
+        return self.d_cl
+
+    def csr_host(self):
+        """(row_ptr, col, nnz) of the rows [ext_lo, ext_hi) as the device holds them (after a step)"""
+        rp = self.d_rp.to_host()
+        nnz = int(rp[-1])
+        if self.d_j is not None:
+            nnz, _ = self.e.cluster_status()            # (resolves the asynchronous clustering: deferred errors surface here)
+        cl = self.d_cl.offset(0, (nnz,)).to_host() if nnz else np.zeros(0, np.int32)
+        return rp, cl, nnz
+
+    def free(self):
+        for a in self.owned:
+            a.free()
+        self.owned = []
 
 
-def _size_range_lists(e, d_j, d_row_of, d_rp):
-    """cluster a shard's range once synchronously at load time.  step() clusters it asynchronously, and an asynchronous
-    sdice_cluster_dev only sizes the context's list buffer at 16 entries per junction: a denser range would fail at the
-    next sync.  The synchronous call grows the buffer to the range's list total (it never shrinks) and reports invalid or
-    duplicate junctions here.  (A range that the fast path can only cluster synchronously -- a sort bucket overflow, e.g.
-    more than 16 384 junctions sharing one (chrom, left) -- still fails in step(); that is not handled here.)"""
-    e.cluster_dev(*d_j, d_row_of, d_rp, sync=True)
-
-
-class CompareShard:
+class CompareShard(_RowRange):
     """One rank's part of quant -> compare_sample_sets, resident in HBM (device engines).
 
     load() uploads the rank's count rows and EITHER its local CSR (cut out of a replicated clustering by the caller)
@@ -225,49 +340,29 @@ class CompareShard:
     bench.py --workload e2e --gpus N times exactly this step."""
 
     def __init__(self, engine, comm, n, s, plan, g1, g2):
-        self.e, self.comm, self.n, self.s, self.plan = engine, comm, n, s, plan
-        part = plan[comm.rank]
-        self.lo, self.hi, self.elo = part["own_lo"], part["own_hi"], part["ext_lo"]
-        self.k = self.hi - self.lo
-        self.m = max(max(p["own_hi"] - p["own_lo"] for p in plan), 1)
-        self.off, self.block = stat_layout(self.m)
+        super().__init__(engine, comm, n, s, plan)
+        m, w = self.maxk, comm.world
+        self.off, self.block = stat_layout(m)
         from .engine import DeviceArray
-        self.packed = engine.empty(self.block, np.uint8).zero()
-        self.views = {name: DeviceArray(engine, (self.m,), dt, ptr=self.packed.ptr + at, owned=False)
+        self.packed = self.empty(self.block, np.uint8).zero()
+        self.views = {name: DeviceArray(engine, (m,), dt, ptr=self.packed.ptr + at, owned=False)
                       for name, (at, dt) in self.off.items()}
-        self.d_g1, self.d_g2 = engine.to_device(g1, np.int32), engine.to_device(g2, np.int32)
-        w = comm.world
-        self.d_p_all, self.d_t_all = engine.empty(w * self.m, np.float64), engine.empty(w * self.m, np.uint8)
-        self.d_q = engine.empty(w * self.m, np.float64)
-        self.recv = engine.empty(w * self.block, np.uint8) if w > 1 else None      # (allocated once: step() is malloc-free)
-        self.d_counts = self.d_rp = self.d_cl = self.d_ps = self.d_row_of = None
-        self.d_j = None
+        self.d_g1, self.d_g2 = self.to_device(g1, np.int32), self.to_device(g2, np.int32)
+        self.d_p_all, self.d_t_all = self.empty(w * m, np.float64), self.empty(w * m, np.uint8)
+        self.d_q = self.empty(w * m, np.float64)
+        self.recv_buf = self.empty(w * self.block, np.uint8) if w > 1 else None    # (allocated once: step() is malloc-free)
+        self.recv = self.recv_buf                    # what the last step gathered
+        self.d_ps = None
 
     def load(self, counts_ext, rp=None, cl=None, junctions=None):
-        """counts_ext: rows [ext_lo, ext_hi); either (rp, cl) -- the local CSR -- or junctions = (chrom_rank, left,
-        right, strand) of those rows in row order"""
-        e = self.e
         if self.k:
-            self.d_counts = e.to_device(np.ascontiguousarray(counts_ext), np.int32)
-            rows = self.d_counts.shape[0]
-            if junctions is not None:
-                cr, l, r, st = junctions
-                assert len(cr) == rows, (len(cr), rows)
-                self.d_j = [e.to_device(cr, np.int32), e.to_device(l, np.int32), e.to_device(r, np.int32), e.to_device(st, np.int8)]
-                self.d_row_of, self.d_rp = e.empty(rows, np.int32), e.empty(rows + 1, np.int64)
-                _size_range_lists(e, self.d_j, self.d_row_of, self.d_rp)
-            else:
-                self.d_rp = e.to_device(rp, np.int64)
-                self.d_cl = e.to_device(cl if cl.size else np.zeros(1, np.int32), np.int32)
-            self.d_ps = e.empty(self.d_counts.shape, np.float32)
+            self.load_rows(counts_ext, rp, cl, junctions)
+            self.d_ps = self.empty(self.d_counts.shape, np.float32)
 
     def step(self):
-        e, k, m, w = self.e, self.k, self.m, self.comm.world
+        e, k, m, w = self.e, self.k, self.maxk, self.comm.world
         if k:
-            d_cl = self.d_cl
-            if self.d_j is not None:                 # the rank's own range, enqueued without a host round trip
-                d_cl, _ = e.cluster_dev(*self.d_j, self.d_row_of, self.d_rp, sync=False)
-                self.d_cl = d_cl                     # (a view of the context's list buffer: not owned)
+            d_cl = self.lists()
             e.set_param("ps.quantize3", 1)          # the '.3f' round trip is fused into the PS store
             try:
                 e.ps_dev(self.d_counts, self.d_rp, d_cl, None, self.d_ps)
@@ -276,29 +371,21 @@ class CompareShard:
             first = self.lo - self.elo
             e.ranksum_dev(self.d_ps.offset(first * self.s, (k, self.s)), self.d_g1, self.d_g2,
                           {name: v.offset(0, (k,)) for name, v in self.views.items()})
-        if w > 1 and hasattr(self.comm, "allgather_into"):
-            self.comm.allgather_into(self.packed, self.recv)          # ONE collective: world x block bytes
-        else:
-            self.recv = self.comm.allgather(self.packed)
+        self.recv = _allgather(self.comm, self.packed, self.recv_buf)     # ONE collective: world x block bytes
         at_p, at_t = self.off["p"][0], self.off["tested"][0]
         e.copy2d_dev(self.d_p_all.ptr, m * 8, self.recv.ptr + at_p, self.block, m * 8, w)      # rank blocks -> one vector
         e.copy2d_dev(self.d_t_all.ptr, m, self.recv.ptr + at_t, self.block, m, w)
         e.bh_masked_dev(self.d_p_all, self.d_t_all, self.d_q)
 
-    def csr_host(self):
-        return _csr_host(self)
-
     def result(self):
-        host = unpack_stats_host(self.recv.to_host(), self.m, self.comm.world)
+        host = unpack_stats_host(self.recv.to_host(), self.maxk, self.comm.world)
         host["corrected"] = self.d_q.to_host()
         return host
 
     def free(self):
-        recv = self.recv if self.recv is not self.packed else None
-        for a in (self.d_counts, self.d_rp, self.d_cl, self.d_ps, self.d_row_of, self.d_g1, self.d_g2, self.packed, self.d_p_all,
-                  self.d_t_all, self.d_q, recv, *(self.d_j or ())):
-            if a is not None:
-                a.free()
+        if self.recv is not None and not any(self.recv is a for a in self.owned):
+            self.recv.free()                         # (a communicator without allgather_into allocated it)
+        super().free()
 
 
 def quant_compare_sharded(engine, comm, counts_ext, row_ptr, col, g1, g2, plan=None, junctions_ext=None):
@@ -313,26 +400,12 @@ def quant_compare_sharded(engine, comm, counts_ext, row_ptr, col, g1, g2, plan=N
     on every rank, plus plan.  `engine`: the HIP Context (device path) or a host double with
     ps / quantize3 / ranksum / bh (/ cluster).  The per-junction table crosses the ranks as ONE packed block in ONE all-gather.
     """
-    if junctions_ext is not None:
-        if plan is None:
-            raise ValueError("junctions_ext needs the plan it was cut by (shard.shard_plan_junctions)")
-        n = plan[-1]["own_hi"]
-    else:
-        n = row_ptr.size - 1
-        plan = plan or shard.shard_plan(row_ptr, col, comm.world)
-    part = plan[comm.rank]
+    dev = hasattr(engine, "ps_dev")
+    n, plan, part, ext, rp, cl = _shard_inputs(engine, comm, counts_ext, row_ptr, col, plan, junctions_ext, dev)
     lo, hi, elo = part["own_lo"], part["own_hi"], part["ext_lo"]
     k = hi - lo
-    max_rows = max(max(p["own_hi"] - p["own_lo"] for p in plan), 1)
-    ext = np.ascontiguousarray(_own_slice(counts_ext, n, part)) if k else counts_ext[:0]
-    dev = hasattr(engine, "ps_dev")
-    rp = cl = None
-    if k and junctions_ext is None:
-        rp, cl = shard.local_csr(row_ptr, col, part)
-    elif k and not dev:
-        row_of, rp, cl = engine.cluster(*junctions_ext)             # the range alone; rows arrive in row order
-        if not np.array_equal(row_of, np.arange(len(row_of))):
-            raise ValueError("junctions_ext must be in output row order")
+    rows_of = rows_per_rank(plan)
+    max_rows = longest(rows_of)
     if dev and comm.device:
         sh = CompareShard(engine, comm, n, ext.shape[1] if k else len(g1) + len(g2), plan, g1, g2)
         try:
@@ -349,11 +422,8 @@ def quant_compare_sharded(engine, comm, counts_ext, row_ptr, col, g1, g2, plan=N
         gathered = comm.allgather(pack_stats_host(stats, max_rows))             # ONE collective
         host = unpack_stats_host(gathered, max_rows, comm.world)
         host["corrected"] = _bh_masked_host(engine, host["p"], host["tested"])
-    out = {}
-    for name, a in host.items():                                                # drop the padding: rows in global order
-        out[name] = np.concatenate([a[r * max_rows: r * max_rows + plan[r]["own_hi"] - plan[r]["own_lo"]]
-                                    for r in range(comm.world)])
-        assert out[name].shape[0] == n
+    out = {name: drop_padding(a, rows_of, max_rows) for name, a in host.items()}     # rows in global order
+    assert all(a.shape[0] == n for a in out.values())
     out["plan"] = plan
     return out
 
@@ -397,8 +467,8 @@ def _pairwise_host(engine, comm, ext, rp, cl, a0, k, plan, n, pairs, correction,
         p = np.zeros((0, pairs), dtype=np.float64)
     if test == "chi2":
         _chi2_abort(comm, n_bad, n * pairs)
-    rows_of = [q["own_hi"] - q["own_lo"] for q in plan]
-    maxk = max(max(rows_of), 1)
+    rows_of = rows_per_rank(plan)
+    maxk = longest(rows_of)
     if correction == "pairwise" and pairs > 0:
         ranges = pair_column_ranges(pairs, comm.world)
         maxw = max(max(b - a for a, b in ranges), 1)
@@ -407,7 +477,7 @@ def _pairwise_host(engine, comm, ext, rp, cl, a0, k, plan, n, pairs, correction,
             send[q, :k, : b - a] = p[:, a:b]
         got = comm.alltoall(send)                             # rank r's rows of MY columns
         a, b = ranges[comm.rank]
-        mine = np.concatenate([got[r][: rows_of[r], : b - a] for r in range(comm.world)], axis=0)
+        mine = drop_padding(got.reshape(comm.world * maxk, maxw), rows_of, maxk)[:, : b - a]
         assert mine.shape == (n, b - a)
         if mine.size:
             mine = engine.bh_columns(mine)
@@ -419,15 +489,18 @@ def _pairwise_host(engine, comm, ext, rp, cl, a0, k, plan, n, pairs, correction,
         for q, (a, b) in enumerate(ranges):
             p[:, a:b] = got[q][:k, : b - a]
     elif correction == "all" and pairs > 0:
-        pad = np.full((maxk, pairs), -1.0)
-        pad[:k] = p
-        everything = comm.allgather(pad)                      # [world * maxk, pairs], absent rows negative
+        everything = comm.allgather(pad_rows(p, maxk, fill=-1.0))      # [world * maxk, pairs], absent rows negative
         q = _bh_masked_host(engine, everything.reshape(-1), None).reshape(everything.shape)
         p = q[comm.rank * maxk: comm.rank * maxk + k]
     return p
 
 
-class PairwiseShard:
+def _groups(width, G):
+    """the G column groups of a rank that owns `width` pair columns: [(lo, hi)] relative to its first column"""
+    return [(g * width // G, (g + 1) * width // G) for g in range(G)]
+
+
+class PairwiseShard(_RowRange):
     """One rank's part of `pairwise`, resident in HBM (device engines): load() uploads the rank's count rows and EITHER
     its local CSR OR the coordinates of its rows [ext_lo, ext_hi) (step() then clusters that range itself, as
     CompareShard does) and allocates every exchange buffer ONCE (their shapes follow from the plan); step() is device
@@ -438,173 +511,136 @@ class PairwiseShard:
     this step."""
 
     def __init__(self, engine, comm, n, s, plan, correction="pairwise", test="fisher", overlap_groups=None):
-        self.e, self.comm, self.n, self.s, self.plan = engine, comm, n, s, plan
+        super().__init__(engine, comm, n, s, plan)
         self.correction, self.test = correction, test
-        part = plan[comm.rank]
-        self.lo, self.hi, self.elo = part["own_lo"], part["own_hi"], part["ext_lo"]
-        self.k = self.hi - self.lo
         self.pairs = s * (s - 1) // 2
         # the exchange that takes the corrected values home goes in G column groups: group g's all-to-all runs on the
         # context's second stream (sdice_comm_fork) while group g + 1 is being corrected.  Every rank derives the same G.
-        ranges = pair_column_ranges(self.pairs, comm.world)
-        wmin = min(b - a for a, b in ranges) if self.pairs else 0
+        self.ranges = pair_column_ranges(self.pairs, comm.world)
+        wmin = min(b - a for a, b in self.ranges) if self.pairs else 0
         if overlap_groups is None:
             overlap_groups = 1 if comm.world == 1 else min(4, max(1, wmin // 1024))
         self.G = max(1, min(int(overlap_groups), max(wmin, 1))) if hasattr(engine, "comm_fork") else 1
-        self.rows_of = [q["own_hi"] - q["own_lo"] for q in plan]
-        self.maxk = max(max(self.rows_of), 1)
-        self.d_p = engine.empty((max(self.k, 1), max(self.pairs, 1)), np.float64)
-        self.d_counts = self.d_rp = self.d_cl = self.d_excl = self.d_row_of = None
-        self.d_j = None
-        self.d_bad = engine.empty(1, np.int64) if test == "chi2" else None
+        # block width of an exchange laid out in 1 or G column groups: the widest group any rank has
+        self.gw = {G: max(max(hi - lo for a, b in self.ranges for lo, hi in _groups(b - a, G)), 1) for G in (1, self.G)}
+        self.d_p = self.empty((max(self.k, 1), max(self.pairs, 1)), np.float64)
+        self.d_excl = None
+        self.d_bad = self.empty(1, np.int64) if test == "chi2" else None
         self.bufs = {}                                        # exchange buffers, allocated by load()
         self.ms = {}                                          # per-collective times of the last timed_collectives()
 
     def load(self, counts_ext, rp=None, cl=None, junctions=None):
-        e, w = self.e, self.comm.world
-        if self.k and self.pairs:
-            self.d_counts = e.to_device(np.ascontiguousarray(counts_ext), np.int32)
-            rows = self.d_counts.shape[0]
-            if junctions is not None:
-                cr, l, r, st = junctions
-                assert len(cr) == rows, (len(cr), rows)
-                self.d_j = [e.to_device(cr, np.int32), e.to_device(l, np.int32), e.to_device(r, np.int32), e.to_device(st, np.int8)]
-                self.d_row_of, self.d_rp = e.empty(rows, np.int32), e.empty(rows + 1, np.int64)
-                _size_range_lists(e, self.d_j, self.d_row_of, self.d_rp)
-            else:
-                self.d_rp = e.to_device(rp, np.int64)
-                self.d_cl = e.to_device(cl if cl.size else np.zeros(1, np.int32), np.int32)
-            self.d_excl = e.empty(self.d_counts.shape, np.int64)
-        if self.pairs and self.correction == "pairwise":
-            ranges = pair_column_ranges(self.pairs, w)
-            maxw = max(max(b - a for a, b in ranges), 1)
-            a, b = ranges[self.comm.rank]
-            shape = (w, self.maxk, maxw)
+        w, maxk, pairs = self.comm.world, self.maxk, self.pairs
+        if self.k and pairs:
+            self.load_rows(counts_ext, rp, cl, junctions)
+            self.d_excl = self.empty(self.d_counts.shape, np.int64)
+        if pairs and self.correction == "pairwise":
+            a, b = self.ranges[self.comm.rank]
+            shape = (w, maxk, self.gw[1])
             # (G > 1: the way back is laid out [group][rank][row][column of the group], so that a group is one contiguous exchange)
-            gw = self._group_width(ranges)
-            shape2 = (self.G, w, self.maxk, gw) if self.G > 1 else shape
-            self.bufs = dict(send=e.empty(shape, np.float64).zero(), back=e.empty(shape2, np.float64).zero(),
-                             mine=e.empty((max(self.n, 1), max(b - a, 1)), np.float64))
+            shape2 = (self.G, w, maxk, self.gw[self.G]) if self.G > 1 else shape
+            self.bufs = dict(send=self.empty(shape, np.float64).zero(), back=self.empty(shape2, np.float64).zero(),
+                             mine=self.empty((max(self.n, 1), max(b - a, 1)), np.float64))
             if w > 1 or self.G > 1:
-                self.bufs.update(got=e.empty(shape, np.float64), got2=e.empty(shape2, np.float64))
-        elif self.pairs and self.correction == "all":
-            self.bufs = dict(pad=e.empty((self.maxk, self.pairs), np.float64),
-                             d_q=e.empty((w * self.maxk, self.pairs), np.float64))
+                self.bufs.update(got=self.empty(shape, np.float64), got2=self.empty(shape2, np.float64))
+        elif pairs and self.correction == "all":
+            self.bufs = dict(pad=self.empty((maxk, pairs), np.float64), d_q=self.empty((w * maxk, pairs), np.float64))
             if w > 1:
-                self.bufs["everything"] = e.empty((w * self.maxk, self.pairs), np.float64)
-
-    def _group_ranges(self, width):
-        """the G column groups of a rank that owns `width` pair columns: [(lo, hi)] relative to its first column"""
-        return [(g * width // self.G, (g + 1) * width // self.G) for g in range(self.G)]
-
-    def _group_width(self, ranges):
-        return max(max(hi - lo for lo, hi in self._group_ranges(b - a)) for a, b in ranges) if self.pairs else 1
-
-    def _alltoall(self, x, into):
-        if into is not None and hasattr(self.comm, "alltoall_into"):
-            return self.comm.alltoall_into(x, into)
-        return self.comm.alltoall(x)
+                self.bufs["everything"] = self.empty((w * maxk, pairs), np.float64)
 
     def step(self):
-        e, comm, k, n, s, pairs = self.e, self.comm, self.k, self.n, self.s, self.pairs
-        a0, d_p, maxk, rows_of = self.lo - self.elo, self.d_p, self.maxk, self.rows_of
+        self._test_rows()
+        if self.pairs and self.correction == "pairwise":
+            self._correct_pairwise()
+        elif self.pairs and self.correction == "all":
+            self._correct_all()
+
+    def _test_rows(self):
+        """exclusion sums and the per-pair test of my rows -> d_p; a chi2 table with an empty row or column anywhere aborts
+        every rank (the one host round trip of a step: the count of such tables)"""
+        e, k, s, pairs, a0 = self.e, self.k, self.s, self.pairs, self.lo - self.elo
         n_bad = 0
         if k and pairs:
-            d_cl = self.d_cl
-            if self.d_j is not None:                          # the rank's own range, enqueued without a host round trip
-                d_cl, _ = e.cluster_dev(*self.d_j, self.d_row_of, self.d_rp, sync=False)
-                self.d_cl = d_cl                              # (a view of the context's list buffer: not owned)
-            e.ps_dev(self.d_counts, self.d_rp, d_cl, self.d_excl, None)
+            e.ps_dev(self.d_counts, self.d_rp, self.lists(), self.d_excl, None)
             inc, exc = self.d_counts.offset(a0 * s, (k, s)), self.d_excl.offset(a0 * s, (k, s))
             if self.test == "chi2":
-                e.chi2_pairs_dev(inc, exc, d_p.offset(0, (k, pairs)), self.d_bad)
+                e.chi2_pairs_dev(inc, exc, self.d_p.offset(0, (k, pairs)), self.d_bad)
                 n_bad = int(self.d_bad.to_host()[0])
             else:
-                e.fisher_pairs_dev(inc, exc, d_p.offset(0, (k, pairs)))
+                e.fisher_pairs_dev(inc, exc, self.d_p.offset(0, (k, pairs)))
         if self.test == "chi2":
-            _chi2_abort(comm, n_bad, n * pairs)
-        if self.correction == "pairwise" and pairs > 0:
-            ranges = pair_column_ranges(pairs, comm.world)
-            maxw = max(max(b - a for a, b in ranges), 1)
-            blk = maxk * maxw * 8
-            send, back, mine = self.bufs["send"], self.bufs["back"], self.bufs["mine"]
-            for q, (a, b) in enumerate(ranges):               # pack my rows of rank q's columns (device, strided)
-                if k and b > a:
-                    e.copy2d_dev(send.ptr + q * blk, maxw * 8, d_p.ptr + a * 8, pairs * 8, (b - a) * 8, k)
-            got = self._alltoall(send, self.bufs.get("got"))
-            a, b = ranges[comm.rank]
-            w = b - a
-            at = 0
-            for r in range(comm.world):                       # rank r's rows of MY columns -> one [n, w] table
-                if rows_of[r] and w:
-                    e.copy2d_dev(mine.ptr + at * w * 8, w * 8, got.ptr + r * blk, maxw * 8, w * 8, rows_of[r])
-                at += rows_of[r]
-            if self.G == 1:
-                if n and w:
-                    e.bh_columns_dev(mine.offset(0, (n, w)))
-                at = 0
-                for r in range(comm.world):
-                    if rows_of[r] and w:
-                        e.copy2d_dev(back.ptr + r * blk, maxw * 8, mine.ptr + at * w * 8, w * 8, w * 8, rows_of[r])
-                    at += rows_of[r]
-                got2 = self._alltoall(back, self.bufs.get("got2"))
-                for q, (a, b) in enumerate(ranges):               # corrected values back into my rows
-                    if k and b > a:
-                        e.copy2d_dev(d_p.ptr + a * 8, pairs * 8, got2.ptr + q * blk, maxw * 8, (b - a) * 8, k)
-            else:
-                # column groups: correct group g, pack it, send it home on the second stream while group g + 1 is corrected
-                gw = self._group_width(ranges)
-                blkg = maxk * gw * 8
-                got2 = self.bufs["got2"]
-                for g, (ga, gb) in enumerate(self._group_ranges(w)):
-                    if n and gb > ga:
-                        e.bh_columns_pitched_dev(mine.offset(ga, (n, gb - ga)), n, gb - ga, w)
-                    at = 0
-                    for r in range(comm.world):
-                        if rows_of[r] and gb > ga:
-                            e.copy2d_dev(back.ptr + (g * comm.world + r) * blkg, gw * 8, mine.ptr + (at * w + ga) * 8, w * 8,
-                                         (gb - ga) * 8, rows_of[r])
-                        at += rows_of[r]
-                    e.comm_fork()                                 # the second stream waits for the group's packing ...
-                    view_s = back.offset(g * comm.world * maxk * gw, (comm.world, maxk, gw))
-                    view_r = got2.offset(g * comm.world * maxk * gw, (comm.world, maxk, gw))
-                    if hasattr(comm, "alltoall_into"):
-                        comm.alltoall_into(view_s, view_r)        # ... and carries it while the main stream goes on
-                    else:
-                        e.copy2d_dev(view_r.ptr, view_s.nbytes, view_s.ptr, view_s.nbytes, view_s.nbytes, 1)
-                e.comm_join()
-                for q, (a, b) in enumerate(ranges):               # corrected values back into my rows
-                    for g, (ga, gb) in enumerate(self._group_ranges(b - a)):
-                        if k and gb > ga:
-                            e.copy2d_dev(d_p.ptr + (a + ga) * 8, pairs * 8, got2.ptr + (g * comm.world + q) * blkg, gw * 8,
-                                         (gb - ga) * 8, k)
-        elif self.correction == "all" and pairs > 0:
-            pad, d_q = self.bufs["pad"].memset(0xBF), self.bufs["d_q"]     # 0xBFBF... is a negative double: "absent"
-            if k:
-                e.copy2d_dev(pad.ptr, pairs * 8, d_p.ptr, pairs * 8, pairs * 8, k)
-            if "everything" in self.bufs and hasattr(comm, "allgather_into"):
-                everything = comm.allgather_into(pad, self.bufs["everything"])
-            else:
-                everything = comm.allgather(pad)
-            e.bh_masked_dev(everything, None, d_q)
-            if k:
-                e.copy2d_dev(d_p.ptr, pairs * 8, d_q.ptr + comm.rank * maxk * pairs * 8, pairs * 8, pairs * 8, k)
+            _chi2_abort(self.comm, n_bad, self.n * pairs)
+
+    def _copy_my_rows(self, blocks, G, pack):
+        """my rows of every rank's columns, d_p -> blocks (pack) or blocks -> d_p; `blocks` is laid out
+        [group][rank][maxk rows][gw[G] columns] with every rank's columns in G groups (device, strided)"""
+        gw = self.gw[G]
+        for q, (a, b) in enumerate(self.ranges):
+            for g, (ga, gb) in enumerate(_groups(b - a, G)):
+                if self.k and gb > ga:
+                    blk = (blocks.ptr + (g * self.comm.world + q) * self.maxk * gw * 8, gw * 8)
+                    own = (self.d_p.ptr + (a + ga) * 8, self.pairs * 8)
+                    self.e.copy2d_dev(*(blk + own if pack else own + blk), (gb - ga) * 8, self.k)
+
+    def _copy_my_columns(self, blocks, g, G, pack):
+        """every rank's rows of group g (of G) of my columns, mine -> blocks (pack) or blocks -> mine, the one [n, w] table
+        of complete columns; `blocks` laid out as in _copy_my_rows"""
+        a, b = self.ranges[self.comm.rank]
+        w, gw, (ga, gb), at = b - a, self.gw[G], _groups(b - a, G)[g], 0
+        for r, rows in enumerate(self.rows_of):
+            if rows and gb > ga:
+                blk = (blocks.ptr + (g * self.comm.world + r) * self.maxk * gw * 8, gw * 8)
+                tab = (self.bufs["mine"].ptr + (at * w + ga) * 8, w * 8)
+                self.e.copy2d_dev(*(blk + tab if pack else tab + blk), (gb - ga) * 8, rows)
+            at += rows
+
+    def _correct_pairwise(self):
+        """BH down every pair column over all junctions: rows -> columns all-to-all, column BH, and the way home in G
+        column groups -- with G > 1 group g travels on the second stream while group g + 1 is corrected"""
+        e, comm, n, G = self.e, self.comm, self.n, self.G
+        send, back, mine, got2 = self.bufs["send"], self.bufs["back"], self.bufs["mine"], self.bufs.get("got2")
+        self._copy_my_rows(send, 1, pack=True)
+        got = _alltoall(comm, send, self.bufs.get("got"))
+        self._copy_my_columns(got, 0, 1, pack=False)
+        a, b = self.ranges[comm.rank]
+        group = (comm.world, self.maxk, self.gw[G])
+        for g, (ga, gb) in enumerate(_groups(b - a, G)):
+            if n and gb > ga:
+                e.bh_columns_pitched_dev(mine.offset(ga, (n, gb - ga)), n, gb - ga, b - a)
+            self._copy_my_columns(back, g, G, pack=True)
+            if G > 1:
+                e.comm_fork()                                 # the second stream waits for the group's packing ...
+            at = g * int(np.prod(group))
+            home = _alltoall(comm, back.offset(at, group), got2.offset(at, group) if got2 is not None else None,
+                             in_place=G > 1)                  # ... and carries it while the main stream goes on
+        if G > 1:
+            e.comm_join()
+            home = got2
+        self._copy_my_rows(home, G, pack=False)
+
+    def _correct_all(self):
+        """one BH over the whole matrix: all-gather the raw rows, rank them redundantly, keep my rows"""
+        e, comm, k, pairs, d_p = self.e, self.comm, self.k, self.pairs, self.d_p
+        pad, d_q = self.bufs["pad"].memset(0xBF), self.bufs["d_q"]     # 0xBFBF... is a negative double: "absent"
+        if k:
+            e.copy2d_dev(pad.ptr, pairs * 8, d_p.ptr, pairs * 8, pairs * 8, k)
+        everything = _allgather(comm, pad, self.bufs.get("everything"))
+        e.bh_masked_dev(everything, None, d_q)
+        if k:
+            e.copy2d_dev(d_p.ptr, pairs * 8, d_q.ptr + comm.rank * self.maxk * pairs * 8, pairs * 8, pairs * 8, k)
 
     def timed_collectives(self, reps=3):
         """ms per all-to-all of the step's block shape, timed alone (after a step)"""
         if "send" not in self.bufs:
             return {}
         e, send = self.e, self.bufs["send"]
-        self._alltoall(send, self.bufs.get("got"))
+        _alltoall(self.comm, send, self.bufs.get("got"))
         e.sync()
         e.timer_start()
         for _ in range(reps):
-            self._alltoall(send, self.bufs.get("got"))
+            _alltoall(self.comm, send, self.bufs.get("got"))
         ms = e.timer_stop() / reps
         return {"alltoall_ms": ms, "alltoall_bytes_per_rank": int(send.nbytes), "alltoalls_per_step": 2}
-
-    def csr_host(self):
-        return _csr_host(self)
 
     def result(self):
         self.e.sync()
@@ -612,21 +648,8 @@ class PairwiseShard:
         return self.d_p.offset(0, (k, pairs)).to_host() if k and pairs else np.zeros((k, pairs), dtype=np.float64)
 
     def free(self):
-        for a in (self.d_counts, self.d_rp, self.d_cl, self.d_excl, self.d_row_of, self.d_p, self.d_bad, *(self.d_j or ()),
-                  *self.bufs.values()):
-            if a is not None:
-                a.free()
+        super().free()
         self.bufs = {}
-
-
-def _pairwise_dev(engine, comm, ext, rp, cl, a0, k, plan, n, pairs, correction, test="fisher", junctions=None, overlap_groups=None):
-    sh = PairwiseShard(engine, comm, n, ext.shape[1], plan, correction, test, overlap_groups=overlap_groups)
-    try:
-        sh.load(ext, rp, cl, junctions=junctions)
-        sh.step()
-        return sh.result()
-    finally:
-        sh.free()
 
 
 def pairwise_sharded(engine, comm, counts_ext, row_ptr, col, correction="pairwise", plan=None, test="fisher",
@@ -648,30 +671,22 @@ def pairwise_sharded(engine, comm, counts_ext, row_ptr, col, correction="pairwis
         raise ValueError("correction must be pairwise | all | none")
     if test not in ("fisher", "chi2"):
         raise ValueError("test must be fisher | chi2")
-    if junctions_ext is not None:
-        if plan is None:
-            raise ValueError("junctions_ext needs the plan it was cut by (shard.shard_plan_junctions)")
-        n = plan[-1]["own_hi"]
-    else:
-        n = row_ptr.size - 1
-        plan = plan or shard.shard_plan(row_ptr, col, comm.world)
-    part = plan[comm.rank]
+    dev = hasattr(engine, "fisher_pairs_dev") and comm.device    # (a device engine with a host communicator: host path)
+    n, plan, part, ext, rp, cl = _shard_inputs(engine, comm, counts_ext, row_ptr, col, plan, junctions_ext, dev)
     lo, hi, elo = part["own_lo"], part["own_hi"], part["ext_lo"]
     k = hi - lo
-    ext = np.ascontiguousarray(_own_slice(counts_ext, n, part))
+    if not k:
+        ext = np.ascontiguousarray(_own_slice(counts_ext, n, part))     # (here a rank without rows has its row count checked too)
     s = ext.shape[1]
     pairs = s * (s - 1) // 2
-    dev = hasattr(engine, "fisher_pairs_dev") and comm.device
-    rp, cl = np.zeros(1, np.int64), np.zeros(0, np.int32)
-    if k and junctions_ext is None:
-        rp, cl = shard.local_csr(row_ptr, col, part)
-    elif k and not dev:
-        row_of, rp, cl = engine.cluster(*junctions_ext)
-        if not np.array_equal(row_of, np.arange(len(row_of))):
-            raise ValueError("junctions_ext must be in output row order")
     if dev:
-        p = _pairwise_dev(engine, comm, ext, rp, cl, lo - elo, k, plan, n, pairs, correction, test,
-                          junctions=junctions_ext if k else None, overlap_groups=overlap_groups)
+        sh = PairwiseShard(engine, comm, n, s, plan, correction, test, overlap_groups=overlap_groups)
+        try:
+            sh.load(ext, rp, cl, junctions=junctions_ext if k else None)
+            sh.step()
+            p = sh.result()
+        finally:
+            sh.free()
     else:
         p = _pairwise_host(engine, comm, ext, rp, cl, lo - elo, k, plan, n, pairs, correction, test)
     return dict(p=p, own=(lo, hi), plan=plan)

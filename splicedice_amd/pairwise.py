@@ -11,6 +11,7 @@ sdice_chi2_pairs); Benjamini-Hochberg :182-193 -> sdice_bh / sdice_bh_columns.
 import numpy as np
 
 from . import textio
+from .distributed import CHI2_ZERO_MSG
 from .engine import Context
 
 
@@ -112,8 +113,7 @@ def device_pipeline(ctx, counts, row_ptr, col, chi2, correction, events, header,
         if n_bad:
             # scipy.stats.chi2_contingency raises on the first such table and the reference
             # run dies with it (pairwise_fisher.py:167-179)
-            raise ValueError("The internally computed table of expected frequencies has a zero element "
-                             f"({n_bad} of {n * pairs} sample-pair tables have an empty row or column)")
+            raise ValueError(f"{CHI2_ZERO_MSG} ({n_bad} of {n * pairs} sample-pair tables have an empty row or column)")
     else:
         ctx.fisher_pairs_dev(d_counts, d_excl, d_p)
     for a in (d_counts, d_rp, d_col, d_excl):
@@ -258,8 +258,7 @@ def run_with(args, ctx=None):
                 if n_bad:
                     # scipy.stats.chi2_contingency raises on the first such table and the reference
                     # run dies with it (pairwise_fisher.py:167-179)
-                    raise ValueError("The internally computed table of expected frequencies has a zero element "
-                                     f"({n_bad} of {parray.size} sample-pair tables have an empty row or column)")
+                    raise ValueError(f"{CHI2_ZERO_MSG} ({n_bad} of {parray.size} sample-pair tables have an empty row or column)")
             else:
                 parray = ctx.fisher_pairs(counts, excl)
             if args.multiple_test_correction == "all":

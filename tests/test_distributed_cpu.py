@@ -305,3 +305,144 @@ def test_subcommands_under_two_rank_launcher(which, tmp_path, golden_dir):
             for g, w in zip(got[1:], want[1:]):
                 np.testing.assert_allclose([float(x) for x in g[1:]], [float(x) for x in w[1:]], rtol=1e-9)
     assert not [f for f in os.listdir(tmp_path) if ".part" in f]
+
+
+# ---------------------------------------------------------------- what step() and free() promise, on a recording engine
+class _RecArray:
+    """engine.DeviceArray's surface; every call that would reach the device is logged on the engine double"""
+
+    def __init__(self, eng, shape, dtype, ptr, owned):
+        self.ctx, self.ptr, self.owned, self.free_calls = eng, ptr, owned, 0
+        self.shape = tuple(int(x) for x in (shape if isinstance(shape, (tuple, list)) else (shape,)))
+        self.dtype = np.dtype(dtype)
+        self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
+
+    def to_host(self, out=None):
+        self.ctx.calls.append("to_host")
+        return np.zeros(self.shape, self.dtype)
+
+    def memset(self, byte):
+        self.ctx.calls.append("memset")
+        return self
+
+    def zero(self):
+        return self.memset(0)
+
+    def offset(self, lead, shape):
+        return _RecArray(self.ctx, shape, self.dtype, self.ptr + lead * self.dtype.itemsize, owned=False)
+
+    def free(self):
+        self.free_calls += 1
+        if self.owned and self.ptr:                              # (as DeviceArray: a view is never released)
+            self.ctx.released.append(self.ptr)
+            self.ptr = None
+
+
+class _RecEngine:
+    """the engine.Context methods the shard classes use: allocations hand out tracked arrays, the rest only log"""
+
+    def __init__(self):
+        self.calls, self.allocated, self.released, self.next_ptr = [], [], [], 1 << 40
+        self.list_ptr = self._address()                          # the context's own list buffer
+
+    def _address(self):
+        self.next_ptr += 1 << 40
+        return self.next_ptr
+
+    def empty(self, shape, dtype):
+        self.calls.append("empty")
+        self.allocated.append(_RecArray(self, shape, dtype, self._address(), owned=True))
+        return self.allocated[-1]
+
+    def to_device(self, host, dtype=None):
+        self.calls.append("to_device")
+        host = np.ascontiguousarray(host, dtype=dtype)
+        self.allocated.append(_RecArray(self, host.shape, host.dtype, self._address(), owned=True))
+        return self.allocated[-1]
+
+    def cluster_dev(self, *arrays, sync=True):
+        self.calls.append("cluster_dev")
+        self.views.append(_RecArray(self, (0,), np.int32, self.list_ptr, owned=False))
+        return self.views[-1], (3 if sync else None)
+
+    views = ()
+
+
+for _name in ("set_param", "sync", "ps_dev", "ranksum_dev", "fisher_pairs_dev", "chi2_pairs_dev", "bh_columns_dev",
+              "bh_columns_pitched_dev", "bh_masked_dev", "copy2d_dev", "comm_fork", "comm_join"):
+    setattr(_RecEngine, _name, lambda self, *a, _name=_name, **kw: self.calls.append(_name))
+
+
+class _IntoComm:
+    """RcclComm's surface at world 2: collectives into a buffer the caller owns; the allocating forms allocate"""
+    device = True
+
+    def __init__(self, eng, rank, world):
+        self.eng, self.rank, self.world = eng, rank, world
+
+    def allgather(self, x):
+        return self.eng.empty((self.world * x.shape[0],) + tuple(x.shape[1:]), x.dtype)
+
+    def alltoall(self, x):
+        return self.eng.empty(x.shape, x.dtype)
+
+    def allgather_into(self, x, recv):
+        self.eng.calls.append("allgather_into")
+        return recv
+
+    def alltoall_into(self, x, recv):
+        self.eng.calls.append("alltoall_into")
+        return recv
+
+    def allsum(self, value):
+        return int(value)
+
+
+_STEP_CASES = [("compare", None, None, None)] + [("pairwise", corr, test, groups)
+                                                  for corr, test, groups in (("pairwise", "fisher", 1), ("pairwise", "fisher", 3),
+                                                                             ("pairwise", "chi2", 1), ("pairwise", "chi2", 3),
+                                                                             ("all", "fisher", 1), ("none", "chi2", 1))]
+
+
+@pytest.mark.parametrize("how", ["csr", "coordinates"])
+@pytest.mark.parametrize("which,correction,test,groups", _STEP_CASES)
+def test_shard_step_is_device_work_only_and_free_releases_everything_once(which, correction, test, groups, how):
+    """CompareShard / PairwiseShard, one group and several, SingleComm at world 1 and a communicator with
+    allgather_into / alltoall_into at world 2: step() allocates nothing (no empty, no to_device), downloads nothing and
+    does not synchronise -- but for the one count a chi2 step reads back -- and after free() every array the object
+    allocated has been freed exactly once, the list view that cluster_dev returned never."""
+    from splicedice_amd import distributed
+    s = 6
+    plans = {1: [dict(own_lo=0, own_hi=7, ext_lo=0, ext_hi=7)],
+             2: [dict(own_lo=0, own_hi=5, ext_lo=0, ext_hi=6), dict(own_lo=5, own_hi=9, ext_lo=4, ext_hi=9)]}
+    for world, rank in ((1, 0), (2, 0), (2, 1)):
+        plan = plans[world]
+        n, rows = plan[-1]["own_hi"], plan[rank]["ext_hi"] - plan[rank]["ext_lo"]
+        eng = _RecEngine()
+        eng.views = []
+        comm = distributed.SingleComm() if world == 1 else _IntoComm(eng, rank, world)
+        if which == "compare":
+            sh = distributed.CompareShard(eng, comm, n, s, plan, np.arange(3, dtype=np.int32), np.arange(3, 6, dtype=np.int32))
+        else:
+            sh = distributed.PairwiseShard(eng, comm, n, s, plan, correction, test, overlap_groups=groups)
+            assert sh.G == groups
+        counts = np.ones((rows, s), np.int32)
+        if how == "csr":
+            sh.load(counts, np.arange(rows + 1, dtype=np.int64), np.zeros(rows, np.int32))
+        else:
+            sh.load(counts, junctions=(np.zeros(rows, np.int32), np.arange(rows, dtype=np.int32), np.arange(rows, dtype=np.int32) + 5,
+                                       np.ones(rows, np.int8)))
+        for _ in range(2):
+            eng.calls.clear()
+            sh.step()
+            assert "ps_dev" in eng.calls and ("cluster_dev" in eng.calls) == (how == "coordinates"), eng.calls
+            assert not {"empty", "to_device", "sync"} & set(eng.calls), (world, rank, eng.calls)
+            assert eng.calls.count("to_host") == (1 if test == "chi2" else 0), (world, rank, eng.calls)
+            if world == 2 and correction != "none":
+                assert any(c.endswith("_into") for c in eng.calls), eng.calls
+            assert ("comm_fork" in eng.calls) == (which == "pairwise" and groups > 1)
+        sh.free()
+        assert all(a.free_calls == 1 and a.ptr is None for a in eng.allocated), (world, rank)
+        assert sorted(eng.released) == sorted(set(eng.released)) and len(eng.released) == len(eng.allocated)
+        assert (len(eng.views) > 0) == (how == "coordinates") and eng.list_ptr not in eng.released
+        assert all(v.ptr == eng.list_ptr and not v.owned for v in eng.views)
