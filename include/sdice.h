@@ -375,21 +375,15 @@ int sdice_prof_report(sdice_ctx* ctx, char* buf, int cap);
 int sdice_timer_start(sdice_ctx* ctx);
 int sdice_timer_stop(sdice_ctx* ctx, double* elapsed_ms);
 
-/* Tuning and test knobs (integer parameters by name); unknown name -> ERR_ARG.  Defaults are the measured optima.
- *   ps.lds_bytes (81920)  ps.threads (1024)  ps.tile_rows (0 = from the LDS budget)  ps.halo_rows (-1 = 16 or the clustering's
- *     reach)  ps.chunk_cols (0 = all columns up to 256, else 128)  ps.xcd_remap (1)  ps.quantize3 (0; 1 = store the '.3f'
- *     round trip of PS)  ps.prio (1 = window loads at raised wave priority)  ps.nt_loads (1 = non-temporal window
- *     loads when the table is not cut into column chunks)  ps.ablate (timing experiments of the ablation instantiations only)
- *   cluster.generic / cluster.legacy (0; 1 = the radix-sort path)  cluster.sample_sort (1)  cluster.bucket_mean (2048)
- *     cluster.spb (0 = 12 samples per bucket up to 2 M junctions, 8 beyond)  cluster.lds_cap (8192; small values force the in-HBM sort: tests)  cluster.ablate
- *     (only in a library built with -DSDICE_CLUSTER_ABLATE=1)
- *   ranksum.variant (0 auto, 1 lane, 2 block, 3 wave, 4 float lane pair, 5 counting)  ranksum.ablate (timing experiments)
- *   fisher.table_max (1 << 20 log-factorials; small values force the lgamma path: tests)  fisher.refill (16 idle lanes before
- *     the next pairs are fetched)  fisher.unroll (8 walk steps per trip: 1, 2, 4, 6 or 8)
- *   bh.columns_path (0 by size, 1 radix, 2 sample sort)  bh.mean (160 values per bucket)  bh.spb (8 samples per bucket)
- *     bh.reg_cap (1024; small values force the in-HBM bucket sort: tests)
- *   sort.rounds (radix-sort scheduling experiment) */
+/* Tuning and test knobs (integer parameters by name); unknown name -> ERR_ARG.  The one table of their names, defaults
+ * and meanings is splicedice_amd/csrc/params.h (INTEGRATION.md lists it; sdice_param_info enumerates it); the defaults are
+ * the measured optima. */
 int sdice_set_param(sdice_ctx* ctx, const char* name, int64_t value);
+/* the value in force: what sdice_set_param stored last, the default if the parameter was never set */
+int sdice_get_param(sdice_ctx* ctx, const char* name, int64_t* value);
+/* row `index` (0, 1, ...) of the parameter table: its name and default (either may be NULL); needs no context and no
+ * device; past the end -> ERR_ARG */
+int sdice_param_info(int32_t index, const char** name, int64_t* dflt);
 
 #ifdef __cplusplus
 }

@@ -253,7 +253,7 @@ extern "C" int sdice_bh_dev(sdice_ctx* ctx, int64_t m, const double* d_p, double
     SD_ARG(d_p && d_q, "NULL pointer");
     SD_HIP(hipSetDevice(ctx->device));
     // bh.vector_path: 0 = by size, 1 = radix path, 2 = sample-sort path (bh_cols.hip, four launches)
-    const int64_t vpath = ctx->param("bh.vector_path", 0);
+    const int64_t vpath = ctx->param(SD_P_BH_VECTOR_PATH);
     if (vpath != 1 && sd_bh_vector_supported(m)) {
         SD_TRY(ctx->arena.reserve(sd_bh_vector_scratch(ctx, m), ctx->stream));
         return sd_bh_vector_samplesort(ctx, m, d_p, nullptr, false, d_q);
@@ -269,7 +269,7 @@ extern "C" int sdice_bh_masked_dev(sdice_ctx* ctx, int64_t n, const double* d_p,
     if (n == 0) return SDICE_OK;
     SD_ARG(d_p && d_q, "NULL pointer");
     SD_HIP(hipSetDevice(ctx->device));
-    const int64_t vpath = ctx->param("bh.vector_path", 0);
+    const int64_t vpath = ctx->param(SD_P_BH_VECTOR_PATH);
     if (vpath != 1 && sd_bh_vector_supported(n)) {
         SD_TRY(ctx->arena.reserve(sd_bh_vector_scratch(ctx, n), ctx->stream));
         return sd_bh_vector_samplesort(ctx, n, d_p, d_tested, true, d_q);
@@ -348,7 +348,7 @@ extern "C" int sdice_bh_columns_pitched_dev(sdice_ctx* ctx, int64_t n, int64_t c
     SD_ARG(pitch >= cols, "pitch must be at least the number of columns");
     SD_HIP(hipSetDevice(ctx->device));
     // bh.columns_path: 0 = by size, 1 = generic radix path, 2 = sample-sort path
-    const int64_t path = ctx->param("bh.columns_path", 0);
+    const int64_t path = ctx->param(SD_P_BH_COLUMNS_PATH);
     if (path != 1 && sd_bh_cols_supported(n, cols)) return bh_columns_samplesort(ctx, n, cols, pitch, d_p_inout);
     SD_ARG(path != 2, "bh.columns_path = 2 needs columns of at most 2^18 values");
     // columns per group from what is free right now: per value 2 x 8 B (transposed in / out) + 8 B (dense slab

@@ -1401,11 +1401,11 @@ int sd_bh_cols_samplesort(sdice_ctx* ctx, int64_t m, int64_t segs, double* d_rm,
     a.segs = (int)segs;
     // buckets: bh.wg threads per bucket workgroup (256 / 512 / 1024: buckets of up to 1024 / 2048 / 4096 values), mean bucket
     // (bh.mean, default: half the workgroup's capacity)
-    int wg_threads = (int)ctx->param("bh.wg", 256);
+    int wg_threads = (int)ctx->param(SD_P_BH_WG);
     wg_threads = wg_threads >= 1024 ? 1024 : wg_threads >= 512 ? 512 : 256;
     int B = 1;
     if (m > 4 * (int64_t)wg_threads) {
-        int64_t mean = ctx->param("bh.mean", 0);
+        int64_t mean = ctx->param(SD_P_BH_MEAN);
         // (25 000 x 19 900, 256 threads: mean 400 / 450 / 512 / 600 -> 14.7 / 14.3 / 14.1 / 13.9 ms: fewer, fuller workgroups
         //  against more buckets beyond the capacity, ~1 % at 0.55 of it)
         if (mean <= 0) mean = wg_threads * 4 * 55 / 100;
@@ -1414,8 +1414,8 @@ int sd_bh_cols_samplesort(sdice_ctx* ctx, int64_t m, int64_t segs, double* d_rm,
         if (B > MAX_B) B = MAX_B;
     }
     a.B = B;
-    a.reg_cap = (int)std::min<int64_t>(2048, std::max<int64_t>(0, ctx->param("bh.reg_cap", 2048)));
-    a.spb = (int)ctx->param("bh.spb", 8);
+    a.reg_cap = (int)std::min<int64_t>(2048, std::max<int64_t>(0, ctx->param(SD_P_BH_REG_CAP)));
+    a.spb = (int)ctx->param(SD_P_BH_SPB);
     if (a.spb < 1) a.spb = 1;
     while (a.spb > 1 && (int64_t)a.spb * B > 8192) a.spb >>= 1;      // the sample is sorted in 96 KB of LDS
     while (a.spb > 1 && (int64_t)a.spb * B * 2 > m) a.spb >>= 1;
@@ -1445,7 +1445,7 @@ int sd_bh_cols_samplesort(sdice_ctx* ctx, int64_t m, int64_t segs, double* d_rm,
     SD_HIP(hipMemsetAsync(zeroed, 0, 16, ctx->stream));
     const int64_t strips = sd_ceil_div(segs, (int64_t)TC_COLS);
     SD_ARG(strips < ((int64_t)1 << 31), "bh: too many columns");
-    const int rows_per_block = (int)std::max<int64_t>(TC_ROWS, std::min<int64_t>(ctx->param("bh.rows_per_block", 2048), m));
+    const int rows_per_block = (int)std::max<int64_t>(TC_ROWS, std::min<int64_t>(ctx->param(SD_P_BH_ROWS_PER_BLOCK), m));
     const int strips_per_xcd = (int)sd_ceil_div(strips, (int64_t)8);
     const int64_t tblocks = (int64_t)strips_per_xcd * 8 * sd_ceil_div(m, (int64_t)rows_per_block);
     SD_ARG(tblocks < ((int64_t)1 << 31), "bh: too many tiles");
@@ -1463,7 +1463,7 @@ int sd_bh_cols_samplesort(sdice_ctx* ctx, int64_t m, int64_t segs, double* d_rm,
         // the splitters of a 16-column strip beside the transpose tile: up to ~190 buckets per column; beyond, the
         // transpose runs alone and the tiles of the scatter kernel count first
         const size_t lds_tc = (size_t)TC_COLS * ((size_t)(B - 1) * 12 + (size_t)B * 4);
-        if (lds_tc <= 48 * 1024 && ctx->param("bh.fused_count", 1)) {
+        if (lds_tc <= 48 * 1024 && ctx->param(SD_P_BH_FUSED_COUNT)) {
             SD_LAUNCH(ctx, "bhs_transpose_count_kernel", (bhs_transpose_kernel<true>), tgrid, dim3(TC_T), lds_tc, a, rows_per_block, strips_per_xcd);
         } else {
             SD_LAUNCH(ctx, "bhs_transpose_kernel", (bhs_transpose_kernel<false>), tgrid, dim3(TC_T), 0, a, rows_per_block, strips_per_xcd);
@@ -1491,7 +1491,7 @@ int sd_bh_cols_samplesort(sdice_ctx* ctx, int64_t m, int64_t segs, double* d_rm,
     const int64_t big_blocks = std::max<int64_t>(1, std::min<int64_t>(n_buckets, (int64_t)ctx->n_cu * 4));
     // the listed buckets of 1 025 ... 2 048 values: 512 threads x 4 values (109 VGPRs) take 0.61 ms on the bench's table where
     // 256 x 8 (173 VGPRs, two waves per SIMD) take 0.77
-    if (ctx->param("bh.big_wg", 512) >= 512) {
+    if (ctx->param(SD_P_BH_BIG_WG) >= 512) {
         SD_LAUNCH(ctx, "bhs_bucket_big_kernel", (bhs_bucket_big_kernel<512, 4>), dim3((unsigned)big_blocks), dim3(512), (bucket_wg_lds<512, 4>()), a);
     } else {
         SD_LAUNCH(ctx, "bhs_bucket_big_kernel", (bhs_bucket_big_kernel<256, 8>), dim3((unsigned)big_blocks), dim3(256), (bucket_wg_lds<256, 8>()), a);
@@ -1500,8 +1500,8 @@ int sd_bh_cols_samplesort(sdice_ctx* ctx, int64_t m, int64_t segs, double* d_rm,
     SD_LAUNCH(ctx, "bhs_suffix_kernel", bhs_suffix_kernel, dim3((unsigned)segs), dim3(256), 0, a);
     // bh.finish_cols: columns per workgroup of the last kernel (16: full 128-byte lines out, 3.2 MB of results per strip
     // at 25 000 rows; 8: half lines, half the L2 footprint of the gather); bh.finish_nt: non-temporal gather loads
-    const int fcols = ctx->param("bh.finish_cols", 16) >= 16 ? 16 : 8;
-    const bool fnt = ctx->param("bh.finish_nt", 0) != 0;
+    const int fcols = ctx->param(SD_P_BH_FINISH_COLS) >= 16 ? 16 : 8;
+    const bool fnt = ctx->param(SD_P_BH_FINISH_NT) != 0;
     const int64_t fstrips = sd_ceil_div(segs, (int64_t)fcols);
     const int64_t row_tiles = sd_ceil_div(m, (int64_t)(2048 / fcols));
     const int64_t fin_blocks = sd_ceil_div(fstrips, (int64_t)8) * 8 * row_tiles;
@@ -1522,13 +1522,13 @@ bool sd_bh_vector_supported(int64_t n) { return n >= 16384 && n <= ((int64_t)2 <
 // geometry of the one-vector path: buckets of ~2048 values, 16 samples per bucket (sizes ~ Gamma(16): sigma = mean / 4);
 // a bucket beyond its slot / the LDS capacity (5632 = mean + 7 sigma) practically never occurs (slow path: one wave, HBM)
 static void bhv_geometry(sdice_ctx* ctx, int64_t n, int* B_out, int* cap_out) {
-    int64_t mean = ctx->param("bhv.mean", 2048);
+    int64_t mean = ctx->param(SD_P_BHV_MEAN);
     if (mean < 512) mean = 512;
     if (mean < sd_ceil_div(n, (int64_t)1024)) mean = sd_ceil_div(n, (int64_t)1024);
     int B = (int)sd_ceil_div(n, mean);
     if (B < 2) B = 2;
     if (B > 1024) B = 1024;
-    int cap = (int)ctx->param("bhv.cap", 5632);     // 5632 x 13 B = 73 KB of LDS: two bucket workgroups per CU
+    int cap = (int)ctx->param(SD_P_BHV_CAP);     // 5632 x 13 B = 73 KB of LDS: two bucket workgroups per CU
     if (cap < 64) cap = 64;
     if (cap > BHV_T * BHV_EPT) cap = BHV_T * BHV_EPT;
     *B_out = B; *cap_out = cap;

@@ -388,7 +388,7 @@ int sd_cluster_legacy(sdice_ctx* ctx, int64_t n, const int32_t* d_chrom, const i
     pk.min_left = (uint32_t)min_left;
     const int bS = bits_for((max_chrom << 1) | 1ull);
     // 62: (n_seg + 1) << seg_shift must not overflow in the segment table
-    const bool packed = (pk.bN + pk.bL + bS <= 62) && !ctx->param("cluster.generic", 0);
+    const bool packed = (pk.bN + pk.bL + bS <= 62) && !ctx->param(SD_P_CLUSTER_GENERIC);
 
     uint32_t* srow;
     uint64_t *ckL, *ckR, *pmax;
@@ -481,7 +481,7 @@ int sd_cluster_legacy(sdice_ctx* ctx, int64_t n, const int32_t* d_chrom, const i
 }
 
 int sd_cluster_check_nnz(sdice_ctx* ctx, int64_t nnz, bool host) {
-    int64_t cap = ctx->param("cluster.max_nnz", 0);
+    int64_t cap = ctx->param(SD_P_CLUSTER_MAX_NNZ);
     const char* what = "param cluster.max_nnz";
     if (cap <= 0) {
         size_t free_b = 0, total_b = 0;

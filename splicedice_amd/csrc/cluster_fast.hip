@@ -1018,7 +1018,8 @@ int fast_plan(sdice_ctx* ctx, int64_t n, const int32_t* d_chrom, const int32_t* 
               const int8_t* d_strand, int32_t* d_row_of, int64_t* d_row_ptr, FastPlan& pl) {
     FastArgs& a = pl.a;
     a.chrom = d_chrom; a.left = d_left; a.right = d_right; a.strand = d_strand; a.n = n;
-    int64_t bucket_mean = ctx->param("cluster.bucket_mean", BUCKET_MEAN);
+    static_assert(kSdParams[SD_P_CLUSTER_BUCKET_MEAN].dflt == BUCKET_MEAN, "the default is the largest mean the kernels take");
+    int64_t bucket_mean = ctx->param(SD_P_CLUSTER_BUCKET_MEAN);
     if (bucket_mean < 256 || bucket_mean > BUCKET_MEAN) bucket_mean = BUCKET_MEAN;
     int64_t B = sd_ceil_div(n, bucket_mean);
     if (B < 1) B = 1;
@@ -1026,16 +1027,16 @@ int fast_plan(sdice_ctx* ctx, int64_t n, const int32_t* d_chrom, const int32_t* 
     a.B = (int)B;
     // samples per bucket: 12 up to 2 M junctions (tighter bucket sizes: the largest bucket IS the sort kernel's time; -1.4 % on
     // the whole quant step at 1 M), 8 beyond (the sample is ranked by brute force, O(S^2))
-    a.spb = (int)ctx->param("cluster.spb", 0);
+    a.spb = (int)ctx->param(SD_P_CLUSTER_SPB);
     if (a.spb < 2 || a.spb > 64) a.spb = n <= ((int64_t)2 << 20) ? 12 : SPB;
     a.S = B > 1 ? (int)(B * a.spb) : 0;
     const int64_t mean = sd_ceil_div(n, B);
     a.slot_cap = B > 1 ? (mean * SLOT_FACTOR < n ? mean * SLOT_FACTOR : n) : n;
-    int64_t lds_cap = ctx->param("cluster.lds_cap", 8192);      // (test knob: 0 = default; small values force the HBM sort)
+    int64_t lds_cap = ctx->param(SD_P_CLUSTER_LDS_CAP);      // (test knob: 0 = default; small values force the HBM sort)
     if (lds_cap <= 0 || lds_cap > 8192) lds_cap = 8192;
     if (lds_cap < 2) lds_cap = 2;
     a.lds_cap = (int)lds_cap;
-    a.sample_sort = ctx->param("cluster.sample_sort", 1) != 0;
+    a.sample_sort = ctx->param(SD_P_CLUSTER_SAMPLE_SORT) != 0;
     pl.n_tiles = (int)sd_ceil_div(n, NB_T);
     const size_t nb64 = (size_t)sd_ceil_div(n, 64) + 2;
     // The status block is a small persistent allocation of the context (an asynchronous call is
@@ -1073,7 +1074,7 @@ int fast_plan(sdice_ctx* ctx, int64_t n, const int32_t* d_chrom, const int32_t* 
     a.bmax64 = a.rank + a.S + 4;
     a.col_done = a.bmax64 + nb64;
     a.row_of = d_row_of; a.row_ptr = d_row_ptr;
-    a.ablate = (int)ctx->param("cluster.ablate", 0);
+    a.ablate = (int)ctx->param(SD_P_CLUSTER_ABLATE);
     return SDICE_OK;
 }
 
@@ -1090,7 +1091,7 @@ int launch_neighbours(sdice_ctx* ctx, FastPlan& pl) {
         per_cu = occ > 0 ? occ : 1;
     }
     int64_t grid = std::min<int64_t>(pl.n_tiles, (int64_t)per_cu * ctx->n_cu);
-    const int64_t forced = ctx->param("cluster.nb_grid", 0);
+    const int64_t forced = ctx->param(SD_P_CLUSTER_NB_GRID);
     if (forced > 0) grid = std::min<int64_t>(grid, forced);
     SD_LAUNCH(ctx, "neighbours_kernel", (neighbours_kernel<NB_T>), dim3((unsigned)std::max<int64_t>(grid, 1)), dim3(NB_T), 0, pl.a);
     return SDICE_OK;
@@ -1207,7 +1208,7 @@ extern "C" int sdice_cluster_dev(sdice_ctx* ctx, int64_t n, const int32_t* d_chr
     // one leaves their status pending: failures accumulate in the sticky word of the status block
     if (nnz_out && ctx->cluster_pending) SD_TRY(sd_cluster_resolve(ctx));
     ctx->reach_n = 0;
-    const bool legacy = n > FAST_MAX_N || ctx->param("cluster.generic", 0) || ctx->param("cluster.legacy", 0);
+    const bool legacy = n > FAST_MAX_N || ctx->param(SD_P_CLUSTER_GENERIC) || ctx->param(SD_P_CLUSTER_LEGACY);
     if ((legacy || n == 0) && ctx->cluster_pending) SD_TRY(sd_cluster_resolve(ctx));     // (the generic path synchronises)
     if (legacy || n == 0) return sd_cluster_legacy(ctx, n, d_chrom, d_left, d_right, d_strand, d_row_of, d_row_ptr, nnz_out);
     SD_ARG(d_chrom && d_left && d_right && d_strand && d_row_of && d_row_ptr, "NULL pointer");

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 #include "sdice.h"
+#include "params.h"
 
 void sdice_set_error(const char* fmt, ...);
 
@@ -95,8 +96,11 @@ struct sdice_ctx {
     std::vector<hipEvent_t> event_pool;
     hipEvent_t t0 = nullptr, t1 = nullptr;
 
-    // tuning parameters
-    std::map<std::string, int64_t> params;
+    // tuning parameters: the values in force, indexed by SdParam (params.h)
+    int64_t params[SD_P_COUNT];
+    sdice_ctx() {
+        for (int i = 0; i < SD_P_COUNT; ++i) params[i] = kSdParams[i].dflt;
+    }
 
     // RCCL
     void* rccl_lib = nullptr;
@@ -107,10 +111,7 @@ struct sdice_ctx {
     bool comm_forked = false;
     hipStream_t coll_stream() const { return comm_forked ? comm_stream : stream; }
 
-    int64_t param(const char* name, int64_t dflt) const {
-        auto it = params.find(name);
-        return it == params.end() ? dflt : it->second;
-    }
+    int64_t param(SdParam which) const { return params[which]; }
 };
 
 int sd_prof_begin(sdice_ctx* ctx, const char* name);

@@ -340,16 +340,34 @@ extern "C" int sdice_timer_stop(sdice_ctx* ctx, double* elapsed_ms) {
     return SDICE_OK;
 }
 
+// ---------------------------------------------------------------- parameters (params.h)
+// row of `name` in the table; -1 (error set, in the name of the entry point `who`) when there is none
+static int param_index(const char* who, const char* name) {
+    for (int i = 0; i < SD_P_COUNT; ++i)
+        if (strcmp(kSdParams[i].name, name) == 0) return i;
+    sdice_set_error("%s: unknown parameter '%s'", who, name);
+    return -1;
+}
+
 extern "C" int sdice_set_param(sdice_ctx* ctx, const char* name, int64_t value) {
     SD_ARG(ctx && name, "bad arguments");
-    static const char* known[] = {"ps.lds_bytes", "ps.tile_rows", "ps.threads", "ps.chunk_cols",
-                                  "ps.xcd_remap", "ps.halo_rows", "cluster.generic", "cluster.legacy", "cluster.lds_cap", "cluster.ablate", "cluster.nb_grid", "cluster.sample_sort", "cluster.bucket_mean", "cluster.spb", "cluster.max_nnz", "ps.ablate", "ps.quantize3", "ps.prio", "ps.nt_loads", "ps.gen1", "ps.use_reach", "sort.rounds", "ranksum.variant", "ranksum.ablate",
-                                  "fisher.table_max", "fisher.refill", "fisher.unroll", "fisher.count_steps", "bh.columns_path", "bh.vector_path", "bhv.mean", "bhv.cap", "bh.reg_cap", "bh.mean", "bh.rows_per_block", "bh.fused_count", "bh.finish_cols", "bh.finish_nt", "bh.wg", "bh.big_wg", "bh.spb", nullptr};
-    for (int i = 0; known[i]; ++i)
-        if (strcmp(known[i], name) == 0) {
-            ctx->params[name] = value;
-            return SDICE_OK;
-        }
-    sdice_set_error("sdice_set_param: unknown parameter '%s'", name);
-    return SDICE_ERR_ARG;
+    const int i = param_index(__func__, name);
+    if (i < 0) return SDICE_ERR_ARG;
+    ctx->params[i] = value;
+    return SDICE_OK;
+}
+
+extern "C" int sdice_get_param(sdice_ctx* ctx, const char* name, int64_t* value) {
+    SD_ARG(ctx && name && value, "bad arguments");
+    const int i = param_index(__func__, name);
+    if (i < 0) return SDICE_ERR_ARG;
+    *value = ctx->params[i];
+    return SDICE_OK;
+}
+
+extern "C" int sdice_param_info(int32_t index, const char** name, int64_t* dflt) {
+    SD_ARG(index >= 0 && index < SD_P_COUNT, "index past the end of the parameter table");
+    if (name) *name = kSdParams[index].name;
+    if (dflt) *dflt = kSdParams[index].dflt;
+    return SDICE_OK;
 }

@@ -393,7 +393,7 @@ fisher_pairs_kernel(const int32_t* __restrict__ incl, const int64_t* __restrict_
 
 // log-factorial table owned by the context (built on first use)
 static int get_lf_table(sdice_ctx* ctx, LfTable* out) {
-    long long want = ctx->param("fisher.table_max", 1 << 20);
+    long long want = ctx->param(SD_P_FISHER_TABLE_MAX);
     if (want < 2) want = 2;
     if (ctx->d_lf && ctx->lf_n == want) {
         out->lf = ctx->d_lf;
@@ -430,12 +430,12 @@ extern "C" int sdice_fisher_pairs_dev(sdice_ctx* ctx, int64_t n, int32_t s, cons
     SD_HIP(hipSetDevice(ctx->device));
     LfTable t;
     SD_TRY(get_lf_table(ctx, &t));
-    int refill = (int)ctx->param("fisher.refill", 12);
+    int refill = (int)ctx->param(SD_P_FISHER_REFILL);
     if (refill < 1) refill = 1;
     if (refill > 64) refill = 64;
     // steps per trip: 16 (153 VGPRs, three waves per SIMD, nothing spilled) 16.0 ms per 25 000 x 19 900; 8 (114 VGPRs, four
     // waves) 16.6 ms; 16 under a 128-VGPR cap spills 100 bytes inside the loop: 18.5 ms; under 96 (five waves): 34-43 ms
-    const int unroll = (int)ctx->param("fisher.unroll", 16);
+    const int unroll = (int)ctx->param(SD_P_FISHER_UNROLL);
     const int64_t n_pairs = (int64_t)s * (s - 1) / 2;
     SD_TRY(ctx->arena.reserve((size_t)n_pairs * 4 + (size_t)n + 8192, ctx->stream));
     unsigned* pair_tab = (unsigned*)ctx->arena.alloc((size_t)n_pairs * 4);
@@ -447,7 +447,7 @@ extern "C" int sdice_fisher_pairs_dev(sdice_ctx* ctx, int64_t n, int32_t s, cons
     SD_LAUNCH(ctx, "pair_table_kernel", pair_table_kernel, dim3((unsigned)sd_ceil_div(n_pairs, (int64_t)256)), dim3(256), 0,
               pair_tab, n_pairs, (int)s);
     const size_t lds = (size_t)s * 16 + 512 * 8;
-    const bool count = ctx->param("fisher.count_steps", 0) != 0;
+    const bool count = ctx->param(SD_P_FISHER_COUNT_STEPS) != 0;
     auto kern = count ? (unroll <= 4 ? fisher_pairs_kernel<4, true> : unroll <= 8 ? fisher_pairs_kernel<8, true> :
                          unroll <= 12 ? fisher_pairs_kernel<12, true> : unroll <= 16 ? fisher_pairs_kernel<16, true> :
                          unroll <= 20 ? fisher_pairs_kernel<20, true> : fisher_pairs_kernel<24, true>)

@@ -765,9 +765,9 @@ extern "C" int sdice_ps_dev(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t*
     const bool aligned = ((uintptr_t)d_counts % 16 == 0) && (!d_ps || (uintptr_t)d_ps % 16 == 0) &&
                          (!d_excl || (uintptr_t)d_excl % 16 == 0);
     const int vec = (s % 4 == 0 && aligned) ? 4 : 1;
-    const int abl = (int)ctx->param("ps.ablate", 0);
+    const int abl = (int)ctx->param(SD_P_PS_ABLATE);
     int cw = s;
-    const int64_t chunk_param = ctx->param("ps.chunk_cols", 0);
+    const int64_t chunk_param = ctx->param(SD_P_PS_CHUNK_COLS);
     if (chunk_param > 0) cw = (int)chunk_param;
     else if (s > 256) cw = 128;
     if (cw > s) cw = s;
@@ -777,13 +777,13 @@ extern "C" int sdice_ps_dev(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t*
     // (ps_tile_kernel; also serves tables whose rows are not 16-byte vectors, column chunks whose vectors do not divide
     // 64, tile shapes beyond the register staging of the newer kernel, and the timing experiments)
     const bool pow2chunk = cw == s || (cw / 4 <= 64 && 64 % (cw / 4) == 0);
-    int kern = ctx->param("ps.gen1", 0) != 0 ? 2 : 0;
+    int kern = ctx->param(SD_P_PS_GEN1) != 0 ? 2 : 0;
     if (vec != 4 || abl != 0 || !pow2chunk) kern = 2;
     if ((int64_t)s * 2048 >= ((int64_t)1 << 30)) kern = 2;       // (the newer kernel addresses a tile's outputs by 32-bit offsets)
-    int64_t lds = ctx->param("ps.lds_bytes", 80 * 1024);   // two workgroups per CU (160 KiB LDS)
+    int64_t lds = ctx->param(SD_P_PS_LDS_BYTES);   // two workgroups per CU (160 KiB LDS)
     if (lds > 160 * 1024) lds = 160 * 1024;
     if (lds < 8 * 1024) lds = 8 * 1024;
-    int threads = (int)ctx->param("ps.threads", 1024);
+    int threads = (int)ctx->param(SD_P_PS_THREADS);
     threads = (threads / 64) * 64;
     if (threads < 64) threads = 64;
     if (threads > 1024) threads = 1024;
@@ -799,8 +799,8 @@ extern "C" int sdice_ps_dev(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t*
         // LDS budget (ints): (R + 2H + 1) * cw window + 16 R staged neighbour offsets + (R + 1) row pointers + scratch
         const int64_t L = lds / 4 - (newk ? 64 : 16);      // (the newer kernel keeps 16 per-wave words behind the row pointers)
         have_reach = newk && d_col != nullptr && d_col == ctx->d_col && ctx->reach_n == n && ctx->d_reach != nullptr &&
-                     ctx->param("ps.use_reach", 1) != 0;
-        H = ctx->param("ps.halo_rows", -1);
+                     ctx->param(SD_P_PS_USE_REACH) != 0;
+        H = ctx->param(SD_P_PS_HALO_ROWS);
         const bool h_auto = H < 0;
         if (h_auto) {
             // rows further than the halo are still summed exactly (global-memory path).  With reach bytes H is the
@@ -820,7 +820,7 @@ extern "C" int sdice_ps_dev(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t*
         const int64_t h_cap = newk ? (int64_t)threads / LV : (int64_t)1 << 20;
         if (H > h_cap) H = h_cap;
         const int64_t per_row = 17;      // 16 staged neighbour offsets + the row pointer
-        const int64_t r_param = ctx->param("ps.tile_rows", 0);
+        const int64_t r_param = ctx->param(SD_P_PS_TILE_ROWS);
         auto fit_rows = [&](int64_t h) {
             int64_t r = r_param > 0 ? r_param : (L - (2 * h + 1) * cw) / (cw + per_row);
             return std::min(r, r_cap);
@@ -860,17 +860,17 @@ extern "C" int sdice_ps_dev(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t*
     a.n_tiles = (int)sd_ceil_div(n, R);
     const int n_chunks = (int)sd_ceil_div(s, cw);
     a.n_chunks = n_chunks;
-    a.prio = ctx->param("ps.prio", 1) != 0;
+    a.prio = ctx->param(SD_P_PS_PRIO) != 0;
     // window loads that do not linger in the L2: -4 % at 1 M x 100 (0.179 -> 0.172 ms in one process); with column chunks
     // the lines shared by two chunks and the halo rows want the L2 (+1.7 % at 2 M x 500): unchunked tables only
-    a.nt = ctx->param("ps.nt_loads", 1) != 0 && n_chunks == 1;
+    a.nt = ctx->param(SD_P_PS_NT_LOADS) != 0 && n_chunks == 1;
     a.reach = use_reach ? ctx->d_reach : nullptr;
     a.lv_shift = 0;                                        // column chunks: log2(row segments per 1 KiB piece)
     for (int b = 0; b <= 6; ++b) if ((cw / 4) == (64 >> b)) a.lv_shift = b;
     int gx = a.n_tiles;
     a.tiles_per_xcd = 0;
-    const bool q3 = ctx->param("ps.quantize3", 0) != 0;
-    if (ctx->param("ps.xcd_remap", 1) && a.n_tiles >= 64) {
+    const bool q3 = ctx->param(SD_P_PS_QUANTIZE3) != 0;
+    if (ctx->param(SD_P_PS_XCD_REMAP) && a.n_tiles >= 64) {
         a.tiles_per_xcd = (int)sd_ceil_div(a.n_tiles, 8);
         gx = a.tiles_per_xcd * 8;
     }

@@ -264,7 +264,7 @@ int sd_radix_sort_pairs_segmented(sdice_ctx* ctx, int64_t n, int64_t segs, const
         }
         return SDICE_OK;
     }
-    int64_t rounds = ctx->param("sort.rounds", 0);
+    int64_t rounds = ctx->param(SD_P_SORT_ROUNDS);
     if (rounds != 4 && rounds != 12) rounds = 12;   // measured: 4 is no faster at 1M keys and 16% slower at 5M
     if (rounds == 4)
         return radix_sort_passes<4>(ctx, n, segs, d_keys_in, d_vals_in, d_keys_out, d_vals_out, d_keys_tmp, d_vals_tmp,

@@ -1317,7 +1317,7 @@ int launch_wave(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32
         SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ranksum_count_kernel<E>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
         SD_LAUNCH(ctx, "ranksum_count_kernel", (ranksum_count_kernel<E>), dim3((unsigned)blocks), dim3(waves * 64), lds_c,
-                  d_ps, n, s, g1, n1, g2, n2, ch, (int)ctx->param("ranksum.ablate", 0), o);
+                  d_ps, n, s, g1, n1, g2, n2, ch, (int)ctx->param(SD_P_RANKSUM_ABLATE), o);
     }
     SD_LAUNCH(ctx, "ranksum_wave_kernel", (ranksum_wave_kernel<E>), dim3((unsigned)blocks), dim3(waves * 64), lds, d_ps, n,
               s, g1, n1, g2, n2, ch, counting ? 1 : 0, o);
@@ -1338,7 +1338,7 @@ int launch_lane(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32
     SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ranksum_lane_kernel<P>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     SD_LAUNCH(ctx, "ranksum_lane_kernel", (ranksum_lane_kernel<P>), dim3((unsigned)blocks), dim3(waves * 64), lds, d_ps, n,
-              s, g1, g2, n1, n2, stride, o, (int)ctx->param("ranksum.ablate", 0));
+              s, g1, g2, n1, n2, stride, o, (int)ctx->param(SD_P_RANKSUM_ABLATE));
     SD_LAUNCH(ctx, "ranksum_finish_kernel", ranksum_finish_kernel, dim3((unsigned)sd_ceil_div(n, 256)), dim3(256), 0, n,
               o.p, o.z);
     return SDICE_OK;
@@ -1416,7 +1416,7 @@ extern "C" int sdice_ranksum_dev(sdice_ctx* ctx, int64_t n, int32_t s, const flo
         return SDICE_OK;
     }
     SD_ARG(d_ps, "ps is NULL");
-    const int64_t variant = ctx->param("ranksum.variant", 0);  // 0 auto, 1 lane, 2 block, 3 wave (sorting only), 4 lane pair, 5 counting + wave
+    const int64_t variant = ctx->param(SD_P_RANKSUM_VARIANT);  // 0 auto, 1 lane, 2 block, 3 wave (sorting only), 4 lane pair, 5 counting + wave
     const bool lane_ok = n1 <= 64 && n2 <= 64;
     SD_ARG((variant != 1 && variant != 4) || lane_ok, "lane variants need n1, n2 <= 64");
     if ((variant == 0 && lane_ok) || variant == 1 || variant == 4) {

@@ -1,4 +1,5 @@
 """Thin numpy-facing wrapper over the C ABI (include/sdice.h).  No compute happens here."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -102,6 +103,26 @@ class Context:
 
     def set_param(self, name, value):
         check(self.lib.sdice_set_param(self.h, name.encode(), int(value)), f"sdice_set_param({name})")
+
+    def get_param(self, name):
+        """the value in force: the last one set, the library's default if the parameter was never set"""
+        v = C.c_int64()
+        check(self.lib.sdice_get_param(self.h, name.encode(), C.byref(v)), f"sdice_get_param({name})")
+        return v.value
+
+    @contextlib.contextmanager
+    def params(self, values):
+        """`with ctx.params({"bh.wg": 512, "bh.mean": 900}):` sets the given parameters for the block and then writes back,
+        in reverse order, the values that were in force before it, so scopes nest and no caller needs to know a default.
+        A parameter that was never set ends up set to its default, which every read treats like unset."""
+        old = [(name, self.get_param(name)) for name in values]
+        try:
+            for name, value in values.items():
+                self.set_param(name, value)
+            yield self
+        finally:
+            for name, value in reversed(old):
+                self.set_param(name, value)
 
     def sync(self):
         check(self.lib.sdice_sync(self.h), "sdice_sync")

@@ -119,19 +119,14 @@ def gen_cluster_big(ctx, rng):
         # refuse it cleanly under a cap, before it allocates anything of that size on either side
         from splicedice_amd.engine import SdiceError
         try:
-            ctx.set_param("cluster.max_nnz", 400_000_000)
-            ctx.cluster(cr, left, right, strand)
+            with ctx.params({"cluster.max_nnz": 400_000_000}):
+                ctx.cluster(cr, left, right, strand)
             return f"cluster_big: a list of > 4e8 entries was materialised under cluster.max_nnz = 4e8 (n={first.size} kind={kind})"
         except SdiceError as e:
             return None if "neighbour list" in str(e) else f"cluster_big: unexpected error for a dense draw: {e}"
-        finally:
-            ctx.set_param("cluster.max_nnz", 0)
     fast = ctx.cluster(cr, left, right, strand)
-    try:
-        ctx.set_param("cluster.generic", 1)
+    with ctx.params({"cluster.generic": 1}):
         generic = ctx.cluster(cr, left, right, strand)
-    finally:
-        ctx.set_param("cluster.generic", 0)
     for name, g, w in zip(("row_of", "row_ptr", "col"), fast, generic):
         if not np.array_equal(g, w):
             return f"cluster_big {name}: fast path != generic path (n={first.size} kind={kind} n_chrom={n_chrom} span={span})"
@@ -300,15 +295,10 @@ def gen_bh(ctx, rng):
         p[:] = np.sort(p, axis=0)[::-1] if rng.random() < 0.5 else np.sort(p, axis=0)
     wg, mean, fused = int(rng.choice([256, 256, 512, 1024])), int(rng.choice([0, 0, 100, 700, 2500])), int(rng.integers(0, 2))
     big_wg = int(rng.choice([256, 512]))
-    try:
-        ctx.set_param("bh.columns_path", 1)
+    with ctx.params({"bh.columns_path": 1}):
         d = ctx.to_device(p); ctx.bh_columns_dev(d); generic = d.to_host()
-        ctx.set_param("bh.columns_path", 2)
-        ctx.set_param("bh.wg", wg); ctx.set_param("bh.mean", mean); ctx.set_param("bh.fused_count", fused); ctx.set_param("bh.big_wg", big_wg)
+    with ctx.params({"bh.columns_path": 2, "bh.wg": wg, "bh.mean": mean, "bh.fused_count": fused, "bh.big_wg": big_wg}):
         d = ctx.to_device(p); ctx.bh_columns_dev(d); fast = d.to_host()
-    finally:
-        ctx.set_param("bh.columns_path", 0)
-        ctx.set_param("bh.wg", 256); ctx.set_param("bh.mean", 0); ctx.set_param("bh.fused_count", 1); ctx.set_param("bh.big_wg", 512)
     if not np.array_equal(generic, fast, equal_nan=True):
         return f"bh columns: sample-sort path != generic path (n={n} cols={cols} kind={kind} wg={wg} mean={mean} fused={fused} big_wg={big_wg})"
     if kind == 8:
@@ -341,21 +331,17 @@ def gen_bh_vector(ctx, rng):
         p[n // 3: n // 2] = 5e-324
     frac = float(rng.choice([1.0, 0.95, 0.5, 0.02]))
     tested = (rng.random(n) < frac).astype(np.uint8)
-    cap = int(rng.choice([5632, 5632, 5632, 3072]))           # a small capacity sends some buckets through the slow path
+    cap = ctx.get_param("bhv.cap")
+    cap = int(rng.choice([cap, cap, cap, 3072]))              # a small capacity sends some buckets through the slow path
     out = {}
-    try:
-        for path in (1, 2):
-            ctx.set_param("bh.vector_path", path)
-            ctx.set_param("bhv.cap", cap)
+    for path in (1, 2):
+        with ctx.params({"bh.vector_path": path, "bhv.cap": cap}):
             d_p, d_q = ctx.to_device(p), ctx.empty(n, np.float64)
             ctx.bh_dev(d_p, d_q)
             a = d_q.to_host()
             d_t = ctx.to_device(tested)
             ctx.bh_masked_dev(d_p, d_t, d_q)
             out[path] = (a, d_q.to_host())
-    finally:
-        ctx.set_param("bh.vector_path", 0)
-        ctx.set_param("bhv.cap", 5632)
     for k, what in ((0, "plain"), (1, "masked")):
         if not np.array_equal(out[1][k].view(np.uint64), out[2][k].view(np.uint64)):
             return f"bh vector ({what}): sample-sort path != radix path (n={n} kind={kind} tested={frac} cap={cap})"

@@ -56,6 +56,78 @@ def test_missing_library_message(monkeypatch, tmp_path):
         _ffi.load()
 
 
+# ----------------------------------------------------------------------------------- parameters
+# the knobs sdice_set_param knew when the table was introduced: none of them may vanish unnoticed
+KNOBS = """ps.lds_bytes ps.tile_rows ps.threads ps.chunk_cols ps.xcd_remap ps.halo_rows cluster.generic cluster.legacy
+    cluster.lds_cap cluster.ablate cluster.nb_grid cluster.sample_sort cluster.bucket_mean cluster.spb cluster.max_nnz
+    ps.ablate ps.quantize3 ps.prio ps.nt_loads ps.gen1 ps.use_reach sort.rounds ranksum.variant ranksum.ablate
+    fisher.table_max fisher.refill fisher.unroll fisher.count_steps bh.columns_path bh.vector_path bhv.mean bhv.cap
+    bh.reg_cap bh.mean bh.rows_per_block bh.fused_count bh.finish_cols bh.finish_nt bh.wg bh.big_wg bh.spb""".split()
+
+
+def test_param_table_is_the_documented_one():
+    """sdice_param_info enumerates the library's table without a context: unique names, every knob of KNOBS still there,
+    and INTEGRATION.md's table lists exactly these names with exactly these defaults"""
+    import ctypes
+    from splicedice_amd import _ffi
+    lib = _ffi.load()
+    table = []
+    name, dflt = ctypes.c_char_p(), ctypes.c_int64()
+    while lib.sdice_param_info(len(table), ctypes.byref(name), ctypes.byref(dflt)) == 0:
+        table.append((name.value.decode(), dflt.value))
+        assert len(table) < 1000
+    assert lib.sdice_param_info(len(table), None, None) < 0 and lib.sdice_param_info(-1, None, None) < 0
+    assert b"parameter table" in lib.sdice_last_error()
+    assert len(KNOBS) == 41 and len(table) >= 41
+    assert len({n for n, _ in table}) == len(table)
+    assert set(KNOBS) <= {n for n, _ in table}
+    doc = open(os.path.join(REPO, "INTEGRATION.md")).read()
+    doc = doc[doc.index("## Context parameters"):doc.index("## Build / test")]
+    rows = re.findall(r"^\| `([a-z0-9_.]+)` \| (-?\d+) \|", doc, flags=re.M)
+    assert len(rows) == len(table)
+    assert {n: int(d) for n, d in rows} == dict(table)
+
+
+class _ParamLib:
+    """stands in for the C library behind engine.Context: a value per knob and a log of the calls"""
+
+    def __init__(self, **values):
+        self.values, self.calls = values, []
+
+    def sdice_get_param(self, h, name, ref):
+        self.calls.append(("get", name.decode()))
+        ref._obj.value = self.values[name.decode()]
+        return 0
+
+    def sdice_set_param(self, h, name, value):
+        self.calls.append(("set", name.decode(), value))
+        self.values[name.decode()] = value
+        return 0
+
+
+def test_context_params_scope_restores_what_was_in_force():
+    from splicedice_amd.engine import Context
+    ctx = Context.__new__(Context)
+    ctx.h, ctx.lib = None, _ParamLib(a=1, b=2, c=3)
+    lib = ctx.lib
+    with ctx.params({"a": 10, "b": 20}):
+        assert lib.values == dict(a=10, b=20, c=3)
+    # the values in force are read before anything is set, and written back in reverse order
+    assert lib.calls == [("get", "a"), ("get", "b"), ("set", "a", 10), ("set", "b", 20), ("set", "b", 2), ("set", "a", 1)]
+    assert lib.values == dict(a=1, b=2, c=3)
+    with pytest.raises(KeyError):                      # the body raises: restored all the same
+        with ctx.params({"c": 30}):
+            assert lib.values["c"] == 30
+            raise KeyError("body")
+    assert lib.values == dict(a=1, b=2, c=3)
+    with ctx.params({"a": 5}):                         # nested: the inner scope puts the OUTER override back
+        with ctx.params({"a": 6, "c": 7}):
+            assert lib.values == dict(a=6, b=2, c=7)
+        assert lib.values == dict(a=5, b=2, c=3)
+    assert lib.values == dict(a=1, b=2, c=3)
+    assert ctx.get_param("b") == 2
+
+
 # ----------------------------------------------------------------------------------- host logic
 def _quant_args(**over):
     a = argparse.Namespace(maxLength=50000, minLength=50, minOverhang=5, drim=False, noMultimap=False,

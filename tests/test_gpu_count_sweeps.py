@@ -140,13 +140,10 @@ def test_ranksum_count_sweep(ctx, n1, n2, flavour):
     assert not want["tested"][0] and not want["tested"][-1]
     assert want["tested"][1:-1].all()
     variants = (0,) + (FORCED.get(n1, ()) if n1 == n2 else ())
-    try:
-        for variant in variants:
-            ctx.set_param("ranksum.variant", variant)
+    for variant in variants:
+        with ctx.params({"ranksum.variant": variant}):
             got = ctx.ranksum(ps, g1, g2)
             _check_ranksum(got, want)
-    finally:
-        ctx.set_param("ranksum.variant", 0)
 
 
 @gpu
@@ -313,9 +310,8 @@ def test_bh_vector_paths_bit_exact(ctx, m):
     want_masked = np.zeros(m)
     want_masked[tested != 0] = O.bh_fdr(p[tested != 0])
     supported = 16384 <= m <= 2 << 20
-    try:
-        for path in (1, 2):
-            ctx.set_param("bh.vector_path", path)
+    for path in (1, 2):
+        with ctx.params({"bh.vector_path": path}):
             d_p, d_q = ctx.to_device(p), ctx.empty(m, np.float64)
             d_t, d_neg = ctx.to_device(tested), ctx.to_device(np.where(tested != 0, p, -1.0))
             if path == 2 and not supported:
@@ -330,8 +326,6 @@ def test_bh_vector_paths_bit_exact(ctx, m):
             assert np.array_equal(d_q.to_host().view(np.uint64), want_masked.view(np.uint64)), path
             ctx.bh_masked_dev(d_neg, None, d_q)
             assert np.array_equal(d_q.to_host().view(np.uint64), want_masked.view(np.uint64)), path
-    finally:
-        ctx.set_param("bh.vector_path", 0)
 
 
 def _bh_columns_values(n, cols, rng):
@@ -350,16 +344,13 @@ def test_bh_columns_paths_bit_exact(ctx, n):
     rng = np.random.default_rng(n)
     p = _bh_columns_values(n, 3, rng)
     want = O.bh_columns(p)
-    try:
-        for path in (1, 2):
-            ctx.set_param("bh.columns_path", path)
+    for path in (1, 2):
+        with ctx.params({"bh.columns_path": path}):
             if path == 2 and n > 1 << 18:
                 with pytest.raises(SdiceError, match="columns_path"):
                     ctx.bh_columns(p)
                 continue
             assert np.array_equal(ctx.bh_columns(p).view(np.uint64), want.view(np.uint64)), path
-    finally:
-        ctx.set_param("bh.columns_path", 0)
 
 
 @gpu
@@ -372,11 +363,8 @@ def test_bh_columns_pitched_range(ctx, n, pitch, c0, cols):
     table = _bh_columns_values(n, pitch, rng)
     want = table.copy()
     want[:, c0:c0 + cols] = O.bh_columns(table[:, c0:c0 + cols])
-    try:
-        for path in (1, 2):
-            ctx.set_param("bh.columns_path", path)
+    for path in (1, 2):
+        with ctx.params({"bh.columns_path": path}):
             d = ctx.to_device(table)
             ctx.bh_columns_pitched_dev(d.offset(c0, (n * pitch - c0,)), n, cols, pitch)
             assert np.array_equal(d.to_host().view(np.uint64), want.view(np.uint64)), path
-    finally:
-        ctx.set_param("bh.columns_path", 0)

@@ -460,13 +460,8 @@ def _check_csr(got, want, what):
 @pytest.mark.parametrize("nb_grid", [0, 3])
 @pytest.mark.parametrize("name", CLUSTER_FIXTURES + ("nk256", "cmax"))
 def test_cluster_dense_vs_oracle(ctx, name, nb_grid, lds_cap):
-    ctx.set_param("cluster.nb_grid", nb_grid)
-    ctx.set_param("cluster.lds_cap", lds_cap)
-    try:
+    with ctx.params({"cluster.nb_grid": nb_grid, "cluster.lds_cap": lds_cap}):
         got = ctx.cluster(*junctions(name))
-    finally:
-        ctx.set_param("cluster.nb_grid", 0)
-        ctx.set_param("cluster.lds_cap", 0)
     _check_csr(got, oracle_csr(name), name)
 
 
@@ -536,10 +531,6 @@ def test_cluster_dev_async_fresh_context():
 
 
 # ------------------------------------------------------------------------------ GPU: PS on the device path
-_PS_KNOBS = ("ps.gen1", "ps.use_reach", "ps.quantize3", "ps.tile_rows")
-_PS_DEFAULTS = {"ps.gen1": 0, "ps.use_reach": 1, "ps.quantize3": 0, "ps.tile_rows": 0}
-
-
 @functools.lru_cache(maxsize=None)
 def _ps_want(name):
     ps, excl = ps_reference(counts(name), *oracle_csr(name)[1:])
@@ -560,26 +551,21 @@ def test_ps_dev_on_device_lists(ctx, name, gen1):
     d_counts = ctx.to_device(cnt, np.int32)
     d_excl, d_ps = ctx.empty((n, S), np.int64), ctx.empty((n, S), np.float32)
     bad = []
-    try:
-        for use_reach in (1, 0):
-            for q3 in (0, 1):
-                for tile_rows in (0, 64, 256):
-                    knobs = {"ps.gen1": gen1, "ps.use_reach": use_reach, "ps.quantize3": q3, "ps.tile_rows": tile_rows}
-                    for k, v in knobs.items():
-                        ctx.set_param(k, v)
+    for use_reach in (1, 0):
+        for q3 in (0, 1):
+            for tile_rows in (0, 64, 256):
+                knobs = {"ps.gen1": gen1, "ps.use_reach": use_reach, "ps.quantize3": q3, "ps.tile_rows": tile_rows}
+                with ctx.params(knobs):
                     d_excl.memset(0xFF)
                     d_ps.memset(0xFF)
                     ctx.ps_dev(d_counts, d_row_ptr, d_col, d_excl, d_ps)
                     ps, excl = d_ps.to_host(), d_excl.to_host()
-                    if not np.array_equal(excl, want_excl):
-                        bad.append((knobs, "excl", np.argwhere(excl != want_excl)[:4].tolist()))
-                    w = want_q if q3 else want_ps
-                    if not np.array_equal(ps, w, equal_nan=True):
-                        diff = ~((ps == w) | (np.isnan(ps) & np.isnan(w)))
-                        bad.append((knobs, "ps", np.argwhere(diff)[:4].tolist()))
-    finally:
-        for k, v in _PS_DEFAULTS.items():
-            ctx.set_param(k, v)
+                if not np.array_equal(excl, want_excl):
+                    bad.append((knobs, "excl", np.argwhere(excl != want_excl)[:4].tolist()))
+                w = want_q if q3 else want_ps
+                if not np.array_equal(ps, w, equal_nan=True):
+                    diff = ~((ps == w) | (np.isnan(ps) & np.isnan(w)))
+                    bad.append((knobs, "ps", np.argwhere(diff)[:4].tolist()))
     assert not bad, bad
 
 

@@ -65,11 +65,8 @@ def test_config5_full_5m_x_1000(ctx):
     keys = ("tested", "p", "z", "med1", "med2", "mean1", "mean2", "delta")
     try:
         _fill_repeated(d_counts, block, n, s)
-        ctx.set_param("ps.quantize3", 1)
-        try:
+        with ctx.params({"ps.quantize3": 1}):
             ctx.ps_dev(d_counts, d_rp, d_col, None, d_ps)
-        finally:
-            ctx.set_param("ps.quantize3", 0)
         g1, g2 = np.arange(0, 500, dtype=np.int32), np.arange(500, 1000, dtype=np.int32)
         d_g1, d_g2 = ctx.to_device(g1), ctx.to_device(g2)
 

@@ -175,11 +175,8 @@ def test_e2e_config5_shard_full_shape(ctx):
     for a in range(0, n, blk):
         d_counts.offset(a * s, (blk, s)).upload(block)
     d_ps = ctx.empty((n, s), np.float32)
-    ctx.set_param("ps.quantize3", 1)
-    try:
+    with ctx.params({"ps.quantize3": 1}):
         ctx.ps_dev(d_counts, d_rp, d_col, None, d_ps)
-    finally:
-        ctx.set_param("ps.quantize3", 0)
     g1, g2 = np.arange(0, 500, dtype=np.int32), np.arange(500, 1000, dtype=np.int32)
     d_g1, d_g2 = ctx.to_device(g1), ctx.to_device(g2)
     def run(a, b):

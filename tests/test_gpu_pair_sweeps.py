@@ -371,24 +371,18 @@ def test_fisher_launch_knobs(ctx, s):
     ref = PaletteRef(SWEEP)
     incl, excl, pid, pi = ref.rows(s, reps=1, seed=5, weights={"mix": MIX_WEIGHTS})
     ids = ref.pair_ids(pid, pi)
-    try:
-        for unroll in (4, 8, 12, 16, 20, 24):
-            ctx.set_param("fisher.unroll", unroll)
-            for refill in (1, 12, 63, 64):
-                ctx.set_param("fisher.refill", refill)
-                ctx.set_param("fisher.count_steps", 0)
+    for unroll in (4, 8, 12, 16, 20, 24):
+        for refill in (1, 12, 63, 64):
+            knobs = {"fisher.unroll": unroll, "fisher.refill": refill}
+            with ctx.params({**knobs, "fisher.count_steps": 0}):
                 plain = ctx.fisher_pairs(incl, excl)
-                ctx.set_param("fisher.count_steps", 1)
+            with ctx.params({**knobs, "fisher.count_steps": 1}):
                 counted = ctx.fisher_pairs(incl, excl)
                 useful, issued = ctx.fisher_step_stats()
-                what = f"fisher s={s} unroll={unroll} refill={refill}"
-                assert np.array_equal(plain.view(np.uint64), counted.view(np.uint64)), what
-                assert 0 < useful <= issued and issued % (64 * unroll) == 0, (what, useful, issued)
-                _check_fisher(ref, plain, ids, what)
-    finally:
-        ctx.set_param("fisher.unroll", 16)
-        ctx.set_param("fisher.refill", 12)
-        ctx.set_param("fisher.count_steps", 0)
+            what = f"fisher s={s} unroll={unroll} refill={refill}"
+            assert np.array_equal(plain.view(np.uint64), counted.view(np.uint64)), what
+            assert 0 < useful <= issued and issued % (64 * unroll) == 0, (what, useful, issued)
+            _check_fisher(ref, plain, ids, what)
 
 
 @gpu
@@ -401,11 +395,8 @@ def test_fisher_table_max_boundary(ctx):
     ids = ref.pair_ids(pid, pi)
     totals = ref.total[ids]
     assert ((totals == TABLE_MAX_T).any(axis=1).sum() >= 24 and (totals.max(axis=1) < TABLE_MAX_T).sum() >= 16)
-    ctx.set_param("fisher.table_max", TABLE_MAX_T)
-    try:
+    with ctx.params({"fisher.table_max": TABLE_MAX_T}):
         got = ctx.fisher_pairs(incl, excl)
-    finally:
-        ctx.set_param("fisher.table_max", 1 << 20)
     _check_fisher(ref, got, ids, f"fisher table_max={TABLE_MAX_T}")
     _check_fisher(ref, ctx.fisher_pairs(incl, excl), ids, "fisher table_max restored")
 

@@ -60,15 +60,10 @@ def test_cluster_paths_and_wide_keys(ctx, generic):
     rng.shuffle(key)
     cr, left, right, strand = key[:, 0].astype(np.int32), key[:, 1].astype(np.int32), key[:, 2].astype(np.int32), key[:, 3].astype(np.int8)
     want = O.cluster_csr(cr, left, right, strand)
-    ctx.set_param("cluster.generic", int(generic == 1))
-    ctx.set_param("cluster.legacy", int(generic == 2))
-    try:
+    with ctx.params({"cluster.generic": int(generic == 1), "cluster.legacy": int(generic == 2)}):
         got = ctx.cluster(cr, left, right, strand)
         cr2, l2, r2, s2 = synth.make_junctions(9000, 31, n_chrom=7)
         got2 = ctx.cluster(cr2, l2, r2, s2)
-    finally:
-        ctx.set_param("cluster.generic", 0)
-        ctx.set_param("cluster.legacy", 0)
     for g, w in zip(got, want):
         assert np.array_equal(g, w)
     for g, w in zip(got2, O.cluster_csr(cr2, l2, r2, s2)):
@@ -102,16 +97,10 @@ def test_cluster_fast_path_buckets(ctx, n, seed, kw, lds_cap):
     if n <= 70000:
         want = O.cluster_csr(cr, left, right, strand)
     else:                                                # the oracle's Python sweep is too slow here: radix path
-        ctx.set_param("cluster.legacy", 1)
-        try:
+        with ctx.params({"cluster.legacy": 1}):
             want = ctx.cluster(cr, left, right, strand)
-        finally:
-            ctx.set_param("cluster.legacy", 0)
-    ctx.set_param("cluster.lds_cap", lds_cap)
-    try:
+    with ctx.params({"cluster.lds_cap": lds_cap}):
         got = ctx.cluster(cr, left, right, strand)
-    finally:
-        ctx.set_param("cluster.lds_cap", 0)
     for g, w in zip(got, want):
         assert np.array_equal(g, w)
 
@@ -225,9 +214,8 @@ def test_cluster_lookback_tile_loop_and_give_up(ctx):
     want = ctx.cluster(cr, left, right, strand)
     d = [ctx.to_device(x) for x in (cr, left, right, strand)]
     d_row_of, d_row_ptr = ctx.empty(n, np.int32), ctx.empty(n + 1, np.int64)
-    try:
-        for grid in (3, 8):
-            ctx.set_param("cluster.nb_grid", grid)
+    for grid in (3, 8):
+        with ctx.params({"cluster.nb_grid": grid}):
             got = ctx.cluster(cr, left, right, strand)
             assert all(np.array_equal(g, w) for g, w in zip(got, want)), grid
             d_row_ptr.zero()
@@ -235,16 +223,12 @@ def test_cluster_lookback_tile_loop_and_give_up(ctx):
             nnz, _ = ctx.cluster_status()
             assert nnz == want[2].size and np.array_equal(d_row_ptr.to_host(), want[1])
             assert np.array_equal(d_col.offset(0, (nnz,)).to_host(), want[2])
-        ctx.set_param("cluster.nb_grid", 0)
-        ctx.set_param("cluster.ablate", 256)
+    with ctx.params({"cluster.ablate": 256}):
         got = ctx.cluster(cr, left, right, strand)                                    # synchronous: generic path takes over
         assert all(np.array_equal(g, w) for g, w in zip(got, want))
         ctx.cluster_dev(*d, d_row_of, d_row_ptr, sync=False)
         with pytest.raises(SdiceError, match="look-back"):
             ctx.sync()
-    finally:
-        ctx.set_param("cluster.nb_grid", 0)
-        ctx.set_param("cluster.ablate", 0)
     got = ctx.cluster(cr, left, right, strand)
     assert all(np.array_equal(g, w) for g, w in zip(got, want))
 
@@ -259,15 +243,13 @@ def test_cluster_list_size_is_bounded(ctx):
     assert want[2].size > 200_000
     fresh = type(ctx)(0)
     try:
-        fresh.set_param("cluster.max_nnz", 100_000)
-        with pytest.raises(SdiceError, match=r"neighbour list.*%d entries" % want[2].size):
-            fresh.cluster(crd, ld, rd, sd)
-        fresh.set_param("cluster.generic", 1)
-        with pytest.raises(SdiceError, match=r"neighbour list.*%d entries" % want[2].size):
-            fresh.cluster(crd, ld, rd, sd)
-        fresh.set_param("cluster.generic", 0)
-        fresh.set_param("cluster.max_nnz", 0)                     # automatic: what HBM and host memory hold
-        got = fresh.cluster(crd, ld, rd, sd)
+        with fresh.params({"cluster.max_nnz": 100_000}):
+            with pytest.raises(SdiceError, match=r"neighbour list.*%d entries" % want[2].size):
+                fresh.cluster(crd, ld, rd, sd)
+            with fresh.params({"cluster.generic": 1}):
+                with pytest.raises(SdiceError, match=r"neighbour list.*%d entries" % want[2].size):
+                    fresh.cluster(crd, ld, rd, sd)
+        got = fresh.cluster(crd, ld, rd, sd)                      # automatic: what HBM and host memory hold
         assert np.array_equal(got[2], want[2])
     finally:
         fresh.close()
@@ -323,23 +305,16 @@ def test_ps_kernel_generations_agree(ctx, n, s):
     d_counts = ctx.to_device(counts)
     d_ps, d_excl = ctx.empty((n, s), np.float32), ctx.empty((n, s), np.int64)
     refs = {}
-    try:
-        for kern, reach, q3 in ((1, 1, 0), (0, 1, 0), (0, 0, 0), (1, 1, 1), (0, 1, 1), (0, 0, 1)):
-            ctx.set_param("ps.gen1", kern)
-            ctx.set_param("ps.use_reach", reach)
-            ctx.set_param("ps.quantize3", q3)
+    for kern, reach, q3 in ((1, 1, 0), (0, 1, 0), (0, 0, 0), (1, 1, 1), (0, 1, 1), (0, 0, 1)):
+        with ctx.params({"ps.gen1": kern, "ps.use_reach": reach, "ps.quantize3": q3}):
             d_ps.memset(0xff)
             d_excl.memset(0xff)
             ctx.ps_dev(d_counts, d_rp, d_col, d_excl, d_ps)
             ctx.sync()
             got = (d_ps.to_host().view(np.uint32), d_excl.to_host())
-            if q3 not in refs:
-                refs[q3] = got
-            assert np.array_equal(got[0], refs[q3][0]) and np.array_equal(got[1], refs[q3][1]), (kern, reach, q3)
-    finally:
-        ctx.set_param("ps.gen1", 0)
-        ctx.set_param("ps.use_reach", 1)
-        ctx.set_param("ps.quantize3", 0)
+        if q3 not in refs:
+            refs[q3] = got
+        assert np.array_equal(got[0], refs[q3][0]) and np.array_equal(got[1], refs[q3][1]), (kern, reach, q3)
     ref = refs[0]
     row_ptr, col = d_rp.to_host(), d_col.to_host()
     want_ps, want_excl = O.calculate_psi_vectorised(counts[:3000], row_ptr[:3001], np.minimum(col[: int(row_ptr[3000])], 2999))
@@ -361,17 +336,8 @@ def test_ps_launch_shapes(ctx, lds, threads, tile_rows, halo, s):
     _, row_ptr, col = O.cluster_csr(cr, left, right, strand)
     counts = synth.make_counts(n, s, 22)
     want_ps, want_excl = O.calculate_psi_vectorised(counts, row_ptr, col)
-    try:
-        ctx.set_param("ps.lds_bytes", lds)
-        ctx.set_param("ps.threads", threads)
-        ctx.set_param("ps.tile_rows", tile_rows)
-        ctx.set_param("ps.halo_rows", halo)
+    with ctx.params({"ps.lds_bytes": lds, "ps.threads": threads, "ps.tile_rows": tile_rows, "ps.halo_rows": halo}):
         ps, excl = ctx.ps(counts, row_ptr, col, want_excl=True)
-    finally:
-        ctx.set_param("ps.lds_bytes", 81920)
-        ctx.set_param("ps.threads", 1024)
-        ctx.set_param("ps.tile_rows", 0)
-        ctx.set_param("ps.halo_rows", -1)
     assert np.array_equal(excl, want_excl)
     assert np.array_equal(ps, want_ps, equal_nan=True)
 
@@ -419,11 +385,8 @@ def test_ps_fused_quantise(ctx, n, s, big):
         counts = counts * 100000 + 7          # sums beyond 2^24: the float64 path
     want = O.quantize3_fast(O.calculate_psi_vectorised(counts, row_ptr, col)[0])
     two_pass = ctx.quantize3(ctx.ps(counts, row_ptr, col))
-    ctx.set_param("ps.quantize3", 1)
-    try:
+    with ctx.params({"ps.quantize3": 1}):
         fused = ctx.ps(counts, row_ptr, col)
-    finally:
-        ctx.set_param("ps.quantize3", 0)
     assert np.array_equal(two_pass, want, equal_nan=True)
     assert np.array_equal(fused, want, equal_nan=True)
 
@@ -452,11 +415,8 @@ def test_ps_fused_quantise_on_rounding_boundaries(ctx):
     x1000 = psi[np.isfinite(psi)].astype(np.float64) * 1000.0
     assert (np.abs(x1000 - np.floor(x1000) - 0.5) == 0).sum() > 50            # exact ties are in the fixture
     two_pass = ctx.quantize3(ctx.ps(counts, row_ptr, col))
-    ctx.set_param("ps.quantize3", 1)
-    try:
+    with ctx.params({"ps.quantize3": 1}):
         fused = ctx.ps(counts, row_ptr, col)
-    finally:
-        ctx.set_param("ps.quantize3", 0)
     assert np.array_equal(two_pass, want, equal_nan=True)
     assert np.array_equal(fused, want, equal_nan=True)
 
@@ -546,11 +506,8 @@ def test_ranksum_kat(ctx, golden_dir):
         x, y = np.float32(c["x"]), np.float32(c["y"])
         row = np.concatenate([x, y])[None, :]
         for variant in ((0, 2, 3, 4) if max(len(x), len(y)) <= 64 else (2, 3)):
-            ctx.set_param("ranksum.variant", variant)
-            try:
+            with ctx.params({"ranksum.variant": variant}):
                 r = ctx.ranksum(row, np.arange(len(x)), np.arange(len(x), len(x) + len(y)))
-            finally:
-                ctx.set_param("ranksum.variant", 0)
             assert r["tested"][0] == 1
             assert r["z"][0] == c["z"]
             assert abs(r["p"][0] - c["p"]) <= P_RTOL_TIGHT * c["p"]
@@ -576,11 +533,8 @@ def test_ranksum_vs_oracle(ctx, n1, n2, s, variant):
     g1 = np.sort(cols[:n1])        # table order (compareSampleSets.py:96-102)
     g2 = np.sort(cols[n1:n1 + n2])
     want = O.compare_rows(ps, g1, g2)
-    ctx.set_param("ranksum.variant", variant)
-    try:
+    with ctx.params({"ranksum.variant": variant}):
         got = ctx.ranksum(ps, g1, g2)
-    finally:
-        ctx.set_param("ranksum.variant", 0)
     _check_ranksum(got, want)
 
 
@@ -597,11 +551,8 @@ def test_fisher_kat(ctx, golden_dir):
     want = np.array([p for _, p in kats])
     got = ctx.fisher_tables(tables)
     np.testing.assert_allclose(got, want, rtol=P_RTOL_TIGHT, atol=0)
-    ctx.set_param("fisher.table_max", 64)      # force the device-lgamma path for large margins
-    try:
+    with ctx.params({"fisher.table_max": 64}):      # force the device-lgamma path for large margins
         got2 = ctx.fisher_tables(tables)
-    finally:
-        ctx.set_param("fisher.table_max", 1 << 20)
     np.testing.assert_allclose(got2, want, rtol=P_RTOL_TIGHT, atol=0)
 
 
@@ -615,11 +566,8 @@ def test_fisher_pairs_vs_scipy(ctx, n, s, mean):
     np.testing.assert_allclose(got, want, rtol=P_RTOL_TIGHT, atol=0)
     # a log-factorial table of 64 entries: tables with a larger total leave the pair kernel as markers and are finished
     # by fisher_beyond_table_kernel (rows with such tables only; here some, all or -- margins of zero -- none of a row's pairs)
-    ctx.set_param("fisher.table_max", 64)
-    try:
+    with ctx.params({"fisher.table_max": 64}):
         got2 = ctx.fisher_pairs(incl, excl)
-    finally:
-        ctx.set_param("fisher.table_max", 1 << 20)
     assert (got2 >= 0).all()
     np.testing.assert_allclose(got2, want, rtol=P_RTOL_TIGHT, atol=0)
 
@@ -649,12 +597,9 @@ def test_fisher_step_counts(ctx):
     incl = synth.make_counts(50, 24, 5, mean=40)
     excl = synth.make_counts(50, 24, 6, mean=160).astype(np.int64)
     plain = ctx.fisher_pairs(incl, excl)
-    ctx.set_param("fisher.count_steps", 1)
-    try:
+    with ctx.params({"fisher.count_steps": 1}):
         counted = ctx.fisher_pairs(incl, excl)
         useful, issued = ctx.fisher_step_stats()
-    finally:
-        ctx.set_param("fisher.count_steps", 0)
     assert np.array_equal(plain, counted)
     a = incl[:, :, None].astype(np.int64); b = incl[:, None, :].astype(np.int64)
     c = excl[:, :, None]; d = excl[:, None, :]
@@ -825,47 +770,35 @@ def test_bh_columns_samplesort_vs_generic(ctx, n, cols):
         # a crowd with a long tail around an ordinary value, and a stray neighbour inside the same bin
         crowd = rng.random(n) < 0.3
         p[crowd, 6] = 0.3 + (rng.standard_cauchy(int(crowd.sum())) * 40).astype(np.int64).clip(-10 ** 7, 10 ** 7) * 2.0 ** -54
-    try:
-        ctx.set_param("bh.columns_path", 1)
+    with ctx.params({"bh.columns_path": 1}):
         d = ctx.to_device(p)
         ctx.bh_columns_dev(d)
         generic = d.to_host()
-        ctx.set_param("bh.columns_path", 2)
+    with ctx.params({"bh.columns_path": 2}):
         d = ctx.to_device(p)
         ctx.bh_columns_dev(d)
         fast = d.to_host()
         assert np.array_equal(generic, fast, equal_nan=True)
-        for wg, mean in ((256, 100), (256, 900), (512, 0), (1024, 0), (256, 3000)):     # threads of a bucket workgroup (4 values
-            ctx.set_param("bh.wg", wg)                                        # each), mean bucket (0: half its capacity); 900 and
-            ctx.set_param("bh.mean", mean)                                    # 3000 fill the second kernel's list
-            d = ctx.to_device(p)
-            ctx.bh_columns_dev(d)
-            assert np.array_equal(generic, d.to_host(), equal_nan=True), (wg, mean)
-        ctx.set_param("bh.wg", 256)
-        ctx.set_param("bh.mean", 900)
-        ctx.set_param("bh.big_wg", 256)                                       # the listed buckets at 256 threads x 8 values
-        d = ctx.to_device(p)
-        ctx.bh_columns_dev(d)
-        assert np.array_equal(generic, d.to_host(), equal_nan=True)
-        ctx.set_param("bh.big_wg", 512)
-        ctx.set_param("bh.mean", 0)
-        ctx.set_param("bh.fused_count", 0)                                    # transpose and count as two kernels
-        d = ctx.to_device(p)
-        ctx.bh_columns_dev(d)
-        assert np.array_equal(generic, d.to_host(), equal_nan=True)
-        ctx.set_param("bh.fused_count", 1)
-        if n > 2000:
-            ctx.set_param("bh.reg_cap", 64)                                   # most buckets through the in-HBM path
+        # threads of a bucket workgroup (4 values each), mean bucket (0: half its capacity); 900 and 3000 fill the second
+        # kernel's list
+        for wg, mean in ((256, 100), (256, 900), (512, 0), (1024, 0), (256, 3000)):
+            with ctx.params({"bh.wg": wg, "bh.mean": mean}):
+                d = ctx.to_device(p)
+                ctx.bh_columns_dev(d)
+                assert np.array_equal(generic, d.to_host(), equal_nan=True), (wg, mean)
+        with ctx.params({"bh.wg": 256, "bh.mean": 900, "bh.big_wg": 256}):   # the listed buckets at 256 threads x 8 values
             d = ctx.to_device(p)
             ctx.bh_columns_dev(d)
             assert np.array_equal(generic, d.to_host(), equal_nan=True)
-    finally:
-        ctx.set_param("bh.columns_path", 0)
-        ctx.set_param("bh.reg_cap", 2048)
-        ctx.set_param("bh.mean", 0)
-        ctx.set_param("bh.wg", 256)
-        ctx.set_param("bh.big_wg", 512)
-        ctx.set_param("bh.fused_count", 1)
+        with ctx.params({"bh.fused_count": 0}):                               # transpose and count as two kernels
+            d = ctx.to_device(p)
+            ctx.bh_columns_dev(d)
+            assert np.array_equal(generic, d.to_host(), equal_nan=True)
+        if n > 2000:
+            with ctx.params({"bh.reg_cap": 64}):                              # most buckets through the in-HBM path
+                d = ctx.to_device(p)
+                ctx.bh_columns_dev(d)
+                assert np.array_equal(generic, d.to_host(), equal_nan=True)
     ok = ~np.isnan(p).any(axis=0)
     np.testing.assert_allclose(fast[:, ok], O.bh_columns(p[:, ok]), rtol=1e-14, atol=0)
 
@@ -922,11 +855,8 @@ def test_ranksum_fuzz_shapes(ctx):
         big = max(n1, n2)
         variants = [0, 2] + ([1, 4] if big <= 64 else []) + ([3, 5] if big <= 1024 else [])
         for variant in variants:
-            ctx.set_param("ranksum.variant", variant)
-            try:
+            with ctx.params({"ranksum.variant": variant}):
                 got = ctx.ranksum(ps, g1, g2)
-            finally:
-                ctx.set_param("ranksum.variant", 0)
             _check_ranksum(got, want)
 
 
@@ -1042,52 +972,47 @@ def test_bh_vector_samplesort_vs_radix(ctx, n):
     p[6000:6005] = [0.0, 5e-324, 1e-300, 1.0, 0.5]
     p = p[rng.permutation(n)]
     out = {}
-    try:
-        for path in (1, 2):
-            ctx.set_param("bh.vector_path", path)
+    for path in (1, 2):
+        with ctx.params({"bh.vector_path": path}):
             d_p, d_q = ctx.to_device(p), ctx.empty(n, np.float64)
             ctx.bh_dev(d_p, d_q)
             out[path] = d_q.to_host()
-        assert np.array_equal(out[1].view(np.uint64), out[2].view(np.uint64))
-        if n <= 100_000:
-            np.testing.assert_allclose(out[2], O.bh_fdr(p), rtol=1e-14, atol=0)
-        # NaN sorts behind every number in both paths
-        pn = p.copy()
-        pn[rng.integers(0, n, size=3)] = np.nan
-        for path in (1, 2):
-            ctx.set_param("bh.vector_path", path)
+    assert np.array_equal(out[1].view(np.uint64), out[2].view(np.uint64))
+    if n <= 100_000:
+        np.testing.assert_allclose(out[2], O.bh_fdr(p), rtol=1e-14, atol=0)
+    # NaN sorts behind every number in both paths
+    pn = p.copy()
+    pn[rng.integers(0, n, size=3)] = np.nan
+    for path in (1, 2):
+        with ctx.params({"bh.vector_path": path}):
             d_p, d_q = ctx.to_device(pn), ctx.empty(n, np.float64)
             ctx.bh_dev(d_p, d_q)
             out[path] = d_q.to_host()
-        assert np.array_equal(out[1].view(np.uint64), out[2].view(np.uint64))
-        # masked: a third of the entries absent
-        tested = (rng.random(n) < 0.67).astype(np.uint8)
-        for path in (1, 2):
-            ctx.set_param("bh.vector_path", path)
+    assert np.array_equal(out[1].view(np.uint64), out[2].view(np.uint64))
+    # masked: a third of the entries absent
+    tested = (rng.random(n) < 0.67).astype(np.uint8)
+    for path in (1, 2):
+        with ctx.params({"bh.vector_path": path}):
             d_p, d_t, d_q = ctx.to_device(p), ctx.to_device(tested), ctx.empty(n, np.float64)
             ctx.bh_masked_dev(d_p, d_t, d_q)
             out[path] = d_q.to_host()
-        assert np.array_equal(out[1].view(np.uint64), out[2].view(np.uint64))
-        assert not out[2][tested == 0].any()
-        if n <= 100_000:
-            np.testing.assert_allclose(out[2][tested != 0], O.bh_fdr(p[tested != 0]), rtol=1e-14, atol=0)
-        pm = np.where(tested != 0, p, -1.0)                      # absent = negative p, no flag array
-        for path in (1, 2):
-            ctx.set_param("bh.vector_path", path)
+    assert np.array_equal(out[1].view(np.uint64), out[2].view(np.uint64))
+    assert not out[2][tested == 0].any()
+    if n <= 100_000:
+        np.testing.assert_allclose(out[2][tested != 0], O.bh_fdr(p[tested != 0]), rtol=1e-14, atol=0)
+    pm = np.where(tested != 0, p, -1.0)                      # absent = negative p, no flag array
+    for path in (1, 2):
+        with ctx.params({"bh.vector_path": path}):
             d_p, d_q = ctx.to_device(pm), ctx.empty(n, np.float64)
             ctx.bh_masked_dev(d_p, None, d_q)
             out[path] = d_q.to_host()
-        assert np.array_equal(out[1].view(np.uint64), out[2].view(np.uint64))
-        if n <= 100_000:
-            # buckets beyond the LDS capacity of a bucket workgroup (forced: every bucket) take the in-HBM network
-            ctx.set_param("bh.vector_path", 2)
-            ctx.set_param("bhv.cap", 512)
+    assert np.array_equal(out[1].view(np.uint64), out[2].view(np.uint64))
+    if n <= 100_000:
+        # buckets beyond the LDS capacity of a bucket workgroup (forced: every bucket) take the in-HBM network
+        with ctx.params({"bh.vector_path": 2, "bhv.cap": 512}):
             d_p, d_q = ctx.to_device(pm), ctx.empty(n, np.float64)
             ctx.bh_masked_dev(d_p, None, d_q)
             assert np.array_equal(out[1].view(np.uint64), d_q.to_host().view(np.uint64))
-    finally:
-        ctx.set_param("bh.vector_path", 0)
-        ctx.set_param("bhv.cap", 5632)
 
 
 def test_bh_high_word_runs(ctx):
@@ -1150,11 +1075,8 @@ def test_ranksum_counting_and_sorting_rows_mixed(ctx):
         g1, g2 = np.arange(n1, dtype=np.int32), np.arange(n1, s, dtype=np.int32)
         want = O.compare_rows(ps, g1, g2)
         for variant in (0, 3, 5):
-            ctx.set_param("ranksum.variant", variant)
-            try:
+            with ctx.params({"ranksum.variant": variant}):
                 got = ctx.ranksum(ps, g1, g2)
-            finally:
-                ctx.set_param("ranksum.variant", 0)
             _check_ranksum(got, want)
 
 

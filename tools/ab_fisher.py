@@ -7,7 +7,6 @@ from splicedice_amd import synth
 from splicedice_amd.engine import Context
 n, s = int(sys.argv[1]), int(sys.argv[2])
 cfgs = sys.argv[3:] or [""]
-DEFAULTS = {"fisher.refill": 12, "fisher.unroll": 16, "fisher.count_steps": 0}
 ctx = Context(0)
 junc = synth.make_junctions(n, 4)
 counts_in = synth.make_counts(n, s, 40)
@@ -21,18 +20,15 @@ ctx.ps_dev(d_counts, d_rp, d_col, d_excl, None)
 ref = None
 for rep in range(2):
     for c in cfgs:
-        kv = [x.split("=") for x in c.split(",") if x]
-        for k, v in kv:
-            ctx.set_param(k, int(v))
-        ms = []
-        for it in range(3):
-            ctx.sync(); ctx.timer_start(); ctx.fisher_pairs_dev(d_counts, d_excl, d_p); ms.append(ctx.timer_stop())
-        extra = ""
-        if any(k == "fisher.count_steps" and int(v) for k, v in kv):
-            u, t = ctx.fisher_step_stats()
-            extra = f"  useful lane-steps {u:.3e} of {t:.3e} issued = {u / max(t, 1):.3f}; {u / (n * pairs):.1f} per pair"
-        for k, v in kv:
-            ctx.set_param(k, DEFAULTS[k])
+        kv = {k: int(v) for k, v in (x.split("=") for x in c.split(",") if x)}
+        with ctx.params(kv):
+            ms = []
+            for it in range(3):
+                ctx.sync(); ctx.timer_start(); ctx.fisher_pairs_dev(d_counts, d_excl, d_p); ms.append(ctx.timer_stop())
+            extra = ""
+            if kv.get("fisher.count_steps"):
+                u, t = ctx.fisher_step_stats()
+                extra = f"  useful lane-steps {u:.3e} of {t:.3e} issued = {u / max(t, 1):.3f}; {u / (n * pairs):.1f} per pair"
         got = d_p.offset(0, (4, pairs)).to_host()
         if ref is None:
             ref = got

@@ -25,4 +25,3 @@ for rep in range(3):
             ctx.ranksum_dev(d_ps, g1, g2, out)
         ms = ctx.timer_stop() / 20
         print(f"rep {rep} variant {variant} ({name}): {ms:.4f} ms per 1M rows (whole call incl. finish kernel)", flush=True)
-ctx.set_param("ranksum.variant", 0)

@@ -30,4 +30,3 @@ for rep in range(3):
         for _ in range(10):
             ctx.ranksum_dev(d_ps, g1, g2, out)
         print(f"rep {rep} ranksum.ablate={abl}: {ctx.timer_stop() / 10:.4f} ms per {n} rows (whole call)", flush=True)
-ctx.set_param("ranksum.ablate", 0)

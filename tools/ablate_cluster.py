@@ -45,5 +45,3 @@ for m in masks:
         pass
     rep = {k: round(v[1] / 5 * 1000, 1) for k, v in ctx.prof_report().items()}
     print(tag, "ablate", m, "async %.3f ms;" % wall, json.dumps(rep), "sum %.1f us" % sum(rep.values()), flush=True)
-ctx.set_param("cluster.ablate", 0)
-ctx.set_param("cluster.sample_sort", 1)

@@ -42,23 +42,19 @@ else:
         d_src.offset(a * cols, (b - a, cols)).upload(blk)
 d = ctx.empty((n, cols), np.float64)
 for c in cfgs:
-    kv = [x.split("=") for x in c.split(",") if x]
-    for k, v in kv:
-        ctx.set_param(k, int(v))
-    for it in range(2):
-        ctx.copy2d_dev(d.ptr, cols * 8, d_src.ptr, cols * 8, cols * 8, n)
-        ctx.bh_columns_dev(d)
-    ctx.sync()
-    ctx.prof_enable(1)
-    ctx.prof_reset()
-    reps = 3
-    for it in range(reps):
-        ctx.copy2d_dev(d.ptr, cols * 8, d_src.ptr, cols * 8, cols * 8, n)
-        ctx.bh_columns_dev(d)
-    ctx.sync()
-    rep = ctx.prof_report()
-    ctx.prof_enable(0)
-    for k, v in kv:
-        ctx.set_param(k, {"bh.reg_cap": 2048, "bh.mean": 0, "bh.wg": 256, "bh.big_wg": 512, "bh.spb": 8, "bh.fused_count": 1, "bh.rows_per_block": 2048, "bh.finish_cols": 16}.get(k, 0))
+    with ctx.params({k: int(v) for k, v in (x.split("=") for x in c.split(",") if x)}):
+        for it in range(2):
+            ctx.copy2d_dev(d.ptr, cols * 8, d_src.ptr, cols * 8, cols * 8, n)
+            ctx.bh_columns_dev(d)
+        ctx.sync()
+        ctx.prof_enable(1)
+        ctx.prof_reset()
+        reps = 3
+        for it in range(reps):
+            ctx.copy2d_dev(d.ptr, cols * 8, d_src.ptr, cols * 8, cols * 8, n)
+            ctx.bh_columns_dev(d)
+        ctx.sync()
+        rep = ctx.prof_report()
+        ctx.prof_enable(0)
     tot = sum(ms for _, ms in rep.values()) / reps
     print(f"[{c}] total {tot:.3f} ms: " + ", ".join(f"{name} {ms / reps:.3f}" for name, (cnt, ms) in sorted(rep.items(), key=lambda kv: -kv[1][1])), flush=True)
