@@ -189,6 +189,30 @@ int sdice_chi2_pairs(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* incl,
 int sdice_chi2_pairs_dev(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* d_incl,
                          const int64_t* d_excl, double* d_p, int64_t* d_n_bad /* device */);
 
+/* ---- pairwise over a chosen list of sample pairs: the loops above (pairwise_fisher.py:142-147, :164-179) for the m
+ *      pairs the caller names instead of all s(s-1)/2 -- matched tumour/normal, treated x control, each sample against
+ *      one reference (no reference counterpart: pairwise_fisher.py always builds every pair).
+ *  pairs[m,2] int32: column indices (i, j) into the count table; any order, i > j allowed (the 2x2 table is then
+ *  [[incl_i, incl_j],[excl_i, excl_j]] with its columns in that order, as the reference would compute it on a table
+ *  with its sample columns swapped), the same pair more than once allowed; i == j or an index outside [0, s) is
+ *  SDICE_ERR_ARG.  1 <= m <= 33 550 336 (the pair count of s = 8192; m = 0 is a no-op), s <= 8192.
+ *  p[n,m] float64 row-major, column q = pair q of the list; n_bad counts the listed tables only.
+ *  The list (i, j) = (0,1),(0,2)...(s-2,s-1) gives bit for bit what sdice_fisher_pairs / sdice_chi2_pairs give. */
+int sdice_fisher_pair_list(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* incl, const int64_t* excl,
+                           int64_t m, const int32_t* pairs, double* p);
+int sdice_chi2_pair_list(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* incl, const int64_t* excl,
+                         int64_t m, const int32_t* pairs, double* p, int64_t* n_bad);
+/* Device forms: the list lives on the device as a packed table of m uint32 (i << 16 | j), written ONCE by
+ * sdice_pair_list_pack_dev -- which validates the host list pairs[m,2] against s as above and copies the table into
+ * d_tab, a buffer of m * 4 bytes the caller owns (sdice_dmalloc); synchronous -- and then read by any number of
+ * asynchronous calls.  The _dev calls trust d_tab: hand them nothing but what sdice_pair_list_pack_dev wrote for the
+ * same s. */
+int sdice_pair_list_pack_dev(sdice_ctx* ctx, int32_t s, int64_t m, const int32_t* pairs /* host */, uint32_t* d_tab);
+int sdice_fisher_pair_list_dev(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* d_incl, const int64_t* d_excl,
+                               int64_t m, const uint32_t* d_tab, double* d_p);
+int sdice_chi2_pair_list_dev(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* d_incl, const int64_t* d_excl,
+                             int64_t m, const uint32_t* d_tab, double* d_p, int64_t* d_n_bad /* device */);
+
 /* ---- Benjamini-Hochberg: replaces statsmodels multipletests(p, method="fdr_bh")[1]
  *      (compareSampleSets.py:235; pairwise_fisher.py:185,190). */
 int sdice_bh(sdice_ctx* ctx, int64_t m, const double* p, double* q);

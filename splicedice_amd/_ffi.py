@@ -56,6 +56,11 @@ SIGNATURES = {
     "sdice_fisher_step_stats": [ctxp, vp, vp],
     "sdice_chi2_pairs": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, c_i64p],
     "sdice_chi2_pairs_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, vp],
+    "sdice_fisher_pair_list": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int64, vp, vp],
+    "sdice_chi2_pair_list": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int64, vp, vp, c_i64p],
+    "sdice_pair_list_pack_dev": [ctxp, C.c_int32, C.c_int64, vp, vp],
+    "sdice_fisher_pair_list_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int64, vp, vp],
+    "sdice_chi2_pair_list_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int64, vp, vp, vp],
     "sdice_bh": [ctxp, C.c_int64, vp, vp],
     "sdice_bh_dev": [ctxp, C.c_int64, vp, vp],
     "sdice_bh_masked_dev": [ctxp, C.c_int64, vp, vp, vp],

@@ -165,6 +165,12 @@ class HostStaging {
 // col entry is in [0, n_rows).  Errors are prefixed with `who`.
 int sd_check_csr(const char* who, int64_t n_out, int64_t n_rows, const int64_t* row_ptr, const int32_t* col);
 
+// Pair lists of the pairwise kernels: a column index takes 16 bits of a packed table entry (s <= 8192) and the pair kernel
+// counts pairs in an int below 2^25 -- a list may be as long as every pair of 8192 samples.  sd_check_pair_list: every
+// (i, j) of pairs[m][2] lies in [0, s) and i != j; errors are prefixed with `who`.
+constexpr int64_t SD_MAX_PAIRS = (int64_t)8192 * 8191 / 2;
+int sd_check_pair_list(const char* who, int32_t s, int64_t m, const int32_t* pairs);
+
 // status of an asynchronous sdice_cluster_dev (synchronises when one is pending)
 int sd_cluster_resolve(sdice_ctx* ctx);
 // SDICE_ERR_NOMEM (message naming nnz) when a neighbour list of nnz entries exceeds param cluster.max_nnz or, when that

@@ -242,12 +242,11 @@ __device__ __forceinline__ bool pmf_block(int s, double* __restrict__ out, const
 
 // the junctions flagged by the pair kernel: p = pmf(a) * sum with lgamma for the pairs that carry a negative sum
 __global__ void __launch_bounds__(256) fisher_beyond_table_kernel(const int32_t* __restrict__ incl, const int64_t* __restrict__ excl,
-                                                                  int64_t n, int s, double* __restrict__ p,
+                                                                  int64_t n, int s, int64_t n_pairs, double* __restrict__ p,
                                                                   const unsigned* __restrict__ pair_tab,
                                                                   const unsigned char* __restrict__ row_flag) {
     const int64_t row = blockIdx.x;
     if (row >= n || !row_flag[row]) return;
-    const int64_t n_pairs = (int64_t)s * (s - 1) / 2;
     double* out = p + row * n_pairs;
     for (int64_t q = threadIdx.x; q < n_pairs; q += 256) {
         const double v = out[q];
@@ -273,9 +272,12 @@ __global__ void __launch_bounds__(256) fisher_beyond_table_kernel(const int32_t*
 // busy -- and writes the 256 p-values as four contiguous 512-byte pieces.  A p-value is written exactly once and nothing
 // is read back (the version with a statically assigned run of 8 pairs per lane wrote the sums, read them again for the
 // pmf pass and wrote the p-values: 12.9 GB of HBM traffic for 4 GB of results).
+// The pairs are the n_pairs entries of pair_tab, column q of the output being the pair pair_tab[q] = i << 16 | j: every
+// pair in row-major order (pair_table_kernel) or a caller's list (sdice_pair_list_pack_dev) -- any order, i > j and
+// repeats included.  Window, ring and blocks are indexed by q alone.
 template <int UNROLL, bool COUNT>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 8)))
-fisher_pairs_kernel(const int32_t* __restrict__ incl, const int64_t* __restrict__ excl, int64_t n, int s,
+fisher_pairs_kernel(const int32_t* __restrict__ incl, const int64_t* __restrict__ excl, int64_t n, int s, int n_pairs,
                     double* __restrict__ p, LfTable tab, const unsigned* __restrict__ pair_tab, int refill,
                     unsigned long long* __restrict__ row_counter, unsigned char* __restrict__ row_flag) {
     // counts staged as doubles (exact below 2^53): the set-up of a pair is four LDS reads and a dozen f64 operations
@@ -283,7 +285,7 @@ fisher_pairs_kernel(const int32_t* __restrict__ incl, const int64_t* __restrict_
     double* exc = smd + s;
     double* ring = smd + 2 * s;                                        // [512] finished sums, slot = q mod 512
     const int lane = threadIdx.x;
-    const int n_pairs = (int)((int64_t)s * (s - 1) / 2);               // (s <= 8192: fewer than 2^25 pairs)
+    // (n_pairs: at most SD_MAX_PAIRS, fewer than 2^25)
     const int n_blk = (n_pairs + 255) >> 8;
     static_assert(UNROLL >= 1 && UNROLL <= 24, "unroll");
     // COUNT (fisher.count_steps, a measurement build): lane-steps issued and lane-steps that advanced a live walk
@@ -420,13 +422,45 @@ static int get_lf_table(sdice_ctx* ctx, LfTable* out) {
     return SDICE_OK;
 }
 
-extern "C" int sdice_fisher_pairs_dev(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* d_incl,
-                                      const int64_t* d_excl, double* d_p) {
+// A caller's pair list: every (i, j) a pair of different columns of [0, s)
+int sd_check_pair_list(const char* who, int32_t s, int64_t m, const int32_t* pairs) {
+    for (int64_t q = 0; q < m; ++q) {
+        const int32_t i = pairs[2 * q], j = pairs[2 * q + 1];
+        if (i < 0 || j < 0 || i >= s || j >= s) {
+            sdice_set_error("%s: pair %lld is (%d, %d): column indices must lie in [0, %d)", who, (long long)q, i, j, s);
+            return SDICE_ERR_ARG;
+        }
+        if (i == j) {
+            sdice_set_error("%s: pair %lld pairs column %d with itself", who, (long long)q, i);
+            return SDICE_ERR_ARG;
+        }
+    }
+    return SDICE_OK;
+}
+
+extern "C" int sdice_pair_list_pack_dev(sdice_ctx* ctx, int32_t s, int64_t m, const int32_t* pairs, uint32_t* d_tab) try {
     SD_ARG(ctx, "ctx is NULL");
-    SD_ARG(n >= 0 && s >= 0, "negative size");
-    if (n == 0 || s < 2) return SDICE_OK;
-    SD_ARG(d_incl && d_excl && d_p, "NULL pointer");
+    SD_ARG(s >= 0 && m >= 0, "negative size");
     SD_ARG(s <= 8192, "more than 8192 samples per junction is not supported");
+    SD_ARG(m <= SD_MAX_PAIRS, "more than 33550336 pairs in one list is not supported");
+    if (m == 0) return SDICE_OK;
+    SD_ARG(pairs && d_tab, "NULL pointer");
+    SD_TRY(sd_check_pair_list(__func__, s, m, pairs));
+    std::vector<uint32_t> tab((size_t)m);
+    for (int64_t q = 0; q < m; ++q) tab[q] = ((uint32_t)pairs[2 * q] << 16) | (uint32_t)pairs[2 * q + 1];
+    return sdice_h2d(ctx, d_tab, tab.data(), m * 4);
+} catch (const std::exception& e) {
+    sdice_set_error("sdice_pair_list_pack_dev: %s", e.what());
+    return SDICE_ERR_NOMEM;
+} catch (...) {
+    sdice_set_error("sdice_pair_list_pack_dev: unknown exception");
+    return SDICE_ERR_STATE;
+}
+
+// The pair kernel and its second pass over n junctions and the n_pairs columns of a pair table: d_list, a caller's
+// packed list, or (d_list == NULL) every pair in row-major order, built here.
+static int fisher_launch(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* d_incl, const int64_t* d_excl,
+                         int64_t n_pairs, const uint32_t* d_list, double* d_p) {
     SD_HIP(hipSetDevice(ctx->device));
     LfTable t;
     SD_TRY(get_lf_table(ctx, &t));
@@ -436,16 +470,21 @@ extern "C" int sdice_fisher_pairs_dev(sdice_ctx* ctx, int64_t n, int32_t s, cons
     // steps per trip: 16 (153 VGPRs, three waves per SIMD, nothing spilled) 16.0 ms per 25 000 x 19 900; 8 (114 VGPRs, four
     // waves) 16.6 ms; 16 under a 128-VGPR cap spills 100 bytes inside the loop: 18.5 ms; under 96 (five waves): 34-43 ms
     const int unroll = (int)ctx->param(SD_P_FISHER_UNROLL);
-    const int64_t n_pairs = (int64_t)s * (s - 1) / 2;
-    SD_TRY(ctx->arena.reserve((size_t)n_pairs * 4 + (size_t)n + 8192, ctx->stream));
-    unsigned* pair_tab = (unsigned*)ctx->arena.alloc((size_t)n_pairs * 4);
+    SD_TRY(ctx->arena.reserve((d_list ? 0 : (size_t)n_pairs * 4) + (size_t)n + 8192, ctx->stream));
+    const unsigned* pair_tab = d_list;
+    if (!d_list) {
+        unsigned* built = (unsigned*)ctx->arena.alloc((size_t)n_pairs * 4);
+        if (!built) return SDICE_ERR_NOMEM;
+        pair_tab = built;
+    }
     unsigned long long* row_counter = (unsigned long long*)ctx->arena.alloc(24);     // + the two step counters
     unsigned char* row_flag = (unsigned char*)ctx->arena.alloc((size_t)n);
-    if (!pair_tab || !row_counter || !row_flag) return SDICE_ERR_NOMEM;
+    if (!row_counter || !row_flag) return SDICE_ERR_NOMEM;
     SD_HIP(hipMemsetAsync(row_counter, 0, 24, ctx->stream));
     SD_HIP(hipMemsetAsync(row_flag, 0, (size_t)n, ctx->stream));
-    SD_LAUNCH(ctx, "pair_table_kernel", pair_table_kernel, dim3((unsigned)sd_ceil_div(n_pairs, (int64_t)256)), dim3(256), 0,
-              pair_tab, n_pairs, (int)s);
+    if (!d_list)
+        SD_LAUNCH(ctx, "pair_table_kernel", pair_table_kernel, dim3((unsigned)sd_ceil_div(n_pairs, (int64_t)256)), dim3(256), 0,
+                  const_cast<unsigned*>(pair_tab), n_pairs, (int)s);
     const size_t lds = (size_t)s * 16 + 512 * 8;
     const bool count = ctx->param(SD_P_FISHER_COUNT_STEPS) != 0;
     auto kern = count ? (unroll <= 4 ? fisher_pairs_kernel<4, true> : unroll <= 8 ? fisher_pairs_kernel<8, true> :
@@ -459,16 +498,38 @@ extern "C" int sdice_fisher_pairs_dev(sdice_ctx* ctx, int64_t n, int32_t s, cons
     SD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 64, lds));
     if (per_cu < 1) per_cu = 1;
     int64_t blocks = std::min<int64_t>(n, (int64_t)ctx->n_cu * per_cu);     // the resident waves; junctions by counter
-    SD_LAUNCH(ctx, "fisher_pairs_kernel", kern, dim3((unsigned)blocks), dim3(64), lds, d_incl, d_excl, n, (int)s, d_p, t,
-              pair_tab, refill, row_counter, row_flag);
+    SD_LAUNCH(ctx, "fisher_pairs_kernel", kern, dim3((unsigned)blocks), dim3(64), lds, d_incl, d_excl, n, (int)s, (int)n_pairs,
+              d_p, t, pair_tab, refill, row_counter, row_flag);
     // junctions with a table beyond the log-factorial table (their workgroups return at once otherwise)
     SD_LAUNCH(ctx, "fisher_beyond_table_kernel", fisher_beyond_table_kernel, dim3((unsigned)n), dim3(256), 0, d_incl, d_excl, n,
-              (int)s, d_p, pair_tab, row_flag);
+              (int)s, n_pairs, d_p, pair_tab, row_flag);
     if (count) {
         SD_HIP(hipMemcpyAsync(ctx->fisher_steps, row_counter + 1, 16, hipMemcpyDeviceToHost, ctx->stream));
         SD_HIP(hipStreamSynchronize(ctx->stream));
     }
     return SDICE_OK;
+}
+
+extern "C" int sdice_fisher_pairs_dev(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* d_incl,
+                                      const int64_t* d_excl, double* d_p) {
+    SD_ARG(ctx, "ctx is NULL");
+    SD_ARG(n >= 0 && s >= 0, "negative size");
+    if (n == 0 || s < 2) return SDICE_OK;
+    SD_ARG(d_incl && d_excl && d_p, "NULL pointer");
+    SD_ARG(s <= 8192, "more than 8192 samples per junction is not supported");
+    return fisher_launch(ctx, n, s, d_incl, d_excl, (int64_t)s * (s - 1) / 2, nullptr, d_p);
+}
+
+extern "C" int sdice_fisher_pair_list_dev(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* d_incl, const int64_t* d_excl,
+                                          int64_t m, const uint32_t* d_tab, double* d_p) {
+    SD_ARG(ctx, "ctx is NULL");
+    SD_ARG(n >= 0 && s >= 0 && m >= 0, "negative size");
+    SD_ARG(s <= 8192, "more than 8192 samples per junction is not supported");
+    SD_ARG(m <= SD_MAX_PAIRS, "more than 33550336 pairs in one list is not supported");
+    if (n == 0 || m == 0) return SDICE_OK;
+    SD_ARG(s >= 2, "a pair list needs at least two samples");
+    SD_ARG(d_incl && d_excl && d_tab && d_p, "NULL pointer");
+    return fisher_launch(ctx, n, s, d_incl, d_excl, m, d_tab, d_p);
 }
 
 extern "C" int sdice_fisher_step_stats(sdice_ctx* ctx, uint64_t* useful, uint64_t* issued) {
@@ -495,6 +556,37 @@ extern "C" int sdice_fisher_pairs(sdice_ctx* ctx, int64_t n, int32_t s, const in
     SD_TRY(st.alloc(&dp, n * n_pairs));
     SD_TRY(sdice_fisher_pairs_dev(ctx, n, s, di, de, dp));
     return st.download(p, dp, n * n_pairs);
+}
+
+extern "C" int sdice_fisher_pair_list(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* incl, const int64_t* excl,
+                                      int64_t m, const int32_t* pairs, double* p) try {
+    SD_ARG(ctx, "ctx is NULL");
+    SD_ARG(n >= 0 && s >= 0 && m >= 0, "negative size");
+    SD_ARG(m == 0 || pairs, "NULL pointer");
+    SD_ARG(s <= 8192, "more than 8192 samples per junction is not supported");
+    SD_ARG(m <= SD_MAX_PAIRS, "more than 33550336 pairs in one list is not supported");
+    SD_TRY(sd_check_pair_list(__func__, s, m, pairs));
+    if (n == 0 || m == 0) return SDICE_OK;
+    SD_ARG(incl && excl && p, "NULL pointer");
+    for (int64_t i = 0; i < n * s; ++i) SD_ARG(incl[i] >= 0 && excl[i] >= 0, "counts must be non-negative");
+    HostStaging st(ctx);
+    int32_t* di;
+    int64_t* de;
+    uint32_t* dt;
+    double* dp;
+    SD_TRY(st.upload(&di, incl, n * s));
+    SD_TRY(st.upload(&de, excl, n * s));
+    SD_TRY(st.alloc(&dt, m));
+    SD_TRY(sdice_pair_list_pack_dev(ctx, s, m, pairs, dt));
+    SD_TRY(st.alloc(&dp, n * m));
+    SD_TRY(sdice_fisher_pair_list_dev(ctx, n, s, di, de, m, dt, dp));
+    return st.download(p, dp, n * m);
+} catch (const std::exception& e) {
+    sdice_set_error("sdice_fisher_pair_list: %s", e.what());
+    return SDICE_ERR_NOMEM;
+} catch (...) {
+    sdice_set_error("sdice_fisher_pair_list: unknown exception");
+    return SDICE_ERR_STATE;
 }
 
 extern "C" int sdice_fisher_tables(sdice_ctx* ctx, int64_t m, const int64_t* abcd, double* p) {

@@ -455,14 +455,15 @@ def _chi2_abort(comm, n_bad, n_tables):
         raise ValueError(f"{CHI2_ZERO_MSG} ({total} of {n_tables} sample-pair tables have an empty row or column)")
 
 
-def _pairwise_host(engine, comm, ext, rp, cl, a0, k, plan, n, pairs, correction, test="fisher"):
+def _pairwise_host(engine, comm, ext, rp, cl, a0, k, plan, n, pairs, correction, test="fisher", pair_list=None):
     n_bad = 0
+    kw = {} if pair_list is None else dict(pairs=pair_list)        # (no list: exactly the calls of an all-pairs run)
     if k:
         excl = engine.ps(ext, rp, cl, want_excl=True, want_ps=False)
         if test == "chi2":
-            p, n_bad = engine.chi2_pairs(ext[a0: a0 + k], excl[a0: a0 + k])
+            p, n_bad = engine.chi2_pairs(ext[a0: a0 + k], excl[a0: a0 + k], **kw)
         else:
-            p = engine.fisher_pairs(ext[a0: a0 + k], excl[a0: a0 + k])
+            p = engine.fisher_pairs(ext[a0: a0 + k], excl[a0: a0 + k], **kw)
     else:
         p = np.zeros((0, pairs), dtype=np.float64)
     if test == "chi2":
@@ -508,12 +509,14 @@ class PairwiseShard(_RowRange):
     correction: "pairwise" packs the p-value matrix into per-rank column blocks ON THE DEVICE (sdice_copy2d_dev),
     all-to-all, column BH on complete columns, all-to-all back, unpack; "all" all-gathers the raw matrix and ranks it
     redundantly (sdice_bh_masked_dev); "none" needs no exchange.  bench.py --workload pairwise --gpus N times exactly
-    this step."""
+    this step.  pair_list ([m, 2] column indices): the m listed pairs instead of all s(s-1)/2; load() packs the list into
+    a device table once (engine.pair_table) and step() hands it to the two kernel calls."""
 
-    def __init__(self, engine, comm, n, s, plan, correction="pairwise", test="fisher", overlap_groups=None):
+    def __init__(self, engine, comm, n, s, plan, correction="pairwise", test="fisher", overlap_groups=None, pair_list=None):
         super().__init__(engine, comm, n, s, plan)
         self.correction, self.test = correction, test
-        self.pairs = s * (s - 1) // 2
+        self.pair_list, self.d_tab = pair_list, None
+        self.pairs = s * (s - 1) // 2 if pair_list is None else len(pair_list)
         # the exchange that takes the corrected values home goes in G column groups: group g's all-to-all runs on the
         # context's second stream (sdice_comm_fork) while group g + 1 is being corrected.  Every rank derives the same G.
         self.ranges = pair_column_ranges(self.pairs, comm.world)
@@ -534,6 +537,9 @@ class PairwiseShard(_RowRange):
         if self.k and pairs:
             self.load_rows(counts_ext, rp, cl, junctions)
             self.d_excl = self.empty(self.d_counts.shape, np.int64)
+            if self.pair_list is not None:
+                self.owned.append(self.e.pair_table(self.s, self.pair_list))
+                self.d_tab = self.owned[-1]
         if pairs and self.correction == "pairwise":
             a, b = self.ranges[self.comm.rank]
             shape = (w, maxk, self.gw[1])
@@ -560,14 +566,15 @@ class PairwiseShard(_RowRange):
         every rank (the one host round trip of a step: the count of such tables)"""
         e, k, s, pairs, a0 = self.e, self.k, self.s, self.pairs, self.lo - self.elo
         n_bad = 0
+        kw = {} if self.d_tab is None else dict(pairs=self.d_tab)
         if k and pairs:
             e.ps_dev(self.d_counts, self.d_rp, self.lists(), self.d_excl, None)
             inc, exc = self.d_counts.offset(a0 * s, (k, s)), self.d_excl.offset(a0 * s, (k, s))
             if self.test == "chi2":
-                e.chi2_pairs_dev(inc, exc, self.d_p.offset(0, (k, pairs)), self.d_bad)
+                e.chi2_pairs_dev(inc, exc, self.d_p.offset(0, (k, pairs)), self.d_bad, **kw)
                 n_bad = int(self.d_bad.to_host()[0])
             else:
-                e.fisher_pairs_dev(inc, exc, self.d_p.offset(0, (k, pairs)))
+                e.fisher_pairs_dev(inc, exc, self.d_p.offset(0, (k, pairs)), **kw)
         if self.test == "chi2":
             _chi2_abort(self.comm, n_bad, self.n * pairs)
 
@@ -653,7 +660,7 @@ class PairwiseShard(_RowRange):
 
 
 def pairwise_sharded(engine, comm, counts_ext, row_ptr, col, correction="pairwise", plan=None, test="fisher",
-                     junctions_ext=None, overlap_groups=None):
+                     junctions_ext=None, overlap_groups=None, pairs=None):
     """`pairwise` with junction rows sharded over ranks.
 
     counts_ext: int32 rows [ext_lo, ext_hi) of this rank's shard in row order; CSR over all rows.
@@ -665,6 +672,9 @@ def pairwise_sharded(engine, comm, counts_ext, row_ptr, col, correction="pairwis
     junctions_ext (with plan = shard.shard_plan_junctions(...), row_ptr = col = None): the rank clusters its own rows
     [ext_lo, ext_hi) itself, as in quant_compare_sharded.  overlap_groups: column groups of the exchange that takes the
     corrected values home (device engines; default: by the width of a rank's column range, 1 on one rank).
+    pairs ([m, 2] column indices, the same list on every rank): test the m listed pairs instead of all s(s-1)/2 --
+    column q is pair q, any order, (j, i) the swapped table, repeats allowed; "pairwise" corrects every listed column,
+    "all" the n * m listed p-values.
     Returns dict(p=[k, pairs] for this rank's own rows, own=(lo, hi), plan=...).
     """
     if correction not in ("pairwise", "all", "none"):
@@ -678,9 +688,15 @@ def pairwise_sharded(engine, comm, counts_ext, row_ptr, col, correction="pairwis
     if not k:
         ext = np.ascontiguousarray(_own_slice(counts_ext, n, part))     # (here a rank without rows has its row count checked too)
     s = ext.shape[1]
-    pairs = s * (s - 1) // 2
+    pair_list = None
+    if pairs is not None:
+        from .engine import pair_array
+        pair_list = pair_array(pairs)
+        if pair_list.min() < 0 or pair_list.max() >= s or (pair_list[:, 0] == pair_list[:, 1]).any():
+            raise ValueError(f"pairs must name two different columns of [0, {s}) each")
+    pairs = s * (s - 1) // 2 if pair_list is None else len(pair_list)
     if dev:
-        sh = PairwiseShard(engine, comm, n, s, plan, correction, test, overlap_groups=overlap_groups)
+        sh = PairwiseShard(engine, comm, n, s, plan, correction, test, overlap_groups=overlap_groups, pair_list=pair_list)
         try:
             sh.load(ext, rp, cl, junctions=junctions_ext if k else None)
             sh.step()
@@ -688,5 +704,5 @@ def pairwise_sharded(engine, comm, counts_ext, row_ptr, col, correction="pairwis
         finally:
             sh.free()
     else:
-        p = _pairwise_host(engine, comm, ext, rp, cl, lo - elo, k, plan, n, pairs, correction, test)
+        p = _pairwise_host(engine, comm, ext, rp, cl, lo - elo, k, plan, n, pairs, correction, test, pair_list)
     return dict(p=p, own=(lo, hi), plan=plan)

@@ -16,6 +16,18 @@ def _c(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
 
 
+def pair_array(pairs):
+    """a pair list as the library takes it: int32 [m, 2], C-contiguous, m >= 1 (the library checks the indices)"""
+    a = np.asarray(pairs)
+    if a.ndim != 2 or a.shape[1] != 2 or a.shape[0] == 0:
+        raise ValueError(f"pairs must be a non-empty [m, 2] array of column indices, got shape {a.shape}")
+    if a.dtype.kind not in "iu":
+        raise TypeError(f"pairs must hold integers, got {a.dtype}")
+    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+        raise ValueError("pairs: column index out of range")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
 class DeviceArray:
     """A device allocation with a numpy-like shape/dtype tag (owned by a Context)."""
 
@@ -250,20 +262,34 @@ class Context:
               "sdice_ranksum")
         return out
 
-    def fisher_pairs(self, incl, excl):
-        """pairwise_fisher.py:164-179 -> p float64[n, s(s-1)/2]"""
+    def fisher_pairs(self, incl, excl, pairs=None):
+        """pairwise_fisher.py:164-179 -> p float64[n, s(s-1)/2]; pairs = [m, 2] column indices: p float64[n, m], column q
+        the table [[incl_i, incl_j], [excl_i, excl_j]] of pair q = (i, j) -- any order, i > j and repeats allowed"""
         incl, excl = _c(incl, np.int32), _c(excl, np.int64)
         n, s = incl.shape
+        if pairs is not None:
+            pairs = pair_array(pairs)
+            p = np.empty((n, len(pairs)), dtype=np.float64)
+            check(self.lib.sdice_fisher_pair_list(self.h, n, s, _ptr(incl), _ptr(excl), len(pairs), _ptr(pairs), _ptr(p)),
+                  "sdice_fisher_pair_list")
+            return p
         p = np.empty((n, s * (s - 1) // 2), dtype=np.float64)
         check(self.lib.sdice_fisher_pairs(self.h, n, s, _ptr(incl), _ptr(excl), _ptr(p)), "sdice_fisher_pairs")
         return p
 
-    def chi2_pairs(self, incl, excl):
-        """pairwise --chi2 (scipy chi2_contingency per pair) -> (p float64[n, s(s-1)/2], n_bad)"""
+    def chi2_pairs(self, incl, excl, pairs=None):
+        """pairwise --chi2 (scipy chi2_contingency per pair) -> (p float64[n, s(s-1)/2], n_bad); pairs as in fisher_pairs:
+        (p float64[n, m], n_bad among the listed tables)"""
         incl, excl = _c(incl, np.int32), _c(excl, np.int64)
         n, s = incl.shape
-        p = np.empty((n, s * (s - 1) // 2), dtype=np.float64)
         bad = C.c_int64()
+        if pairs is not None:
+            pairs = pair_array(pairs)
+            p = np.empty((n, len(pairs)), dtype=np.float64)
+            check(self.lib.sdice_chi2_pair_list(self.h, n, s, _ptr(incl), _ptr(excl), len(pairs), _ptr(pairs), _ptr(p),
+                                                C.byref(bad)), "sdice_chi2_pair_list")
+            return p, bad.value
+        p = np.empty((n, s * (s - 1) // 2), dtype=np.float64)
         check(self.lib.sdice_chi2_pairs(self.h, n, s, _ptr(incl), _ptr(excl), _ptr(p), C.byref(bad)), "sdice_chi2_pairs")
         return p, bad.value
 
@@ -351,8 +377,25 @@ class Context:
                                          out["med1"].ptr, out["med2"].ptr, out["mean1"].ptr, out["mean2"].ptr,
                                          out["delta"].ptr), "sdice_ranksum_dev")
 
-    def fisher_pairs_dev(self, d_incl, d_excl, d_p):
+    def pair_table(self, s, pairs):
+        """a pair list for the _dev calls: checked against s samples, packed and uploaded once -> DeviceArray uint32[m]
+        (synchronous; the caller frees it)"""
+        pairs = pair_array(pairs)
+        d_tab = self.empty(len(pairs), np.uint32)
+        try:
+            check(self.lib.sdice_pair_list_pack_dev(self.h, int(s), len(pairs), _ptr(pairs), d_tab.ptr), "sdice_pair_list_pack_dev")
+        except Exception:
+            d_tab.free()
+            raise
+        return d_tab
+
+    def fisher_pairs_dev(self, d_incl, d_excl, d_p, pairs=None):
+        """pairs: None (every pair) or the device table pair_table() made for these s samples; d_p is [n, m] then"""
         n, s = d_incl.shape
+        if pairs is not None:
+            check(self.lib.sdice_fisher_pair_list_dev(self.h, n, s, d_incl.ptr, d_excl.ptr, pairs.shape[0], pairs.ptr, d_p.ptr),
+                  "sdice_fisher_pair_list_dev")
+            return
         check(self.lib.sdice_fisher_pairs_dev(self.h, n, s, d_incl.ptr, d_excl.ptr, d_p.ptr), "sdice_fisher_pairs_dev")
 
     def fisher_step_stats(self):
@@ -361,8 +404,12 @@ class Context:
         check(self.lib.sdice_fisher_step_stats(self.h, C.byref(u), C.byref(t)), "sdice_fisher_step_stats")
         return int(u.value), int(t.value)
 
-    def chi2_pairs_dev(self, d_incl, d_excl, d_p, d_n_bad):
+    def chi2_pairs_dev(self, d_incl, d_excl, d_p, d_n_bad, pairs=None):
         n, s = d_incl.shape
+        if pairs is not None:
+            check(self.lib.sdice_chi2_pair_list_dev(self.h, n, s, d_incl.ptr, d_excl.ptr, pairs.shape[0], pairs.ptr, d_p.ptr,
+                                                    d_n_bad.ptr), "sdice_chi2_pair_list_dev")
+            return
         check(self.lib.sdice_chi2_pairs_dev(self.h, n, s, d_incl.ptr, d_excl.ptr, d_p.ptr, d_n_bad.ptr), "sdice_chi2_pairs_dev")
 
     def bh_columns_dev(self, d_p):

@@ -7,6 +7,9 @@ On the GPU: the exclusion gather :158-160 (an O(N) name scan per event in the re
 -> sdice_ps (integer sums over a CSR built once on the host from the name lists); the per-pair
 scipy fisher_exact :164-179 -> sdice_fisher_pairs (or, with --chi2, chi2_contingency :133-136 ->
 sdice_chi2_pairs); Benjamini-Hochberg :182-193 -> sdice_bh / sdice_bh_columns.
+
+One flag the reference does not have: `--pairs FILE` tests the listed sample pairs only (read_pair_list) instead of all
+s(s-1)/2 -- the same kernels over a caller's pair table (sdice_fisher_pair_list / sdice_chi2_pair_list).
 """
 import numpy as np
 
@@ -45,6 +48,39 @@ def get_event_counts(filename, filter_list=None):
         return samples, events, textio.counts_to_int32(mat, filename)
     except ValueError:
         return samples, events, np.ascontiguousarray(mat, dtype=np.float64)
+
+
+def read_pair_list(filename, samples):
+    """`--pairs FILE`: one pair per line, two sample names of the count table's header separated by a tab (a line without
+    a tab is split on white space, as compare_sample_sets reads its manifests); blank lines are skipped.
+    -> [(i, j)] column indices in file order; `b a` is the pair (b, a), column `b_a`, the swapped table.
+    ValueError naming file, line and token for: a name that is not in the header, a line without exactly two names, a
+    sample paired with itself, the same ordered pair twice, an empty list."""
+    col_of = {}
+    for k, name in enumerate(samples):
+        col_of.setdefault(name, k)
+    pairs, seen = [], {}
+    with open(filename) as fh:
+        for ln, line in enumerate(fh, 1):
+            line = line.rstrip("\r\n")
+            if not line.strip():
+                continue
+            names = [x.strip() for x in line.split("\t")] if "\t" in line else line.split()
+            if len(names) != 2 or not all(names):
+                raise ValueError(f"{filename}:{ln}: expected two sample names, got {len(names)}: {line!r}")
+            for name in names:
+                if name not in col_of:
+                    raise ValueError(f"{filename}:{ln}: sample {name!r} is not in the header of the count table")
+            a, b = names
+            if col_of[a] == col_of[b]:
+                raise ValueError(f"{filename}:{ln}: sample {a!r} is paired with itself")
+            if (a, b) in seen:
+                raise ValueError(f"{filename}:{ln}: pair {a!r} {b!r} is already listed at line {seen[(a, b)]}")
+            seen[(a, b)] = ln
+            pairs.append((col_of[a], col_of[b]))
+    if not pairs:
+        raise ValueError(f"{filename}: the pair list is empty")
+    return pairs
 
 
 def fractional_tables(ctx, counts, row_ptr, col):
@@ -86,14 +122,17 @@ def exclusion_csr(events, clusters):
 SLAB_BYTES = 256 << 20      # host memory of the streamed output (rows x pairs x 8 B per slab)
 
 
-def device_pipeline(ctx, counts, row_ptr, col, chi2, correction, events, header, path, excl=None):
+def device_pipeline(ctx, counts, row_ptr, col, chi2, correction, events, header, path, excl=None, pair_list=None):
     """exclusion sums -> per-pair test -> correction with the [n, pairs] p-value matrix RESIDENT IN HBM
     (config 4: 200 000 x 19 900 doubles = 32 GB; the reference holds it in host memory,
     pairwise_fisher.py:123-193), then streamed to the output table in row slabs: device -> host ->
-    formatter -> file, so host memory stays bounded by SLAB_BYTES whatever the table size."""
+    formatter -> file, so host memory stays bounded by SLAB_BYTES whatever the table size.
+    pair_list ([m, 2] column indices): the matrix is [n, m], one column per listed pair."""
     from . import _stages
     n, s = counts.shape
-    pairs = s * (s - 1) // 2
+    pairs = s * (s - 1) // 2 if pair_list is None else len(pair_list)
+    d_tab = None if pair_list is None else ctx.pair_table(s, pair_list)
+    kw = {} if d_tab is None else dict(pairs=d_tab)
     with _stages.stage("h2d"):
         d_counts = ctx.to_device(counts, np.int32)
         d_rp = ctx.to_device(row_ptr, np.int64)
@@ -108,15 +147,15 @@ def device_pipeline(ctx, counts, row_ptr, col, chi2, correction, events, header,
     d_p = ctx.empty((n, pairs), np.float64)
     if chi2:
         d_bad = ctx.empty(1, np.int64)
-        ctx.chi2_pairs_dev(d_counts, d_excl, d_p, d_bad)
+        ctx.chi2_pairs_dev(d_counts, d_excl, d_p, d_bad, **kw)
         n_bad = int(d_bad.to_host()[0])
         if n_bad:
             # scipy.stats.chi2_contingency raises on the first such table and the reference
             # run dies with it (pairwise_fisher.py:167-179)
             raise ValueError(f"{CHI2_ZERO_MSG} ({n_bad} of {n * pairs} sample-pair tables have an empty row or column)")
     else:
-        ctx.fisher_pairs_dev(d_counts, d_excl, d_p)
-    for a in (d_counts, d_rp, d_col, d_excl):
+        ctx.fisher_pairs_dev(d_counts, d_excl, d_p, **kw)
+    for a in (d_counts, d_rp, d_col, d_excl) + (() if d_tab is None else (d_tab,)):
         a.free()
     if correction == "all":
         d_q = ctx.empty((n, pairs), np.float64)
@@ -166,6 +205,10 @@ def add_parser(parser):
                         help="Benjamini-Hochberg scope: per sample pair (default), over all p-values, or off")
     parser.add_argument("-f", "--filter_list", help="text file with one event per line: only these rows are analysed")
     parser.add_argument("-o", "--output", default="pairwise.tsv", help="output table (tab separated)")
+    # not in the reference, which always tests every pair
+    parser.add_argument("--pairs", default=None, metavar="FILE",
+                        help="text file with one sample pair per line (two names of the table's header, tab separated): "
+                             "only these pairs are tested, columns in file order (default: every pair)")
 
 
 def run_with(args, ctx=None):
@@ -184,7 +227,13 @@ def run_with(args, ctx=None):
     with _stages.stage("parse"):
         clusters = get_clusters(args.clusters)
     print("Clusters loaded from", args.clusters, "...")
-    pairs = [(i, j) for i in range(len(samples) - 1) for j in range(i + 1, len(samples))]
+    pair_file = getattr(args, "pairs", None)
+    if pair_file is not None:
+        pairs = read_pair_list(pair_file, samples)
+        kw = dict(pairs=np.asarray(pairs, dtype=np.int32))
+    else:
+        pairs = [(i, j) for i in range(len(samples) - 1) for j in range(i + 1, len(samples))]
+        kw = {}                     # (no list: exactly the calls of an all-pairs run)
     columns = [f"{samples[a]}_{samples[b]}" for a, b in pairs]
     print("Analyzing pairs:")
     print(",".join(columns))
@@ -207,9 +256,10 @@ def run_with(args, ctx=None):
                 row_ptr, col = exclusion_csr(events, clusters)
                 incl, excl = fractional_tables(ctx, counts, row_ptr, col)
                 if hasattr(ctx, "fisher_pairs_dev"):
-                    device_pipeline(ctx, incl, row_ptr, col, False, args.multiple_test_correction, events, header, args.output, excl)
+                    device_pipeline(ctx, incl, row_ptr, col, False, args.multiple_test_correction, events, header, args.output, excl,
+                                    pair_list=kw.get("pairs"))
                 else:
-                    parray = ctx.fisher_pairs(incl, excl)
+                    parray = ctx.fisher_pairs(incl, excl, **kw)
                     if args.multiple_test_correction == "all":
                         parray = ctx.bh(parray.ravel()).reshape(parray.shape)
                     elif args.multiple_test_correction == "pairwise":
@@ -228,7 +278,7 @@ def run_with(args, ctx=None):
         try:
             row_ptr, col = exclusion_csr(events, clusters)
             out = distributed.pairwise_sharded(ctx, L.comm(ctx), np.ascontiguousarray(counts, dtype=np.int32), row_ptr, col,
-                                               args.multiple_test_correction, test="chi2" if args.chi2 else "fisher")
+                                               args.multiple_test_correction, test="chi2" if args.chi2 else "fisher", **kw)
         finally:
             if own_ctx:
                 ctx.close()
@@ -244,7 +294,8 @@ def run_with(args, ctx=None):
     if totaln and pairs and hasattr(ctx, "fisher_pairs_dev"):
         try:
             row_ptr, col = exclusion_csr(events, clusters)
-            device_pipeline(ctx, counts, row_ptr, col, args.chi2, args.multiple_test_correction, events, header, args.output)
+            device_pipeline(ctx, counts, row_ptr, col, args.chi2, args.multiple_test_correction, events, header, args.output,
+                            pair_list=kw.get("pairs"))
         finally:
             if own_ctx:
                 ctx.close()
@@ -254,13 +305,13 @@ def run_with(args, ctx=None):
         if totaln and pairs:
             excl = ctx.ps(counts, row_ptr, col, want_excl=True, want_ps=False)
             if args.chi2:
-                parray, n_bad = ctx.chi2_pairs(counts, excl)
+                parray, n_bad = ctx.chi2_pairs(counts, excl, **kw)
                 if n_bad:
                     # scipy.stats.chi2_contingency raises on the first such table and the reference
                     # run dies with it (pairwise_fisher.py:167-179)
                     raise ValueError(f"{CHI2_ZERO_MSG} ({n_bad} of {parray.size} sample-pair tables have an empty row or column)")
             else:
-                parray = ctx.fisher_pairs(counts, excl)
+                parray = ctx.fisher_pairs(counts, excl, **kw)
             if args.multiple_test_correction == "all":
                 parray = ctx.bh(parray.ravel()).reshape(parray.shape)
             elif args.multiple_test_correction == "pairwise":
