@@ -164,6 +164,23 @@ int sdice_ranksum_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps,
                       uint8_t* d_tested, double* d_p, double* d_z, float* d_med1, float* d_med2,
                       float* d_mean1, float* d_mean2, float* d_delta);
 
+/* ---- compare_sample_sets -mx: Kruskal-Wallis H test across k sets, scipy.stats.kruskal per row under the row rules
+ *      above (per set: NaN drop; the row is tested when every set keeps >= 3 values).
+ *  cols: the column indices of all sets back to back; set_ptr[k+1]: CSR-style offsets into cols (set i is
+ *  cols[set_ptr[i] .. set_ptr[i+1])).  2 <= k <= 64, every set non-empty, a column in one set only, at most 16384
+ *  selected columns; otherwise SDICE_ERR_ARG before any launch, outputs untouched.  set_ptr is a HOST array in both
+ *  calls (launch metadata, like n1 / n2 above); the host call also checks the indices and the one-set rule.
+ *  Outputs, one slot per row: tested[n], p[n] = chi2.sf(H, k-1) and h[n] float64 (h optional, NULL to skip),
+ *  med[k][n] / mean[k][n] float32 SET-major (np.median / np.mean of a set's kept values), delta[n] = largest minus
+ *  smallest set median; 0 where not tested.  A row whose kept values are all equal is tested with H = 0, p = 1
+ *  (scipy raises there).  Any finite float32 values; rows of 3-decimal PS values take the histogram kernel. */
+int sdice_kruskal(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps, const int32_t* cols,
+                  const int32_t* set_ptr, int32_t k, uint8_t* tested, double* p, double* h,
+                  float* med, float* mean, float* delta);
+int sdice_kruskal_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, const int32_t* d_cols,
+                      const int32_t* set_ptr, int32_t k, uint8_t* d_tested, double* d_p, double* d_h,
+                      float* d_med, float* d_mean, float* d_delta);
+
 /* ---- pairwise: replaces the per-pair loop pairwise_fisher.py:164-179
  *      (scipy.stats.fisher_exact two-sided on [[incl_a, incl_b],[excl_a, excl_b]]).
  *  incl[n,s] int32, excl[n,s] int64 (from sdice_ps); p[n, s(s-1)/2] float64 row-major,

@@ -5,6 +5,10 @@ flags, same `<3 samples` exit, same output columns
 `event mean1 mean2 median1 median2 delta p-value corrected` (+ gene/overlapping/transcript_id
 with -a GTF), values printed as numpy float32 / float64 scalars.
 
+One flag the reference lacks: `-mx FILE [FILE ...]` names the third and later sample sets; the test is then the
+Kruskal-Wallis H test across all k sets (sdice_kruskal) and the columns are
+`event mean1..meank median1..mediank delta H p-value corrected`.
+
 On the GPU: the per-row loop :216-232 (NaN drop, <3 skip, scipy ranksums, medians, means)
 -> sdice_ranksum; multipletests(..., "fdr_bh") :235 -> sdice_bh over the tested rows.
 The GTF annotation columns are host string work, as in the reference.
@@ -150,6 +154,37 @@ def compare(matrix, g1_idx, g2_idx, ctx):
     return keep, out
 
 
+def compare_sets_dev(matrix, set_idx, ctx):
+    """the k-set pipeline (-mx): table up, Kruskal-Wallis + BH over the tested rows on resident vectors, per-row results
+    down -> (kept row indices, dict: mean / med float32 [k, kept], delta, h, p, corrected)"""
+    from . import _stages
+    from .engine import kruskal_sets
+    n, s = matrix.shape
+    cols, set_ptr = kruskal_sets(set_idx, s)          # (raises on a column in two sets, before any launch)
+    k = len(set_idx)
+    with _stages.stage("h2d"):
+        d_ps = ctx.to_device(matrix, np.float32)
+        d_cols = ctx.to_device(cols, np.int32)
+        out = dict(tested=ctx.empty(n, np.uint8), p=ctx.empty(n, np.float64), h=ctx.empty(n, np.float64),
+                   med=ctx.empty((k, n), np.float32), mean=ctx.empty((k, n), np.float32), delta=ctx.empty(n, np.float32))
+        d_q = ctx.empty(n, np.float64)
+    with _stages.stage("kernels"):
+        ctx.kruskal_dev(d_ps, d_cols, set_ptr, out)
+        ctx.bh_masked_dev(out["p"], out["tested"], d_q)
+        ctx.sync()
+    with _stages.stage("d2h"):
+        res = {name: v.to_host() for name, v in out.items()}
+        q = d_q.to_host()
+    for a in (d_ps, d_cols, d_q, *out.values()):
+        a.free()
+    keep = np.flatnonzero(res["tested"])
+    r = {name: res[name][keep] for name in ("p", "h", "delta")}
+    r["med"] = np.ascontiguousarray(res["med"][:, keep])
+    r["mean"] = np.ascontiguousarray(res["mean"][:, keep])
+    r["corrected"] = q[keep]
+    return keep, r
+
+
 def compare_sharded(matrix, g1_idx, g2_idx, ctx, L):
     """compare() with the table rows cut into one block per rank (rows are independent here): every rank tests its
     block, the per-row statistics cross the ranks as ONE packed block in ONE all-gather (distributed.stat_layout, padded to
@@ -177,10 +212,44 @@ def add_parser(parser):
                         help="Manifest containing samples for sample set group1")
     parser.add_argument("-m2", "--manifest2", type=str, required=True,
                         help="Manifest containing samples for sample set group2")
+    parser.add_argument("-mx", "--moreManifests", type=str, nargs="+", required=False, default=None, metavar="FILE",
+                        help="Manifests of the third and later sample sets: the rank-sum test becomes the Kruskal-Wallis "
+                             "H test across all sets (not part of the reference)")
     parser.add_argument("-a", "--annotation", type=str, required=False, default="",
                         help="Optional GTF file to label known splice junctions and genes")
     parser.add_argument("-o", "--outputFile", type=str, required=True,
                         help="Output filename for tab-separated table")
+
+
+MULTI_RANK_REFUSAL = ("compare_sample_sets: -mx/--moreManifests is not available under the multi-rank launcher "
+                      "(the packed all-gather carries the two-set fields only); run it in one process.")
+
+
+def run_sets(args, groups, ctx=None, device=0):
+    """compare_sample_sets with -mx: k >= 3 sets, Kruskal-Wallis per junction, BH over the tested rows; columns
+    event mean1..meank median1..mediank delta H p-value corrected (+ the GTF columns with -a)."""
+    from . import _stages, textio
+    with _stages.stage("parse"):
+        rows, cols, matrix = read_ps_table(args.psiSPLICEDICE, as_table=True)
+    set_idx = [column_indices(g, cols) for g in groups]
+    own_ctx = ctx is None
+    ctx = ctx if ctx is not None else Context(device)
+    try:
+        keep, r = compare_sets_dev(matrix, set_idx, ctx)
+    finally:
+        if own_ctx:
+            ctx.close()
+    k = len(groups)
+    header = "\t".join(["event"] + [f"mean{i + 1}" for i in range(k)] + [f"median{i + 1}" for i in range(k)] +
+                       ["delta", "H", "p-value", "corrected"])
+    columns = [*r["mean"], *r["med"], r["delta"], r["h"], r["p"], r["corrected"]]
+    if not args.annotation:
+        with _stages.stage("format+write"):
+            textio.write_columns(args.outputFile, header + "\n", rows.take(keep), columns, ["repr"] * len(columns))
+        return
+    names = list(rows.take(keep))
+    textio.write_columns(args.outputFile, header + "\tgene\toverlapping\ttranscript_id\n", names, columns,
+                         ["repr"] * len(columns), suffixes=annotation_suffixes(names, args.annotation))
 
 
 def run_with(args, ctx=None):
@@ -188,9 +257,15 @@ def run_with(args, ctx=None):
     L = mgpu.launcher()             # (reads the torchrun environment before any GPU call)
     g1 = samples_from_manifest(args.manifest1)
     g2 = samples_from_manifest(args.manifest2)
-    if len(g1) < 3 or len(g2) < 3:
+    more = [samples_from_manifest(m) for m in (getattr(args, "moreManifests", None) or [])]
+    if len(g1) < 3 or len(g2) < 3 or any(len(g) < 3 for g in more):
         print("Cannot conduct wilcoxon with less than 3 samples in either group. Exit.", file=sys.stderr)
         sys.exit(1)
+    if more:
+        if L.world > 1:
+            print(MULTI_RANK_REFUSAL, file=sys.stderr)
+            sys.exit(1)
+        return run_sets(args, [g1, g2] + more, ctx, L.local_rank)
 
     from . import _stages
     with _stages.stage("parse"):

@@ -28,6 +28,25 @@ def pair_array(pairs):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def kruskal_sets(sets, s=None):
+    """k lists of column indices as the library takes them -> (cols int32 of all sets back to back, set_ptr int32[k + 1]).
+    A column may belong to one set only: a column listed twice (inside a set or across sets) raises ValueError here, on
+    the host, before anything is launched; so does an index outside [0, s) when s is given."""
+    sets = [np.asarray(g).reshape(-1).astype(np.int32) for g in sets]
+    set_ptr = np.zeros(len(sets) + 1, dtype=np.int32)
+    set_ptr[1:] = np.cumsum([g.size for g in sets])
+    cols = np.concatenate(sets) if sets else np.zeros(0, np.int32)
+    if s is not None and cols.size and (cols.min() < 0 or cols.max() >= s):
+        raise ValueError(f"kruskal: column index outside [0, {s})")
+    seen = {}
+    for i, g in enumerate(sets):
+        for c in g.tolist():
+            if c in seen:
+                raise ValueError(f"kruskal: column {c} is in set {seen[c] + 1} and in set {i + 1}; a column may belong to one set only")
+            seen[c] = i
+    return np.ascontiguousarray(cols, dtype=np.int32), set_ptr
+
+
 class DeviceArray:
     """A device allocation with a numpy-like shape/dtype tag (owned by a Context)."""
 
@@ -262,6 +281,20 @@ class Context:
               "sdice_ranksum")
         return out
 
+    def kruskal(self, ps, sets):
+        """scipy.stats.kruskal per row across the k column sets under the row rules of ranksum(); un-compacted outputs:
+        tested, p, h [n], med, mean [k, n] (set-major), delta [n] = largest minus smallest set median."""
+        ps = _c(ps, np.float32)
+        n, s = ps.shape
+        cols, set_ptr = kruskal_sets(sets, s)
+        k = len(set_ptr) - 1
+        out = dict(tested=np.zeros(n, np.uint8), p=np.zeros(n, np.float64), h=np.zeros(n, np.float64),
+                   med=np.zeros((k, n), np.float32), mean=np.zeros((k, n), np.float32), delta=np.zeros(n, np.float32))
+        check(self.lib.sdice_kruskal(self.h, n, s, _ptr(ps), _ptr(cols), _ptr(set_ptr), k, _ptr(out["tested"]),
+                                     _ptr(out["p"]), _ptr(out["h"]), _ptr(out["med"]), _ptr(out["mean"]),
+                                     _ptr(out["delta"])), "sdice_kruskal")
+        return out
+
     def fisher_pairs(self, incl, excl, pairs=None):
         """pairwise_fisher.py:164-179 -> p float64[n, s(s-1)/2]; pairs = [m, 2] column indices: p float64[n, m], column q
         the table [[incl_i, incl_j], [excl_i, excl_j]] of pair q = (i, j) -- any order, i > j and repeats allowed"""
@@ -376,6 +409,15 @@ class Context:
                                          out["tested"].ptr, out["p"].ptr, out["z"].ptr if out.get("z") else None,
                                          out["med1"].ptr, out["med2"].ptr, out["mean1"].ptr, out["mean2"].ptr,
                                          out["delta"].ptr), "sdice_ranksum_dev")
+
+    def kruskal_dev(self, d_ps, d_cols, set_ptr, out):
+        """d_cols: the device copy of kruskal_sets()'s cols; set_ptr: its HOST offsets; out: device tested, p, (h), med and
+        mean [k, n], delta"""
+        n, s = d_ps.shape
+        set_ptr = _c(set_ptr, np.int32)
+        check(self.lib.sdice_kruskal_dev(self.h, n, s, d_ps.ptr, d_cols.ptr, _ptr(set_ptr), set_ptr.size - 1,
+                                         out["tested"].ptr, out["p"].ptr, out["h"].ptr if out.get("h") else None,
+                                         out["med"].ptr, out["mean"].ptr, out["delta"].ptr), "sdice_kruskal_dev")
 
     def pair_table(self, s, pairs):
         """a pair list for the _dev calls: checked against s samples, packed and uploaded once -> DeviceArray uint32[m]
