@@ -34,8 +34,9 @@ namespace {
 constexpr int KW_MAX_SETS = 64;
 constexpr int KW_MAX_N = 16384;          // selected columns per row, both kernels (block kernel: 8 B of LDS per column)
 constexpr int KW_BINS = 1024;            // 1001 used
-constexpr int KW_PW_DEPTH = 8;           // levels of numpy's pairwise recursion for up to 16384 values (<= 256 leaves)
-constexpr int KW_LEAF_MAX = 256;
+constexpr int KW_SUM_PIECE = 8192;       // np.add.reduce hands the pairwise loop at most np.getbufsize() = 8192 values at a time
+constexpr int KW_PW_DEPTH = 7;           // levels of numpy's pairwise recursion inside a piece (7689 values are the first to need 7)
+constexpr int KW_LEAF_MAX = 128;         // a part after 7 halvings is at most 8192 / 128 + 15 values long
 constexpr unsigned char KW_REDO = 0xFF;  // `tested` mark: row left to the block kernel by the grid kernel
 
 struct KwSets { int32_t ptr[KW_MAX_SETS + 1]; };
@@ -110,9 +111,9 @@ __device__ __forceinline__ float kw_wave_min(float v) {
     return v;
 }
 
-// wave_pairwise_sum of ranksum.hip over float32(key / 1000) of K[0..nv), nv <= KW_MAX_N: lane = leaf * 8 + j owns
+// wave_pairwise_sum of ranksum.hip over float32(key / 1000) of K[0..nv), nv <= KW_SUM_PIECE: lane = leaf * 8 + j owns
 // accumulator j of its leaf, 8 leaves per round
-__device__ __forceinline__ float kw_wave_sum_keys(const unsigned short* K, int nv, int lane, int* leaf_off, float* leaf_sum) {
+__device__ __forceinline__ float kw_wave_tree_keys(const unsigned short* K, int nv, int lane, int* leaf_off, float* leaf_sum) {
     int nl = 0;
     pw_leaves<KW_PW_DEPTH>(0, nv, leaf_off, nl, lane == 0);
     if (lane == 0) leaf_off[nl] = nv;
@@ -139,6 +140,15 @@ __device__ __forceinline__ float kw_wave_sum_keys(const unsigned short* K, int n
     const float out = pw_combine<KW_PW_DEPTH>(nv, leaf_sum, next);
     SD_WAVE_SYNC();
     return out;
+}
+
+// np.sum of a contiguous float32 array: the identity 0 plus the pairwise tree of every piece of KW_SUM_PIECE values, the
+// pieces added left to right (at most two: nv <= KW_MAX_N).  The whole-array tree is a different sum above one piece.
+__device__ __forceinline__ float kw_wave_sum_keys(const unsigned short* K, int nv, int lane, int* leaf_off, float* leaf_sum) {
+    float sum = 0.0f + kw_wave_tree_keys(K, min(nv, KW_SUM_PIECE), lane, leaf_off, leaf_sum);
+    if (nv > KW_SUM_PIECE)               // wave-uniform
+        sum += kw_wave_tree_keys(K + KW_SUM_PIECE, nv - KW_SUM_PIECE, lane, leaf_off, leaf_sum);
+    return sum;
 }
 
 // ------------------------------------------------------------------ grid path: one wave per row
@@ -412,7 +422,11 @@ __global__ void __launch_bounds__(RB_THREADS) kruskal_block_kernel(const float* 
             const int a = sptr[i];
             const int nv = block_compact(prow, cols + a, sptr[i + 1] - a, F, wcnt);
             if (nv < 3) { all3 = false; break; }     // block-uniform
-            const float sum = block_pairwise_sum<KW_PW_DEPTH>(F, nv, leaf_off, leaf_sum, scratch8, KW_LEAF_MAX);
+            // np.sum: 0 + the tree of the first KW_SUM_PIECE values (+ the tree of the rest), see kw_wave_sum_keys; the
+            // leading 0 makes a sum of -0.0 values +0.0 as numpy's is
+            float sum = 0.0f + block_pairwise_sum<KW_PW_DEPTH>(F, min(nv, KW_SUM_PIECE), leaf_off, leaf_sum, scratch8, KW_LEAF_MAX);
+            if (nv > KW_SUM_PIECE)                   // block-uniform
+                sum += block_pairwise_sum<KW_PW_DEPTH>(F + KW_SUM_PIECE, nv - KW_SUM_PIECE, leaf_off, leaf_sum, scratch8, KW_LEAF_MAX);
             if (tid == 0) { nvs[i] = nv; meanS[i] = sum / (float)nv; }
         }
         if (!all3) {
@@ -545,9 +559,11 @@ extern "C" int sdice_kruskal_dev(sdice_ctx* ctx, int64_t n, int32_t s, const flo
     for (int i = 0; i < k; ++i) maxset = std::max(maxset, (int)(set_ptr[i + 1] - set_ptr[i]));
     const int nsel = set_ptr[k];
     KwOut o{d_tested, d_p, d_h, d_med, d_mean, d_delta};
-    {   // grid path.  Leaves of the pairwise recursion: after d halvings a part is at most maxset / 2^d + 15 long
+    {   // grid path.  Leaves of the pairwise recursion over a piece of at most KW_SUM_PIECE values: after d halvings a
+        // part is at most piece / 2^d + 15 long, a leaf from 128 down
+        const int piece = std::min(maxset, KW_SUM_PIECE);
         int leaf_cap = 1;
-        while (leaf_cap < KW_LEAF_MAX && maxset > 113 * leaf_cap) leaf_cap <<= 1;
+        while (leaf_cap < KW_LEAF_MAX && piece > 113 * leaf_cap) leaf_cap <<= 1;
         const int wstride = (int)((2 * KW_BINS * 4 + (2 * leaf_cap + 1) * 4 + 2 * nsel + 15) & ~15);
         int waves = 64 * 1024 / wstride;             // the workgroup is sized from the LDS a wave needs
         waves = waves > 4 ? 4 : (waves < 1 ? 1 : waves);

@@ -3,10 +3,35 @@
 H comes from the textbook definition evaluated in rational arithmetic (fractions.Fraction) on integer keys, so it has
 no rounding at all; p = scipy.stats.chi2.sf(float(H), k - 1).  Keys are any integers that order the values the way the
 values order: 1000 * value for 3-decimal PS values, a dense rank for arbitrary float32 values.
+
+The float32 fields are numpy's own (np.mean, np.median).  numpy_sum() restates the order np.sum adds a contiguous float32
+array in, so that the tests can show what the kernels have to reproduce; p_exact() is chi2.sf from mpmath at 50 digits,
+the licence for scipy's chi2.sf as the p referee.
 """
 from fractions import Fraction
 
 import numpy as np
+
+SUM_PIECE = 8192        # np.getbufsize(): add.reduce hands the pairwise loop at most this many elements at a time
+
+
+def numpy_sum(a):
+    """np.sum of a contiguous 1-D float32 array restated: pieces of SUM_PIECE values, each summed by numpy's pairwise
+    tree (tree_sum of test_gpu_count_sweeps), the pieces added left to right onto the identity 0"""
+    from test_gpu_count_sweeps import tree_sum
+    total = np.float32(0.0)
+    for at in range(0, a.size, SUM_PIECE):
+        total = np.float32(total + tree_sum(a[at: at + SUM_PIECE]))
+    return total
+
+
+def p_exact(h, df):
+    """chi2.sf(h, df) of an exact H (a Fraction) as the regularised upper incomplete gamma function Q(df / 2, h / 2),
+    evaluated by mpmath at 50 digits -> mpmath.mpf (far below the float64 range where H is large)"""
+    import mpmath
+    with mpmath.workdps(50):
+        x = mpmath.mpf(h.numerator) / mpmath.mpf(h.denominator) / 2
+        return mpmath.gammainc(mpmath.mpf(df) / 2, x, mpmath.inf, regularized=True)
 
 
 def grid_keys(values):
