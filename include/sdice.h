@@ -154,7 +154,13 @@ int sdice_quantize3_dev(sdice_ctx* ctx, int64_t n_elems, float* d_ps_inout);
  *  Outputs are un-compacted, one slot per row: tested[n] (1 = row was tested),
  *  p[n] float64, med1/med2/mean1/mean2/delta[n] float32 (0 where not tested);
  *  z[n] float64 optional (NULL to skip).  The host compacts in row order.
- */
+ *  Any float32 values, NaN meaning "no value": signed zeros (one tie group), subnormals (distinct values), values
+ *  outside [0, 1] and infinities included; rows of 3-decimal PS values take the 16-bit-key / histogram kernels, every
+ *  other row the sorting kernels, with the same results.  A row whose kept values are all equal is tested with z = 0,
+ *  p = 1.  mean1 / mean2 are np.mean of a group's kept values bit for bit (+0.0 for a group of -0.0 values, +-inf or
+ *  NaN where the float32 sum overflows or meets inf - inf), med1 / med2 np.median by value; p = erfc(|z| / sqrt 2)
+ *  within 1e-9 relative down to 1e-280, below 2e-280 under that and 0 past the float64 range.  Groups of up to 4096
+ *  columns. */
 int sdice_ranksum(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps,
                   const int32_t* g1, int32_t n1, const int32_t* g2, int32_t n2,
                   uint8_t* tested, double* p, double* z, float* med1, float* med2,

@@ -11,7 +11,8 @@
 //   2U = sum_i (lower_bound(B, a_i) + upper_bound(B, a_i)) over the sorted second group.
 //   np.mean(float32 vector) = numpy's pairwise summation in float32 (8 interleaved
 //   accumulators per <=128-element block, halving recursion above) divided by n in float32;
-//   it is reproduced operation for operation so the means are bit-identical.
+//   it is reproduced operation for operation, the identity 0 that np.sum starts from included (a group
+//   of -0.0 values has the mean +0.0), so the means are bit-identical.
 //
 // Kernels (auto dispatch: lane pair for groups <= 64, wave for <= 1024, block above):
 //   ranksum_pair_kernel  (n1, n2 <= 64): the lane kernel's machinery with TWO lanes per row (one
@@ -116,7 +117,7 @@ __device__ __forceinline__ int lane_group(float* row, int cnt, float& mean) {
         for (int k = 8; k < P; ++k)
             if (k >= main_n && k < nv) res += a[k];
     }
-    mean = nv > 0 ? res / (float)nv : 0.f;
+    mean = nv > 0 ? (0.0f + res) / (float)nv : 0.f;      // (np.sum starts from the identity 0: a sum of -0.0 values is +0.0)
     bitonic_regs<P>(a);
 #pragma unroll
     for (int k = 0; k < P; ++k)
@@ -772,7 +773,8 @@ __global__ void __launch_bounds__(RB_THREADS) ranksum_block_kernel(const float* 
             o.tested[row] = 1; o.p[row] = p;
             if (o.z) o.z[row] = z;
             o.med1[row] = med1; o.med2[row] = med2;
-            o.mean1[row] = sum1 / (float)nv1; o.mean2[row] = sum2 / (float)nv2;
+            // (np.sum starts from the identity 0: a sum of -0.0 values is +0.0)
+            o.mean1[row] = (0.0f + sum1) / (float)nv1; o.mean2[row] = (0.0f + sum2) / (float)nv2;
             o.delta[row] = med1 - med2;
         }
         __syncthreads();
@@ -991,9 +993,9 @@ __global__ void __launch_bounds__(256) ranksum_wave_kernel(const float* __restri
         const int64_t row = row0 + lane;
         const bool tested = s_nv1 >= 3 && s_nv2 >= 3;
         float mean1 = 0.f, mean2 = 0.f;
-        if (tested) {
-            mean1 = s_sum1 / (float)s_nv1;
-            mean2 = s_sum2 / (float)s_nv2;
+        if (tested) {      // (np.sum starts from the identity 0: a sum of -0.0 values is +0.0)
+            mean1 = (0.0f + s_sum1) / (float)s_nv1;
+            mean2 = (0.0f + s_sum2) / (float)s_nv2;
         }
         // (2U, n1, n2) travel to ranksum_finish_kernel in the bits of p[row]: the double
         // precision tail (sqrt, divide, erfc) would otherwise set this kernel's VGPR budget
@@ -1270,9 +1272,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E <= 4
         const int64_t row = row0 + lane;
         const bool tested = s_nv1 >= 3 && s_nv2 >= 3;
         float mean1 = 0.f, mean2 = 0.f;
-        if (tested) {
-            mean1 = s_sum1 / (float)s_nv1;
-            mean2 = s_sum2 / (float)s_nv2;
+        if (tested) {      // (np.sum starts from the identity 0: a sum of -0.0 values is +0.0)
+            mean1 = (0.0f + s_sum1) / (float)s_nv1;
+            mean2 = (0.0f + s_sum2) / (float)s_nv2;
         }
         const unsigned long long packed =
             tested ? ((unsigned long long)(unsigned)s_u2 | ((unsigned long long)s_nv1 << 32) | ((unsigned long long)s_nv2 << 48))
