@@ -111,43 +111,13 @@ __device__ __forceinline__ float kw_wave_min(float v) {
     return v;
 }
 
-// wave_pairwise_sum of ranksum.hip over float32(key / 1000) of K[0..nv), nv <= KW_SUM_PIECE: lane = leaf * 8 + j owns
-// accumulator j of its leaf, 8 leaves per round
-__device__ __forceinline__ float kw_wave_tree_keys(const unsigned short* K, int nv, int lane, int* leaf_off, float* leaf_sum) {
-    int nl = 0;
-    pw_leaves<KW_PW_DEPTH>(0, nv, leaf_off, nl, lane == 0);
-    if (lane == 0) leaf_off[nl] = nv;
-    SD_WAVE_SYNC();
-    const int j = lane & 7;
-    for (int base = 0; base < nl; base += 8) {          // wave-uniform trip count
-        const int L = base + (lane >> 3);
-        int off = 0, len = 0;
-        if (L < nl) { off = leaf_off[L]; len = leaf_off[L + 1] - off; }
-        const int main_n = len - (len & 7);
-        float r = 0.f;
-        if (len >= 8) {
-            r = ps_of_key((float)K[off + j]);
-            for (int i = 8; i < main_n; i += 8) r += ps_of_key((float)K[off + i + j]);
-        }
-        r = r + __shfl_xor(r, 1);
-        r = r + __shfl_xor(r, 2);
-        r = r + __shfl_xor(r, 4);
-        for (int i = (len >= 8 ? main_n : 0); i < len; ++i) r += ps_of_key((float)K[off + i]);
-        if (j == 0 && L < nl) leaf_sum[L] = r;
-    }
-    SD_WAVE_SYNC();
-    int next = 0;
-    const float out = pw_combine<KW_PW_DEPTH>(nv, leaf_sum, next);
-    SD_WAVE_SYNC();
-    return out;
-}
-
-// np.sum of a contiguous float32 array: the identity 0 plus the pairwise tree of every piece of KW_SUM_PIECE values, the
-// pieces added left to right (at most two: nv <= KW_MAX_N).  The whole-array tree is a different sum above one piece.
+// np.sum of the contiguous float32 array float32(K[0..nv) / 1000): the identity 0 plus the pairwise tree of every piece
+// of KW_SUM_PIECE values, the pieces added left to right (at most two: nv <= KW_MAX_N).  The whole-array tree is a
+// different sum above one piece.
 __device__ __forceinline__ float kw_wave_sum_keys(const unsigned short* K, int nv, int lane, int* leaf_off, float* leaf_sum) {
-    float sum = 0.0f + kw_wave_tree_keys(K, min(nv, KW_SUM_PIECE), lane, leaf_off, leaf_sum);
+    float sum = 0.0f + wave_pairwise_sum<KW_PW_DEPTH>(KeyAt{K}, min(nv, KW_SUM_PIECE), lane, leaf_off, leaf_sum);
     if (nv > KW_SUM_PIECE)               // wave-uniform
-        sum += kw_wave_tree_keys(K + KW_SUM_PIECE, nv - KW_SUM_PIECE, lane, leaf_off, leaf_sum);
+        sum += wave_pairwise_sum<KW_PW_DEPTH>(KeyAt{K + KW_SUM_PIECE}, nv - KW_SUM_PIECE, lane, leaf_off, leaf_sum);
     return sum;
 }
 
@@ -186,10 +156,9 @@ __global__ void __launch_bounds__(256) kruskal_grid_kernel(const float* __restri
         bool ok = true;
         for (int j = lane; j < nsel; j += 64) {
             const float v = __builtin_nontemporal_load(prow + cols[j]);
-            // (a value outside [0, 1] clamps to a key whose float it is not: no separate range check)
-            const float kf = __builtin_amdgcn_fmed3f(rintf(v * 1000.0f), 0.0f, 1000.0f);
-            ok = ok && (v != v || ps_of_key(kf) == v);
-            keys[j] = (v != v) ? (unsigned short)0xFFFF : (unsigned short)(int)kf;
+            const PsKey pk = key_of_ps(v);
+            ok = ok && (v != v || pk.exact());
+            keys[j] = (v != v) ? (unsigned short)0xFFFF : (unsigned short)pk.key();
         }
         if (__ballot(!ok) != 0ull) {
             if (lane == ri) s_flag = KW_REDO;
@@ -243,22 +212,10 @@ __global__ void __launch_bounds__(256) kruskal_grid_kernel(const float* __restri
                 if (lane >= ofs) pre += up;
             }
             const int cum0 = pre - tot;
-            // the bin where the cumulative count crosses a middle position (as ranksum_count_kernel: the owning lane by a
-            // ballot, its 16 counters examined by lanes 0..15 together)
-            auto find_bin = [&](int target) -> int {
-                const int L = __ffsll((long long)__ballot(target >= cum0 && target < cum0 + tot)) - 1;
-                const int base = __shfl(cum0, L);
-                int inc = lane < 16 ? (int)Hset[L * 16 + lane] : 0;
-#pragma unroll
-                for (int ofs = 1; ofs < 16; ofs <<= 1) {
-                    const int up = __shfl_up(inc, ofs);
-                    if (lane >= ofs) inc += up;
-                }
-                return L * 16 + (__ffsll((long long)__ballot(lane < 16 && target < base + inc)) - 1);
-            };
+            // the median: the bins where the cumulative count crosses the middle positions
             const int hh = nv >> 1;
-            const int bin1 = find_bin(hh);
-            const int bin0 = (nv & 1) ? bin1 : find_bin(hh - 1);      // wave-uniform branch
+            const int bin1 = find_bin<0, ~0u>(Hset, lane, hh, cum0, tot);
+            const int bin0 = (nv & 1) ? bin1 : find_bin<0, ~0u>(Hset, lane, hh - 1, cum0, tot);      // wave-uniform branch
             const float v0 = ps_of_key((float)bin0), v1 = ps_of_key((float)bin1);
             const float med = (nv & 1) ? v1 : (v0 + v1) / 2.0f;       // np.median on float32
             SD_WAVE_SYNC();          // find_bin's readers are done with Hset
@@ -568,9 +525,7 @@ extern "C" int sdice_kruskal_dev(sdice_ctx* ctx, int64_t n, int32_t s, const flo
         int waves = 64 * 1024 / wstride;             // the workgroup is sized from the LDS a wave needs
         waves = waves > 4 ? 4 : (waves < 1 ? 1 : waves);
         const size_t lds = (size_t)waves * wstride;
-        const int64_t slots = (int64_t)ctx->n_cu * 32;
-        int ch = 64;
-        while (ch > 1 && sd_ceil_div(n, ch) < 2 * slots) ch >>= 1;
+        const int ch = rows_per_chunk(ctx->n_cu, n);
         int64_t blocks = sd_ceil_div(sd_ceil_div(n, ch), waves);
         const int64_t cap = (int64_t)ctx->n_cu * 32 / waves;
         if (blocks > cap) blocks = cap;

@@ -31,6 +31,8 @@
 //       LDS, binary searches for U.
 #include "common.h"
 #include <math.h>
+#include <algorithm>
+#include "rowsum.h"
 
 namespace {
 
@@ -44,6 +46,16 @@ struct RsOut {
     float* mean2;
     float* delta;
 };
+
+// (2U, n1, n2) of a tested row travel to ranksum_finish_kernel in the bits of p[row] (0 = not tested): the double
+// precision tail (sqrt, divide, erfc) would otherwise set the VGPR budget of the kernel that found them
+__device__ __forceinline__ unsigned long long rs_pack(unsigned u2, int nv1, int nv2) {
+    return (unsigned long long)u2 | ((unsigned long long)nv1 << 32) | ((unsigned long long)nv2 << 48);
+}
+struct RsCounts { long long u2; int nv1, nv2; };
+__device__ __forceinline__ RsCounts rs_unpack(unsigned long long packed) {
+    return {(long long)(packed & 0xffffffffull), (int)((packed >> 32) & 0xffff), (int)(packed >> 48)};
+}
 
 __device__ __forceinline__ void rs_finish(int nv1, int nv2, long long u2, double& z, double& p) {
     // scipy ranksums: z = (s - n1(n1+n2+1)/2) / sqrt(n1 n2 (n1+n2+1)/12), s - expected = U - n1 n2/2
@@ -125,13 +137,6 @@ __device__ __forceinline__ int lane_group(float* row, int cnt, float& mean) {
     return nv;
 }
 
-__device__ __forceinline__ float median_sorted(const float* a, int nv) {
-    // np.median: odd -> middle; even -> np.mean of the two middle values in float32
-    const int h = nv >> 1;
-    if (nv & 1) return a[h];
-    return (a[h - 1] + a[h]) / 2.0f;
-}
-
 template <int P>
 __global__ void __launch_bounds__(256) ranksum_lane_kernel(const float* __restrict__ ps, int64_t n, int s,
                                                            const int32_t* __restrict__ gsel1, const int32_t* __restrict__ gsel2, int n1, int n2,
@@ -194,7 +199,7 @@ __global__ void __launch_bounds__(256) ranksum_lane_kernel(const float* __restri
         if (rr < n) {
             const bool tested = nv1 >= 3 && nv2 >= 3;
             float med1 = 0.f, med2 = 0.f, dl = 0.f;
-            unsigned long long packed = 0;      // (2U, n1, n2) for ranksum_finish_kernel, as the wave kernel
+            unsigned long long packed = 0;
             if (tested && !(ablate & 1)) {
                 const float* A = row;
                 const float* B = row + n1;
@@ -224,7 +229,7 @@ __global__ void __launch_bounds__(256) ranksum_lane_kernel(const float* __restri
                         av = A[i < nv1 ? i : nv1 - 1];
                     }
                 }
-                packed = (unsigned long long)(unsigned)u2 | ((unsigned long long)nv1 << 32) | ((unsigned long long)nv2 << 48);
+                packed = rs_pack((unsigned)u2, nv1, nv2);
             } else {
                 mean1 = 0.f; mean2 = 0.f;
             }
@@ -323,9 +328,7 @@ __global__ void __launch_bounds__(256) ranksum_pair_kernel(const float* __restri
         const float mean_other = __shfl_xor(mean, 1);
         const int64_t rr = row0 + r;
         if (grp == 0 && rr < n) {
-            const unsigned long long packed =
-                tested ? ((unsigned long long)(unsigned)u2 | ((unsigned long long)nv1 << 32) | ((unsigned long long)nv2 << 48))
-                       : 0ull;
+            const unsigned long long packed = tested ? rs_pack(u2, nv1, nv2) : 0ull;
             o.tested[rr] = tested ? 1 : 0;
             reinterpret_cast<unsigned long long*>(o.p)[rr] = packed;
             o.med1[rr] = med; o.med2[rr] = med_other;
@@ -372,14 +375,6 @@ __device__ __forceinline__ uint32_t pk_max16(uint32_t a, uint32_t b) {
     return r.u;
 }
 __device__ __forceinline__ uint32_t swap16(uint32_t a) { return (a >> 16) | (a << 16); }
-// float32(k / 1000.0) for k = 0..1000 without the table: the product with float32(0.001) plus one residual step is
-// the correctly rounded quotient for every one of the 1001 values (checked exhaustively against the table's
-// definition, tests/test_abi_and_host.py) -- three VALU instructions instead of an LDS look-up, which is what this
-// kernel is short of
-__device__ __forceinline__ float ps_of_key(float kf) {
-    const float q = kf * 0.001f;
-    return __builtin_fmaf(__builtin_fmaf(-q, 1000.0f, kf), 0.001f, q);
-}
 __device__ __forceinline__ uint32_t lo_hi(uint32_t lo_from, uint32_t hi_from) { return (lo_from & 0xffffu) | (hi_from & 0xffff0000u); }
 
 // ascending sort of P 16-bit keys, k[r] = element r | element (r + P/2) << 16  (flip + disperse network)
@@ -467,11 +462,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))
                     const bool live = r < rows_avail;
                     // key of a value: k = rint(1000 x) when x == float32(k / 1000) exactly, 0xFFFF for NaN (and rows past the end)
                     const float a0 = x0[q], a1 = x1[q];
-                    const float kf0 = __builtin_amdgcn_fmed3f(__builtin_rintf(a0 * 1000.0f), 0.0f, 1000.0f);     // (a NaN's key is never used)
-                    const float kf1 = __builtin_amdgcn_fmed3f(__builtin_rintf(a1 * 1000.0f), 0.0f, 1000.0f);
-                    const int k0 = (int)kf0, k1 = (int)kf1;
+                    const PsKey p0 = key_of_ps(a0), p1 = key_of_ps(a1);
+                    const int k0 = p0.key(), k1 = p1.key();
                     const bool nan0 = !(a0 == a0) || !live, nan1 = !(a1 == a1) || !live;
-                    const bool bad0 = act0 && !nan0 && ps_of_key(kf0) != a0, bad1 = act1 && !nan1 && ps_of_key(kf1) != a1;
+                    const bool bad0 = act0 && !nan0 && !p0.exact(), bad1 = act1 && !nan1 && !p1.exact();
                     if (__ballot(bad0 || bad1)) redo_rows |= 1u << r;
                     const uint32_t kk0 = (act0 && !nan0) ? (uint32_t)k0 : 0xFFFFu, kk1 = (act1 && !nan1) ? (uint32_t)k1 : 0xFFFFu;
                     tile32[r * pitch32 + lane + (lane >> 5)] = kk0 | (kk1 << 16);      // (group 2 starts at dword 33)
@@ -584,9 +578,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))
         const int64_t rr = row0 + r;
         if (grp == 0 && rr < n) {
             const bool redo = (redo_rows >> r) & 1u;
-            const unsigned long long packed =
-                (tested && !redo) ? ((unsigned long long)(unsigned)u2 | ((unsigned long long)nv1 << 32) | ((unsigned long long)nv2 << 48))
-                                  : 0ull;
+            const unsigned long long packed = (tested && !redo) ? rs_pack(u2, nv1, nv2) : 0ull;
             o.tested[rr] = redo ? RS_REDO_Q : (tested ? 1 : 0);
             reinterpret_cast<unsigned long long*>(o.p)[rr] = packed;
             o.med1[rr] = med; o.med2[rr] = med_other;
@@ -598,104 +590,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))
 }
 
 // ------------------------------------------------------------------ block-per-row variant
-constexpr int RB_THREADS = 256;
-
-// ordered compaction of the non-NaN values of ps[row, idx[0..cnt)] into dst; returns count
-__device__ int block_compact(const float* __restrict__ prow, const int32_t* __restrict__ idx, int cnt,
-                             float* dst, int* wcnt /* [RB_THREADS/64 + 1] shared */) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    int base = 0;
-    for (int c0 = 0; c0 < cnt; c0 += RB_THREADS) {
-        const int k = c0 + tid;
-        float x = __builtin_nanf("");
-        if (k < cnt) x = prow[idx[k]];
-        const bool valid = x == x;
-        const unsigned long long m = __ballot(valid);
-        const int pre = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) wcnt[w] = __popcll(m);
-        __syncthreads();
-        int woff = 0, tot = 0;
-        for (int q = 0; q < RB_THREADS / 64; ++q) {
-            if (q < w) woff += wcnt[q];
-            tot += wcnt[q];
-        }
-        if (valid) dst[base + woff + pre] = x;
-        base += tot;
-        __syncthreads();
-    }
-    return base;
-}
-
-// numpy's pairwise_sum recursion  `n <= 128 ? leaf : sum(a, n2) + sum(a + n2, n - n2)`,
-// n2 = n/2 - (n/2) % 8, unrolled at compile time to PW_DEPTH levels.  The larger half is up to
-// len/2 + 7.5, so 4096 values can need SIX levels (4095 -> 2055 -> 1031 -> 519 -> 263 -> 135 -> 71)
-// and up to 64 leaves.  Every thread walks it redundantly with block-uniform arguments: no stacks,
-// no single-lane section.
-constexpr int PW_DEPTH = 6;
-
-template <int DEPTH>
-__device__ __forceinline__ void pw_leaves(int off, int len, int* leaf_off, int& nl, bool writer) {
-    if (DEPTH == 0 || len <= 128) {
-        if (writer) leaf_off[nl] = off;
-        ++nl;
-    } else {
-        int n2 = len / 2;
-        n2 -= n2 % 8;
-        pw_leaves<(DEPTH > 0 ? DEPTH - 1 : 0)>(off, n2, leaf_off, nl, writer);
-        pw_leaves<(DEPTH > 0 ? DEPTH - 1 : 0)>(off + n2, len - n2, leaf_off, nl, writer);
-    }
-}
-
-template <int DEPTH>
-__device__ __forceinline__ float pw_combine(int len, const float* leaf_sum, int& next) {
-    if (DEPTH == 0 || len <= 128) return leaf_sum[next++];
-    int n2 = len / 2;
-    n2 -= n2 % 8;
-    const float l = pw_combine<(DEPTH > 0 ? DEPTH - 1 : 0)>(n2, leaf_sum, next);
-    const float r = pw_combine<(DEPTH > 0 ? DEPTH - 1 : 0)>(len - n2, leaf_sum, next);
-    return l + r;
-}
-
-// numpy pairwise_sum over a[0..n) in float32 by the whole block; result to all threads
-__device__ float block_pairwise_sum(const float* a, int n, int* leaf_off /*[LEAF_MAX+1]*/, float* leaf_sum,
-                                    float* scratch8 /* [LEAF_MAX*8] */, int leaf_max) {
-    const int tid = threadIdx.x;
-    (void)leaf_max;
-    int nl = 0;
-    pw_leaves<PW_DEPTH>(0, n, leaf_off, nl, tid == 0);
-    if (tid == 0) leaf_off[nl] = n;
-    __syncthreads();
-    for (int t = tid; t < nl * 8; t += blockDim.x) {
-        const int L = t >> 3, j = t & 7;
-        const int off = leaf_off[L], len = leaf_off[L + 1] - off;
-        float r = 0.f;
-        if (len >= 8) {
-            r = a[off + j];
-            for (int i = 8; i < len - (len % 8); i += 8) r += a[off + i + j];
-        }
-        scratch8[t] = r;
-    }
-    __syncthreads();
-    for (int L = tid; L < nl; L += blockDim.x) {
-        const int off = leaf_off[L], len = leaf_off[L + 1] - off;
-        float res;
-        if (len < 8) {
-            res = 0.f;
-            for (int i = 0; i < len; ++i) res += a[off + i];
-        } else {
-            const float* r = scratch8 + L * 8;
-            res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-            for (int i = len - (len % 8); i < len; ++i) res += a[off + i];
-        }
-        leaf_sum[L] = res;
-    }
-    __syncthreads();
-    int next = 0;
-    const float out = pw_combine<PW_DEPTH>(n, leaf_sum, next);
-    __syncthreads();      // leaf_sum / leaf_off are reused by the next call
-    return out;
-}
-
 __global__ void __launch_bounds__(RB_THREADS) ranksum_block_kernel(const float* __restrict__ ps, int64_t n, int s,
                                                                    const int32_t* __restrict__ g1, int n1,
                                                                    const int32_t* __restrict__ g2, int n2, int P1,
@@ -724,8 +618,8 @@ __global__ void __launch_bounds__(RB_THREADS) ranksum_block_kernel(const float* 
             __syncthreads();
             continue;
         }
-        const float sum1 = block_pairwise_sum(A, nv1, leaf_off, leaf_sum, scratch8, leaf_max);
-        const float sum2 = block_pairwise_sum(B, nv2, leaf_off, leaf_sum, scratch8, leaf_max);
+        const float sum1 = block_pairwise_sum<PW_DEPTH>(A, nv1, leaf_off, leaf_sum, scratch8, leaf_max);
+        const float sum2 = block_pairwise_sum<PW_DEPTH>(B, nv2, leaf_off, leaf_sum, scratch8, leaf_max);
         for (int i = nv1 + tid; i < P1; i += RB_THREADS) A[i] = inf;
         for (int i = nv2 + tid; i < P2; i += RB_THREADS) B[i] = inf;
         if (tid == 0) u2_s = 0;
@@ -781,11 +675,6 @@ __global__ void __launch_bounds__(RB_THREADS) ranksum_block_kernel(const float* 
     }
 }
 
-// number of set bits of a wave mask below this lane (v_mbcnt_lo + v_mbcnt_hi: two instructions, no 64-bit mask per lane)
-__device__ __forceinline__ int lanes_below(unsigned long long m, int base = 0) {
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, (uint32_t)base));
-}
-
 // ------------------------------------------------------------------ wave-per-row variant
 // 64 < max(n1, n2) <= 64*E: one WAVE per row, E values of a group per lane, no workgroup
 // barrier anywhere.  The sort is a bitonic network over 64*E elements in "blocked" layout
@@ -793,13 +682,6 @@ __device__ __forceinline__ int lanes_below(unsigned long long m, int base = 0) {
 // are register-to-register, the others are one cross-lane exchange per register.  The
 // per-wave LDS buffers hold the compacted (then sorted) groups for the mean, the medians and
 // the binary searches of the U statistic.
-#define SD_WAVE_SYNC()                                        \
-    do {                                                      \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \
-        __builtin_amdgcn_wave_barrier();                      \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); \
-    } while (0)
-
 template <int E>
 __device__ __forceinline__ void bitonic_wave(float (&a)[E], int lane) {
 #pragma unroll
@@ -837,41 +719,10 @@ __device__ __forceinline__ void bitonic_wave(float (&a)[E], int lane) {
     }
 }
 
-// numpy pairwise_sum of C[0..nv) (nv <= 1024) by one wave: lane = leaf*8 + j owns accumulator j
-// of its leaf; the 8 accumulators are folded with three xor-exchanges, which reproduces
-// ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) because float addition is commutative.  The halving keeps
-// multiples of 8 on the left, so the larger half is up to len/2 + 7.5: 1024 values need up to FOUR
-// levels (e.g. 972 -> 492 -> 252 -> 132 -> 68) and up to 16 leaves -- two rounds of 8 leaves.
+// wave_pairwise_sum over a group of at most 1024 values: the halving keeps multiples of 8 on the left, so the larger half
+// is up to len/2 + 7.5 and 1024 values need up to FOUR levels (e.g. 972 -> 492 -> 252 -> 132 -> 68) and up to 16
+// leaves -- two rounds of 8 leaves.
 constexpr int PW_WAVE_DEPTH = 4;
-
-__device__ __forceinline__ float wave_pairwise_sum(const float* C, int nv, int lane, int* leaf_off, float* leaf_sum) {
-    int nl = 0;
-    pw_leaves<PW_WAVE_DEPTH>(0, nv, leaf_off, nl, lane == 0);
-    if (lane == 0) leaf_off[nl] = nv;
-    SD_WAVE_SYNC();
-    const int j = lane & 7;
-    for (int base = 0; base < nl; base += 8) {          // wave-uniform trip count
-        const int L = base + (lane >> 3);
-        int off = 0, len = 0;
-        if (L < nl) { off = leaf_off[L]; len = leaf_off[L + 1] - off; }
-        const int main_n = len - (len & 7);
-        float r = 0.f;
-        if (len >= 8) {
-            r = C[off + j];
-            for (int i = 8; i < main_n; i += 8) r += C[off + i + j];
-        }
-        r = r + __shfl_xor(r, 1);
-        r = r + __shfl_xor(r, 2);
-        r = r + __shfl_xor(r, 4);
-        for (int i = (len >= 8 ? main_n : 0); i < len; ++i) r += C[off + i];
-        if (j == 0 && L < nl) leaf_sum[L] = r;
-    }
-    SD_WAVE_SYNC();
-    int next = 0;
-    const float out = pw_combine<PW_WAVE_DEPTH>(nv, leaf_sum, next);
-    SD_WAVE_SYNC();
-    return out;
-}
 
 constexpr unsigned char RS_REDO = 0xFF;     // `tested` mark: row left to the sorting kernel by ranksum_count_kernel
 
@@ -942,8 +793,8 @@ __global__ void __launch_bounds__(256) ranksum_wave_kernel(const float* __restri
             if (lane == ri) { s_nv1 = nv1; s_nv2 = nv2; }
             continue;
         }
-        const float sum1 = wave_pairwise_sum(SA, nv1, lane, leaf_off, leaf_sum);
-        const float sum2 = wave_pairwise_sum(SB, nv2, lane, leaf_off, leaf_sum);
+        const float sum1 = wave_pairwise_sum<PW_WAVE_DEPTH>(FloatAt{SA}, nv1, lane, leaf_off, leaf_sum);
+        const float sum2 = wave_pairwise_sum<PW_WAVE_DEPTH>(FloatAt{SB}, nv2, lane, leaf_off, leaf_sum);
         // sort group 2 then group 1 through one copy of the network; x ends up holding sorted A
 #pragma nounroll
         for (int gi = 1; gi >= 0; --gi) {
@@ -997,11 +848,7 @@ __global__ void __launch_bounds__(256) ranksum_wave_kernel(const float* __restri
             mean1 = (0.0f + s_sum1) / (float)s_nv1;
             mean2 = (0.0f + s_sum2) / (float)s_nv2;
         }
-        // (2U, n1, n2) travel to ranksum_finish_kernel in the bits of p[row]: the double
-        // precision tail (sqrt, divide, erfc) would otherwise set this kernel's VGPR budget
-        const unsigned long long packed =
-            tested ? ((unsigned long long)(unsigned)s_u2 | ((unsigned long long)s_nv1 << 32) | ((unsigned long long)s_nv2 << 48))
-                   : 0ull;
+        const unsigned long long packed = tested ? rs_pack(s_u2, s_nv1, s_nv2) : 0ull;
         o.tested[row] = tested ? 1 : 0;
         reinterpret_cast<unsigned long long*>(o.p)[row] = packed;
         o.med1[row] = s_med1; o.med2[row] = s_med2;
@@ -1119,17 +966,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E <= 4
             {
                 // (a value outside [0, 1] clamps to a key whose float it is not: no separate range check; arithmetic, no table)
                 const float v = x[e];
-                const float kf = __builtin_amdgcn_fmed3f(rintf(v * 1000.0f), 0.0f, 1000.0f);
-                const int k = (int)kf;
-                ok = ok && (v != v || ps_of_key(kf) == v);
-                packed_k = (v != v) ? 0u : (unsigned)(k + 1);
+                const PsKey pk = key_of_ps(v);
+                ok = ok && (v != v || pk.exact());
+                packed_k = (v != v) ? 0u : (unsigned)(pk.key() + 1);
             }
             {
                 const float v = y[e];
-                const float kf = __builtin_amdgcn_fmed3f(rintf(v * 1000.0f), 0.0f, 1000.0f);
-                const int k = (int)kf;
-                ok = ok && (v != v || ps_of_key(kf) == v);
-                packed_k |= (v != v) ? 0u : ((unsigned)(k + 1) << 16);
+                const PsKey pk = key_of_ps(v);
+                ok = ok && (v != v || pk.exact());
+                packed_k |= (v != v) ? 0u : ((unsigned)(pk.key() + 1) << 16);
             }
             kk[e] = packed_k;
         }
@@ -1179,8 +1024,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E <= 4
         if (E <= 8) {
             wave_pairwise_sum2(SA, nv1, SB, nv2, lane, leaf_off, leaf_sum, sum1, sum2);
         } else {
-            sum1 = wave_pairwise_sum(SA, nv1, lane, leaf_off, leaf_sum);
-            sum2 = wave_pairwise_sum(SB, nv2, lane, leaf_off, leaf_sum);
+            sum1 = wave_pairwise_sum<PW_WAVE_DEPTH>(FloatAt{SA}, nv1, lane, leaf_off, leaf_sum);
+            sum2 = wave_pairwise_sum<PW_WAVE_DEPTH>(FloatAt{SB}, nv2, lane, leaf_off, leaf_sum);
         }
         if (H_ALIAS) {
             SD_WAVE_SYNC();                 // every lane has read its values
@@ -1239,26 +1084,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E <= 4
         }
 #pragma unroll
         for (int ofs = 32; ofs > 0; ofs >>= 1) local += __shfl_xor(local, ofs);
-        // medians: the bin where a group's cumulative count crosses a middle position.  The lane whose 16
-        // bins contain the position is found with a ballot; its 16 counters are then examined by lanes
-        // 0..15 together (prefix by shuffles, crossing by a second ballot) -- uniform, no divergent walk.
-        auto find_bin = [&](int target, bool second) -> int {
-            const int c0 = second ? cumB0 : cumA0, tt = second ? totB : totA;
-            const int L = __ffsll((long long)__ballot(target >= c0 && target < c0 + tt)) - 1;
-            const int base = __shfl(c0, L);
-            const unsigned wq = lane < 16 ? H[L * 16 + lane] : 0u;
-            int inc = second ? (int)(wq >> 16) : (int)(wq & 0xffffu);
-#pragma unroll
-            for (int ofs = 1; ofs < 16; ofs <<= 1) {
-                const int up = __shfl_up(inc, ofs);
-                if (lane >= ofs) inc += up;
-            }
-            return L * 16 + (__ffsll((long long)__ballot(lane < 16 && target < base + inc)) - 1);
-        };
+        // medians: the bins where a group's cumulative count crosses the middle positions (group 1 in the low halves)
         const int hA = nv1 >> 1, hB = nv2 >> 1;
-        const int binA1 = find_bin(hA, false), binB1 = find_bin(hB, true);
-        const int binA0 = (nv1 & 1) ? binA1 : find_bin(hA - 1, false);      // wave-uniform branches
-        const int binB0 = (nv2 & 1) ? binB1 : find_bin(hB - 1, true);
+        const int binA1 = find_bin<0, 0xffffu>(H, lane, hA, cumA0, totA), binB1 = find_bin<16, 0xffffu>(H, lane, hB, cumB0, totB);
+        const int binA0 = (nv1 & 1) ? binA1 : find_bin<0, 0xffffu>(H, lane, hA - 1, cumA0, totA);      // wave-uniform branches
+        const int binB0 = (nv2 & 1) ? binB1 : find_bin<16, 0xffffu>(H, lane, hB - 1, cumB0, totB);
         // np.median: odd -> middle value; even -> (v[h-1] + v[h]) / 2 in float32
         const float a0 = ps_of_key((float)binA0), a1 = ps_of_key((float)binA1), b0 = ps_of_key((float)binB0), b1 = ps_of_key((float)binB1);
         const float med1 = (nv1 & 1) ? a1 : (a0 + a1) / 2.0f;
@@ -1276,9 +1106,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E <= 4
             mean1 = (0.0f + s_sum1) / (float)s_nv1;
             mean2 = (0.0f + s_sum2) / (float)s_nv2;
         }
-        const unsigned long long packed =
-            tested ? ((unsigned long long)(unsigned)s_u2 | ((unsigned long long)s_nv1 << 32) | ((unsigned long long)s_nv2 << 48))
-                   : 0ull;
+        const unsigned long long packed = tested ? rs_pack(s_u2, s_nv1, s_nv2) : 0ull;
         o.tested[row] = s_redo ? RS_REDO : (tested ? 1 : 0);
         reinterpret_cast<unsigned long long*>(o.p)[row] = packed;
         o.med1[row] = s_med1; o.med2[row] = s_med2;
@@ -1294,38 +1122,55 @@ __global__ void __launch_bounds__(256) ranksum_finish_kernel(int64_t n, double* 
     if (row >= n) return;
     const unsigned long long packed = reinterpret_cast<const unsigned long long*>(p_io)[row];
     double z = 0.0, p = 0.0;
-    if (packed) rs_finish((int)((packed >> 32) & 0xffff), (int)(packed >> 48), (long long)(packed & 0xffffffffull), z, p);
+    if (packed) {
+        const RsCounts c = rs_unpack(packed);
+        rs_finish(c.nv1, c.nv2, c.u2, z, p);
+    }
     p_io[row] = p;
     if (z_out) z_out[row] = z;
 }
 
 int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
-template <int E>
-int launch_wave(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* g1, int n1, const int32_t* g2,
-                int n2, RsOut o, bool counting) {
-    const int waves = 4;
-    const size_t lds = (size_t)waves * (2 * 64 * E + 40) * 4;
-    // rows per chunk: as many as keeps every wave slot of the chip (32 per CU) busy twice over
-    const int64_t slots = (int64_t)ctx->n_cu * 32;
-    int ch = 64;
-    while (ch > 1 && sd_ceil_div(n, ch) < 2 * slots) ch >>= 1;
-    int64_t blocks = sd_ceil_div(sd_ceil_div(n, ch), waves);
-    const int64_t cap = (int64_t)ctx->n_cu * 8;
-    if (blocks > cap) blocks = cap;
-    if (counting) {
-        // histogram path for rows of 3-decimal PS values; the sorting kernel then takes the rows it marked
-        const size_t lds_c = (size_t)(waves * (2 * 64 * E + 40 + (2 * 64 * E >= RS_BINS ? 0 : RS_BINS) + 8)) * 4;
-        SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ranksum_count_kernel<E>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
-        SD_LAUNCH(ctx, "ranksum_count_kernel", (ranksum_count_kernel<E>), dim3((unsigned)blocks), dim3(waves * 64), lds_c,
-                  d_ps, n, s, g1, n1, g2, n2, ch, (int)ctx->param(SD_P_RANKSUM_ABLATE), o);
-    }
-    SD_LAUNCH(ctx, "ranksum_wave_kernel", (ranksum_wave_kernel<E>), dim3((unsigned)blocks), dim3(waves * 64), lds, d_ps, n,
-              s, g1, n1, g2, n2, ch, counting ? 1 : 0, o);
+// the double precision tail of every kernel that leaves (2U, n1, n2) in p[row]
+int launch_finish(sdice_ctx* ctx, int64_t n, RsOut o) {
     SD_LAUNCH(ctx, "ranksum_finish_kernel", ranksum_finish_kernel, dim3((unsigned)sd_ceil_div(n, 256)), dim3(256), 0, n,
               o.p, o.z);
     return SDICE_OK;
+}
+
+// grid of the wave-per-row kernels (4 waves per workgroup, `ch` rows per wave and chunk)
+int64_t wave_blocks(sdice_ctx* ctx, int64_t n, int ch) {
+    return std::min(sd_ceil_div(sd_ceil_div(n, ch), 4), (int64_t)ctx->n_cu * 8);
+}
+
+// the sorting wave kernel over every row, or (redo_only) over the rows a key kernel marked RS_REDO
+template <int E>
+int launch_wave_sort(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* g1, int n1, const int32_t* g2,
+                     int n2, RsOut o, bool redo_only) {
+    const int waves = 4;
+    const size_t lds = (size_t)waves * (2 * 64 * E + 40) * 4;
+    const int ch = rows_per_chunk(ctx->n_cu, n);
+    SD_LAUNCH(ctx, "ranksum_wave_kernel", (ranksum_wave_kernel<E>), dim3((unsigned)wave_blocks(ctx, n, ch)), dim3(waves * 64),
+              lds, d_ps, n, s, g1, n1, g2, n2, ch, redo_only ? 1 : 0, o);
+    return SDICE_OK;
+}
+
+template <int E>
+int launch_wave(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* g1, int n1, const int32_t* g2,
+                int n2, RsOut o, bool counting) {
+    if (counting) {
+        // histogram path for rows of 3-decimal PS values; the sorting kernel then takes the rows it marked
+        const int waves = 4;
+        const int ch = rows_per_chunk(ctx->n_cu, n);
+        const size_t lds_c = (size_t)(waves * (2 * 64 * E + 40 + (2 * 64 * E >= RS_BINS ? 0 : RS_BINS) + 8)) * 4;
+        SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ranksum_count_kernel<E>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
+        SD_LAUNCH(ctx, "ranksum_count_kernel", (ranksum_count_kernel<E>), dim3((unsigned)wave_blocks(ctx, n, ch)),
+                  dim3(waves * 64), lds_c, d_ps, n, s, g1, n1, g2, n2, ch, (int)ctx->param(SD_P_RANKSUM_ABLATE), o);
+    }
+    SD_TRY(launch_wave_sort<E>(ctx, d_ps, n, s, g1, n1, g2, n2, o, counting));
+    return launch_finish(ctx, n, o);
 }
 
 template <int P>
@@ -1341,9 +1186,7 @@ int launch_lane(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     SD_LAUNCH(ctx, "ranksum_lane_kernel", (ranksum_lane_kernel<P>), dim3((unsigned)blocks), dim3(waves * 64), lds, d_ps, n,
               s, g1, g2, n1, n2, stride, o, (int)ctx->param(SD_P_RANKSUM_ABLATE));
-    SD_LAUNCH(ctx, "ranksum_finish_kernel", ranksum_finish_kernel, dim3((unsigned)sd_ceil_div(n, 256)), dim3(256), 0, n,
-              o.p, o.z);
-    return SDICE_OK;
+    return launch_finish(ctx, n, o);
 }
 
 template <int P>
@@ -1358,9 +1201,7 @@ int launch_pair(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     SD_LAUNCH(ctx, "ranksum_pair_kernel", (ranksum_pair_kernel<P>), dim3((unsigned)blocks), dim3(waves * 64), lds, d_ps, n,
               s, g1, g2, n1, n2, stride, o);
-    SD_LAUNCH(ctx, "ranksum_finish_kernel", ranksum_finish_kernel, dim3((unsigned)sd_ceil_div(n, 256)), dim3(256), 0, n,
-              o.p, o.z);
-    return SDICE_OK;
+    return launch_finish(ctx, n, o);
 }
 
 // 16-bit-key lane-pair kernel, then the sorting wave kernel over the rows it marked (non 3-decimal values)
@@ -1378,20 +1219,8 @@ int launch_pairq(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int3
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     SD_LAUNCH(ctx, "ranksum_pairq_kernel", (ranksum_pairq_kernel<P>), dim3((unsigned)blocks), dim3(waves * 64), lds, d_ps, n,
               s, g1, g2, n1, n2, stride, o);
-    {   // rows marked RS_REDO (a value that is not float32(k/1000)): the float sorting kernel, marked rows only
-        const int ww = 4;
-        const size_t lds_w = (size_t)ww * (2 * 64 + 40) * 4;
-        const int64_t slots = (int64_t)ctx->n_cu * 32;
-        int ch = 64;
-        while (ch > 1 && sd_ceil_div(n, ch) < 2 * slots) ch >>= 1;
-        int64_t wb = sd_ceil_div(sd_ceil_div(n, ch), ww);
-        if (wb > (int64_t)ctx->n_cu * 8) wb = (int64_t)ctx->n_cu * 8;
-        SD_LAUNCH(ctx, "ranksum_wave_kernel", (ranksum_wave_kernel<1>), dim3((unsigned)wb), dim3(ww * 64), lds_w, d_ps, n, s, g1,
-                  n1, g2, n2, ch, 1, o);
-    }
-    SD_LAUNCH(ctx, "ranksum_finish_kernel", ranksum_finish_kernel, dim3((unsigned)sd_ceil_div(n, 256)), dim3(256), 0, n,
-              o.p, o.z);
-    return SDICE_OK;
+    SD_TRY(launch_wave_sort<1>(ctx, d_ps, n, s, g1, n1, g2, n2, o, true));
+    return launch_finish(ctx, n, o);
 }
 
 }  // namespace

@@ -1,9 +1,10 @@
-// Per-row device helpers of the rank tests, lifted from ranksum.hip word for word for kruskal.hip: numpy's float32
-// pairwise summation reproduced operation for operation, the ordered NaN-dropping compaction of a row's selected columns,
-// np.median of a sorted run, and the float of a 3-decimal PS key.  ranksum.hip still carries its own copies: its source
-// file stamps the committed counter pass that bench.py quotes (kernel_source_sha16), so it is left byte for byte as it
-// was; when that pass is next retaken, ranksum.hip should include this header instead (the device code of its kernels
-// came out identical with the include in place).
+// Per-row device helpers that the rank tests share (ranksum.hip: K5, kruskal.hip: K12): numpy's float32 pairwise
+// summation reproduced operation for operation (by a block and by a wave), the ordered NaN-dropping compaction of a
+// row's selected columns, np.median of a sorted run, the 3-decimal PS key of a float and its float back, the median
+// search in the 16-bins-per-lane histograms of the counting kernels, and the rows-per-wave chunk of their launches.
+// Every helper is inlined into the kernels that call it and the kernels themselves stay in their .hip files, so a change
+// to a helper here is a change to each kernel that uses it -- ranksum.hip's pairq and count kernels among them, whose
+// committed counter pass is stamped with the hash of ranksum.hip alone and will not notice.
 #pragma once
 #include "common.h"
 
@@ -134,5 +135,85 @@ __device__ float block_pairwise_sum(const float* a, int n, int* leaf_off /*[LEAF
 // number of set bits of a wave mask below this lane (v_mbcnt_lo + v_mbcnt_hi: two instructions, no 64-bit mask per lane)
 __device__ __forceinline__ int lanes_below(unsigned long long m, int base = 0) {
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, (uint32_t)base));
+}
+
+// key of a PS value v: rint(1000 v) clamped to 0..1000 (a value outside [0, 1] clamps to a key whose float it is not: no
+// separate range check), and whether v is exactly float32(key / 1000).  A NaN is not exact and its key is never used.
+// exact() is evaluated where it is asked for, so a caller's `a || b.exact()` skips it as the written-out test did.
+struct PsKey {
+    float v, kf;
+    __device__ __forceinline__ int key() const { return (int)kf; }
+    __device__ __forceinline__ bool exact() const { return ps_of_key(kf) == v; }
+};
+__device__ __forceinline__ PsKey key_of_ps(float v) {
+    return {v, __builtin_amdgcn_fmed3f(__builtin_rintf(v * 1000.0f), 0.0f, 1000.0f)};
+}
+
+// element loaders of wave_pairwise_sum: floats as they are, 16-bit keys as float32(key / 1000)
+struct FloatAt { const float* a; __device__ __forceinline__ float operator()(int i) const { return a[i]; } };
+struct KeyAt { const unsigned short* k; __device__ __forceinline__ float operator()(int i) const { return ps_of_key((float)k[i]); } };
+
+// numpy pairwise_sum of at(0..nv) by one wave, nv needing at most DEPTH halvings: lane = leaf*8 + j owns accumulator j
+// of its leaf, 8 leaves per round; the 8 accumulators are folded with three xor-exchanges, which reproduces
+// ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) because float addition is commutative.  leaf_off [2^DEPTH + 1] and leaf_sum
+// [2^DEPTH] are the wave's own LDS.
+template <int DEPTH, class At>
+__device__ __forceinline__ float wave_pairwise_sum(At at, int nv, int lane, int* leaf_off, float* leaf_sum) {
+    int nl = 0;
+    pw_leaves<DEPTH>(0, nv, leaf_off, nl, lane == 0);
+    if (lane == 0) leaf_off[nl] = nv;
+    SD_WAVE_SYNC();
+    const int j = lane & 7;
+    for (int base = 0; base < nl; base += 8) {          // wave-uniform trip count
+        const int L = base + (lane >> 3);
+        int off = 0, len = 0;
+        if (L < nl) { off = leaf_off[L]; len = leaf_off[L + 1] - off; }
+        const int main_n = len - (len & 7);
+        float r = 0.f;
+        if (len >= 8) {
+            r = at(off + j);
+            for (int i = 8; i < main_n; i += 8) r += at(off + i + j);
+        }
+        r = r + __shfl_xor(r, 1);
+        r = r + __shfl_xor(r, 2);
+        r = r + __shfl_xor(r, 4);
+        for (int i = (len >= 8 ? main_n : 0); i < len; ++i) r += at(off + i);
+        if (j == 0 && L < nl) leaf_sum[L] = r;
+    }
+    SD_WAVE_SYNC();
+    int next = 0;
+    const float out = pw_combine<DEPTH>(nv, leaf_sum, next);
+    SD_WAVE_SYNC();
+    return out;
+}
+
+// Histogram of 1024 bins scanned by one wave, lane owns bins [16 lane, 16 lane + 16): the bin where the cumulative
+// count crosses position `target`.  cum0 / tot are this lane's count below its 16 bins and inside them, a bin's count is
+// (H[bin] >> SHIFT) & MASK.  The lane whose 16 bins contain the position is found with a ballot; its 16 counters are
+// then examined by lanes 0..15 together (prefix by shuffles, crossing by a second ballot) -- uniform, no divergent walk.
+// (The caller's values by reference: with by-value parameters the counting and the grid kernel are allocated a register
+// or two fewer and come out up to 26 instructions longer or shorter; this way their code is what it was with the
+// search written out in each.)
+template <int SHIFT, unsigned MASK>
+__device__ __forceinline__ int find_bin(const unsigned* const& H, const int& lane, int target, const int& cum0, const int& tot) {
+    const int L = __ffsll((long long)__ballot(target >= cum0 && target < cum0 + tot)) - 1;
+    const int base = __shfl(cum0, L);
+    const unsigned wq = lane < 16 ? H[L * 16 + lane] : 0u;
+    int inc = (int)((wq >> SHIFT) & MASK);
+#pragma unroll
+    for (int ofs = 1; ofs < 16; ofs <<= 1) {
+        const int up = __shfl_up(inc, ofs);
+        if (lane >= ofs) inc += up;
+    }
+    return L * 16 + (__ffsll((long long)__ballot(lane < 16 && target < base + inc)) - 1);
+}
+
+// Host: rows of one wave's chunk in the wave-per-row kernels -- as many (64 at most) as keeps every wave slot of the
+// chip (32 per CU) busy twice over
+inline int rows_per_chunk(int n_cu, int64_t n) {
+    const int64_t slots = (int64_t)n_cu * 32;
+    int ch = 64;
+    while (ch > 1 && sd_ceil_div(n, ch) < 2 * slots) ch >>= 1;
+    return ch;
 }
 }  // namespace

@@ -532,7 +532,7 @@ def test_rank_over_m_by_reciprocal(tmp_path):
 
 
 def test_ps_of_key_formula_reproduces_the_table():
-    """ranksum.hip ps_of_key(): q = k * 0.001f; q = fma(fma(-q, 1000, k), 0.001f, q) must equal float32(k / 1000.0)
+    """csrc/rowsum.h ps_of_key(): q = k * 0.001f; q = fma(fma(-q, 1000, k), 0.001f, q) must equal float32(k / 1000.0)
     (the '.3f' text read back as float32, compareSampleSets.py:202) for every k = 0..1000 -- exact rational
     arithmetic with one correct rounding per float32 operation."""
     from fractions import Fraction
