@@ -445,10 +445,13 @@ __device__ __forceinline__ unsigned wave_max_dpp(unsigned x) {
 // (which gives the tile's count bound for free; an LDS-DMA staging, global_load_lds_dwordx4, was built in round 3,
 // bit-exact and slower -- DESIGN appendix A.3):
 //   * EVERY global load of the tile is issued before the first one is waited for: the tile's own rows (up to four
-//     vectors per thread), then -- behind one scalar-load round trip for the first / last row pointer and the reach
-//     words -- the halo rows the lists really reach (reach words of the clustering kernel, 16 rows in all on
-//     gene-shaped data instead of 2 x 16), the neighbour indices and the row pointers; hipcc's counted vmcnt waits
-//     then retire them in issue order while the data moves to LDS;
+//     vectors per thread) but the last vector a tile of this shape has, then -- behind one scalar-load round trip for
+//     the first / last row pointer and the reach words -- the halo rows below the tile that the lists really reach
+//     (reach words of the clustering kernel, 16 rows in all on gene-shaped data instead of 2 x 16), the neighbour
+//     indices and the row pointers, and last the tile's last own vector and the halo rows above it; hipcc's counted
+//     vmcnt waits then retire them in issue order while the data moves to LDS, so the lists and the low end of the
+//     window stand in LDS while the high end is still landing.  An own vector that no tile of the launch has (the
+//     fourth at 96-row tiles of 128-column chunks) is not loaded at all;
 //   * one workgroup barrier: the count bound goes through one LDS word per wave (DPP reduction, sixteen broadcast
 //     reads after the barrier), the degree enters per item: an item is fast iff (degree + 1) * bound < 2^24.
 template <bool CHUNKED, bool WEXCL, bool WPS, bool Q3>
@@ -492,31 +495,36 @@ __global__ void __launch_bounds__(1024, 8) ps_tile_v3_kernel(PsArgs a) {
     const int zero_off = win_cap * a.chunk_cols * 4;
     int4* win4 = reinterpret_cast<int4*>(tileL);
 
-    // ---- (1) the tile's own rows: up to four vectors per thread, all in flight
+    // ---- (1) the tile's own rows, up to four vectors per thread: slots 0, 1 and -- where tiles have a fourth vector --
+    // 2 go out now; slot 3 is the LAST vector a tile of this shape has (its third or fourth) and goes out in (6).  A
+    // vector that no tile of this launch has is not loaded (wave-uniform branches)
     const char* gtile = reinterpret_cast<const char*>(a.counts + (int64_t)r0 * a.s + c0);
     const int64_t row_stride = (int64_t)a.s * 4;
     const int ctot = nr * LV;
+    const int tvec = a.tile_rows * LV;                     // (uniform)
+    const bool grp3 = tvec > 2 * T, grp4 = tvec > 3 * T;
     int4 cv[4];
     bool cok[4];
-    {
-        // unconditional loads at clamped positions (a predicated load drags exec-mask code and early waits into the
-        // sequence); the predicate acts on the LDS store
-        const int4* g[4];
+    int cdst[4];                                            // LDS vector index
+    const int4* g[4];
+    // unconditional loads at clamped positions (a predicated load drags exec-mask code and early waits into the
+    // sequence); the predicate acts on the LDS store
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int idx = tid + k * T;
-            cok[k] = idx < ctot;
-            const int ic = min(idx, ctot - 1);
-            if (!CHUNKED) g[k] = reinterpret_cast<const int4*>(gtile) + ic;
-            else {
-                const int rr = ic >> lsh, cc = ic & (LV - 1);
-                cok[k] = cok[k] && cc < V;
-                g[k] = reinterpret_cast<const int4*>(gtile + rr * row_stride) + min(cc, V - 1);
-            }
+    for (int k = 0; k < 4; ++k) {
+        const int idx = tid + (k < 3 ? k : (grp4 ? 3 : 2)) * T;
+        cok[k] = idx < ctot && (k < 2 || (k == 2 ? grp4 : grp3));
+        cdst[k] = a.halo * LV + idx;
+        const int ic = min(idx, ctot - 1);
+        if (!CHUNKED) g[k] = reinterpret_cast<const int4*>(gtile) + ic;
+        else {
+            const int rr = ic >> lsh, cc = ic & (LV - 1);
+            cok[k] = cok[k] && cc < V;
+            g[k] = reinterpret_cast<const int4*>(gtile + rr * row_stride) + min(cc, V - 1);
         }
-        if (a.nt) { cv[0] = nt_load(g[0]); cv[1] = nt_load(g[1]); cv[2] = nt_load(g[2]); cv[3] = nt_load(g[3]); }
-        else      { cv[0] = *g[0]; cv[1] = *g[1]; cv[2] = *g[2]; cv[3] = *g[3]; }
     }
+    // (a.nt: unchunked tables only; cv[2] stays unset, and unused, where no tile has a fourth vector)
+    if (!CHUNKED && a.nt) { cv[0] = nt_load(g[0]); cv[1] = nt_load(g[1]); if (grp4) cv[2] = nt_load(g[2]); }
+    else                  { cv[0] = *g[0]; cv[1] = *g[1]; if (grp4) cv[2] = *g[2]; }
 
     // ---- (2) uniform scalars of the tile (scalar loads: they return on lgkmcnt, the vector queue stays untouched)
     long long kbase, kend;
@@ -554,31 +562,29 @@ __global__ void __launch_bounds__(1024, 8) ps_tile_v3_kernel(PsArgs a) {
     const int shi = min((int)a.n, r0 + nr + nhi);
     const int wrows = shi - slo;
 
-    // ---- (3) halo rows: the run below the tile, then the run above it, two vectors per thread
+    // ---- (3) halo rows: the run below the tile (loaded here) and the run above it (loaded in (6)), one vector per
+    // thread each (the host keeps a run at T vectors)
     const int lo_rows = r0 - slo, hi_rows = shi - (r0 + nr);
-    const int lo_n = lo_rows * LV, hi_n = hi_rows * LV;
     int4 hv[2];
     int hdst[2];                                            // LDS vector index, -1: nothing
+    const int4* hg[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        const int idx = tid + k * T;
-        const bool is_lo = idx < lo_n;
-        const int j = is_lo ? idx : idx - lo_n;            // vector inside its run
-        bool ok = is_lo || j < hi_n;
+        const bool is_lo = k == 0;
+        bool ok = tid < (is_lo ? lo_rows : hi_rows) * LV;
         // (clamped: the tile's first vector stands in for a missing one)
         const char* grun = is_lo ? gtile - lo_rows * row_stride : (ok ? gtile + nr * row_stride : gtile);
-        const int jc = ok ? j : 0;
-        const int ldst = (is_lo ? (slo - wbase) : (a.halo + nr)) * LV + j;
-        const int4* g;
-        if (!CHUNKED) g = reinterpret_cast<const int4*>(grun) + jc;
+        const int jc = ok ? tid : 0;
+        const int ldst = (is_lo ? (slo - wbase) : (a.halo + nr)) * LV + tid;
+        if (!CHUNKED) hg[k] = reinterpret_cast<const int4*>(grun) + jc;
         else {
             const int rr = jc >> lsh, cc = jc & (LV - 1);
             ok = ok && cc < V;
-            g = reinterpret_cast<const int4*>(grun + rr * row_stride) + min(cc, V - 1);
+            hg[k] = reinterpret_cast<const int4*>(grun + rr * row_stride) + min(cc, V - 1);
         }
         hdst[k] = ok ? ldst : -1;
-        hv[k] = *g;                                         // (halo rows are another tile's own rows: they may stay in the L2)
     }
+    hv[0] = *hg[0];                                         // (halo rows are another tile's own rows: they may stay in the L2)
     // ---- (4) neighbour indices (three per thread) and (5) row pointers (two per thread)
     const bool col_in_lds = nk <= a.col_cap && nk <= 3 * T;
     int jv[3];
@@ -592,16 +598,19 @@ __global__ void __launch_bounds__(1024, 8) ps_tile_v3_kernel(PsArgs a) {
     int rp_mine[2];                                         // (low words: a tile's lists are < 2^31 entries)
     rp_mine[0] = reinterpret_cast<const int*>(a.row_ptr + r0 + min(tid, nr))[0];
     rp_mine[1] = reinterpret_cast<const int*>(a.row_ptr + r0 + min(tid + T, nr))[0];
+    // ---- (6) the high end of the window, behind everything else in the vector queue (loads retire in issue order): the
+    // tile's last own vector and the run above the tile
+    asm volatile("" ::: "memory");
+    if (!CHUNKED && a.nt) cv[3] = nt_load(g[3]); else cv[3] = *g[3];
+    hv[1] = *hg[1];
     if (a.prio) __builtin_amdgcn_s_setprio(0);
 
     // ---- retire them in issue order: window vectors to LDS (their maximum on the way), offsets, pointers
     unsigned cmax = 0;
 #pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (cok[k]) { win4[a.halo * LV + tid + k * T] = cv[k]; cmax = max(cmax, vmax(cv[k])); }
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-        if (hdst[k] >= 0) { win4[hdst[k]] = hv[k]; cmax = max(cmax, vmax(hv[k])); }
+    for (int k = 0; k < 3; ++k)
+        if (cok[k]) { win4[cdst[k]] = cv[k]; cmax = max(cmax, vmax(cv[k])); }
+    if (hdst[0] >= 0) { win4[hdst[0]] = hv[0]; cmax = max(cmax, vmax(hv[0])); }
     bool outside = false;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -615,6 +624,11 @@ __global__ void __launch_bounds__(1024, 8) ps_tile_v3_kernel(PsArgs a) {
     }
     if (tid <= nr) rpL[tid] = rp_mine[0] - (int)kbase;
     if (tid + T <= nr) rpL[tid + T] = rp_mine[1] - (int)kbase;
+    if (cok[3]) { win4[cdst[3]] = cv[3]; cmax = max(cmax, vmax(cv[3])); }
+    // (the last load is consumed outside the predicate: its wait, vmcnt(0), then stands on every path, and the item
+    // loop, whose registers these were, needs none -- a wait there would be a wait for its own stores)
+    cmax = max(cmax, hdst[1] >= 0 ? vmax(hv[1]) : 0u);
+    if (hdst[1] >= 0) win4[hdst[1]] = hv[1];
     {
         cmax = wave_max_dpp(cmax);
         const unsigned long long any_out = __ballot(outside);
@@ -815,7 +829,7 @@ extern "C" int sdice_ps_dev(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t*
         //  loads in flight during the gather -- was built and measured 30 % slower: the kernel is VALU-issue
         //  bound, and halving the resident waves costs more than hiding the load latency gains)
         // caps of the register staging: rows <= 4 T / LV (own rows), rows <= 2 T - 1 (row pointers: nr + 1 of them),
-        // halo <= T / LV (the two runs together take two vectors per thread)
+        // halo <= T / LV (each of the two runs takes one vector per thread)
         const int64_t r_cap = newk ? std::min<int64_t>(4 * (int64_t)threads / LV, 2 * (int64_t)threads - 1) : 2 * (int64_t)threads;
         const int64_t h_cap = newk ? (int64_t)threads / LV : (int64_t)1 << 20;
         if (H > h_cap) H = h_cap;
