@@ -187,6 +187,31 @@ int sdice_kruskal_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, c
                       const int32_t* set_ptr, int32_t k, uint8_t* d_tested, double* d_p, double* d_h,
                       float* d_med, float* d_mean, float* d_delta);
 
+/* ---- compare_sample_sets --paired: Wilcoxon signed-rank test over m matched column pairs, per row
+ *      scipy.stats.wilcoxon(d, zero_method="wilcox", correction=False, alternative="two-sided", method="asymptotic")
+ *      under the row rules above.
+ *  Pair q is the columns (a[q], b[q]), 1 <= m <= 4096, a column at most once over both lists; otherwise SDICE_ERR_ARG
+ *  before any launch, outputs untouched (the host call checks the index range and the one-appearance rule, the _dev
+ *  call m and 2 m <= s).  Values are finite float32 or NaN.
+ *  Per row: a pair is kept when both of its values are non-NaN; with fewer than 3 kept pairs the row is not tested and
+ *  every output slot is 0.  mean1 / med1 are np.mean / np.median of the a-side values of the kept pairs in pair order,
+ *  bit for bit as in sdice_ranksum, mean2 / med2 of the b side, delta = med1 - med2 in float32; equal pairs count here.
+ *  Differences: when every kept value of the row is a 3-decimal PS value float32(key / 1000), key = 0..1000, d =
+ *  key_a - key_b as an integer (thousandths), otherwise d = x - y in float32.  This departs from scipy on purpose: a
+ *  floating subtraction of 3-decimal values breaks ties by rounding noise (float32(0.3) - float32(0.2) !=
+ *  float32(0.2) - float32(0.1)), and equal printed differences must tie.
+ *  Zero differences are dropped (n' are left), |d| gets average ranks, R+ is the rank sum of the positive ones:
+ *  z = (R+ - n'(n'+1)/4) / sqrt((n'(n'+1)(2n'+1) - sum(t^3 - t)/2) / 24), positive when side 1 is larger (scipy
+ *  reports -|z|), p = erfc(|z| / sqrt 2), as accurate as sdice_ranksum's.  A tested row with n' = 0 has z = 0, p = 1
+ *  (scipy: NaN).  Always the normal approximation, from 3 pairs up: scipy's exact and permutation p-values
+ *  (method="auto") are not offered.  z optional (NULL to skip). */
+int sdice_signedrank(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps, const int32_t* a,
+                     const int32_t* b, int32_t m, uint8_t* tested, double* p, double* z, float* med1,
+                     float* med2, float* mean1, float* mean2, float* delta);
+int sdice_signedrank_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, const int32_t* d_a,
+                         const int32_t* d_b, int32_t m, uint8_t* d_tested, double* d_p, double* d_z,
+                         float* d_med1, float* d_med2, float* d_mean1, float* d_mean2, float* d_delta);
+
 /* ---- pairwise: replaces the per-pair loop pairwise_fisher.py:164-179
  *      (scipy.stats.fisher_exact two-sided on [[incl_a, incl_b],[excl_a, excl_b]]).
  *  incl[n,s] int32, excl[n,s] int64 (from sdice_ps); p[n, s(s-1)/2] float64 row-major,

@@ -9,6 +9,10 @@ One flag the reference lacks: `-mx FILE [FILE ...]` names the third and later sa
 Kruskal-Wallis H test across all k sets (sdice_kruskal) and the columns are
 `event mean1..meank median1..mediank delta H p-value corrected`.
 
+Another one: `--paired` pairs line i of -m1 with line i of -m2 (matched samples: tumour / normal of one patient, before /
+after) and the test is the Wilcoxon signed-rank test of the pairs (sdice_signedrank); the output columns are the
+two-set ones.
+
 On the GPU: the per-row loop :216-232 (NaN drop, <3 skip, scipy ranksums, medians, means)
 -> sdice_ranksum; multipletests(..., "fdr_bh") :235 -> sdice_bh over the tested rows.
 The GTF annotation columns are host string work, as in the reference.
@@ -116,9 +120,9 @@ def annotation_suffixes(names, gtf_path):
             "\t" + ",".join(transcript_ids.get(j, nan)) for n, j in enumerate(junctions)]
 
 
-def compare_dev(matrix, g1_idx, g2_idx, ctx):
-    """compare() on the HIP engine stage by stage: table up, rank-sum + BH over the tested rows on resident vectors,
-    per-row results down (sdice_ranksum + sdice_bh do the same steps inside two host calls)"""
+def compare_dev(matrix, g1_idx, g2_idx, ctx, paired=False):
+    """compare() on the HIP engine stage by stage: table up, rank-sum (paired: signed-rank) + BH over the tested rows on
+    resident vectors, per-row results down (sdice_ranksum + sdice_bh do the same steps inside two host calls)"""
     from . import _stages
     n = matrix.shape[0]
     f32 = ("med1", "med2", "mean1", "mean2", "delta")
@@ -129,7 +133,7 @@ def compare_dev(matrix, g1_idx, g2_idx, ctx):
                    **{k: ctx.empty(n, np.float32) for k in f32})
         d_q = ctx.empty(n, np.float64)
     with _stages.stage("kernels"):
-        ctx.ranksum_dev(d_ps, d_g1, d_g2, out)
+        (ctx.signedrank_dev if paired else ctx.ranksum_dev)(d_ps, d_g1, d_g2, out)
         ctx.bh_masked_dev(out["p"], out["tested"], d_q)
         ctx.sync()
     with _stages.stage("d2h"):
@@ -143,11 +147,12 @@ def compare_dev(matrix, g1_idx, g2_idx, ctx):
     return keep, r
 
 
-def compare(matrix, g1_idx, g2_idx, ctx):
-    """-> (kept row indices, dict of compacted per-row results incl. BH-corrected p)."""
+def compare(matrix, g1_idx, g2_idx, ctx, paired=False):
+    """-> (kept row indices, dict of compacted per-row results incl. BH-corrected p).  paired: g1_idx[q] and g2_idx[q]
+    are the columns of pair q and the test is the signed-rank test."""
     if hasattr(ctx, "ranksum_dev") and matrix.shape[0]:
-        return compare_dev(matrix, g1_idx, g2_idx, ctx)
-    res = ctx.ranksum(matrix, g1_idx, g2_idx)
+        return compare_dev(matrix, g1_idx, g2_idx, ctx, paired)
+    res = (ctx.signedrank if paired else ctx.ranksum)(matrix, g1_idx, g2_idx)
     keep = np.flatnonzero(res["tested"])
     out = {k: res[k][keep] for k in ("p", "med1", "med2", "mean1", "mean2", "delta")}
     out["corrected"] = ctx.bh(out["p"]) if keep.size else np.zeros(0)
@@ -185,7 +190,7 @@ def compare_sets_dev(matrix, set_idx, ctx):
     return keep, r
 
 
-def compare_sharded(matrix, g1_idx, g2_idx, ctx, L):
+def compare_sharded(matrix, g1_idx, g2_idx, ctx, L, paired=False):
     """compare() with the table rows cut into one block per rank (rows are independent here): every rank tests its
     block, the per-row statistics cross the ranks as ONE packed block in ONE all-gather (distributed.stat_layout, padded to
     the longest block), rank 0 corrects."""
@@ -194,7 +199,7 @@ def compare_sharded(matrix, g1_idx, g2_idx, ctx, L):
     lo, hi = L.row_block(n)
     rows_of = [b - a for a, b in (L.row_block(n, r) for r in range(L.world))]
     maxk = distributed.longest(rows_of)
-    res = ctx.ranksum(np.ascontiguousarray(matrix[lo:hi]), g1_idx, g2_idx)
+    res = (ctx.signedrank if paired else ctx.ranksum)(np.ascontiguousarray(matrix[lo:hi]), g1_idx, g2_idx)
     stats = {k: distributed.pad_rows(np.asarray(res[k], dt), maxk) for k, dt in zip(distributed.STAT_NAMES, distributed.STAT_DTYPES)}
     gathered = L.comm(ctx).allgather(distributed.pack_stats_host(stats, maxk))
     host = distributed.unpack_stats_host(gathered, maxk, L.world)
@@ -215,6 +220,10 @@ def add_parser(parser):
     parser.add_argument("-mx", "--moreManifests", type=str, nargs="+", required=False, default=None, metavar="FILE",
                         help="Manifests of the third and later sample sets: the rank-sum test becomes the Kruskal-Wallis "
                              "H test across all sets (not part of the reference)")
+    parser.add_argument("--paired", action="store_true",
+                        help="Matched samples: line i of -m1 is paired with line i of -m2 (MANIFEST order, not the "
+                             "table order of the unpaired test) and the test is the Wilcoxon signed-rank test of the "
+                             "pairs; same output columns (not part of the reference)")
     parser.add_argument("-a", "--annotation", type=str, required=False, default="",
                         help="Optional GTF file to label known splice junctions and genes")
     parser.add_argument("-o", "--outputFile", type=str, required=True,
@@ -223,6 +232,38 @@ def add_parser(parser):
 
 MULTI_RANK_REFUSAL = ("compare_sample_sets: -mx/--moreManifests is not available under the multi-rank launcher "
                       "(the packed all-gather carries the two-set fields only); run it in one process.")
+
+
+def paired_columns(g1, g2, header_names):
+    """--paired: the manifests' sample lists and the table's column names -> (a, b) int32 column indices, pair q =
+    (a[q], b[q]) in manifest order; prints why and exits with status 1 when the lists cannot be paired"""
+    def refuse(why):
+        print(f"compare_sample_sets --paired: {why}. Exit.", file=sys.stderr)
+        sys.exit(1)
+    if len(g1) != len(g2):
+        refuse(f"the manifests differ in length ({len(g1)} and {len(g2)} samples); line i of -m1 is paired with line i of -m2")
+    if len(g1) < 3:
+        refuse(f"cannot conduct the signed-rank test with fewer than 3 pairs (got {len(g1)})")
+    seen = set()
+    for name in g1 + g2:
+        if name in seen:
+            refuse(f"sample {name!r} appears twice in the manifests; a sample belongs to one pair only")
+        seen.add(name)
+    where = {}
+    for j, name in enumerate(header_names):
+        where.setdefault(name, []).append(j)
+    for name in g1 + g2:
+        hits = where.get(name, [])
+        if len(hits) != 1:
+            refuse(f"sample {name!r} " + ("is missing from the table header" if not hits else
+                                          f"appears {len(hits)} times in the table header"))
+    return (np.array([where[x][0] for x in g1], dtype=np.int32), np.array([where[x][0] for x in g2], dtype=np.int32))
+
+
+def table_header_names(path):
+    """the sample names of an `_allPS.tsv` header (its first line alone is read)"""
+    with open(path) as fin:
+        return fin.readline().strip().split("\t")[1:]
 
 
 def run_sets(args, groups, ctx=None, device=0):
@@ -258,6 +299,13 @@ def run_with(args, ctx=None):
     g1 = samples_from_manifest(args.manifest1)
     g2 = samples_from_manifest(args.manifest2)
     more = [samples_from_manifest(m) for m in (getattr(args, "moreManifests", None) or [])]
+    paired = bool(getattr(args, "paired", False))
+    if paired:
+        if more:
+            print("compare_sample_sets --paired: cannot be combined with -mx/--moreManifests (the signed-rank test "
+                  "compares two matched sets). Exit.", file=sys.stderr)
+            sys.exit(1)
+        pair_idx = paired_columns(g1, g2, table_header_names(args.psiSPLICEDICE))      # (exits before any GPU call)
     if len(g1) < 3 or len(g2) < 3 or any(len(g) < 3 for g in more):
         print("Cannot conduct wilcoxon with less than 3 samples in either group. Exit.", file=sys.stderr)
         sys.exit(1)
@@ -270,13 +318,15 @@ def run_with(args, ctx=None):
     from . import _stages
     with _stages.stage("parse"):
         rows, cols, matrix = read_ps_table(args.psiSPLICEDICE, as_table=True)
-    g1_idx = column_indices(g1, cols)
-    g2_idx = column_indices(g2, cols)
+    g1_idx, g2_idx = pair_idx if paired else (column_indices(g1, cols), column_indices(g2, cols))
 
     own_ctx = ctx is None
     ctx = ctx if ctx is not None else Context(L.local_rank)
     try:
-        keep, r = compare_sharded(matrix, g1_idx, g2_idx, ctx, L) if L.world > 1 else compare(matrix, g1_idx, g2_idx, ctx)
+        if L.world > 1:
+            keep, r = compare_sharded(matrix, g1_idx, g2_idx, ctx, L, paired)
+        else:
+            keep, r = compare(matrix, g1_idx, g2_idx, ctx, paired)
     finally:
         if own_ctx:
             ctx.close()

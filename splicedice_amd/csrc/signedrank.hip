@@ -1,0 +1,750 @@
+// K13: Wilcoxon signed-rank test per junction row over m matched column pairs (a[q], b[q]) + median / mean of each side.
+//
+// scipy.stats.wilcoxon(d, zero_method="wilcox", correction=False, alternative="two-sided", method="asymptotic") per row
+// under the row rules of the two-set path: a pair is kept when both of its values are non-NaN, the row is tested when
+// at least 3 pairs are kept.  Medians and means are np.median / np.mean of each side's kept values in pair order (equal
+// pairs included).  The differences of the kept pairs lose their zeros, |d| gets average ranks, z is signed (positive
+// when side 1 is larger) and p = erfc(|z| / sqrt 2); a tested row without a non-zero difference has z = 0, p = 1.
+//
+// Differences.  A row whose kept values all are 3-decimal PS values float32(key / 1000), key = 0..1000 (all that
+// compare_sample_sets ever reads), takes d = key_a - key_b as an integer: equal printed differences tie, which a float
+// subtraction of such values does not give (float32(0.3) - float32(0.2) != float32(0.2) - float32(0.1)).  Any other
+// row takes d = x - y in float32.  The choice is a ballot per row and the only difference between the two kinds of row.
+//
+// Arithmetic, in integers up to the last step (as kruskal.hip):
+//   sort key of a kept non-zero pair = (code << 1) | (d > 0), code = |key_a - key_b| or the bits of |d| (below 2^31),
+//       0xFFFFFFFF pads; sorted ascending, a tie run is a run of equal `key >> 1`
+//   r2   = 2 * average rank = first + last + 2 over the run [first, last]
+//   W2   = sum of r2 over d > 0 (= 2 R+),   T = sum over runs of t^3 - t,   n' = number of non-zero differences
+//   z    = (2 W2 - n'(n'+1)) / sqrt((2 n'(n'+1)(2n'+1) - T) / 3)
+//        = (R+ - n'(n'+1)/4) / sqrt((n'(n'+1)(2n'+1) - T/2) / 24)
+//
+// Kernels:
+//   signedrank_lane_kernel<P>: m <= 8 (P = 4 or 8), the small matched cohorts.  One LANE per row, the pairs in registers:
+//       three sorting networks without a cross-lane step, the tie runs walked one after another, the sums in numpy's
+//       order without a compaction (below 8 values numpy adds them one by one; 8 values are P = 8 with nothing dropped).
+//       A wave reads 64 consecutive rows and stores 64 consecutive results.
+//   signedrank_group_kernel<P>: 9 <= m <= 64.  A group of P = next_pow2(m) lanes owns a row, one pair per lane, 64 / P
+//       rows per wave side by side: three bitonic networks of __shfl_xor inside the group (the keys, the two sides'
+//       order-preserving bits for the medians), run bounds from a ballot of run starts, group reductions by xor
+//       exchanges.  The kept values are compacted through the wave's LDS for the numpy-order sums (at most 64 values:
+//       one leaf of numpy's pairwise recursion).  Lane i of the wave keeps the results of the chunk's i-th row; the
+//       double precision finish and the stores happen once per chunk, for all its rows at once.
+//   signedrank_block_kernel: 65 <= m <= 4096, one workgroup per row, modelled on kruskal_block_kernel: ordered
+//       compaction of the kept pairs, numpy pairwise sums, one LDS bitonic sort that carries the three arrays through
+//       the same barriers, run bounds by binary search.
+// (A wave-per-row kernel with several elements per lane for 65..1024 pairs was left out: the block kernel computes the
+// same thing and paired cohorts of that size are rare.)
+//
+// rowsum.h is used as it is (PsKey, ps_of_key, block_pairwise_sum, rows_per_chunk, SD_WAVE_SYNC); sr_ord / sr_unord
+// repeat kruskal.hip's kw_ord / kw_unord because moving those would change that file.
+#include "common.h"
+#include <math.h>
+#include <vector>
+#include "rowsum.h"
+
+namespace {
+
+constexpr int SR_MAX_PAIRS = 4096;
+constexpr int SR_GROUP_MAX = 64;         // pairs the lane-group kernel takes
+constexpr int SR_LEAF_MAX = 64;          // leaves of numpy's pairwise recursion over 4096 values (PW_DEPTH levels)
+constexpr uint32_t SR_PAD = 0xFFFFFFFFu;
+
+struct SrOut {
+    uint8_t* tested;
+    double* p;
+    double* z;       // may be NULL
+    float* med1;
+    float* med2;
+    float* mean1;
+    float* mean2;
+    float* delta;
+};
+
+__device__ __forceinline__ uint32_t sr_ord(float v) {          // order-preserving bits of a non-NaN float (-0 == +0), below SR_PAD
+    const uint32_t b = __float_as_uint(v + 0.0f);
+    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ __forceinline__ float sr_unord(uint32_t o) {
+    return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
+}
+
+// sort key of a kept pair (see the file comment); SR_PAD for a zero difference
+__device__ __forceinline__ uint32_t sr_key(float x, float y, bool grid) {
+    if (grid) {
+        const int d = key_of_ps(x).key() - key_of_ps(y).key();
+        return d == 0 ? SR_PAD : (((uint32_t)(d < 0 ? -d : d) << 1) | (d > 0 ? 1u : 0u));
+    }
+    const float d = x - y;
+    return d == 0.0f ? SR_PAD : ((__float_as_uint(fabsf(d)) << 1) | (d > 0.0f ? 1u : 0u));
+}
+
+// ---- p where most rows are (p >= 2.2e-5): erfc in double-double arithmetic, so that the float64 that comes out is the
+// correctly rounded one (the library erfc is an ulp or two off, which shows in the last printed digit of the table).
+// erfc(x) = 1 - 2/sqrt(pi) x sum_n (-x^2)^n / (n! (2n+1)) with x^2 = xn / xd taken from the two integers: up to x^2 = 9
+// the alternating terms grow to 56 and erfc falls to 2.2e-5, about 22 of the 106 bits; beyond that the library erfc.
+// (This function compiled for the host, against mpmath: 0 of 5048 random (n', W2, T) and break points differ from the correctly
+// rounded value.)
+constexpr double SR_DD_X2_MAX = 9.0;
+struct SrDD { double hi, lo; };
+__device__ __forceinline__ SrDD dd_fast2sum(double a, double b) {          // |a| >= |b|
+    const double s = a + b;
+    return {s, b - (s - a)};
+}
+__device__ __forceinline__ SrDD dd_2sum(double a, double b) {
+    const double s = a + b, bb = s - a;
+    return {s, (a - (s - bb)) + (b - bb)};
+}
+__device__ __forceinline__ SrDD dd_add(SrDD a, SrDD b) {
+    SrDD s = dd_2sum(a.hi, b.hi);
+    const SrDD t = dd_2sum(a.lo, b.lo);
+    s = dd_fast2sum(s.hi, s.lo + t.hi);
+    return dd_fast2sum(s.hi, s.lo + t.lo);
+}
+__device__ __forceinline__ SrDD dd_mul(SrDD a, SrDD b) {
+    const double p = a.hi * b.hi;
+    const double e = __builtin_fma(a.hi, b.hi, -p) + (a.hi * b.lo + a.lo * b.hi);
+    return dd_fast2sum(p, e);
+}
+__device__ __forceinline__ SrDD dd_div_d(SrDD a, double b) {
+    const double q1 = a.hi / b;
+    const double r = __builtin_fma(-q1, b, a.hi) + a.lo;
+    return dd_fast2sum(q1, r / b);
+}
+// coefficients (-1)^n / (n! (2n+1)) of the series as double-double constants; SR_ERF_TERMS[i] of them leave less than
+// 2^-112 behind for x^2 <= SR_ERF_BREAK[i]
+__device__ const double SR_ERF_C[70][2] = {
+    {0x1.0000000000000p+0, 0x0.0p+0},
+    {-0x1.5555555555555p-2, -0x1.5555555555555p-56},
+    {0x1.999999999999ap-4, -0x1.999999999999ap-58},
+    {-0x1.8618618618618p-6, -0x1.8618618618618p-60},
+    {0x1.2f684bda12f68p-8, 0x1.2f684bda12f68p-62},
+    {-0x1.8d3018d3018d3p-11, -0x1.8d3018d3018d3p-71},
+    {0x1.c01c01c01c01cp-14, 0x1.c01c01c01c01cp-74},
+    {-0x1.bbd779334ef0bp-17, 0x1.4e65f77088199p-71},
+    {0x1.87a00187a0018p-20, 0x1.e80061e80061fp-74},
+    {-0x1.3777c55568ccdp-23, -0x1.aaabe22270001p-79},
+    {0x1.c2e3054870b38p-27, -0x1.d5bceb1cfc09cp-81},
+    {-0x1.2b67310aa9f3ap-30, -0x1.0a97d2e29d0a6p-85},
+    {0x1.6f448e13e85e1p-34, -0x1.7f9c97a441499p-90},
+    {-0x1.a289ee7e40f74p-38, 0x1.d70bcaede276bp-92},
+    {0x1.bd577e658d020p-42, 0x1.20ed35aaf6f95p-97},
+    {-0x1.bc6250fb14231p-46, 0x1.a5ccd0da99260p-100},
+    {0x1.a173a167fba4dp-50, -0x1.4e2d0241b6a79p-104},
+    {-0x1.7271cbe5863ecp-54, -0x1.12d42fe81b396p-108},
+    {0x1.377c2110f2083p-58, 0x1.98394fbf35b19p-117},
+    {-0x1.f1b4073b34a68p-63, 0x1.84a9e0b9a5e9bp-117},
+    {0x1.7abd72258fb6ep-67, 0x1.2780872890580p-123},
+    {-0x1.13246abce1bddp-71, -0x1.b85c8446def6cp-125},
+    {0x1.7e6b81382cd42p-76, 0x1.f8367249eb893p-131},
+    {-0x1.fd6bebd65107ap-81, -0x1.64abb94b856f1p-135},
+    {0x1.45c0a838efe59p-85, -0x1.423cdb5cc4cc3p-139},
+    {-0x1.909c9de3a31c5p-90, 0x1.889db7273c973p-145},
+    {0x1.da7460554e5dbp-95, 0x1.59a4d60d2d7dap-149},
+    {-0x1.0eef30fa10d2cp-99, 0x1.28594b7fcd32dp-153},
+    {0x1.2ac65385f79acp-104, 0x1.03fafe0077abep-161},
+    {-0x1.3e81bb5701ac5p-109, 0x1.209a8bade2337p-164},
+    {0x1.4899fcdef0a8dp-114, -0x1.aec1a99185f98p-173},
+    {-0x1.486eea20c2656p-119, 0x1.9ae3d63d0a79fp-173},
+    {0x1.3e53defc4e233p-124, 0x1.d436dda5545e7p-178},
+    {-0x1.2b778acc3dedfp-129, -0x1.f264aece2ab96p-184},
+    {0x1.11ae81077a49ep-134, -0x1.f8cb0d503e384p-189},
+    {-0x1.e6597092ccbf0p-140, -0x1.d930aabd4497fp-197},
+    {0x1.a47767f2a3c32p-145, 0x1.eb53c552fbc05p-201},
+    {-0x1.61f30bc3acd1ap-150, -0x1.a9e9f60cd9edap-204},
+    {0x1.22521d98f98a9p-155, -0x1.637b9778df025p-209},
+    {-0x1.d05cc9e3507c9p-161, 0x1.29b6f9c13f797p-215},
+    {0x1.6a513f56f8a2fp-166, -0x1.8794747d7f461p-220},
+    {-0x1.13f85fc9e143ep-171, -0x1.27bd43d20fbfcp-225},
+    {0x1.9aa19d4d16643p-177, -0x1.ad0ff92af832dp-231},
+    {-0x1.2a8fa59ffec31p-182, 0x1.44478f2f75d87p-236},
+    {0x1.a8830736a5123p-188, -0x1.1af9ae0a12e66p-245},
+    {-0x1.273d8edcec957p-193, 0x1.ab7b8539d42f6p-249},
+    {0x1.91ef82b367a95p-199, 0x1.690b4eaa147d4p-254},
+    {-0x1.0be5a4cd94283p-204, 0x1.fbd6d97519e8fp-258},
+    {0x1.5dd4c9219115ap-210, 0x1.73661ef9ff986p-264},
+    {-0x1.bfb10e0f68c50p-216, 0x1.159dc3de3de07p-273},
+    {0x1.18d952ef00889p-221, -0x1.8e04468edd83dp-278},
+    {-0x1.59982b2e94840p-227, 0x1.68a4cb414cb71p-281},
+    {0x1.a13ec00b39f6fp-233, -0x1.af38c63806b25p-288},
+    {-0x1.ee6cefaa5a158p-239, 0x1.7a47a5ca12246p-293},
+    {0x1.1f9dec94da5f8p-244, -0x1.6472662f16fe2p-298},
+    {-0x1.48a6b3820b441p-250, 0x1.df79984d16d0dp-305},
+    {0x1.70f41ac13e2a1p-256, 0x1.8af98ff8f9fd6p-310},
+    {-0x1.970f1cb2ad53fp-262, -0x1.b7fc559391cc2p-316},
+    {0x1.b97d90d3e603bp-268, 0x1.1965394a5d61cp-323},
+    {-0x1.d6db2a7c68dcbp-274, 0x1.f1ad59160452ep-329},
+    {0x1.edf1e6e4658a9p-280, -0x1.3aa36c1523b23p-334},
+    {-0x1.fdcf88bbf71dbp-286, 0x1.6f1a1abfe27e7p-342},
+    {0x1.02eb04e5f82f5p-291, 0x1.98847a7286982p-349},
+    {-0x1.02e2bc1b5790ep-297, 0x1.6a12f5351a054p-352},
+    {0x1.fdbe706576d5dp-304, -0x1.2ce505402f725p-358},
+    {-0x1.ee3d33862f55bp-310, 0x1.f1da0c3f22056p-366},
+    {0x1.d80e20102c46ep-316, -0x1.a560ae14c0c74p-372},
+    {-0x1.bc3cf47bca3afp-322, 0x1.82f01ff45da58p-385},
+    {0x1.9c00b17fe33c8p-328, -0x1.bc97c630526bcp-383},
+    {-0x1.78a61f51a767fp-334, -0x1.1fcc8fc30c961p-388},
+};
+__device__ const double SR_ERF_BREAK[8] = {0.25, 0.5, 1, 2, 3, 4.5, 6, 9};
+__device__ const int SR_ERF_TERMS[8] = {21, 25, 30, 37, 43, 50, 57, 69};
+
+__device__ double sr_erfc_dd(double xn, double xd) {                       // 0 < xn / xd <= SR_DD_X2_MAX, both integers below 2^53
+    const SrDD x2 = dd_div_d({xn, 0.0}, xd);
+    const double s = sqrt(x2.hi);
+    const SrDD x = dd_fast2sum(s, (__builtin_fma(-s, s, x2.hi) + x2.lo) / (2.0 * s));
+    int last = SR_ERF_TERMS[7];
+#pragma unroll
+    for (int i = 6; i >= 0; --i)
+        if (x2.hi <= SR_ERF_BREAK[i]) last = SR_ERF_TERMS[i];
+    SrDD sum = {SR_ERF_C[last][0], SR_ERF_C[last][1]};                     // Horner in x^2, no division
+    for (int n = last - 1; n >= 0; --n) sum = dd_add(dd_mul(sum, x2), {SR_ERF_C[n][0], SR_ERF_C[n][1]});
+    const SrDD two_over_sqrt_pi = {0x1.20dd750429b6dp+0, 0x1.1ae3a914fed80p-56};
+    const SrDD erf = dd_mul(dd_mul(two_over_sqrt_pi, x), sum);
+    const SrDD r = dd_add({1.0, 0.0}, {-erf.hi, -erf.lo});
+    return r.hi + r.lo;
+}
+
+// z and p of a tested row from the integer pieces
+__device__ __forceinline__ void sr_finish(int np, long long w2, long long tie, double& z, double& p) {
+    if (np == 0) { z = 0.0; p = 1.0; return; }           // every kept pair equal
+    const long long nn = (long long)np * (np + 1);
+    const long long num = 2 * w2 - nn;                   // 4 (R+ - n'(n'+1)/4)
+    const long long v2 = 2 * nn * (2 * np + 1) - tie;    // 48 Var(R+), > 0
+    z = (double)num / sqrt((double)v2 / 3.0);
+    // erfc's argument |z| / sqrt 2 = sqrt(3 num^2 / (2 v2)) from the integers themselves (3 num^2 < 2^53): two roundings,
+    // not z's three and a product -- down the tail every rounding of the argument costs p about z^2 of them
+    const double xn = (double)(3 * num * num), xd = (double)(2 * v2);
+    if (num == 0) p = 1.0;
+    else if (xn <= SR_DD_X2_MAX * xd) p = sr_erfc_dd(xn, xd);
+    else p = erfc(sqrt(xn / xd));
+}
+
+// ------------------------------------------------------------------ lane-group path: P lanes per row
+// ascending bitonic sort of one value per lane inside aligned groups of P lanes
+template <int P>
+__device__ __forceinline__ uint32_t sr_group_sort(uint32_t v, int gl) {
+#pragma unroll
+    for (int k = 2; k <= P; k <<= 1) {
+#pragma unroll
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            const uint32_t other = __shfl_xor(v, j);
+            const bool upper = (gl & j) != 0;
+            const bool asc = (gl & k) == 0;              // k == P: ascending everywhere
+            const uint32_t lo = min(v, other), hi = max(v, other);
+            v = (asc != upper) ? lo : hi;
+        }
+    }
+    return v;
+}
+
+template <int P>
+__device__ __forceinline__ int sr_group_add(int v) {
+#pragma unroll
+    for (int ofs = 1; ofs < P; ofs <<= 1) v += __shfl_xor(v, ofs);
+    return v;
+}
+
+// np.median of the group's nv sorted order-preserving values (lane g0 + i holds the i-th smallest)
+__device__ __forceinline__ float sr_group_median(uint32_t sorted, int g0, int nv) {
+    const int h = nv >> 1;
+    const float v1 = sr_unord(__shfl(sorted, g0 + h));
+    const float v0 = sr_unord(__shfl(sorted, g0 + (h > 0 ? h - 1 : 0)));
+    return (nv & 1) ? v1 : (v0 + v1) / 2.0f;
+}
+
+// numpy pairwise_sum of A[0..nv), nv <= 64 (one leaf), by a group of P lanes, every lane of the group gets it: for
+// nv >= 8 lane j (mod 8) owns accumulator j, folded as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) by three xor exchanges as
+// in wave_pairwise_sum; then the tail (or, below 8 values, all of them) one after another.  (P >= 16: the
+// exchanges stay inside the group.)
+template <int P>
+__device__ __forceinline__ float sr_group_sum(const float* A, int nv, int gl) {
+    const int main_n = nv & ~7, j = gl & 7;
+    float r = 0.f;
+    if (nv >= 8) {
+        r = A[j];
+        for (int i = 8; i < main_n; i += 8) r += A[i + j];
+    }
+    r = r + __shfl_xor(r, 1);
+    r = r + __shfl_xor(r, 2);
+    r = r + __shfl_xor(r, 4);
+    if (nv < 8) r = 0.f;
+    for (int i = (nv >= 8 ? main_n : 0); i < nv; ++i) r += A[i];
+    return r;
+}
+
+template <int P>
+__global__ void __launch_bounds__(256) signedrank_group_kernel(const float* __restrict__ ps, int64_t n, int s,
+                                                               const int32_t* __restrict__ a, const int32_t* __restrict__ b,
+                                                               int m, int ch, SrOut o) {
+    constexpr int R = 64 / P;                            // rows side by side in a wave
+    constexpr unsigned long long GMASK = P == 64 ? ~0ull : ((1ull << (P & 63)) - 1ull);
+    __shared__ float cx[4][64], cy[4][64];               // the kept values of the wave's rows, compacted, in pair order
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
+    const int g = lane / P, gl = lane % P, g0 = g * P;
+    float* X = cx[wave] + g0;
+    float* Y = cy[wave] + g0;
+    const int ca = gl < m ? a[gl] : 0, cb = gl < m ? b[gl] : 0;
+    const int64_t n_chunks = (n + ch - 1) / ch;
+    for (int64_t c = (int64_t)blockIdx.x * wpb + wave; c < n_chunks; c += (int64_t)gridDim.x * wpb) {
+      const int64_t row0 = c * ch;
+      const int rows_here = (int)min((int64_t)ch, n - row0);
+      // lane i keeps the chunk's i-th row
+      int s_pack = 0, s_tie = 0;                         // tested << 31 | W2 << 8 | n'  (W2 <= 64 * 65, n' <= 64); T <= 64^3
+      float s_med1 = 0.f, s_med2 = 0.f, s_mean1 = 0.f, s_mean2 = 0.f;
+      for (int r0 = 0; r0 < rows_here; r0 += R) {        // wave-uniform
+        const int ri = r0 + g;
+        float x = __builtin_nanf(""), y = x;
+        if (ri < rows_here && gl < m) {
+            const float* prow = ps + (row0 + ri) * s;
+            x = __builtin_nontemporal_load(prow + ca);
+            y = __builtin_nontemporal_load(prow + cb);
+        }
+        const bool kept = x == x && y == y;
+        const unsigned long long km = (__ballot(kept) >> g0) & GMASK;
+        const int nv = __popcll(km);
+        const bool offgrid = kept && !(key_of_ps(x).exact() && key_of_ps(y).exact());
+        const bool grid = ((__ballot(offgrid) >> g0) & GMASK) == 0ull;
+        // ---- the numpy-order sums over the compacted values
+        SD_WAVE_SYNC();          // the previous pass's readers are done with the wave's LDS
+        if (kept) {
+            const int pos = __popcll(km & ((1ull << gl) - 1ull));
+            X[pos] = x;
+            Y[pos] = y;
+        }
+        SD_WAVE_SYNC();
+        const float sum1 = 0.0f + sr_group_sum<P>(X, nv, gl);      // np.sum starts from the identity 0: -0.0 values sum to +0.0
+        const float sum2 = 0.0f + sr_group_sum<P>(Y, nv, gl);
+        // ---- the medians
+        const uint32_t ox = sr_group_sort<P>(kept ? sr_ord(x) : SR_PAD, gl);
+        const uint32_t oy = sr_group_sort<P>(kept ? sr_ord(y) : SR_PAD, gl);
+        const float med1 = sr_group_median(ox, g0, nv), med2 = sr_group_median(oy, g0, nv);
+        // ---- the ranks of |d|
+        const uint32_t key = sr_group_sort<P>(kept ? sr_key(x, y, grid) : SR_PAD, gl);
+        const bool valid = key != SR_PAD;
+        const int np = __popcll((__ballot(valid) >> g0) & GMASK);
+        const uint32_t prev = __shfl_up(key, 1);
+        const bool start = valid && (gl == 0 || (prev >> 1) != (key >> 1));
+        const unsigned long long sm = (__ballot(start) >> g0) & GMASK;       // bit i: a tie run starts at position i
+        const unsigned long long upto = (2ull << gl) - 1ull;                 // positions 0..gl
+        int w2 = 0, tie = 0;
+        if (valid) {
+            const int first = 63 - __clzll((long long)(sm & upto));
+            const unsigned long long above = sm & ~upto;
+            const int last = above ? (__ffsll((long long)above) - 2) : np - 1;
+            if (key & 1u) w2 = first + last + 2;
+            const int t = last - first + 1;
+            if (start) tie = t * t * t - t;
+        }
+        w2 = sr_group_add<P>(w2);
+        tie = sr_group_add<P>(tie);
+        // ---- to the lanes that keep the rows of this pass: lane r0 + q takes group q's
+        const int src = ((lane - r0) * P) & 63;
+        const bool mine = lane >= r0 && lane < r0 + R;
+        const int pack = nv >= 3 ? (int)(0x80000000u | ((unsigned)w2 << 8) | (unsigned)np) : 0;
+        const int t_pack = __shfl(pack, src), t_tie = __shfl(tie, src);
+        const float t_med1 = __shfl(med1, src), t_med2 = __shfl(med2, src);
+        const float t_mean1 = __shfl(sum1 / (float)nv, src), t_mean2 = __shfl(sum2 / (float)nv, src);
+        if (mine) { s_pack = t_pack; s_tie = t_tie; s_med1 = t_med1; s_med2 = t_med2; s_mean1 = t_mean1; s_mean2 = t_mean2; }
+      }
+      if (lane < rows_here) {
+        const int64_t row = row0 + lane;
+        const bool tested = s_pack < 0;
+        double z = 0.0, p = 0.0;
+        if (tested) sr_finish(s_pack & 0xff, (long long)((s_pack >> 8) & 0x7fffff), (long long)s_tie, z, p);
+        o.tested[row] = tested ? 1 : 0;
+        o.p[row] = p;
+        if (o.z) o.z[row] = z;
+        o.med1[row] = tested ? s_med1 : 0.f;
+        o.med2[row] = tested ? s_med2 : 0.f;
+        o.mean1[row] = tested ? s_mean1 : 0.f;
+        o.mean2[row] = tested ? s_mean2 : 0.f;
+        o.delta[row] = tested ? s_med1 - s_med2 : 0.f;
+      }
+    }
+}
+
+// ------------------------------------------------------------------ lane path: one lane per row, m <= 8
+// ascending sort of P values in registers: the bitonic network, every index a compile-time constant
+template <int P>
+__device__ __forceinline__ void sr_sort_regs(uint32_t (&v)[P]) {
+#pragma unroll
+    for (int k = 2; k <= P; k <<= 1) {
+#pragma unroll
+        for (int j = k >> 1; j > 0; j >>= 1) {
+#pragma unroll
+            for (int i = 0; i < P; ++i) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const uint32_t lo = min(v[i], v[l]), hi = max(v[i], v[l]);
+                    const bool asc = (i & k) == 0;
+                    v[i] = asc ? lo : hi;
+                    v[l] = asc ? hi : lo;
+                }
+            }
+        }
+    }
+}
+
+template <int P>
+__device__ __forceinline__ uint32_t sr_pick(const uint32_t (&v)[P], int idx) {
+    uint32_t r = v[0];
+#pragma unroll
+    for (int i = 1; i < P; ++i) r = idx == i ? v[i] : r;
+    return r;
+}
+
+// np.median of the nv smallest of the sorted order-preserving values
+template <int P>
+__device__ __forceinline__ float sr_regs_median(const uint32_t (&sorted)[P], int nv) {
+    const int h = nv >> 1;
+    const float v1 = sr_unord(sr_pick<P>(sorted, h));
+    const float v0 = sr_unord(sr_pick<P>(sorted, h > 0 ? h - 1 : 0));
+    return (nv & 1) ? v1 : (v0 + v1) / 2.0f;
+}
+
+// numpy pairwise_sum of the kept values (NaN = not kept) in pair order: below 8 values one after another from 0, at 8
+// values (P = 8, nothing dropped) the eight accumulators hold one value each and only their fold is left
+template <int P>
+__device__ __forceinline__ float sr_regs_sum(const float (&v)[P], int nv) {
+    float r = 0.f;
+#pragma unroll
+    for (int q = 0; q < P; ++q)
+        if (v[q] == v[q]) r += v[q];
+    if constexpr (P == 8) {
+        const float tree = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+        if (nv == 8) r = tree;
+    }
+    return r;
+}
+
+template <int P>
+__global__ void __launch_bounds__(256) signedrank_lane_kernel(const float* __restrict__ ps, int64_t n, int s,
+                                                              const int32_t* __restrict__ a, const int32_t* __restrict__ b,
+                                                              int m, SrOut o) {
+    for (int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; row < n; row += (int64_t)gridDim.x * blockDim.x) {
+        const float* prow = ps + row * s;
+        float x[P], y[P];
+#pragma unroll
+        for (int q = 0; q < P; ++q) {
+            x[q] = y[q] = __builtin_nanf("");
+            if (q < m) {                                 // uniform
+                x[q] = __builtin_nontemporal_load(prow + a[q]);
+                y[q] = __builtin_nontemporal_load(prow + b[q]);
+            }
+        }
+        int nv = 0;
+        bool grid = true;
+#pragma unroll
+        for (int q = 0; q < P; ++q) {
+            const bool kept = x[q] == x[q] && y[q] == y[q];
+            if (!kept) x[q] = y[q] = __builtin_nanf("");  // a NaN on both sides marks a dropped pair from here on
+            nv += kept ? 1 : 0;
+            grid = grid && (!kept || (key_of_ps(x[q]).exact() && key_of_ps(y[q]).exact()));
+        }
+        const float sum1 = 0.0f + sr_regs_sum<P>(x, nv), sum2 = 0.0f + sr_regs_sum<P>(y, nv);
+        uint32_t ux[P], uy[P], kd[P];
+#pragma unroll
+        for (int q = 0; q < P; ++q) {
+            const bool kept = x[q] == x[q];
+            ux[q] = kept ? sr_ord(x[q]) : SR_PAD;
+            uy[q] = kept ? sr_ord(y[q]) : SR_PAD;
+            kd[q] = kept ? sr_key(x[q], y[q], grid) : SR_PAD;
+        }
+        sr_sort_regs<P>(ux);
+        sr_sort_regs<P>(uy);
+        sr_sort_regs<P>(kd);
+        const float med1 = sr_regs_median<P>(ux, nv), med2 = sr_regs_median<P>(uy, nv);
+        // tie runs of the sorted keys, one after another: a run [first, i] with cp positive members adds cp r2 to W2
+        int np = 0, w2 = 0, tie = 0, first = 0, cp = 0;
+        uint32_t prev = SR_PAD;                          // no code is this large
+#pragma unroll
+        for (int i = 0; i < P; ++i) {
+            if (kd[i] != SR_PAD) {
+                const uint32_t code = kd[i] >> 1;
+                if (code != prev) { first = i; cp = 0; }
+                prev = code;
+                cp += (int)(kd[i] & 1u);
+                ++np;
+                bool ends = true;
+                if (i + 1 < P) ends = (kd[i + 1 < P ? i + 1 : i] >> 1) != code;      // (a pad's code is a NaN pattern)
+                if (ends) {
+                    const int t = i - first + 1;
+                    w2 += cp * (first + i + 2);
+                    tie += t * t * t - t;
+                }
+            }
+        }
+        const bool tested = nv >= 3;
+        double z = 0.0, p = 0.0;
+        if (tested) sr_finish(np, (long long)w2, (long long)tie, z, p);
+        o.tested[row] = tested ? 1 : 0;
+        o.p[row] = p;
+        if (o.z) o.z[row] = z;
+        o.med1[row] = tested ? med1 : 0.f;
+        o.med2[row] = tested ? med2 : 0.f;
+        o.mean1[row] = tested ? sum1 / (float)nv : 0.f;
+        o.mean2[row] = tested ? sum2 / (float)nv : 0.f;
+        o.delta[row] = tested ? med1 - med2 : 0.f;
+    }
+}
+
+// ------------------------------------------------------------------ general path: one workgroup per row
+// ordered compaction of the pairs of ps[row, (a[q], b[q])] without a NaN into fx / fy; returns the count
+__device__ int sr_block_compact(const float* __restrict__ prow, const int32_t* __restrict__ a, const int32_t* __restrict__ b,
+                                int m, float* fx, float* fy, int* wcnt /* [RB_THREADS/64] shared */) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    int base = 0;
+    for (int c0 = 0; c0 < m; c0 += RB_THREADS) {
+        const int q = c0 + tid;
+        float x = __builtin_nanf(""), y = x;
+        if (q < m) { x = prow[a[q]]; y = prow[b[q]]; }
+        const bool valid = x == x && y == y;
+        const unsigned long long mk = __ballot(valid);
+        if (lane == 0) wcnt[w] = __popcll(mk);
+        __syncthreads();
+        int woff = 0, tot = 0;
+        for (int i = 0; i < RB_THREADS / 64; ++i) {
+            if (i < w) woff += wcnt[i];
+            tot += wcnt[i];
+        }
+        if (valid) {
+            const int pos = base + woff + lanes_below(mk);
+            fx[pos] = x;
+            fy[pos] = y;
+        }
+        base += tot;
+        __syncthreads();
+    }
+    return base;
+}
+
+// ascending bitonic sort of A[0..P), B[0..P) and C[0..P), each on its own, by the whole block through the same barriers
+// (P a power of two); ends with a barrier
+__device__ void sr_block_sort3(uint32_t* A, uint32_t* B, uint32_t* C, int P) {
+    const int tid = threadIdx.x;
+    for (int kk = 2; kk <= P; kk <<= 1) {
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < P; i += RB_THREADS) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const bool asc = (i & kk) == 0;
+                    uint32_t* const arr[3] = {A, B, C};
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) {
+                        const uint32_t x = arr[q][i], y = arr[q][l];
+                        if ((x > y) == asc) { arr[q][i] = y; arr[q][l] = x; }
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__global__ void __launch_bounds__(RB_THREADS) signedrank_block_kernel(const float* __restrict__ ps, int64_t n, int s,
+                                                                      const int32_t* __restrict__ a,
+                                                                      const int32_t* __restrict__ b, int m, int P, SrOut o) {
+    extern __shared__ __align__(16) unsigned char smems[];
+    uint32_t* KX = reinterpret_cast<uint32_t*>(smems);         // [P] side 1: first the compacted floats, then their order bits
+    uint32_t* KY = KX + P;                                      // [P] side 2
+    uint32_t* KD = KY + P;                                      // [P] the sort keys of the differences
+    float* FX = reinterpret_cast<float*>(KX);
+    float* FY = reinterpret_cast<float*>(KY);
+    __shared__ float leaf_sum[SR_LEAF_MAX];
+    __shared__ float scratch8[SR_LEAF_MAX * 8];
+    __shared__ int leaf_off[SR_LEAF_MAX + 1];
+    __shared__ int wcnt[RB_THREADS / 64];
+    __shared__ unsigned long long accS[2];                      // W2, T
+    const int tid = threadIdx.x, lane = tid & 63;
+    for (int64_t row = blockIdx.x; row < n; row += gridDim.x) {
+        const float* prow = ps + row * s;
+        const int nv = sr_block_compact(prow, a, b, m, FX, FY, wcnt);
+        if (nv < 3) {                                           // block-uniform
+            if (tid == 0) {
+                o.tested[row] = 0; o.p[row] = 0.0;
+                if (o.z) o.z[row] = 0.0;
+                o.med1[row] = 0.f; o.med2[row] = 0.f; o.mean1[row] = 0.f; o.mean2[row] = 0.f; o.delta[row] = 0.f;
+            }
+            continue;                                           // (sr_block_compact ended with a barrier)
+        }
+        // np.sum: the identity 0 plus the pairwise tree
+        const float sum1 = 0.0f + block_pairwise_sum<PW_DEPTH>(FX, nv, leaf_off, leaf_sum, scratch8, SR_LEAF_MAX);
+        const float sum2 = 0.0f + block_pairwise_sum<PW_DEPTH>(FY, nv, leaf_off, leaf_sum, scratch8, SR_LEAF_MAX);
+        // ---- grid row or not; keys of the differences, order bits of the two sides, padding last
+        int off = 0;
+        for (int i = tid; i < nv; i += RB_THREADS) off |= !(key_of_ps(FX[i]).exact() && key_of_ps(FY[i]).exact());
+        const bool grid = __syncthreads_or(off) == 0;
+        for (int i = tid; i < P; i += RB_THREADS) {
+            uint32_t kx = SR_PAD, ky = SR_PAD, kd = SR_PAD;
+            if (i < nv) {
+                const float x = FX[i], y = FY[i];
+                kx = sr_ord(x); ky = sr_ord(y); kd = sr_key(x, y, grid);
+            }
+            KX[i] = kx; KY[i] = ky; KD[i] = kd;
+        }
+        if (tid < 2) accS[tid] = 0ull;
+        __syncthreads();
+        sr_block_sort3(KX, KY, KD, P);
+        int np = 0;                                             // first padding key: the number of non-zero differences
+        {
+            int hi = nv;
+            while (np < hi) { const int mid = (np + hi) >> 1; if (KD[mid] != SR_PAD) np = mid + 1; else hi = mid; }
+        }
+        // ---- ranks
+        long long w2 = 0, tie = 0;
+        for (int q = tid; q < np; q += RB_THREADS) {
+            const uint32_t key = KD[q], code = key >> 1;
+            int lo = 0, hi = np;                                // first position with code >= this one's
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if ((KD[mid] >> 1) < code) lo = mid + 1; else hi = mid; }
+            const int first = lo;
+            hi = np;                                            // first position with a larger code
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if ((KD[mid] >> 1) <= code) lo = mid + 1; else hi = mid; }
+            if (key & 1u) w2 += first + lo + 1;
+            if (q == first) {
+                const long long t = lo - first;
+                tie += t * t * t - t;
+            }
+        }
+#pragma unroll
+        for (int ofs = 32; ofs > 0; ofs >>= 1) {
+            w2 += __shfl_xor(w2, ofs);
+            tie += __shfl_xor(tie, ofs);
+        }
+        if (lane == 0) {
+            if (w2) atomicAdd(&accS[0], (unsigned long long)w2);
+            if (tie) atomicAdd(&accS[1], (unsigned long long)tie);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            const int h = nv >> 1;
+            const float a1 = sr_unord(KX[h]), b1 = sr_unord(KY[h]);
+            const float med1 = (nv & 1) ? a1 : (sr_unord(KX[h - 1]) + a1) / 2.0f;      // np.median on float32
+            const float med2 = (nv & 1) ? b1 : (sr_unord(KY[h - 1]) + b1) / 2.0f;
+            double z, p;
+            sr_finish(np, (long long)accS[0], (long long)accS[1], z, p);
+            o.tested[row] = 1; o.p[row] = p;
+            if (o.z) o.z[row] = z;
+            o.med1[row] = med1; o.med2[row] = med2;
+            o.mean1[row] = sum1 / (float)nv; o.mean2[row] = sum2 / (float)nv;
+            o.delta[row] = med1 - med2;
+        }
+        __syncthreads();           // thread 0 has read the row's LDS
+    }
+}
+
+template <int P>
+int sr_launch_group(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* d_a, const int32_t* d_b, int m, SrOut o) {
+    const int waves = 4;
+    const int ch = rows_per_chunk(ctx->n_cu, n);
+    int64_t blocks = sd_ceil_div(sd_ceil_div(n, ch), waves);
+    const int64_t cap = (int64_t)ctx->n_cu * 32 / waves;
+    if (blocks > cap) blocks = cap;
+    SD_LAUNCH(ctx, "signedrank_group_kernel", (signedrank_group_kernel<P>), dim3((unsigned)blocks), dim3(waves * 64), 0, d_ps,
+              n, s, d_a, d_b, m, ch, o);
+    return SDICE_OK;
+}
+
+template <int P>
+int sr_launch_lane(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* d_a, const int32_t* d_b, int m, SrOut o) {
+    int64_t blocks = sd_ceil_div(n, 256);
+    const int64_t cap = (int64_t)ctx->n_cu * 8;
+    if (blocks > cap) blocks = cap;
+    SD_LAUNCH(ctx, "signedrank_lane_kernel", (signedrank_lane_kernel<P>), dim3((unsigned)blocks), dim3(256), 0, d_ps, n, s,
+              d_a, d_b, m, o);
+    return SDICE_OK;
+}
+
+int sr_check_m(int32_t m) {
+    if (m > SR_MAX_PAIRS) {
+        sdice_set_error("sdice_signedrank: %d pairs, at most %d are supported", (int)m, SR_MAX_PAIRS);
+        return SDICE_ERR_ARG;
+    }
+    SD_ARG(m >= 1, "the number of pairs must be 1..4096");
+    return SDICE_OK;
+}
+
+}  // namespace
+
+extern "C" int sdice_signedrank_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, const int32_t* d_a,
+                                    const int32_t* d_b, int32_t m, uint8_t* d_tested, double* d_p, double* d_z,
+                                    float* d_med1, float* d_med2, float* d_mean1, float* d_mean2, float* d_delta) {
+    SD_ARG(ctx, "ctx is NULL");
+    SD_ARG(n >= 0 && s >= 0, "negative size");
+    SD_TRY(sr_check_m(m));
+    SD_ARG(2 * (int64_t)m <= s, "more paired columns than the table has (a column belongs to one pair only)");
+    if (n == 0) return SDICE_OK;
+    SD_ARG(d_tested && d_p && d_med1 && d_med2 && d_mean1 && d_mean2 && d_delta, "NULL output");
+    SD_ARG(d_ps && d_a && d_b, "NULL input");
+    SD_HIP(hipSetDevice(ctx->device));
+    SD_TRY(ctx->arena.reset(ctx->stream));
+    SrOut o{d_tested, d_p, d_z, d_med1, d_med2, d_mean1, d_mean2, d_delta};
+    if (m < 3) {
+        // no row can be tested
+        SD_HIP(hipMemsetAsync(d_tested, 0, (size_t)n, ctx->stream));
+        SD_HIP(hipMemsetAsync(d_p, 0, (size_t)n * 8, ctx->stream));
+        if (d_z) SD_HIP(hipMemsetAsync(d_z, 0, (size_t)n * 8, ctx->stream));
+        float* f[5] = {d_med1, d_med2, d_mean1, d_mean2, d_delta};
+        for (auto q : f) SD_HIP(hipMemsetAsync(q, 0, (size_t)n * 4, ctx->stream));
+        return SDICE_OK;
+    }
+    if (m <= SR_GROUP_MAX) {
+        if (m <= 4) return sr_launch_lane<4>(ctx, d_ps, n, s, d_a, d_b, m, o);
+        if (m <= 8) return sr_launch_lane<8>(ctx, d_ps, n, s, d_a, d_b, m, o);
+        if (m <= 16) return sr_launch_group<16>(ctx, d_ps, n, s, d_a, d_b, m, o);
+        if (m <= 32) return sr_launch_group<32>(ctx, d_ps, n, s, d_a, d_b, m, o);
+        return sr_launch_group<64>(ctx, d_ps, n, s, d_a, d_b, m, o);
+    }
+    int P = 128;
+    while (P < m) P <<= 1;
+    const size_t lds = (size_t)P * 3 * 4;
+    int64_t blocks = n;
+    const int64_t cap = (int64_t)ctx->n_cu * 8;
+    if (blocks > cap) blocks = cap;
+    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(signedrank_block_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    SD_LAUNCH(ctx, "signedrank_block_kernel", signedrank_block_kernel, dim3((unsigned)blocks), dim3(RB_THREADS), lds, d_ps, n,
+              (int)s, d_a, d_b, (int)m, P, o);
+    return SDICE_OK;
+}
+
+extern "C" int sdice_signedrank(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps, const int32_t* a,
+                                const int32_t* b, int32_t m, uint8_t* tested, double* p, double* z, float* med1,
+                                float* med2, float* mean1, float* mean2, float* delta) {
+    SD_ARG(ctx, "ctx is NULL");
+    SD_ARG(n >= 0 && s >= 0, "negative size");
+    SD_TRY(sr_check_m(m));
+    SD_ARG(a && b, "pair index list is NULL");
+    {
+        std::vector<char> seen((size_t)s, 0);
+        const int32_t* lists[2] = {a, b};
+        for (const int32_t* l : lists)
+            for (int q = 0; q < m; ++q) {
+                SD_ARG(l[q] >= 0 && l[q] < s, "column index out of range");
+                SD_ARG(!seen[l[q]], "a column may appear once over both pair lists");
+                seen[l[q]] = 1;
+            }
+    }
+    if (n == 0) return SDICE_OK;
+    SD_ARG(tested && p && med1 && med2 && mean1 && mean2 && delta, "NULL output");
+    SD_ARG(ps, "ps is NULL");
+    HostStaging st(ctx);
+    float *d_ps, *df;
+    int32_t *da, *db;
+    uint8_t* dt;
+    double* dd;
+    SD_TRY(st.upload(&d_ps, ps, n * s));
+    SD_TRY(st.upload(&da, a, m));
+    SD_TRY(st.upload(&db, b, m));
+    SD_TRY(st.alloc(&dt, n));
+    SD_TRY(st.alloc(&dd, n * 2));      // p, z
+    SD_TRY(st.alloc(&df, n * 5));      // med1, med2, mean1, mean2, delta
+    SD_TRY(sdice_signedrank_dev(ctx, n, s, d_ps, da, db, m, dt, dd, dd + n, df, df + n, df + 2 * n, df + 3 * n, df + 4 * n));
+    SD_TRY(st.download(tested, dt, n));
+    SD_TRY(st.download(p, dd, n));
+    if (z) SD_TRY(st.download(z, dd + n, n));
+    SD_TRY(st.download(med1, df, n));
+    SD_TRY(st.download(med2, df + n, n));
+    SD_TRY(st.download(mean1, df + 2 * n, n));
+    SD_TRY(st.download(mean2, df + 3 * n, n));
+    return st.download(delta, df + 4 * n, n);
+}

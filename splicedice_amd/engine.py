@@ -295,6 +295,22 @@ class Context:
                                      _ptr(out["delta"])), "sdice_kruskal")
         return out
 
+    def signedrank(self, ps, a, b):
+        """scipy.stats.wilcoxon (asymptotic, zero_method="wilcox") per row over the matched column pairs (a[q], b[q])
+        under the row rules of ranksum(); same un-compacted outputs + tested mask (z > 0: side a is larger)."""
+        ps = _c(ps, np.float32)
+        n, s = ps.shape
+        a, b = _c(a, np.int32), _c(b, np.int32)
+        if a.shape != b.shape or a.ndim != 1:
+            raise ValueError(f"signedrank: the pair lists must be two vectors of one length, got {a.shape} and {b.shape}")
+        out = dict(tested=np.zeros(n, np.uint8), p=np.zeros(n, np.float64), z=np.zeros(n, np.float64),
+                   med1=np.zeros(n, np.float32), med2=np.zeros(n, np.float32), mean1=np.zeros(n, np.float32),
+                   mean2=np.zeros(n, np.float32), delta=np.zeros(n, np.float32))
+        check(self.lib.sdice_signedrank(self.h, n, s, _ptr(ps), _ptr(a), _ptr(b), a.size, _ptr(out["tested"]),
+                                        _ptr(out["p"]), _ptr(out["z"]), _ptr(out["med1"]), _ptr(out["med2"]),
+                                        _ptr(out["mean1"]), _ptr(out["mean2"]), _ptr(out["delta"])), "sdice_signedrank")
+        return out
+
     def fisher_pairs(self, incl, excl, pairs=None):
         """pairwise_fisher.py:164-179 -> p float64[n, s(s-1)/2]; pairs = [m, 2] column indices: p float64[n, m], column q
         the table [[incl_i, incl_j], [excl_i, excl_j]] of pair q = (i, j) -- any order, i > j and repeats allowed"""
@@ -409,6 +425,13 @@ class Context:
                                          out["tested"].ptr, out["p"].ptr, out["z"].ptr if out.get("z") else None,
                                          out["med1"].ptr, out["med2"].ptr, out["mean1"].ptr, out["mean2"].ptr,
                                          out["delta"].ptr), "sdice_ranksum_dev")
+
+    def signedrank_dev(self, d_ps, d_a, d_b, out):
+        n, s = d_ps.shape
+        check(self.lib.sdice_signedrank_dev(self.h, n, s, d_ps.ptr, d_a.ptr, d_b.ptr, d_a.shape[0],
+                                            out["tested"].ptr, out["p"].ptr, out["z"].ptr if out.get("z") else None,
+                                            out["med1"].ptr, out["med2"].ptr, out["mean1"].ptr, out["mean2"].ptr,
+                                            out["delta"].ptr), "sdice_signedrank_dev")
 
     def kruskal_dev(self, d_ps, d_cols, set_ptr, out):
         """d_cols: the device copy of kruskal_sets()'s cols; set_ptr: its HOST offsets; out: device tested, p, (h), med and
