@@ -212,6 +212,28 @@ int sdice_signedrank_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps
                          const int32_t* d_b, int32_t m, uint8_t* d_tested, double* d_p, double* d_z,
                          float* d_med1, float* d_med2, float* d_mean1, float* d_mean2, float* d_delta);
 
+/* ---- correlate: Spearman rank correlation of the PS values of m listed columns with one covariate value per listed
+ *      column, per row scipy.stats.spearmanr(x_kept, ps_kept) under the row rules above (not in the reference).
+ *  The covariate does not cross the ABI.  cols[m]: the columns sorted by covariate value, ties in table order; xg[m]: the
+ *  dense tie-group id of each listed column: xg[0] = 0, never decreasing, steps of 0 or 1 (equal covariate values share
+ *  an id; engine.spearman_order() makes both).  3 <= m <= 4096, every index in [0, s), a column listed once; otherwise,
+ *  or with a malformed xg, SDICE_ERR_ARG before any launch, outputs untouched (the host call checks the two arrays, the
+ *  _dev call m, m <= s and the sizes).  Values are finite float32 or NaN.
+ *  Per row: a sample is kept when its PS value is not NaN; with fewer than 3 kept the row is not tested and every output
+ *  slot is 0.  n_kept is the kept count; mean / med are np.mean / np.median of the kept values in the order of cols, bit
+ *  for bit as in sdice_ranksum.  Both sides get average ranks among the kept samples of the row (PS ties by float32
+ *  equality, -0.0 == +0.0; covariate ties by xg), rho is the Pearson correlation of the ranks, formed from exact integer
+ *  sums of the doubled ranks, and p = 2 t.sf(|t|, n' - 2) = I_{1 - rho^2}((n' - 2) / 2, 1 / 2) in float64.
+ *  A row whose kept PS values, or whose kept covariate values, are all equal is tested with rho = 0, p = 1 (scipy: NaN).
+ *  |rho| = 1 gives p = 0 and rho = 0 gives p = 1 exactly, from 3 kept samples up: always scipy's t approximation, no
+ *  exact or permutation p.  rho optional (NULL to skip). */
+int sdice_spearman(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps, const int32_t* cols,
+                   const int32_t* xg, int32_t m, uint8_t* tested, double* p, double* rho, int32_t* n_kept,
+                   float* med, float* mean);
+int sdice_spearman_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, const int32_t* d_cols,
+                       const int32_t* d_xg, int32_t m, uint8_t* d_tested, double* d_p, double* d_rho,
+                       int32_t* d_n_kept, float* d_med, float* d_mean);
+
 /* ---- pairwise: replaces the per-pair loop pairwise_fisher.py:164-179
  *      (scipy.stats.fisher_exact two-sided on [[incl_a, incl_b],[excl_a, excl_b]]).
  *  incl[n,s] int32, excl[n,s] int64 (from sdice_ps); p[n, s(s-1)/2] float64 row-major,

@@ -15,6 +15,7 @@ ACCELERATED = {
     "counts_to_ps": "splicedice_amd.counts_to_ps",
     "compare_sample_sets": "splicedice_amd.compare_sample_sets",
     "pairwise": "splicedice_amd.pairwise",
+    "correlate": "splicedice_amd.correlate",
     "similarity": "splicedice_amd.similarity",
     "findOutliers": "splicedice_amd.find_outliers",
     "ir_table": "splicedice_amd.ir_table",

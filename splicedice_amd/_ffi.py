@@ -54,6 +54,8 @@ SIGNATURES = {
     "sdice_kruskal_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 6,
     "sdice_signedrank": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 8,
     "sdice_signedrank_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 8,
+    "sdice_spearman": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 6,
+    "sdice_spearman_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 6,
     "sdice_fisher_pairs": [ctxp, C.c_int64, C.c_int32, vp, vp, vp],
     "sdice_fisher_pairs_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, vp],
     "sdice_fisher_tables": [ctxp, C.c_int64, vp, vp],

@@ -1,4 +1,4 @@
-// Per-row device helpers that the rank tests share (ranksum.hip: K5, kruskal.hip: K12): numpy's float32 pairwise
+// Per-row device helpers that the rank tests share (ranksum.hip: K5, kruskal.hip: K12, signedrank.hip: K13, spearman.hip: K14): numpy's float32 pairwise
 // summation reproduced operation for operation (by a block and by a wave), the ordered NaN-dropping compaction of a
 // row's selected columns, np.median of a sorted run, the 3-decimal PS key of a float and its float back, the median
 // search in the 16-bins-per-lane histograms of the counting kernels, and the rows-per-wave chunk of their launches.
@@ -206,6 +206,16 @@ __device__ __forceinline__ int find_bin(const unsigned* const& H, const int& lan
         if (lane >= ofs) inc += up;
     }
     return L * 16 + (__ffsll((long long)__ballot(lane < 16 && target < base + inc)) - 1);
+}
+
+// order-preserving bits of a non-NaN float (-0.0 == +0.0), below 0xFFFFFFFF, and the float back (+0.0 for either zero):
+// what spearman.hip sorts and counts on (kruskal.hip and signedrank.hip keep their own kw_ / sr_ copies)
+__device__ __forceinline__ uint32_t f32_ord(float v) {
+    const uint32_t b = __float_as_uint(v + 0.0f);
+    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ __forceinline__ float f32_unord(uint32_t o) {
+    return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
 }
 
 // Host: rows of one wave's chunk in the wave-per-row kernels -- as many (64 at most) as keeps every wave slot of the

@@ -1,0 +1,706 @@
+// K14: Spearman rank correlation per junction row between the PS values of m listed columns and one covariate value per
+// listed column + n / mean / median of the row's kept PS values (the `correlate` sub-command).
+//
+// scipy.stats.spearmanr(x_kept, ps_kept) per row: a sample is kept when its PS value is not NaN, the row is tested when
+// at least 3 are kept, the covariate is ranked again among the kept samples of each row, rho is the Pearson correlation of
+// the two average-rank vectors and p = 2 t.sf(|t|, nu) = I_{1 - rho^2}(nu / 2, 1 / 2), nu = n' - 2.  PS values tie by
+// float32 equality (-0.0 == +0.0), covariate values by the tie-group ids the host passes.
+//
+// What arrives: the columns sorted by covariate (ties in table order) and a dense tie-group id per column, xg[0] = 0,
+// non-decreasing in steps of 0 or 1.  The covariate itself never reaches the device: the ranks of a row's kept subset
+// are a prefix count over the kept flags in that order, closed per tie group --
+//   a2 = 2 * average covariate rank = (kept before the group) + (kept up to the group's end) + 1
+//   b2 = 2 * average PS rank        = 2 (kept values below) + (kept values equal, itself included) + 1
+// Arithmetic, in integers up to the last step: both doubled rank vectors sum to S = n'(n'+1), so with
+//   N  = n' sum(a2 b2) - S^2,   Dx = n' sum(a2^2) - S^2,   Dy = n' sum(b2^2) - S^2        (below 2^47 at 4096 samples)
+//   rho = N / sqrt(Dx Dy),   1 - rho^2 = (Dx Dy - N^2) / (Dx Dy)   with the products as 128-bit integers (93 bits)
+// there is no rank rounding and no cancellation near |rho| = 1.  Dx = 0 or Dy = 0 (covariate or PS constant among the
+// kept; scipy: NaN): rho = 0, p = 1, the row stays tested.  N = 0: p = 1.  N^2 = Dx Dy: rho = +-1, p = 0, also at 3 kept
+// samples (scipy's t approximation; no exact or permutation p).  Otherwise rho is the double-double square root of
+// N^2 / (Dx Dy), rounded once, and p is the regularized incomplete beta:
+//   up to 64 kept samples: a power series in double-double arithmetic (sp_beta_half_dd), the correctly rounded float64 --
+//       the table `correlate` prints equals the 50-digit referee's byte for byte there;
+//   above: in float64 by the continued fraction (modified Lentz), taken from the side that converges: I_x(a, 1/2)
+//       directly for x < (a + 1) / (a + 5/2), else 1 - I_{rho^2}(1/2, a) -- where that branch is taken p is above 0.05
+//       and nothing cancels.  Within 1e-12 relative of the referee at 4096 samples.
+//
+// Kernels:
+//   spearman_group_kernel<P>: m <= 64, P = 8, 16, 32 or 64 lanes own a row, one column per lane, 64 / P rows per wave side
+//       by side (the lane groups of signedrank.hip).  The PS ranks need no sort: every lane reads the group's P values one
+//       after another and counts those below and equal to its own; the median is the value of the lane whose rank interval
+//       holds the middle position.  Covariate ranks: two popcounts of the kept mask.  The kept values are compacted through
+//       the wave's LDS for the numpy-order sum (one leaf of numpy's pairwise recursion).  Lane i of a wave keeps the
+//       results of the chunk's i-th row; the float64 finish and the stores happen once per chunk.
+//   spearman_wave_kernel<E>: 65 <= m <= 256, one wave per row, E = 2 or 4 columns per lane, the same steps: every value
+//       is broadcast once (v_readlane) and every lane counts against its E values; covariate ranks from 2 E popcounts of
+//       the E kept masks; the sum by wave_pairwise_sum.
+//   spearman_block_kernel: 257 <= m <= 4096, one workgroup per row after signedrank_block_kernel: ordered compaction that
+//       also leaves the kept-prefix of every list position, block_pairwise_sum, one LDS bitonic sort of the order bits
+//       that carries a2 as a 16-bit payload, run bounds by binary search.  The tie-group bounds of the list positions are
+//       found once per workgroup.
+// (Left out: a wave-per-row tier for 257..1024 columns -- counting is quadratic in m and stops paying there -- and the
+// 1001-bin count for rows of 3-decimal values; the block kernel computes the same thing.)
+//
+// rowsum.h: block_pairwise_sum, wave_pairwise_sum, lanes_below, rows_per_chunk, SD_WAVE_SYNC as they are; f32_ord /
+// f32_unord were added there for this file.
+#include "common.h"
+#include <math.h>
+#include <vector>
+#include "rowsum.h"
+
+namespace {
+
+constexpr int SP_MIN_COLS = 3;
+constexpr int SP_MAX_COLS = 4096;
+constexpr int SP_GROUP_MAX = 64;         // columns the lane-group kernel takes
+constexpr int SP_WAVE_MAX = 256;         // columns the wave-per-row kernel takes
+constexpr int SP_LEAF_MAX = 64;          // leaves of numpy's pairwise recursion over 4096 values (PW_DEPTH levels)
+constexpr uint32_t SP_PAD = 0xFFFFFFFFu;
+
+struct SpOut {
+    uint8_t* tested;
+    double* p;
+    double* rho;     // may be NULL
+    int32_t* n_kept;
+    float* med;
+    float* mean;
+};
+
+// ---- p: I_x(a, 1/2) in float64
+// continued fraction of the incomplete beta function (modified Lentz); converges in O(sqrt(max(a, b))) rounds for
+// x < (a + 1) / (a + b + 2)
+__host__ __device__ inline double sp_betacf(double a, double b, double x) {
+    const double tiny = 1e-300, eps = 2.3e-16;
+    const double qab = a + b, qap = a + 1.0, qam = a - 1.0;
+    double c = 1.0, d = 1.0 - qab * x / qap;
+    if (fabs(d) < tiny) d = tiny;
+    d = 1.0 / d;
+    double h = d;
+    for (int i = 1; i <= 4000; ++i) {
+        const double fi = (double)i, i2 = 2.0 * fi;
+        double aa = fi * (b - fi) * x / ((qam + i2) * (a + i2));
+        d = 1.0 + aa * d;
+        if (fabs(d) < tiny) d = tiny;
+        c = 1.0 + aa / c;
+        if (fabs(c) < tiny) c = tiny;
+        d = 1.0 / d;
+        h *= d * c;
+        aa = -(a + fi) * (qab + fi) * x / ((a + i2) * (qap + i2));
+        d = 1.0 + aa * d;
+        if (fabs(d) < tiny) d = tiny;
+        c = 1.0 + aa / c;
+        if (fabs(c) < tiny) c = tiny;
+        d = 1.0 / d;
+        const double del = d * c;
+        h *= del;
+        if (fabs(del - 1.0) <= eps) break;
+    }
+    return h;
+}
+
+// I_x(a, 1/2), a >= 31.5, with y = 1 - x given apart (both come from the integers, neither from the other).
+// ln(Gamma(a + 1/2) / Gamma(a)) by its asymptotic series, not as a difference of two lgamma of size 1e4: the next term,
+// 31 / (18432 a^9), is below 6e-17 from a = 31.5 up.
+__host__ __device__ inline double sp_beta_half(double a, double x, double y) {
+    const double ln_sqrt_pi = 0.5723649429247000870717;
+    const double w = 1.0 / a, w2 = w * w;
+    const double ln_ratio = 0.5 * log(a) - w * (1.0 / 8.0 - w2 * (1.0 / 192.0 - w2 * (1.0 / 640.0 - w2 * (17.0 / 14336.0))));
+    const double front = exp(ln_ratio - ln_sqrt_pi + a * log(x) + 0.5 * log(y));
+    double r;
+    if (x < (a + 1.0) / (a + 2.5)) r = front * sp_betacf(a, 0.5, x) / a;
+    else r = 1.0 - front * sp_betacf(0.5, a, y) * 2.0;
+    return r < 0.0 ? 0.0 : (r > 1.0 ? 1.0 : r);
+}
+
+// ---- double-double arithmetic: rho everywhere, and p of the rows with at most SP_DD_MAX_KEPT kept samples, where the
+// float64 that comes out is the correctly rounded one (the continued fraction is a few 1e-15 off, which shows in the
+// last printed digit of the table)
+constexpr int SP_DD_MAX_KEPT = 64;
+struct SpDD { double hi, lo; };
+__host__ __device__ inline SpDD sp_fast2sum(double a, double b) {          // |a| >= |b|
+    const double s = a + b;
+    return {s, b - (s - a)};
+}
+__host__ __device__ inline SpDD sp_2sum(double a, double b) {
+    const double s = a + b, bb = s - a;
+    return {s, (a - (s - bb)) + (b - bb)};
+}
+__host__ __device__ inline SpDD sp_add(SpDD a, SpDD b) {
+    SpDD s = sp_2sum(a.hi, b.hi);
+    const SpDD t = sp_2sum(a.lo, b.lo);
+    s = sp_fast2sum(s.hi, s.lo + t.hi);
+    return sp_fast2sum(s.hi, s.lo + t.lo);
+}
+__host__ __device__ inline SpDD sp_mul(SpDD a, SpDD b) {
+    const double p = a.hi * b.hi;
+    const double e = __builtin_fma(a.hi, b.hi, -p) + (a.hi * b.lo + a.lo * b.hi);
+    return sp_fast2sum(p, e);
+}
+__host__ __device__ inline SpDD sp_mul_d(SpDD a, double b) {
+    const double p = a.hi * b;
+    const double e = __builtin_fma(a.hi, b, -p) + a.lo * b;
+    return sp_fast2sum(p, e);
+}
+__host__ __device__ inline SpDD sp_div_d(SpDD a, double b) {               // one division: the residual step absorbs q1's error
+    const double inv = 1.0 / b, q1 = a.hi * inv;
+    const double r = __builtin_fma(-q1, b, a.hi) + a.lo;
+    return sp_fast2sum(q1, r * inv);
+}
+__host__ __device__ inline SpDD sp_div(SpDD a, SpDD b) {
+    const double q1 = a.hi / b.hi;
+    SpDD r = sp_add(a, sp_mul_d(b, -q1));
+    const double q2 = r.hi / b.hi;
+    r = sp_add(r, sp_mul_d(b, -q2));
+    const double q3 = r.hi / b.hi;
+    const SpDD q = sp_fast2sum(q1, q2);
+    return sp_fast2sum(q.hi, q.lo + q3);
+}
+__host__ __device__ inline SpDD sp_sqrt(SpDD a) {                         // a > 0
+    const double s = sqrt(a.hi);
+    return sp_fast2sum(s, (__builtin_fma(-s, s, a.hi) + a.lo) / (2.0 * s));
+}
+__host__ __device__ inline SpDD sp_u128_dd(unsigned __int128 v) {          // exact below 2^106
+    const uint64_t lo = (uint64_t)v;
+    const SpDD top = sp_2sum((double)(uint64_t)(v >> 64) * 18446744073709551616.0, (double)(lo >> 32) * 4294967296.0);
+    return sp_add(top, {(double)(lo & 0xffffffffull), 0.0});
+}
+
+// I_x(a, 1/2), a = nu / 2 <= 31, from x = 1 - rho^2, y = rho^2 and r = |rho|: with front = r x^a / B(a, 1/2),
+//   x <= 1/2:  front / a * sum_k (a + 1/2)_k / (a + 1)_k x^k            (every term positive: exact down any tail)
+//   else:      1 - 2 front * sum_k (a + 1/2)_k / (3/2)_k y^k            (y < 1/2, p > 1e-10: at most 34 of the 106 bits cancel)
+// B by B(a + 1, 1/2) = B(a, 1/2) a / (a + 1/2) from B(1/2, 1/2) = pi or B(1, 1/2) = 2
+__host__ __device__ inline double sp_beta_half_dd(int nu, SpDD x, SpDD y, SpDD r) {
+    const SpDD pi = {0x1.921fb54442d18p+1, 0x1.1a62633145c07p-53};
+    double a0 = (nu & 1) ? 0.5 : 1.0;
+    SpDD front = (nu & 1) ? sp_div(sp_sqrt(x), pi) : sp_mul_d(x, 0.5);     // x^a0 / B(a0, 1/2)
+    const double a = 0.5 * (double)nu;
+    for (; a0 < a; a0 += 1.0) front = sp_div_d(sp_mul_d(sp_mul(front, x), a0 + 0.5), a0);
+    front = sp_mul(front, r);
+    const bool direct = x.hi <= 0.5;
+    const SpDD z = direct ? x : y;
+    const double den0 = direct ? a + 1.0 : 1.5;
+    SpDD term = {1.0, 0.0}, sum = {1.0, 0.0};
+    for (int k = 0; k < 4000; ++k) {
+        term = sp_div_d(sp_mul_d(sp_mul(term, z), a + 0.5 + (double)k), den0 + (double)k);
+        sum = sp_add(sum, term);
+        if (term.hi < sum.hi * 0x1p-112 && z.hi * (a + 1.5 + (double)k) < den0 + 1.0 + (double)k) break;   // past the peak
+    }
+    SpDD p = sp_mul(front, sum);
+    if (direct) p = sp_div_d(p, a);
+    else p = sp_add({1.0, 0.0}, {-2.0 * p.hi, -2.0 * p.lo});
+    return p.hi + p.lo;
+}
+
+// rho and p of a tested row from the integer sums over its nv kept samples
+__host__ __device__ inline void sp_finish(int nv, long long sab, long long saa, long long sbb, double& rho, double& p) {
+    const long long S = (long long)nv * (nv + 1);
+    const long long N = nv * sab - S * S, Dx = nv * saa - S * S, Dy = nv * sbb - S * S;
+    rho = 0.0;
+    p = 1.0;
+    if (Dx == 0 || Dy == 0 || N == 0) return;            // a constant side; no monotone trend
+    const unsigned long long an = (unsigned long long)(N < 0 ? -N : N);
+    const unsigned __int128 DD = (unsigned __int128)(unsigned long long)Dx * (unsigned long long)Dy;
+    const unsigned __int128 NN = (unsigned __int128)an * an;
+    if (NN >= DD) {                                       // (Cauchy-Schwarz: never above)
+        rho = N > 0 ? 1.0 : -1.0;
+        p = 0.0;
+        return;
+    }
+    const SpDD dd = sp_u128_dd(DD);
+    const SpDD x = sp_div(sp_u128_dd(DD - NN), dd), y = sp_div(sp_u128_dd(NN), dd);      // 1 - rho^2, rho^2
+    const SpDD r = sp_sqrt(y);
+    rho = N > 0 ? r.hi + r.lo : -(r.hi + r.lo);
+    if (nv <= SP_DD_MAX_KEPT) p = sp_beta_half_dd(nv - 2, x, y, r);
+    else p = sp_beta_half(0.5 * (double)(nv - 2), x.hi, y.hi);
+}
+
+// ------------------------------------------------------------------ lane-group path: P lanes per row
+template <int P>
+__device__ __forceinline__ int sp_group_add(int v) {
+#pragma unroll
+    for (int ofs = 1; ofs < P; ofs <<= 1) v += __shfl_xor(v, ofs);
+    return v;
+}
+
+// numpy pairwise_sum of A[0..nv), nv <= 64 (one leaf), by a group of P >= 8 lanes, every lane of the group gets it: for
+// nv >= 8 lane j (mod 8) owns accumulator j, folded as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) by three xor exchanges as
+// in wave_pairwise_sum; then the tail (or, below 8 values, all of them) one after another
+__device__ __forceinline__ float sp_group_sum(const float* A, int nv, int gl) {
+    const int main_n = nv & ~7, j = gl & 7;
+    float r = 0.f;
+    if (nv >= 8) {
+        r = A[j];
+        for (int i = 8; i < main_n; i += 8) r += A[i + j];
+    }
+    r = r + __shfl_xor(r, 1);
+    r = r + __shfl_xor(r, 2);
+    r = r + __shfl_xor(r, 4);
+    if (nv < 8) r = 0.f;
+    for (int i = (nv >= 8 ? main_n : 0); i < nv; ++i) r += A[i];
+    return r;
+}
+
+template <int P>
+__global__ void __launch_bounds__(256) spearman_group_kernel(const float* __restrict__ ps, int64_t n, int s,
+                                                             const int32_t* __restrict__ cols, const int32_t* __restrict__ xg,
+                                                             int m, int ch, SpOut o) {
+    constexpr int R = 64 / P;                            // rows side by side in a wave
+    constexpr unsigned long long GMASK = P == 64 ? ~0ull : ((1ull << (P & 63)) - 1ull);
+    __shared__ float cx[4][64];                          // the kept values of the wave's rows, compacted, in list order
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
+    const int g = lane / P, gl = lane % P, g0 = g * P;
+    float* X = cx[wave] + g0;
+    const int col = gl < m ? cols[gl] : 0;
+    // the covariate tie group of this lane's list position covers the positions [glo, ghi) (a lane past the list is a
+    // group of its own)
+    unsigned long long below_lo, below_hi;
+    {
+        const int mine = gl < m ? xg[gl] : -1 - gl;
+        const int prev = __shfl_up(mine, 1);
+        const unsigned long long sm = (__ballot(gl == 0 || prev != mine) >> g0) & GMASK;      // bit i: a group starts at i
+        const unsigned long long upto = (2ull << gl) - 1ull;                                   // positions 0..gl
+        const int glo = 63 - __clzll((long long)(sm & upto));
+        const unsigned long long above = sm & ~upto;
+        const int ghi = above ? (__ffsll((long long)above) - 1) : P;
+        below_lo = (1ull << glo) - 1ull;
+        below_hi = ghi >= 64 ? ~0ull : ((1ull << ghi) - 1ull);
+    }
+    const int64_t n_chunks = (n + ch - 1) / ch;
+    for (int64_t c = (int64_t)blockIdx.x * wpb + wave; c < n_chunks; c += (int64_t)gridDim.x * wpb) {
+      const int64_t row0 = c * ch;
+      const int rows_here = (int)min((int64_t)ch, n - row0);
+      // lane i keeps the chunk's i-th row
+      int s_nv = 0, s_ab = 0, s_aa = 0, s_bb = 0;        // sums of products of doubled ranks <= 64 * 129^2
+      float s_med = 0.f, s_mean = 0.f;
+      for (int r0 = 0; r0 < rows_here; r0 += R) {        // wave-uniform
+        const int ri = r0 + g;
+        float x = __builtin_nanf("");
+        if (ri < rows_here && gl < m) x = __builtin_nontemporal_load(ps + (row0 + ri) * s + col);
+        const bool kept = x == x;
+        const unsigned long long km = (__ballot(kept) >> g0) & GMASK;
+        const int nv = __popcll(km);
+        // ---- the numpy-order sum over the compacted values
+        SD_WAVE_SYNC();          // the previous pass's readers are done with the wave's LDS
+        if (kept) X[__popcll(km & ((1ull << gl) - 1ull))] = x;
+        SD_WAVE_SYNC();
+        const float sum = 0.0f + sp_group_sum(X, nv, gl);            // np.sum starts from the identity 0: -0.0 values sum to +0.0
+        // ---- PS ranks by counting
+        const uint32_t xo = kept ? f32_ord(x) : SP_PAD;
+        int less = 0, eq = 0;
+#pragma unroll 8
+        for (int j = 0; j < P; ++j) {
+            const uint32_t v = __shfl(xo, g0 + j);
+            less += v < xo ? 1 : 0;
+            eq += v == xo ? 1 : 0;
+        }
+        // ---- the median: the values whose rank intervals [less, less + eq) hold positions h and h - 1
+        const int h = nv >> 1;
+        const unsigned long long mh = __ballot(kept && less <= h && h < less + eq) >> g0 & GMASK;
+        const unsigned long long ml = __ballot(kept && less <= h - 1 && h - 1 < less + eq) >> g0 & GMASK;
+        const float v1 = f32_unord(__shfl(xo, g0 + (mh ? __ffsll((long long)mh) - 1 : 0)));
+        const float v0 = f32_unord(__shfl(xo, g0 + (ml ? __ffsll((long long)ml) - 1 : 0)));
+        const float med = (nv & 1) ? v1 : (v0 + v1) / 2.0f;
+        // ---- the sums of the doubled ranks' products
+        const int a2 = __popcll(km & below_lo) + __popcll(km & below_hi) + 1;
+        const int b2 = 2 * less + eq + 1;
+        const int ab = sp_group_add<P>(kept ? a2 * b2 : 0);
+        const int aa = sp_group_add<P>(kept ? a2 * a2 : 0);
+        const int bb = sp_group_add<P>(kept ? b2 * b2 : 0);
+        // ---- to the lanes that keep the rows of this pass: lane r0 + q takes group q's
+        const int src = ((lane - r0) * P) & 63;
+        const bool mine = lane >= r0 && lane < r0 + R;
+        const int t_nv = __shfl(nv, src), t_ab = __shfl(ab, src), t_aa = __shfl(aa, src), t_bb = __shfl(bb, src);
+        const float t_med = __shfl(med, src), t_mean = __shfl(sum / (float)nv, src);
+        if (mine) { s_nv = t_nv; s_ab = t_ab; s_aa = t_aa; s_bb = t_bb; s_med = t_med; s_mean = t_mean; }
+      }
+      if (lane < rows_here) {
+        const int64_t row = row0 + lane;
+        const bool tested = s_nv >= 3;
+        double rho = 0.0, p = 0.0;
+        if (tested) sp_finish(s_nv, (long long)s_ab, (long long)s_aa, (long long)s_bb, rho, p);
+        o.tested[row] = tested ? 1 : 0;
+        o.p[row] = p;
+        if (o.rho) o.rho[row] = rho;
+        o.n_kept[row] = tested ? s_nv : 0;
+        o.med[row] = tested ? s_med : 0.f;
+        o.mean[row] = tested ? s_mean : 0.f;
+      }
+    }
+}
+
+// ------------------------------------------------------------------ wave path: one wave per row, E columns per lane
+// list position e * 64 + lane is element e of the lane, so a load and a ballot cover 64 consecutive positions
+template <int E>
+__global__ void __launch_bounds__(256) spearman_wave_kernel(const float* __restrict__ ps, int64_t n, int s,
+                                                            const int32_t* __restrict__ cols, const int32_t* __restrict__ xg,
+                                                            int m, int ch, SpOut o) {
+    constexpr int DEPTH = 2;                             // numpy's pairwise recursion over at most 256 values: 4 leaves
+    __shared__ float cx[4][64 * E];                      // the kept values of the wave's row, compacted, in list order
+    __shared__ int leaf_off[4][(1 << DEPTH) + 1];
+    __shared__ float leaf_sum[4][1 << DEPTH];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
+    float* X = cx[wave];
+    // the column of each of the lane's list positions and the bounds [glo, ghi) of its covariate tie group (xg never
+    // decreases); a position past the list has no column and an empty group
+    int col[E], glo[E], ghi[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int q = e * 64 + lane;
+        col[e] = 0; glo[e] = 0; ghi[e] = 0;
+        if (q < m) {
+            col[e] = cols[q];
+            const int mine = xg[q];
+            int lo = 0, hi = q;
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (xg[mid] < mine) lo = mid + 1; else hi = mid; }
+            glo[e] = lo;
+            lo = q + 1; hi = m;
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (xg[mid] <= mine) lo = mid + 1; else hi = mid; }
+            ghi[e] = lo;
+        }
+    }
+    const int64_t n_chunks = (n + ch - 1) / ch;
+    for (int64_t c = (int64_t)blockIdx.x * wpb + wave; c < n_chunks; c += (int64_t)gridDim.x * wpb) {
+      const int64_t row0 = c * ch;
+      const int rows_here = (int)min((int64_t)ch, n - row0);
+      // lane i keeps the chunk's i-th row
+      int s_nv = 0, s_ab = 0, s_aa = 0, s_bb = 0;        // sums of products of doubled ranks <= 256 * 513^2
+      float s_med = 0.f, s_mean = 0.f;
+      for (int r = 0; r < rows_here; ++r) {              // wave-uniform
+        const float* prow = ps + (row0 + r) * s;
+        float x[E];
+        unsigned long long km[E];
+        int base[E], nv = 0;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            x[e] = __builtin_nanf("");
+            if (e * 64 + lane < m) x[e] = __builtin_nontemporal_load(prow + col[e]);
+            km[e] = __ballot(x[e] == x[e]);
+            base[e] = nv;
+            nv += __popcll(km[e]);
+        }
+        // ---- the numpy-order sum over the compacted values
+        SD_WAVE_SYNC();          // the previous row's readers are done with the wave's LDS
+#pragma unroll
+        for (int e = 0; e < E; ++e)
+            if (x[e] == x[e]) X[base[e] + lanes_below(km[e])] = x[e];
+        SD_WAVE_SYNC();
+        const float sum = 0.0f + wave_pairwise_sum<DEPTH>(FloatAt{X}, nv, lane, leaf_off[wave], leaf_sum[wave]);
+        // ---- PS ranks by counting: every position's value is broadcast once
+        uint32_t xo[E];
+        int less[E], eq[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            xo[e] = x[e] == x[e] ? f32_ord(x[e]) : SP_PAD;
+            less[e] = 0; eq[e] = 0;
+        }
+#pragma unroll
+        for (int e2 = 0; e2 < E; ++e2) {
+            const int jn = min(64, m - e2 * 64);         // wave-uniform
+            for (int j = 0; j < jn; ++j) {
+                const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)xo[e2], j);
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    less[e] += v < xo[e] ? 1 : 0;
+                    eq[e] += v == xo[e] ? 1 : 0;
+                }
+            }
+        }
+        // ---- the median: the values whose rank intervals [less, less + eq) hold positions h and h - 1
+        const int h = nv >> 1;
+        uint32_t o1 = 0, o0 = 0;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const bool kept = x[e] == x[e];
+            const unsigned long long mh = __ballot(kept && less[e] <= h && h < less[e] + eq[e]);
+            const unsigned long long ml = __ballot(kept && less[e] <= h - 1 && h - 1 < less[e] + eq[e]);
+            if (mh) o1 = (uint32_t)__builtin_amdgcn_readlane((int)xo[e], __ffsll((long long)mh) - 1);      // (wave-uniform)
+            if (ml) o0 = (uint32_t)__builtin_amdgcn_readlane((int)xo[e], __ffsll((long long)ml) - 1);
+        }
+        const float v1 = f32_unord(o1), v0 = f32_unord(o0);
+        const float med = (nv & 1) ? v1 : (v0 + v1) / 2.0f;
+        // ---- the sums of the doubled ranks' products
+        int ab = 0, aa = 0, bb = 0;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            int before = 0, upto = 0;                    // kept positions below glo, below ghi
+#pragma unroll
+            for (int e2 = 0; e2 < E; ++e2) {
+                const int bl = glo[e] - e2 * 64, bh = ghi[e] - e2 * 64;
+                before += bl >= 64 ? __popcll(km[e2]) : (bl <= 0 ? 0 : __popcll(km[e2] & ((1ull << bl) - 1ull)));
+                upto += bh >= 64 ? __popcll(km[e2]) : (bh <= 0 ? 0 : __popcll(km[e2] & ((1ull << bh) - 1ull)));
+            }
+            if (x[e] == x[e]) {
+                const int a2 = before + upto + 1, b2 = 2 * less[e] + eq[e] + 1;
+                ab += a2 * b2;
+                aa += a2 * a2;
+                bb += b2 * b2;
+            }
+        }
+        ab = sp_group_add<64>(ab);
+        aa = sp_group_add<64>(aa);
+        bb = sp_group_add<64>(bb);
+        if (lane == r) { s_nv = nv; s_ab = ab; s_aa = aa; s_bb = bb; s_med = med; s_mean = sum / (float)nv; }
+      }
+      if (lane < rows_here) {
+        const int64_t row = row0 + lane;
+        const bool tested = s_nv >= 3;
+        double rho = 0.0, p = 0.0;
+        if (tested) sp_finish(s_nv, (long long)s_ab, (long long)s_aa, (long long)s_bb, rho, p);
+        o.tested[row] = tested ? 1 : 0;
+        o.p[row] = p;
+        if (o.rho) o.rho[row] = rho;
+        o.n_kept[row] = tested ? s_nv : 0;
+        o.med[row] = tested ? s_med : 0.f;
+        o.mean[row] = tested ? s_mean : 0.f;
+      }
+    }
+}
+
+// ------------------------------------------------------------------ general path: one workgroup per row
+// ascending bitonic sort of K[0..P) by the whole block, A[0..P) carried along (P a power of two); ends with a barrier
+__device__ void sp_block_sort(uint32_t* K, unsigned short* A, int P) {
+    const int tid = threadIdx.x;
+    for (int kk = 2; kk <= P; kk <<= 1) {
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < P; i += RB_THREADS) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const bool asc = (i & kk) == 0;
+                    const uint32_t x = K[i], y = K[l];
+                    if ((x > y) == asc && x != y) {
+                        K[i] = y; K[l] = x;
+                        const unsigned short t = A[i];
+                        A[i] = A[l]; A[l] = t;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__global__ void __launch_bounds__(RB_THREADS) spearman_block_kernel(const float* __restrict__ ps, int64_t n, int s,
+                                                                    const int32_t* __restrict__ cols,
+                                                                    const int32_t* __restrict__ xg, int m, int P, SpOut o) {
+    extern __shared__ __align__(16) unsigned char smems[];
+    uint32_t* K = reinterpret_cast<uint32_t*>(smems);          // [P] first the compacted floats, then their order bits
+    uint32_t* GB = K + P;                                       // [P] list position -> its tie group's ghi << 16 | glo
+    unsigned short* A = reinterpret_cast<unsigned short*>(GB + P);   // [P] kept element -> list position, then its a2
+    unsigned short* C = A + P;                                  // [P + 2] list position -> kept values before it; C[m] = all
+    float* F = reinterpret_cast<float*>(K);
+    __shared__ float leaf_sum[SP_LEAF_MAX];
+    __shared__ float scratch8[SP_LEAF_MAX * 8];
+    __shared__ int leaf_off[SP_LEAF_MAX + 1];
+    __shared__ int wcnt[RB_THREADS / 64];
+    __shared__ unsigned long long accS[3];                      // sum a2 b2, sum a2^2, sum b2^2
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    // the tie-group bounds of every list position, once: xg never decreases
+    for (int q = tid; q < m; q += RB_THREADS) {
+        const int mine = xg[q];
+        int lo = 0, hi = q;                                     // first position of the group
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (xg[mid] < mine) lo = mid + 1; else hi = mid; }
+        const int glo = lo;
+        lo = q + 1; hi = m;                                     // first position past it
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (xg[mid] <= mine) lo = mid + 1; else hi = mid; }
+        GB[q] = ((uint32_t)lo << 16) | (uint32_t)glo;
+    }
+    __syncthreads();
+    for (int64_t row = blockIdx.x; row < n; row += gridDim.x) {
+        const float* prow = ps + row * s;
+        // ---- ordered compaction of the non-NaN values, with the list position of each and the prefix of every position
+        int nv = 0;
+        for (int c0 = 0; c0 < m; c0 += RB_THREADS) {
+            const int q = c0 + tid;
+            float x = __builtin_nanf("");
+            if (q < m) x = prow[cols[q]];
+            const bool valid = x == x;
+            const unsigned long long mk = __ballot(valid);
+            if (lane == 0) wcnt[w] = __popcll(mk);
+            __syncthreads();
+            int woff = 0, tot = 0;
+            for (int i = 0; i < RB_THREADS / 64; ++i) {
+                if (i < w) woff += wcnt[i];
+                tot += wcnt[i];
+            }
+            const int pos = nv + woff + lanes_below(mk);
+            if (q < m) C[q] = (unsigned short)pos;
+            if (valid) {
+                F[pos] = x;
+                A[pos] = (unsigned short)q;
+            }
+            nv += tot;
+            __syncthreads();
+        }
+        if (nv < 3) {                                           // block-uniform
+            if (tid == 0) {
+                o.tested[row] = 0; o.p[row] = 0.0;
+                if (o.rho) o.rho[row] = 0.0;
+                o.n_kept[row] = 0; o.med[row] = 0.f; o.mean[row] = 0.f;
+            }
+            continue;                                           // (the compaction ended with a barrier)
+        }
+        if (tid == 0) C[m] = (unsigned short)nv;
+        if (tid < 3) accS[tid] = 0ull;
+        // np.sum: the identity 0 plus the pairwise tree
+        const float sum = 0.0f + block_pairwise_sum<PW_DEPTH>(F, nv, leaf_off, leaf_sum, scratch8, SP_LEAF_MAX);
+        // ---- covariate ranks of the kept, order bits of their values, padding last (each index in place)
+        for (int i = tid; i < P; i += RB_THREADS) {
+            uint32_t k = SP_PAD;
+            unsigned short a2 = 0;
+            if (i < nv) {
+                const uint32_t gb = GB[A[i]];
+                a2 = (unsigned short)((int)C[gb & 0xffffu] + (int)C[gb >> 16] + 1);
+                k = f32_ord(F[i]);
+            }
+            K[i] = k;
+            A[i] = a2;
+        }
+        __syncthreads();
+        sp_block_sort(K, A, P);
+        // ---- PS ranks from the run bounds
+        long long ab = 0, aa = 0, bb = 0;
+        for (int q = tid; q < nv; q += RB_THREADS) {
+            const uint32_t code = K[q];
+            int lo = 0, hi = q;                                 // first position with this code
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (K[mid] < code) lo = mid + 1; else hi = mid; }
+            const int first = lo;
+            lo = q + 1; hi = nv;                                // first position with a larger code
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (K[mid] <= code) lo = mid + 1; else hi = mid; }
+            const long long b2 = first + lo + 1, a2 = A[q];
+            ab += a2 * b2;
+            aa += a2 * a2;
+            bb += b2 * b2;
+        }
+#pragma unroll
+        for (int ofs = 32; ofs > 0; ofs >>= 1) {
+            ab += __shfl_xor(ab, ofs);
+            aa += __shfl_xor(aa, ofs);
+            bb += __shfl_xor(bb, ofs);
+        }
+        if (lane == 0) {
+            atomicAdd(&accS[0], (unsigned long long)ab);
+            atomicAdd(&accS[1], (unsigned long long)aa);
+            atomicAdd(&accS[2], (unsigned long long)bb);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            const int h = nv >> 1;
+            const float v1 = f32_unord(K[h]);
+            const float med = (nv & 1) ? v1 : (f32_unord(K[h - 1]) + v1) / 2.0f;        // np.median on float32
+            double rho, p;
+            sp_finish(nv, (long long)accS[0], (long long)accS[1], (long long)accS[2], rho, p);
+            o.tested[row] = 1; o.p[row] = p;
+            if (o.rho) o.rho[row] = rho;
+            o.n_kept[row] = nv; o.med[row] = med; o.mean[row] = sum / (float)nv;
+        }
+        __syncthreads();           // thread 0 has read the row's LDS
+    }
+}
+
+template <int P>
+int sp_launch_group(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* d_cols, const int32_t* d_xg, int m,
+                    SpOut o) {
+    const int waves = 4;
+    const int ch = rows_per_chunk(ctx->n_cu, n);
+    int64_t blocks = sd_ceil_div(sd_ceil_div(n, ch), waves);
+    const int64_t cap = (int64_t)ctx->n_cu * 32 / waves;
+    if (blocks > cap) blocks = cap;
+    SD_LAUNCH(ctx, "spearman_group_kernel", (spearman_group_kernel<P>), dim3((unsigned)blocks), dim3(waves * 64), 0, d_ps, n,
+              s, d_cols, d_xg, m, ch, o);
+    return SDICE_OK;
+}
+
+template <int E>
+int sp_launch_wave(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* d_cols, const int32_t* d_xg, int m,
+                   SpOut o) {
+    const int waves = 4;
+    const int ch = rows_per_chunk(ctx->n_cu, n);
+    int64_t blocks = sd_ceil_div(sd_ceil_div(n, ch), waves);
+    const int64_t cap = (int64_t)ctx->n_cu * 32 / waves;
+    if (blocks > cap) blocks = cap;
+    SD_LAUNCH(ctx, "spearman_wave_kernel", (spearman_wave_kernel<E>), dim3((unsigned)blocks), dim3(waves * 64), 0, d_ps, n,
+              s, d_cols, d_xg, m, ch, o);
+    return SDICE_OK;
+}
+
+int sp_check_scalars(int64_t n, int32_t s, int32_t m) {
+    SD_ARG(n >= 0 && s >= 0, "negative size");
+    if (m < SP_MIN_COLS || m > SP_MAX_COLS) {
+        sdice_set_error("sdice_spearman: %d columns listed, %d..%d are supported", (int)m, SP_MIN_COLS, SP_MAX_COLS);
+        return SDICE_ERR_ARG;
+    }
+    SD_ARG(m <= s, "more columns listed than the table has (a column may be listed once)");
+    return SDICE_OK;
+}
+
+}  // namespace
+
+extern "C" int sdice_spearman_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, const int32_t* d_cols,
+                                  const int32_t* d_xg, int32_t m, uint8_t* d_tested, double* d_p, double* d_rho,
+                                  int32_t* d_n_kept, float* d_med, float* d_mean) {
+    SD_ARG(ctx, "ctx is NULL");
+    SD_TRY(sp_check_scalars(n, s, m));
+    if (n == 0) return SDICE_OK;
+    SD_ARG(d_tested && d_p && d_n_kept && d_med && d_mean, "NULL output");
+    SD_ARG(d_ps && d_cols && d_xg, "NULL input");
+    SD_HIP(hipSetDevice(ctx->device));
+    SD_TRY(ctx->arena.reset(ctx->stream));
+    SpOut o{d_tested, d_p, d_rho, d_n_kept, d_med, d_mean};
+    if (m <= SP_GROUP_MAX) {
+        if (m <= 8) return sp_launch_group<8>(ctx, d_ps, n, s, d_cols, d_xg, m, o);
+        if (m <= 16) return sp_launch_group<16>(ctx, d_ps, n, s, d_cols, d_xg, m, o);
+        if (m <= 32) return sp_launch_group<32>(ctx, d_ps, n, s, d_cols, d_xg, m, o);
+        return sp_launch_group<64>(ctx, d_ps, n, s, d_cols, d_xg, m, o);
+    }
+    if (m <= SP_WAVE_MAX / 2) return sp_launch_wave<2>(ctx, d_ps, n, s, d_cols, d_xg, m, o);
+    if (m <= SP_WAVE_MAX) return sp_launch_wave<4>(ctx, d_ps, n, s, d_cols, d_xg, m, o);
+    int P = 512;
+    while (P < m) P <<= 1;
+    const size_t lds = (size_t)P * 12 + 8;                // K, GB: 4 bytes each; A, C: 2 bytes each, C two entries longer (49160 B at most)
+    int64_t blocks = n;
+    const int64_t cap = (int64_t)ctx->n_cu * 8;
+    if (blocks > cap) blocks = cap;
+    SD_LAUNCH(ctx, "spearman_block_kernel", spearman_block_kernel, dim3((unsigned)blocks), dim3(RB_THREADS), lds, d_ps, n,
+              (int)s, d_cols, d_xg, (int)m, P, o);
+    return SDICE_OK;
+}
+
+extern "C" int sdice_spearman(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps, const int32_t* cols,
+                              const int32_t* xg, int32_t m, uint8_t* tested, double* p, double* rho, int32_t* n_kept,
+                              float* med, float* mean) {
+    SD_ARG(ctx, "ctx is NULL");
+    SD_TRY(sp_check_scalars(n, s, m));
+    SD_ARG(cols && xg, "column list or tie-group list is NULL");
+    {
+        std::vector<char> seen((size_t)s, 0);
+        for (int q = 0; q < m; ++q) {
+            SD_ARG(cols[q] >= 0 && cols[q] < s, "column index out of range");
+            SD_ARG(!seen[cols[q]], "a column may be listed once");
+            seen[cols[q]] = 1;
+        }
+        SD_ARG(xg[0] == 0, "xg must start at 0");
+        for (int q = 1; q < m; ++q) SD_ARG(xg[q] == xg[q - 1] || xg[q] == xg[q - 1] + 1, "xg must rise in steps of 0 or 1");
+    }
+    if (n == 0) return SDICE_OK;
+    SD_ARG(tested && p && n_kept && med && mean, "NULL output");
+    SD_ARG(ps, "ps is NULL");
+    HostStaging st(ctx);
+    float *d_ps, *df;
+    int32_t *dc, *dg, *dn;
+    uint8_t* dt;
+    double* dd;
+    SD_TRY(st.upload(&d_ps, ps, n * s));
+    SD_TRY(st.upload(&dc, cols, m));
+    SD_TRY(st.upload(&dg, xg, m));
+    SD_TRY(st.alloc(&dt, n));
+    SD_TRY(st.alloc(&dd, n * 2));      // p, rho
+    SD_TRY(st.alloc(&dn, n));
+    SD_TRY(st.alloc(&df, n * 2));      // med, mean
+    SD_TRY(sdice_spearman_dev(ctx, n, s, d_ps, dc, dg, m, dt, dd, dd + n, dn, df, df + n));
+    SD_TRY(st.download(tested, dt, n));
+    SD_TRY(st.download(p, dd, n));
+    if (rho) SD_TRY(st.download(rho, dd + n, n));
+    SD_TRY(st.download(n_kept, dn, n));
+    SD_TRY(st.download(med, df, n));
+    return st.download(mean, df + n, n);
+}

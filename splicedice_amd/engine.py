@@ -47,6 +47,26 @@ def kruskal_sets(sets, s=None):
     return np.ascontiguousarray(cols, dtype=np.int32), set_ptr
 
 
+def spearman_order(cols, x):
+    """the listed columns and the covariate value of each as sdice_spearman takes them -> (cols int32 sorted by x, ties in
+    the order given (a stable sort), xg int32: the dense tie-group id of each sorted column: xg[0] = 0, one more at every
+    step to a larger x).  Ties are by float64 equality (-0.0 == 0.0).  A NaN or an infinite x raises ValueError."""
+    cols = np.asarray(cols).reshape(-1)
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    if cols.size != x.size:
+        raise ValueError(f"spearman: {cols.size} columns but {x.size} covariate values")
+    if cols.size and cols.dtype.kind not in "iu":
+        raise TypeError(f"spearman: column indices must be integers, got {cols.dtype}")
+    if not np.all(np.isfinite(x)):
+        raise ValueError("spearman: the covariate must be finite (leave a sample without a value out of the list)")
+    order = np.argsort(x, kind="stable")
+    xs = x[order]
+    xg = np.zeros(x.size, dtype=np.int32)
+    if x.size:
+        xg[1:] = np.cumsum(xs[1:] != xs[:-1])
+    return np.ascontiguousarray(cols[order], dtype=np.int32), xg
+
+
 class DeviceArray:
     """A device allocation with a numpy-like shape/dtype tag (owned by a Context)."""
 
@@ -311,6 +331,20 @@ class Context:
                                         _ptr(out["mean1"]), _ptr(out["mean2"]), _ptr(out["delta"])), "sdice_signedrank")
         return out
 
+    def spearman(self, ps, cols, x):
+        """scipy.stats.spearmanr(x_kept, ps_kept) per row between the PS values of the listed columns and the covariate x
+        (one finite value per listed column) under the row rules of ranksum(); un-compacted outputs: tested, p, rho,
+        n_kept (int32), med, mean of the kept PS values (in the order of spearman_order(cols, x))."""
+        ps = _c(ps, np.float32)
+        n, s = ps.shape
+        cols, xg = spearman_order(cols, x)
+        out = dict(tested=np.zeros(n, np.uint8), p=np.zeros(n, np.float64), rho=np.zeros(n, np.float64),
+                   n_kept=np.zeros(n, np.int32), med=np.zeros(n, np.float32), mean=np.zeros(n, np.float32))
+        check(self.lib.sdice_spearman(self.h, n, s, _ptr(ps), _ptr(cols), _ptr(xg), cols.size, _ptr(out["tested"]),
+                                      _ptr(out["p"]), _ptr(out["rho"]), _ptr(out["n_kept"]), _ptr(out["med"]),
+                                      _ptr(out["mean"])), "sdice_spearman")
+        return out
+
     def fisher_pairs(self, incl, excl, pairs=None):
         """pairwise_fisher.py:164-179 -> p float64[n, s(s-1)/2]; pairs = [m, 2] column indices: p float64[n, m], column q
         the table [[incl_i, incl_j], [excl_i, excl_j]] of pair q = (i, j) -- any order, i > j and repeats allowed"""
@@ -432,6 +466,13 @@ class Context:
                                             out["tested"].ptr, out["p"].ptr, out["z"].ptr if out.get("z") else None,
                                             out["med1"].ptr, out["med2"].ptr, out["mean1"].ptr, out["mean2"].ptr,
                                             out["delta"].ptr), "sdice_signedrank_dev")
+
+    def spearman_dev(self, d_ps, d_cols, d_xg, out):
+        """d_cols, d_xg: the device copies of spearman_order()'s pair; out: device tested, p, (rho), n_kept, med, mean"""
+        n, s = d_ps.shape
+        check(self.lib.sdice_spearman_dev(self.h, n, s, d_ps.ptr, d_cols.ptr, d_xg.ptr, d_cols.shape[0],
+                                          out["tested"].ptr, out["p"].ptr, out["rho"].ptr if out.get("rho") else None,
+                                          out["n_kept"].ptr, out["med"].ptr, out["mean"].ptr), "sdice_spearman_dev")
 
     def kruskal_dev(self, d_ps, d_cols, set_ptr, out):
         """d_cols: the device copy of kruskal_sets()'s cols; set_ptr: its HOST offsets; out: device tested, p, (h), med and
