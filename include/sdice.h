@@ -234,6 +234,38 @@ int sdice_spearman_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, 
                        const int32_t* d_xg, int32_t m, uint8_t* d_tested, double* d_p, double* d_rho,
                        int32_t* d_n_kept, float* d_med, float* d_mean);
 
+/* ---- sample_matrix: sample-by-sample sums over the rows two samples share (not in the reference).
+ *  cols[m]: the selected columns in output order, 2 <= m <= 4096, every index in [0, s), each at most once.  The four
+ *  outputs are m x m int64, row-major, entry [a * m + b].  With k_a(r) the integer key of ps[r, cols[a]] (the value is
+ *  float32(k / 1000), k = 0 .. 1000; -0.0 is key 0) and v_a(r) = 1 when that value is not NaN (any payload), else 0, over
+ *  the rows r of the table:
+ *    shared[a,b] = sum v_a v_b            the junctions both samples have (symmetric)
+ *    sum1[a,b]   = sum k_a v_a v_b        a's key sum over the shared rows (sum1[b,a] is b's)
+ *    sum2[a,b]   = sum k_a^2 v_a v_b
+ *    prod[a,b]   = sum k_a k_b v_a v_b    (symmetric)
+ *  All sums are exact integers, whatever the launch shape (param gram.rows_per_wg).  Any other value in a selected column
+ *  -- off the 3-decimal grid, outside [0, 1], +-inf -- is refused: SDICE_ERR_ARG, sdice_last_error() names the row and the
+ *  table column of the first one, and the check runs before any accumulation, so the outputs are untouched.  Unselected
+ *  columns are never read.  m out of range, a column out of range or listed twice, a NULL output: SDICE_ERR_ARG before any
+ *  launch, outputs untouched (the host call checks the column list; the _dev call checks m, m <= s and the pointers, and
+ *  refuses a column index outside [0, s) that its pre-pass meets).  n = 0 gives all-zero matrices.  Every call zeroes its
+ *  outputs itself.  The _dev call synchronises the context stream ONCE, after the pre-pass, to read the result of the
+ *  bad-value check back; the sums are then queued asynchronously.  Device scratch: 2 bytes per row and selected column
+ *  (rounded up to 64 columns) + two m x m int64 planes. */
+int sdice_sample_gram(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps, const int32_t* cols, int32_t m,
+                      int64_t* shared, int64_t* sum1, int64_t* sum2, int64_t* prod);
+int sdice_sample_gram_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, const int32_t* d_cols, int32_t m,
+                          int64_t* d_shared, int64_t* d_sum1, int64_t* d_sum2, int64_t* d_prod);
+/* The host finish of the four matrices above (no context, no GPU): per pair, N = shared[a,b], all integers formed exactly
+ * (128-bit):  num = N prod[a,b] - sum1[a,b] sum1[b,a],  va = N sum2[a,b] - sum1[a,b]^2,  vb likewise from [b,a].
+ *  corr[a,b] = double(num) / sqrt(double(va) double(vb)) clamped to [-1, 1], the Pearson correlation of the two samples'
+ *  PS values over the shared rows; NaN when N < min_shared or va <= 0 or vb <= 0; the diagonal is exactly 1.0 when va > 0.
+ *  rmsd[a,b] = sqrt(double(sum2[a,b] + sum2[b,a] - 2 prod[a,b]) / double(N)) / 1000, the root-mean-square PS difference
+ *  over the shared rows; NaN when N < min_shared or N = 0; defined for constant samples, 0 on the diagonal.
+ *  Both come out symmetric bit for bit.  min_shared < 1, m < 1 or a NULL pointer: SDICE_ERR_ARG. */
+int sdice_sample_matrix_finish(int32_t m, const int64_t* shared, const int64_t* sum1, const int64_t* sum2,
+                               const int64_t* prod, int64_t min_shared, double* corr, double* rmsd);
+
 /* ---- pairwise: replaces the per-pair loop pairwise_fisher.py:164-179
  *      (scipy.stats.fisher_exact two-sided on [[incl_a, incl_b],[excl_a, excl_b]]).
  *  incl[n,s] int32, excl[n,s] int64 (from sdice_ps); p[n, s(s-1)/2] float64 row-major,

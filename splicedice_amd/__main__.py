@@ -16,6 +16,7 @@ ACCELERATED = {
     "compare_sample_sets": "splicedice_amd.compare_sample_sets",
     "pairwise": "splicedice_amd.pairwise",
     "correlate": "splicedice_amd.correlate",
+    "sample_matrix": "splicedice_amd.sample_matrix",
     "similarity": "splicedice_amd.similarity",
     "findOutliers": "splicedice_amd.find_outliers",
     "ir_table": "splicedice_amd.ir_table",

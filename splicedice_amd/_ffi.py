@@ -56,6 +56,9 @@ SIGNATURES = {
     "sdice_signedrank_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 8,
     "sdice_spearman": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 6,
     "sdice_spearman_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 6,
+    "sdice_sample_gram": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32] + [vp] * 4,
+    "sdice_sample_gram_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32] + [vp] * 4,
+    "sdice_sample_matrix_finish": [C.c_int32, vp, vp, vp, vp, C.c_int64, vp, vp],
     "sdice_fisher_pairs": [ctxp, C.c_int64, C.c_int32, vp, vp, vp],
     "sdice_fisher_pairs_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, vp],
     "sdice_fisher_tables": [ctxp, C.c_int64, vp, vp],

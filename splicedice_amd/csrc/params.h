@@ -53,7 +53,9 @@
     X(BH_FINISH_NT, "bh.finish_nt", 0, "1 = non-temporal gather loads in the finish kernel")                            \
     X(BH_WG, "bh.wg", 256, "threads of a bucket workgroup: 256, 512 or 1024")                                           \
     X(BH_BIG_WG, "bh.big_wg", 512, "threads of a workgroup of the second bucket kernel: 512 (4 values per thread) or 256 (8)") \
-    X(BH_SPB, "bh.spb", 8, "samples per bucket")
+    X(BH_SPB, "bh.spb", 8, "samples per bucket")                                                                        \
+    /* sample Gram sums (gram.hip) */                                                                                   \
+    X(GRAM_ROWS_PER_WG, "gram.rows_per_wg", 0, "rows of a workgroup's slice, raised to a multiple of 64 (the smallest slice); 0 = by size: 4096, halved down to 256 while the grid is small")
 
 enum SdParam : int {
 #define X(id, name, dflt, meaning) SD_P_##id,

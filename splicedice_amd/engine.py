@@ -67,6 +67,31 @@ def spearman_order(cols, x):
     return np.ascontiguousarray(cols[order], dtype=np.int32), xg
 
 
+def gram_columns(cols):
+    """the selected columns of sample_gram as the library takes them: int32 [m], C-contiguous (the library checks the range
+    and that each is listed once)"""
+    a = np.asarray(cols).reshape(-1)
+    if a.size and a.dtype.kind not in "iu":
+        raise TypeError(f"sample_gram: column indices must be integers, got {a.dtype}")
+    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+        raise ValueError("sample_gram: column index out of range")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def sample_matrix_finish(shared, sum1, sum2, prod, min_shared=3):
+    """the four int64 [m, m] matrices of sample_gram -> (corr, rmsd) float64 [m, m]: the Pearson correlation and the
+    root-mean-square PS difference of every sample pair over the rows both have, NaN where fewer than min_shared rows are
+    shared (corr also where a sample is constant over them).  Host code: no context, no GPU (sdice_sample_matrix_finish)."""
+    mats = [np.ascontiguousarray(x, dtype=np.int64) for x in (shared, sum1, sum2, prod)]
+    m = mats[0].shape[0]
+    if any(x.shape != (m, m) for x in mats):
+        raise ValueError(f"sample_matrix_finish: four square matrices of one size, got {[x.shape for x in mats]}")
+    corr, rmsd = np.empty((m, m), np.float64), np.empty((m, m), np.float64)
+    check(_ffi.load().sdice_sample_matrix_finish(m, *[_ptr(x) for x in mats], int(min_shared), _ptr(corr), _ptr(rmsd)),
+          "sdice_sample_matrix_finish")
+    return corr, rmsd
+
+
 class DeviceArray:
     """A device allocation with a numpy-like shape/dtype tag (owned by a Context)."""
 
@@ -345,6 +370,19 @@ class Context:
                                       _ptr(out["mean"])), "sdice_spearman")
         return out
 
+    def sample_gram(self, ps, cols):
+        """the exact integer sums of every pair of the listed columns over the rows both have a value in -> dict of int64
+        [m, m]: shared (row count), sum1 / sum2 ([a, b]: a's sum of 3-decimal keys / squared keys over the rows shared
+        with b), prod (sum of key products).  A value off the 3-decimal grid in a listed column raises SdiceError."""
+        ps = _c(ps, np.float32)
+        n, s = ps.shape
+        cols = gram_columns(cols)
+        m = cols.size
+        out = {k: np.zeros((m, m), np.int64) for k in ("shared", "sum1", "sum2", "prod")}
+        check(self.lib.sdice_sample_gram(self.h, n, s, _ptr(ps), _ptr(cols), m, _ptr(out["shared"]), _ptr(out["sum1"]),
+                                         _ptr(out["sum2"]), _ptr(out["prod"])), "sdice_sample_gram")
+        return out
+
     def fisher_pairs(self, incl, excl, pairs=None):
         """pairwise_fisher.py:164-179 -> p float64[n, s(s-1)/2]; pairs = [m, 2] column indices: p float64[n, m], column q
         the table [[incl_i, incl_j], [excl_i, excl_j]] of pair q = (i, j) -- any order, i > j and repeats allowed"""
@@ -473,6 +511,13 @@ class Context:
         check(self.lib.sdice_spearman_dev(self.h, n, s, d_ps.ptr, d_cols.ptr, d_xg.ptr, d_cols.shape[0],
                                           out["tested"].ptr, out["p"].ptr, out["rho"].ptr if out.get("rho") else None,
                                           out["n_kept"].ptr, out["med"].ptr, out["mean"].ptr), "sdice_spearman_dev")
+
+    def sample_gram_dev(self, d_ps, d_cols, out):
+        """d_cols: the device copy of gram_columns(); out: device shared, sum1, sum2, prod, int64 [m, m] each.  Synchronises
+        once (the bad-value check of the pre-pass); the sums are queued."""
+        n, s = d_ps.shape
+        check(self.lib.sdice_sample_gram_dev(self.h, n, s, d_ps.ptr, d_cols.ptr, d_cols.shape[0], out["shared"].ptr,
+                                             out["sum1"].ptr, out["sum2"].ptr, out["prod"].ptr), "sdice_sample_gram_dev")
 
     def kruskal_dev(self, d_ps, d_cols, set_ptr, out):
         """d_cols: the device copy of kruskal_sets()'s cols; set_ptr: its HOST offsets; out: device tested, p, (h), med and
