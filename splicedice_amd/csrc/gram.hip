@@ -304,14 +304,7 @@ extern "C" int sdice_sample_gram(sdice_ctx* ctx, int64_t n, int32_t s, const flo
     SD_ARG(ctx, "ctx is NULL");
     SD_TRY(gram_check_scalars(n, s, m));
     SD_ARG(cols, "column list is NULL");
-    {
-        std::vector<char> seen((size_t)s, 0);
-        for (int q = 0; q < m; ++q) {
-            SD_ARG(cols[q] >= 0 && cols[q] < s, "column index out of range");
-            SD_ARG(!seen[cols[q]], "a column may be listed once");
-            seen[cols[q]] = 1;
-        }
-    }
+    SD_TRY(check_columns(__func__, {cols}, m, s, "column index out of range", "a column may be listed once"));
     SD_ARG(shared && sum1 && sum2 && prod, "NULL output");
     SD_ARG(ps || n == 0, "ps is NULL");
     const int64_t mm = (int64_t)m * m;

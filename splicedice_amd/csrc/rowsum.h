@@ -1,12 +1,16 @@
 // Per-row device helpers that the rank tests share (ranksum.hip: K5, kruskal.hip: K12, signedrank.hip: K13, spearman.hip: K14): numpy's float32 pairwise
-// summation reproduced operation for operation (by a block and by a wave), the ordered NaN-dropping compaction of a
-// row's selected columns, np.median of a sorted run, the 3-decimal PS key of a float and its float back, the median
-// search in the 16-bins-per-lane histograms of the counting kernels, and the rows-per-wave chunk of their launches.
+// summation reproduced operation for operation (by a block, by a wave and by a lane group), the ordered NaN-dropping
+// compaction of a row's selected columns, np.median of a sorted run, the 3-decimal PS key of a float and its float back,
+// the order-preserving bits of a float, the workgroup's bitonic network, the tie-run bounds of a sorted array, the median
+// search in the 16-bins-per-lane histograms of the counting kernels; and for the host the launch sizes of the
+// wave-per-chunk and row-per-workgroup kernels and the check of a column list (gram.hip takes only that).
 // Every helper is inlined into the kernels that call it and the kernels themselves stay in their .hip files, so a change
 // to a helper here is a change to each kernel that uses it -- ranksum.hip's pairq and count kernels among them, whose
 // committed counter pass is stamped with the hash of ranksum.hip alone and will not notice.
 #pragma once
 #include "common.h"
+#include <algorithm>
+#include <initializer_list>
 
 #define SD_WAVE_SYNC()                                        \
     do {                                                      \
@@ -209,13 +213,121 @@ __device__ __forceinline__ int find_bin(const unsigned* const& H, const int& lan
 }
 
 // order-preserving bits of a non-NaN float (-0.0 == +0.0), below 0xFFFFFFFF, and the float back (+0.0 for either zero):
-// what spearman.hip sorts and counts on (kruskal.hip and signedrank.hip keep their own kw_ / sr_ copies)
+// what the block kernels of kruskal.hip, signedrank.hip and spearman.hip sort and the others count on
 __device__ __forceinline__ uint32_t f32_ord(float v) {
     const uint32_t b = __float_as_uint(v + 0.0f);
     return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
 }
 __device__ __forceinline__ float f32_unord(uint32_t o) {
     return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
+}
+
+// np.median of the nv smallest of K[0..), sorted ascending, whose low 32 bits are order-preserving bits
+template <class T>
+__device__ __forceinline__ float median_of_ord(const T* K, int nv) {
+    const int h = nv >> 1;
+    const float v1 = f32_unord((uint32_t)K[h]);
+    return (nv & 1) ? v1 : (f32_unord((uint32_t)K[h - 1]) + v1) / 2.0f;
+}
+
+// ---- lane groups: P lanes (a power of two) own a row, 64 / P rows side by side in a wave, a pass of the chunk loop takes
+// the rows r0 .. r0 + R of the chunk and lane i of the wave keeps what the chunk's i-th row came to
+template <int P>
+struct LaneGroup {
+    static constexpr int R = 64 / P;
+    static constexpr unsigned long long MASK = P == 64 ? ~0ull : ((1ull << (P & 63)) - 1ull);      // of a ballot shifted down to the group
+    // the lane that holds group q's value for lane r0 + q, and whether this lane keeps a row of the pass
+    static __device__ __forceinline__ int src(int lane, int r0) { return ((lane - r0) * P) & 63; }
+    static __device__ __forceinline__ bool mine(int lane, int r0) { return lane >= r0 && lane < r0 + R; }
+};
+
+// sum over the group, to every lane of it
+template <int P>
+__device__ __forceinline__ int group_add(int v) {
+#pragma unroll
+    for (int ofs = 1; ofs < P; ofs <<= 1) v += __shfl_xor(v, ofs);
+    return v;
+}
+
+// numpy pairwise_sum of A[0..nv), nv <= 64 (one leaf), by a group of P >= 8 lanes, every lane of the group gets it: for
+// nv >= 8 lane j (mod 8) owns accumulator j, folded as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) by three xor exchanges as
+// in wave_pairwise_sum; then the tail (or, below 8 values, all of them) one after another
+__device__ __forceinline__ float group_sum(const float* A, int nv, int gl) {
+    const int main_n = nv & ~7, j = gl & 7;
+    float r = 0.f;
+    if (nv >= 8) {
+        r = A[j];
+        for (int i = 8; i < main_n; i += 8) r += A[i + j];
+    }
+    r = r + __shfl_xor(r, 1);
+    r = r + __shfl_xor(r, 2);
+    r = r + __shfl_xor(r, 4);
+    if (nv < 8) r = 0.f;
+    for (int i = (nv >= 8 ? main_n : 0); i < nv; ++i) r += A[i];
+    return r;
+}
+
+// ---- a row per workgroup
+// Ordered NaN-dropping compaction by the whole block, the general form: load(q) gives position q's value, a float or a
+// pair of them (NaN past the list: q runs to cnt rounded up to the block), kept when it holds no NaN; sink(q, pos,
+// kept, v) follows with pos = the number of kept positions below q.  Returns the count; ends with a barrier.
+// (block_compact above is the one-list case with the prefix from a 64-bit mask, as ranksum.hip's and kruskal.hip's
+// kernels were built with.)
+__device__ __forceinline__ bool holds_no_nan(float v) { return v == v; }
+__device__ __forceinline__ bool holds_no_nan(float2 v) { return v.x == v.x && v.y == v.y; }
+template <class Load, class Sink>
+__device__ int block_compact_by(int cnt, int* wcnt /* [RB_THREADS/64] shared */, Load load, Sink sink) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    int base = 0;
+    for (int c0 = 0; c0 < cnt; c0 += RB_THREADS) {
+        const int q = c0 + tid;
+        const auto v = load(q);
+        const bool valid = holds_no_nan(v);
+        const unsigned long long mk = __ballot(valid);
+        if (lane == 0) wcnt[w] = __popcll(mk);
+        __syncthreads();
+        int woff = 0, tot = 0;
+        for (int i = 0; i < RB_THREADS / 64; ++i) {
+            if (i < w) woff += wcnt[i];
+            tot += wcnt[i];
+        }
+        sink(q, base + woff + lanes_below(mk), valid, v);
+        base += tot;
+        __syncthreads();
+    }
+    return base;
+}
+
+// The bitonic sorting network over positions 0..P) (a power of two) by the whole block: cx(i, l, desc) compare-exchanges
+// positions i < l, ascending when desc == 0; ends with a barrier
+template <class CX>
+__device__ void block_bitonic(int P, CX cx) {
+    const int tid = threadIdx.x;
+    for (int kk = 2; kk <= P; kk <<= 1) {
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < P; i += RB_THREADS) {
+                const int l = i ^ j;
+                if (l > i) cx(i, l, i & kk);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// Bounds [first, past) of the run of `code` in K[0..n), ascending under proj, by two binary searches.  With a position
+// `at` of the run given the searches stay on its two sides; without, the second starts where the first ended.
+struct RunBounds { int first, past; };
+struct ProjSelf { template <class T> __device__ __forceinline__ T operator()(T v) const { return v; } };
+struct ProjAbove1 { __device__ __forceinline__ uint32_t operator()(uint32_t v) const { return v >> 1; } };
+template <class T, class C, class Proj>
+__device__ __forceinline__ RunBounds run_bounds(const T* K, int n, C code, Proj proj, int at = -1) {
+    int lo = 0, hi = at < 0 ? n : at;                   // first position with a code >= this one
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (proj(K[mid]) < code) lo = mid + 1; else hi = mid; }
+    const int first = lo;
+    if (at >= 0) lo = at + 1;
+    hi = n;                                             // first position with a larger code
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (proj(K[mid]) <= code) lo = mid + 1; else hi = mid; }
+    return {first, lo};
 }
 
 // Host: rows of one wave's chunk in the wave-per-row kernels -- as many (64 at most) as keeps every wave slot of the
@@ -225,5 +337,36 @@ inline int rows_per_chunk(int n_cu, int64_t n) {
     int ch = 64;
     while (ch > 1 && sd_ceil_div(n, ch) < 2 * slots) ch >>= 1;
     return ch;
+}
+
+// Host: workgroups of `waves` waves for a kernel whose waves walk chunks of ch rows, every wave slot of the chip filled
+// at most once (ranksum.hip's wave_blocks computes the same for its 4 waves); and of a kernel whose workgroups walk n
+// rows (or n blocks of rows), 8 a CU at most
+inline int64_t wave_launch_blocks(const sdice_ctx* ctx, int64_t n, int ch, int waves) {
+    return std::min(sd_ceil_div(sd_ceil_div(n, ch), waves), (int64_t)ctx->n_cu * 32 / waves);
+}
+inline int64_t row_launch_blocks(const sdice_ctx* ctx, int64_t n) { return std::min(n, (int64_t)ctx->n_cu * 8); }
+
+// Host: the power of two from `from` (one itself) up that is not below v
+inline int next_pow2(int v, int from) {
+    while (from < v) from <<= 1;
+    return from;
+}
+
+// Host: every one of the m entries of each list is a column of the table (0 .. s) and no column is listed twice, in one
+// list or two; `fn` is the entry point the error names, with the wording it has always had
+inline int check_columns(const char* fn, std::initializer_list<const int32_t*> lists, int m, int s, const char* range_msg,
+                         const char* once_msg) {
+    std::vector<char> seen((size_t)s, 0);
+    for (const int32_t* l : lists)
+        for (int q = 0; q < m; ++q) {
+            const char* msg = (l[q] < 0 || l[q] >= s) ? range_msg : (seen[l[q]] ? once_msg : nullptr);
+            if (msg) {
+                sdice_set_error("%s: %s", fn, msg);
+                return SDICE_ERR_ARG;
+            }
+            seen[l[q]] = 1;
+        }
+    return SDICE_OK;
 }
 }  // namespace

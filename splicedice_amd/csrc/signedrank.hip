@@ -36,12 +36,12 @@
 // (A wave-per-row kernel with several elements per lane for 65..1024 pairs was left out: the block kernel computes the
 // same thing and paired cohorts of that size are rare.)
 //
-// rowsum.h is used as it is (PsKey, ps_of_key, block_pairwise_sum, rows_per_chunk, SD_WAVE_SYNC); sr_ord / sr_unord
-// repeat kruskal.hip's kw_ord / kw_unord because moving those would change that file.
+// rowsum.h: PsKey, the order bits of a float, the lane groups with their sums, the block's compaction, pairwise sum,
+// bitonic network and run bounds, the launch sizes and the column check; dd.h: the double-double arithmetic.
 #include "common.h"
 #include <math.h>
-#include <vector>
 #include "rowsum.h"
+#include "dd.h"
 
 namespace {
 
@@ -61,14 +61,6 @@ struct SrOut {
     float* delta;
 };
 
-__device__ __forceinline__ uint32_t sr_ord(float v) {          // order-preserving bits of a non-NaN float (-0 == +0), below SR_PAD
-    const uint32_t b = __float_as_uint(v + 0.0f);
-    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float sr_unord(uint32_t o) {
-    return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
-}
-
 // sort key of a kept pair (see the file comment); SR_PAD for a zero difference
 __device__ __forceinline__ uint32_t sr_key(float x, float y, bool grid) {
     if (grid) {
@@ -86,31 +78,6 @@ __device__ __forceinline__ uint32_t sr_key(float x, float y, bool grid) {
 // (This function compiled for the host, against mpmath: 0 of 5048 random (n', W2, T) and break points differ from the correctly
 // rounded value.)
 constexpr double SR_DD_X2_MAX = 9.0;
-struct SrDD { double hi, lo; };
-__device__ __forceinline__ SrDD dd_fast2sum(double a, double b) {          // |a| >= |b|
-    const double s = a + b;
-    return {s, b - (s - a)};
-}
-__device__ __forceinline__ SrDD dd_2sum(double a, double b) {
-    const double s = a + b, bb = s - a;
-    return {s, (a - (s - bb)) + (b - bb)};
-}
-__device__ __forceinline__ SrDD dd_add(SrDD a, SrDD b) {
-    SrDD s = dd_2sum(a.hi, b.hi);
-    const SrDD t = dd_2sum(a.lo, b.lo);
-    s = dd_fast2sum(s.hi, s.lo + t.hi);
-    return dd_fast2sum(s.hi, s.lo + t.lo);
-}
-__device__ __forceinline__ SrDD dd_mul(SrDD a, SrDD b) {
-    const double p = a.hi * b.hi;
-    const double e = __builtin_fma(a.hi, b.hi, -p) + (a.hi * b.lo + a.lo * b.hi);
-    return dd_fast2sum(p, e);
-}
-__device__ __forceinline__ SrDD dd_div_d(SrDD a, double b) {
-    const double q1 = a.hi / b;
-    const double r = __builtin_fma(-q1, b, a.hi) + a.lo;
-    return dd_fast2sum(q1, r / b);
-}
 // coefficients (-1)^n / (n! (2n+1)) of the series as double-double constants; SR_ERF_TERMS[i] of them leave less than
 // 2^-112 behind for x^2 <= SR_ERF_BREAK[i]
 __device__ const double SR_ERF_C[70][2] = {
@@ -189,18 +156,19 @@ __device__ const double SR_ERF_BREAK[8] = {0.25, 0.5, 1, 2, 3, 4.5, 6, 9};
 __device__ const int SR_ERF_TERMS[8] = {21, 25, 30, 37, 43, 50, 57, 69};
 
 __device__ double sr_erfc_dd(double xn, double xd) {                       // 0 < xn / xd <= SR_DD_X2_MAX, both integers below 2^53
-    const SrDD x2 = dd_div_d({xn, 0.0}, xd);
+    const DD x2 = dd_div_d({xn, 0.0}, xd);
+    // (dd_sqrt written out: called, it swaps the operands of one v_add_f64 in the lane and group kernels)
     const double s = sqrt(x2.hi);
-    const SrDD x = dd_fast2sum(s, (__builtin_fma(-s, s, x2.hi) + x2.lo) / (2.0 * s));
+    const DD x = dd_fast2sum(s, (__builtin_fma(-s, s, x2.hi) + x2.lo) / (2.0 * s));
     int last = SR_ERF_TERMS[7];
 #pragma unroll
     for (int i = 6; i >= 0; --i)
         if (x2.hi <= SR_ERF_BREAK[i]) last = SR_ERF_TERMS[i];
-    SrDD sum = {SR_ERF_C[last][0], SR_ERF_C[last][1]};                     // Horner in x^2, no division
+    DD sum = {SR_ERF_C[last][0], SR_ERF_C[last][1]};                     // Horner in x^2, no division
     for (int n = last - 1; n >= 0; --n) sum = dd_add(dd_mul(sum, x2), {SR_ERF_C[n][0], SR_ERF_C[n][1]});
-    const SrDD two_over_sqrt_pi = {0x1.20dd750429b6dp+0, 0x1.1ae3a914fed80p-56};
-    const SrDD erf = dd_mul(dd_mul(two_over_sqrt_pi, x), sum);
-    const SrDD r = dd_add({1.0, 0.0}, {-erf.hi, -erf.lo});
+    const DD two_over_sqrt_pi = {0x1.20dd750429b6dp+0, 0x1.1ae3a914fed80p-56};
+    const DD erf = dd_mul(dd_mul(two_over_sqrt_pi, x), sum);
+    const DD r = dd_add({1.0, 0.0}, {-erf.hi, -erf.lo});
     return r.hi + r.lo;
 }
 
@@ -237,47 +205,19 @@ __device__ __forceinline__ uint32_t sr_group_sort(uint32_t v, int gl) {
     return v;
 }
 
-template <int P>
-__device__ __forceinline__ int sr_group_add(int v) {
-#pragma unroll
-    for (int ofs = 1; ofs < P; ofs <<= 1) v += __shfl_xor(v, ofs);
-    return v;
-}
-
 // np.median of the group's nv sorted order-preserving values (lane g0 + i holds the i-th smallest)
 __device__ __forceinline__ float sr_group_median(uint32_t sorted, int g0, int nv) {
     const int h = nv >> 1;
-    const float v1 = sr_unord(__shfl(sorted, g0 + h));
-    const float v0 = sr_unord(__shfl(sorted, g0 + (h > 0 ? h - 1 : 0)));
+    const float v1 = f32_unord(__shfl(sorted, g0 + h));
+    const float v0 = f32_unord(__shfl(sorted, g0 + (h > 0 ? h - 1 : 0)));
     return (nv & 1) ? v1 : (v0 + v1) / 2.0f;
-}
-
-// numpy pairwise_sum of A[0..nv), nv <= 64 (one leaf), by a group of P lanes, every lane of the group gets it: for
-// nv >= 8 lane j (mod 8) owns accumulator j, folded as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) by three xor exchanges as
-// in wave_pairwise_sum; then the tail (or, below 8 values, all of them) one after another.  (P >= 16: the
-// exchanges stay inside the group.)
-template <int P>
-__device__ __forceinline__ float sr_group_sum(const float* A, int nv, int gl) {
-    const int main_n = nv & ~7, j = gl & 7;
-    float r = 0.f;
-    if (nv >= 8) {
-        r = A[j];
-        for (int i = 8; i < main_n; i += 8) r += A[i + j];
-    }
-    r = r + __shfl_xor(r, 1);
-    r = r + __shfl_xor(r, 2);
-    r = r + __shfl_xor(r, 4);
-    if (nv < 8) r = 0.f;
-    for (int i = (nv >= 8 ? main_n : 0); i < nv; ++i) r += A[i];
-    return r;
 }
 
 template <int P>
 __global__ void __launch_bounds__(256) signedrank_group_kernel(const float* __restrict__ ps, int64_t n, int s,
                                                                const int32_t* __restrict__ a, const int32_t* __restrict__ b,
                                                                int m, int ch, SrOut o) {
-    constexpr int R = 64 / P;                            // rows side by side in a wave
-    constexpr unsigned long long GMASK = P == 64 ? ~0ull : ((1ull << (P & 63)) - 1ull);
+    using G = LaneGroup<P>;                              // G::R rows side by side in a wave
     __shared__ float cx[4][64], cy[4][64];               // the kept values of the wave's rows, compacted, in pair order
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
     const int g = lane / P, gl = lane % P, g0 = g * P;
@@ -291,7 +231,7 @@ __global__ void __launch_bounds__(256) signedrank_group_kernel(const float* __re
       // lane i keeps the chunk's i-th row
       int s_pack = 0, s_tie = 0;                         // tested << 31 | W2 << 8 | n'  (W2 <= 64 * 65, n' <= 64); T <= 64^3
       float s_med1 = 0.f, s_med2 = 0.f, s_mean1 = 0.f, s_mean2 = 0.f;
-      for (int r0 = 0; r0 < rows_here; r0 += R) {        // wave-uniform
+      for (int r0 = 0; r0 < rows_here; r0 += G::R) {        // wave-uniform
         const int ri = r0 + g;
         float x = __builtin_nanf(""), y = x;
         if (ri < rows_here && gl < m) {
@@ -300,10 +240,10 @@ __global__ void __launch_bounds__(256) signedrank_group_kernel(const float* __re
             y = __builtin_nontemporal_load(prow + cb);
         }
         const bool kept = x == x && y == y;
-        const unsigned long long km = (__ballot(kept) >> g0) & GMASK;
+        const unsigned long long km = (__ballot(kept) >> g0) & G::MASK;
         const int nv = __popcll(km);
         const bool offgrid = kept && !(key_of_ps(x).exact() && key_of_ps(y).exact());
-        const bool grid = ((__ballot(offgrid) >> g0) & GMASK) == 0ull;
+        const bool grid = ((__ballot(offgrid) >> g0) & G::MASK) == 0ull;
         // ---- the numpy-order sums over the compacted values
         SD_WAVE_SYNC();          // the previous pass's readers are done with the wave's LDS
         if (kept) {
@@ -312,19 +252,19 @@ __global__ void __launch_bounds__(256) signedrank_group_kernel(const float* __re
             Y[pos] = y;
         }
         SD_WAVE_SYNC();
-        const float sum1 = 0.0f + sr_group_sum<P>(X, nv, gl);      // np.sum starts from the identity 0: -0.0 values sum to +0.0
-        const float sum2 = 0.0f + sr_group_sum<P>(Y, nv, gl);
+        const float sum1 = 0.0f + group_sum(X, nv, gl);      // np.sum starts from the identity 0: -0.0 values sum to +0.0
+        const float sum2 = 0.0f + group_sum(Y, nv, gl);
         // ---- the medians
-        const uint32_t ox = sr_group_sort<P>(kept ? sr_ord(x) : SR_PAD, gl);
-        const uint32_t oy = sr_group_sort<P>(kept ? sr_ord(y) : SR_PAD, gl);
+        const uint32_t ox = sr_group_sort<P>(kept ? f32_ord(x) : SR_PAD, gl);
+        const uint32_t oy = sr_group_sort<P>(kept ? f32_ord(y) : SR_PAD, gl);
         const float med1 = sr_group_median(ox, g0, nv), med2 = sr_group_median(oy, g0, nv);
         // ---- the ranks of |d|
         const uint32_t key = sr_group_sort<P>(kept ? sr_key(x, y, grid) : SR_PAD, gl);
         const bool valid = key != SR_PAD;
-        const int np = __popcll((__ballot(valid) >> g0) & GMASK);
+        const int np = __popcll((__ballot(valid) >> g0) & G::MASK);
         const uint32_t prev = __shfl_up(key, 1);
         const bool start = valid && (gl == 0 || (prev >> 1) != (key >> 1));
-        const unsigned long long sm = (__ballot(start) >> g0) & GMASK;       // bit i: a tie run starts at position i
+        const unsigned long long sm = (__ballot(start) >> g0) & G::MASK;       // bit i: a tie run starts at position i
         const unsigned long long upto = (2ull << gl) - 1ull;                 // positions 0..gl
         int w2 = 0, tie = 0;
         if (valid) {
@@ -335,11 +275,11 @@ __global__ void __launch_bounds__(256) signedrank_group_kernel(const float* __re
             const int t = last - first + 1;
             if (start) tie = t * t * t - t;
         }
-        w2 = sr_group_add<P>(w2);
-        tie = sr_group_add<P>(tie);
+        w2 = group_add<P>(w2);
+        tie = group_add<P>(tie);
         // ---- to the lanes that keep the rows of this pass: lane r0 + q takes group q's
-        const int src = ((lane - r0) * P) & 63;
-        const bool mine = lane >= r0 && lane < r0 + R;
+        const int src = G::src(lane, r0);
+        const bool mine = G::mine(lane, r0);
         const int pack = nv >= 3 ? (int)(0x80000000u | ((unsigned)w2 << 8) | (unsigned)np) : 0;
         const int t_pack = __shfl(pack, src), t_tie = __shfl(tie, src);
         const float t_med1 = __shfl(med1, src), t_med2 = __shfl(med2, src);
@@ -397,8 +337,8 @@ __device__ __forceinline__ uint32_t sr_pick(const uint32_t (&v)[P], int idx) {
 template <int P>
 __device__ __forceinline__ float sr_regs_median(const uint32_t (&sorted)[P], int nv) {
     const int h = nv >> 1;
-    const float v1 = sr_unord(sr_pick<P>(sorted, h));
-    const float v0 = sr_unord(sr_pick<P>(sorted, h > 0 ? h - 1 : 0));
+    const float v1 = f32_unord(sr_pick<P>(sorted, h));
+    const float v0 = f32_unord(sr_pick<P>(sorted, h > 0 ? h - 1 : 0));
     return (nv & 1) ? v1 : (v0 + v1) / 2.0f;
 }
 
@@ -446,8 +386,8 @@ __global__ void __launch_bounds__(256) signedrank_lane_kernel(const float* __res
 #pragma unroll
         for (int q = 0; q < P; ++q) {
             const bool kept = x[q] == x[q];
-            ux[q] = kept ? sr_ord(x[q]) : SR_PAD;
-            uy[q] = kept ? sr_ord(y[q]) : SR_PAD;
+            ux[q] = kept ? f32_ord(x[q]) : SR_PAD;
+            uy[q] = kept ? f32_ord(y[q]) : SR_PAD;
             kd[q] = kept ? sr_key(x[q], y[q], grid) : SR_PAD;
         }
         sr_sort_regs<P>(ux);
@@ -489,58 +429,6 @@ __global__ void __launch_bounds__(256) signedrank_lane_kernel(const float* __res
 }
 
 // ------------------------------------------------------------------ general path: one workgroup per row
-// ordered compaction of the pairs of ps[row, (a[q], b[q])] without a NaN into fx / fy; returns the count
-__device__ int sr_block_compact(const float* __restrict__ prow, const int32_t* __restrict__ a, const int32_t* __restrict__ b,
-                                int m, float* fx, float* fy, int* wcnt /* [RB_THREADS/64] shared */) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    int base = 0;
-    for (int c0 = 0; c0 < m; c0 += RB_THREADS) {
-        const int q = c0 + tid;
-        float x = __builtin_nanf(""), y = x;
-        if (q < m) { x = prow[a[q]]; y = prow[b[q]]; }
-        const bool valid = x == x && y == y;
-        const unsigned long long mk = __ballot(valid);
-        if (lane == 0) wcnt[w] = __popcll(mk);
-        __syncthreads();
-        int woff = 0, tot = 0;
-        for (int i = 0; i < RB_THREADS / 64; ++i) {
-            if (i < w) woff += wcnt[i];
-            tot += wcnt[i];
-        }
-        if (valid) {
-            const int pos = base + woff + lanes_below(mk);
-            fx[pos] = x;
-            fy[pos] = y;
-        }
-        base += tot;
-        __syncthreads();
-    }
-    return base;
-}
-
-// ascending bitonic sort of A[0..P), B[0..P) and C[0..P), each on its own, by the whole block through the same barriers
-// (P a power of two); ends with a barrier
-__device__ void sr_block_sort3(uint32_t* A, uint32_t* B, uint32_t* C, int P) {
-    const int tid = threadIdx.x;
-    for (int kk = 2; kk <= P; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < P; i += RB_THREADS) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const bool asc = (i & kk) == 0;
-                    uint32_t* const arr[3] = {A, B, C};
-#pragma unroll
-                    for (int q = 0; q < 3; ++q) {
-                        const uint32_t x = arr[q][i], y = arr[q][l];
-                        if ((x > y) == asc) { arr[q][i] = y; arr[q][l] = x; }
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
 __global__ void __launch_bounds__(RB_THREADS) signedrank_block_kernel(const float* __restrict__ ps, int64_t n, int s,
                                                                       const int32_t* __restrict__ a,
                                                                       const int32_t* __restrict__ b, int m, int P, SrOut o) {
@@ -558,14 +446,24 @@ __global__ void __launch_bounds__(RB_THREADS) signedrank_block_kernel(const floa
     const int tid = threadIdx.x, lane = tid & 63;
     for (int64_t row = blockIdx.x; row < n; row += gridDim.x) {
         const float* prow = ps + row * s;
-        const int nv = sr_block_compact(prow, a, b, m, FX, FY, wcnt);
+        // ordered compaction of the pairs of ps[row, (a[q], b[q])] without a NaN
+        const int nv = block_compact_by(
+            m, wcnt,
+            [=](int q) {
+                float2 v = {__builtin_nanf(""), __builtin_nanf("")};
+                if (q < m) { v.x = prow[a[q]]; v.y = prow[b[q]]; }
+                return v;
+            },
+            [=](int, int pos, bool valid, float2 v) {
+                if (valid) { FX[pos] = v.x; FY[pos] = v.y; }
+            });
         if (nv < 3) {                                           // block-uniform
             if (tid == 0) {
                 o.tested[row] = 0; o.p[row] = 0.0;
                 if (o.z) o.z[row] = 0.0;
                 o.med1[row] = 0.f; o.med2[row] = 0.f; o.mean1[row] = 0.f; o.mean2[row] = 0.f; o.delta[row] = 0.f;
             }
-            continue;                                           // (sr_block_compact ended with a barrier)
+            continue;                                           // (the compaction ended with a barrier)
         }
         // np.sum: the identity 0 plus the pairwise tree
         const float sum1 = 0.0f + block_pairwise_sum<PW_DEPTH>(FX, nv, leaf_off, leaf_sum, scratch8, SR_LEAF_MAX);
@@ -578,13 +476,21 @@ __global__ void __launch_bounds__(RB_THREADS) signedrank_block_kernel(const floa
             uint32_t kx = SR_PAD, ky = SR_PAD, kd = SR_PAD;
             if (i < nv) {
                 const float x = FX[i], y = FY[i];
-                kx = sr_ord(x); ky = sr_ord(y); kd = sr_key(x, y, grid);
+                kx = f32_ord(x); ky = f32_ord(y); kd = sr_key(x, y, grid);
             }
             KX[i] = kx; KY[i] = ky; KD[i] = kd;
         }
         if (tid < 2) accS[tid] = 0ull;
         __syncthreads();
-        sr_block_sort3(KX, KY, KD, P);
+        block_bitonic(P, [=](int i, int l, int desc) {           // the three arrays, each on its own, through the same barriers
+            const bool asc = desc == 0;
+            uint32_t* const arr[3] = {KX, KY, KD};
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const uint32_t x = arr[q][i], y = arr[q][l];
+                if ((x > y) == asc) { arr[q][i] = y; arr[q][l] = x; }
+            }
+        });
         int np = 0;                                             // first padding key: the number of non-zero differences
         {
             int hi = nv;
@@ -594,14 +500,10 @@ __global__ void __launch_bounds__(RB_THREADS) signedrank_block_kernel(const floa
         long long w2 = 0, tie = 0;
         for (int q = tid; q < np; q += RB_THREADS) {
             const uint32_t key = KD[q], code = key >> 1;
-            int lo = 0, hi = np;                                // first position with code >= this one's
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if ((KD[mid] >> 1) < code) lo = mid + 1; else hi = mid; }
-            const int first = lo;
-            hi = np;                                            // first position with a larger code
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if ((KD[mid] >> 1) <= code) lo = mid + 1; else hi = mid; }
-            if (key & 1u) w2 += first + lo + 1;
-            if (q == first) {
-                const long long t = lo - first;
+            const RunBounds run = run_bounds(KD, np, code, ProjAbove1{});
+            if (key & 1u) w2 += run.first + run.past + 1;
+            if (q == run.first) {
+                const long long t = run.past - run.first;
                 tie += t * t * t - t;
             }
         }
@@ -616,10 +518,7 @@ __global__ void __launch_bounds__(RB_THREADS) signedrank_block_kernel(const floa
         }
         __syncthreads();
         if (tid == 0) {
-            const int h = nv >> 1;
-            const float a1 = sr_unord(KX[h]), b1 = sr_unord(KY[h]);
-            const float med1 = (nv & 1) ? a1 : (sr_unord(KX[h - 1]) + a1) / 2.0f;      // np.median on float32
-            const float med2 = (nv & 1) ? b1 : (sr_unord(KY[h - 1]) + b1) / 2.0f;
+            const float med1 = median_of_ord(KX, nv), med2 = median_of_ord(KY, nv);    // np.median on float32
             double z, p;
             sr_finish(np, (long long)accS[0], (long long)accS[1], z, p);
             o.tested[row] = 1; o.p[row] = p;
@@ -636,9 +535,7 @@ template <int P>
 int sr_launch_group(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* d_a, const int32_t* d_b, int m, SrOut o) {
     const int waves = 4;
     const int ch = rows_per_chunk(ctx->n_cu, n);
-    int64_t blocks = sd_ceil_div(sd_ceil_div(n, ch), waves);
-    const int64_t cap = (int64_t)ctx->n_cu * 32 / waves;
-    if (blocks > cap) blocks = cap;
+    const int64_t blocks = wave_launch_blocks(ctx, n, ch, waves);
     SD_LAUNCH(ctx, "signedrank_group_kernel", (signedrank_group_kernel<P>), dim3((unsigned)blocks), dim3(waves * 64), 0, d_ps,
               n, s, d_a, d_b, m, ch, o);
     return SDICE_OK;
@@ -646,9 +543,7 @@ int sr_launch_group(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const i
 
 template <int P>
 int sr_launch_lane(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* d_a, const int32_t* d_b, int m, SrOut o) {
-    int64_t blocks = sd_ceil_div(n, 256);
-    const int64_t cap = (int64_t)ctx->n_cu * 8;
-    if (blocks > cap) blocks = cap;
+    const int64_t blocks = row_launch_blocks(ctx, sd_ceil_div(n, 256));
     SD_LAUNCH(ctx, "signedrank_lane_kernel", (signedrank_lane_kernel<P>), dim3((unsigned)blocks), dim3(256), 0, d_ps, n, s,
               d_a, d_b, m, o);
     return SDICE_OK;
@@ -694,12 +589,9 @@ extern "C" int sdice_signedrank_dev(sdice_ctx* ctx, int64_t n, int32_t s, const 
         if (m <= 32) return sr_launch_group<32>(ctx, d_ps, n, s, d_a, d_b, m, o);
         return sr_launch_group<64>(ctx, d_ps, n, s, d_a, d_b, m, o);
     }
-    int P = 128;
-    while (P < m) P <<= 1;
+    const int P = next_pow2(m, 128);
     const size_t lds = (size_t)P * 3 * 4;
-    int64_t blocks = n;
-    const int64_t cap = (int64_t)ctx->n_cu * 8;
-    if (blocks > cap) blocks = cap;
+    const int64_t blocks = row_launch_blocks(ctx, n);
     SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(signedrank_block_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     SD_LAUNCH(ctx, "signedrank_block_kernel", signedrank_block_kernel, dim3((unsigned)blocks), dim3(RB_THREADS), lds, d_ps, n,
@@ -714,16 +606,7 @@ extern "C" int sdice_signedrank(sdice_ctx* ctx, int64_t n, int32_t s, const floa
     SD_ARG(n >= 0 && s >= 0, "negative size");
     SD_TRY(sr_check_m(m));
     SD_ARG(a && b, "pair index list is NULL");
-    {
-        std::vector<char> seen((size_t)s, 0);
-        const int32_t* lists[2] = {a, b};
-        for (const int32_t* l : lists)
-            for (int q = 0; q < m; ++q) {
-                SD_ARG(l[q] >= 0 && l[q] < s, "column index out of range");
-                SD_ARG(!seen[l[q]], "a column may appear once over both pair lists");
-                seen[l[q]] = 1;
-            }
-    }
+    SD_TRY(check_columns(__func__, {a, b}, m, s, "column index out of range", "a column may appear once over both pair lists"));
     if (n == 0) return SDICE_OK;
     SD_ARG(tested && p && med1 && med2 && mean1 && mean2 && delta, "NULL output");
     SD_ARG(ps, "ps is NULL");

@@ -41,12 +41,12 @@
 // (Left out: a wave-per-row tier for 257..1024 columns -- counting is quadratic in m and stops paying there -- and the
 // 1001-bin count for rows of 3-decimal values; the block kernel computes the same thing.)
 //
-// rowsum.h: block_pairwise_sum, wave_pairwise_sum, lanes_below, rows_per_chunk, SD_WAVE_SYNC as they are; f32_ord /
-// f32_unord were added there for this file.
+// rowsum.h: the order bits of a float, the lane groups with their sums, wave_pairwise_sum, the block's compaction, pairwise
+// sum, bitonic network and run bounds, the launch sizes and the column check; dd.h: the double-double arithmetic.
 #include "common.h"
 #include <math.h>
-#include <vector>
 #include "rowsum.h"
+#include "dd.h"
 
 namespace {
 
@@ -112,82 +112,33 @@ __host__ __device__ inline double sp_beta_half(double a, double x, double y) {
     return r < 0.0 ? 0.0 : (r > 1.0 ? 1.0 : r);
 }
 
-// ---- double-double arithmetic: rho everywhere, and p of the rows with at most SP_DD_MAX_KEPT kept samples, where the
-// float64 that comes out is the correctly rounded one (the continued fraction is a few 1e-15 off, which shows in the
-// last printed digit of the table)
+// ---- in double-double arithmetic (dd.h): rho everywhere, and p of the rows with at most SP_DD_MAX_KEPT kept samples,
+// where the float64 that comes out is the correctly rounded one (the continued fraction is a few 1e-15 off, which shows
+// in the last printed digit of the table)
 constexpr int SP_DD_MAX_KEPT = 64;
-struct SpDD { double hi, lo; };
-__host__ __device__ inline SpDD sp_fast2sum(double a, double b) {          // |a| >= |b|
-    const double s = a + b;
-    return {s, b - (s - a)};
-}
-__host__ __device__ inline SpDD sp_2sum(double a, double b) {
-    const double s = a + b, bb = s - a;
-    return {s, (a - (s - bb)) + (b - bb)};
-}
-__host__ __device__ inline SpDD sp_add(SpDD a, SpDD b) {
-    SpDD s = sp_2sum(a.hi, b.hi);
-    const SpDD t = sp_2sum(a.lo, b.lo);
-    s = sp_fast2sum(s.hi, s.lo + t.hi);
-    return sp_fast2sum(s.hi, s.lo + t.lo);
-}
-__host__ __device__ inline SpDD sp_mul(SpDD a, SpDD b) {
-    const double p = a.hi * b.hi;
-    const double e = __builtin_fma(a.hi, b.hi, -p) + (a.hi * b.lo + a.lo * b.hi);
-    return sp_fast2sum(p, e);
-}
-__host__ __device__ inline SpDD sp_mul_d(SpDD a, double b) {
-    const double p = a.hi * b;
-    const double e = __builtin_fma(a.hi, b, -p) + a.lo * b;
-    return sp_fast2sum(p, e);
-}
-__host__ __device__ inline SpDD sp_div_d(SpDD a, double b) {               // one division: the residual step absorbs q1's error
-    const double inv = 1.0 / b, q1 = a.hi * inv;
-    const double r = __builtin_fma(-q1, b, a.hi) + a.lo;
-    return sp_fast2sum(q1, r * inv);
-}
-__host__ __device__ inline SpDD sp_div(SpDD a, SpDD b) {
-    const double q1 = a.hi / b.hi;
-    SpDD r = sp_add(a, sp_mul_d(b, -q1));
-    const double q2 = r.hi / b.hi;
-    r = sp_add(r, sp_mul_d(b, -q2));
-    const double q3 = r.hi / b.hi;
-    const SpDD q = sp_fast2sum(q1, q2);
-    return sp_fast2sum(q.hi, q.lo + q3);
-}
-__host__ __device__ inline SpDD sp_sqrt(SpDD a) {                         // a > 0
-    const double s = sqrt(a.hi);
-    return sp_fast2sum(s, (__builtin_fma(-s, s, a.hi) + a.lo) / (2.0 * s));
-}
-__host__ __device__ inline SpDD sp_u128_dd(unsigned __int128 v) {          // exact below 2^106
-    const uint64_t lo = (uint64_t)v;
-    const SpDD top = sp_2sum((double)(uint64_t)(v >> 64) * 18446744073709551616.0, (double)(lo >> 32) * 4294967296.0);
-    return sp_add(top, {(double)(lo & 0xffffffffull), 0.0});
-}
-
 // I_x(a, 1/2), a = nu / 2 <= 31, from x = 1 - rho^2, y = rho^2 and r = |rho|: with front = r x^a / B(a, 1/2),
 //   x <= 1/2:  front / a * sum_k (a + 1/2)_k / (a + 1)_k x^k            (every term positive: exact down any tail)
 //   else:      1 - 2 front * sum_k (a + 1/2)_k / (3/2)_k y^k            (y < 1/2, p > 1e-10: at most 34 of the 106 bits cancel)
 // B by B(a + 1, 1/2) = B(a, 1/2) a / (a + 1/2) from B(1/2, 1/2) = pi or B(1, 1/2) = 2
-__host__ __device__ inline double sp_beta_half_dd(int nu, SpDD x, SpDD y, SpDD r) {
-    const SpDD pi = {0x1.921fb54442d18p+1, 0x1.1a62633145c07p-53};
+__host__ __device__ inline double sp_beta_half_dd(int nu, DD x, DD y, DD r) {
+    const DD pi = {0x1.921fb54442d18p+1, 0x1.1a62633145c07p-53};
     double a0 = (nu & 1) ? 0.5 : 1.0;
-    SpDD front = (nu & 1) ? sp_div(sp_sqrt(x), pi) : sp_mul_d(x, 0.5);     // x^a0 / B(a0, 1/2)
+    DD front = (nu & 1) ? dd_div(dd_sqrt(x), pi) : dd_mul_d(x, 0.5);     // x^a0 / B(a0, 1/2)
     const double a = 0.5 * (double)nu;
-    for (; a0 < a; a0 += 1.0) front = sp_div_d(sp_mul_d(sp_mul(front, x), a0 + 0.5), a0);
-    front = sp_mul(front, r);
+    for (; a0 < a; a0 += 1.0) front = dd_div_d_recip(dd_mul_d(dd_mul(front, x), a0 + 0.5), a0);
+    front = dd_mul(front, r);
     const bool direct = x.hi <= 0.5;
-    const SpDD z = direct ? x : y;
+    const DD z = direct ? x : y;
     const double den0 = direct ? a + 1.0 : 1.5;
-    SpDD term = {1.0, 0.0}, sum = {1.0, 0.0};
+    DD term = {1.0, 0.0}, sum = {1.0, 0.0};
     for (int k = 0; k < 4000; ++k) {
-        term = sp_div_d(sp_mul_d(sp_mul(term, z), a + 0.5 + (double)k), den0 + (double)k);
-        sum = sp_add(sum, term);
+        term = dd_div_d_recip(dd_mul_d(dd_mul(term, z), a + 0.5 + (double)k), den0 + (double)k);
+        sum = dd_add(sum, term);
         if (term.hi < sum.hi * 0x1p-112 && z.hi * (a + 1.5 + (double)k) < den0 + 1.0 + (double)k) break;   // past the peak
     }
-    SpDD p = sp_mul(front, sum);
-    if (direct) p = sp_div_d(p, a);
-    else p = sp_add({1.0, 0.0}, {-2.0 * p.hi, -2.0 * p.lo});
+    DD p = dd_mul(front, sum);
+    if (direct) p = dd_div_d_recip(p, a);
+    else p = dd_add({1.0, 0.0}, {-2.0 * p.hi, -2.0 * p.lo});
     return p.hi + p.lo;
 }
 
@@ -199,16 +150,16 @@ __host__ __device__ inline void sp_finish(int nv, long long sab, long long saa, 
     p = 1.0;
     if (Dx == 0 || Dy == 0 || N == 0) return;            // a constant side; no monotone trend
     const unsigned long long an = (unsigned long long)(N < 0 ? -N : N);
-    const unsigned __int128 DD = (unsigned __int128)(unsigned long long)Dx * (unsigned long long)Dy;
+    const unsigned __int128 DXY = (unsigned __int128)(unsigned long long)Dx * (unsigned long long)Dy;
     const unsigned __int128 NN = (unsigned __int128)an * an;
-    if (NN >= DD) {                                       // (Cauchy-Schwarz: never above)
+    if (NN >= DXY) {                                       // (Cauchy-Schwarz: never above)
         rho = N > 0 ? 1.0 : -1.0;
         p = 0.0;
         return;
     }
-    const SpDD dd = sp_u128_dd(DD);
-    const SpDD x = sp_div(sp_u128_dd(DD - NN), dd), y = sp_div(sp_u128_dd(NN), dd);      // 1 - rho^2, rho^2
-    const SpDD r = sp_sqrt(y);
+    const DD dd = dd_u128(DXY);
+    const DD x = dd_div(dd_u128(DXY - NN), dd), y = dd_div(dd_u128(NN), dd);      // 1 - rho^2, rho^2
+    const DD r = dd_sqrt(y);
     rho = N > 0 ? r.hi + r.lo : -(r.hi + r.lo);
     if (nv <= SP_DD_MAX_KEPT) p = sp_beta_half_dd(nv - 2, x, y, r);
     else p = sp_beta_half(0.5 * (double)(nv - 2), x.hi, y.hi);
@@ -216,36 +167,10 @@ __host__ __device__ inline void sp_finish(int nv, long long sab, long long saa, 
 
 // ------------------------------------------------------------------ lane-group path: P lanes per row
 template <int P>
-__device__ __forceinline__ int sp_group_add(int v) {
-#pragma unroll
-    for (int ofs = 1; ofs < P; ofs <<= 1) v += __shfl_xor(v, ofs);
-    return v;
-}
-
-// numpy pairwise_sum of A[0..nv), nv <= 64 (one leaf), by a group of P >= 8 lanes, every lane of the group gets it: for
-// nv >= 8 lane j (mod 8) owns accumulator j, folded as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) by three xor exchanges as
-// in wave_pairwise_sum; then the tail (or, below 8 values, all of them) one after another
-__device__ __forceinline__ float sp_group_sum(const float* A, int nv, int gl) {
-    const int main_n = nv & ~7, j = gl & 7;
-    float r = 0.f;
-    if (nv >= 8) {
-        r = A[j];
-        for (int i = 8; i < main_n; i += 8) r += A[i + j];
-    }
-    r = r + __shfl_xor(r, 1);
-    r = r + __shfl_xor(r, 2);
-    r = r + __shfl_xor(r, 4);
-    if (nv < 8) r = 0.f;
-    for (int i = (nv >= 8 ? main_n : 0); i < nv; ++i) r += A[i];
-    return r;
-}
-
-template <int P>
 __global__ void __launch_bounds__(256) spearman_group_kernel(const float* __restrict__ ps, int64_t n, int s,
                                                              const int32_t* __restrict__ cols, const int32_t* __restrict__ xg,
                                                              int m, int ch, SpOut o) {
-    constexpr int R = 64 / P;                            // rows side by side in a wave
-    constexpr unsigned long long GMASK = P == 64 ? ~0ull : ((1ull << (P & 63)) - 1ull);
+    using G = LaneGroup<P>;                              // G::R rows side by side in a wave
     __shared__ float cx[4][64];                          // the kept values of the wave's rows, compacted, in list order
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
     const int g = lane / P, gl = lane % P, g0 = g * P;
@@ -257,7 +182,7 @@ __global__ void __launch_bounds__(256) spearman_group_kernel(const float* __rest
     {
         const int mine = gl < m ? xg[gl] : -1 - gl;
         const int prev = __shfl_up(mine, 1);
-        const unsigned long long sm = (__ballot(gl == 0 || prev != mine) >> g0) & GMASK;      // bit i: a group starts at i
+        const unsigned long long sm = (__ballot(gl == 0 || prev != mine) >> g0) & G::MASK;      // bit i: a group starts at i
         const unsigned long long upto = (2ull << gl) - 1ull;                                   // positions 0..gl
         const int glo = 63 - __clzll((long long)(sm & upto));
         const unsigned long long above = sm & ~upto;
@@ -272,18 +197,18 @@ __global__ void __launch_bounds__(256) spearman_group_kernel(const float* __rest
       // lane i keeps the chunk's i-th row
       int s_nv = 0, s_ab = 0, s_aa = 0, s_bb = 0;        // sums of products of doubled ranks <= 64 * 129^2
       float s_med = 0.f, s_mean = 0.f;
-      for (int r0 = 0; r0 < rows_here; r0 += R) {        // wave-uniform
+      for (int r0 = 0; r0 < rows_here; r0 += G::R) {        // wave-uniform
         const int ri = r0 + g;
         float x = __builtin_nanf("");
         if (ri < rows_here && gl < m) x = __builtin_nontemporal_load(ps + (row0 + ri) * s + col);
         const bool kept = x == x;
-        const unsigned long long km = (__ballot(kept) >> g0) & GMASK;
+        const unsigned long long km = (__ballot(kept) >> g0) & G::MASK;
         const int nv = __popcll(km);
         // ---- the numpy-order sum over the compacted values
         SD_WAVE_SYNC();          // the previous pass's readers are done with the wave's LDS
         if (kept) X[__popcll(km & ((1ull << gl) - 1ull))] = x;
         SD_WAVE_SYNC();
-        const float sum = 0.0f + sp_group_sum(X, nv, gl);            // np.sum starts from the identity 0: -0.0 values sum to +0.0
+        const float sum = 0.0f + group_sum(X, nv, gl);            // np.sum starts from the identity 0: -0.0 values sum to +0.0
         // ---- PS ranks by counting
         const uint32_t xo = kept ? f32_ord(x) : SP_PAD;
         int less = 0, eq = 0;
@@ -295,20 +220,20 @@ __global__ void __launch_bounds__(256) spearman_group_kernel(const float* __rest
         }
         // ---- the median: the values whose rank intervals [less, less + eq) hold positions h and h - 1
         const int h = nv >> 1;
-        const unsigned long long mh = __ballot(kept && less <= h && h < less + eq) >> g0 & GMASK;
-        const unsigned long long ml = __ballot(kept && less <= h - 1 && h - 1 < less + eq) >> g0 & GMASK;
+        const unsigned long long mh = __ballot(kept && less <= h && h < less + eq) >> g0 & G::MASK;
+        const unsigned long long ml = __ballot(kept && less <= h - 1 && h - 1 < less + eq) >> g0 & G::MASK;
         const float v1 = f32_unord(__shfl(xo, g0 + (mh ? __ffsll((long long)mh) - 1 : 0)));
         const float v0 = f32_unord(__shfl(xo, g0 + (ml ? __ffsll((long long)ml) - 1 : 0)));
         const float med = (nv & 1) ? v1 : (v0 + v1) / 2.0f;
         // ---- the sums of the doubled ranks' products
         const int a2 = __popcll(km & below_lo) + __popcll(km & below_hi) + 1;
         const int b2 = 2 * less + eq + 1;
-        const int ab = sp_group_add<P>(kept ? a2 * b2 : 0);
-        const int aa = sp_group_add<P>(kept ? a2 * a2 : 0);
-        const int bb = sp_group_add<P>(kept ? b2 * b2 : 0);
+        const int ab = group_add<P>(kept ? a2 * b2 : 0);
+        const int aa = group_add<P>(kept ? a2 * a2 : 0);
+        const int bb = group_add<P>(kept ? b2 * b2 : 0);
         // ---- to the lanes that keep the rows of this pass: lane r0 + q takes group q's
-        const int src = ((lane - r0) * P) & 63;
-        const bool mine = lane >= r0 && lane < r0 + R;
+        const int src = G::src(lane, r0);
+        const bool mine = G::mine(lane, r0);
         const int t_nv = __shfl(nv, src), t_ab = __shfl(ab, src), t_aa = __shfl(aa, src), t_bb = __shfl(bb, src);
         const float t_med = __shfl(med, src), t_mean = __shfl(sum / (float)nv, src);
         if (mine) { s_nv = t_nv; s_ab = t_ab; s_aa = t_aa; s_bb = t_bb; s_med = t_med; s_mean = t_mean; }
@@ -349,6 +274,8 @@ __global__ void __launch_bounds__(256) spearman_wave_kernel(const float* __restr
         col[e] = 0; glo[e] = 0; ghi[e] = 0;
         if (q < m) {
             col[e] = cols[q];
+            // (written out: through run_bounds of rowsum.h both instantiations change, and no timing tool lists the
+            // 129..256 columns that reach E = 4)
             const int mine = xg[q];
             int lo = 0, hi = q;
             while (lo < hi) { const int mid = (lo + hi) >> 1; if (xg[mid] < mine) lo = mid + 1; else hi = mid; }
@@ -436,9 +363,9 @@ __global__ void __launch_bounds__(256) spearman_wave_kernel(const float* __restr
                 bb += b2 * b2;
             }
         }
-        ab = sp_group_add<64>(ab);
-        aa = sp_group_add<64>(aa);
-        bb = sp_group_add<64>(bb);
+        ab = group_add<64>(ab);
+        aa = group_add<64>(aa);
+        bb = group_add<64>(bb);
         if (lane == r) { s_nv = nv; s_ab = ab; s_aa = aa; s_bb = bb; s_med = med; s_mean = sum / (float)nv; }
       }
       if (lane < rows_here) {
@@ -457,28 +384,6 @@ __global__ void __launch_bounds__(256) spearman_wave_kernel(const float* __restr
 }
 
 // ------------------------------------------------------------------ general path: one workgroup per row
-// ascending bitonic sort of K[0..P) by the whole block, A[0..P) carried along (P a power of two); ends with a barrier
-__device__ void sp_block_sort(uint32_t* K, unsigned short* A, int P) {
-    const int tid = threadIdx.x;
-    for (int kk = 2; kk <= P; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < P; i += RB_THREADS) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const bool asc = (i & kk) == 0;
-                    const uint32_t x = K[i], y = K[l];
-                    if ((x > y) == asc && x != y) {
-                        K[i] = y; K[l] = x;
-                        const unsigned short t = A[i];
-                        A[i] = A[l]; A[l] = t;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
 __global__ void __launch_bounds__(RB_THREADS) spearman_block_kernel(const float* __restrict__ ps, int64_t n, int s,
                                                                     const int32_t* __restrict__ cols,
                                                                     const int32_t* __restrict__ xg, int m, int P, SpOut o) {
@@ -493,44 +398,26 @@ __global__ void __launch_bounds__(RB_THREADS) spearman_block_kernel(const float*
     __shared__ int leaf_off[SP_LEAF_MAX + 1];
     __shared__ int wcnt[RB_THREADS / 64];
     __shared__ unsigned long long accS[3];                      // sum a2 b2, sum a2^2, sum b2^2
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     // the tie-group bounds of every list position, once: xg never decreases
     for (int q = tid; q < m; q += RB_THREADS) {
-        const int mine = xg[q];
-        int lo = 0, hi = q;                                     // first position of the group
-        while (lo < hi) { const int mid = (lo + hi) >> 1; if (xg[mid] < mine) lo = mid + 1; else hi = mid; }
-        const int glo = lo;
-        lo = q + 1; hi = m;                                     // first position past it
-        while (lo < hi) { const int mid = (lo + hi) >> 1; if (xg[mid] <= mine) lo = mid + 1; else hi = mid; }
-        GB[q] = ((uint32_t)lo << 16) | (uint32_t)glo;
+        const RunBounds grp = run_bounds(xg, m, xg[q], ProjSelf{}, q);
+        GB[q] = ((uint32_t)grp.past << 16) | (uint32_t)grp.first;
     }
     __syncthreads();
     for (int64_t row = blockIdx.x; row < n; row += gridDim.x) {
         const float* prow = ps + row * s;
         // ---- ordered compaction of the non-NaN values, with the list position of each and the prefix of every position
-        int nv = 0;
-        for (int c0 = 0; c0 < m; c0 += RB_THREADS) {
-            const int q = c0 + tid;
-            float x = __builtin_nanf("");
-            if (q < m) x = prow[cols[q]];
-            const bool valid = x == x;
-            const unsigned long long mk = __ballot(valid);
-            if (lane == 0) wcnt[w] = __popcll(mk);
-            __syncthreads();
-            int woff = 0, tot = 0;
-            for (int i = 0; i < RB_THREADS / 64; ++i) {
-                if (i < w) woff += wcnt[i];
-                tot += wcnt[i];
-            }
-            const int pos = nv + woff + lanes_below(mk);
-            if (q < m) C[q] = (unsigned short)pos;
-            if (valid) {
-                F[pos] = x;
-                A[pos] = (unsigned short)q;
-            }
-            nv += tot;
-            __syncthreads();
-        }
+        const int nv = block_compact_by(
+            m, wcnt,
+            [=](int q) { return q < m ? prow[cols[q]] : __builtin_nanf(""); },
+            [=](int q, int pos, bool valid, float x) {
+                if (q < m) C[q] = (unsigned short)pos;
+                if (valid) {
+                    F[pos] = x;
+                    A[pos] = (unsigned short)q;
+                }
+            });
         if (nv < 3) {                                           // block-uniform
             if (tid == 0) {
                 o.tested[row] = 0; o.p[row] = 0.0;
@@ -556,17 +443,21 @@ __global__ void __launch_bounds__(RB_THREADS) spearman_block_kernel(const float*
             A[i] = a2;
         }
         __syncthreads();
-        sp_block_sort(K, A, P);
+        block_bitonic(P, [=](int i, int l, int desc) {           // a2 carried along as the payload; equal keys stay
+            const bool asc = desc == 0;
+            const uint32_t x = K[i], y = K[l];
+            if ((x > y) == asc && x != y) {
+                K[i] = y; K[l] = x;
+                const unsigned short t = A[i];
+                A[i] = A[l]; A[l] = t;
+            }
+        });
         // ---- PS ranks from the run bounds
         long long ab = 0, aa = 0, bb = 0;
         for (int q = tid; q < nv; q += RB_THREADS) {
             const uint32_t code = K[q];
-            int lo = 0, hi = q;                                 // first position with this code
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if (K[mid] < code) lo = mid + 1; else hi = mid; }
-            const int first = lo;
-            lo = q + 1; hi = nv;                                // first position with a larger code
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if (K[mid] <= code) lo = mid + 1; else hi = mid; }
-            const long long b2 = first + lo + 1, a2 = A[q];
+            const RunBounds run = run_bounds(K, nv, code, ProjSelf{}, q);
+            const long long b2 = run.first + run.past + 1, a2 = A[q];
             ab += a2 * b2;
             aa += a2 * a2;
             bb += b2 * b2;
@@ -584,9 +475,7 @@ __global__ void __launch_bounds__(RB_THREADS) spearman_block_kernel(const float*
         }
         __syncthreads();
         if (tid == 0) {
-            const int h = nv >> 1;
-            const float v1 = f32_unord(K[h]);
-            const float med = (nv & 1) ? v1 : (f32_unord(K[h - 1]) + v1) / 2.0f;        // np.median on float32
+            const float med = median_of_ord(K, nv);             // np.median on float32
             double rho, p;
             sp_finish(nv, (long long)accS[0], (long long)accS[1], (long long)accS[2], rho, p);
             o.tested[row] = 1; o.p[row] = p;
@@ -602,9 +491,7 @@ int sp_launch_group(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const i
                     SpOut o) {
     const int waves = 4;
     const int ch = rows_per_chunk(ctx->n_cu, n);
-    int64_t blocks = sd_ceil_div(sd_ceil_div(n, ch), waves);
-    const int64_t cap = (int64_t)ctx->n_cu * 32 / waves;
-    if (blocks > cap) blocks = cap;
+    const int64_t blocks = wave_launch_blocks(ctx, n, ch, waves);
     SD_LAUNCH(ctx, "spearman_group_kernel", (spearman_group_kernel<P>), dim3((unsigned)blocks), dim3(waves * 64), 0, d_ps, n,
               s, d_cols, d_xg, m, ch, o);
     return SDICE_OK;
@@ -615,9 +502,7 @@ int sp_launch_wave(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const in
                    SpOut o) {
     const int waves = 4;
     const int ch = rows_per_chunk(ctx->n_cu, n);
-    int64_t blocks = sd_ceil_div(sd_ceil_div(n, ch), waves);
-    const int64_t cap = (int64_t)ctx->n_cu * 32 / waves;
-    if (blocks > cap) blocks = cap;
+    const int64_t blocks = wave_launch_blocks(ctx, n, ch, waves);
     SD_LAUNCH(ctx, "spearman_wave_kernel", (spearman_wave_kernel<E>), dim3((unsigned)blocks), dim3(waves * 64), 0, d_ps, n,
               s, d_cols, d_xg, m, ch, o);
     return SDICE_OK;
@@ -654,12 +539,9 @@ extern "C" int sdice_spearman_dev(sdice_ctx* ctx, int64_t n, int32_t s, const fl
     }
     if (m <= SP_WAVE_MAX / 2) return sp_launch_wave<2>(ctx, d_ps, n, s, d_cols, d_xg, m, o);
     if (m <= SP_WAVE_MAX) return sp_launch_wave<4>(ctx, d_ps, n, s, d_cols, d_xg, m, o);
-    int P = 512;
-    while (P < m) P <<= 1;
+    const int P = next_pow2(m, 512);
     const size_t lds = (size_t)P * 12 + 8;                // K, GB: 4 bytes each; A, C: 2 bytes each, C two entries longer (49160 B at most)
-    int64_t blocks = n;
-    const int64_t cap = (int64_t)ctx->n_cu * 8;
-    if (blocks > cap) blocks = cap;
+    const int64_t blocks = row_launch_blocks(ctx, n);
     SD_LAUNCH(ctx, "spearman_block_kernel", spearman_block_kernel, dim3((unsigned)blocks), dim3(RB_THREADS), lds, d_ps, n,
               (int)s, d_cols, d_xg, (int)m, P, o);
     return SDICE_OK;
@@ -671,16 +553,9 @@ extern "C" int sdice_spearman(sdice_ctx* ctx, int64_t n, int32_t s, const float*
     SD_ARG(ctx, "ctx is NULL");
     SD_TRY(sp_check_scalars(n, s, m));
     SD_ARG(cols && xg, "column list or tie-group list is NULL");
-    {
-        std::vector<char> seen((size_t)s, 0);
-        for (int q = 0; q < m; ++q) {
-            SD_ARG(cols[q] >= 0 && cols[q] < s, "column index out of range");
-            SD_ARG(!seen[cols[q]], "a column may be listed once");
-            seen[cols[q]] = 1;
-        }
-        SD_ARG(xg[0] == 0, "xg must start at 0");
-        for (int q = 1; q < m; ++q) SD_ARG(xg[q] == xg[q - 1] || xg[q] == xg[q - 1] + 1, "xg must rise in steps of 0 or 1");
-    }
+    SD_TRY(check_columns(__func__, {cols}, m, s, "column index out of range", "a column may be listed once"));
+    SD_ARG(xg[0] == 0, "xg must start at 0");
+    for (int q = 1; q < m; ++q) SD_ARG(xg[q] == xg[q - 1] || xg[q] == xg[q - 1] + 1, "xg must rise in steps of 0 or 1");
     if (n == 0) return SDICE_OK;
     SD_ARG(tested && p && n_kept && med && mean, "NULL output");
     SD_ARG(ps, "ps is NULL");
