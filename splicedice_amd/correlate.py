@@ -12,12 +12,11 @@ the kept count, mean and median are of the kept PS values, floats are printed as
 
 On the GPU: sdice_spearman (rank correlation, its p-value, n, mean, median) -> sdice_bh over the tested rows.
 """
-import sys
-
 import numpy as np
 
-from .compare_sample_sets import annotation_suffixes, read_ps_table, table_header_names
-from .engine import Context, spearman_order
+from . import _cli
+from ._cli import read_ps_table, table_header_names
+from .engine import SPEARMAN_FIELDS, Context, field_shapes, spearman_order
 
 MIN_SAMPLES = 3
 MAX_SAMPLES = 4096                  # columns one sdice_spearman call takes (include/sdice.h)
@@ -26,9 +25,7 @@ MULTI_RANK_REFUSAL = ("correlate: not available under the multi-rank launcher (t
                       "fields only); run it in one process.")
 
 
-def refuse(why):
-    print(f"correlate: {why}. Exit.", file=sys.stderr)
-    sys.exit(1)
+refuse = _cli.refusal("correlate")
 
 
 def read_covariate(path):
@@ -66,41 +63,15 @@ def covariate_columns(names, header_names):
         refuse(f"cannot correlate with fewer than {MIN_SAMPLES} samples that have a value (got {len(names)})")
     if len(names) > MAX_SAMPLES:
         refuse(f"{len(names)} samples have a value, at most {MAX_SAMPLES} are supported")
-    where = {}
-    for j, name in enumerate(header_names):
-        where.setdefault(name, []).append(j)
-    for name in names:
-        hits = where.get(name, [])
-        if len(hits) != 1:
-            refuse(f"sample {name!r} " + ("is missing from the table header" if not hits else
-                                          f"appears {len(hits)} times in the table header"))
-    return np.array([where[x][0] for x in names], dtype=np.int32)
+    return _cli.columns_in_header(names, header_names, refuse)
 
 
 def correlate_dev(matrix, cols, xg, ctx):
     """the pipeline of compare_sample_sets.compare_dev: table up, Spearman + BH over the tested rows on resident vectors,
     per-row results down -> (kept row indices, dict of compacted per-row results incl. BH-corrected p)"""
-    from . import _stages
-    n = matrix.shape[0]
-    with _stages.stage("h2d"):
-        d_ps = ctx.to_device(matrix, np.float32)
-        d_cols, d_xg = ctx.to_device(cols, np.int32), ctx.to_device(xg, np.int32)
-        out = dict(tested=ctx.empty(n, np.uint8), p=ctx.empty(n, np.float64), rho=ctx.empty(n, np.float64),
-                   n_kept=ctx.empty(n, np.int32), med=ctx.empty(n, np.float32), mean=ctx.empty(n, np.float32))
-        d_q = ctx.empty(n, np.float64)
-    with _stages.stage("kernels"):
-        ctx.spearman_dev(d_ps, d_cols, d_xg, out)
-        ctx.bh_masked_dev(out["p"], out["tested"], d_q)
-        ctx.sync()
-    with _stages.stage("d2h"):
-        res = {k: v.to_host() for k, v in out.items()}
-        q = d_q.to_host()
-    for a in (d_ps, d_cols, d_xg, d_q, *out.values()):
-        a.free()
-    keep = np.flatnonzero(res["tested"])
-    r = {k: res[k][keep] for k in ("n_kept", "mean", "med", "rho", "p")}
-    r["corrected"] = q[keep]
-    return keep, r
+    return _cli.tested_rows(ctx, dict(ps=(matrix, np.float32), cols=(cols, np.int32), xg=(xg, np.int32)),
+                            field_shapes(SPEARMAN_FIELDS, matrix.shape[0]),
+                            lambda d, out: ctx.spearman_dev(d["ps"], d["cols"], d["xg"], out))
 
 
 def add_parser(parser):
@@ -115,41 +86,24 @@ def add_parser(parser):
 
 
 def run_with(args, ctx=None):
-    from . import _stages, mgpu, textio
+    from . import _stages, mgpu
     L = mgpu.launcher()             # (reads the torchrun environment before any GPU call)
-    if L.world > 1:
-        print(MULTI_RANK_REFUSAL, file=sys.stderr)
-        sys.exit(1)
+    _cli.refuse_multi_rank(L, MULTI_RANK_REFUSAL)
     names, values = read_covariate(args.covariate)
     idx = covariate_columns(names, table_header_names(args.psiSPLICEDICE))      # (exits before any GPU call)
     cols, xg = spearman_order(idx, values)
     with _stages.stage("parse"):
         rows, _, matrix = read_ps_table(args.psiSPLICEDICE, as_table=True)
-    n = matrix.shape[0]
-    if n:
-        own_ctx = ctx is None
-        ctx = ctx if ctx is not None else Context(L.local_rank)
-        try:
+    if matrix.shape[0]:
+        with _cli.engine_scope(ctx, lambda: Context(L.local_rank)) as ctx:
             keep, r = correlate_dev(matrix, cols, xg, ctx)
-        finally:
-            if own_ctx:
-                ctx.close()
     else:
         keep = np.zeros(0, np.int64)
         r = dict(n_kept=np.zeros(0, np.int32), mean=np.zeros(0, np.float32), med=np.zeros(0, np.float32),
                  rho=np.zeros(0), p=np.zeros(0), corrected=np.zeros(0))
-    header = "event\tn\tmean\tmedian\trho\tp-value\tcorrected"
-    columns = [r["n_kept"], r["mean"], r["med"], r["rho"], r["p"], r["corrected"]]
-    modes = [".0f"] + ["repr"] * 5
-    if not args.annotation:
-        with _stages.stage("format+write"):
-            textio.write_columns(args.outputFile, header + "\n", rows.take(keep), columns, modes)
-        return
-    kept_names = list(rows.take(keep))
-    suffixes = annotation_suffixes(kept_names, args.annotation)
-    with _stages.stage("format+write"):
-        textio.write_columns(args.outputFile, header + "\tgene\toverlapping\ttranscript_id\n", kept_names, columns, modes,
-                             suffixes=suffixes)
+    _cli.write_event_table(args.outputFile, "event\tn\tmean\tmedian\trho\tp-value\tcorrected", rows, keep,
+                           [r["n_kept"], r["mean"], r["med"], r["rho"], r["p"], r["corrected"]], [".0f"] + ["repr"] * 5,
+                           args.annotation)
 
 
 if __name__ == "__main__":

@@ -14,6 +14,7 @@ float32 as quant does.
 import numpy as np
 
 from . import textio
+from ._cli import engine_scope
 from .engine import Context
 
 
@@ -96,9 +97,7 @@ def add_parser(parser):
 
 
 def run_with(args, ctx=None):
-    own_ctx = ctx is None
-    ctx = ctx if ctx is not None else Context(0)
-    try:
+    with engine_scope(ctx, lambda: Context(0)) as ctx:
         if args.clusters:
             print("Gathering clusters...")
             clusters = get_clusters(args.clusters)
@@ -114,9 +113,6 @@ def run_with(args, ctx=None):
         print("Calculating PS values...")
         write_ps_values(clusters, header, index, counts, args.output_prefix, ctx)
         print("Done.")
-    finally:
-        if own_ctx:
-            ctx.close()
 
 
 if __name__ == "__main__":

@@ -33,9 +33,9 @@ in _shard_inputs; pad_rows / drop_padding pad to the longest shard and back.
 import numpy as np
 
 from . import shard
+from .engine import RANKSUM_FIELDS
 
-STAT_NAMES = ("tested", "p", "z", "med1", "med2", "mean1", "mean2", "delta")
-STAT_DTYPES = (np.uint8, np.float64, np.float64, np.float32, np.float32, np.float32, np.float32, np.float32)
+STAT_NAMES, STAT_DTYPES = zip(*RANKSUM_FIELDS)      # (the packed all-gather carries the rank-sum fields, in their order)
 
 
 def _is_dev(x):

@@ -16,6 +16,27 @@ def _c(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
 
 
+# The result fields of every per-row test, in the order of its C entry point (include/sdice.h).  A field is [n]; one marked
+# PER_SET is [k, n], one row per sample set.  GRAM_FIELDS: the four [m, m] matrices of sample_gram.
+PER_SET = "per set"
+RANKSUM_FIELDS = [("tested", np.uint8), ("p", np.float64), ("z", np.float64), ("med1", np.float32), ("med2", np.float32),
+                  ("mean1", np.float32), ("mean2", np.float32), ("delta", np.float32)]       # (ranksum and signedrank)
+KRUSKAL_FIELDS = [("tested", np.uint8), ("p", np.float64), ("h", np.float64), ("med", np.float32, PER_SET),
+                  ("mean", np.float32, PER_SET), ("delta", np.float32)]
+SPEARMAN_FIELDS = [("tested", np.uint8), ("p", np.float64), ("rho", np.float64), ("n_kept", np.int32), ("med", np.float32),
+                   ("mean", np.float32)]
+GRAM_FIELDS = [("shared", np.int64), ("sum1", np.int64), ("sum2", np.int64), ("prod", np.int64)]
+
+
+def field_shapes(fields, shape, k=None):
+    """a field table -> name: (shape, dtype) in its order; `shape` for a plain field, (k, shape) for one marked PER_SET"""
+    return {f[0]: ((k, shape) if f[2:] else shape, f[1]) for f in fields}
+
+
+def _zeros(fields, shape, k=None):
+    return {name: np.zeros(sh, dt) for name, (sh, dt) in field_shapes(fields, shape, k).items()}
+
+
 def pair_array(pairs):
     """a pair list as the library takes it: int32 [m, 2], C-contiguous, m >= 1 (the library checks the indices)"""
     a = np.asarray(pairs)
@@ -317,12 +338,8 @@ class Context:
         ps = _c(ps, np.float32)
         n, s = ps.shape
         g1, g2 = _c(g1, np.int32), _c(g2, np.int32)
-        out = dict(tested=np.zeros(n, np.uint8), p=np.zeros(n, np.float64), z=np.zeros(n, np.float64),
-                   med1=np.zeros(n, np.float32), med2=np.zeros(n, np.float32), mean1=np.zeros(n, np.float32),
-                   mean2=np.zeros(n, np.float32), delta=np.zeros(n, np.float32))
-        check(self.lib.sdice_ranksum(self.h, n, s, _ptr(ps), _ptr(g1), g1.size, _ptr(g2), g2.size,
-                                     _ptr(out["tested"]), _ptr(out["p"]), _ptr(out["z"]), _ptr(out["med1"]),
-                                     _ptr(out["med2"]), _ptr(out["mean1"]), _ptr(out["mean2"]), _ptr(out["delta"])),
+        out = _zeros(RANKSUM_FIELDS, n)
+        check(self.lib.sdice_ranksum(self.h, n, s, _ptr(ps), _ptr(g1), g1.size, _ptr(g2), g2.size, *map(_ptr, out.values())),
               "sdice_ranksum")
         return out
 
@@ -333,11 +350,9 @@ class Context:
         n, s = ps.shape
         cols, set_ptr = kruskal_sets(sets, s)
         k = len(set_ptr) - 1
-        out = dict(tested=np.zeros(n, np.uint8), p=np.zeros(n, np.float64), h=np.zeros(n, np.float64),
-                   med=np.zeros((k, n), np.float32), mean=np.zeros((k, n), np.float32), delta=np.zeros(n, np.float32))
-        check(self.lib.sdice_kruskal(self.h, n, s, _ptr(ps), _ptr(cols), _ptr(set_ptr), k, _ptr(out["tested"]),
-                                     _ptr(out["p"]), _ptr(out["h"]), _ptr(out["med"]), _ptr(out["mean"]),
-                                     _ptr(out["delta"])), "sdice_kruskal")
+        out = _zeros(KRUSKAL_FIELDS, n, k)
+        check(self.lib.sdice_kruskal(self.h, n, s, _ptr(ps), _ptr(cols), _ptr(set_ptr), k, *map(_ptr, out.values())),
+              "sdice_kruskal")
         return out
 
     def signedrank(self, ps, a, b):
@@ -348,12 +363,9 @@ class Context:
         a, b = _c(a, np.int32), _c(b, np.int32)
         if a.shape != b.shape or a.ndim != 1:
             raise ValueError(f"signedrank: the pair lists must be two vectors of one length, got {a.shape} and {b.shape}")
-        out = dict(tested=np.zeros(n, np.uint8), p=np.zeros(n, np.float64), z=np.zeros(n, np.float64),
-                   med1=np.zeros(n, np.float32), med2=np.zeros(n, np.float32), mean1=np.zeros(n, np.float32),
-                   mean2=np.zeros(n, np.float32), delta=np.zeros(n, np.float32))
-        check(self.lib.sdice_signedrank(self.h, n, s, _ptr(ps), _ptr(a), _ptr(b), a.size, _ptr(out["tested"]),
-                                        _ptr(out["p"]), _ptr(out["z"]), _ptr(out["med1"]), _ptr(out["med2"]),
-                                        _ptr(out["mean1"]), _ptr(out["mean2"]), _ptr(out["delta"])), "sdice_signedrank")
+        out = _zeros(RANKSUM_FIELDS, n)
+        check(self.lib.sdice_signedrank(self.h, n, s, _ptr(ps), _ptr(a), _ptr(b), a.size, *map(_ptr, out.values())),
+              "sdice_signedrank")
         return out
 
     def spearman(self, ps, cols, x):
@@ -363,11 +375,9 @@ class Context:
         ps = _c(ps, np.float32)
         n, s = ps.shape
         cols, xg = spearman_order(cols, x)
-        out = dict(tested=np.zeros(n, np.uint8), p=np.zeros(n, np.float64), rho=np.zeros(n, np.float64),
-                   n_kept=np.zeros(n, np.int32), med=np.zeros(n, np.float32), mean=np.zeros(n, np.float32))
-        check(self.lib.sdice_spearman(self.h, n, s, _ptr(ps), _ptr(cols), _ptr(xg), cols.size, _ptr(out["tested"]),
-                                      _ptr(out["p"]), _ptr(out["rho"]), _ptr(out["n_kept"]), _ptr(out["med"]),
-                                      _ptr(out["mean"])), "sdice_spearman")
+        out = _zeros(SPEARMAN_FIELDS, n)
+        check(self.lib.sdice_spearman(self.h, n, s, _ptr(ps), _ptr(cols), _ptr(xg), cols.size, *map(_ptr, out.values())),
+              "sdice_spearman")
         return out
 
     def sample_gram(self, ps, cols):
@@ -378,9 +388,8 @@ class Context:
         n, s = ps.shape
         cols = gram_columns(cols)
         m = cols.size
-        out = {k: np.zeros((m, m), np.int64) for k in ("shared", "sum1", "sum2", "prod")}
-        check(self.lib.sdice_sample_gram(self.h, n, s, _ptr(ps), _ptr(cols), m, _ptr(out["shared"]), _ptr(out["sum1"]),
-                                         _ptr(out["sum2"]), _ptr(out["prod"])), "sdice_sample_gram")
+        out = _zeros(GRAM_FIELDS, (m, m))
+        check(self.lib.sdice_sample_gram(self.h, n, s, _ptr(ps), _ptr(cols), m, *map(_ptr, out.values())), "sdice_sample_gram")
         return out
 
     def fisher_pairs(self, incl, excl, pairs=None):

@@ -18,6 +18,7 @@ import sys
 
 import numpy as np
 
+from ._cli import engine_scope
 from .engine import Context
 
 
@@ -73,9 +74,9 @@ def run_with(args, ctx=None):
     cols, rows, matrix = data["cols"], data["rows"], data["data"]
     null_idx = np.flatnonzero(np.isin(cols, null))
     sample_idx = np.flatnonzero(np.isin(cols, samples))
-    ctx = ctx if ctx is not None else Context(0)
     if matrix.dtype not in (np.float32, np.float64):
         matrix = matrix.astype(np.float64)
-    ev, pos, z, mean, std = find_hits(ctx, matrix, null_idx, sample_idx, args.outlierCutoff)
+    with engine_scope(ctx, lambda: Context(0)) as ctx:
+        ev, pos, z, mean, std = find_hits(ctx, matrix, null_idx, sample_idx, args.outlierCutoff)
     for e, p in zip(ev.tolist(), pos.tolist()):
         print(rows[e], cols[sample_idx[p]], z[e, p], matrix[e, sample_idx[p]], mean[e], std[e], sep="\t")

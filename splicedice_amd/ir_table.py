@@ -23,6 +23,7 @@ import os
 import numpy as np
 
 from . import textio
+from ._cli import engine_scope
 from .engine import Context
 
 
@@ -145,13 +146,8 @@ def run_with(args, ctx=None):
         lines[sample] = rec
     excl = None
     if clusters is not None and events:
-        own_ctx = ctx is None
-        ctx = ctx if ctx is not None else Context(0)
-        try:
+        with engine_scope(ctx, lambda: Context(0)) as ctx:
             excl = cluster_sums(ctx, counts, index, clusters, wanted, own_first=not integral)
-        finally:
-            if own_ctx:
-                ctx.close()
     # pass 2: the reference's per-line arithmetic and messages, in its order (ir_table.py:96-138)
     IR, RSD, junctions = {}, {}, set()
     for sample in samples:

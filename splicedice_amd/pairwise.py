@@ -14,6 +14,7 @@ s(s-1)/2 -- the same kernels over a caller's pair table (sdice_fisher_pair_list 
 import numpy as np
 
 from . import textio
+from ._cli import engine_scope
 from .distributed import CHI2_ZERO_MSG
 from .engine import Context
 
@@ -242,17 +243,15 @@ def run_with(args, ctx=None):
     for n in range(0, totaln, 50):
         print(f"[{n} / {totaln}] events analyzed...")
 
-    own_ctx = ctx is None
-    ctx = ctx if ctx is not None else Context(L.local_rank)
     header = "clusterID\t" + "\t".join(columns) + "\n"
-    fractional = counts.dtype != np.int32
-    if fractional and args.chi2:
-        raise ValueError("pairwise --chi2 needs integer counts here (the chi-square kernel takes integer tables; the "
-                         "reference would feed the fractional table to scipy.stats.chi2_contingency as it stands)")
-    if fractional and totaln and pairs:
-        # a table with non-integer cells: float sums in table order, truncated as scipy's int64 cast does; one rank
-        if L.root:
-            try:
+    with engine_scope(ctx, lambda: Context(L.local_rank)) as ctx:
+        fractional = counts.dtype != np.int32
+        if fractional and args.chi2:
+            raise ValueError("pairwise --chi2 needs integer counts here (the chi-square kernel takes integer tables; the "
+                             "reference would feed the fractional table to scipy.stats.chi2_contingency as it stands)")
+        if fractional and totaln and pairs:
+            # a table with non-integer cells: float sums in table order, truncated as scipy's int64 cast does; one rank
+            if L.root:
                 row_ptr, col = exclusion_csr(events, clusters)
                 incl, excl = fractional_tables(ctx, counts, row_ptr, col)
                 if hasattr(ctx, "fisher_pairs_dev"):
@@ -265,43 +264,27 @@ def run_with(args, ctx=None):
                     elif args.multiple_test_correction == "pairwise":
                         parray = ctx.bh_columns(parray)
                     textio.write_table(args.output, header, events, np.asarray(parray, dtype=np.float64), "repr")
-            finally:
-                if own_ctx:
-                    ctx.close()
-        elif own_ctx:
-            ctx.close()
-        return
-    if L.world > 1 and totaln and pairs:
-        # junction rows sharded over the ranks (distributed.pairwise_sharded); every rank formats its own
-        # rows, rank 0 stitches the parts into the one output table
-        from . import distributed
-        try:
+            return
+        if L.world > 1 and totaln and pairs:
+            # junction rows sharded over the ranks (distributed.pairwise_sharded); every rank formats its own
+            # rows, rank 0 stitches the parts into the one output table
+            from . import distributed
             row_ptr, col = exclusion_csr(events, clusters)
             out = distributed.pairwise_sharded(ctx, L.comm(ctx), np.ascontiguousarray(counts, dtype=np.int32), row_ptr, col,
                                                args.multiple_test_correction, test="chi2" if args.chi2 else "fisher", **kw)
-        finally:
-            if own_ctx:
-                ctx.close()
-        lo, hi = out["own"]
-        textio.write_table(L.part(args.output), header if L.root else "", events[lo:hi],
-                           np.asarray(out["p"], dtype=np.float64).reshape(hi - lo, len(pairs)), "repr")
-        L.stitch(args.output)
-        return
-    if not L.root:
-        if own_ctx:
-            ctx.close()
-        return                       # (empty inputs are not sharded: rank 0 alone)
-    if totaln and pairs and hasattr(ctx, "fisher_pairs_dev"):
-        try:
-            row_ptr, col = exclusion_csr(events, clusters)
+            lo, hi = out["own"]
+            textio.write_table(L.part(args.output), header if L.root else "", events[lo:hi],
+                               np.asarray(out["p"], dtype=np.float64).reshape(hi - lo, len(pairs)), "repr")
+            L.stitch(args.output)
+            return
+        if not L.root:
+            return                       # (empty inputs are not sharded: rank 0 alone)
+        row_ptr, col = exclusion_csr(events, clusters)
+        if totaln and pairs and hasattr(ctx, "fisher_pairs_dev"):
             device_pipeline(ctx, counts, row_ptr, col, args.chi2, args.multiple_test_correction, events, header, args.output,
                             pair_list=kw.get("pairs"))
-        finally:
-            if own_ctx:
-                ctx.close()
-        return
-    try:        # host-array engine (the CPU test double) and empty inputs
-        row_ptr, col = exclusion_csr(events, clusters)
+            return
+        # host-array engine (the CPU test double) and empty inputs
         if totaln and pairs:
             excl = ctx.ps(counts, row_ptr, col, want_excl=True, want_ps=False)
             if args.chi2:
@@ -318,10 +301,6 @@ def run_with(args, ctx=None):
                 parray = ctx.bh_columns(parray)
         else:
             parray = np.zeros((totaln, len(pairs)))
-    finally:
-        if own_ctx:
-            ctx.close()
-
     # str(numpy.float64) per cell (pairwise_fisher.py:195-200) through the library's formatter
     textio.write_table(args.output, header, events,
                        np.asarray(parray, dtype=np.float64).reshape(len(events), len(pairs)), "repr")

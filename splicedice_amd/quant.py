@@ -15,6 +15,7 @@ from time import time
 import numpy as np
 
 from . import _stages, juncio, textio
+from ._cli import engine_scope
 from .engine import Context
 
 
@@ -82,15 +83,10 @@ class Quant:
         self.args = args
         self.manifestFilename = manifest_filename
         self.outputPrefix = output_prefix
-        own_ctx = ctx is None
         from . import mgpu
         self.L = mgpu.launcher()            # (reads the torchrun environment before any GPU call)
-        self.ctx = ctx if ctx is not None else Context(self.L.local_rank)
-        try:
+        with engine_scope(ctx, lambda: Context(self.L.local_rank)) as self.ctx:
             self._run()
-        finally:
-            if own_ctx:
-                self.ctx.close()
 
     def _run(self):
         timer = Timer()

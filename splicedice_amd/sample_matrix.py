@@ -17,8 +17,9 @@ import sys
 
 import numpy as np
 
-from .compare_sample_sets import read_ps_table, table_header_names
-from .engine import Context, SdiceError, sample_matrix_finish
+from . import _cli
+from ._cli import read_ps_table, table_header_names
+from .engine import GRAM_FIELDS, Context, SdiceError, field_shapes, sample_matrix_finish
 
 MIN_SAMPLES = 2
 MAX_SAMPLES = 4096                  # columns one sdice_sample_gram call takes (include/sdice.h)
@@ -27,9 +28,7 @@ MULTI_RANK_REFUSAL = ("sample_matrix: not available under the multi-rank launche
                       "but no exchange for them exists yet); run it in one process.")
 
 
-def refuse(why):
-    print(f"sample_matrix: {why}. Exit.", file=sys.stderr)
-    sys.exit(1)
+refuse = _cli.refusal("sample_matrix")
 
 
 def read_samples(path):
@@ -52,40 +51,20 @@ def sample_columns(names, header_names):
     """the chosen samples (None: every column in table order) and the table's column names -> (names, int32 column index of
     each); prints why and exits with status 1 when a sample is not exactly once in the header or their number is outside
     2..4096"""
-    where = {}
-    for j, name in enumerate(header_names):
-        where.setdefault(name, []).append(j)
     if names is None:
         names = list(header_names)
     if len(names) < MIN_SAMPLES:
         refuse(f"cannot compare fewer than {MIN_SAMPLES} samples (got {len(names)})")
     if len(names) > MAX_SAMPLES:
         refuse(f"{len(names)} samples, at most {MAX_SAMPLES} are supported")
-    for name in names:
-        hits = where.get(name, [])
-        if len(hits) != 1:
-            refuse(f"sample {name!r} " + ("is missing from the table header" if not hits else
-                                          f"appears {len(hits)} times in the table header"))
-    return names, np.array([where[x][0] for x in names], dtype=np.int32)
+    return names, _cli.columns_in_header(names, header_names, refuse)
 
 
 def gram_dev(matrix, cols, ctx):
     """table up, the four integer matrices on resident buffers, matrices down -> dict of int64 [m, m]"""
-    from . import _stages
-    m = cols.size
-    with _stages.stage("h2d"):
-        d_ps = ctx.to_device(matrix, np.float32)
-        d_cols = ctx.to_device(cols, np.int32)
-        out = {k: ctx.empty((m, m), np.int64) for k in ("shared", "sum1", "sum2", "prod")}
-    try:
-        with _stages.stage("kernels"):
-            ctx.sample_gram_dev(d_ps, d_cols, out)
-            ctx.sync()
-        with _stages.stage("d2h"):
-            return {k: v.to_host() for k, v in out.items()}
-    finally:
-        for a in (d_ps, d_cols, *out.values()):
-            a.free()
+    return _cli.device_call(ctx, dict(ps=(matrix, np.float32), cols=(cols, np.int32)),
+                            field_shapes(GRAM_FIELDS, (cols.size, cols.size)),
+                            lambda d, out: ctx.sample_gram_dev(d["ps"], d["cols"], out))
 
 
 def add_parser(parser):
@@ -103,25 +82,19 @@ def add_parser(parser):
 def run_with(args, ctx=None):
     from . import _stages, mgpu, textio
     L = mgpu.launcher()             # (reads the torchrun environment before any GPU call)
-    if L.world > 1:
-        print(MULTI_RANK_REFUSAL, file=sys.stderr)
-        sys.exit(1)
+    _cli.refuse_multi_rank(L, MULTI_RANK_REFUSAL)
     if args.minShared < 1:
         refuse(f"--minShared must be at least 1 (got {args.minShared})")
     chosen = read_samples(args.samples) if args.samples else None
     names, cols = sample_columns(chosen, table_header_names(args.psiSPLICEDICE))     # (exits before any GPU call)
     with _stages.stage("parse"):
         _, _, matrix = read_ps_table(args.psiSPLICEDICE, as_table=True)
-    own_ctx = ctx is None
-    ctx = ctx if ctx is not None else Context(L.local_rank)
-    try:
-        sums = gram_dev(matrix, cols, ctx)
-    except SdiceError as e:         # a value off the 3-decimal grid: the library's line
-        print(f"sample_matrix: {e}", file=sys.stderr)
-        sys.exit(1)
-    finally:
-        if own_ctx:
-            ctx.close()
+    with _cli.engine_scope(ctx, lambda: Context(L.local_rank)) as ctx:
+        try:
+            sums = gram_dev(matrix, cols, ctx)
+        except SdiceError as e:         # a value off the 3-decimal grid: the library's line
+            print(f"sample_matrix: {e}", file=sys.stderr)
+            sys.exit(1)
     corr, rmsd = sample_matrix_finish(sums["shared"], sums["sum1"], sums["sum2"], sums["prod"], args.minShared)
     header = "sample\t" + "\t".join(names) + "\n"
     with _stages.stage("format+write"):

@@ -17,6 +17,7 @@ reading and writing rules (splicedice/similarity.py, line numbers below):
 import numpy as np
 
 from . import textio
+from ._cli import engine_scope
 from .engine import Context
 
 P_CUTOFF = 0.05
@@ -88,7 +89,7 @@ def add_parser(parser):
 
 
 def run_with(args, ctx=None):
-    ctx = ctx if ctx is not None else Context(0)
     events = significant_events(args.comparison)
-    samples, scores, counts = score_table(ctx, args.allps, events)
+    with engine_scope(ctx, lambda: Context(0)) as ctx:
+        samples, scores, counts = score_table(ctx, args.allps, events)
     write_report(args.output, samples, scores, counts, sample_groups(args.manifest) if args.manifest else None)

@@ -14,7 +14,7 @@ import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-from splicedice_amd.engine import Context, kruskal_sets
+from splicedice_amd.engine import KRUSKAL_FIELDS, Context, field_shapes, kruskal_sets
 
 HBM_BYTES_PER_S = 8e12
 
@@ -58,8 +58,7 @@ for n, s, splits in ((1_000_000, 100, (2, 4)), (625_000, 1000, (2, 10))):
         sets = [np.arange(i * (s // k), (i + 1) * (s // k), dtype=np.int32) for i in range(k)]
         cols, set_ptr = kruskal_sets(sets, s)
         d_cols = ctx.to_device(cols, np.int32)
-        out = dict(tested=ctx.empty(n, np.uint8), p=ctx.empty(n, np.float64), h=ctx.empty(n, np.float64),
-                   med=ctx.empty((k, n), np.float32), mean=ctx.empty((k, n), np.float32), delta=ctx.empty(n, np.float32))
+        out = {x: ctx.empty(*sd) for x, sd in field_shapes(KRUSKAL_FIELDS, n, k).items()}
         med, lo, hi = timed(lambda: ctx.kruskal_dev(d_ps, d_cols, set_ptr, out))
         tested = int(out["tested"].to_host().sum())
         row = dict(call="kruskal_dev", rows=n, samples=s, sets=k, set_size=s // k, reps=args.reps, median_ms=med, min_ms=lo,

@@ -24,11 +24,11 @@ os.environ.setdefault("OPENBLAS_NUM_THREADS", "16")
 os.environ.setdefault("MKL_NUM_THREADS", "16")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-from splicedice_amd.engine import Context
+from splicedice_amd.engine import GRAM_FIELDS, Context
 
 LANES_PER_CU_CLOCK = 128
 CLOCK_HZ = 2.4e9
-NAMES = ("shared", "sum1", "sum2", "prod")
+NAMES = [name for name, _ in GRAM_FIELDS]
 TILE = 64
 
 ap = argparse.ArgumentParser()

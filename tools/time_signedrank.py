@@ -16,7 +16,7 @@ import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-from splicedice_amd.engine import Context
+from splicedice_amd.engine import RANKSUM_FIELDS, Context, field_shapes
 
 HBM_BYTES_PER_S = 8e12
 
@@ -58,8 +58,7 @@ for n, m, blk in ((1_000_000, 50, 25_000), (1_000_000, 8, 25_000), (100_000, 500
     d_ps = table(n, s, blk)
     g1, g2 = np.arange(0, m, dtype=np.int32), np.arange(m, s, dtype=np.int32)
     d_g1, d_g2 = ctx.to_device(g1, np.int32), ctx.to_device(g2, np.int32)
-    out = dict(tested=ctx.empty(n, np.uint8), p=ctx.empty(n, np.float64), z=ctx.empty(n, np.float64),
-               **{x: ctx.empty(n, np.float32) for x in ("med1", "med2", "mean1", "mean2", "delta")})
+    out = {x: ctx.empty(*sd) for x, sd in field_shapes(RANKSUM_FIELDS, n).items()}
     row = dict(rows=n, samples=s, pairs=m, reps=args.reps)
     for call in ("ranksum_dev", "signedrank_dev"):
         med, lo, hi = timed(lambda: getattr(ctx, call)(d_ps, d_g1, d_g2, out))

@@ -16,7 +16,7 @@ import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-from splicedice_amd.engine import Context, spearman_order
+from splicedice_amd.engine import RANKSUM_FIELDS, SPEARMAN_FIELDS, Context, field_shapes, spearman_order
 
 HBM_BYTES_PER_S = 8e12
 
@@ -59,10 +59,8 @@ for n, s, blk in ((1_000_000, 16, 25_000), (1_000_000, 100, 25_000), (100_000, 1
     d_g1, d_g2 = ctx.to_device(g1, np.int32), ctx.to_device(g2, np.int32)
     cols, xg = spearman_order(np.arange(s), rng.integers(0, max(2, s // 4), size=s))
     d_cols, d_xg = ctx.to_device(cols, np.int32), ctx.to_device(xg, np.int32)
-    rs_out = dict(tested=ctx.empty(n, np.uint8), p=ctx.empty(n, np.float64), z=ctx.empty(n, np.float64),
-                  **{x: ctx.empty(n, np.float32) for x in ("med1", "med2", "mean1", "mean2", "delta")})
-    sp_out = dict(tested=ctx.empty(n, np.uint8), p=ctx.empty(n, np.float64), rho=ctx.empty(n, np.float64),
-                  n_kept=ctx.empty(n, np.int32), med=ctx.empty(n, np.float32), mean=ctx.empty(n, np.float32))
+    rs_out = {x: ctx.empty(*sd) for x, sd in field_shapes(RANKSUM_FIELDS, n).items()}
+    sp_out = {x: ctx.empty(*sd) for x, sd in field_shapes(SPEARMAN_FIELDS, n).items()}
     row = dict(rows=n, samples=s, reps=args.reps)
     for name, call, out in (("ranksum_dev", lambda: ctx.ranksum_dev(d_ps, d_g1, d_g2, rs_out), rs_out),
                             ("spearman_dev", lambda: ctx.spearman_dev(d_ps, d_cols, d_xg, sp_out), sp_out)):
