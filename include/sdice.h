@@ -204,13 +204,49 @@ int sdice_kruskal_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, c
  *  z = (R+ - n'(n'+1)/4) / sqrt((n'(n'+1)(2n'+1) - sum(t^3 - t)/2) / 24), positive when side 1 is larger (scipy
  *  reports -|z|), p = erfc(|z| / sqrt 2), as accurate as sdice_ranksum's.  A tested row with n' = 0 has z = 0, p = 1
  *  (scipy: NaN).  Always the normal approximation, from 3 pairs up: scipy's exact and permutation p-values
- *  (method="auto") are not offered.  z optional (NULL to skip). */
+ *  (method="auto") are not offered by this call (sdice_signedrank_exact below has the exact one).  z optional (NULL to skip). */
 int sdice_signedrank(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps, const int32_t* a,
                      const int32_t* b, int32_t m, uint8_t* tested, double* p, double* z, float* med1,
                      float* med2, float* mean1, float* mean2, float* delta);
 int sdice_signedrank_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, const int32_t* d_a,
                          const int32_t* d_b, int32_t m, uint8_t* d_tested, double* d_p, double* d_z,
                          float* d_med1, float* d_med2, float* d_mean1, float* d_mean2, float* d_delta);
+
+/* ---- compare_sample_sets --exact: the two tests above with the exact conditional p-value on small rows (not in the
+ *      reference).  Arguments, refusals and limits are those of sdice_ranksum / sdice_signedrank plus a trailing
+ *      exact[n] (uint8, required); the row rules, tested, med1/2, mean1/2, delta and z are theirs bit for bit.  Only p
+ *      changes, and only on eligible rows: exact[row] = 1 where p is the exact value, 0 where the row is not tested or
+ *      keeps the asymptotic p (bit for bit that of the plain call).  Groups of up to 4096 columns stay legal; their rows
+ *      are eligible only where NaNs leave few enough values.
+ *  Rank-sum: a tested row is eligible when its kept counts satisfy n1' + n2' = N <= 32 (C(32, 16) fits 32 bits).
+ *  Doubled mid-ranks r_i = 2 #(v_j < v_i) + #(v_j == v_i) + 1 by float32 value: -0.0 == +0.0 is one tie group,
+ *  subnormals are distinct values, +-inf are ordinary values.  k = min(n1', n2'), W = the doubled rank sum of that set
+ *  (set 1 on a tie of sizes), D = |W - k(N+1)|,
+ *      p = #{k-subsets S of the N doubled ranks : |sum(S) - k(N+1)| >= D} / C(N, k),
+ *  both integers, p one float64 division: the permutation distribution given the observed ties, the exact counterpart
+ *  of erfc(|z| / sqrt 2), symmetric in which set is taken.  Untied rows: scipy.stats.mannwhitneyu(method="exact").  An
+ *  all-equal row has D = 0, p = 1.
+ *  Signed-rank: a tested row is eligible when it has 1 <= n' <= 31 non-zero differences (2^31 fits 32 bits); n' = 0
+ *  keeps p = 1 with exact = 1.  The differences are sdice_signedrank's (integer thousandths on a row of 3-decimal
+ *  values, float32 otherwise), doubled mid-ranks of |d|, W = the doubled rank sum of the positive ones,
+ *  D = |2W - n'(n'+1)|,
+ *      p = #{sign patterns : |2 sum(S) - n'(n'+1)| >= D} / 2^n'.
+ *  Rows without ties or zeros: scipy.stats.wilcoxon(method="exact"). */
+int sdice_ranksum_exact(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps,
+                        const int32_t* g1, int32_t n1, const int32_t* g2, int32_t n2,
+                        uint8_t* tested, double* p, double* z, float* med1, float* med2,
+                        float* mean1, float* mean2, float* delta, uint8_t* exact);
+int sdice_ranksum_exact_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps,
+                            const int32_t* d_g1, int32_t n1, const int32_t* d_g2, int32_t n2,
+                            uint8_t* d_tested, double* d_p, double* d_z, float* d_med1, float* d_med2,
+                            float* d_mean1, float* d_mean2, float* d_delta, uint8_t* d_exact);
+int sdice_signedrank_exact(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps, const int32_t* a,
+                           const int32_t* b, int32_t m, uint8_t* tested, double* p, double* z, float* med1,
+                           float* med2, float* mean1, float* mean2, float* delta, uint8_t* exact);
+int sdice_signedrank_exact_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, const int32_t* d_a,
+                               const int32_t* d_b, int32_t m, uint8_t* d_tested, double* d_p, double* d_z,
+                               float* d_med1, float* d_med2, float* d_mean1, float* d_mean2, float* d_delta,
+                               uint8_t* d_exact);
 
 /* ---- correlate: Spearman rank correlation of the PS values of m listed columns with one covariate value per listed
  *      column, per row scipy.stats.spearmanr(x_kept, ps_kept) under the row rules above (not in the reference).

@@ -13,6 +13,11 @@ Another one: `--paired` pairs line i of -m1 with line i of -m2 (matched samples:
 after) and the test is the Wilcoxon signed-rank test of the pairs (sdice_signedrank); the output columns are the
 two-set ones.
 
+A third: `--exact` replaces the normal approximation of the p-value by the exact conditional (permutation) value on the
+rows small enough for it -- at most 32 kept values in the two-set test, at most 31 non-zero differences with `--paired`
+(sdice_ranksum_exact, sdice_signedrank_exact); larger rows keep the asymptotic p-value, as R's wilcox.test does.  Same
+columns; not with -mx.
+
 On the GPU: the per-row loop :216-232 (NaN drop, <3 skip, scipy ranksums, medians, means)
 -> sdice_ranksum; multipletests(..., "fdr_bh") :235 -> sdice_bh over the tested rows.
 The GTF annotation columns are host string work, as in the reference.
@@ -23,9 +28,15 @@ import numpy as np
 
 from . import _cli
 from ._cli import annotation_suffixes, read_annotation, read_ps_table, samples_from_manifest, table_header_names  # noqa: F401
-from .engine import KRUSKAL_FIELDS, RANKSUM_FIELDS, Context, field_shapes
+from .engine import KRUSKAL_FIELDS, RANKSUM_EXACT_FIELDS, RANKSUM_FIELDS, Context, field_shapes
 
 refuse = _cli.refusal("compare_sample_sets --paired")
+refuse_exact = _cli.refusal("compare_sample_sets --exact")
+
+
+def row_test(ctx, paired, exact, dev=False):
+    """the context's call for the chosen test: ranksum / signedrank, their _exact forms with --exact, _dev on resident data"""
+    return getattr(ctx, ("signedrank" if paired else "ranksum") + ("_exact" if exact else "") + ("_dev" if dev else ""))
 
 
 def column_indices(group, cols):
@@ -33,20 +44,24 @@ def column_indices(group, cols):
     return np.nonzero(np.isin(cols, group))[0].astype(np.int32)
 
 
-def compare_dev(matrix, g1_idx, g2_idx, ctx, paired=False):
+def compare_dev(matrix, g1_idx, g2_idx, ctx, paired=False, exact=False):
     """compare() on the HIP engine stage by stage: table up, rank-sum (paired: signed-rank) + BH over the tested rows on
-    resident vectors, per-row results down (sdice_ranksum + sdice_bh do the same steps inside two host calls)"""
-    test = ctx.signedrank_dev if paired else ctx.ranksum_dev
-    return _cli.tested_rows(ctx, dict(ps=(matrix, np.float32), g1=(g1_idx, np.int32), g2=(g2_idx, np.int32)),
-                            field_shapes(RANKSUM_FIELDS, matrix.shape[0]), lambda d, out: test(d["ps"], d["g1"], d["g2"], out))
+    resident vectors, per-row results down (sdice_ranksum + sdice_bh do the same steps inside two host calls).  exact:
+    the _exact calls; BH runs over the mixed p vector and the `exact` marks stay behind."""
+    test = row_test(ctx, paired, exact, dev=True)
+    keep, r = _cli.tested_rows(ctx, dict(ps=(matrix, np.float32), g1=(g1_idx, np.int32), g2=(g2_idx, np.int32)),
+                               field_shapes(RANKSUM_EXACT_FIELDS if exact else RANKSUM_FIELDS, matrix.shape[0]),
+                               lambda d, out: test(d["ps"], d["g1"], d["g2"], out))
+    r.pop("exact", None)
+    return keep, r
 
 
-def compare(matrix, g1_idx, g2_idx, ctx, paired=False):
+def compare(matrix, g1_idx, g2_idx, ctx, paired=False, exact=False):
     """-> (kept row indices, dict of compacted per-row results incl. BH-corrected p).  paired: g1_idx[q] and g2_idx[q]
-    are the columns of pair q and the test is the signed-rank test."""
+    are the columns of pair q and the test is the signed-rank test.  exact: exact p-values on the small rows."""
     if hasattr(ctx, "ranksum_dev") and matrix.shape[0]:
-        return compare_dev(matrix, g1_idx, g2_idx, ctx, paired)
-    res = (ctx.signedrank if paired else ctx.ranksum)(matrix, g1_idx, g2_idx)
+        return compare_dev(matrix, g1_idx, g2_idx, ctx, paired, exact)
+    res = row_test(ctx, paired, exact)(matrix, g1_idx, g2_idx)
     keep = np.flatnonzero(res["tested"])
     out = {k: res[k][keep] for k in ("p", "med1", "med2", "mean1", "mean2", "delta")}
     out["corrected"] = ctx.bh(out["p"]) if keep.size else np.zeros(0)
@@ -64,16 +79,16 @@ def compare_sets_dev(matrix, set_idx, ctx):
                             lambda d, out: ctx.kruskal_dev(d["ps"], d["cols"], set_ptr, out))
 
 
-def compare_sharded(matrix, g1_idx, g2_idx, ctx, L, paired=False):
+def compare_sharded(matrix, g1_idx, g2_idx, ctx, L, paired=False, exact=False):
     """compare() with the table rows cut into one block per rank (rows are independent here): every rank tests its
     block, the per-row statistics cross the ranks as ONE packed block in ONE all-gather (distributed.stat_layout, padded to
-    the longest block), rank 0 corrects."""
+    the longest block), rank 0 corrects.  exact: the _exact call; its `exact` marks are not packed."""
     from . import distributed
     n = matrix.shape[0]
     lo, hi = L.row_block(n)
     rows_of = [b - a for a, b in (L.row_block(n, r) for r in range(L.world))]
     maxk = distributed.longest(rows_of)
-    res = (ctx.signedrank if paired else ctx.ranksum)(np.ascontiguousarray(matrix[lo:hi]), g1_idx, g2_idx)
+    res = row_test(ctx, paired, exact)(np.ascontiguousarray(matrix[lo:hi]), g1_idx, g2_idx)
     stats = {k: distributed.pad_rows(np.asarray(res[k], dt), maxk) for k, dt in RANKSUM_FIELDS}
     gathered = L.comm(ctx).allgather(distributed.pack_stats_host(stats, maxk))
     host = distributed.unpack_stats_host(gathered, maxk, L.world)
@@ -98,6 +113,11 @@ def add_parser(parser):
                         help="Matched samples: line i of -m1 is paired with line i of -m2 (MANIFEST order, not the "
                              "table order of the unpaired test) and the test is the Wilcoxon signed-rank test of the "
                              "pairs; same output columns (not part of the reference)")
+    parser.add_argument("--exact", action="store_true",
+                        help="Exact p-values for small sample sets: the conditional permutation distribution given the "
+                             "row's ties instead of the normal approximation, on rows that keep at most 32 values (with "
+                             "--paired: at most 31 non-zero differences).  Rows above these limits keep the asymptotic "
+                             "p-value, as R's wilcox.test does.  Not with -mx (not part of the reference)")
     parser.add_argument("-a", "--annotation", type=str, required=False, default="",
                         help="Optional GTF file to label known splice junctions and genes")
     parser.add_argument("-o", "--outputFile", type=str, required=True,
@@ -132,6 +152,9 @@ def run_with(args, ctx=None):
     g2 = samples_from_manifest(args.manifest2)
     more = [samples_from_manifest(m) for m in (getattr(args, "moreManifests", None) or [])]
     paired = bool(getattr(args, "paired", False))
+    exact = bool(getattr(args, "exact", False))
+    if exact and more:
+        refuse_exact("cannot be combined with -mx/--moreManifests (there is no exact Kruskal-Wallis test here)")
     if paired:
         if more:
             refuse("cannot be combined with -mx/--moreManifests (the signed-rank test compares two matched sets)")
@@ -150,9 +173,9 @@ def run_with(args, ctx=None):
         else:
             g1_idx, g2_idx = pair_idx if paired else (column_indices(g1, cols), column_indices(g2, cols))
             if L.world > 1:
-                keep, r = compare_sharded(matrix, g1_idx, g2_idx, ctx, L, paired)
+                keep, r = compare_sharded(matrix, g1_idx, g2_idx, ctx, L, paired, exact)
             else:
-                keep, r = compare(matrix, g1_idx, g2_idx, ctx, paired)
+                keep, r = compare(matrix, g1_idx, g2_idx, ctx, paired, exact)
     if not L.root:
         return                       # one set of output files: rank 0 writes the table
     # the library's multithreaded formatter (numpy str() of float32 / float64 per column, byte-identical to the

@@ -3,7 +3,8 @@
 // compaction of a row's selected columns, np.median of a sorted run, the 3-decimal PS key of a float and its float back,
 // the order-preserving bits of a float, the workgroup's bitonic network, the tie-run bounds of a sorted array, the median
 // search in the 16-bins-per-lane histograms of the counting kernels; and for the host the launch sizes of the
-// wave-per-chunk and row-per-workgroup kernels and the check of a column list (gram.hip takes only that).
+// wave-per-chunk and row-per-workgroup kernels and the check of a column list (gram.hip takes only that; exactrank.hip: K16
+// takes the PS key, the wave fence, the launch size and the check).
 // Every helper is inlined into the kernels that call it and the kernels themselves stay in their .hip files, so a change
 // to a helper here is a change to each kernel that uses it -- ranksum.hip's pairq and count kernels among them, whose
 // committed counter pass is stamped with the hash of ranksum.hip alone and will not notice.

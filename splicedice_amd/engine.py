@@ -21,6 +21,7 @@ def _c(a, dtype):
 PER_SET = "per set"
 RANKSUM_FIELDS = [("tested", np.uint8), ("p", np.float64), ("z", np.float64), ("med1", np.float32), ("med2", np.float32),
                   ("mean1", np.float32), ("mean2", np.float32), ("delta", np.float32)]       # (ranksum and signedrank)
+RANKSUM_EXACT_FIELDS = RANKSUM_FIELDS + [("exact", np.uint8)]                                # (the two --exact calls)
 KRUSKAL_FIELDS = [("tested", np.uint8), ("p", np.float64), ("h", np.float64), ("med", np.float32, PER_SET),
                   ("mean", np.float32, PER_SET), ("delta", np.float32)]
 SPEARMAN_FIELDS = [("tested", np.uint8), ("p", np.float64), ("rho", np.float64), ("n_kept", np.int32), ("med", np.float32),
@@ -343,6 +344,17 @@ class Context:
               "sdice_ranksum")
         return out
 
+    def ranksum_exact(self, ps, g1, g2):
+        """ranksum() with the exact conditional p-value on the rows that keep at most 32 values (include/sdice.h): the
+        same outputs + exact (1 where p is the exact value); every other field is ranksum()'s bit for bit."""
+        ps = _c(ps, np.float32)
+        n, s = ps.shape
+        g1, g2 = _c(g1, np.int32), _c(g2, np.int32)
+        out = _zeros(RANKSUM_EXACT_FIELDS, n)
+        check(self.lib.sdice_ranksum_exact(self.h, n, s, _ptr(ps), _ptr(g1), g1.size, _ptr(g2), g2.size,
+                                           *map(_ptr, out.values())), "sdice_ranksum_exact")
+        return out
+
     def kruskal(self, ps, sets):
         """scipy.stats.kruskal per row across the k column sets under the row rules of ranksum(); un-compacted outputs:
         tested, p, h [n], med, mean [k, n] (set-major), delta [n] = largest minus smallest set median."""
@@ -366,6 +378,19 @@ class Context:
         out = _zeros(RANKSUM_FIELDS, n)
         check(self.lib.sdice_signedrank(self.h, n, s, _ptr(ps), _ptr(a), _ptr(b), a.size, *map(_ptr, out.values())),
               "sdice_signedrank")
+        return out
+
+    def signedrank_exact(self, ps, a, b):
+        """signedrank() with the exact p-value on the rows with at most 31 non-zero differences (include/sdice.h): the
+        same outputs + exact; every other field is signedrank()'s bit for bit."""
+        ps = _c(ps, np.float32)
+        n, s = ps.shape
+        a, b = _c(a, np.int32), _c(b, np.int32)
+        if a.shape != b.shape or a.ndim != 1:
+            raise ValueError(f"signedrank_exact: the pair lists must be two vectors of one length, got {a.shape} and {b.shape}")
+        out = _zeros(RANKSUM_EXACT_FIELDS, n)
+        check(self.lib.sdice_signedrank_exact(self.h, n, s, _ptr(ps), _ptr(a), _ptr(b), a.size, *map(_ptr, out.values())),
+              "sdice_signedrank_exact")
         return out
 
     def spearman(self, ps, cols, x):
@@ -513,6 +538,21 @@ class Context:
                                             out["tested"].ptr, out["p"].ptr, out["z"].ptr if out.get("z") else None,
                                             out["med1"].ptr, out["med2"].ptr, out["mean1"].ptr, out["mean2"].ptr,
                                             out["delta"].ptr), "sdice_signedrank_dev")
+
+    def ranksum_exact_dev(self, d_ps, d_g1, d_g2, out):
+        """out: the device fields of RANKSUM_EXACT_FIELDS (z optional)"""
+        n, s = d_ps.shape
+        check(self.lib.sdice_ranksum_exact_dev(self.h, n, s, d_ps.ptr, d_g1.ptr, d_g1.shape[0], d_g2.ptr, d_g2.shape[0],
+                                               out["tested"].ptr, out["p"].ptr, out["z"].ptr if out.get("z") else None,
+                                               out["med1"].ptr, out["med2"].ptr, out["mean1"].ptr, out["mean2"].ptr,
+                                               out["delta"].ptr, out["exact"].ptr), "sdice_ranksum_exact_dev")
+
+    def signedrank_exact_dev(self, d_ps, d_a, d_b, out):
+        n, s = d_ps.shape
+        check(self.lib.sdice_signedrank_exact_dev(self.h, n, s, d_ps.ptr, d_a.ptr, d_b.ptr, d_a.shape[0],
+                                                  out["tested"].ptr, out["p"].ptr, out["z"].ptr if out.get("z") else None,
+                                                  out["med1"].ptr, out["med2"].ptr, out["mean1"].ptr, out["mean2"].ptr,
+                                                  out["delta"].ptr, out["exact"].ptr), "sdice_signedrank_exact_dev")
 
     def spearman_dev(self, d_ps, d_cols, d_xg, out):
         """d_cols, d_xg: the device copies of spearman_order()'s pair; out: device tested, p, (rho), n_kept, med, mean"""
