@@ -248,6 +248,42 @@ int sdice_signedrank_exact_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float
                                float* d_med1, float* d_med2, float* d_mean1, float* d_mean2, float* d_delta,
                                uint8_t* d_exact);
 
+/* ---- compare_sample_sets --strata: the rank-sum test stratified by batch (van Elteren's stratified Wilcoxon test; not
+ *      in the reference), per row under the row rules above.  What coin::wilcox_test(y ~ g | batch) computes.
+ *  g1[n1], g2[n2]: the column indices of the two groups as in sdice_ranksum; strat1[n1], strat2[n2]: the int32 stratum id
+ *  of each listed column, in [0, n_strata), parallel to g1 and g2.  1 <= n_strata <= 64, 1 <= n1, n2 <= 4096, a column
+ *  at most once over both lists; otherwise SDICE_ERR_ARG before any launch, outputs untouched, the reason in
+ *  sdice_last_error (the host call checks the index range, the stratum ids and the one-appearance rule, the _dev call
+ *  n1, n2, n_strata and n1 + n2 <= s).  Values are finite float32 or NaN.
+ *  Per row and stratum h: the values at the group-1 and at the group-2 columns of h with NaNs dropped, n1h and n2h kept,
+ *  N_h = n1h + n2h.  A stratum is informative when n1h >= 1 and n2h >= 1; any other stratum (one that holds samples of
+ *  one group only, or none after the NaN drop) contributes nothing.  Inside an informative stratum, over its N_h values
+ *  only: r2(v) = 2 #{x < v} + #{x == v} + 1 (twice the mid-rank, an integer; ties by float32 equality, -0.0 == +0.0),
+ *      D_h = sum of r2 over group 1 of h - n1h (N_h + 1)            (= 2 (W_h - E[W_h]))
+ *      T_h = sum of t^3 - t over the stratum's tie runs
+ *      d_h = D_h / (2 (N_h + 1))
+ *      V_h = n1h n2h (N_h^3 - N_h - T_h) / (12 N_h (N_h - 1) (N_h + 1)^2)
+ *  and over the strata z = sum d_h / sqrt(sum V_h), p = erfc(|z| / sqrt 2): weights 1 / (N_h + 1), the tie-corrected
+ *  variance, no continuity correction; z > 0 when group 1 is larger.  z and p do not depend on how the strata are
+ *  numbered (bit for bit), and swapping the groups gives -z and the same p.
+ *  With n1', n2' the kept counts summed over the informative strata the row is tested when n1' >= 3 and n2' >= 3;
+ *  otherwise every output slot is 0.  A tested row with sum V_h = 0 (every informative stratum fully tied) has z = 0,
+ *  p = 1.  With one stratum and no ties z is scipy.stats.ranksums'; with ties p is scipy.stats.mannwhitneyu(
+ *  use_continuity=False, method="asymptotic")'s, NOT sdice_ranksum's, which has no tie correction.
+ *  med1 / med2 / mean1 / mean2 are np.median / np.mean of ALL kept values of a group (every stratum, informative or not)
+ *  in the order of g1 / g2, delta = med1 - med2 in float32: on every row this call tests, bit for bit what sdice_ranksum
+ *  reports for the same lists.  p is as accurate as sdice_ranksum's.  z optional (NULL to skip). */
+int sdice_ranksum_strata(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps,
+                         const int32_t* g1, int32_t n1, const int32_t* g2, int32_t n2,
+                         const int32_t* strat1, const int32_t* strat2, int32_t n_strata,
+                         uint8_t* tested, double* p, double* z, float* med1, float* med2,
+                         float* mean1, float* mean2, float* delta);
+int sdice_ranksum_strata_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps,
+                             const int32_t* d_g1, int32_t n1, const int32_t* d_g2, int32_t n2,
+                             const int32_t* d_strat1, const int32_t* d_strat2, int32_t n_strata,
+                             uint8_t* d_tested, double* d_p, double* d_z, float* d_med1, float* d_med2,
+                             float* d_mean1, float* d_mean2, float* d_delta);
+
 /* ---- correlate: Spearman rank correlation of the PS values of m listed columns with one covariate value per listed
  *      column, per row scipy.stats.spearmanr(x_kept, ps_kept) under the row rules above (not in the reference).
  *  The covariate does not cross the ABI.  cols[m]: the columns sorted by covariate value, ties in table order; xg[m]: the

@@ -1,5 +1,5 @@
 """What the sub-commands share above the engine: engine_scope (who closes the context),
-refusal / refuse_multi_rank and columns_in_header (the checks before any GPU call), device_call / tested_rows (the device
+refusal / refuse_multi_rank, columns_in_header and read_labels (the checks before any GPU call), device_call / tested_rows (the device
 round trip of a per-row test), write_event_table, and the readers of the PS table, the manifests and the GTF."""
 import contextlib
 import sys
@@ -94,6 +94,23 @@ def samples_from_manifest(path):
     """First whitespace-separated token of every line (compareSampleSets.py:105-115)."""
     with open(path) as fin:
         return [line.split()[0] for line in fin]
+
+
+def read_labels(path, refuse):
+    """a label file, one `sample<TAB>label` per line (labels are arbitrary strings; blank lines are skipped) -> sample ->
+    the list of its labels in file order, so that the caller can tell a sample without a label from one with two;
+    refuse()s a line without a tab"""
+    labels = {}
+    with open(path) as fin:
+        for at, line in enumerate(fin, 1):
+            line = line.rstrip("\r\n")
+            if not line.strip():
+                continue
+            sample, tab, label = line.partition("\t")
+            if not tab:
+                refuse(f"line {at} of {path} is not `sample<TAB>label`")
+            labels.setdefault(sample, []).append(label)
+    return labels
 
 
 def table_header_names(path):

@@ -58,6 +58,8 @@ SIGNATURES = {
     "sdice_ranksum_exact_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32] + [vp] * 9,
     "sdice_signedrank_exact": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 9,
     "sdice_signedrank_exact_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 9,
+    "sdice_ranksum_strata": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32] + [vp] * 8,
+    "sdice_ranksum_strata_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32] + [vp] * 8,
     "sdice_spearman": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 6,
     "sdice_spearman_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 6,
     "sdice_sample_gram": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32] + [vp] * 4,

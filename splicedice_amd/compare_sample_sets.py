@@ -18,6 +18,11 @@ rows small enough for it -- at most 32 kept values in the two-set test, at most 
 (sdice_ranksum_exact, sdice_signedrank_exact); larger rows keep the asymptotic p-value, as R's wilcox.test does.  Same
 columns; not with -mx.
 
+A fourth: `--strata FILE` (lines `sample<TAB>label`) names the batch (centre, library prep, sex, ...) of every sample
+and the test becomes van Elteren's stratified rank-sum test (sdice_ranksum_strata): values are ranked inside their batch
+only and the batches' rank-sum deviations are added with weights 1 / (N_h + 1).  Same columns; not with --paired, -mx or
+--exact.  Unlike the plain test its variance carries the tie correction.
+
 On the GPU: the per-row loop :216-232 (NaN drop, <3 skip, scipy ranksums, medians, means)
 -> sdice_ranksum; multipletests(..., "fdr_bh") :235 -> sdice_bh over the tested rows.
 The GTF annotation columns are host string work, as in the reference.
@@ -32,6 +37,8 @@ from .engine import KRUSKAL_FIELDS, RANKSUM_EXACT_FIELDS, RANKSUM_FIELDS, Contex
 
 refuse = _cli.refusal("compare_sample_sets --paired")
 refuse_exact = _cli.refusal("compare_sample_sets --exact")
+refuse_strata = _cli.refusal("compare_sample_sets --strata")
+MAX_STRATA = 64                     # strata a call accepts (include/sdice.h)
 
 
 def row_test(ctx, paired, exact, dev=False):
@@ -66,6 +73,19 @@ def compare(matrix, g1_idx, g2_idx, ctx, paired=False, exact=False):
     out = {k: res[k][keep] for k in ("p", "med1", "med2", "mean1", "mean2", "delta")}
     out["corrected"] = ctx.bh(out["p"]) if keep.size else np.zeros(0)
     return keep, out
+
+
+def compare_strata(matrix, g1_idx, g2_idx, strat1, strat2, n_strata, ctx):
+    """compare_dev() for --strata: table, column lists and their stratum ids up, the stratified rank-sum test + BH over
+    the tested rows on resident vectors, per-row results down"""
+    if not matrix.shape[0]:
+        res = ctx.ranksum_strata(matrix, g1_idx, g2_idx, strat1, strat2)
+        out = {k: res[k][:0] for k in ("p", "z", "med1", "med2", "mean1", "mean2", "delta")}
+        return np.zeros(0, np.int64), {**out, "corrected": np.zeros(0)}
+    return _cli.tested_rows(ctx, dict(ps=(matrix, np.float32), g1=(g1_idx, np.int32), g2=(g2_idx, np.int32),
+                                      s1=(strat1, np.int32), s2=(strat2, np.int32)),
+                            field_shapes(RANKSUM_FIELDS, matrix.shape[0]),
+                            lambda d, out: ctx.ranksum_strata_dev(d["ps"], d["g1"], d["g2"], d["s1"], d["s2"], n_strata, out))
 
 
 def compare_sets_dev(matrix, set_idx, ctx):
@@ -118,6 +138,15 @@ def add_parser(parser):
                              "row's ties instead of the normal approximation, on rows that keep at most 32 values (with "
                              "--paired: at most 31 non-zero differences).  Rows above these limits keep the asymptotic "
                              "p-value, as R's wilcox.test does.  Not with -mx (not part of the reference)")
+    parser.add_argument("--strata", type=str, required=False, default=None, metavar="FILE",
+                        help="Batch labels, one `sample<TAB>label` per line: the test becomes van Elteren's stratified "
+                             "rank-sum test -- values are ranked inside their batch only and the batches are combined "
+                             "with weights 1/(N_h+1).  Every sample of -m1 / -m2 in the table needs exactly one label, at "
+                             "most 64 distinct labels; a batch with samples of one set only contributes nothing.  The "
+                             "variance carries the tie correction, which the plain test (scipy ranksums) lacks: with one "
+                             "batch the p-value is mannwhitneyu(use_continuity=False, method='asymptotic'), equal to "
+                             "the plain one only on rows without ties.  Not with --paired, -mx or --exact (not part of "
+                             "the reference)")
     parser.add_argument("-a", "--annotation", type=str, required=False, default="",
                         help="Optional GTF file to label known splice junctions and genes")
     parser.add_argument("-o", "--outputFile", type=str, required=True,
@@ -127,6 +156,32 @@ def add_parser(parser):
 MULTI_RANK_REFUSAL = ("compare_sample_sets: -mx/--moreManifests is not available under the multi-rank launcher "
                       "(the packed all-gather carries the two-set fields only); run it in one process.")
 
+STRATA_MULTI_RANK_REFUSAL = ("compare_sample_sets: --strata is not available under the multi-rank launcher "
+                             "(the sharded two-set path does not carry the stratum ids); run it in one process.")
+
+
+def strata_columns(g1, g2, header_names, labels):
+    """--strata: the manifests' sample lists, the table's column names and the label file's sample -> [labels] ->
+    (g1_idx, g2_idx in table order, strat1, strat2 int32 dense ids by first appearance, the number of strata); prints why
+    and exits with status 1 when a selected column has no label or more than one, sits in both sets, or the selected
+    columns carry more than MAX_STRATA labels"""
+    from .engine import strata_ids
+    cols = np.array(header_names)
+    g1_idx, g2_idx = column_indices(g1, cols), column_indices(g2, cols)
+    both = np.intersect1d(g1_idx, g2_idx)
+    if both.size:
+        refuse_strata(f"sample {header_names[both[0]]!r} is in both manifests; a column belongs to one set here")
+    chosen = []
+    for j in np.concatenate([g1_idx, g2_idx]).tolist():
+        found = labels.get(header_names[j], [])
+        if len(found) != 1:
+            refuse_strata(f"sample {header_names[j]!r} " + ("has no label in the strata file" if not found else
+                                                           f"has {len(found)} lines in the strata file"))
+        chosen.append(found[0])
+    ids, names = strata_ids(chosen)
+    if len(names) > MAX_STRATA:
+        refuse_strata(f"{len(names)} distinct labels among the selected samples, at most {MAX_STRATA} strata are supported")
+    return g1_idx, g2_idx, ids[:g1_idx.size].copy(), ids[g1_idx.size:].copy(), len(names)
 
 
 def paired_columns(g1, g2, header_names):
@@ -155,6 +210,15 @@ def run_with(args, ctx=None):
     exact = bool(getattr(args, "exact", False))
     if exact and more:
         refuse_exact("cannot be combined with -mx/--moreManifests (there is no exact Kruskal-Wallis test here)")
+    strata = getattr(args, "strata", None)
+    if strata:
+        for on, flag in ((paired, "--paired (the signed-rank test pairs samples one to one)"),
+                         (more, "-mx/--moreManifests (there is no stratified Kruskal-Wallis test here)"),
+                         (exact, "--exact (there is no exact stratified test here)")):
+            if on:
+                refuse_strata(f"cannot be combined with {flag}")
+        _cli.refuse_multi_rank(L, STRATA_MULTI_RANK_REFUSAL)
+        strat = strata_columns(g1, g2, table_header_names(args.psiSPLICEDICE), _cli.read_labels(strata, refuse_strata))
     if paired:
         if more:
             refuse("cannot be combined with -mx/--moreManifests (the signed-rank test compares two matched sets)")
@@ -167,7 +231,9 @@ def run_with(args, ctx=None):
     with _stages.stage("parse"):
         rows, cols, matrix = read_ps_table(args.psiSPLICEDICE, as_table=True)
     with _cli.engine_scope(ctx, lambda: Context(L.local_rank)) as ctx:
-        if more:
+        if strata:
+            keep, r = compare_strata(matrix, *strat, ctx)
+        elif more:
             # k >= 3 sets: Kruskal-Wallis per junction; columns event mean1..meank median1..mediank delta H p-value corrected
             keep, r = compare_sets_dev(matrix, [column_indices(g, cols) for g in [g1, g2] + more], ctx)
         else:

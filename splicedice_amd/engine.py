@@ -69,6 +69,14 @@ def kruskal_sets(sets, s=None):
     return np.ascontiguousarray(cols, dtype=np.int32), set_ptr
 
 
+def strata_ids(labels):
+    """arbitrary stratum labels (batch names, centres, ...) -> (int32 dense ids numbered by first appearance, the distinct
+    labels in that order): what ranksum_strata() takes as strat1 / strat2 once the two lists' labels are numbered together"""
+    where = {}
+    ids = np.array([where.setdefault(x, len(where)) for x in labels], dtype=np.int32)
+    return ids, list(where)
+
+
 def spearman_order(cols, x):
     """the listed columns and the covariate value of each as sdice_spearman takes them -> (cols int32 sorted by x, ties in
     the order given (a stable sort), xg int32: the dense tie-group id of each sorted column: xg[0] = 0, one more at every
@@ -355,6 +363,21 @@ class Context:
                                            *map(_ptr, out.values())), "sdice_ranksum_exact")
         return out
 
+    def ranksum_strata(self, ps, g1, g2, strat1, strat2):
+        """van Elteren's stratified rank-sum test per row (include/sdice.h): strat1 / strat2 are the dense stratum ids
+        (strata_ids) of the columns g1 / g2; the outputs of ranksum(), with medians and means that are ranksum()'s."""
+        ps = _c(ps, np.float32)
+        n, s = ps.shape
+        g1, g2, strat1, strat2 = (_c(v, np.int32).reshape(-1) for v in (g1, g2, strat1, strat2))
+        if g1.size != strat1.size or g2.size != strat2.size:
+            raise ValueError(f"ranksum_strata: one stratum id per listed column, got {g1.size} / {strat1.size} and "
+                             f"{g2.size} / {strat2.size}")
+        n_strata = int(max(strat1.max(initial=-1), strat2.max(initial=-1))) + 1
+        out = _zeros(RANKSUM_FIELDS, n)
+        check(self.lib.sdice_ranksum_strata(self.h, n, s, _ptr(ps), _ptr(g1), g1.size, _ptr(g2), g2.size, _ptr(strat1),
+                                            _ptr(strat2), n_strata, *map(_ptr, out.values())), "sdice_ranksum_strata")
+        return out
+
     def kruskal(self, ps, sets):
         """scipy.stats.kruskal per row across the k column sets under the row rules of ranksum(); un-compacted outputs:
         tested, p, h [n], med, mean [k, n] (set-major), delta [n] = largest minus smallest set median."""
@@ -531,6 +554,16 @@ class Context:
                                          out["tested"].ptr, out["p"].ptr, out["z"].ptr if out.get("z") else None,
                                          out["med1"].ptr, out["med2"].ptr, out["mean1"].ptr, out["mean2"].ptr,
                                          out["delta"].ptr), "sdice_ranksum_dev")
+
+    def ranksum_strata_dev(self, d_ps, d_g1, d_g2, d_strat1, d_strat2, n_strata, out):
+        """d_strat1, d_strat2: the device copies of the stratum ids of d_g1, d_g2 (checked by the caller: the host call
+        checks them, this one cannot); out: the device fields of RANKSUM_FIELDS (z optional)"""
+        n, s = d_ps.shape
+        check(self.lib.sdice_ranksum_strata_dev(self.h, n, s, d_ps.ptr, d_g1.ptr, d_g1.shape[0], d_g2.ptr, d_g2.shape[0],
+                                                d_strat1.ptr, d_strat2.ptr, int(n_strata),
+                                                out["tested"].ptr, out["p"].ptr, out["z"].ptr if out.get("z") else None,
+                                                out["med1"].ptr, out["med2"].ptr, out["mean1"].ptr, out["mean2"].ptr,
+                                                out["delta"].ptr), "sdice_ranksum_strata_dev")
 
     def signedrank_dev(self, d_ps, d_a, d_b, out):
         n, s = d_ps.shape
