@@ -39,26 +39,16 @@ constexpr int EX_SLOTS = 32;             // keys (and ranks) a group holds
 constexpr int EX_HEAD = 2 * EX_SLOTS;    // words in front of a group's table
 constexpr int EX_THREADS = 256;
 constexpr int EX_LDS_BYTES = 64 * 1024;
-constexpr uint32_t EX_PAD = 0xFFFFFFFFu;
 
-// order-preserving bits of a non-NaN float, either zero as +0.0, by integer operations only
+// order-preserving bits of a non-NaN float, either zero as +0.0, by integer operations only (on purpose not rowsum.h's
+// f32_ord, whose `v + 0.0f` a flush-to-zero mode could turn into 0)
 __device__ __forceinline__ uint32_t ex_ord(float v) {
     uint32_t b = __float_as_uint(v);
     if ((b << 1) == 0u) b = 0u;
     return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
 }
 
-// K13's sort key of a kept pair: (code << 1) | (d > 0), EX_PAD for a zero difference
-__device__ __forceinline__ uint32_t ex_pair_key(float x, float y, bool grid) {
-    if (grid) {
-        const int d = key_of_ps(x).key() - key_of_ps(y).key();
-        return d == 0 ? EX_PAD : (((uint32_t)(d < 0 ? -d : d) << 1) | (d > 0 ? 1u : 0u));
-    }
-    const float d = x - y;
-    return d == 0.0f ? EX_PAD : ((__float_as_uint(fabsf(d)) << 1) | (d > 0.0f ? 1u : 0u));
-}
-
-// the lane group of a thread
+// the lane group of a thread (its width is a run-time value of the launch: not rowsum.h's LaneGroup<P>)
 struct ExGroup {
     int G, gl, g0, grp;                  // lanes, lane in the group, the group's first lane in the wave, group in the workgroup
     unsigned long long mask;
@@ -202,12 +192,12 @@ __global__ void __launch_bounds__(EX_THREADS) exact_signedrank_kernel(const floa
         int np = 0;
         for (int q0 = 0; q0 < m; q0 += G) {
             const int q = q0 + g.gl;
-            uint32_t key = EX_PAD;
+            uint32_t key = PAD32;
             if (q < m) {
                 const float x = prow[a[q]], y = prow[b[q]];
-                if (x == x && y == y) key = ex_pair_key(x, y, grid);
+                if (x == x && y == y) key = pair_diff_key(x, y, grid);
             }
-            const bool valid = key != EX_PAD;
+            const bool valid = key != PAD32;
             const unsigned long long mk = g.vote(valid);
             const int pos = np + g.below(mk);
             if (valid && pos < EX_SLOTS) V[pos] = key;
@@ -329,27 +319,17 @@ extern "C" int sdice_ranksum_exact(sdice_ctx* ctx, int64_t n, int32_t s, const f
     for (int i = 0; i < n2; ++i) SD_ARG(g2[i] >= 0 && g2[i] < s, "g2 index out of range");
     SD_ARG(ps, "ps is NULL");
     HostStaging st(ctx);
-    float *d_ps, *df;
+    TwoSampleStaging res;
+    float* d_ps;
     int32_t *dg1, *dg2;
-    uint8_t* dt;             // tested, exact
-    double* dd;              // p, z
     SD_TRY(st.upload(&d_ps, ps, n * s));
     SD_TRY(st.upload(&dg1, g1, n1));
     SD_TRY(st.upload(&dg2, g2, n2));
-    SD_TRY(st.alloc(&dt, n * 2));
-    SD_TRY(st.alloc(&dd, n * 2));
-    SD_TRY(st.alloc(&df, n * 5));      // med1, med2, mean1, mean2, delta
-    SD_TRY(sdice_ranksum_exact_dev(ctx, n, s, d_ps, dg1, n1, dg2, n2, dt, dd, dd + n, df, df + n, df + 2 * n, df + 3 * n,
-                                   df + 4 * n, dt + n));
-    SD_TRY(st.download(tested, dt, n));
-    SD_TRY(st.download(exact, dt + n, n));
-    SD_TRY(st.download(p, dd, n));
-    if (z) SD_TRY(st.download(z, dd + n, n));
-    SD_TRY(st.download(med1, df, n));
-    SD_TRY(st.download(med2, df + n, n));
-    SD_TRY(st.download(mean1, df + 2 * n, n));
-    SD_TRY(st.download(mean2, df + 3 * n, n));
-    return st.download(delta, df + 4 * n, n);
+    SD_TRY(res.alloc(st, n, true));
+    const TwoSampleOut o = res.out();
+    SD_TRY(sdice_ranksum_exact_dev(ctx, n, s, d_ps, dg1, n1, dg2, n2, o.tested, o.p, o.z, o.med1, o.med2, o.mean1, o.mean2,
+                                   o.delta, res.exact()));
+    return res.download(st, {tested, p, z, med1, med2, mean1, mean2, delta}, exact);
 }
 
 extern "C" int sdice_signedrank_exact_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, const int32_t* d_a,
@@ -383,25 +363,15 @@ extern "C" int sdice_signedrank_exact(sdice_ctx* ctx, int64_t n, int32_t s, cons
     SD_ARG(tested && p && med1 && med2 && mean1 && mean2 && delta && exact, "NULL output");
     SD_ARG(ps, "ps is NULL");
     HostStaging st(ctx);
-    float *d_ps, *df;
+    TwoSampleStaging res;
+    float* d_ps;
     int32_t *da, *db;
-    uint8_t* dt;             // tested, exact
-    double* dd;              // p, z
     SD_TRY(st.upload(&d_ps, ps, n * s));
     SD_TRY(st.upload(&da, a, m));
     SD_TRY(st.upload(&db, b, m));
-    SD_TRY(st.alloc(&dt, n * 2));
-    SD_TRY(st.alloc(&dd, n * 2));
-    SD_TRY(st.alloc(&df, n * 5));      // med1, med2, mean1, mean2, delta
-    SD_TRY(sdice_signedrank_exact_dev(ctx, n, s, d_ps, da, db, m, dt, dd, dd + n, df, df + n, df + 2 * n, df + 3 * n, df + 4 * n,
-                                      dt + n));
-    SD_TRY(st.download(tested, dt, n));
-    SD_TRY(st.download(exact, dt + n, n));
-    SD_TRY(st.download(p, dd, n));
-    if (z) SD_TRY(st.download(z, dd + n, n));
-    SD_TRY(st.download(med1, df, n));
-    SD_TRY(st.download(med2, df + n, n));
-    SD_TRY(st.download(mean1, df + 2 * n, n));
-    SD_TRY(st.download(mean2, df + 3 * n, n));
-    return st.download(delta, df + 4 * n, n);
+    SD_TRY(res.alloc(st, n, true));
+    const TwoSampleOut o = res.out();
+    SD_TRY(sdice_signedrank_exact_dev(ctx, n, s, d_ps, da, db, m, o.tested, o.p, o.z, o.med1, o.med2, o.mean1, o.mean2, o.delta,
+                                      res.exact()));
+    return res.download(st, {tested, p, z, med1, med2, mean1, mean2, delta}, exact);
 }

@@ -36,16 +36,7 @@
 
 namespace {
 
-struct RsOut {
-    uint8_t* tested;
-    double* p;
-    double* z;
-    float* med1;
-    float* med2;
-    float* mean1;
-    float* mean2;
-    float* delta;
-};
+using RsOut = TwoSampleOut;          // (rowsum.h; the kernels here keep the name they were written with)
 
 // (2U, n1, n2) of a tested row travel to ranksum_finish_kernel in the bits of p[row] (0 = not tested): the double
 // precision tail (sqrt, divide, erfc) would otherwise set the VGPR budget of the kernel that found them
@@ -1237,15 +1228,7 @@ extern "C" int sdice_ranksum_dev(sdice_ctx* ctx, int64_t n, int32_t s, const flo
     SD_HIP(hipSetDevice(ctx->device));
     SD_TRY(ctx->arena.reset(ctx->stream));
     RsOut o{d_tested, d_p, d_z, d_med1, d_med2, d_mean1, d_mean2, d_delta};
-    if (n1 < 3 || n2 < 3) {
-        // no row can be tested (compareSampleSets.py:223)
-        SD_HIP(hipMemsetAsync(d_tested, 0, (size_t)n, ctx->stream));
-        SD_HIP(hipMemsetAsync(d_p, 0, (size_t)n * 8, ctx->stream));
-        if (d_z) SD_HIP(hipMemsetAsync(d_z, 0, (size_t)n * 8, ctx->stream));
-        float* f[5] = {d_med1, d_med2, d_mean1, d_mean2, d_delta};
-        for (auto q : f) SD_HIP(hipMemsetAsync(q, 0, (size_t)n * 4, ctx->stream));
-        return SDICE_OK;
-    }
+    if (n1 < 3 || n2 < 3) return zero_two_sample(ctx, n, o);         // no row can be tested (compareSampleSets.py:223)
     SD_ARG(d_ps, "ps is NULL");
     const int64_t variant = ctx->param(SD_P_RANKSUM_VARIANT);  // 0 auto, 1 lane, 2 block, 3 wave (sorting only), 4 lane pair, 5 counting + wave
     const bool lane_ok = n1 <= 64 && n2 <= 64;
@@ -1310,25 +1293,14 @@ extern "C" int sdice_ranksum(sdice_ctx* ctx, int64_t n, int32_t s, const float* 
     for (int i = 0; i < n1; ++i) SD_ARG(g1[i] >= 0 && g1[i] < s, "g1 index out of range");
     for (int i = 0; i < n2; ++i) SD_ARG(g2[i] >= 0 && g2[i] < s, "g2 index out of range");
     HostStaging st(ctx);
-    float *d_ps, *df;
+    TwoSampleStaging res;
+    float* d_ps;
     int32_t *dg1, *dg2;
-    uint8_t* dt;
-    double *dp, *dz;
     SD_TRY(st.upload(&d_ps, ps, n * s));
     SD_TRY(st.upload(&dg1, g1, n1));
     SD_TRY(st.upload(&dg2, g2, n2));
-    SD_TRY(st.alloc(&dt, n));
-    SD_TRY(st.alloc(&dp, n));
-    SD_TRY(st.alloc(&dz, n));
-    SD_TRY(st.alloc(&df, n * 5));      // med1, med2, mean1, mean2, delta
-    SD_TRY(sdice_ranksum_dev(ctx, n, s, d_ps, dg1, n1, dg2, n2, dt, dp, dz, df, df + n, df + 2 * n, df + 3 * n,
-                             df + 4 * n));
-    SD_TRY(st.download(tested, dt, n));
-    SD_TRY(st.download(p, dp, n));
-    if (z) SD_TRY(st.download(z, dz, n));
-    SD_TRY(st.download(med1, df, n));
-    SD_TRY(st.download(med2, df + n, n));
-    SD_TRY(st.download(mean1, df + 2 * n, n));
-    SD_TRY(st.download(mean2, df + 3 * n, n));
-    return st.download(delta, df + 4 * n, n);
+    SD_TRY(res.alloc(st, n));
+    const RsOut o = res.out();
+    SD_TRY(sdice_ranksum_dev(ctx, n, s, d_ps, dg1, n1, dg2, n2, o.tested, o.p, o.z, o.med1, o.med2, o.mean1, o.mean2, o.delta));
+    return res.download(st, {tested, p, z, med1, med2, mean1, mean2, delta});
 }

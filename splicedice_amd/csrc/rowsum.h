@@ -1,10 +1,24 @@
-// Per-row device helpers that the rank tests share (ranksum.hip: K5, kruskal.hip: K12, signedrank.hip: K13, spearman.hip: K14): numpy's float32 pairwise
-// summation reproduced operation for operation (by a block, by a wave and by a lane group), the ordered NaN-dropping
-// compaction of a row's selected columns, np.median of a sorted run, the 3-decimal PS key of a float and its float back,
-// the order-preserving bits of a float, the workgroup's bitonic network, the tie-run bounds of a sorted array, the median
-// search in the 16-bins-per-lane histograms of the counting kernels; and for the host the launch sizes of the
-// wave-per-chunk and row-per-workgroup kernels and the check of a column list (gram.hip takes only that; exactrank.hip: K16
-// takes the PS key, the wave fence, the launch size and the check).
+// Per-row helpers that the rank tests share.  Device: numpy's float32 pairwise summation reproduced operation for
+// operation (by a block, by a wave and by a lane group), the ordered NaN-dropping compaction of a row's selected columns,
+// np.median of a sorted run, the 3-decimal PS key of a float and its float back, the order-preserving bits of a float, the
+// lane groups with their sums, bitonic sort and median, the key of a signed-rank difference, the workgroup's bitonic
+// network, the tie-run bounds of a sorted array, the median search in the 16-bins-per-lane histograms of the counting
+// kernels, the stores of a two-sample row.  Host: the eight output pointers of the two-sample tests, their "no row can be
+// tested" block and their staging for a host entry point, the launch sizes of the wave-per-chunk and row-per-workgroup
+// kernels, the check of a column list.  What each file takes:
+//   ranksum.hip (K5)      PsKey, median_sorted, block_compact, the pairwise sums, find_bin, lanes_below; TwoSampleOut (as
+//                         RsOut), zero_two_sample, TwoSampleStaging
+//   kruskal.hip (K12)     as ranksum.hip's kernels + f32_ord, median_of_ord, block_bitonic
+//   signedrank.hip (K13)  PsKey, f32_ord, LaneGroup, group_add / group_sum / group_sort / group_median, pair_diff_key,
+//                         block_compact_by, block_pairwise_sum, block_bitonic, run_bounds, median_of_ord, store_two_sample,
+//                         the launch sizes, check_columns; TwoSampleOut, zero_two_sample, TwoSampleStaging
+//   spearman.hip (K14)    PsKey, f32_ord, LaneGroup and its sums, the block's compaction, sum, network and run bounds, the
+//                         launch sizes, check_columns
+//   gram.hip              check_columns
+//   exactrank.hip (K16)   PsKey, pair_diff_key, SD_WAVE_SYNC, row_launch_blocks, check_columns; TwoSampleStaging
+//   strata.hip (K17)      PsKey, f32_ord, LaneGroup, group_add / group_sum / group_sort / group_median, block_compact,
+//                         block_pairwise_sum, block_bitonic, run_bounds, median_of_ord, store_two_sample, the launch sizes;
+//                         TwoSampleOut, zero_two_sample, TwoSampleStaging
 // Every helper is inlined into the kernels that call it and the kernels themselves stay in their .hip files, so a change
 // to a helper here is a change to each kernel that uses it -- ranksum.hip's pairq and count kernels among them, whose
 // committed counter pass is stamped with the hash of ranksum.hip alone and will not notice.
@@ -21,6 +35,32 @@
     } while (0)
 
 namespace {
+
+// The outputs of a two-sample test (ranksum.hip, signedrank.hip, strata.hip and, with `exact` beside them, exactrank.hip):
+// [n] each, device pointers in a kernel's argument, host or device pointers on the host
+struct TwoSampleOut {
+    uint8_t* tested;
+    double* p;
+    double* z;       // may be NULL
+    float* med1;
+    float* med2;
+    float* mean1;
+    float* mean2;
+    float* delta;
+};
+
+// the stores of a row: the fields of an untested row are 0 (p and z are the caller's), delta = med1 - med2
+__device__ __forceinline__ void store_two_sample(const TwoSampleOut& o, int64_t row, bool tested, double p, double z, float med1,
+                                                 float med2, float mean1, float mean2) {
+    o.tested[row] = tested ? 1 : 0;
+    o.p[row] = p;
+    if (o.z) o.z[row] = z;
+    o.med1[row] = tested ? med1 : 0.f;
+    o.med2[row] = tested ? med2 : 0.f;
+    o.mean1[row] = tested ? mean1 : 0.f;
+    o.mean2[row] = tested ? mean2 : 0.f;
+    o.delta[row] = tested ? med1 - med2 : 0.f;
+}
 
 __device__ __forceinline__ float median_sorted(const float* a, int nv) {
     // np.median: odd -> middle; even -> np.mean of the two middle values in float32
@@ -231,6 +271,21 @@ __device__ __forceinline__ float median_of_ord(const T* K, int nv) {
     return (nv & 1) ? v1 : (f32_unord((uint32_t)K[h - 1]) + v1) / 2.0f;
 }
 
+// what pads a sort of 32-bit keys: above every f32_ord and every key below
+constexpr uint32_t PAD32 = 0xFFFFFFFFu;
+
+// Sort key of a kept pair (x, y) of the signed-rank test (signedrank.hip's file comment): (code << 1) | (d > 0), code =
+// |key_x - key_y| on a row of 3-decimal PS values (`grid`), else the bits of |x - y|; PAD32 for a zero difference.
+// signedrank.hip ranks by it for z and exactrank.hip for the exact p: one function, so both see the same ranks.
+__device__ __forceinline__ uint32_t pair_diff_key(float x, float y, bool grid) {
+    if (grid) {
+        const int d = key_of_ps(x).key() - key_of_ps(y).key();
+        return d == 0 ? PAD32 : (((uint32_t)(d < 0 ? -d : d) << 1) | (d > 0 ? 1u : 0u));
+    }
+    const float d = x - y;
+    return d == 0.0f ? PAD32 : ((__float_as_uint(fabsf(d)) << 1) | (d > 0.0f ? 1u : 0u));
+}
+
 // ---- lane groups: P lanes (a power of two) own a row, 64 / P rows side by side in a wave, a pass of the chunk loop takes
 // the rows r0 .. r0 + R of the chunk and lane i of the wave keeps what the chunk's i-th row came to
 template <int P>
@@ -248,6 +303,31 @@ __device__ __forceinline__ int group_add(int v) {
 #pragma unroll
     for (int ofs = 1; ofs < P; ofs <<= 1) v += __shfl_xor(v, ofs);
     return v;
+}
+
+// ascending bitonic sort of one value per lane (gl = lane in the group) inside aligned groups of P lanes
+template <int P, class T>
+__device__ __forceinline__ T group_sort(T v, int gl) {
+#pragma unroll
+    for (int k = 2; k <= P; k <<= 1) {
+#pragma unroll
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            const T other = __shfl_xor(v, j);
+            const bool upper = (gl & j) != 0;
+            const bool asc = (gl & k) == 0;              // k == P: ascending everywhere
+            const T lo = v < other ? v : other, hi = v < other ? other : v;
+            v = (asc != upper) ? lo : hi;
+        }
+    }
+    return v;
+}
+
+// np.median of the group's nv sorted order-preserving values (lane g0 + i holds the i-th smallest)
+__device__ __forceinline__ float group_median(uint32_t sorted, int g0, int nv) {
+    const int h = nv >> 1;
+    const float v1 = f32_unord(__shfl(sorted, g0 + h));
+    const float v0 = f32_unord(__shfl(sorted, g0 + (h > 0 ? h - 1 : 0)));
+    return (nv & 1) ? v1 : (v0 + v1) / 2.0f;
 }
 
 // numpy pairwise_sum of A[0..nv), nv <= 64 (one leaf), by a group of P >= 8 lanes, every lane of the group gets it: for
@@ -353,6 +433,49 @@ inline int next_pow2(int v, int from) {
     while (from < v) from <<= 1;
     return from;
 }
+
+// Host: "no row can be tested" -- every field of the n rows is 0, queued on the context's stream
+inline int zero_two_sample(sdice_ctx* ctx, int64_t n, const TwoSampleOut& o) {
+    SD_HIP(hipMemsetAsync(o.tested, 0, (size_t)n, ctx->stream));
+    SD_HIP(hipMemsetAsync(o.p, 0, (size_t)n * 8, ctx->stream));
+    if (o.z) SD_HIP(hipMemsetAsync(o.z, 0, (size_t)n * 8, ctx->stream));
+    for (float* q : {o.med1, o.med2, o.mean1, o.mean2, o.delta}) SD_HIP(hipMemsetAsync(q, 0, (size_t)n * 4, ctx->stream));
+    return SDICE_OK;
+}
+
+// Host: the device copies of a host entry point's two-sample outputs, three blocks of the caller's HostStaging: tested
+// (+ exact), p and z, the five floats
+class TwoSampleStaging {
+  public:
+    int alloc(HostStaging& st, int64_t n, bool with_exact = false) {
+        n_ = n;
+        SD_TRY(st.alloc(&dt_, with_exact ? n * 2 : n));
+        SD_TRY(st.alloc(&dd_, n * 2));
+        return st.alloc(&df_, n * 5);
+    }
+    // what the _dev call writes
+    TwoSampleOut out() const { return {dt_, dd_, dd_ + n_, df_, df_ + n_, df_ + 2 * n_, df_ + 3 * n_, df_ + 4 * n_}; }
+    uint8_t* exact() const { return dt_ + n_; }
+    // synchronous copies into the caller's arrays; h.z and exact may be NULL
+    int download(HostStaging& st, const TwoSampleOut& h, uint8_t* exact = nullptr) const {
+        const TwoSampleOut d = out();
+        SD_TRY(st.download(h.tested, d.tested, n_));
+        if (exact) SD_TRY(st.download(exact, dt_ + n_, n_));
+        SD_TRY(st.download(h.p, d.p, n_));
+        if (h.z) SD_TRY(st.download(h.z, d.z, n_));
+        SD_TRY(st.download(h.med1, d.med1, n_));
+        SD_TRY(st.download(h.med2, d.med2, n_));
+        SD_TRY(st.download(h.mean1, d.mean1, n_));
+        SD_TRY(st.download(h.mean2, d.mean2, n_));
+        return st.download(h.delta, d.delta, n_);
+    }
+
+  private:
+    int64_t n_ = 0;
+    uint8_t* dt_ = nullptr;
+    double* dd_ = nullptr;
+    float* df_ = nullptr;
+};
 
 // Host: every one of the m entries of each list is a column of the table (0 .. s) and no column is listed twice, in one
 // list or two; `fn` is the entry point the error names, with the wording it has always had

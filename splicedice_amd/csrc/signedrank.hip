@@ -36,8 +36,10 @@
 // (A wave-per-row kernel with several elements per lane for 65..1024 pairs was left out: the block kernel computes the
 // same thing and paired cohorts of that size are rare.)
 //
-// rowsum.h: PsKey, the order bits of a float, the lane groups with their sums, the block's compaction, pairwise sum,
-// bitonic network and run bounds, the launch sizes and the column check; dd.h: the double-double arithmetic.
+// rowsum.h: PsKey, the order bits of a float, the key of a difference (pair_diff_key, exactrank.hip's too), the lane groups
+// with their sums, sort and median, the block's compaction, pairwise sum, bitonic network and run bounds, the stores of a
+// row, the output pointers with their zeroing and staging, the launch sizes and the column check; dd.h: the double-double
+// arithmetic.
 #include "common.h"
 #include <math.h>
 #include "rowsum.h"
@@ -48,28 +50,6 @@ namespace {
 constexpr int SR_MAX_PAIRS = 4096;
 constexpr int SR_GROUP_MAX = 64;         // pairs the lane-group kernel takes
 constexpr int SR_LEAF_MAX = 64;          // leaves of numpy's pairwise recursion over 4096 values (PW_DEPTH levels)
-constexpr uint32_t SR_PAD = 0xFFFFFFFFu;
-
-struct SrOut {
-    uint8_t* tested;
-    double* p;
-    double* z;       // may be NULL
-    float* med1;
-    float* med2;
-    float* mean1;
-    float* mean2;
-    float* delta;
-};
-
-// sort key of a kept pair (see the file comment); SR_PAD for a zero difference
-__device__ __forceinline__ uint32_t sr_key(float x, float y, bool grid) {
-    if (grid) {
-        const int d = key_of_ps(x).key() - key_of_ps(y).key();
-        return d == 0 ? SR_PAD : (((uint32_t)(d < 0 ? -d : d) << 1) | (d > 0 ? 1u : 0u));
-    }
-    const float d = x - y;
-    return d == 0.0f ? SR_PAD : ((__float_as_uint(fabsf(d)) << 1) | (d > 0.0f ? 1u : 0u));
-}
 
 // ---- p where most rows are (p >= 2.2e-5): erfc in double-double arithmetic, so that the float64 that comes out is the
 // correctly rounded one (the library erfc is an ulp or two off, which shows in the last printed digit of the table).
@@ -188,35 +168,10 @@ __device__ __forceinline__ void sr_finish(int np, long long w2, long long tie, d
 }
 
 // ------------------------------------------------------------------ lane-group path: P lanes per row
-// ascending bitonic sort of one value per lane inside aligned groups of P lanes
-template <int P>
-__device__ __forceinline__ uint32_t sr_group_sort(uint32_t v, int gl) {
-#pragma unroll
-    for (int k = 2; k <= P; k <<= 1) {
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const uint32_t other = __shfl_xor(v, j);
-            const bool upper = (gl & j) != 0;
-            const bool asc = (gl & k) == 0;              // k == P: ascending everywhere
-            const uint32_t lo = min(v, other), hi = max(v, other);
-            v = (asc != upper) ? lo : hi;
-        }
-    }
-    return v;
-}
-
-// np.median of the group's nv sorted order-preserving values (lane g0 + i holds the i-th smallest)
-__device__ __forceinline__ float sr_group_median(uint32_t sorted, int g0, int nv) {
-    const int h = nv >> 1;
-    const float v1 = f32_unord(__shfl(sorted, g0 + h));
-    const float v0 = f32_unord(__shfl(sorted, g0 + (h > 0 ? h - 1 : 0)));
-    return (nv & 1) ? v1 : (v0 + v1) / 2.0f;
-}
-
 template <int P>
 __global__ void __launch_bounds__(256) signedrank_group_kernel(const float* __restrict__ ps, int64_t n, int s,
                                                                const int32_t* __restrict__ a, const int32_t* __restrict__ b,
-                                                               int m, int ch, SrOut o) {
+                                                               int m, int ch, TwoSampleOut o) {
     using G = LaneGroup<P>;                              // G::R rows side by side in a wave
     __shared__ float cx[4][64], cy[4][64];               // the kept values of the wave's rows, compacted, in pair order
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
@@ -255,12 +210,12 @@ __global__ void __launch_bounds__(256) signedrank_group_kernel(const float* __re
         const float sum1 = 0.0f + group_sum(X, nv, gl);      // np.sum starts from the identity 0: -0.0 values sum to +0.0
         const float sum2 = 0.0f + group_sum(Y, nv, gl);
         // ---- the medians
-        const uint32_t ox = sr_group_sort<P>(kept ? f32_ord(x) : SR_PAD, gl);
-        const uint32_t oy = sr_group_sort<P>(kept ? f32_ord(y) : SR_PAD, gl);
-        const float med1 = sr_group_median(ox, g0, nv), med2 = sr_group_median(oy, g0, nv);
+        const uint32_t ox = group_sort<P, uint32_t>(kept ? f32_ord(x) : PAD32, gl);
+        const uint32_t oy = group_sort<P, uint32_t>(kept ? f32_ord(y) : PAD32, gl);
+        const float med1 = group_median(ox, g0, nv), med2 = group_median(oy, g0, nv);
         // ---- the ranks of |d|
-        const uint32_t key = sr_group_sort<P>(kept ? sr_key(x, y, grid) : SR_PAD, gl);
-        const bool valid = key != SR_PAD;
+        const uint32_t key = group_sort<P, uint32_t>(kept ? pair_diff_key(x, y, grid) : PAD32, gl);
+        const bool valid = key != PAD32;
         const int np = __popcll((__ballot(valid) >> g0) & G::MASK);
         const uint32_t prev = __shfl_up(key, 1);
         const bool start = valid && (gl == 0 || (prev >> 1) != (key >> 1));
@@ -291,14 +246,7 @@ __global__ void __launch_bounds__(256) signedrank_group_kernel(const float* __re
         const bool tested = s_pack < 0;
         double z = 0.0, p = 0.0;
         if (tested) sr_finish(s_pack & 0xff, (long long)((s_pack >> 8) & 0x7fffff), (long long)s_tie, z, p);
-        o.tested[row] = tested ? 1 : 0;
-        o.p[row] = p;
-        if (o.z) o.z[row] = z;
-        o.med1[row] = tested ? s_med1 : 0.f;
-        o.med2[row] = tested ? s_med2 : 0.f;
-        o.mean1[row] = tested ? s_mean1 : 0.f;
-        o.mean2[row] = tested ? s_mean2 : 0.f;
-        o.delta[row] = tested ? s_med1 - s_med2 : 0.f;
+        store_two_sample(o, row, tested, p, z, s_med1, s_med2, s_mean1, s_mean2);
       }
     }
 }
@@ -360,7 +308,7 @@ __device__ __forceinline__ float sr_regs_sum(const float (&v)[P], int nv) {
 template <int P>
 __global__ void __launch_bounds__(256) signedrank_lane_kernel(const float* __restrict__ ps, int64_t n, int s,
                                                               const int32_t* __restrict__ a, const int32_t* __restrict__ b,
-                                                              int m, SrOut o) {
+                                                              int m, TwoSampleOut o) {
     for (int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; row < n; row += (int64_t)gridDim.x * blockDim.x) {
         const float* prow = ps + row * s;
         float x[P], y[P];
@@ -386,9 +334,9 @@ __global__ void __launch_bounds__(256) signedrank_lane_kernel(const float* __res
 #pragma unroll
         for (int q = 0; q < P; ++q) {
             const bool kept = x[q] == x[q];
-            ux[q] = kept ? f32_ord(x[q]) : SR_PAD;
-            uy[q] = kept ? f32_ord(y[q]) : SR_PAD;
-            kd[q] = kept ? sr_key(x[q], y[q], grid) : SR_PAD;
+            ux[q] = kept ? f32_ord(x[q]) : PAD32;
+            uy[q] = kept ? f32_ord(y[q]) : PAD32;
+            kd[q] = kept ? pair_diff_key(x[q], y[q], grid) : PAD32;
         }
         sr_sort_regs<P>(ux);
         sr_sort_regs<P>(uy);
@@ -396,10 +344,10 @@ __global__ void __launch_bounds__(256) signedrank_lane_kernel(const float* __res
         const float med1 = sr_regs_median<P>(ux, nv), med2 = sr_regs_median<P>(uy, nv);
         // tie runs of the sorted keys, one after another: a run [first, i] with cp positive members adds cp r2 to W2
         int np = 0, w2 = 0, tie = 0, first = 0, cp = 0;
-        uint32_t prev = SR_PAD;                          // no code is this large
+        uint32_t prev = PAD32;                          // no code is this large
 #pragma unroll
         for (int i = 0; i < P; ++i) {
-            if (kd[i] != SR_PAD) {
+            if (kd[i] != PAD32) {
                 const uint32_t code = kd[i] >> 1;
                 if (code != prev) { first = i; cp = 0; }
                 prev = code;
@@ -417,21 +365,14 @@ __global__ void __launch_bounds__(256) signedrank_lane_kernel(const float* __res
         const bool tested = nv >= 3;
         double z = 0.0, p = 0.0;
         if (tested) sr_finish(np, (long long)w2, (long long)tie, z, p);
-        o.tested[row] = tested ? 1 : 0;
-        o.p[row] = p;
-        if (o.z) o.z[row] = z;
-        o.med1[row] = tested ? med1 : 0.f;
-        o.med2[row] = tested ? med2 : 0.f;
-        o.mean1[row] = tested ? sum1 / (float)nv : 0.f;
-        o.mean2[row] = tested ? sum2 / (float)nv : 0.f;
-        o.delta[row] = tested ? med1 - med2 : 0.f;
+        store_two_sample(o, row, tested, p, z, med1, med2, sum1 / (float)nv, sum2 / (float)nv);
     }
 }
 
 // ------------------------------------------------------------------ general path: one workgroup per row
 __global__ void __launch_bounds__(RB_THREADS) signedrank_block_kernel(const float* __restrict__ ps, int64_t n, int s,
                                                                       const int32_t* __restrict__ a,
-                                                                      const int32_t* __restrict__ b, int m, int P, SrOut o) {
+                                                                      const int32_t* __restrict__ b, int m, int P, TwoSampleOut o) {
     extern __shared__ __align__(16) unsigned char smems[];
     uint32_t* KX = reinterpret_cast<uint32_t*>(smems);         // [P] side 1: first the compacted floats, then their order bits
     uint32_t* KY = KX + P;                                      // [P] side 2
@@ -458,11 +399,7 @@ __global__ void __launch_bounds__(RB_THREADS) signedrank_block_kernel(const floa
                 if (valid) { FX[pos] = v.x; FY[pos] = v.y; }
             });
         if (nv < 3) {                                           // block-uniform
-            if (tid == 0) {
-                o.tested[row] = 0; o.p[row] = 0.0;
-                if (o.z) o.z[row] = 0.0;
-                o.med1[row] = 0.f; o.med2[row] = 0.f; o.mean1[row] = 0.f; o.mean2[row] = 0.f; o.delta[row] = 0.f;
-            }
+            if (tid == 0) store_two_sample(o, row, false, 0.0, 0.0, 0.f, 0.f, 0.f, 0.f);
             continue;                                           // (the compaction ended with a barrier)
         }
         // np.sum: the identity 0 plus the pairwise tree
@@ -473,10 +410,10 @@ __global__ void __launch_bounds__(RB_THREADS) signedrank_block_kernel(const floa
         for (int i = tid; i < nv; i += RB_THREADS) off |= !(key_of_ps(FX[i]).exact() && key_of_ps(FY[i]).exact());
         const bool grid = __syncthreads_or(off) == 0;
         for (int i = tid; i < P; i += RB_THREADS) {
-            uint32_t kx = SR_PAD, ky = SR_PAD, kd = SR_PAD;
+            uint32_t kx = PAD32, ky = PAD32, kd = PAD32;
             if (i < nv) {
                 const float x = FX[i], y = FY[i];
-                kx = f32_ord(x); ky = f32_ord(y); kd = sr_key(x, y, grid);
+                kx = f32_ord(x); ky = f32_ord(y); kd = pair_diff_key(x, y, grid);
             }
             KX[i] = kx; KY[i] = ky; KD[i] = kd;
         }
@@ -494,7 +431,7 @@ __global__ void __launch_bounds__(RB_THREADS) signedrank_block_kernel(const floa
         int np = 0;                                             // first padding key: the number of non-zero differences
         {
             int hi = nv;
-            while (np < hi) { const int mid = (np + hi) >> 1; if (KD[mid] != SR_PAD) np = mid + 1; else hi = mid; }
+            while (np < hi) { const int mid = (np + hi) >> 1; if (KD[mid] != PAD32) np = mid + 1; else hi = mid; }
         }
         // ---- ranks
         long long w2 = 0, tie = 0;
@@ -521,18 +458,14 @@ __global__ void __launch_bounds__(RB_THREADS) signedrank_block_kernel(const floa
             const float med1 = median_of_ord(KX, nv), med2 = median_of_ord(KY, nv);    // np.median on float32
             double z, p;
             sr_finish(np, (long long)accS[0], (long long)accS[1], z, p);
-            o.tested[row] = 1; o.p[row] = p;
-            if (o.z) o.z[row] = z;
-            o.med1[row] = med1; o.med2[row] = med2;
-            o.mean1[row] = sum1 / (float)nv; o.mean2[row] = sum2 / (float)nv;
-            o.delta[row] = med1 - med2;
+            store_two_sample(o, row, true, p, z, med1, med2, sum1 / (float)nv, sum2 / (float)nv);
         }
         __syncthreads();           // thread 0 has read the row's LDS
     }
 }
 
 template <int P>
-int sr_launch_group(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* d_a, const int32_t* d_b, int m, SrOut o) {
+int sr_launch_group(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* d_a, const int32_t* d_b, int m, TwoSampleOut o) {
     const int waves = 4;
     const int ch = rows_per_chunk(ctx->n_cu, n);
     const int64_t blocks = wave_launch_blocks(ctx, n, ch, waves);
@@ -542,7 +475,7 @@ int sr_launch_group(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const i
 }
 
 template <int P>
-int sr_launch_lane(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* d_a, const int32_t* d_b, int m, SrOut o) {
+int sr_launch_lane(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* d_a, const int32_t* d_b, int m, TwoSampleOut o) {
     const int64_t blocks = row_launch_blocks(ctx, sd_ceil_div(n, 256));
     SD_LAUNCH(ctx, "signedrank_lane_kernel", (signedrank_lane_kernel<P>), dim3((unsigned)blocks), dim3(256), 0, d_ps, n, s,
               d_a, d_b, m, o);
@@ -572,17 +505,9 @@ extern "C" int sdice_signedrank_dev(sdice_ctx* ctx, int64_t n, int32_t s, const 
     SD_ARG(d_ps && d_a && d_b, "NULL input");
     SD_HIP(hipSetDevice(ctx->device));
     SD_TRY(ctx->arena.reset(ctx->stream));
-    SrOut o{d_tested, d_p, d_z, d_med1, d_med2, d_mean1, d_mean2, d_delta};
-    if (m < 3) {
-        // no row can be tested
-        SD_HIP(hipMemsetAsync(d_tested, 0, (size_t)n, ctx->stream));
-        SD_HIP(hipMemsetAsync(d_p, 0, (size_t)n * 8, ctx->stream));
-        if (d_z) SD_HIP(hipMemsetAsync(d_z, 0, (size_t)n * 8, ctx->stream));
-        float* f[5] = {d_med1, d_med2, d_mean1, d_mean2, d_delta};
-        for (auto q : f) SD_HIP(hipMemsetAsync(q, 0, (size_t)n * 4, ctx->stream));
-        return SDICE_OK;
-    }
-    if (m <= SR_GROUP_MAX) {
+    TwoSampleOut o{d_tested, d_p, d_z, d_med1, d_med2, d_mean1, d_mean2, d_delta};
+    if (m < 3) return zero_two_sample(ctx, n, o);            // no row can be tested
+    if (m <= SR_GROUP_MAX) {                                   // (a ladder per file: the launches differ in their arguments)
         if (m <= 4) return sr_launch_lane<4>(ctx, d_ps, n, s, d_a, d_b, m, o);
         if (m <= 8) return sr_launch_lane<8>(ctx, d_ps, n, s, d_a, d_b, m, o);
         if (m <= 16) return sr_launch_group<16>(ctx, d_ps, n, s, d_a, d_b, m, o);
@@ -611,23 +536,14 @@ extern "C" int sdice_signedrank(sdice_ctx* ctx, int64_t n, int32_t s, const floa
     SD_ARG(tested && p && med1 && med2 && mean1 && mean2 && delta, "NULL output");
     SD_ARG(ps, "ps is NULL");
     HostStaging st(ctx);
-    float *d_ps, *df;
+    TwoSampleStaging res;
+    float* d_ps;
     int32_t *da, *db;
-    uint8_t* dt;
-    double* dd;
     SD_TRY(st.upload(&d_ps, ps, n * s));
     SD_TRY(st.upload(&da, a, m));
     SD_TRY(st.upload(&db, b, m));
-    SD_TRY(st.alloc(&dt, n));
-    SD_TRY(st.alloc(&dd, n * 2));      // p, z
-    SD_TRY(st.alloc(&df, n * 5));      // med1, med2, mean1, mean2, delta
-    SD_TRY(sdice_signedrank_dev(ctx, n, s, d_ps, da, db, m, dt, dd, dd + n, df, df + n, df + 2 * n, df + 3 * n, df + 4 * n));
-    SD_TRY(st.download(tested, dt, n));
-    SD_TRY(st.download(p, dd, n));
-    if (z) SD_TRY(st.download(z, dd + n, n));
-    SD_TRY(st.download(med1, df, n));
-    SD_TRY(st.download(med2, df + n, n));
-    SD_TRY(st.download(mean1, df + 2 * n, n));
-    SD_TRY(st.download(mean2, df + 3 * n, n));
-    return st.download(delta, df + 4 * n, n);
+    SD_TRY(res.alloc(st, n));
+    const TwoSampleOut o = res.out();
+    SD_TRY(sdice_signedrank_dev(ctx, n, s, d_ps, da, db, m, o.tested, o.p, o.z, o.med1, o.med2, o.mean1, o.mean2, o.delta));
+    return res.download(st, {tested, p, z, med1, med2, mean1, mean2, delta});
 }

@@ -38,8 +38,9 @@
 //       group, then ONE bitonic network in LDS that carries two arrays through the same barriers -- (group, value) for the
 //       medians and the rank keys --, run and segment bounds by binary search, the stratum sums in LDS, one wave finishes.
 //
-// rowsum.h: PsKey, order bits, lane groups, group_sum, the block's compaction, pairwise sum, bitonic network, run bounds,
-// launch sizes; dd.h: the double-double sum.
+// rowsum.h: PsKey, order bits, lane groups with group_sum, group_sort (both key widths) and group_median, the block's
+// compaction, pairwise sum, bitonic network, run bounds, the stores of a row, the output pointers with their zeroing and
+// staging, launch sizes; dd.h: the double-double sum.
 #include "common.h"
 #include <math.h>
 #include <vector>
@@ -52,18 +53,6 @@ constexpr int ST_MAX_GROUP = 4096;       // columns of one group
 constexpr int ST_MAX_STRATA = 64;
 constexpr int ST_GROUP_MAX = 64;         // selected columns the lane-group kernel takes
 constexpr int ST_LEAF_MAX = 64;          // leaves of numpy's pairwise recursion over 4096 values (PW_DEPTH levels)
-constexpr uint32_t ST_PAD32 = 0xFFFFFFFFu;
-
-struct StOut {
-    uint8_t* tested;
-    double* p;
-    double* z;       // may be NULL
-    float* med1;
-    float* med2;
-    float* mean1;
-    float* mean2;
-    float* delta;
-};
 
 // the two key widths: padding, the stratum of a key; `key >> 1` is (stratum, value) and `key & 1` group 1 in both
 template <class K> struct StKey;
@@ -117,38 +106,13 @@ __device__ __forceinline__ double st_dd_lane_sum(double term) {
 }
 
 // ------------------------------------------------------------------ lane-group path: P lanes per row
-// ascending bitonic sort of one value per lane inside aligned groups of P lanes
-template <int P, class T>
-__device__ __forceinline__ T st_group_sort(T v, int gl) {
-#pragma unroll
-    for (int k = 2; k <= P; k <<= 1) {
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const T other = __shfl_xor(v, j);
-            const bool upper = (gl & j) != 0;
-            const bool asc = (gl & k) == 0;              // k == P: ascending everywhere
-            const T lo = v < other ? v : other, hi = v < other ? other : v;
-            v = (asc != upper) ? lo : hi;
-        }
-    }
-    return v;
-}
-
-// np.median of the group's nv sorted order-preserving values (lane g0 + i holds the i-th smallest)
-__device__ __forceinline__ float st_group_median(uint32_t sorted, int g0, int nv) {
-    const int h = nv >> 1;
-    const float v1 = f32_unord(__shfl(sorted, g0 + h));
-    const float v0 = f32_unord(__shfl(sorted, g0 + (h > 0 ? h - 1 : 0)));
-    return (nv & 1) ? v1 : (v0 + v1) / 2.0f;
-}
-
 struct StSums { double sd, sv; int cnt; };       // sum d_h, sum V_h, n1' | n2' << 16 over the informative strata
 
 // the group's keys -> its sums, to every lane of the group
 template <int P, class K>
 __device__ __forceinline__ StSums st_group_sums(K unsorted, int gl, int g0) {
     using G = LaneGroup<P>;
-    const K key = st_group_sort<P, K>(unsorted, gl);
+    const K key = group_sort<P, K>(unsorted, gl);
     const bool valid = key != StKey<K>::PAD;                             // the valid keys are positions 0 .. N
     const int N = __popcll((__ballot(valid) >> g0) & G::MASK);
     const K prev = __shfl_up(key, 1);
@@ -195,7 +159,7 @@ __global__ void __launch_bounds__(256) strata_group_kernel(const float* __restri
                                                            const int32_t* __restrict__ g1, int n1,
                                                            const int32_t* __restrict__ g2, int n2,
                                                            const int32_t* __restrict__ st1, const int32_t* __restrict__ st2,
-                                                           int ch, StOut o) {
+                                                           int ch, TwoSampleOut o) {
     using G = LaneGroup<P>;                              // G::R rows side by side in a wave
     __shared__ float cx[4][64], cy[4][64];               // the kept values of the wave's rows, compacted, in list order
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
@@ -238,9 +202,9 @@ __global__ void __launch_bounds__(256) strata_group_kernel(const float* __restri
         const float sum1 = 0.0f + group_sum(X, nv1, gl);     // np.sum starts from the identity 0: -0.0 values sum to +0.0
         const float sum2 = 0.0f + group_sum(Y, nv2, gl);
         // ---- the medians
-        const uint32_t o1 = st_group_sort<P, uint32_t>(kept && in1 ? f32_ord(x) : ST_PAD32, gl);
-        const uint32_t o2 = st_group_sort<P, uint32_t>(kept && !in1 ? f32_ord(x) : ST_PAD32, gl);
-        const float med1 = st_group_median(o1, g0, nv1), med2 = st_group_median(o2, g0, nv2);
+        const uint32_t o1 = group_sort<P, uint32_t>(kept && in1 ? f32_ord(x) : PAD32, gl);
+        const uint32_t o2 = group_sort<P, uint32_t>(kept && !in1 ? f32_ord(x) : PAD32, gl);
+        const float med1 = group_median(o1, g0, nv1), med2 = group_median(o2, g0, nv2);
         // ---- the ranks inside the strata; the narrow key when every row of the pass is on the 3-decimal grid
         StSums sums;
         if (__ballot(offgrid) == 0ull)                       // wave-uniform
@@ -266,14 +230,7 @@ __global__ void __launch_bounds__(256) strata_group_kernel(const float* __restri
         const bool tested = s_tested != 0;
         double z = 0.0, p = 0.0;
         if (tested) st_finish(s_sd, s_sv, z, p);
-        o.tested[row] = tested ? 1 : 0;
-        o.p[row] = p;
-        if (o.z) o.z[row] = z;
-        o.med1[row] = tested ? s_med1 : 0.f;
-        o.med2[row] = tested ? s_med2 : 0.f;
-        o.mean1[row] = tested ? s_mean1 : 0.f;
-        o.mean2[row] = tested ? s_mean2 : 0.f;
-        o.delta[row] = tested ? s_med1 - s_med2 : 0.f;
+        store_two_sample(o, row, tested, p, z, s_med1, s_med2, s_mean1, s_mean2);
       }
     }
 }
@@ -347,7 +304,7 @@ __global__ void __launch_bounds__(RB_THREADS) strata_block_kernel(const float* _
                                                                   const int32_t* __restrict__ g1, int n1,
                                                                   const int32_t* __restrict__ g2, int n2,
                                                                   const int32_t* __restrict__ st1,
-                                                                  const int32_t* __restrict__ st2, int P, StOut o) {
+                                                                  const int32_t* __restrict__ st2, int P, TwoSampleOut o) {
     extern __shared__ __align__(16) unsigned char smemst[];
     unsigned long long* A = reinterpret_cast<unsigned long long*>(smemst);      // [P] group << 32 | order bits: the medians
     unsigned long long* B64 = A + P;                                            // [P] the rank keys, wide ...
@@ -379,7 +336,7 @@ __global__ void __launch_bounds__(RB_THREADS) strata_block_kernel(const float* _
             const bool grid = __syncthreads_or(off) == 0;       // (a barrier: the sums are done with F)
             for (int j = tid; j < P; j += RB_THREADS) {
                 unsigned long long a = ~0ull, b64 = ~0ull;
-                uint32_t b32 = ST_PAD32;
+                uint32_t b32 = PAD32;
                 if (j < m) {
                     const bool in1 = j < n1;
                     const float v = prow[in1 ? g1[j] : g2[j - n1]];
@@ -421,6 +378,8 @@ __global__ void __launch_bounds__(RB_THREADS) strata_block_kernel(const float* _
                 med1 = median_of_ord(A, nv1);                   // np.median on float32
                 med2 = median_of_ord(A + nv1, nv2);
             }
+            // (written out: through store_two_sample the two divisions leave the `tested` branch, and the kernel so changed
+            // timed 0.2 - 0.5 % above the range of the one before it: EXPERIMENTS A.12)
             o.tested[row] = tested ? 1 : 0;
             o.p[row] = p;
             if (o.z) o.z[row] = z;
@@ -436,7 +395,7 @@ __global__ void __launch_bounds__(RB_THREADS) strata_block_kernel(const float* _
 
 template <int P>
 int st_launch_group(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* d_g1, int n1, const int32_t* d_g2,
-                    int n2, const int32_t* d_st1, const int32_t* d_st2, StOut o) {
+                    int n2, const int32_t* d_st1, const int32_t* d_st2, TwoSampleOut o) {
     const int waves = 4;
     const int ch = rows_per_chunk(ctx->n_cu, n);
     const int64_t blocks = wave_launch_blocks(ctx, n, ch, waves);
@@ -482,18 +441,10 @@ extern "C" int sdice_ranksum_strata_dev(sdice_ctx* ctx, int64_t n, int32_t s, co
     SD_ARG(d_ps && d_g1 && d_g2 && d_strat1 && d_strat2, "NULL input");
     SD_HIP(hipSetDevice(ctx->device));
     SD_TRY(ctx->arena.reset(ctx->stream));
-    StOut o{d_tested, d_p, d_z, d_med1, d_med2, d_mean1, d_mean2, d_delta};
+    TwoSampleOut o{d_tested, d_p, d_z, d_med1, d_med2, d_mean1, d_mean2, d_delta};
     const int m = n1 + n2;
-    if (n1 < 3 || n2 < 3) {
-        // no row can be tested
-        SD_HIP(hipMemsetAsync(d_tested, 0, (size_t)n, ctx->stream));
-        SD_HIP(hipMemsetAsync(d_p, 0, (size_t)n * 8, ctx->stream));
-        if (d_z) SD_HIP(hipMemsetAsync(d_z, 0, (size_t)n * 8, ctx->stream));
-        float* f[5] = {d_med1, d_med2, d_mean1, d_mean2, d_delta};
-        for (auto q : f) SD_HIP(hipMemsetAsync(q, 0, (size_t)n * 4, ctx->stream));
-        return SDICE_OK;
-    }
-    if (m <= ST_GROUP_MAX) {
+    if (n1 < 3 || n2 < 3) return zero_two_sample(ctx, n, o);         // no row can be tested
+    if (m <= ST_GROUP_MAX) {                                   // (a ladder per file: the launches differ in their arguments)
         if (m <= 8) return st_launch_group<8>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, d_strat1, d_strat2, o);
         if (m <= 16) return st_launch_group<16>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, d_strat1, d_strat2, o);
         if (m <= 32) return st_launch_group<32>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, d_strat1, d_strat2, o);
@@ -537,26 +488,17 @@ extern "C" int sdice_ranksum_strata(sdice_ctx* ctx, int64_t n, int32_t s, const 
     SD_ARG(tested && p && med1 && med2 && mean1 && mean2 && delta, "NULL output");
     SD_ARG(ps, "ps is NULL");
     HostStaging st(ctx);
-    float *d_ps, *df;
+    TwoSampleStaging res;
+    float* d_ps;
     int32_t *dg1, *dg2, *ds1, *ds2;
-    uint8_t* dt;
-    double* dd;
     SD_TRY(st.upload(&d_ps, ps, n * s));
     SD_TRY(st.upload(&dg1, g1, n1));
     SD_TRY(st.upload(&dg2, g2, n2));
     SD_TRY(st.upload(&ds1, strat1, n1));
     SD_TRY(st.upload(&ds2, strat2, n2));
-    SD_TRY(st.alloc(&dt, n));
-    SD_TRY(st.alloc(&dd, n * 2));      // p, z
-    SD_TRY(st.alloc(&df, n * 5));      // med1, med2, mean1, mean2, delta
-    SD_TRY(sdice_ranksum_strata_dev(ctx, n, s, d_ps, dg1, n1, dg2, n2, ds1, ds2, n_strata, dt, dd, dd + n, df, df + n,
-                                    df + 2 * n, df + 3 * n, df + 4 * n));
-    SD_TRY(st.download(tested, dt, n));
-    SD_TRY(st.download(p, dd, n));
-    if (z) SD_TRY(st.download(z, dd + n, n));
-    SD_TRY(st.download(med1, df, n));
-    SD_TRY(st.download(med2, df + n, n));
-    SD_TRY(st.download(mean1, df + 2 * n, n));
-    SD_TRY(st.download(mean2, df + 3 * n, n));
-    return st.download(delta, df + 4 * n, n);
+    SD_TRY(res.alloc(st, n));
+    const TwoSampleOut o = res.out();
+    SD_TRY(sdice_ranksum_strata_dev(ctx, n, s, d_ps, dg1, n1, dg2, n2, ds1, ds2, n_strata, o.tested, o.p, o.z, o.med1, o.med2,
+                                    o.mean1, o.mean2, o.delta));
+    return res.download(st, {tested, p, z, med1, med2, mean1, mean2, delta});
 }

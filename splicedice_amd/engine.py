@@ -38,6 +38,11 @@ def _zeros(fields, shape, k=None):
     return {name: np.zeros(sh, dt) for name, (sh, dt) in field_shapes(fields, shape, k).items()}
 
 
+def _dev_ptrs(fields, out, optional):
+    """the device pointers of a _dev call in the order of its field table; None for the field `optional` when `out` lacks it"""
+    return [out[f[0]].ptr if f[0] != optional or out.get(f[0]) else None for f in fields]
+
+
 def pair_array(pairs):
     """a pair list as the library takes it: int32 [m, 2], C-contiguous, m >= 1 (the library checks the indices)"""
     a = np.asarray(pairs)
@@ -342,26 +347,23 @@ class Context:
         check(self.lib.sdice_quantize3(self.h, out.size, _ptr(out)), "sdice_quantize3")
         return out
 
-    def ranksum(self, ps, g1, g2):
-        """compareSampleSets.py:216-232 for every row; un-compacted outputs + tested mask."""
+    def _ranksum(self, name, fields, ps, g1, g2):
         ps = _c(ps, np.float32)
         n, s = ps.shape
         g1, g2 = _c(g1, np.int32), _c(g2, np.int32)
-        out = _zeros(RANKSUM_FIELDS, n)
-        check(self.lib.sdice_ranksum(self.h, n, s, _ptr(ps), _ptr(g1), g1.size, _ptr(g2), g2.size, *map(_ptr, out.values())),
-              "sdice_ranksum")
+        out = _zeros(fields, n)
+        check(getattr(self.lib, "sdice_" + name)(self.h, n, s, _ptr(ps), _ptr(g1), g1.size, _ptr(g2), g2.size,
+                                                 *map(_ptr, out.values())), "sdice_" + name)
         return out
+
+    def ranksum(self, ps, g1, g2):
+        """compareSampleSets.py:216-232 for every row; un-compacted outputs + tested mask."""
+        return self._ranksum("ranksum", RANKSUM_FIELDS, ps, g1, g2)
 
     def ranksum_exact(self, ps, g1, g2):
         """ranksum() with the exact conditional p-value on the rows that keep at most 32 values (include/sdice.h): the
         same outputs + exact (1 where p is the exact value); every other field is ranksum()'s bit for bit."""
-        ps = _c(ps, np.float32)
-        n, s = ps.shape
-        g1, g2 = _c(g1, np.int32), _c(g2, np.int32)
-        out = _zeros(RANKSUM_EXACT_FIELDS, n)
-        check(self.lib.sdice_ranksum_exact(self.h, n, s, _ptr(ps), _ptr(g1), g1.size, _ptr(g2), g2.size,
-                                           *map(_ptr, out.values())), "sdice_ranksum_exact")
-        return out
+        return self._ranksum("ranksum_exact", RANKSUM_EXACT_FIELDS, ps, g1, g2)
 
     def ranksum_strata(self, ps, g1, g2, strat1, strat2):
         """van Elteren's stratified rank-sum test per row (include/sdice.h): strat1 / strat2 are the dense stratum ids
@@ -390,31 +392,26 @@ class Context:
               "sdice_kruskal")
         return out
 
-    def signedrank(self, ps, a, b):
-        """scipy.stats.wilcoxon (asymptotic, zero_method="wilcox") per row over the matched column pairs (a[q], b[q])
-        under the row rules of ranksum(); same un-compacted outputs + tested mask (z > 0: side a is larger)."""
+    def _signedrank(self, name, fields, ps, a, b):
         ps = _c(ps, np.float32)
         n, s = ps.shape
         a, b = _c(a, np.int32), _c(b, np.int32)
         if a.shape != b.shape or a.ndim != 1:
-            raise ValueError(f"signedrank: the pair lists must be two vectors of one length, got {a.shape} and {b.shape}")
-        out = _zeros(RANKSUM_FIELDS, n)
-        check(self.lib.sdice_signedrank(self.h, n, s, _ptr(ps), _ptr(a), _ptr(b), a.size, *map(_ptr, out.values())),
-              "sdice_signedrank")
+            raise ValueError(f"{name}: the pair lists must be two vectors of one length, got {a.shape} and {b.shape}")
+        out = _zeros(fields, n)
+        check(getattr(self.lib, "sdice_" + name)(self.h, n, s, _ptr(ps), _ptr(a), _ptr(b), a.size, *map(_ptr, out.values())),
+              "sdice_" + name)
         return out
+
+    def signedrank(self, ps, a, b):
+        """scipy.stats.wilcoxon (asymptotic, zero_method="wilcox") per row over the matched column pairs (a[q], b[q])
+        under the row rules of ranksum(); same un-compacted outputs + tested mask (z > 0: side a is larger)."""
+        return self._signedrank("signedrank", RANKSUM_FIELDS, ps, a, b)
 
     def signedrank_exact(self, ps, a, b):
         """signedrank() with the exact p-value on the rows with at most 31 non-zero differences (include/sdice.h): the
         same outputs + exact; every other field is signedrank()'s bit for bit."""
-        ps = _c(ps, np.float32)
-        n, s = ps.shape
-        a, b = _c(a, np.int32), _c(b, np.int32)
-        if a.shape != b.shape or a.ndim != 1:
-            raise ValueError(f"signedrank_exact: the pair lists must be two vectors of one length, got {a.shape} and {b.shape}")
-        out = _zeros(RANKSUM_EXACT_FIELDS, n)
-        check(self.lib.sdice_signedrank_exact(self.h, n, s, _ptr(ps), _ptr(a), _ptr(b), a.size, *map(_ptr, out.values())),
-              "sdice_signedrank_exact")
-        return out
+        return self._signedrank("signedrank_exact", RANKSUM_EXACT_FIELDS, ps, a, b)
 
     def spearman(self, ps, cols, x):
         """scipy.stats.spearmanr(x_kept, ps_kept) per row between the PS values of the listed columns and the covariate x
@@ -551,9 +548,7 @@ class Context:
     def ranksum_dev(self, d_ps, d_g1, d_g2, out):
         n, s = d_ps.shape
         check(self.lib.sdice_ranksum_dev(self.h, n, s, d_ps.ptr, d_g1.ptr, d_g1.shape[0], d_g2.ptr, d_g2.shape[0],
-                                         out["tested"].ptr, out["p"].ptr, out["z"].ptr if out.get("z") else None,
-                                         out["med1"].ptr, out["med2"].ptr, out["mean1"].ptr, out["mean2"].ptr,
-                                         out["delta"].ptr), "sdice_ranksum_dev")
+                                         *_dev_ptrs(RANKSUM_FIELDS, out, "z")), "sdice_ranksum_dev")
 
     def ranksum_strata_dev(self, d_ps, d_g1, d_g2, d_strat1, d_strat2, n_strata, out):
         """d_strat1, d_strat2: the device copies of the stratum ids of d_g1, d_g2 (checked by the caller: the host call
@@ -561,45 +556,36 @@ class Context:
         n, s = d_ps.shape
         check(self.lib.sdice_ranksum_strata_dev(self.h, n, s, d_ps.ptr, d_g1.ptr, d_g1.shape[0], d_g2.ptr, d_g2.shape[0],
                                                 d_strat1.ptr, d_strat2.ptr, int(n_strata),
-                                                out["tested"].ptr, out["p"].ptr, out["z"].ptr if out.get("z") else None,
-                                                out["med1"].ptr, out["med2"].ptr, out["mean1"].ptr, out["mean2"].ptr,
-                                                out["delta"].ptr), "sdice_ranksum_strata_dev")
+                                                *_dev_ptrs(RANKSUM_FIELDS, out, "z")), "sdice_ranksum_strata_dev")
 
     def signedrank_dev(self, d_ps, d_a, d_b, out):
         n, s = d_ps.shape
         check(self.lib.sdice_signedrank_dev(self.h, n, s, d_ps.ptr, d_a.ptr, d_b.ptr, d_a.shape[0],
-                                            out["tested"].ptr, out["p"].ptr, out["z"].ptr if out.get("z") else None,
-                                            out["med1"].ptr, out["med2"].ptr, out["mean1"].ptr, out["mean2"].ptr,
-                                            out["delta"].ptr), "sdice_signedrank_dev")
+                                            *_dev_ptrs(RANKSUM_FIELDS, out, "z")), "sdice_signedrank_dev")
 
     def ranksum_exact_dev(self, d_ps, d_g1, d_g2, out):
         """out: the device fields of RANKSUM_EXACT_FIELDS (z optional)"""
         n, s = d_ps.shape
         check(self.lib.sdice_ranksum_exact_dev(self.h, n, s, d_ps.ptr, d_g1.ptr, d_g1.shape[0], d_g2.ptr, d_g2.shape[0],
-                                               out["tested"].ptr, out["p"].ptr, out["z"].ptr if out.get("z") else None,
-                                               out["med1"].ptr, out["med2"].ptr, out["mean1"].ptr, out["mean2"].ptr,
-                                               out["delta"].ptr, out["exact"].ptr), "sdice_ranksum_exact_dev")
+                                               *_dev_ptrs(RANKSUM_EXACT_FIELDS, out, "z")), "sdice_ranksum_exact_dev")
 
     def signedrank_exact_dev(self, d_ps, d_a, d_b, out):
         n, s = d_ps.shape
         check(self.lib.sdice_signedrank_exact_dev(self.h, n, s, d_ps.ptr, d_a.ptr, d_b.ptr, d_a.shape[0],
-                                                  out["tested"].ptr, out["p"].ptr, out["z"].ptr if out.get("z") else None,
-                                                  out["med1"].ptr, out["med2"].ptr, out["mean1"].ptr, out["mean2"].ptr,
-                                                  out["delta"].ptr, out["exact"].ptr), "sdice_signedrank_exact_dev")
+                                                  *_dev_ptrs(RANKSUM_EXACT_FIELDS, out, "z")), "sdice_signedrank_exact_dev")
 
     def spearman_dev(self, d_ps, d_cols, d_xg, out):
         """d_cols, d_xg: the device copies of spearman_order()'s pair; out: device tested, p, (rho), n_kept, med, mean"""
         n, s = d_ps.shape
         check(self.lib.sdice_spearman_dev(self.h, n, s, d_ps.ptr, d_cols.ptr, d_xg.ptr, d_cols.shape[0],
-                                          out["tested"].ptr, out["p"].ptr, out["rho"].ptr if out.get("rho") else None,
-                                          out["n_kept"].ptr, out["med"].ptr, out["mean"].ptr), "sdice_spearman_dev")
+                                          *_dev_ptrs(SPEARMAN_FIELDS, out, "rho")), "sdice_spearman_dev")
 
     def sample_gram_dev(self, d_ps, d_cols, out):
         """d_cols: the device copy of gram_columns(); out: device shared, sum1, sum2, prod, int64 [m, m] each.  Synchronises
         once (the bad-value check of the pre-pass); the sums are queued."""
         n, s = d_ps.shape
-        check(self.lib.sdice_sample_gram_dev(self.h, n, s, d_ps.ptr, d_cols.ptr, d_cols.shape[0], out["shared"].ptr,
-                                             out["sum1"].ptr, out["sum2"].ptr, out["prod"].ptr), "sdice_sample_gram_dev")
+        check(self.lib.sdice_sample_gram_dev(self.h, n, s, d_ps.ptr, d_cols.ptr, d_cols.shape[0],
+                                             *_dev_ptrs(GRAM_FIELDS, out, None)), "sdice_sample_gram_dev")
 
     def kruskal_dev(self, d_ps, d_cols, set_ptr, out):
         """d_cols: the device copy of kruskal_sets()'s cols; set_ptr: its HOST offsets; out: device tested, p, (h), med and
@@ -607,8 +593,7 @@ class Context:
         n, s = d_ps.shape
         set_ptr = _c(set_ptr, np.int32)
         check(self.lib.sdice_kruskal_dev(self.h, n, s, d_ps.ptr, d_cols.ptr, _ptr(set_ptr), set_ptr.size - 1,
-                                         out["tested"].ptr, out["p"].ptr, out["h"].ptr if out.get("h") else None,
-                                         out["med"].ptr, out["mean"].ptr, out["delta"].ptr), "sdice_kruskal_dev")
+                                         *_dev_ptrs(KRUSKAL_FIELDS, out, "h")), "sdice_kruskal_dev")
 
     def pair_table(self, s, pairs):
         """a pair list for the _dev calls: checked against s samples, packed and uploaded once -> DeviceArray uint32[m]
