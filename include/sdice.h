@@ -187,6 +187,23 @@ int sdice_kruskal_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, c
                       const int32_t* set_ptr, int32_t k, uint8_t* d_tested, double* d_p, double* d_h,
                       float* d_med, float* d_mean, float* d_delta);
 
+/* ---- compare_sample_sets -mx --trend: Jonckheere-Terpstra trend test across k ORDERED sets (set 0 < set 1 < ... as
+ *      given) under the row rules, the inputs, the checks and the refusals of sdice_kruskal above.
+ *  J = sum over the set pairs i < j of #{x in i, y in j: x < y} + #{x == y} / 2; E[J] = sum_{i<j} n_i n_j / 2; Var(J) is the
+ *  exact conditional (permutation) variance given the row's ties, evaluated in integers; z = (J - E[J]) / sqrt(Var J)
+ *  without a continuity correction, z > 0 when the values rise along the set order; p = erfc(|z| / sqrt 2), two-sided,
+ *  asymptotic only.  Ties are by float32 equality (-0.0 == +0.0, subnormals are distinct values).
+ *  Outputs, one slot per row: tested[n], p[n], z[n] float64, j[n] float64 = J exactly (optional, NULL to skip);
+ *  med[k][n] / mean[k][n] SET-major and delta[n] are those of sdice_kruskal bit for bit; 0 where not tested.  A row whose
+ *  kept values are all equal is tested with z = 0, p = 1, J = E[J].  Any finite float32 values; rows of 3-decimal PS
+ *  values take the histogram kernel. */
+int sdice_jonckheere(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps, const int32_t* cols,
+                     const int32_t* set_ptr, int32_t k, uint8_t* tested, double* p, double* z, double* j,
+                     float* med, float* mean, float* delta);
+int sdice_jonckheere_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, const int32_t* d_cols,
+                         const int32_t* set_ptr, int32_t k, uint8_t* d_tested, double* d_p, double* d_z, double* d_j,
+                         float* d_med, float* d_mean, float* d_delta);
+
 /* ---- compare_sample_sets --paired: Wilcoxon signed-rank test over m matched column pairs, per row
  *      scipy.stats.wilcoxon(d, zero_method="wilcox", correction=False, alternative="two-sided", method="asymptotic")
  *      under the row rules above.

@@ -23,6 +23,11 @@ and the test becomes van Elteren's stratified rank-sum test (sdice_ranksum_strat
 only and the batches' rank-sum deviations are added with weights 1 / (N_h + 1).  Same columns; not with --paired, -mx or
 --exact.  Unlike the plain test its variance carries the tie correction.
 
+A fifth: `--trend` (with -mx) takes the sets as ORDERED -- dose levels, time points, stages: -m1 < -m2 < the -mx files in
+the order given -- and the test becomes the Jonckheere-Terpstra trend test (sdice_jonckheere): z > 0 where the PS rises
+along the order, two-sided asymptotic p.  The columns are the -mx ones with `z` where `H` stood; not with --paired, --exact
+or --strata.
+
 On the GPU: the per-row loop :216-232 (NaN drop, <3 skip, scipy ranksums, medians, means)
 -> sdice_ranksum; multipletests(..., "fdr_bh") :235 -> sdice_bh over the tested rows.
 The GTF annotation columns are host string work, as in the reference.
@@ -33,11 +38,12 @@ import numpy as np
 
 from . import _cli
 from ._cli import annotation_suffixes, read_annotation, read_ps_table, samples_from_manifest, table_header_names  # noqa: F401
-from .engine import KRUSKAL_FIELDS, RANKSUM_EXACT_FIELDS, RANKSUM_FIELDS, Context, field_shapes
+from .engine import JONCKHEERE_FIELDS, KRUSKAL_FIELDS, RANKSUM_EXACT_FIELDS, RANKSUM_FIELDS, Context, field_shapes
 
 refuse = _cli.refusal("compare_sample_sets --paired")
 refuse_exact = _cli.refusal("compare_sample_sets --exact")
 refuse_strata = _cli.refusal("compare_sample_sets --strata")
+refuse_trend = _cli.refusal("compare_sample_sets --trend")
 MAX_STRATA = 64                     # strata a call accepts (include/sdice.h)
 
 
@@ -88,15 +94,17 @@ def compare_strata(matrix, g1_idx, g2_idx, strat1, strat2, n_strata, ctx):
                             lambda d, out: ctx.ranksum_strata_dev(d["ps"], d["g1"], d["g2"], d["s1"], d["s2"], n_strata, out))
 
 
-def compare_sets_dev(matrix, set_idx, ctx):
-    """the k-set pipeline (-mx): table up, Kruskal-Wallis + BH over the tested rows on resident vectors, per-row results
-    down -> (kept row indices, dict: mean / med float32 [k, kept], delta, h, p, corrected)"""
+def compare_sets_dev(matrix, set_idx, ctx, trend=False):
+    """the k-set pipeline (-mx): table up, Kruskal-Wallis (trend: Jonckheere-Terpstra over the sets in their order) + BH
+    over the tested rows on resident vectors, per-row results down -> (kept row indices, dict: mean / med float32
+    [k, kept], delta, h (trend: z, j), p, corrected)"""
     from .engine import kruskal_sets
     n, s = matrix.shape
     cols, set_ptr = kruskal_sets(set_idx, s)          # (raises on a column in two sets, before any launch)
+    test = ctx.jonckheere_dev if trend else ctx.kruskal_dev
     return _cli.tested_rows(ctx, dict(ps=(matrix, np.float32), cols=(cols, np.int32)),
-                            field_shapes(KRUSKAL_FIELDS, n, len(set_idx)),
-                            lambda d, out: ctx.kruskal_dev(d["ps"], d["cols"], set_ptr, out))
+                            field_shapes(JONCKHEERE_FIELDS if trend else KRUSKAL_FIELDS, n, len(set_idx)),
+                            lambda d, out: test(d["ps"], d["cols"], set_ptr, out))
 
 
 def compare_sharded(matrix, g1_idx, g2_idx, ctx, L, paired=False, exact=False):
@@ -147,6 +155,13 @@ def add_parser(parser):
                              "batch the p-value is mannwhitneyu(use_continuity=False, method='asymptotic'), equal to "
                              "the plain one only on rows without ties.  Not with --paired, -mx or --exact (not part of "
                              "the reference)")
+    parser.add_argument("--trend", action="store_true",
+                        help="With -mx: the sets are ORDERED (dose levels, time points, stages), -m1 < -m2 < the -mx files "
+                             "in the order given, and the test becomes the Jonckheere-Terpstra trend test: z > 0 where the "
+                             "PS rises along that order, z < 0 where it falls; the table carries z where the -mx table "
+                             "carries H.  The two-sided p-value is asymptotic only (normal approximation with the "
+                             "tie-corrected variance, no exact form).  Not with --paired, --exact or --strata (not part of "
+                             "the reference)")
     parser.add_argument("-a", "--annotation", type=str, required=False, default="",
                         help="Optional GTF file to label known splice junctions and genes")
     parser.add_argument("-o", "--outputFile", type=str, required=True,
@@ -158,6 +173,10 @@ MULTI_RANK_REFUSAL = ("compare_sample_sets: -mx/--moreManifests is not available
 
 STRATA_MULTI_RANK_REFUSAL = ("compare_sample_sets: --strata is not available under the multi-rank launcher "
                              "(the sharded two-set path does not carry the stratum ids); run it in one process.")
+
+
+TREND_MULTI_RANK_REFUSAL = ("compare_sample_sets: --trend is not available under the multi-rank launcher "
+                            "(the packed all-gather carries the two-set fields only); run it in one process.")
 
 
 def strata_columns(g1, g2, header_names, labels):
@@ -208,6 +227,16 @@ def run_with(args, ctx=None):
     more = [samples_from_manifest(m) for m in (getattr(args, "moreManifests", None) or [])]
     paired = bool(getattr(args, "paired", False))
     exact = bool(getattr(args, "exact", False))
+    trend = bool(getattr(args, "trend", False))
+    if trend:
+        if not more:
+            refuse_trend("needs -mx/--moreManifests (three or more ordered sets; two sets are the rank-sum test)")
+        for on, flag in ((paired, "--paired (the signed-rank test compares two matched sets)"),
+                         (exact, "--exact (the trend test is asymptotic only)"),
+                         (getattr(args, "strata", None), "--strata (there is no stratified trend test here)")):
+            if on:
+                refuse_trend(f"cannot be combined with {flag}")
+        _cli.refuse_multi_rank(L, TREND_MULTI_RANK_REFUSAL)
     if exact and more:
         refuse_exact("cannot be combined with -mx/--moreManifests (there is no exact Kruskal-Wallis test here)")
     strata = getattr(args, "strata", None)
@@ -235,7 +264,8 @@ def run_with(args, ctx=None):
             keep, r = compare_strata(matrix, *strat, ctx)
         elif more:
             # k >= 3 sets: Kruskal-Wallis per junction; columns event mean1..meank median1..mediank delta H p-value corrected
-            keep, r = compare_sets_dev(matrix, [column_indices(g, cols) for g in [g1, g2] + more], ctx)
+            # (--trend: Jonckheere-Terpstra over the sets in this order, z where H stands)
+            keep, r = compare_sets_dev(matrix, [column_indices(g, cols) for g in [g1, g2] + more], ctx, trend)
         else:
             g1_idx, g2_idx = pair_idx if paired else (column_indices(g1, cols), column_indices(g2, cols))
             if L.world > 1:
@@ -249,8 +279,8 @@ def run_with(args, ctx=None):
     if more:
         k = 2 + len(more)
         header = "\t".join(["event"] + [f"mean{i + 1}" for i in range(k)] + [f"median{i + 1}" for i in range(k)] +
-                           ["delta", "H", "p-value", "corrected"])
-        columns = [*r["mean"], *r["med"], r["delta"], r["h"], r["p"], r["corrected"]]
+                           ["delta", "z" if trend else "H", "p-value", "corrected"])
+        columns = [*r["mean"], *r["med"], r["delta"], r["z" if trend else "h"], r["p"], r["corrected"]]
     else:
         header = "event\tmean1\tmean2\tmedian1\tmedian2\tdelta\tp-value\tcorrected"
         columns = [r["mean1"], r["mean2"], r["med1"], r["med2"], r["delta"], r["p"], r["corrected"]]

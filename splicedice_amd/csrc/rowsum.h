@@ -9,6 +9,9 @@
 //   ranksum.hip (K5)      PsKey, median_sorted, block_compact, the pairwise sums, find_bin, lanes_below; TwoSampleOut (as
 //                         RsOut), zero_two_sample, TwoSampleStaging
 //   kruskal.hip (K12)     as ranksum.hip's kernels + f32_ord, median_of_ord, block_bitonic
+//                         + the k-set section: the limits, KwSets, kw_stage_row / kw_walk_set (the first walk of the grid
+//                         kernel), kw_block_sort_sets (the block kernel up to its medians), kw_check_sets, kw_plan
+//   jonckheere.hip (K18)  the k-set section as kruskal.hip, kw_load_bins / kw_scan_bins, the launch sizes, check_columns
 //   signedrank.hip (K13)  PsKey, f32_ord, LaneGroup, group_add / group_sum / group_sort / group_median, pair_diff_key,
 //                         block_compact_by, block_pairwise_sum, block_bitonic, run_bounds, median_of_ord, store_two_sample,
 //                         the launch sizes, check_columns; TwoSampleOut, zero_two_sample, TwoSampleStaging
@@ -411,6 +414,210 @@ __device__ __forceinline__ RunBounds run_bounds(const T* K, int n, C code, Proj 
     return {first, lo};
 }
 
+// ---- k sample sets (kruskal.hip, jonckheere.hip): the limits, the sets as a kernel argument, the first walk of a wave
+// over a row of 3-decimal values and the (set, value) sort of a workgroup over any row
+constexpr int KW_MAX_SETS = 64;
+constexpr int KW_MAX_N = 16384;          // selected columns per row, both kernels (block kernel: 8 B of LDS per column)
+constexpr int KW_BINS = 1024;            // 1001 used
+constexpr int KW_SUM_PIECE = 8192;       // np.add.reduce hands the pairwise loop at most np.getbufsize() = 8192 values at a time
+constexpr int KW_PW_DEPTH = 7;           // levels of numpy's pairwise recursion inside a piece (7689 values are the first to need 7)
+constexpr int KW_LEAF_MAX = 128;         // a part after 7 halvings is at most 8192 / 128 + 15 values long
+constexpr unsigned char KW_REDO = 0xFF;  // `tested` mark: row left to the block kernel by the grid kernel
+
+struct KwSets { int32_t ptr[KW_MAX_SETS + 1]; };
+
+__device__ __forceinline__ float kw_wave_max(float v) {
+#pragma unroll
+    for (int ofs = 32; ofs > 0; ofs >>= 1) v = fmaxf(v, __shfl_xor(v, ofs));
+    return v;
+}
+__device__ __forceinline__ float kw_wave_min(float v) {
+#pragma unroll
+    for (int ofs = 32; ofs > 0; ofs >>= 1) v = fminf(v, __shfl_xor(v, ofs));
+    return v;
+}
+
+// np.sum of the contiguous float32 array float32(K[0..nv) / 1000): the identity 0 plus the pairwise tree of every piece
+// of KW_SUM_PIECE values, the pieces added left to right (at most two: nv <= KW_MAX_N).  The whole-array tree is a
+// different sum above one piece.
+__device__ __forceinline__ float kw_wave_sum_keys(const unsigned short* K, int nv, int lane, int* leaf_off, float* leaf_sum) {
+    float sum = 0.0f + wave_pairwise_sum<KW_PW_DEPTH>(KeyAt{K}, min(nv, KW_SUM_PIECE), lane, leaf_off, leaf_sum);
+    if (nv > KW_SUM_PIECE)               // wave-uniform
+        sum += wave_pairwise_sum<KW_PW_DEPTH>(KeyAt{K + KW_SUM_PIECE}, nv - KW_SUM_PIECE, lane, leaf_off, leaf_sum);
+    return sum;
+}
+
+// The wave's LDS in the grid kernels: Htot[1024] | Hset[1024] | leaf_sum[leaf_cap] | leaf_off[leaf_cap + 1] | keys[nsel] u16
+struct KwWaveLds {
+    unsigned* Htot;
+    unsigned* Hset;
+    float* leaf_sum;
+    int* leaf_off;
+    unsigned short* keys;
+    __device__ __forceinline__ KwWaveLds(unsigned char* base, int leaf_cap) {
+        Htot = reinterpret_cast<unsigned*>(base);
+        Hset = Htot + KW_BINS;
+        leaf_sum = reinterpret_cast<float*>(Hset + KW_BINS);
+        leaf_off = reinterpret_cast<int*>(leaf_sum + leaf_cap);
+        keys = reinterpret_cast<unsigned short*>(leaf_off + leaf_cap + 1);
+    }
+};
+
+// A row's selected columns staged as keys (0xFFFF = NaN); false when a value is not its key's float (wave-uniform).  On
+// true both histograms are cleared and the wave is in step.
+__device__ __forceinline__ bool kw_stage_row(const float* __restrict__ prow, const int32_t* __restrict__ cols, int nsel,
+                                             const KwWaveLds& L, int lane) {
+    bool ok = true;
+    for (int j = lane; j < nsel; j += 64) {
+        const float v = __builtin_nontemporal_load(prow + cols[j]);
+        const PsKey pk = key_of_ps(v);
+        ok = ok && (v != v || pk.exact());
+        L.keys[j] = (v != v) ? (unsigned short)0xFFFF : (unsigned short)pk.key();
+    }
+    if (__ballot(!ok) != 0ull) return false;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        reinterpret_cast<uint4*>(L.Htot)[lane * 4 + q] = make_uint4(0, 0, 0, 0);
+        reinterpret_cast<uint4*>(L.Hset)[lane * 4 + q] = make_uint4(0, 0, 0, 0);
+    }
+    SD_WAVE_SYNC();
+    return true;
+}
+
+// this lane's 16 bins of a histogram
+__device__ __forceinline__ void kw_load_bins(const unsigned* H, int lane, unsigned (&w)[16]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint4 t4 = reinterpret_cast<const uint4*>(H)[lane * 4 + q];
+        w[4 * q] = t4.x; w[4 * q + 1] = t4.y; w[4 * q + 2] = t4.z; w[4 * q + 3] = t4.w;
+    }
+}
+
+// this lane's count inside its 16 bins (tot) and the inclusive scan of that over the lanes
+__device__ __forceinline__ int kw_scan_bins(const unsigned (&w)[16], int lane, int& tot) {
+    tot = 0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) tot += (int)w[q];
+    int pre = tot;
+#pragma unroll
+    for (int ofs = 1; ofs < 64; ofs <<= 1) {
+        const int up = __shfl_up(pre, ofs);
+        if (lane >= ofs) pre += up;
+    }
+    return pre;
+}
+
+// One set of the first walk: K[0..cnt) are the set's staged keys.  Ordered compaction in place (a key moves to a slot at
+// or below its own; every lane reads its key of the round before any lane writes) + the set's histogram; with fewer
+// than 3 kept values the count is returned at once (wave-uniform, the histogram is left as it is).  Then the numpy-order
+// mean, the median from the histogram's scan, before_join(w, t) with this lane's 16 bins of the set and of the total
+// of the sets BEFORE it, and the set joins the total, its own bins cleared.
+template <class BeforeJoin>
+__device__ __forceinline__ int kw_walk_set(unsigned short* K, int cnt, const KwWaveLds& L, int lane, float& med, float& mean,
+                                           BeforeJoin before_join) {
+    int nv = 0;
+    for (int c0 = 0; c0 < cnt; c0 += 64) {
+        const int j = c0 + lane;
+        const unsigned key = j < cnt ? (unsigned)K[j] : 0xFFFFu;
+        const bool valid = key != 0xFFFFu;
+        const unsigned long long m = __ballot(valid);
+        SD_WAVE_SYNC();
+        if (valid) {
+            K[lanes_below(m, nv)] = (unsigned short)key;
+            atomicAdd(&L.Hset[key], 1u);
+        }
+        nv += __popcll(m);
+    }
+    SD_WAVE_SYNC();
+    if (nv < 3) return nv;
+    const float sum = kw_wave_sum_keys(K, nv, lane, L.leaf_off, L.leaf_sum);
+    // scan of the set's histogram, lane owns bins [16 lane, 16 lane + 16)
+    unsigned w[16];
+    kw_load_bins(L.Hset, lane, w);
+    int tot;
+    const int cum0 = kw_scan_bins(w, lane, tot) - tot;
+    // the median: the bins where the cumulative count crosses the middle positions
+    const int hh = nv >> 1;
+    const int bin1 = find_bin<0, ~0u>(L.Hset, lane, hh, cum0, tot);
+    const int bin0 = (nv & 1) ? bin1 : find_bin<0, ~0u>(L.Hset, lane, hh - 1, cum0, tot);      // wave-uniform branch
+    const float v0 = ps_of_key((float)bin0), v1 = ps_of_key((float)bin1);
+    med = (nv & 1) ? v1 : (v0 + v1) / 2.0f;      // np.median on float32
+    mean = sum / (float)nv;
+    SD_WAVE_SYNC();          // find_bin's readers are done with Hset
+    unsigned t[16];
+    kw_load_bins(L.Htot, lane, t);
+    before_join(w, t);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        reinterpret_cast<uint4*>(L.Htot)[lane * 4 + q] =
+            make_uint4(t[4 * q] + w[4 * q], t[4 * q + 1] + w[4 * q + 1], t[4 * q + 2] + w[4 * q + 2], t[4 * q + 3] + w[4 * q + 3]);
+        reinterpret_cast<uint4*>(L.Hset)[lane * 4 + q] = make_uint4(0, 0, 0, 0);
+    }
+    SD_WAVE_SYNC();
+    return nv;
+}
+
+// The workgroup's named LDS in the block kernels (the sort area K[P] is dynamic)
+struct KwBlockLds {
+    float leaf_sum[KW_LEAF_MAX];
+    float scratch8[KW_LEAF_MAX * 8];
+    int leaf_off[KW_LEAF_MAX + 1];
+    int wcnt[RB_THREADS / 64 + 1];
+    int sptr[KW_MAX_SETS + 1];
+    int nvs[KW_MAX_SETS];
+    int starts[KW_MAX_SETS + 1];
+    float meanS[KW_MAX_SETS], medS[KW_MAX_SETS];
+};
+
+// One row by the workgroup.  Per set: ordered compaction + numpy pairwise sum (the key area is the float buffer); false
+// (block-uniform) when a set keeps fewer than 3 values.  Otherwise sh.nvs / sh.meanS hold the sets' counts and means,
+// K[0..P) the 64-bit keys (set << 32 | order bits of the value) sorted ascending, NaNs and padding last, so set i is the
+// sorted run K[sh.starts[i] .. sh.starts[i + 1]), and sh.medS its np.median; ends with a barrier.
+__device__ __forceinline__ bool kw_block_sort_sets(const float* __restrict__ prow, const int32_t* __restrict__ cols, int k, int P,
+                                                   unsigned long long* K, KwBlockLds& sh) {
+    const int tid = threadIdx.x;
+    float* F = reinterpret_cast<float*>(K);
+    const int nsel = sh.sptr[k];
+    for (int i = 0; i < k; ++i) {
+        const int a = sh.sptr[i];
+        const int nv = block_compact(prow, cols + a, sh.sptr[i + 1] - a, F, sh.wcnt);
+        if (nv < 3) return false;                // block-uniform
+        // np.sum: 0 + the tree of the first KW_SUM_PIECE values (+ the tree of the rest), see kw_wave_sum_keys; the
+        // leading 0 makes a sum of -0.0 values +0.0 as numpy's is
+        float sum = 0.0f + block_pairwise_sum<KW_PW_DEPTH>(F, min(nv, KW_SUM_PIECE), sh.leaf_off, sh.leaf_sum, sh.scratch8, KW_LEAF_MAX);
+        if (nv > KW_SUM_PIECE)                   // block-uniform
+            sum += block_pairwise_sum<KW_PW_DEPTH>(F + KW_SUM_PIECE, nv - KW_SUM_PIECE, sh.leaf_off, sh.leaf_sum, sh.scratch8, KW_LEAF_MAX);
+        if (tid == 0) { sh.nvs[i] = nv; sh.meanS[i] = sum / (float)nv; }
+    }
+    // ---- keys (set, value), NaNs and padding last; sort; medians
+    for (int j = tid; j < P; j += RB_THREADS) {
+        unsigned long long key = ~0ull;
+        if (j < nsel) {
+            const float v = prow[cols[j]];
+            if (v == v) {
+                int lo = 0, hi = k;              // the set of selection j: last i with sptr[i] <= j
+                while (hi - lo > 1) { const int m = (lo + hi) >> 1; if (sh.sptr[m] <= j) lo = m; else hi = m; }
+                key = ((unsigned long long)lo << 32) | f32_ord(v);
+            }
+        }
+        K[j] = key;
+    }
+    if (tid == 0) {
+        int acc = 0;
+        for (int i = 0; i < k; ++i) { sh.starts[i] = acc; acc += sh.nvs[i]; }
+        sh.starts[k] = acc;
+    }
+    __syncthreads();
+    block_bitonic(P, [K](int i, int l, int desc) {
+        const bool asc = desc == 0;
+        const unsigned long long x = K[i], y = K[l];
+        if ((x > y) == asc) { K[i] = y; K[l] = x; }
+    });
+    if (tid < k) sh.medS[tid] = median_of_ord(K + sh.starts[tid], sh.nvs[tid]);        // np.median on float32
+    __syncthreads();
+    return true;
+}
+
 // Host: rows of one wave's chunk in the wave-per-row kernels -- as many (64 at most) as keeps every wave slot of the
 // chip (32 per CU) busy twice over
 inline int rows_per_chunk(int n_cu, int64_t n) {
@@ -432,6 +639,56 @@ inline int64_t row_launch_blocks(const sdice_ctx* ctx, int64_t n) { return std::
 inline int next_pow2(int v, int from) {
     while (from < v) from <<= 1;
     return from;
+}
+
+// Host: the checks the k-set entry points share (`fn` names the public call in the error); set_ptr is a HOST array
+inline int kw_check_sets(const char* fn, const int32_t* set_ptr, int32_t k, int32_t s) {
+    const char* msg = nullptr;
+    if (!set_ptr) msg = "set_ptr is NULL";
+    else if (!(k >= 2 && k <= KW_MAX_SETS)) msg = "the number of sets must be 2..64";
+    else if (set_ptr[0] != 0) msg = "set_ptr[0] must be 0";
+    for (int i = 0; !msg && i < k; ++i)
+        if (!(set_ptr[i + 1] > set_ptr[i])) msg = "empty set (set_ptr must increase)";
+    if (msg) {
+        sdice_set_error("kw_check_sets: %s", msg);
+        return SDICE_ERR_ARG;
+    }
+    if (set_ptr[k] > KW_MAX_N) {
+        sdice_set_error("%s: %d selected columns, at most %d are supported", fn, (int)set_ptr[k], KW_MAX_N);
+        return SDICE_ERR_ARG;
+    }
+    if (set_ptr[k] > s) {
+        sdice_set_error("kw_check_sets: more selected columns than the table has (a column belongs to one set only)");
+        return SDICE_ERR_ARG;
+    }
+    return SDICE_OK;
+}
+
+// Host: the sets as the kernels take them, the launch shape of a grid kernel over KwWaveLds and the sort length of a
+// block kernel
+struct KwPlan {
+    KwSets sets;
+    int leaf_cap, wstride, waves, P;
+    size_t grid_lds, block_lds;
+};
+inline KwPlan kw_plan(const int32_t* set_ptr, int k) {
+    KwPlan pl;
+    int maxset = 0;
+    for (int i = 0; i <= KW_MAX_SETS; ++i) pl.sets.ptr[i] = i <= k ? set_ptr[i] : set_ptr[k];
+    for (int i = 0; i < k; ++i) maxset = std::max(maxset, (int)(set_ptr[i + 1] - set_ptr[i]));
+    const int nsel = set_ptr[k];
+    // Leaves of the pairwise recursion over a piece of at most KW_SUM_PIECE values: after d halvings a part is at most
+    // piece / 2^d + 15 long, a leaf from 128 down
+    const int piece = std::min(maxset, KW_SUM_PIECE);
+    pl.leaf_cap = 1;
+    while (pl.leaf_cap < KW_LEAF_MAX && piece > 113 * pl.leaf_cap) pl.leaf_cap <<= 1;
+    pl.wstride = (int)((2 * KW_BINS * 4 + (2 * pl.leaf_cap + 1) * 4 + 2 * nsel + 15) & ~15);
+    const int waves = 64 * 1024 / pl.wstride;        // the workgroup is sized from the LDS a wave needs
+    pl.waves = waves > 4 ? 4 : (waves < 1 ? 1 : waves);
+    pl.grid_lds = (size_t)pl.waves * pl.wstride;
+    pl.P = next_pow2(nsel, 2);
+    pl.block_lds = (size_t)pl.P * 8;
+    return pl;
 }
 
 // Host: "no row can be tested" -- every field of the n rows is 0, queued on the context's stream

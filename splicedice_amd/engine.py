@@ -24,6 +24,8 @@ RANKSUM_FIELDS = [("tested", np.uint8), ("p", np.float64), ("z", np.float64), ("
 RANKSUM_EXACT_FIELDS = RANKSUM_FIELDS + [("exact", np.uint8)]                                # (the two --exact calls)
 KRUSKAL_FIELDS = [("tested", np.uint8), ("p", np.float64), ("h", np.float64), ("med", np.float32, PER_SET),
                   ("mean", np.float32, PER_SET), ("delta", np.float32)]
+JONCKHEERE_FIELDS = [("tested", np.uint8), ("p", np.float64), ("z", np.float64), ("j", np.float64),
+                     ("med", np.float32, PER_SET), ("mean", np.float32, PER_SET), ("delta", np.float32)]
 SPEARMAN_FIELDS = [("tested", np.uint8), ("p", np.float64), ("rho", np.float64), ("n_kept", np.int32), ("med", np.float32),
                    ("mean", np.float32)]
 GRAM_FIELDS = [("shared", np.int64), ("sum1", np.int64), ("sum2", np.int64), ("prod", np.int64)]
@@ -392,6 +394,19 @@ class Context:
               "sdice_kruskal")
         return out
 
+    def jonckheere(self, ps, sets):
+        """Jonckheere-Terpstra trend test per row across the k ORDERED column sets (set 0 < set 1 < ...) under the row rules
+        of kruskal(); un-compacted outputs: tested, p, z (> 0: the values rise along the order), j = J [n], med, mean
+        [k, n] and delta [n] as kruskal()'s."""
+        ps = _c(ps, np.float32)
+        n, s = ps.shape
+        cols, set_ptr = kruskal_sets(sets, s)
+        k = len(set_ptr) - 1
+        out = _zeros(JONCKHEERE_FIELDS, n, k)
+        check(self.lib.sdice_jonckheere(self.h, n, s, _ptr(ps), _ptr(cols), _ptr(set_ptr), k, *map(_ptr, out.values())),
+              "sdice_jonckheere")
+        return out
+
     def _signedrank(self, name, fields, ps, a, b):
         ps = _c(ps, np.float32)
         n, s = ps.shape
@@ -594,6 +609,14 @@ class Context:
         set_ptr = _c(set_ptr, np.int32)
         check(self.lib.sdice_kruskal_dev(self.h, n, s, d_ps.ptr, d_cols.ptr, _ptr(set_ptr), set_ptr.size - 1,
                                          *_dev_ptrs(KRUSKAL_FIELDS, out, "h")), "sdice_kruskal_dev")
+
+    def jonckheere_dev(self, d_ps, d_cols, set_ptr, out):
+        """d_cols: the device copy of kruskal_sets()'s cols; set_ptr: its HOST offsets; out: device tested, p, z, (j), med and
+        mean [k, n], delta"""
+        n, s = d_ps.shape
+        set_ptr = _c(set_ptr, np.int32)
+        check(self.lib.sdice_jonckheere_dev(self.h, n, s, d_ps.ptr, d_cols.ptr, _ptr(set_ptr), set_ptr.size - 1,
+                                            *_dev_ptrs(JONCKHEERE_FIELDS, out, "j")), "sdice_jonckheere_dev")
 
     def pair_table(self, s, pairs):
         """a pair list for the _dev calls: checked against s samples, packed and uploaded once -> DeviceArray uint32[m]
