@@ -12,13 +12,14 @@ from fractions import Fraction
 
 import numpy as np
 
+from rank_support import tree_sum
+
 SUM_PIECE = 8192        # np.getbufsize(): add.reduce hands the pairwise loop at most this many elements at a time
 
 
 def numpy_sum(a):
     """np.sum of a contiguous 1-D float32 array restated: pieces of SUM_PIECE values, each summed by numpy's pairwise
-    tree (tree_sum of test_gpu_count_sweeps), the pieces added left to right onto the identity 0"""
-    from test_gpu_count_sweeps import tree_sum
+    tree (tree_sum of rank_support), the pieces added left to right onto the identity 0"""
     total = np.float32(0.0)
     for at in range(0, a.size, SUM_PIECE):
         total = np.float32(total + tree_sum(a[at: at + SUM_PIECE]))

@@ -11,13 +11,15 @@
 """
 import argparse
 import os
+import sys
 
 import numpy as np
 import pytest
 
-from oracle import oracle_np as O
-from splicedice_amd import _cli
-from tests.test_pair_list_cpu import ListEngine, _args, _pair_file, _quiet
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from oracle import oracle_np as O  # noqa: E402
+from pair_fixtures import ListEngine, _args, _pair_file, _quiet  # noqa: E402
+from splicedice_amd import _cli  # noqa: E402
 
 
 # ------------------------------------------------------------------------------ engine_scope

@@ -5,11 +5,14 @@ methods as the HIP Context -- this test is about the distribution logic; the sam
 runs on the real engine in tests/test_gpu_distributed.py."""
 import os
 import socket
+import sys
 
 import numpy as np
 import pytest
 
-from oracle import oracle_np as O
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from oracle import oracle_np as O  # noqa: E402
+from pair_fixtures import _IntoComm, _RecEngine  # noqa: E402
 
 
 class OracleEngine:
@@ -308,96 +311,6 @@ def test_subcommands_under_two_rank_launcher(which, tmp_path, golden_dir):
 
 
 # ---------------------------------------------------------------- what step() and free() promise, on a recording engine
-class _RecArray:
-    """engine.DeviceArray's surface; every call that would reach the device is logged on the engine double"""
-
-    def __init__(self, eng, shape, dtype, ptr, owned):
-        self.ctx, self.ptr, self.owned, self.free_calls = eng, ptr, owned, 0
-        self.shape = tuple(int(x) for x in (shape if isinstance(shape, (tuple, list)) else (shape,)))
-        self.dtype = np.dtype(dtype)
-        self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
-
-    def to_host(self, out=None):
-        self.ctx.calls.append("to_host")
-        return np.zeros(self.shape, self.dtype)
-
-    def memset(self, byte):
-        self.ctx.calls.append("memset")
-        return self
-
-    def zero(self):
-        return self.memset(0)
-
-    def offset(self, lead, shape):
-        return _RecArray(self.ctx, shape, self.dtype, self.ptr + lead * self.dtype.itemsize, owned=False)
-
-    def free(self):
-        self.free_calls += 1
-        if self.owned and self.ptr:                              # (as DeviceArray: a view is never released)
-            self.ctx.released.append(self.ptr)
-            self.ptr = None
-
-
-class _RecEngine:
-    """the engine.Context methods the shard classes use: allocations hand out tracked arrays, the rest only log"""
-
-    def __init__(self):
-        self.calls, self.allocated, self.released, self.next_ptr = [], [], [], 1 << 40
-        self.list_ptr = self._address()                          # the context's own list buffer
-
-    def _address(self):
-        self.next_ptr += 1 << 40
-        return self.next_ptr
-
-    def empty(self, shape, dtype):
-        self.calls.append("empty")
-        self.allocated.append(_RecArray(self, shape, dtype, self._address(), owned=True))
-        return self.allocated[-1]
-
-    def to_device(self, host, dtype=None):
-        self.calls.append("to_device")
-        host = np.ascontiguousarray(host, dtype=dtype)
-        self.allocated.append(_RecArray(self, host.shape, host.dtype, self._address(), owned=True))
-        return self.allocated[-1]
-
-    def cluster_dev(self, *arrays, sync=True):
-        self.calls.append("cluster_dev")
-        self.views.append(_RecArray(self, (0,), np.int32, self.list_ptr, owned=False))
-        return self.views[-1], (3 if sync else None)
-
-    views = ()
-
-
-for _name in ("set_param", "sync", "ps_dev", "ranksum_dev", "fisher_pairs_dev", "chi2_pairs_dev", "bh_columns_dev",
-              "bh_columns_pitched_dev", "bh_masked_dev", "copy2d_dev", "comm_fork", "comm_join"):
-    setattr(_RecEngine, _name, lambda self, *a, _name=_name, **kw: self.calls.append(_name))
-
-
-class _IntoComm:
-    """RcclComm's surface at world 2: collectives into a buffer the caller owns; the allocating forms allocate"""
-    device = True
-
-    def __init__(self, eng, rank, world):
-        self.eng, self.rank, self.world = eng, rank, world
-
-    def allgather(self, x):
-        return self.eng.empty((self.world * x.shape[0],) + tuple(x.shape[1:]), x.dtype)
-
-    def alltoall(self, x):
-        return self.eng.empty(x.shape, x.dtype)
-
-    def allgather_into(self, x, recv):
-        self.eng.calls.append("allgather_into")
-        return recv
-
-    def alltoall_into(self, x, recv):
-        self.eng.calls.append("alltoall_into")
-        return recv
-
-    def allsum(self, value):
-        return int(value)
-
-
 _STEP_CASES = [("compare", None, None, None)] + [("pairwise", corr, test, groups)
                                                   for corr, test, groups in (("pairwise", "fisher", 1), ("pairwise", "fisher", 3),
                                                                              ("pairwise", "chi2", 1), ("pairwise", "chi2", 3),

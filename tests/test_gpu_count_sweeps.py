@@ -13,38 +13,22 @@ only at the counts random NaNs happen to leave.
 The CPU self-checks (not gpu-marked) show that the rank-sum fixtures tell numpy's tree from a sequential sum and from a
 tree that splits at n/2 without the multiple-of-8 adjustment.
 """
+import os
+import sys
 import warnings
 
 import numpy as np
 import pytest
 
-from oracle import oracle_np as O
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from oracle import oracle_np as O  # noqa: E402
+from rank_support import PLACEMENTS, _kept_positions, _values, tree_sum  # noqa: E402
 
 P_RTOL_TIGHT = 1e-9    # p-values (tests/test_gpu_parity.py); every other output below is bit-exact
 gpu = pytest.mark.gpu
 
 
 # ------------------------------------------------------------------------------ rank-sum fixtures
-PLACEMENTS = ("front", "back", "spread", "random")     # where a group's NaNs sit, in group (table) order
-
-
-def _kept_positions(g, nv, how, rng):
-    """positions (0..g-1, ascending) inside a group of g columns that keep a value; the others hold NaN"""
-    if how == "front":
-        return np.arange(g - nv, g)
-    if how == "back":
-        return np.arange(nv)
-    if how == "spread":
-        return np.round(np.linspace(0, g - 1, nv)).astype(np.int64)     # step >= 1: distinct
-    return np.sort(rng.choice(g, nv, replace=False))
-
-
-def _values(rng, k, flavour):
-    if flavour == "q3":          # 3-decimal PS values: the counting kernel's input for groups of 65..1024
-        return (rng.integers(0, 1001, size=k) / 1000.0).astype(np.float32)
-    return (rng.random(k) ** 4).astype(np.float32)
-
-
 def sweep_table(n1, n2, flavour, seed=0):
     """-> (ps float32[rows, n1 + n2], g1, g2, nv1, nv2).  Row pair i keeps nv1 = 3 + i % (n1 - 2) values of group 1
     and nv2 = n2 - i % (n2 - 2) of group 2, with two NaN placements per count; one row with nv1 = 2 before the
@@ -66,18 +50,6 @@ def sweep_table(n1, n2, flavour, seed=0):
     nv1 = np.array([a for a, _, _ in plan])
     nv2 = np.array([b for _, b, _ in plan])
     return ps, g1, g2, nv1, nv2
-
-
-def tree_sum(a, split8=True):
-    """numpy's float32 pairwise_sum: a leaf of <= 128 values is numpy's own leaf (8 accumulators), above that
-    n2 = n/2 - (n/2) % 8; split8=False drops the adjustment (a plausible wrong tree)"""
-    n = a.size
-    if n <= 128:
-        return np.add.reduce(a)
-    n2 = n // 2
-    if split8:
-        n2 -= n2 % 8
-    return np.float32(tree_sum(a[:n2], split8) + tree_sum(a[n2:], split8))
 
 
 # ------------------------------------------------------------------------------ CPU self-checks of the fixtures

@@ -10,7 +10,6 @@ and N <= 34, each as every kind of RS_KINDS; N = 33, 34 are the rows above the l
 and every n' = 0..34 as every kind of SR_KINDS.  The builders and their references are cached and shared with
 tests/test_gpu_exact_sweeps.py.  Tests without the gpu mark check on the CPU that the tables are what they claim."""
 import argparse
-import ctypes as C
 import functools
 import math
 import os
@@ -21,9 +20,10 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import exact_referee as ER  # noqa: E402
+import rank_support as RS  # noqa: E402
 import signedrank_referee as SR  # noqa: E402
-import test_gpu_signedrank as TS  # noqa: E402
 from oracle import oracle_np as O  # noqa: E402
+from rank_support import bits  # noqa: E402
 
 gpu = pytest.mark.gpu
 
@@ -37,11 +37,6 @@ SR_PAIRS = 34
 SR_KINDS = ("grid", "off-grid", "2 distinct |d|", "equal printed differences", "all positive", "all negative",
             "signed zeros", "an infinity", "subnormal differences")
 TINY = np.float32(1e-45)              # the smallest subnormal, 2^-149
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({1: np.uint8, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
 
 
 # ---------------------------------------------------------------- the rank-sum table
@@ -166,7 +161,7 @@ def sr_table():
     """-> (ps float32 [rows, 71], a, b, n' [rows], kind [rows]): every n' = 0..34 as every kind, the other pairs equal or
     dropped by a NaN on either side"""
     rng = np.random.default_rng(3431)
-    a, b, s = TS.draw_pairs(rng, SR_PAIRS)
+    a, b, s = RS.draw_pairs(rng, SR_PAIRS)
     rows, nps, kinds = [], [], []
     for n_prime in range(SR_PAIRS + 1):
         for kind in range(len(SR_KINDS)):
@@ -325,15 +320,9 @@ def test_host_and_dev_entry_points_agree(ctx, paired):
         assert np.array_equal(bits(host[name]), bits(dev[name])), name
 
 
-def _raw_call(ctx, paired, ps, c1, c2, n1, n2, outs):
-    ps = np.ascontiguousarray(ps, dtype=np.float32)
-    n, s = ps.shape
-    ptr = lambda v: v.ctypes.data_as(C.c_void_p)     # noqa: E731
-    c1, c2 = np.ascontiguousarray(c1, np.int32), np.ascontiguousarray(c2, np.int32)
-    o = [ptr(outs[x]) for x in OUTS]
-    if paired:
-        return ctx.lib.sdice_signedrank_exact(ctx.h, n, s, ptr(ps), ptr(c1), ptr(c2), n1, *o)
-    return ctx.lib.sdice_ranksum_exact(ctx.h, n, s, ptr(ps), ptr(c1), n1, ptr(c2), n2, *o)
+def _raw_call(ctx, paired, exact, ps, c1, c2, n1, n2, outs):
+    symbol = ("sdice_signedrank" if paired else "sdice_ranksum") + ("_exact" if exact else "")
+    return RS.raw_call(ctx, symbol, ps, (c1, c2, n1) if paired else (c1, n1, c2, n2), outs, OUTS if exact else OUTS[:-1])
 
 
 REFUSALS = [(False, "g1 index out of range"), (False, "g2 negative index"), (False, "negative group size"),
@@ -369,20 +358,14 @@ def test_refusals_leave_every_output_untouched(ctx, paired, case):
     ps = np.full((n, s), 0.5, dtype=np.float32)
     outs = {name: np.full(n, 7 + i, DTYPES[name]) for i, name in enumerate(OUTS)}
     before = {x: v.copy() for x, v in outs.items()}
-    rc = _raw_call(ctx, paired, ps, c1, c2, n1, n2, outs)
+    rc = _raw_call(ctx, paired, True, ps, c1, c2, n1, n2, outs)
     assert rc == -1, case                                   # SDICE_ERR_ARG
     assert ctx.lib.sdice_last_error()
     for x in outs:
         assert np.array_equal(outs[x], before[x]), (case, x)
     # the plain call refuses the same arguments
     plain = {x: v.copy() for x, v in before.items() if x != "exact"}
-    ptr = lambda v: v.ctypes.data_as(C.c_void_p)     # noqa: E731
-    a1, a2 = np.ascontiguousarray(c1, np.int32), np.ascontiguousarray(c2, np.int32)
-    o = [ptr(plain[x]) for x in OUTS[:-1]]
-    if paired:
-        assert ctx.lib.sdice_signedrank(ctx.h, n, s, ptr(ps), ptr(a1), ptr(a2), n1, *o) == -1
-    else:
-        assert ctx.lib.sdice_ranksum(ctx.h, n, s, ptr(ps), ptr(a1), n1, ptr(a2), n2, *o) == -1
+    assert _raw_call(ctx, paired, False, ps, c1, c2, n1, n2, plain) == -1
     ok = ctx.ranksum_exact(np.tile(np.array([0.1, 0.2, 0.3, 0.3, 0.1, 0.2], np.float32), (2, 1)), [0, 1, 2], [3, 4, 5])
     assert ok["tested"].tolist() == [1, 1] and ok["exact"].tolist() == [1, 1]       # the context still works
 
@@ -428,7 +411,7 @@ def test_cli_exact_byte_for_byte(ctx, golden_dir, tmp_path, paired, gtf):
     """test 6 of the issue: --exact and --paired --exact, with and without -a, on the 40-row table of the --paired test;
     the file equals the referee's table byte for byte"""
     from splicedice_amd import compare_sample_sets as css
-    table_path, m1, m2, names, matrix, a, b = TS._write_cli_inputs(tmp_path)
+    table_path, m1, m2, names, matrix, a, b = RS.write_paired_cli_inputs(tmp_path)
     out = str(tmp_path / "out.tsv")
     anno = os.path.join(golden_dir, "compare", "anno.gtf") if gtf else ""
     css.run_with(argparse.Namespace(psiSPLICEDICE=table_path, manifest1=m1, manifest2=m2, moreManifests=None, paired=paired,

@@ -17,113 +17,48 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import jonckheere_referee as JR  # noqa: E402
+import kset_fixtures as KF  # noqa: E402
+import rank_support as RS  # noqa: E402
+from kset_fixtures import CHS, PALETTE_S, _edge_rows, _zero_sum_rows, draw_sets, palette, palette_index  # noqa: E402
 from oracle import oracle_np as O  # noqa: E402
-from test_gpu_kruskal_sweeps import (CHS, PALETTE_S, _edge_rows, _on_grid, _scatter, _twin, _zero_sum_rows,  # noqa: E402
-                                     chunk_table_rows, palette, palette_index)
+from rank_support import N_LIMIT, P_FLOOR, P_RTOL, chunk_table_rows  # noqa: E402
+from rank_support import bits as _bits, on_grid as _on_grid, scatter as _scatter, twin as _twin  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 Z_TOL = 1e-12
-P_RTOL = 1e-9
-P_FLOOR = 1e-280
-N_LIMIT = 16384                     # selected columns per row the library supports (include/sdice.h)
 KS = (2, 3, 4, 5, 8, 16, 33, 64)
 SIZE_RANGES = ((3, 6), (3, 40), (3, 300))
 SHAPES = ("uniform", "shifted", "ties", "cluster", "trend")
 FLOAT_FIELDS = ("med", "mean", "delta")
-
-
-def _bits(a):
-    return a.view({1: np.uint8, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-
-
-# ------------------------------------------------------------------------------ tables (test_gpu_kruskal.py's, restated)
-def _draw_sets(rng, k, lo, hi, spare=3):
-    """k disjoint column lists of lo..hi columns in a shuffled table of sum + spare columns"""
-    sizes = rng.integers(lo, hi + 1, size=k)
-    s = int(sizes.sum()) + spare
-    perm = rng.permutation(s)
-    sets, at = [], 0
-    for m in sizes:
-        sets.append(perm[at: at + m].astype(np.int32))
-        at += int(m)
-    return sets, s
-
-
-def _values(rng, shape, sets, s, hi):
-    """one row of values in [0, 1] before rounding / NaNs"""
-    if shape == "uniform":
-        return rng.random(s)
-    if shape == "ties":
-        return rng.choice([0.0, 0.5, 1.0], size=s, p=[0.4, 0.2, 0.4])
-    if shape == "cluster":
-        return 0.5 + 0.004 * rng.standard_normal(s)
-    row = rng.random(s)
-    if shape == "trend":            # set i centred at 0.5 + a (i / (k - 1) - 1/2), a = U(-6, 6) / sqrt(N), noise 0.1
-        k, N = len(sets), sum(g.size for g in sets)
-        a = rng.uniform(-6.0, 6.0) / np.sqrt(N)
-        for i, g in enumerate(sets):
-            row[g] = 0.5 + a * (i / (k - 1) - 0.5) + 0.1 * rng.standard_normal(g.size)
-        return row
-    for g in sets:                  # shifted normals: set means apart by about two standard errors of a set mean
-        row[g] = 0.5 + 0.3 * rng.standard_normal() / np.sqrt(hi) + 0.15 * rng.standard_normal(g.size)
-    return row
+OUTS = ("tested", "p", "z", "j", "med", "mean", "delta")
 
 
 def _table(rng, sets, s, hi, rows_per_shape, grid):
-    rows = []
-    for shape in SHAPES:
-        for r in range(rows_per_shape):
-            v = np.clip(_values(rng, shape, sets, s, hi), 0.0, 1.0)
-            if grid:
-                row = (np.rint(v * 1000.0) / 1000.0).astype(np.float32)       # float32(k / 1000.0)
-            else:
-                row = (v * 1.7 - 0.3).astype(np.float32)                       # off the grid, some outside [0, 1]
-                row += rng.random(s, dtype=np.float32) * np.float32(1e-3)      # random mantissas
-                dup = rng.integers(0, s, size=(max(2, s // 6), 2))             # some exact duplicates
-                row[dup[:, 0]] = row[dup[:, 1]]
-            if r % 3 != 0:
-                row[rng.random(s) < 0.06] = np.nan
-            if r % 3 == 2 and shape in ("uniform", "trend"):                   # one set falls below 3 values
-                g = sets[int(rng.integers(len(sets)))]
-                row[g[2:]] = np.nan
-            rows.append(row)
-    return np.ascontiguousarray(np.stack(rows))
+    return KF.table(rng, sets, s, hi, rows_per_shape, grid, SHAPES, lambda shape, r: r % 3 == 2 and shape in ("uniform", "trend"))
 
 
 # ------------------------------------------------------------------------------ comparison
 def _check(got, ref, label, kw=None):
     """every bar on every row -> (tested rows, cells below the p floor, worst z error, worst relative p error)"""
-    bad = np.flatnonzero(got["tested"] != ref["tested"])
-    assert bad.size == 0, (label, "tested", bad[:5].tolist())
-    t = ref["tested"].astype(bool)
-    for name in FLOAT_FIELDS:
-        for other, who in ((ref, "numpy"), (kw, "kruskal")):
-            if other is None:
-                continue
-            bad = np.argwhere(_bits(got[name]) != _bits(other[name]))
-            assert bad.size == 0, (label, name, who, len(bad), bad[:5].tolist())
+    t = RS.check_common(got, ref, FLOAT_FIELDS, ("p", "z", "j"), label)
     if kw is not None:
         assert np.array_equal(got["tested"], kw["tested"]), label
-    for name in ("p", "z", "j"):
-        assert not _bits(got[name])[~t].any(), (label, name, "untested rows")
+        for name in FLOAT_FIELDS:
+            RS.assert_same_bits(got[name], kw[name], (label, name, "kruskal"))
     bad = np.flatnonzero(got["j"] != ref["j"])
     assert bad.size == 0, (label, "j", bad[:5].tolist(), got["j"][bad[:5]], ref["j"][bad[:5]])
     z, zr = got["z"][t], ref["z"][t]
     err_z = np.abs(z - zr) / np.maximum(1.0, np.abs(zr))
     worst_z = float(err_z.max()) if err_z.size else 0.0
     zero = ref["zero_num"][t]
-    p, pr = got["p"][t], ref["p"][t]
-    cell = pr >= P_FLOOR
-    err_p = np.abs(p[cell] - pr[cell]) / pr[cell]
-    worst_p = float(err_p.max()) if err_p.size else 0.0
-    print(f"{label}: rows {t.size} tested {int(t.sum())} worst z err {worst_z:.3g} largest |z| {np.abs(zr).max() if zr.size else 0:.3g} "
-          f"worst p rel {worst_p:.3g} smallest p {pr.min() if pr.size else 1:.3g} below floor {int((~cell).sum())}")
+    p = got["p"][t]
+    print(f"{label}: rows {t.size} tested {int(t.sum())} worst z err {worst_z:.3g} largest |z| {np.abs(zr).max() if zr.size else 0:.3g}",
+          end=" ")
     assert worst_z <= Z_TOL, (label, "z", worst_z)
     assert not _bits(z)[zero].any() and np.all(p[zero] == 1.0), (label, "zero numerator")
-    assert worst_p <= P_RTOL, (label, "p", worst_p)
-    assert np.all(p[~cell] < 2 * P_FLOOR), label
-    return int(t.sum()), int((~cell).sum()), worst_z, worst_p
+    below, worst_p = RS.check_p(p, ref["p"][t], label)
+    return int(t.sum()), below, worst_z, worst_p
 
 
 def _both(ctx, ps, sets, grid, label):
@@ -142,14 +77,15 @@ def test_parity(ctx, grid):
     tested = below = 0
     for k in KS:
         for lo, hi in SIZE_RANGES:
-            sets, s = _draw_sets(rng, k, lo, hi)
+            sets, s = draw_sets(rng, k, lo, hi)
             assert sum(g.size for g in sets) <= N_LIMIT
             ps = _table(rng, sets, s, hi, 3, grid)
             assert bool(np.all(_on_grid(ps[:, np.concatenate(sets)]))) == grid
             _, (a, b, _, _) = _both(ctx, ps, sets, grid, f"{'grid' if grid else 'general'} k={k} sizes {lo}..{hi}")
             tested += a
             below += b
-    assert tested > 250 and below <= 0.01 * tested, (tested, below)
+    assert tested > 250, tested
+    RS.check_floor_share(tested, below, "parity")
 
 
 @pytest.mark.parametrize("grid", [True, False], ids=["grid", "general"])
@@ -157,7 +93,7 @@ def test_every_set_count(ctx, grid):
     """every k = 2..64 with sets of 3..5 columns, five rows each (one per value shape): the lane-per-set bookkeeping at each k"""
     rng = np.random.default_rng(1813 + grid)
     for k in range(2, 65):
-        sets, s = _draw_sets(rng, k, 3, 5, spare=2)
+        sets, s = draw_sets(rng, k, 3, 5, spare=2)
         ps = _table(rng, sets, s, 5, 1, grid)
         _both(ctx, ps, sets, grid, f"k={k}")
 
@@ -245,7 +181,7 @@ def test_rows_at_the_limit(ctx, split, grid):
 @functools.lru_cache(maxsize=None)
 def _symmetry_table():
     rng = np.random.default_rng(1816)
-    sets, s = _draw_sets(rng, 5, 4, 12, spare=4)
+    sets, s = draw_sets(rng, 5, 4, 12, spare=4)
     grid = _table(rng, sets, s, 12, 7, True)[:32]
     off = _table(rng, sets, s, 12, 7, False)[:32]
     return np.ascontiguousarray(np.concatenate([grid, off])), sets, s
@@ -397,15 +333,6 @@ def test_p_ladder(ctx):
 
 
 # ------------------------------------------------------------------------------ refusals
-def _raw_call(ctx, ps, cols, set_ptr, k, outs):
-    ps = np.ascontiguousarray(ps, dtype=np.float32)
-    n, s = ps.shape
-    ptr = lambda a: a.ctypes.data_as(C.c_void_p)     # noqa: E731
-    cols, set_ptr = np.ascontiguousarray(cols, np.int32), np.ascontiguousarray(set_ptr, np.int32)
-    return ctx.lib.sdice_jonckheere(ctx.h, n, s, ptr(ps), ptr(cols), ptr(set_ptr), k, *[ptr(outs[x]) for x in
-                                    ("tested", "p", "z", "j", "med", "mean", "delta")])
-
-
 @pytest.mark.parametrize("case", ["k=1", "k=65", "empty set", "N over the limit", "column in two sets"])
 def test_errors_leave_the_outputs_untouched(ctx, case):
     n = 3
@@ -424,7 +351,7 @@ def test_errors_leave_the_outputs_untouched(ctx, case):
     outs = dict(tested=np.full(n, 7, np.uint8), p=np.full(n, -3.0), z=np.full(n, -4.0), j=np.full(n, -8.0),
                 med=np.full((kk, n), -5.0, np.float32), mean=np.full((kk, n), -6.0, np.float32), delta=np.full(n, -7.0, np.float32))
     before = {x: v.copy() for x, v in outs.items()}
-    rc = _raw_call(ctx, ps, cols, set_ptr, k, outs)
+    rc = RS.raw_call(ctx, "sdice_jonckheere", ps, (cols, set_ptr, k), outs, OUTS)
     assert rc < 0, case
     assert ctx.lib.sdice_last_error()
     for x in outs:
@@ -447,7 +374,7 @@ def _write_cli_inputs(tmp_path):
     columns belong to no set): rising, falling and flat rows, heavy ties, all-equal rows, rows with a starved set"""
     rng = np.random.default_rng(1819)
     n, s = 120, 20
-    samples = [f"samp{j}" for j in range(s)]
+    samples, _ = RS.ps_names(n, s)
     member = np.array([0, 1, 2, 0, 1, 2, 0, 1, 2, 0, 1, 2, 0, 1, 2, 0, 1, 2, -1, -1])
     slope = rng.uniform(-0.25, 0.25, size=(n, 1)) * (np.arange(n)[:, None] % 3 != 0)
     v = np.clip(0.5 + slope * (member[None, :] - 1) + 0.12 * rng.standard_normal((n, s)), 0, 1)
@@ -455,21 +382,11 @@ def _write_cli_inputs(tmp_path):
     text = np.where(rng.random((n, s)) < 0.07, "nan", np.char.mod("%.3f", v))
     text[20:26] = "0.500"                                                  # all-equal rows stay in the table
     text[30:36][:, np.flatnonzero(member == 1)[1:]] = "nan"                # the second set keeps one value: rows dropped
-    names = [f"chr1:{1000 + 10 * i}-{2000 + 10 * i}:+" for i in range(n)]
-    table = tmp_path / "in_allPS.tsv"
-    with open(table, "w") as f:
-        f.write("cluster\t" + "\t".join(samples) + "\n")
-        for i in range(n):
-            f.write(names[i] + "\t" + "\t".join(text[i]) + "\n")
     groups = [[samples[j] for j in np.flatnonzero(member == i)] for i in range(3)]
     groups[1] = groups[1][::-1] + ["not_in_the_table"]
-    manifests = []
-    for i, g in enumerate(groups):
-        p = tmp_path / f"m{i + 1}.tsv"
-        p.write_text("".join(f"{x}\tpath\tmeta\tA\n" for x in g))
-        manifests.append(str(p))
+    path, manifests, names = RS.write_ps_inputs(tmp_path, text, [(g, "A") for g in groups])
     matrix = text.astype(np.float64).astype(np.float32)
-    return str(table), manifests, [np.flatnonzero(member == i) for i in range(3)], names, matrix
+    return path, manifests, [np.flatnonzero(member == i) for i in range(3)], names, matrix
 
 
 @pytest.mark.parametrize("gtf", [False, True])

@@ -5,7 +5,6 @@ Bars: tested mask, medians, means and delta bit-exact agai
 exact rational; p within 1e-9 relative wherever the referee's p >= 1e-280, and those excluded cells are at most 1 % of
 the tested rows (asserted)."""
 import argparse
-import ctypes as C
 import os
 import sys
 
@@ -14,85 +13,32 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kruskal_referee as KR  # noqa: E402
+import kset_fixtures as KF  # noqa: E402
+import rank_support as RS  # noqa: E402
 from oracle import oracle_np as O  # noqa: E402
+from rank_support import N_LIMIT, P_RTOL  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 H_RTOL = 1e-12
-P_RTOL = 1e-9
-P_FLOOR = 1e-280
-N_LIMIT = 16384                     # selected columns per row the library supports (include/sdice.h)
 KS = (3, 4, 5, 8, 16, 33, 64)
 SIZE_RANGES = ((3, 6), (3, 40), (3, 300))
 SHAPES = ("uniform", "shifted", "ties", "cluster")
-
-
-def _draw_sets(rng, k, lo, hi, spare=3):
-    """k disjoint column lists of lo..hi columns in a shuffled table of sum + spare columns"""
-    sizes = rng.integers(lo, hi + 1, size=k)
-    s = int(sizes.sum()) + spare
-    perm = rng.permutation(s)
-    sets, at = [], 0
-    for m in sizes:
-        sets.append(perm[at: at + m].astype(np.int32))
-        at += int(m)
-    return sets, s
-
-
-def _values(rng, shape, sets, s, hi):
-    """one row of values in [0, 1] before rounding / NaNs"""
-    if shape == "uniform":
-        return rng.random(s)
-    if shape == "ties":
-        return rng.choice([0.0, 0.5, 1.0], size=s, p=[0.4, 0.2, 0.4])
-    if shape == "cluster":
-        return 0.5 + 0.004 * rng.standard_normal(s)
-    row = rng.random(s)             # shifted normals: set means apart by about two standard errors of a set mean
-    for g in sets:
-        row[g] = 0.5 + 0.3 * rng.standard_normal() / np.sqrt(hi) + 0.15 * rng.standard_normal(g.size)
-    return row
+OUTS = ("tested", "p", "h", "med", "mean", "delta")
 
 
 def _table(rng, sets, s, hi, rows_per_shape, grid):
-    rows = []
-    for shape in SHAPES:
-        for r in range(rows_per_shape):
-            v = np.clip(_values(rng, shape, sets, s, hi), 0.0, 1.0)
-            if grid:
-                row = (np.rint(v * 1000.0) / 1000.0).astype(np.float32)       # float32(k / 1000.0)
-            else:
-                row = (v * 1.7 - 0.3).astype(np.float32)                       # off the grid, some outside [0, 1]
-                row += rng.random(s, dtype=np.float32) * np.float32(1e-3)      # random mantissas
-                dup = rng.integers(0, s, size=(max(2, s // 6), 2))             # some exact duplicates
-                row[dup[:, 0]] = row[dup[:, 1]]
-            if r % 3 != 0:
-                row[rng.random(s) < 0.06] = np.nan
-            if r % 6 == 5:          # one set falls below 3 values
-                g = sets[int(rng.integers(len(sets)))]
-                row[g[2:]] = np.nan
-            rows.append(row)
-    return np.ascontiguousarray(np.stack(rows))
+    return KF.table(rng, sets, s, hi, rows_per_shape, grid, SHAPES, lambda shape, r: r % 6 == 5)
 
 
 def _check(got, ref, label):
     """-> (tested rows, cells below the p floor); asserts every bar"""
-    assert np.array_equal(got["tested"], ref["tested"]), label
-    t = ref["tested"].astype(bool)
-    for name in ("med", "mean"):
-        assert np.array_equal(got[name].view(np.uint32), ref[name].view(np.uint32)), (label, name)
-    assert np.array_equal(got["delta"].view(np.uint32), ref["delta"].view(np.uint32)), label
-    assert not got["p"][~t].any() and not got["h"][~t].any(), label
+    t = RS.check_common(got, ref, ("med", "mean", "delta"), ("p", "h"), label)
     h, hr = got["h"][t], ref["hf"][t]
     err_h = np.abs(h - hr) / np.where(hr > 0, hr, 1.0)
     print(f"{label}: rows {t.size} tested {int(t.sum())} worst H rel {err_h.max() if err_h.size else 0:.3g}", end=" ")
     assert np.all(err_h <= H_RTOL), (label, float(err_h.max()))
-    p, pr = got["p"][t], ref["p"][t]
-    cell = pr >= P_FLOOR
-    err_p = np.abs(p[cell] - pr[cell]) / pr[cell]
-    print(f"worst p rel {err_p.max() if err_p.size else 0:.3g} smallest p {pr.min() if pr.size else 1:.3g} below floor {int((~cell).sum())}")
-    assert np.all(err_p <= P_RTOL), (label, float(err_p.max()))
-    assert np.all(p[~cell] < 2 * P_FLOOR), label
-    return int(t.sum()), int((~cell).sum())
+    return int(t.sum()), RS.check_p(got["p"][t], ref["p"][t], label)[0]
 
 
 def _parity(ctx, grid, seed, rows_per_shape):
@@ -100,14 +46,14 @@ def _parity(ctx, grid, seed, rows_per_shape):
     tested = below = 0
     for k in KS:
         for lo, hi in SIZE_RANGES:
-            sets, s = _draw_sets(rng, k, lo, hi)
+            sets, s = KF.draw_sets(rng, k, lo, hi)
             assert sum(g.size for g in sets) <= N_LIMIT
             ps = _table(rng, sets, s, hi, rows_per_shape, grid)
             got = ctx.kruskal(ps, sets)
             a, b = _check(got, KR.table_reference(ps, sets, grid), f"{'grid' if grid else 'general'} k={k} sizes {lo}..{hi}")
             tested += a
             below += b
-    assert tested > 0 and below <= 0.01 * tested, (tested, below)
+    RS.check_floor_share(tested, below, "parity")
 
 
 def test_parity_grid_path(ctx):
@@ -208,15 +154,6 @@ def test_all_equal_rows(ctx):
     assert np.array_equal(got["med"], np.repeat(ps[:, :1], 3, axis=1).T)
 
 
-def _raw_call(ctx, ps, cols, set_ptr, k, outs):
-    ps = np.ascontiguousarray(ps, dtype=np.float32)
-    n, s = ps.shape
-    ptr = lambda a: a.ctypes.data_as(C.c_void_p)     # noqa: E731
-    cols, set_ptr = np.ascontiguousarray(cols, np.int32), np.ascontiguousarray(set_ptr, np.int32)
-    return ctx.lib.sdice_kruskal(ctx.h, n, s, ptr(ps), ptr(cols), ptr(set_ptr), k, *[ptr(outs[x]) for x in
-                                 ("tested", "p", "h", "med", "mean", "delta")])
-
-
 @pytest.mark.parametrize("case", ["k=1", "k=65", "empty set", "N over the limit", "column in two sets"])
 def test_errors_leave_the_outputs_untouched(ctx, case):
     n = 3
@@ -235,7 +172,7 @@ def test_errors_leave_the_outputs_untouched(ctx, case):
     outs = dict(tested=np.full(n, 7, np.uint8), p=np.full(n, -3.0), h=np.full(n, -4.0), med=np.full((kk, n), -5.0, np.float32),
                 mean=np.full((kk, n), -6.0, np.float32), delta=np.full(n, -7.0, np.float32))
     before = {x: v.copy() for x, v in outs.items()}
-    rc = _raw_call(ctx, ps, cols, set_ptr, k, outs)
+    rc = RS.raw_call(ctx, "sdice_kruskal", ps, (cols, set_ptr, k), outs, OUTS)
     assert rc < 0, case
     assert ctx.lib.sdice_last_error()
     for x in outs:
@@ -256,7 +193,7 @@ def test_engine_refuses_a_column_in_two_sets_before_any_launch(ctx):
 def _write_cli_inputs(tmp_path):
     rng = np.random.default_rng(4242)
     n, s = 300, 24
-    samples = [f"samp{j}" for j in range(s)]
+    samples, _ = RS.ps_names(n, s)
     v = rng.integers(0, 1001, size=(n, s)) / 1000.0
     v[:, 6:12] = np.clip(v[:, 6:12] * 0.7 + 0.2 * rng.random((n, 1)), 0, 1)
     v[:40] = np.round(v[:40] * 2) / 2                                     # heavy ties
@@ -264,19 +201,9 @@ def _write_cli_inputs(tmp_path):
     text = np.where(rng.random((n, s)) < 0.08, "nan", np.char.mod("%.3f", v))
     text[40:50] = "0.500"
     text[60:70, 0:5] = "nan"                                              # the first set keeps one value: rows dropped
-    names = [f"chr1:{1000 + 10 * i}-{2000 + 10 * i}:+" for i in range(n)]
-    table = tmp_path / "in_allPS.tsv"
-    with open(table, "w") as f:
-        f.write("cluster\t" + "\t".join(samples) + "\n")
-        for i in range(n):
-            f.write(names[i] + "\t" + "\t".join(text[i]) + "\n")
     groups = [samples[0:6], samples[6:12] + ["not_in_the_table"], samples[12:17], samples[17:23]]
-    manifests = []
-    for i, g in enumerate(groups):
-        p = tmp_path / f"m{i + 1}.tsv"
-        p.write_text("".join(f"{x}\tpath\tmeta\tA\n" for x in g))
-        manifests.append(str(p))
-    return str(table), manifests, groups, samples, names
+    table, manifests, names = RS.write_ps_inputs(tmp_path, text, [(g, "A") for g in groups])
+    return table, manifests, groups, samples, names
 
 
 @pytest.mark.parametrize("gtf", [False, True])

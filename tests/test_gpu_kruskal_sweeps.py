@@ -29,67 +29,30 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kruskal_referee as KR  # noqa: E402
-from test_gpu_count_sweeps import PLACEMENTS, _kept_positions, _values, tree_sum  # noqa: E402
+import rank_support as RS  # noqa: E402
+from kset_fixtures import (CHS, KINDS, PALETTE_S, PER_KIND, _edge_rows, _zero_sum_rows, palette, palette_index)  # noqa: E402
+from rank_support import (N_LIMIT, NOMINAL_CUS, P_FLOOR, PLACEMENTS, _kept_positions, _values, chunk_table_rows, tree_sum)  # noqa: E402
+from rank_support import bits as _bits, on_grid as _on_grid, scatter as _scatter, twin as _twin  # noqa: E402
 
 gpu = pytest.mark.gpu
 
 H_RTOL = 1e-12
-P_RTOL = 1e-9
-P_FLOOR = 1e-280
-N_LIMIT = 16384                     # selected columns per row the library supports (include/sdice.h)
 FLAVOURS = ("q3", "cont")           # 3-decimal values: the histogram kernel; random ** 4: the sorting kernel
 
 
 # ------------------------------------------------------------------------------ comparison
-def _bits(a):
-    return a.view(np.uint32 if a.dtype == np.float32 else np.uint64)
-
-
 def _check(got, ref, label, nv=None, p_ref=None):
     """every bar on every row -> (worst relative H error, worst relative p error at or above the floor);
-    p_ref: the referee's p where it is not ref["p"] (floats; mpmath's on the ladder)"""
-    bad = np.flatnonzero(got["tested"] != ref["tested"])
-    assert bad.size == 0, (label, "tested", bad.size, bad[:5].tolist())
-    t = ref["tested"].astype(bool)
-    for name in ("med", "mean", "delta"):
-        bad = np.argwhere(_bits(got[name]) != _bits(ref[name]))
-        rows = bad[:, -1]
-        assert bad.size == 0, (label, name, f"{len(bad)} cells differ", "rows", rows[:8].tolist(),
-                               "kept values of the swept set", None if nv is None else nv[rows[:8]].tolist())
-    assert not got["p"][~t].any() and not got["h"][~t].any(), label
+    p_ref: the referee's p where it is not ref["p"] (floats; mpmath's on the ladder); nv: the kept values of the swept
+    set per row, named in a failure message"""
+    t = RS.check_common(got, ref, ("med", "mean", "delta"), ("p", "h"), label,
+                        where=None if nv is None else lambda rows: ("kept values of the swept set", nv[rows].tolist()))
     h, hr = got["h"][t], ref["hf"][t]
     err_h = np.abs(h - hr) / np.where(hr > 0, hr, 1.0)
     worst_h = float(err_h.max()) if err_h.size else 0.0
+    print(f"{label}: rows {t.size} tested {int(t.sum())} worst H rel {worst_h:.3g}", end=" ")
     assert worst_h <= H_RTOL, (label, "H", worst_h)
-    p, pr = got["p"][t], (ref["p"] if p_ref is None else p_ref)[t]
-    cell = pr >= P_FLOOR
-    err_p = np.abs(p[cell] - pr[cell]) / pr[cell]
-    worst_p = float(err_p.max()) if err_p.size else 0.0
-    print(f"{label}: rows {t.size} tested {int(t.sum())} worst H rel {worst_h:.3g} worst p rel {worst_p:.3g} "
-          f"smallest p {pr.min() if pr.size else 1:.3g} below floor {int((~cell).sum())}")
-    assert worst_p <= P_RTOL, (label, "p", worst_p)
-    assert np.all(p[~cell] < 2 * P_FLOOR), label
-    return worst_h, worst_p
-
-
-def _on_grid(v):
-    """the grid kernel's own question restated: is the value float32(key / 1000) of its clamped key (NaN: yes)"""
-    kf = np.clip(np.rint(v * np.float32(1000.0)), 0.0, 1000.0)
-    return np.isnan(v) | ((kf.astype(np.float64) / 1000.0).astype(np.float32) == v)
-
-
-def _twin(ps, cols):
-    """the off-grid twin of a 3-decimal table: x -> x * float32(0.9) + float32(0.0123) in float32.  The map is strictly
-    increasing over the 1001 grid values, so it keeps the order and the ties of every row; every row with a kept value
-    among `cols` gets a value off the grid there, so the grid kernel hands the whole table to the sorting kernel."""
-    grid = (np.arange(1001) / 1000.0).astype(np.float32)
-    image = grid * np.float32(0.9) + np.float32(0.0123)
-    assert image.dtype == np.float32 and np.all(np.diff(image) > 0)
-    assert np.all(_on_grid(ps[:, cols]))
-    tw = ps * np.float32(0.9) + np.float32(0.0123)
-    kept = ~np.isnan(ps[:, cols]).all(axis=1)
-    assert np.all((~_on_grid(tw[:, cols])).any(axis=1) == kept)
-    return np.ascontiguousarray(tw)
+    return worst_h, RS.check_p(got["p"][t], (ref["p"] if p_ref is None else p_ref)[t], label)[1]
 
 
 def _numpy_fields(ps, sets):
@@ -291,71 +254,6 @@ def test_kruskal_large_set_sweep(ctx, G, flavour):
 
 
 # ------------------------------------------------------------------------------ C: rows per wave
-KINDS = ("grid tested", "grid starved", "off-grid tested", "off-grid starved", "all equal on the grid",
-         "all equal off the grid", "grid with NaNs")
-PER_KIND = 40
-PALETTE_S = 20
-NOMINAL_CUS = 256
-CHS = (64, 32, 8, 2)
-
-
-def palette():
-    """-> (rows float32[7 * 40, 20], sets, kind[280]): k = 3 sets of 4, 5 and 6 of the 20 columns (interleaved); the
-    five other columns hold values that would show if they were read"""
-    rng = np.random.default_rng(64328)
-    perm = rng.permutation(PALETTE_S)
-    sets = [np.sort(perm[:4]).astype(np.int32), np.sort(perm[4:9]).astype(np.int32), np.sort(perm[9:15]).astype(np.int32)]
-    other = perm[15:]
-    rows = np.empty((len(KINDS) * PER_KIND, PALETTE_S), np.float32)
-    for r in range(rows.shape[0]):
-        kind = KINDS[r // PER_KIND]
-        v = r % PER_KIND
-        if kind.startswith("all equal"):
-            row = np.full(PALETTE_S, _values(rng, 1, "q3" if kind.endswith("on the grid") else "cont")[0], np.float32)
-        else:
-            row = _values(rng, PALETTE_S, "q3" if kind.startswith("grid") else "cont")
-            if v % 4 == 1:                                   # ties across sets
-                row[rng.integers(0, PALETTE_S, 6)] = row[rng.integers(0, PALETTE_S, 6)]
-        g = sets[v % 3]
-        if kind.endswith("starved"):
-            row[g[2:]] = np.nan                              # the set keeps two values
-            if v % 2:
-                row[sets[(v + 1) % 3][0]] = np.nan
-        elif kind == "grid with NaNs" or (kind == "off-grid tested" and v % 2):
-            row[g[rng.integers(0, g.size)]] = np.nan          # every set still keeps >= 3
-            if v % 2:
-                row[sets[2][rng.integers(0, 3, 2)]] = np.nan
-        row[other] = rng.choice(np.array([np.nan, 1e30, -7.0, 0.12345], np.float32), size=other.size)
-        rows[r] = row
-    return rows, sets, np.repeat(np.arange(len(KINDS)), PER_KIND)
-
-
-def rows_per_wave(n, compute_units):
-    """the rule of sdice_kruskal_dev: the largest ch of 64, 32, .. 1 with ceil(n / ch) >= 2 * 32 * compute_units"""
-    ch = 64
-    while ch > 1 and -(-n // ch) < 2 * 32 * compute_units:
-        ch >>= 1
-    return ch
-
-
-def chunk_table_rows(ch, compute_units):
-    """the smallest n that selects ch, plus 37 rows (38 where 37 would fill the last chunk: ch = 2)"""
-    n = 64 * compute_units * ch - (ch - 1)
-    assert rows_per_wave(n, compute_units) == ch and rows_per_wave(n - 1, compute_units) == ch // 2
-    n += 37
-    n += n % ch == 0
-    assert rows_per_wave(n, compute_units) == ch and n % ch
-    return n
-
-
-def palette_index(n):
-    """row r takes kind (r + r // 64) % 7: a 64-row chunk cycles through all kinds, and the kind at a chunk's positions
-    0 and 63 moves on by two from chunk to chunk; the variant inside the kind is seeded"""
-    r = np.arange(n, dtype=np.int64)
-    kind = (r + r // 64) % len(KINDS)
-    return kind * PER_KIND + np.random.default_rng(n).integers(0, PER_KIND, size=n)
-
-
 def test_palette_kinds_are_what_they_claim():
     rows, sets, kind = palette()
     ref = KR.table_reference(rows, sets, False)
@@ -394,10 +292,6 @@ def test_palette_index_arrangement(ch):
         stride_rows = 256 * 8 * NOMINAL_CUS                     # where the sorting kernel's grid-stride loop starts
         assert n > stride_rows and n * PALETTE_S * 4 < 90e6
         assert set(kind[stride_rows:].tolist()) == set(range(len(KINDS)))
-
-
-def _scatter(ref, idx):
-    return {name: np.ascontiguousarray(v[..., idx]) for name, v in ref.items()}
 
 
 @gpu
@@ -529,57 +423,6 @@ def test_kruskal_p_ladder_every_df(ctx):
 
 
 # ------------------------------------------------------------------------------ E: edge values
-def _edge_rows():
-    """-> (ps float32[rows, 16], sets, names).  Sets: columns 0..5, 6..10, 11..15.  A row named `... / sorted` is the row
-    before it with one value moved up by an ulp, which takes it off the grid and to the sorting kernel."""
-    f = np.float32
-    up = lambda x: np.nextafter(f(x), f(np.inf))                # noqa: E731
-    down = lambda x: np.nextafter(f(x), f(-np.inf))             # noqa: E731
-    nan = np.nan
-    tiny = f(1e-45)                                             # the smallest float32 subnormal
-    rows = {
-        "-0.0 among +0.0 (one tie group)":
-            [-0.0, 0.0, -0.0, 0.0, 0.5, 0.25,   -0.0, -0.0, -0.0, 0.0, 0.0,   0.1, 0.0, -0.0, 0.2, 0.3],
-        "only -0.0 in every set but one":
-            [-0.0, -0.0, -0.0, -0.0, -0.0, -0.0,   -0.0, -0.0, -0.0, -0.0, nan,   -0.0, -0.0, -0.0, -0.0, 0.001],
-        "subnormals next to 0.0 (distinct values)":
-            [0.0, tiny, 2 * tiny, -tiny, 0.0, f(1.1754942e-38),   tiny, 0.0, -0.0, 3 * tiny, -2 * tiny,
-             0.0, f(1e-40), tiny, -tiny, f(1.17549435e-38)],
-        "one ulp above and one ulp below a grid value, the grid value beside them":
-            [0.3, up(0.3), 0.5, 0.7, 0.1, 0.9,   0.7, down(0.7), 0.3, 0.2, 0.5,   0.3, 0.7, 0.4, 0.6, 0.8],
-        "just outside [0, 1]: clamp to keys 0 and 1000":
-            [f(1.0004), 1.0, 0.0, 0.5, 0.25, f(-0.0004),   1.0, 0.0, f(-0.0004), 0.75, 0.5,   f(1.0004), 1.0, 0.999, 0.001, 0.0],
-        "a set keeps exactly 3":
-            [0.2, nan, nan, 0.8, nan, 0.5,   0.1, 0.2, nan, 0.4, 0.5,   nan, 0.9, 0.2, nan, 0.7],
-        "every set keeps exactly 3, ties":
-            [0.5, nan, nan, 0.5, nan, 0.25,   0.25, 0.5, nan, nan, 0.75,   nan, 0.75, 0.5, nan, 0.25],
-    }
-    names, table = [], []
-    for name, row in rows.items():
-        row = np.array(row, np.float32)
-        names.append(name)
-        table.append(row)
-        if np.all(_on_grid(row)):
-            moved = row.copy()
-            at = int(np.nanargmax(row))                         # the row's largest value: no order changes
-            moved[at] = up(row[at])
-            names.append(name + " / sorted")
-            table.append(moved)
-    sets = [np.arange(0, 6, dtype=np.int32), np.arange(6, 11, dtype=np.int32), np.arange(11, 16, dtype=np.int32)]
-    return np.stack(table), sets, names
-
-
-def _zero_sum_rows():
-    """-> (ps float32[2, 20], sets): a set of ten -0.0 (a pairwise leaf with its eight accumulators; np.sum starts from the
-    identity 0, so numpy's mean is +0.0) beside two sets of five, on the grid and with one value off it"""
-    ps = np.empty((2, 20), np.float32)
-    ps[:, :10] = -0.0
-    ps[:, 10:15] = [0.1, 0.2, 0.0, 0.4, 0.5]
-    ps[:, 15:] = [0.3, -0.0, 0.25, 0.125, 0.75]
-    ps[1, 19] = np.float32(0.7500001)
-    return ps, [np.arange(0, 10, dtype=np.int32), np.arange(10, 15, dtype=np.int32), np.arange(15, 20, dtype=np.int32)]
-
-
 def test_edge_rows_are_what_they_claim():
     ps, sets, names = _edge_rows()
     ref = KR.table_reference(ps, sets, False)

@@ -15,13 +15,15 @@ import argparse
 import contextlib
 import io
 import os
+import sys
 
 import numpy as np
 import pytest
 
-from oracle import oracle_np as O
-from splicedice_amd.engine import SdiceError
-from tests.test_gpu_pair_sweeps import MIX_WEIGHTS, SWEEP, TABLE_MAX_T, PaletteRef, _check_chi2, _check_fisher
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from oracle import oracle_np as O  # noqa: E402
+from pair_fixtures import MIX_WEIGHTS, SWEEP, TABLE_MAX_T, PaletteRef, _check_chi2, _check_fisher  # noqa: E402
+from splicedice_amd.engine import SdiceError  # noqa: E402
 
 gpu = pytest.mark.gpu
 CLI_RTOL = 1e-6

@@ -27,200 +27,19 @@ The CPU self-checks (not gpu-marked) show that the scatter equals the per-pair o
 rational sum agrees with scipy, and that every palette reaches what it is there for.
 """
 import math
-import warnings
-from fractions import Fraction
+import os
+import sys
 
 import numpy as np
 import pytest
 
-from oracle import oracle_np as O
-from splicedice_amd.engine import SdiceError
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from oracle import oracle_np as O  # noqa: E402
+from pair_fixtures import (BIG_TOTAL, EXACT_MAX_TOTAL, MIX_WEIGHTS, P_RTOL_TIGHT, PALETTES, SWEEP, TABLE_MAX_T, PaletteRef,  # noqa: E402
+                           _check_chi2, _check_fisher, chi2_scipy, exact_two_sided, fisher_scipy)
+from splicedice_amd.engine import SdiceError  # noqa: E402
 
-P_RTOL_TIGHT = 1e-9    # p-values (tests/test_gpu_parity.py)
-P_RTOL_BIG = 1e-7      # Fisher tables with a total above 5e4: pmf(a) = exp of nine log-factorials (test_fisher_fuzz_tables)
-BIG_TOTAL = 50_000
-EXACT_MAX_TOTAL = 400  # the rational sum is used where the total (so every margin) is at most this
 gpu = pytest.mark.gpu
-
-# (incl, excl) per sample.  A pair (i, j) is the table [[incl_i, incl_j], [excl_i, excl_j]].
-PALETTES = {
-    # zero margins (p = 1; chi2 raises), a = 0 or a at the top of the support (one-sided walks), expected == observed
-    "zeros": [(0, 0), (0, 9), (6, 0), (1, 0), (0, 1), (5, 5), (3, 12), (11, 2)],
-    # (x, y) beside (y, x): symmetric tables, pmf(k) == pmf(a) for a k on the other side of the mode
-    "ties": [(4, 9), (9, 4), (20, 7), (7, 20), (13, 13), (1, 6), (6, 1), (30, 30)],
-    # margins up to ~200 (the rational sum), a at either end of the support, p down to ~1e-77
-    "small": [(17, 60), (45, 12), (2, 90), (80, 3), (33, 33), (0, 140), (120, 0), (9, 25)],
-    # counts in the thousands: walks of hundreds of steps, rescaled products, the negligible-tail cut
-    "thousands": [(2500, 9000), (3300, 12000), (2900, 8800), (3100, 11500), (2700, 9900), (3000, 10400)],
-    # totals above 5e4
-    "big": [(9000, 30000), (8000, 29000), (10500, 31000), (8800, 33000)],
-    # hundreds of sigma out: p down to ~1e-267 (scipy is reliable above ~1e-280)
-    "tiny": [(450, 3), (2, 440), (430, 0), (0, 460), (440, 6), (5, 450), (300, 300)],
-    # fisher.table_max = 256: totals 128 + 128 = T (lgamma), 127 + 128 = T - 1 (the last table entry), 127 + 127
-    "edge": [(40, 88), (100, 27), (3, 125), (64, 64), (1, 126), (0, 128), (120, 8), (0, 0)],
-    # every total below T = 256: a row of these is never flagged
-    "under": [(100, 27), (1, 126), (60, 67), (0, 0), (20, 20), (5, 0)],
-    # a bit of everything, for rows where long walks must stay rare (s = 8192, 20 000 junctions): see MIX_WEIGHTS
-    "mix": [(0, 0), (0, 9), (6, 0), (13, 13), (7, 20), (20, 7), (45, 12), (2, 90), (450, 3), (2, 440), (2900, 8800),
-            (2800, 9000)],
-}
-MIX_WEIGHTS = np.array([8, 8, 8, 10, 10, 10, 10, 10, 1, 1, 0.5, 0.5])
-SWEEP = ("zeros", "ties", "small", "thousands", "big", "tiny", "mix")
-TABLE_MAX_T = 256
-
-
-# ------------------------------------------------------------------------------ references per distinct table
-def exact_two_sided(a, b, c, d):
-    """scipy's two-sided Fisher p in rational arithmetic: the sum of pmf(k) over the support with
-    pmf(k) <= pmf(a) (1 + 1e-12) (the acceptance rule of tools/exact_fisher.py), any zero margin -> 1, clipped at 1.
-    pmf(k) = comb(n1, k) comb(n2, n - k) / comb(M, n): the weights share the denominator, so the test is on integers."""
-    n1, n2, n = a + b, c + d, a + c
-    if n1 == 0 or n2 == 0 or n == 0 or b + d == 0:
-        return 1.0
-    w = [math.comb(n1, k) * math.comb(n2, n - k) for k in range(max(0, n - n2), min(n1, n) + 1)]
-    wa = math.comb(n1, a) * math.comb(n2, n - a)
-    acc = sum(x for x in w if x * 10 ** 12 <= wa * (10 ** 12 + 1))
-    return float(min(Fraction(acc, math.comb(n1 + n2, n)), Fraction(1)))
-
-
-_FISHER, _CHI2 = {}, {}
-
-
-def fisher_scipy(t):
-    if t not in _FISHER:
-        from scipy.stats import fisher_exact
-        a, b, c, d = t
-        _FISHER[t] = float(fisher_exact([[a, b], [c, d]])[1])
-    return _FISHER[t]
-
-
-def chi2_scipy(t):
-    """p of scipy chi2_contingency, NaN where scipy raises (a zero expected frequency: the kernel's n_bad)"""
-    if t not in _CHI2:
-        from scipy.stats import chi2_contingency
-        a, b, c, d = t
-        with warnings.catch_warnings(), np.errstate(all="ignore"):
-            warnings.simplefilter("ignore", RuntimeWarning)
-            try:
-                _CHI2[t] = float(chi2_contingency([[a, b], [c, d]])[1])
-            except ValueError:
-                _CHI2[t] = math.nan
-    return _CHI2[t]
-
-
-def _pack(t):
-    assert (t >= 0).all() and (t < 1 << 16).all()
-    return (t[..., 0] << 48) | (t[..., 1] << 32) | (t[..., 2] << 16) | t[..., 3]
-
-
-class PaletteRef:
-    """The distinct tables of a set of palettes (np.unique on packed keys), their references, and the table id of every
-    ordered palette pair: ids[k, x, y] for samples of palette k holding entries x and y."""
-
-    def __init__(self, names):
-        self.names = list(names)
-        pmax = max(len(PALETTES[nm]) for nm in self.names)
-        tabs = np.zeros((len(self.names), pmax, pmax, 4), np.int64)
-        for k, nm in enumerate(self.names):
-            pal = np.array(PALETTES[nm], np.int64)
-            p = len(pal)
-            tabs[k, :p, :p, 0] = pal[:, None, 0]
-            tabs[k, :p, :p, 1] = pal[None, :, 0]
-            tabs[k, :p, :p, 2] = pal[:, None, 1]
-            tabs[k, :p, :p, 3] = pal[None, :, 1]
-        uniq, inv = np.unique(_pack(tabs).ravel(), return_inverse=True)
-        self.tables = np.stack([(uniq >> sh) & 0xFFFF for sh in (48, 32, 16, 0)], axis=1)
-        self.ids = inv.reshape(tabs.shape[:3]).astype(np.int32)
-        self.total = self.tables.sum(axis=1)
-        self._fisher = self._chi2 = None
-
-    def fisher(self):
-        """(p, rtol) per distinct table; where the total is small the rational sum must agree with scipy first"""
-        if self._fisher is None:
-            p = np.array([fisher_scipy(tuple(int(v) for v in t)) for t in self.tables])
-            for t, ps, tot in zip(self.tables, p, self.total):
-                if tot <= EXACT_MAX_TOTAL:
-                    assert abs(exact_two_sided(*(int(v) for v in t)) - ps) <= 1e-12 * ps, (t, ps)
-            self._fisher = p, np.where(self.total > BIG_TOTAL, P_RTOL_BIG, P_RTOL_TIGHT)
-        return self._fisher
-
-    def chi2(self):
-        """(p, rtol) per distinct table, p = NaN for the tables scipy refuses"""
-        if self._chi2 is None:
-            self._chi2 = np.array([chi2_scipy(tuple(int(v) for v in t)) for t in self.tables]), \
-                np.full(len(self.tables), P_RTOL_TIGHT)
-        return self._chi2
-
-    def rows(self, s, reps=1, seed=0, weights=None):
-        """-> (incl int32[n, s], excl int64[n, s], pid[n], pi[n, s]): `reps` rows per palette; pi[r, k] is the palette
-        entry of sample k.  s = 2: one row per ordered entry pair instead.  s >= 2P: the entries in order and then in
-        reverse order at a random place in the row, so that every ordered pair of entries (x, x included) appears."""
-        rng = np.random.default_rng(seed * 7919 + s)
-        pid, pi = [], []
-        for k, nm in enumerate(self.names):
-            p = len(PALETTES[nm])
-            if s == 2:
-                xy = np.stack(np.meshgrid(np.arange(p), np.arange(p), indexing="ij"), axis=-1).reshape(-1, 2)
-                pid += [k] * len(xy)
-                pi += list(xy)
-                continue
-            w = None
-            if weights is not None and nm in weights:
-                w = weights[nm] / weights[nm].sum()
-            for _ in range(reps):
-                if s >= 2 * p:
-                    rest, at = rng.choice(p, s - 2 * p, p=w), rng.integers(0, s - 2 * p + 1)
-                    pi.append(np.r_[rest[:at], np.arange(p), np.arange(p)[::-1], rest[at:]])
-                else:
-                    pi.append(rng.choice(p, s, p=w))
-                pid.append(k)
-        pid, pi = np.array(pid), np.array(pi)
-        pal = np.zeros((len(self.names), self.ids.shape[1], 2), np.int64)
-        for k, nm in enumerate(self.names):
-            pal[k, :len(PALETTES[nm])] = PALETTES[nm]
-        vals = pal[pid[:, None], pi]
-        return vals[..., 0].astype(np.int32), vals[..., 1].astype(np.int64), pid, pi
-
-    def pair_ids(self, pid, pi):
-        """table id of every pair of every row, int32[n, s(s-1)/2], built one i at a time (vectorised over rows and j:
-        no s^2 index arrays at s = 8192)"""
-        n, s = pi.shape
-        out = np.empty((n, s * (s - 1) // 2), np.int32)
-        q = 0
-        for i in range(s - 1):
-            out[:, q:q + s - 1 - i] = self.ids[pid[:, None], pi[:, i:i + 1], pi[:, i + 1:]]
-            q += s - 1 - i
-        return out
-
-
-def assert_p_match(got, ids, want, rtol, what):
-    """every element: |got - want| <= rtol * want per table (NaN where want is NaN), in slices so that s = 8192 needs
-    no s^2-sized temporaries; returns the number of p-values compared"""
-    assert got.shape == ids.shape, (got.shape, ids.shape)
-    g, t = got.reshape(-1), ids.reshape(-1)
-    step = 1 << 22
-    for lo in range(0, g.size, step):
-        gs, ts = g[lo:lo + step], t[lo:lo + step]
-        w, r = want[ts], rtol[ts]
-        nan_w = np.isnan(w)
-        ok = np.where(nan_w, np.isnan(gs), np.abs(gs - w) <= r * w)
-        if not ok.all():
-            bad = lo + np.flatnonzero(~ok)[:5]
-            idx = [np.unravel_index(b, got.shape) for b in bad]
-            raise AssertionError(f"{what}: {int((~ok).sum())} p-values differ in [{lo}, {lo + gs.size}); first (row, q, "
-                                 f"got, want): {[(int(i[0]), int(i[1]), g[b], want[t[b]]) for i, b in zip(idx, bad)]}")
-    return g.size
-
-
-def _check_fisher(ref, got, ids, what):
-    p, rtol = ref.fisher()
-    return assert_p_match(got, ids, p, rtol, what)
-
-
-def _check_chi2(ref, got, n_bad, ids, what):
-    p, rtol = ref.chi2()
-    assert n_bad == int(np.isnan(p)[ids].sum()), (what, n_bad)
-    return assert_p_match(got, ids, p, rtol, what)
 
 
 def _is_tie(t):

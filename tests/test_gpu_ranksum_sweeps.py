@@ -35,14 +35,13 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from oracle import oracle_np as O  # noqa: E402
-from test_gpu_count_sweeps import PLACEMENTS, _kept_positions, _values  # noqa: E402
-from test_gpu_kruskal_sweeps import CHS, NOMINAL_CUS, _bits, chunk_table_rows, rows_per_wave  # noqa: E402
-from test_gpu_kruskal_sweeps import _on_grid as _kw_on_grid  # noqa: E402
-from test_gpu_parity import P_RTOL_TIGHT  # noqa: E402
+from rank_support import (NOMINAL_CUS, P_FLOOR, P_RTOL, PLACEMENTS, _kept_positions, _values, chunk_table_rows, on_grid,  # noqa: E402
+                          rows_per_wave)
+from rank_support import bits as _bits, scatter as _scatter  # noqa: E402
 
 gpu = pytest.mark.gpu
 
-P_FLOOR = 1e-280
+CHS = (64, 32, 8, 2)
 FIELDS = ("med1", "med2", "mean1", "mean2", "delta")
 OUT_DTYPES = dict(tested=np.uint8, p=np.float64, z=np.float64, med1=np.float32, med2=np.float32, mean1=np.float32,
                   mean2=np.float32, delta=np.float32)
@@ -56,7 +55,7 @@ POISON = np.array([np.nan, 1e30, -7.0, 0.12345], np.float32)       # what an uns
 def _on_grid(v):
     """is the value float32(key / 1000) of its clamped key, the kernels' own question (FLT_MAX * 1000 overflows: off)"""
     with np.errstate(over="ignore"):
-        return _kw_on_grid(v)
+        return on_grid(v)
 
 
 def _reference(ps, g1, g2):
@@ -65,10 +64,6 @@ def _reference(ps, g1, g2):
     with np.errstate(all="ignore"), warnings.catch_warnings():
         warnings.simplefilter("ignore")
         return O.compare_rows(ps, g1, g2)
-
-
-def _scatter(ref, idx):
-    return {name: np.ascontiguousarray(v[idx]) for name, v in ref.items()}
 
 
 def _check(got, ref, label, p_ref=None, where=None):
@@ -100,7 +95,7 @@ def _check(got, ref, label, p_ref=None, where=None):
     cell = t & (pr >= P_FLOOR)
     err = np.abs(got["p"][cell] - pr[cell]) / pr[cell]
     worst = float(err.max()) if err.size else 0.0
-    assert worst <= P_RTOL_TIGHT, say(("p", worst), np.flatnonzero(cell)[np.argsort(-err)])
+    assert worst <= P_RTOL, say(("p", worst), np.flatnonzero(cell)[np.argsort(-err)])
     low = t & ~cell
     bad = np.flatnonzero(low & ~((got["p"] >= 0) & (got["p"] < 2 * P_FLOOR)))
     assert bad.size == 0, say(("p below the floor", got["p"][bad[:4]], pr[bad[:4]]), bad)

@@ -10,7 +10,6 @@ The tables mix every row kind of KINDS at every pair count of MS, with shuffled 
 references are cached and shared with tests/test_gpu_signedrank_sweeps.py.  Tests without the gpu mark check on the CPU
 that the tables are what they claim."""
 import argparse
-import ctypes as C
 import functools
 import os
 import sys
@@ -19,14 +18,14 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rank_support as RS  # noqa: E402
 import signedrank_referee as SR  # noqa: E402
 from oracle import oracle_np as O  # noqa: E402
+from rank_support import P_FLOOR, P_RTOL, draw_pairs  # noqa: E402
 
 gpu = pytest.mark.gpu
 
 Z_RTOL = 1e-12
-P_RTOL = 1e-9
-P_FLOOR = 1e-280
 M_LIMIT = 4096                      # pairs a call accepts (include/sdice.h)
 # every dispatch and lane-group edge: a lane per row with 4 and 8 registers a side, groups of 16, 32 and 64 lanes, the
 # workgroup kernel from 65, its LDS sizes
@@ -36,14 +35,6 @@ KINDS = ("grid", "off-grid", "grid with NaNs", "off-grid with NaNs", "two kept p
 PER_KIND = 20
 F32 = ("med1", "med2", "mean1", "mean2", "delta")
 OUTS = ("tested", "p", "z") + F32
-
-
-def draw_pairs(rng, m, spare=3):
-    """m disjoint column pairs of a shuffled table of 2 m + spare columns: a[q] lies before or after b[q] and the pairs
-    are not in table order"""
-    s = 2 * m + spare
-    perm = rng.permutation(s).astype(np.int32)
-    return perm[:m].copy(), perm[m: 2 * m].copy(), s
 
 
 def _base(rng, m, grid):
@@ -135,34 +126,18 @@ def reference(m):
     return SR.table_reference(ps, a, b)
 
 
-def same_f32(got, want):
-    """bit-identical"""
-    return np.asarray(got, np.float32).view(np.uint32) == np.asarray(want, np.float32).view(np.uint32)
-
-
 def check(got, ref, label, floor_share=True):
     """asserts every bar -> dict(tested, below, z_err, p_err)"""
-    assert np.array_equal(got["tested"], ref["tested"]), (label, np.flatnonzero(got["tested"] != ref["tested"])[:5])
-    t = ref["tested"].astype(bool)
-    for name in F32:
-        bad = np.flatnonzero(~same_f32(got[name], ref[name]))
-        assert bad.size == 0, (label, name, bad[:5], got[name][bad[:5]], ref[name][bad[:5]])
-    assert not got["p"][~t].any() and not got["z"][~t].any(), label
+    t = RS.check_common(got, ref, F32, ("p", "z"), label)
     z, zr = got["z"][t], ref["z"][t]
     assert np.all(z[zr == 0] == 0), label
     err_z = np.abs(z - zr) / np.where(zr != 0, np.abs(zr), 1.0)
-    p, pr = got["p"][t], ref["p"][t]
-    cell = pr >= P_FLOOR
-    err_p = np.abs(p[cell] - pr[cell]) / pr[cell]
-    out = dict(tested=int(t.sum()), below=int((~cell).sum()), z_err=float(err_z.max()) if err_z.size else 0.0,
-               p_err=float(err_p.max()) if err_p.size else 0.0)
-    print(f"{label}: rows {t.size} tested {out['tested']} worst z rel {out['z_err']:.3g} worst p rel {out['p_err']:.3g} "
-          f"smallest p {pr.min() if pr.size else 1:.3g} below floor {out['below']}")
+    out = dict(tested=int(t.sum()), z_err=float(err_z.max()) if err_z.size else 0.0)
+    print(f"{label}: rows {t.size} tested {out['tested']} worst z rel {out['z_err']:.3g}", end=" ")
     assert np.all(err_z <= Z_RTOL), (label, out["z_err"])
-    assert np.all(err_p <= P_RTOL), (label, out["p_err"])
-    assert np.all(p[~cell] < 2 * P_FLOOR), label
+    out["below"], out["p_err"] = RS.check_p(got["p"][t], ref["p"][t], label)
     if floor_share:
-        assert out["tested"] > 0 and out["below"] <= 0.01 * out["tested"], (label, out)
+        RS.check_floor_share(out["tested"], out["below"], label)
     return out
 
 
@@ -250,14 +225,6 @@ def test_all_equal_rows_and_tiny_calls(ctx):
     assert all(empty[name].shape == (0,) for name in OUTS)
 
 
-def _raw_call(ctx, ps, a, b, m, outs):
-    ps = np.ascontiguousarray(ps, dtype=np.float32)
-    n, s = ps.shape
-    ptr = lambda v: v.ctypes.data_as(C.c_void_p)     # noqa: E731
-    a, b = np.ascontiguousarray(a, np.int32), np.ascontiguousarray(b, np.int32)
-    return ctx.lib.sdice_signedrank(ctx.h, n, s, ptr(ps), ptr(a), ptr(b), m, *[ptr(outs[x]) for x in OUTS])
-
-
 @gpu
 @pytest.mark.parametrize("case", ["m=0", "m over the limit", "index out of range", "negative index", "twice in one list",
                                   "in both lists"])
@@ -281,7 +248,7 @@ def test_errors_leave_the_outputs_untouched(ctx, case):
     ps = np.full((n, s), 0.5, dtype=np.float32)
     outs = {name: np.full(n, 7 + i, dt) for i, (name, dt) in enumerate(SR.FIELDS)}
     before = {x: v.copy() for x, v in outs.items()}
-    rc = _raw_call(ctx, ps, a, b, m, outs)
+    rc = RS.raw_call(ctx, "sdice_signedrank", ps, (a, b, m), outs, OUTS)
     assert rc == -1, case                                   # SDICE_ERR_ARG
     assert ctx.lib.sdice_last_error()
     for x in outs:
@@ -300,37 +267,11 @@ def test_engine_refuses_pair_lists_of_two_lengths(ctx):
 
 
 # ---------------------------------------------------------------- command line
-def _write_cli_inputs(tmp_path):
-    """40 rows x 6 pairs + 2 samples outside the manifests; the manifests' order is not the table's"""
-    rng = np.random.default_rng(606)
-    n, s = 40, 14
-    samples = [f"samp{j}" for j in range(s)]
-    v = rng.integers(0, 1001, size=(n, s)) / 1000.0
-    v[:, :6] = np.clip(v[:, 6:12] + 0.08 * rng.standard_normal((n, 6)) + 0.05, 0, 1)      # pairs (j, j + 6) move together
-    v[:8] = np.round(v[:8] * 4) / 4                                                      # heavy ties, equal pairs
-    text = np.where(rng.random((n, s)) < 0.08, "nan", np.char.mod("%.3f", v))
-    text[8:11] = "0.500"                                                                  # all-equal rows stay in the table
-    text[11:14, 0:4] = "nan"                                                              # two kept pairs: rows dropped
-    names = [f"chr1:{1000 + 10 * i}-{2000 + 10 * i}:+" for i in range(n)]
-    path = tmp_path / "in_allPS.tsv"
-    with open(path, "w") as f:
-        f.write("cluster\t" + "\t".join(samples) + "\n")
-        for i in range(n):
-            f.write(names[i] + "\t" + "\t".join(text[i]) + "\n")
-    order = [3, 0, 5, 1, 4, 2]
-    g1, g2 = [samples[j] for j in order], [samples[j + 6] for j in order]
-    m1, m2 = tmp_path / "m1.tsv", tmp_path / "m2.tsv"
-    m1.write_text("".join(f"{x}\tpath\tmeta\tA\n" for x in g1))
-    m2.write_text("".join(f"{x}\tpath\tmeta\tB\n" for x in g2))
-    matrix = text.astype(np.float64).astype(np.float32)
-    return str(path), str(m1), str(m2), names, matrix, np.array(order, np.int32), np.array(order, np.int32) + 6
-
-
 def _run_cli_paired(ctx, golden_dir, tmp_path, gtf):
     """-> (the command's file as lines of cells, the referee's table as lines of cells: float32 / float64 cells as numpy
     str(), BH over the tested rows from the oracle, the GTF columns from the host annotation code)"""
     from splicedice_amd import compare_sample_sets as css
-    table_path, m1, m2, names, matrix, a, b = _write_cli_inputs(tmp_path)
+    table_path, m1, m2, names, matrix, a, b = RS.write_paired_cli_inputs(tmp_path)
     out = str(tmp_path / "out.tsv")
     anno = os.path.join(golden_dir, "compare", "anno.gtf") if gtf else ""
     args = argparse.Namespace(psiSPLICEDICE=table_path, manifest1=m1, manifest2=m2, moreManifests=None, paired=True,

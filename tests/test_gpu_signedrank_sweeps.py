@@ -14,41 +14,16 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import signedrank_referee as SR  # noqa: E402
-from test_gpu_signedrank import OUTS, P_FLOOR, check, draw_pairs, reference, table  # noqa: E402
+from rank_support import NOMINAL_CUS, P_FLOOR, chunk_table_rows, draw_pairs, palette_index, scatter  # noqa: E402
+from test_gpu_signedrank import OUTS, check, reference, table  # noqa: E402
 
 gpu = pytest.mark.gpu
 
-NOMINAL_CUS = 256
 CHS = (64, 32, 16, 8, 4, 2, 1)
 # (pairs, rows per wave chunk): all choices at 9 pairs (the lane-group kernel, 4 rows side by side in a wave: more than a
 # chunk of 2 or 1 has), some at 17 (2 side by side) and 33 (1); the lane-per-row kernel of 8 and 3 pairs has no chunks,
 # its tables are there for their length
 CHUNK_CASES = tuple((9, ch) for ch in CHS) + ((17, 32), (33, 16), (8, 64), (8, 1), (3, 64))
-
-
-def rows_per_wave(n, compute_units):
-    """the rule of the launch: the largest ch of 64, 32, .. 1 with ceil(n / ch) >= 2 * 32 * compute_units"""
-    ch = 64
-    while ch > 1 and -(-n // ch) < 2 * 32 * compute_units:
-        ch >>= 1
-    return ch
-
-
-def chunk_table_rows(ch, compute_units):
-    """the smallest n that selects ch, plus 37 rows (38 where 37 would fill the last chunk)"""
-    n = 64 * compute_units * ch - (ch - 1)
-    assert rows_per_wave(n, compute_units) == ch and (ch == 1 or rows_per_wave(n - 1, compute_units) == ch // 2)
-    n += 37
-    n += ch > 1 and n % ch == 0
-    assert rows_per_wave(n, compute_units) == ch and (ch == 1 or n % ch)
-    return n
-
-
-def palette_index(n, rows):
-    """row r takes palette row (r + 3 (r // 64)) mod rows: neighbours are of different kinds (the palette interleaves
-    them) and what sits at a chunk's first and last position moves on from chunk to chunk"""
-    r = np.arange(n, dtype=np.int64)
-    return (r + 3 * (r // 64)) % rows
 
 
 @pytest.mark.parametrize("m,ch", CHUNK_CASES)
@@ -74,7 +49,7 @@ def test_signedrank_rows_per_wave(ctx, m, ch):
     idx = palette_index(n, rows.shape[0])
     ps = np.ascontiguousarray(rows[idx])
     got = ctx.signedrank(ps, a, b)
-    check(got, {name: v[idx] for name, v in reference(m).items()}, f"m={m} ch={ch} n={n} on {cus} CUs")
+    check(got, scatter(reference(m), idx), f"m={m} ch={ch} n={n} on {cus} CUs")
     if (m, ch) not in ((8, 64), (9, 64)):
         return
     assert -(-n // 64) > 32 * cus and n > 256 * 8 * cus           # more chunks than waves, more rows than lanes

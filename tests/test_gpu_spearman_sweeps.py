@@ -16,11 +16,11 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import spearman_referee as SP  # noqa: E402
-from test_gpu_spearman import KINDS, OUTS, P_FLOOR, check, make_row, design, covariate, sorted_design  # noqa: E402
+from rank_support import NOMINAL_CUS, P_FLOOR, chunk_table_rows, palette_index, rows_per_wave, scatter  # noqa: E402
+from test_gpu_spearman import KINDS, OUTS, check, make_row, design, covariate, sorted_design  # noqa: E402
 
 gpu = pytest.mark.gpu
 
-NOMINAL_CUS = 256
 BIG_ROWS = 1_048_576 + 37
 BIG_MS = (6, 12, 24, 40)            # one column count per lane-group width: 8, 16, 32, 64 lanes
 BIG_S = 44
@@ -28,30 +28,6 @@ PALETTE_VARIANTS = 16               # x 12 kinds = 192 palette rows
 # (columns, rows per wave chunk): fewer rows in a chunk than groups side by side in a wave (4 < 8 at 8 lanes a row), as
 # many, and more; the wave-per-row kernel with 2 and with 4 columns a lane
 CHUNK_CASES = ((5, 4), (5, 8), (12, 16), (20, 2), (40, 32), (70, 16), (130, 4), (130, 1))
-
-
-def rows_per_wave(n, compute_units):
-    """the rule of the launch: the largest ch of 64, 32, .. 1 with ceil(n / ch) >= 2 * 32 * compute_units"""
-    ch = 64
-    while ch > 1 and -(-n // ch) < 2 * 32 * compute_units:
-        ch >>= 1
-    return ch
-
-
-def chunk_table_rows(ch, compute_units):
-    """the smallest n that selects ch, plus 37 rows (38 where 37 would fill the last chunk)"""
-    n = 64 * compute_units * ch - (ch - 1)
-    n += 37
-    n += ch > 1 and n % ch == 0
-    assert rows_per_wave(n, compute_units) == ch and (ch == 1 or n % ch)
-    return n
-
-
-def palette_index(n, rows):
-    """row r takes palette row (r + 3 (r // 64)) mod rows: neighbours are of different kinds (the palette interleaves
-    them) and what sits at a chunk's first and last position moves on from chunk to chunk"""
-    r = np.arange(n, dtype=np.int64)
-    return (r + 3 * (r // 64)) % rows
 
 
 @functools.lru_cache(maxsize=None)
@@ -164,7 +140,7 @@ def test_spearman_workgroup_kernel_strides_over_rows(ctx, m):
     rows, cols, _ = table(m)
     idx = palette_index(n, rows.shape[0])
     got = ctx.spearman(np.ascontiguousarray(rows[idx]), cols, covariate(m, "tied"))
-    check(got, {name: v[idx] for name, v in reference(m, "tied").items()}, f"m={m} n={n} on {cus} CUs")
+    check(got, scatter(reference(m, "tied"), idx), f"m={m} n={n} on {cus} CUs")
 
 
 @gpu
@@ -177,7 +153,7 @@ def test_spearman_rows_per_wave(ctx, m, ch):
     rows, cols = palette(m)
     idx = palette_index(n, rows.shape[0])
     got = ctx.spearman(np.ascontiguousarray(rows[idx]), cols, covariate(m, "tied"))
-    check(got, {name: v[idx] for name, v in palette_reference(m).items()}, f"m={m} ch={ch} n={n} on {cus} CUs")
+    check(got, scatter(palette_reference(m), idx), f"m={m} ch={ch} n={n} on {cus} CUs")
 
 
 # ------------------------------------------------------------------------------ the p ladder

@@ -13,7 +13,6 @@ The tables mix every row kind of KINDS, each on 3-decimal values and on off-grid
 count that changes the kernel or its lane-group width; builders and references are cached and shared with
 tests/test_gpu_strata_sweeps.py.  Tests without the gpu mark check on the CPU that the tables are what they claim."""
 import argparse
-import ctypes as C
 import functools
 import os
 import sys
@@ -22,13 +21,13 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rank_support as RS  # noqa: E402
 import strata_referee as VR  # noqa: E402
+from rank_support import P_FLOOR, P_RTOL, same_f32  # noqa: E402
 
 gpu = pytest.mark.gpu
 
 Z_TOL = 1e-12
-P_RTOL = 1e-9
-P_FLOOR = 1e-280
 COND_MAX = 100.0
 GROUP_LIMIT = 4096                  # columns of one group, and
 STRATA_LIMIT = 64                   # strata a call accepts (include/sdice.h)
@@ -154,47 +153,30 @@ def split(total):
     return total // 2, total - total // 2
 
 
-def same_f32(got, want):
-    """bit-identical"""
-    return np.asarray(got, np.float32).view(np.uint32) == np.asarray(want, np.float32).view(np.uint32)
-
-
 def check(got, ref, label, floor_share=True, plain=None, quiet=False):
     """asserts every bar -> dict(tested, below, z_err, p_err, cond); plain: ctx.ranksum's result on the same lists"""
-    assert np.array_equal(got["tested"], ref["tested"]), (label, np.flatnonzero(got["tested"] != ref["tested"])[:5])
-    t = ref["tested"].astype(bool)
-    for name in F32:
-        bad = np.flatnonzero(~same_f32(got[name], ref[name]))
-        assert bad.size == 0, (label, name, bad[:5], got[name][bad[:5]], ref[name][bad[:5]])
-        if plain is not None:
+    t = RS.check_common(got, ref, F32, OUTS, label)
+    if plain is not None:
+        for name in F32:
             both = t & plain["tested"].astype(bool)
             unlike = both & ~same_f32(got[name], plain[name])
             # the one licence: where the plain call itself departs from numpy, in the sign of a zero median (or of the
             # delta of two zero medians), this call keeps numpy's zero
             excused = ~same_f32(plain[name], ref[name]) & (plain[name] == 0) & (ref[name] == 0) & (name in ("med1", "med2", "delta"))
             assert not (unlike & ~excused).any(), (label, name, "unlike the unstratified call", np.flatnonzero(unlike & ~excused)[:5])
-    if plain is not None:
         assert np.all(plain["tested"][t] == 1), label           # (what this call tests the plain call tests)
-    for name in OUTS:
-        assert not np.asarray(got[name])[~t].view(np.uint8).any(), (label, name, "a slot of a row that is not tested")
     cond = float(ref["cond"][t].max()) if t.any() else 0.0
     assert cond <= COND_MAX, (label, cond)
     z, zr = got["z"][t], ref["z"][t]
     err_z = np.abs(z - zr) / np.maximum(1.0, np.abs(zr))
-    p, pr = got["p"][t], ref["p"][t]
-    cell = pr >= P_FLOOR
-    err_p = np.abs(p[cell] - pr[cell]) / pr[cell]
-    out = dict(tested=int(t.sum()), below=int((~cell).sum()), z_err=float(err_z.max()) if err_z.size else 0.0,
-               p_err=float(err_p.max()) if err_p.size else 0.0, cond=cond)
+    out = dict(tested=int(t.sum()), z_err=float(err_z.max()) if err_z.size else 0.0, cond=cond)
     if not quiet:
-        print(f"{label}: rows {t.size} tested {out['tested']} worst z err {out['z_err']:.3g} worst p rel {out['p_err']:.3g} "
-              f"smallest p {pr.min() if pr.size else 1:.3g} below floor {out['below']} largest cond {cond:.3g}")
+        print(f"{label}: rows {t.size} tested {out['tested']} worst z err {out['z_err']:.3g} largest cond {cond:.3g}", end=" ")
     assert np.all(err_z <= Z_TOL), (label, out["z_err"])
     assert np.all(z[ref["cond"][t] == 0] == 0), label           # no informative deviation at all: z is 0, not small
-    assert np.all(err_p <= P_RTOL), (label, out["p_err"])
-    assert np.all(p[~cell] < 2 * P_FLOOR), label
+    out["below"], out["p_err"] = RS.check_p(got["p"][t], ref["p"][t], label, quiet)
     if floor_share:
-        assert out["below"] <= 0.01 * out["tested"], (label, out)
+        RS.check_floor_share(out["tested"], out["below"], label)
     return out
 
 
@@ -352,11 +334,8 @@ def _error_call(ctx, case, dev):
     ps = np.full((n, s), 0.5, dtype=np.float32)
     outs = {name: np.full(n, 7 + i, dt) for i, (name, dt) in enumerate(VR.FIELDS)}
     before = {x: v.copy() for x, v in outs.items()}
-    ptr = lambda v: v.ctypes.data_as(C.c_void_p)     # noqa: E731
     if not dev:
-        rc = ctx.lib.sdice_ranksum_strata(ctx.h, n, s, ptr(ps), ptr(g1), n1, ptr(g2), g2.size, ptr(s1), ptr(s2), H,
-                                          *[ptr(outs[x]) for x in OUTS])
-        return rc, outs, before
+        return RS.raw_call(ctx, "sdice_ranksum_strata", ps, (g1, n1, g2, g2.size, s1, s2, H), outs, OUTS), outs, before
     held = [ctx.to_device(v, v.dtype) for v in (ps, g1, g2, s1, s2)] + [ctx.to_device(outs[x], outs[x].dtype) for x in OUTS]
     try:
         rc = ctx.lib.sdice_ranksum_strata_dev(ctx.h, n, s, held[0].ptr, held[1].ptr, n1, held[2].ptr, g2.size, held[3].ptr,
@@ -407,7 +386,7 @@ def _write_cli_inputs(tmp_path):
     manifests' order is not the table's, batch "B" has samples of set 1 only on some rows' kept values"""
     rng = np.random.default_rng(707)
     n, s = 60, 20
-    samples = [f"samp{j}" for j in range(s)]
+    samples, _ = RS.ps_names(n, s)
     batch = np.array([j % 3 for j in range(18)] + [0, 1])
     set1 = np.array([0, 2, 4, 6, 8, 10, 12, 14, 16])
     set2 = np.array([1, 3, 5, 7, 9, 11, 13, 15, 17])
@@ -419,18 +398,12 @@ def _write_cli_inputs(tmp_path):
     text[10:13] = "0.500"                                                                 # all-equal rows stay in the table
     text[13:16, set2[1:]] = "nan"                                                         # one value left in set 2: rows dropped
     text[16:18][:, set2[batch[set2] != 1]] = "nan"                                        # set 2 kept in batch B only
-    names = [f"chr1:{1000 + 10 * i}-{2000 + 10 * i}:+" for i in range(n)]
-    path = tmp_path / "in_allPS.tsv"
-    with open(path, "w") as f:
-        f.write("cluster\t" + "\t".join(samples) + "\n")
-        for i in range(n):
-            f.write(names[i] + "\t" + "\t".join(text[i]) + "\n")
-    m1, m2, lab = tmp_path / "m1.tsv", tmp_path / "m2.tsv", tmp_path / "batches.tsv"
-    m1.write_text("".join(f"{samples[j]}\tpath\tmeta\tA\n" for j in set1[::-1]))
-    m2.write_text("".join(f"{samples[j]}\tpath\tmeta\tB\n" for j in rng.permutation(set2)))
+    path, (m1, m2), names = RS.write_ps_inputs(tmp_path, text, [([samples[j] for j in set1[::-1]], "A"),
+                                                             ([samples[j] for j in rng.permutation(set2)], "B")])
+    lab = tmp_path / "batches.tsv"
     lab.write_text("".join(f"{samples[j]}\t{BATCHES[batch[j]]}\n" for j in rng.permutation(19)))       # samp19: no label
     matrix = text.astype(np.float64).astype(np.float32)
-    return str(path), str(m1), str(m2), str(lab), names, matrix, set1.astype(np.int32), set2.astype(np.int32), batch
+    return path, m1, m2, str(lab), names, matrix, set1.astype(np.int32), set2.astype(np.int32), batch
 
 
 def _cells(path):

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rank_support as RS  # noqa: E402
 import strata_referee as VR  # noqa: E402
 import test_gpu_strata as T  # noqa: E402
 
@@ -51,9 +52,7 @@ def dev_call(ctx, d_ps, lists, H, n):
 
 def same_bits(got, want, label):
     for name in T.OUTS:
-        a, b = np.ascontiguousarray(got[name]), np.ascontiguousarray(want[name])
-        bad = np.flatnonzero(a.view(f"u{a.itemsize}") != b.view(f"u{b.itemsize}"))
-        assert bad.size == 0, (label, name, bad[:5])
+        RS.assert_same_bits(got[name], want[name], (label, name))
 
 
 @pytest.mark.parametrize("n1,n2,H", [(4, 4, 2), (40, 40, 3)])

@@ -14,88 +14,25 @@
 The same checks on the real engine: tests/test_gpu_pair_list.py.
 """
 import argparse
-import contextlib
-import io
 import os
 import socket
+import sys
 
 import numpy as np
 import pytest
 
-from oracle import oracle_np as O
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from oracle import oracle_np as O  # noqa: E402
+from pair_fixtures import ListEngine, _IntoComm, _RecArray, _RecEngine, _args, _pair_file, _quiet  # noqa: E402
 
 P_RTOL = 1e-9        # p-values against scipy (tests/test_gpu_parity.py)
 LISTED = [("p0", "p3"), ("p4", "p1"), ("p2", "p5")]          # the second pair reversed
 MIRROR = ["p0_p3", "p1_p4", "p2_p5"]                         # the golden columns they equal
 
 
-class ListEngine:
-    """Host stand-in for engine.Context with the pair-list keyword: scipy on every listed table, column q =
-    [[incl_i, incl_j], [excl_i, excl_j]] of pair q = (i, j) -- for (j, i) the swapped table, which is what the reference
-    would compute on a count table with those two sample columns exchanged."""
-
-    def __init__(self):
-        self.calls = []
-
-    def ps(self, counts, row_ptr, col, want_excl=False, want_ps=True):
-        ps, excl = O.calculate_psi_vectorised(counts, row_ptr, col)
-        return (ps, excl) if want_excl and want_ps else excl if want_excl else ps
-
-    def _pairs(self, s, pairs):
-        self.calls.append(None if pairs is None else np.asarray(pairs).tolist())
-        return O.pair_list(s) if pairs is None else [(int(i), int(j)) for i, j in np.asarray(pairs)]
-
-    def fisher_pairs(self, incl, excl, pairs=None):
-        from scipy.stats import fisher_exact
-        incl, excl = np.asarray(incl), np.asarray(excl)
-        plist = self._pairs(incl.shape[1], pairs)
-        out = np.empty((incl.shape[0], len(plist)))
-        for r in range(incl.shape[0]):
-            for q, (i, j) in enumerate(plist):
-                out[r, q] = fisher_exact([[incl[r, i], incl[r, j]], [excl[r, i], excl[r, j]]])[1]
-        return out
-
-    def chi2_pairs(self, incl, excl, pairs=None):
-        incl, excl = np.asarray(incl), np.asarray(excl)
-        plist = self._pairs(incl.shape[1], pairs)
-        out, bad = np.ones((incl.shape[0], len(plist))), 0
-        for r in range(incl.shape[0]):
-            for q, (i, j) in enumerate(plist):
-                try:
-                    out[r, q] = O.chi2_yates_restated(incl[r, i], incl[r, j], excl[r, i], excl[r, j])
-                except ValueError:
-                    bad += 1
-        return out, bad
-
-    def bh(self, p):
-        return O.bh_fdr(p)
-
-    def bh_columns(self, p):
-        return O.bh_columns(p)
-
-
 def _read(path):
     rows = [ln.rstrip("\n").split("\t") for ln in open(path)]
     return rows[0], [r[0] for r in rows[1:]], np.array([[float(x) for x in r[1:]] for r in rows[1:]])
-
-
-def _args(golden_dir, out, mode="none", pairs=None, chi2=False, table="in_inclusionCounts.tsv", filt=None):
-    d = os.path.join(golden_dir, "pairwise")
-    return argparse.Namespace(inclusionSPLICEDICE=os.path.join(d, table), clusters=os.path.join(d, "in_allClusters.tsv"),
-                              chi2=chi2, multiple_test_correction=mode, filter_list=filt, output=str(out), pairs=pairs)
-
-
-def _pair_file(tmp_path, text, name="pairs.txt"):
-    f = tmp_path / name
-    f.write_text(text)
-    return str(f)
-
-
-def _quiet(fn, *a, **k):
-    buf = io.StringIO()
-    with contextlib.redirect_stdout(buf):
-        fn(*a, **k)
-    return buf.getvalue()
 
 
 # ------------------------------------------------------------------------------ the ABI
@@ -417,7 +354,6 @@ def test_pairs_flag_under_two_rank_launcher(tmp_path, golden_dir):
 @pytest.mark.parametrize("correction,test", [("pairwise", "fisher"), ("all", "fisher"), ("none", "chi2")])
 def test_shard_packs_the_list_in_load_and_step_stays_device_work_only(correction, test):
     from splicedice_amd import distributed
-    from tests.test_distributed_cpu import _IntoComm, _RecArray, _RecEngine
 
     class Eng(_RecEngine):
         def pair_table(self, s, pairs):

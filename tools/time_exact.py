@@ -12,77 +12,49 @@ HIP events on the context stream through sdice_timer_*, one event pair per launc
 ratio is exact / asymptotic of the same run.  --only NAME (3v3, 8v8, 16v16, 10pairs, 31pairs) times one table, so that a
 job script can give every table a time limit of its own; a run with --out merges its rows into the file that is there.
 Prints one JSON document."""
-import argparse
 import json
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+from _timing import emit, host_block, parse_args, resident_table, timed
 from splicedice_amd.engine import RANKSUM_EXACT_FIELDS, Context, field_shapes
 
 TABLES = {"3v3": (False, 3), "8v8": (False, 8), "16v16": (False, 16), "10pairs": (True, 10), "31pairs": (True, 31)}
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--reps", type=int, default=21)
-ap.add_argument("--rows", type=int, default=1_000_000)
-ap.add_argument("--only", choices=sorted(TABLES), default=None)
-ap.add_argument("--out", default="")
-args = ap.parse_args()
-assert args.reps >= 20
 
+def flags(ap):
+    ap.add_argument("--rows", type=int, default=1_000_000)
+    ap.add_argument("--only", choices=sorted(TABLES), default=None)
+
+
+args = parse_args(flags)
 ctx = Context(0)
 rng = np.random.default_rng(17)
-
-
-def table(n, s, blk):
-    block = (rng.integers(0, 51, size=(blk, s)) / 1000.0).astype(np.float32)
-    d = ctx.empty((n, s), np.float32)
-    assert n % blk == 0
-    for a in range(0, n, blk):
-        d.offset(a * s, (blk, s)).upload(block)
-    return d
-
-
-def timed(call):
-    for _ in range(2):
-        call()
-    ctx.sync()
-    ms = []
-    for _ in range(args.reps):
-        ctx.timer_start()
-        call()
-        ms.append(ctx.timer_stop())
-    return float(np.median(ms)), float(min(ms)), float(max(ms))
-
 
 results = []
 for name, (paired, m) in TABLES.items():
     if args.only not in (None, name):
         continue
     n, s = args.rows, 2 * m
-    d_ps = table(n, s, 25_000)
+    d_ps = resident_table(ctx, host_block(rng, 25_000, s, nan=0, top=50), n)
     g1, g2 = np.arange(0, m, dtype=np.int32), np.arange(m, s, dtype=np.int32)
     d_g1, d_g2 = ctx.to_device(g1, np.int32), ctx.to_device(g2, np.int32)
     out = {x: ctx.empty(*sd) for x, sd in field_shapes(RANKSUM_EXACT_FIELDS, n).items()}
     plain, exact = ("signedrank_dev", "signedrank_exact_dev") if paired else ("ranksum_dev", "ranksum_exact_dev")
     row = dict(table=name, test="signed-rank" if paired else "rank-sum", rows=n, samples=s, reps=args.reps)
     for key, call in (("asymptotic", plain), ("exact", exact)):
-        med, lo, hi = timed(lambda: getattr(ctx, call)(d_ps, d_g1, d_g2, out))
+        med, lo, hi = timed(ctx, lambda: getattr(ctx, call)(d_ps, d_g1, d_g2, out), args.reps)
         row[key] = dict(call=call, median_ms=med, min_ms=lo, max_ms=hi, tested_rows=int(out["tested"].to_host().sum()))
     row["exact"]["exact_rows"] = int(out["exact"].to_host().sum())
     row["ratio_exact_to_asymptotic"] = row["exact"]["median_ms"] / row["asymptotic"]["median_ms"]
     results.append(row)
     for a in (d_ps, d_g1, d_g2, *out.values()):
         a.free()
-doc = dict(device=ctx.device_info()["name"].strip(), results=results)
 if args.out and os.path.exists(args.out):
     old = json.load(open(args.out))
-    if old.get("device") == doc["device"]:
-        doc["results"] = [r for r in old["results"] if r["table"] not in {x["table"] for x in results}] + results
-        doc["results"].sort(key=lambda r: list(TABLES).index(r["table"]))
-text = json.dumps(doc, indent=1)
-print(text, flush=True)
-if args.out:
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    if old.get("device") == ctx.device_info()["name"].strip():
+        results = [r for r in old["results"] if r["table"] not in {x["table"] for x in results}] + results
+        results.sort(key=lambda r: list(TABLES).index(r["table"]))
+emit(ctx, results, args.out, hbm=False)
 ctx.close()

@@ -16,6 +16,7 @@ import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+from _timing import resident_table, timed
 from splicedice_amd import _ffi, synth
 
 lib_path, mode = os.path.abspath(sys.argv[1]), sys.argv[2]
@@ -38,10 +39,7 @@ row_of, row_ptr, col = ctx.cluster(*junc)
 counts = np.zeros_like(counts_in)
 counts[row_of] = counts_in
 excl = ctx.ps(counts, row_ptr, col, want_excl=True, want_ps=False)
-d_incl, d_excl = ctx.empty((n, s), np.int32), ctx.empty((n, s), np.int64)
-for a in range(0, n, blk):                 # (a long table is the 25 000-row block repeated)
-    d_incl.offset(a * s, (blk, s)).upload(counts)
-    d_excl.offset(a * s, (blk, s)).upload(excl)
+d_incl, d_excl = resident_table(ctx, counts, n), resident_table(ctx, excl, n)       # (the 25 000-row block repeated)
 if mode == "allpairs":
     m, kw = s * (s - 1) // 2, {}
 else:
@@ -53,19 +51,13 @@ d_bad = ctx.empty(1, np.int64)
 reps = 9 if n * m <= 1 << 30 else 3
 
 
-def timed(call):
-    call()
-    ctx.sync()
-    ms = []
-    for _ in range(reps):
-        ctx.timer_start()
-        call()
-        ms.append(ctx.timer_stop())
-    return dict(median_ms=float(np.median(ms)), min_ms=min(ms), max_ms=max(ms), p_values_per_s=n * m / (np.median(ms) * 1e-3))
+def stats(call):
+    med, lo, hi = timed(ctx, call, reps, warmup=1)
+    return dict(median_ms=med, min_ms=lo, max_ms=hi, p_values_per_s=n * m / (med * 1e-3))
 
 
 out = dict(lib=os.path.relpath(lib_path), mode=mode, rows=n, samples=s, pairs=m, reps=reps,
-           fisher=timed(lambda: ctx.fisher_pairs_dev(d_incl, d_excl, d_p, **kw)),
-           chi2=timed(lambda: ctx.chi2_pairs_dev(d_incl, d_excl, d_p, d_bad, **kw)))
+           fisher=stats(lambda: ctx.fisher_pairs_dev(d_incl, d_excl, d_p, **kw)),
+           chi2=stats(lambda: ctx.chi2_pairs_dev(d_incl, d_excl, d_p, d_bad, **kw)))
 print(json.dumps(out), flush=True)
 ctx.close()

@@ -10,51 +10,20 @@ PS values with 2 % NaN (what `correlate` reads; a block of rows repeated).  HIP 
 sdice_timer_*, one event pair per launch, two warm-up launches, then the median of `reps`.  Per table: both times, the
 table bytes (n * s * 4) over the time as a fraction of 8 TB/s, and the ratio of the Spearman time to the rank-sum time of
 the same run -- the unchanged rank-sum call is the yardstick.  Prints one JSON document (and writes it to --out)."""
-import argparse
-import json
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+from _timing import HBM_BYTES_PER_S, emit, host_block, parse_args, resident_table, timed
 from splicedice_amd.engine import RANKSUM_FIELDS, SPEARMAN_FIELDS, Context, field_shapes, spearman_order
 
-HBM_BYTES_PER_S = 8e12
-
-ap = argparse.ArgumentParser()
-ap.add_argument("--reps", type=int, default=21)
-ap.add_argument("--out", default="")
-args = ap.parse_args()
-assert args.reps >= 20
-
+args = parse_args()
 ctx = Context(0)
 rng = np.random.default_rng(14)
 
-
-def table(n, s, blk):
-    block = (rng.integers(0, 1001, size=(blk, s)) / 1000.0).astype(np.float32)
-    block[rng.random((blk, s)) < 0.02] = np.nan
-    d = ctx.empty((n, s), np.float32)
-    assert n % blk == 0
-    for a in range(0, n, blk):
-        d.offset(a * s, (blk, s)).upload(block)
-    return d
-
-
-def timed(call):
-    for _ in range(2):
-        call()
-    ctx.sync()
-    ms = []
-    for _ in range(args.reps):
-        ctx.timer_start()
-        call()
-        ms.append(ctx.timer_stop())
-    return float(np.median(ms)), float(min(ms)), float(max(ms))
-
-
 results = []
 for n, s, blk in ((1_000_000, 16, 25_000), (1_000_000, 100, 25_000), (100_000, 1000, 5_000), (20_000, 4096, 1_000)):
-    d_ps = table(n, s, blk)
+    d_ps = resident_table(ctx, host_block(rng, blk, s), n)
     g1, g2 = np.arange(0, s // 2, dtype=np.int32), np.arange(s // 2, s, dtype=np.int32)
     d_g1, d_g2 = ctx.to_device(g1, np.int32), ctx.to_device(g2, np.int32)
     cols, xg = spearman_order(np.arange(s), rng.integers(0, max(2, s // 4), size=s))
@@ -64,17 +33,12 @@ for n, s, blk in ((1_000_000, 16, 25_000), (1_000_000, 100, 25_000), (100_000, 1
     row = dict(rows=n, samples=s, reps=args.reps)
     for name, call, out in (("ranksum_dev", lambda: ctx.ranksum_dev(d_ps, d_g1, d_g2, rs_out), rs_out),
                             ("spearman_dev", lambda: ctx.spearman_dev(d_ps, d_cols, d_xg, sp_out), sp_out)):
-        med, lo, hi = timed(call)
+        med, lo, hi = timed(ctx, call, args.reps)
         row[name] = dict(median_ms=med, min_ms=lo, max_ms=hi, tested_rows=int(out["tested"].to_host().sum()),
                          hbm_fraction=n * s * 4 / (med * 1e-3) / HBM_BYTES_PER_S)
     row["ratio_to_ranksum"] = row["spearman_dev"]["median_ms"] / row["ranksum_dev"]["median_ms"]
     results.append(row)
     for a in (d_ps, d_g1, d_g2, d_cols, d_xg, *rs_out.values(), *sp_out.values()):
         a.free()
-doc = dict(device=ctx.device_info()["name"].strip(), hbm_peak_bytes_per_s=HBM_BYTES_PER_S, results=results)
-text = json.dumps(doc, indent=1)
-print(text, flush=True)
-if args.out:
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+emit(ctx, results, args.out)
 ctx.close()

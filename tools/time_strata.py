@@ -10,52 +10,21 @@ with 2 % NaN (what compare_sample_sets reads; a block of rows repeated).  HIP ev
 sdice_timer_*, one event pair per launch, two warm-up launches, then the median of `reps`.  Per table: both times, the table
 bytes (n * s * 4) over the time as a fraction of 8 TB/s, and the ratio of the stratified time to the rank-sum time of the
 same run -- the unchanged rank-sum call is the yardstick.  Prints one JSON document (and writes it to --out)."""
-import argparse
-import json
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+from _timing import HBM_BYTES_PER_S, emit, host_block, parse_args, resident_table, timed
 from splicedice_amd.engine import RANKSUM_FIELDS, Context, field_shapes
 
-HBM_BYTES_PER_S = 8e12
-
-ap = argparse.ArgumentParser()
-ap.add_argument("--reps", type=int, default=21)
-ap.add_argument("--out", default="")
-args = ap.parse_args()
-assert args.reps >= 20
-
+args = parse_args()
 ctx = Context(0)
 rng = np.random.default_rng(17)
-
-
-def table(n, s, blk):
-    block = (rng.integers(0, 1001, size=(blk, s)) / 1000.0).astype(np.float32)
-    block[rng.random((blk, s)) < 0.02] = np.nan
-    d = ctx.empty((n, s), np.float32)
-    assert n % blk == 0
-    for a in range(0, n, blk):
-        d.offset(a * s, (blk, s)).upload(block)
-    return d
-
-
-def timed(call):
-    for _ in range(2):
-        call()
-    ctx.sync()
-    ms = []
-    for _ in range(args.reps):
-        ctx.timer_start()
-        call()
-        ms.append(ctx.timer_stop())
-    return float(np.median(ms)), float(min(ms)), float(max(ms))
-
 
 results = []
 for n, m, H, blk in ((1_000_000, 8, 2, 25_000), (1_000_000, 50, 4, 25_000), (100_000, 500, 8, 5_000)):
     s = 2 * m
-    d_ps = table(n, s, blk)
+    d_ps = resident_table(ctx, host_block(rng, blk, s), n)
     g1, g2 = np.arange(0, m, dtype=np.int32), np.arange(m, s, dtype=np.int32)
     strat = (np.arange(m) % H).astype(np.int32)
     d_g1, d_g2, d_st = ctx.to_device(g1, np.int32), ctx.to_device(g2, np.int32), ctx.to_device(strat, np.int32)
@@ -64,17 +33,12 @@ for n, m, H, blk in ((1_000_000, 8, 2, 25_000), (1_000_000, 50, 4, 25_000), (100
     calls = dict(ranksum_dev=lambda: ctx.ranksum_dev(d_ps, d_g1, d_g2, out),
                  ranksum_strata_dev=lambda: ctx.ranksum_strata_dev(d_ps, d_g1, d_g2, d_st, d_st, H, out))
     for name, call in calls.items():
-        med, lo, hi = timed(call)
+        med, lo, hi = timed(ctx, call, args.reps)
         row[name] = dict(median_ms=med, min_ms=lo, max_ms=hi, tested_rows=int(out["tested"].to_host().sum()),
                          hbm_fraction=n * s * 4 / (med * 1e-3) / HBM_BYTES_PER_S)
     row["ratio_to_ranksum"] = row["ranksum_strata_dev"]["median_ms"] / row["ranksum_dev"]["median_ms"]
     results.append(row)
     for a in (d_ps, d_g1, d_g2, d_st, *out.values()):
         a.free()
-doc = dict(device=ctx.device_info()["name"].strip(), hbm_peak_bytes_per_s=HBM_BYTES_PER_S, results=results)
-text = json.dumps(doc, indent=1)
-print(text, flush=True)
-if args.out:
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+emit(ctx, results, args.out)
 ctx.close()
