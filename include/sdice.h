@@ -359,6 +359,22 @@ int sdice_sample_matrix_finish(int32_t m, const int64_t* shared, const int64_t* 
  *      (scipy.stats.fisher_exact two-sided on [[incl_a, incl_b],[excl_a, excl_b]]).
  *  incl[n,s] int32, excl[n,s] int64 (from sdice_ps); p[n, s(s-1)/2] float64 row-major,
  *  pair order (0,1),(0,2)...(s-2,s-1) (pairwise_fisher.py:142-147).
+ *  COUNT RANGE of sdice_fisher_* and sdice_chi2_*: counts are non-negative, and the kernels take them as doubles, so for
+ *  ANY two samples i != j of a junction -- the table [[a, b], [c, d]] = [[incl_i, incl_j], [excl_i, excl_j]] -- the
+ *  total a + b + c + d must be at most 2^53; for sdice_fisher_* also a*d <= 2^53 and b*c <= 2^53 (the ratio walk steps on
+ *  these products, and only an exact product ends at 0 where the support ends: beyond 2^53 the sum, and with it p, can
+ *  come out with any value or sign).  So an inclusion count of 2^31 - 1 goes with exclusion sums up to 2^22, an
+ *  exclusion sum of 2^40 with inclusion counts up to 8192.  The host entry points -- sdice_fisher_pairs, _pair_list,
+ *  _tables, sdice_chi2_pairs, _pair_list -- check every junction (the pair-list forms too check all its samples, listed
+ *  or not) and return SDICE_ERR_ARG before any launch, outputs untouched; the _dev forms cannot look and leave the range
+ *  to the caller.  sdice_fisher_tables applies it per table.
+ *  ACCURACY within the range, relative to the exact two-sided sum (scipy's rule: pmf(k) <= pmf(a)), for p >= 1e-280:
+ *  1e-9 for totals up to 5e4, 1e-7 up to the log-factorial table's end (context parameter "fisher.table_max", 2^20: pmf(a)
+ *  is a difference of nine log-factorials), 1e-6 beyond it at every accepted magnitude (pmf(a) in the saddle-point form,
+ *  whose error does not grow with the counts; observed: DESIGN.md section 7).  Smaller p come out below 2e-280.  A table
+ *  with a ratio pmf(k) / pmf(a) within 1e-12 above 1 counts that term as a tie.  chi2: 1e-9 against the formula below in
+ *  exact arithmetic, for p >= 1e-280.  Walk length grows with the counts (about half the smaller margin for a balanced
+ *  table): counts of 1e8 take seconds per pair.
  */
 int sdice_fisher_pairs(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* incl,
                        const int64_t* excl, double* p);

@@ -132,7 +132,7 @@ extern "C" int sdice_chi2_pairs(sdice_ctx* ctx, int64_t n, int32_t s, const int3
     *n_bad = 0;
     if (n == 0 || s < 2) return SDICE_OK;
     SD_ARG(incl && excl && p, "NULL pointer");
-    for (int64_t i = 0; i < n * s; ++i) SD_ARG(incl[i] >= 0 && excl[i] >= 0, "counts must be non-negative");
+    SD_TRY(sd_check_pair_counts(__func__, n, s, incl, excl, false));
     const int64_t n_pairs = (int64_t)s * (s - 1) / 2;
     HostStaging st(ctx);
     int32_t* di;
@@ -159,7 +159,7 @@ extern "C" int sdice_chi2_pair_list(sdice_ctx* ctx, int64_t n, int32_t s, const 
     SD_TRY(sd_check_pair_list(__func__, s, m, pairs));
     if (n == 0 || m == 0) return SDICE_OK;
     SD_ARG(incl && excl && p, "NULL pointer");
-    for (int64_t i = 0; i < n * s; ++i) SD_ARG(incl[i] >= 0 && excl[i] >= 0, "counts must be non-negative");
+    SD_TRY(sd_check_pair_counts(__func__, n, s, incl, excl, false));
     HostStaging st(ctx);
     int32_t* di;
     int64_t *de, *db;

@@ -170,6 +170,12 @@ int sd_check_csr(const char* who, int64_t n_out, int64_t n_rows, const int64_t* 
 // (i, j) of pairs[m][2] lies in [0, s) and i != j; errors are prefixed with `who`.
 constexpr int64_t SD_MAX_PAIRS = (int64_t)8192 * 8191 / 2;
 int sd_check_pair_list(const char* who, int32_t s, int64_t m, const int32_t* pairs);
+// Count range of the pair tests (host entry points; include/sdice.h): the kernels take the counts as doubles, so for ANY
+// two samples i != j of a junction -- the table [[a, b], [c, d]] = [[incl_i, incl_j], [excl_i, excl_j]] -- the total
+// a + b + c + d must not exceed 2^53 (every count, margin and total an exact double) and, walk (Fisher): neither must
+// a d or b c (the walk's step products, fisher.hip Walk).  Non-negative counts; SDICE_ERR_ARG prefixed with `who`.
+constexpr int64_t SD_MAX_COUNT = (int64_t)1 << 53;
+int sd_check_pair_counts(const char* who, int64_t n, int32_t s, const int32_t* incl, const int64_t* excl, bool walk);
 
 // status of an asynchronous sdice_cluster_dev (synchronises when one is pending)
 int sd_cluster_resolve(sdice_ctx* ctx);

@@ -7,7 +7,7 @@
 // two-sided p is the sum of pmf(k) over the support with pmf(k) <= pmf(a) * (1 + 1e-14)
 // (its cdf/sf + binary-search branches compute exactly that set), clipped at 1.
 //
-// Here: pmf(a) from a log-factorial table in HBM/L2 (device lgamma beyond the table), and
+// Here: pmf(a) from a log-factorial table in HBM/L2 (the saddle-point form beyond the table), and
 // the RATIOS r_k = pmf(k)/pmf(a) by the exact one-step recurrence outward from k = a in both
 // directions, so the tie test r_k <= 1 + 1e-12 is decided to ~1e-14, far tighter than a
 // log-gamma difference could.  p = pmf(a) * (1 + sum of the accepted r_k).  Monotone tails are
@@ -24,12 +24,52 @@ struct LfTable {
     long long n;
 };
 
-// beyond the table (margins above fisher.table_max): a real call, so that the nine look-ups of a
-// p-value do not inline nine copies of lgamma and their registers into the kernels
-__device__ __noinline__ double lgamma_beyond_table(double x) { return lgamma(x); }
-
-__device__ __forceinline__ double logfact(const LfTable& t, long long k) {
-    return k < t.n ? t.lf[k] : lgamma_beyond_table((double)k + 1.0);
+// ---- log pmf(a) of a table whose total lies beyond the log-factorial table (fisher.table_max, 2^20 by default).
+// The nine log-factorials cancel from ~M log M down to ~1e2, so their difference carries a few ulp of lgamma(M): 2e-9 at
+// M = 2^20, 1e-5 at 1e9, 4e-3 at 2^40.  With log x! = x log x - x + h(x) the linear terms cancel identically (margins and
+// cells both add up to 2M) and the x log x terms collect into the cells' deviances from their expectations
+// e = row * col / M (Loader's saddle-point form of the hypergeometric pmf):
+//   log pmf(a) = h(n1) + h(n2) + h(n) + h(m) - h(M) - h(a) - h(b) - h(c) - h(d) - sum over the cells of dev(x, e),
+//   dev(x, e) = x log(x / e) + e - x >= 0.
+// Every term is of the size of the result: h(x) = 0.5 log(2 pi x) + O(1/x) and the deviances sum to -log pmf(a) up to
+// the h's, so the error is a few 1e-15 whatever the counts are.
+// h(x): 0 at x = 0; lgamma below 16; from there the Stirling series (the first term left out, (691/360360) x^-11, is
+// below 1.1e-16).
+__device__ double stirling_rest(double x) {
+    if (x == 0.0) return 0.0;
+    if (x < 16.0) return lgamma(x + 1.0) - (x * log(x) - x);
+    const double r = 1.0 / (x * x);
+    const double s = (1.0 / 12.0 - (1.0 / 360.0 - (1.0 / 1260.0 - (1.0 / 1680.0 - (1.0 / 1188.0) * r) * r) * r) * r) / x;
+    return 0.5 * log(6.283185307179586 * x) + s;
+}
+// dev(x, e) with delta = x - e given to full precision (x - e itself cancels when x is large).  Near the expectation,
+// with v = delta / (x + e):  x / e = (1 + v) / (1 - v), log(x / e) = 2 atanh(v), 2 x v - delta = delta v, so
+// dev = delta v + 2 x v (v^2 / 3 + v^4 / 5 + ...): |v| < 0.1, twelve terms reach 1e-26.
+__device__ double deviance_term(double x, double e, double delta) {
+    if (x == 0.0) return -delta;
+    if (fabs(delta) < 0.1 * (x + e)) {
+        const double v = delta / (x + e), w = v * v;
+        double s = 0.0;
+#pragma unroll
+        for (int j = 23; j >= 5; j -= 2) s = (s + 1.0 / (double)j) * w;
+        s = (s + 1.0 / 3.0) * w;
+        return delta * v + 2.0 * x * v * s;
+    }
+    return x * log(x / e) - delta;
+}
+// All four cells are off their expectations by the same +-delta = (ad - bc) / M; the products come with their rounding
+// errors (fma), so delta is good to ~3e-16 relative however close ad and bc are.  A real call: the kernels that use it
+// are cold paths and keep their registers.
+__device__ __noinline__ double log_pmf_beyond_table(double a, double b, double c, double d) {
+    const double n1 = a + b, n2 = c + d, nn = a + c, mm = b + d, M = n1 + n2;
+    const double ad = a * d, bc = b * c;
+    const double det = (ad - bc) + (fma(a, d, -ad) - fma(b, c, -bc));
+    const double delta = det / M;
+    const double dev = deviance_term(a, n1 * nn / M, delta) + deviance_term(b, n1 * mm / M, -delta) +
+                       deviance_term(c, n2 * nn / M, -delta) + deviance_term(d, n2 * mm / M, delta);
+    const double rest = (stirling_rest(n1) + stirling_rest(n2) + stirling_rest(nn) + stirling_rest(mm)) - stirling_rest(M) -
+                        (stirling_rest(a) + stirling_rest(b) + stirling_rest(c) + stirling_rest(d));
+    return rest - dev;
 }
 
 // 1/y for y an integer-valued double in [1, 2^63): hardware seed + two Newton steps (no scaling or
@@ -52,9 +92,14 @@ __device__ __forceinline__ double rcp_pos(double y) {
 // one reciprocal per p-value.  "Accepted" (pmf(k) <= pmf(a) (1 + 1e-12)) is P <= slack Q; the products carry
 // a few 1e-16 of rounding per step.
 // The step is BRANCH-FREE and needs no end test: N = u1 u2 and D = v1 v2 are quadratics in the step index,
-// advanced by their first differences (N += dN, dN += 2: exact integers below 2^63), and at the end of the
-// support one of u1, u2 is zero, so N = 0 there, P = 0 from then on and further steps leave S/Q unchanged (both
-// take the same factor D).  A lane may therefore run past its end, and a lane with nothing to do may step on
+// advanced by their first differences (N += dN, dN += 2).  They are DOUBLES: exact integers only while the products
+// stay at or below 2^53, i.e. a d <= 2^53 and b c <= 2^53 for the table [[a, b], [c, d]] -- the host entry points
+// refuse anything else (sd_check_pair_counts).  At the end of the support one of u1, u2 is zero, so N = 0 there, P = 0 from then on and further steps leave S/Q unchanged (both
+// take the same factor D).  That needs N to be EXACT: a start product rounded to 53 bits drifts off the quadratic by
+// up to an ulp per step and ends a few thousand off zero, with either sign; the steps past the end then add
+// r_end * N_end / D and its successors to the sum -- a negative term is always "accepted" -- which for a table deep
+// in a tail (r_end = pmf(end) / pmf(a) of 1e30) turns the sum into -1e30 or -inf.  (D only needs to be relatively
+// accurate, and is.)  A lane may therefore run past its end, and a lane with nothing to do may step on
 // stale state: the state machine issues steps for the whole wave without touching the exec mask
 // (10 VALU per step -- 2 mul, 1 fma, 4 add, 1 compare, 2 select -- against 15 + ~10 scalar for the exec-masked step
 // with the four factors kept separately).
@@ -143,8 +188,11 @@ __device__ double fisher_two_sided(long long a, long long b, long long c, long l
     const long long M = n1 + n2;
     const long long lo = n - n2 > 0 ? n - n2 : 0;
     const long long hi = n1 < n ? n1 : n;
-    const double logp = logfact(t, n1) + logfact(t, n2) + logfact(t, n) + logfact(t, M - n) - logfact(t, M) -
-                        logfact(t, a) - logfact(t, n1 - a) - logfact(t, n - a) - logfact(t, n2 - n + a);
+    // (the same two evaluations, term for term, as pmf_block and fisher_beyond_table_kernel: the entry points agree
+    // bit for bit on a table)
+    const double* lf = t.lf;
+    const double logp = M < t.n ? lf[n1] + lf[n2] + lf[n] + lf[m] - lf[M] - lf[a] - lf[b] - lf[c] - lf[d]
+                                : log_pmf_beyond_table((double)a, (double)b, (double)c, (double)d);
     const double pexact = exp(logp);
     const double da = (double)a, dn1 = (double)n1, dn2 = (double)n2, dn = (double)n;
     Walk w;
@@ -189,16 +237,6 @@ __global__ void __launch_bounds__(256) pair_table_kernel(unsigned* __restrict__ 
     tab[q] = ((unsigned)i << 16) | (unsigned)j;
 }
 
-__device__ __forceinline__ double logfact_d(const LfTable& t, double k) {
-    return k < (double)t.n ? t.lf[(int)k] : lgamma_beyond_table(k + 1.0);
-}
-// log pmf(a) of a table whose total is beyond the log-factorial table
-__device__ __noinline__ double log_pmf_beyond_table(double a, double b, double c, double d) {
-    const double n1 = a + b, n2 = c + d, nn = a + c, mm = b + d;
-    return lgamma(n1 + 1.0) + lgamma(n2 + 1.0) + lgamma(nn + 1.0) + lgamma(mm + 1.0) - lgamma(n1 + n2 + 1.0) - lgamma(a + 1.0) -
-           lgamma(b + 1.0) - lgamma(c + 1.0) - lgamma(d + 1.0);
-}
-
 // p = pmf(a) * sum for the 256 pairs from q0 on, whose sums wait in the ring: the whole wave, four pairs per lane, the
 // p-values leave as contiguous 512-byte pieces.  No call in here: a table whose total lies beyond the log-factorial table
 // (counts above fisher.table_max, 2^20 by default) leaves MINUS its sum (sums are >= 1) and raises the junction's flag;
@@ -240,7 +278,8 @@ __device__ __forceinline__ bool pmf_block(int s, double* __restrict__ out, const
     return beyond;
 }
 
-// the junctions flagged by the pair kernel: p = pmf(a) * sum with lgamma for the pairs that carry a negative sum
+// the junctions flagged by the pair kernel: p = pmf(a) * sum, pmf(a) by log_pmf_beyond_table, for the pairs that carry a
+// negative sum
 __global__ void __launch_bounds__(256) fisher_beyond_table_kernel(const int32_t* __restrict__ incl, const int64_t* __restrict__ excl,
                                                                   int64_t n, int s, int64_t n_pairs, double* __restrict__ p,
                                                                   const unsigned* __restrict__ pair_tab,
@@ -438,6 +477,48 @@ int sd_check_pair_list(const char* who, int32_t s, int64_t m, const int32_t* pai
     return SDICE_OK;
 }
 
+// The count range of the pair tests (include/sdice.h): see common.h
+int sd_check_pair_counts(const char* who, int64_t n, int32_t s, const int32_t* incl, const int64_t* excl, bool walk) {
+    typedef unsigned __int128 u128;
+    for (int64_t row = 0; row < n; ++row) {
+        // the two largest sample totals, inclusion counts and exclusion sums of the junction (and whose they are)
+        int64_t t1 = 0, t2 = 0, i1 = 0, i2 = 0, e1 = 0, e2 = 0;
+        int32_t i1k = -1, e1k = -1;
+        for (int32_t k = 0; k < s; ++k) {
+            const int64_t a = incl[row * s + k], c = excl[row * s + k];
+            if (a < 0 || c < 0) {
+                sdice_set_error("%s: counts must be non-negative", who);
+                return SDICE_ERR_ARG;
+            }
+            if (c > SD_MAX_COUNT) {
+                sdice_set_error("%s: junction %lld, sample %d: an exclusion sum of %lld is above 2^53", who, (long long)row, k,
+                                (long long)c);
+                return SDICE_ERR_ARG;
+            }
+            const int64_t t = a + c;
+            if (t > t1) { t2 = t1; t1 = t; } else if (t > t2) t2 = t;
+            if (a > i1) { i2 = i1; i1 = a; i1k = k; } else if (a > i2) i2 = a;
+            if (c > e1) { e2 = e1; e1 = c; e1k = k; } else if (c > e2) e2 = c;
+        }
+        if (t1 + t2 > SD_MAX_COUNT) {
+            sdice_set_error("%s: junction %lld: two samples' counts add up to %lld, above 2^53", who, (long long)row,
+                            (long long)(t1 + t2));
+            return SDICE_ERR_ARG;
+        }
+        if (walk) {
+            // the largest incl_i * excl_j over i != j
+            const u128 prod = i1k != e1k ? (u128)i1 * (u128)e1 : std::max((u128)i1 * (u128)e2, (u128)i2 * (u128)e1);
+            if (prod > (u128)SD_MAX_COUNT) {
+                sdice_set_error("%s: junction %lld: an inclusion count times another sample's exclusion sum is above 2^53 "
+                                "(largest inclusion count %lld, largest exclusion sum %lld)", who, (long long)row, (long long)i1,
+                                (long long)e1);
+                return SDICE_ERR_ARG;
+            }
+        }
+    }
+    return SDICE_OK;
+}
+
 extern "C" int sdice_pair_list_pack_dev(sdice_ctx* ctx, int32_t s, int64_t m, const int32_t* pairs, uint32_t* d_tab) try {
     SD_ARG(ctx, "ctx is NULL");
     SD_ARG(s >= 0 && m >= 0, "negative size");
@@ -545,7 +626,7 @@ extern "C" int sdice_fisher_pairs(sdice_ctx* ctx, int64_t n, int32_t s, const in
     SD_ARG(n >= 0 && s >= 0, "negative size");
     if (n == 0 || s < 2) return SDICE_OK;
     SD_ARG(incl && excl && p, "NULL pointer");
-    for (int64_t i = 0; i < n * s; ++i) SD_ARG(incl[i] >= 0 && excl[i] >= 0, "counts must be non-negative");
+    SD_TRY(sd_check_pair_counts(__func__, n, s, incl, excl, true));
     const int64_t n_pairs = (int64_t)s * (s - 1) / 2;
     HostStaging st(ctx);
     int32_t* di;
@@ -568,7 +649,7 @@ extern "C" int sdice_fisher_pair_list(sdice_ctx* ctx, int64_t n, int32_t s, cons
     SD_TRY(sd_check_pair_list(__func__, s, m, pairs));
     if (n == 0 || m == 0) return SDICE_OK;
     SD_ARG(incl && excl && p, "NULL pointer");
-    for (int64_t i = 0; i < n * s; ++i) SD_ARG(incl[i] >= 0 && excl[i] >= 0, "counts must be non-negative");
+    SD_TRY(sd_check_pair_counts(__func__, n, s, incl, excl, true));
     HostStaging st(ctx);
     int32_t* di;
     int64_t* de;
@@ -595,6 +676,17 @@ extern "C" int sdice_fisher_tables(sdice_ctx* ctx, int64_t m, const int64_t* abc
     if (m == 0) return SDICE_OK;
     SD_ARG(abcd && p, "NULL pointer");
     for (int64_t i = 0; i < 4 * m; ++i) SD_ARG(abcd[i] >= 0, "table entries must be non-negative");
+    for (int64_t i = 0; i < m; ++i) {                                 // the count range of sd_check_pair_counts, per table
+        typedef unsigned __int128 u128;
+        const int64_t* t = abcd + 4 * i;
+        const bool fits = t[0] <= SD_MAX_COUNT && t[1] <= SD_MAX_COUNT && t[2] <= SD_MAX_COUNT && t[3] <= SD_MAX_COUNT &&
+                          (u128)t[0] + (u128)t[1] + (u128)t[2] + (u128)t[3] <= (u128)SD_MAX_COUNT;
+        if (!fits || (u128)t[0] * (u128)t[3] > (u128)SD_MAX_COUNT || (u128)t[1] * (u128)t[2] > (u128)SD_MAX_COUNT) {
+            sdice_set_error("%s: table %lld (%lld, %lld, %lld, %lld): the total, a*d and b*c must not exceed 2^53", __func__,
+                            (long long)i, (long long)t[0], (long long)t[1], (long long)t[2], (long long)t[3]);
+            return SDICE_ERR_ARG;
+        }
+    }
     SD_HIP(hipSetDevice(ctx->device));
     LfTable t;
     SD_TRY(get_lf_table(ctx, &t));

@@ -2,7 +2,7 @@
 references per distinct 2x2 table (scipy.stats.fisher_exact and an exact rational sum, scipy chi2_contingency) and the
 element-wise comparison, of tests/test_gpu_pair_sweeps.py and tests/test_gpu_pair_list.py; the host stand-in engine and
 argument helpers of the `pairwise --pairs` tests; the recording engine, array and communicator doubles of the sharded
-pipelines' step() tests."""
+pipelines' step() tests; the large-count rows of tests/test_gpu_pair_large_counts.py and tests/test_fisher_referee_cpu.py."""
 import argparse
 import contextlib
 import io
@@ -356,3 +356,104 @@ class _IntoComm:
 
     def allsum(self, value):
         return int(value)
+
+
+# ------------------------------------------------------------------------------ large counts (test_gpu_pair_large_counts)
+# Rows of (incl, excl) samples; every ordered pair (i, j), i != j, of a row is a fixture table [[incl_i, incl_j],
+# [excl_i, excl_j]].  Expected values: tests/fisher_referee.py.  Every table meets (tests/test_fisher_referee_cpu.py):
+#   - nearest >= 1e-9: no ratio r_k != 1 within 1e-9 of 1, so the kernel's tie slack (1e-12), scipy's (1e-14) and the
+#     referee's (ties only) select the same terms.  Two samples with EQUAL totals give mathematical ties
+#     (pmf(k) = pmf(a + b - k)); two huge totals that differ by little give near-ties, hence the spread of a few per cent;
+#   - the step budget: at most LARGE_MAX_STEPS walk steps per table and LARGE_MAX_LANE_STEPS per set of rows, counted
+#     by tests/fisher_walk_model.py at the longest trip (24) -- a GPU test runs one set through each entry point once;
+#   - the count range of include/sdice.h: total, a d and b c at most 2^53.
+LARGE_MAX_STEPS = 2_000_000
+LARGE_MAX_LANE_STEPS = 20_000_000
+LF_TABLE_DEFAULT = 1 << 20      # fisher.table_max: a total below it reads the log-factorial table
+I32_MAX = (1 << 31) - 1
+_H = 1 << 19
+
+
+def _near(x, incl=(1500, 1700, 0, 2000, 37, 1, 640, 1100)):
+    """small inclusion counts against exclusion sums within a few per cent of x; samples 0 and 1 share their total (exact
+    ties), sample 2 has a = 0 (and, listed second, b = 0: a at either end of its support)"""
+    spread = (0, 0, 31, -17, 43, -29, 11, -7)             # in thousandths of x
+    out = []
+    for k, (a, sp) in enumerate(zip(incl, spread)):
+        out.append((a, x + x * sp // 1000 + 13 * k))
+    out[1] = (incl[1], out[0][0] + out[0][1] - incl[1])
+    return out
+
+
+LARGE_SETS = {
+    # totals of 2^20 - 1, 2^20 and 2^20 + 1 at the default table: sample totals 2^19 (0, 1), 2^19 - 1 (2), 2^19 + 1 (3);
+    # the second row stays inside the table
+    "boundary": [
+        [(104858, _H - 104858), (105500, _H - 105500), (104000, _H - 1 - 104000), (105900, _H + 1 - 105900),
+         (40, 190), (0, 77), (2100, 8000), (13, 13)],
+        [(104858, _H - 2 - 104858), (105500, _H - 105500), (104000, _H - 1 - 104000), (20000, 80500),
+         (40, 190), (0, 77), (2100, 8000), (13, 13)],
+    ],
+    # balanced tables at counts of 1e5 (inside the table), 3e5 and 1e6 (beyond it): long walks, many rescales, a tail
+    # cut that fires late; small columns beside them
+    "balanced": [
+        [(1_000_000, 4_000_000), (1_003_000, 4_001_000), (300_000, 1_200_000), (301_500, 1_200_700),
+         (100_000, 400_000), (100_600, 400_300), (12, 50), (0, 7)],
+    ],
+    "1e7": [_near(10 ** 7) + [(12, 50), (700, 1300), (1300, 700)]],
+    "1e9": [_near(10 ** 9) + [(12, 50), (700, 1300), (1300, 700)]],
+    "2^31": [_near((1 << 31) - 1)[:4] + _near((1 << 31) + 1)[4:] + [(12, 50), (700, 1300), (1300, 700)]],
+    "1e10": [_near(10 ** 10) + [(12, 50), (700, 1300), (1300, 700)]],
+    "2^40": [_near(1 << 40) + [(12, 50), (700, 1300), (1300, 700)]],
+    # a d <= 2^53 leaves inclusion counts of 0, 1 and 2 at exclusion sums of 2^52; sample totals of exactly 2^52 twice:
+    # a table total of 2^53, the largest accepted
+    "2^52": [[(2, (1 << 52) - 2), (1, (1 << 52) - 1), (0, (1 << 51) + (1 << 49)), (2, (1 << 51) + 5), (1, 3), (2, 7), (0, 5),
+              (1, 1 << 40), (2, 1 << 45)]],
+    # the largest inclusion count against 2^40, beside columns it is balanced with (incl ~ excl / 512) and a d <= 2^53
+    "int32": [[(I32_MAX, 1 << 40), (1000, 512_000), (1100, 520_000), (640, 300_000), (2, 1000), (0, 4000),
+               (4090, 1 << 21), (5, 2560)]],
+}
+# the unroll sweep runs on the small-a / huge-d sets only
+LARGE_SMALL_A = ("1e7", "1e9", "2^31", "1e10", "2^40", "2^52", "int32")
+
+
+def large_tables(name):
+    """the distinct tables of a set: every ordered pair of every row -> list of (a, b, c, d)"""
+    seen = {}
+    for row in LARGE_SETS[name]:
+        for i, (a, c) in enumerate(row):
+            for j, (b, d) in enumerate(row):
+                if i != j:
+                    seen[(a, b, c, d)] = None
+    return list(seen)
+
+
+def large_arrays(name):
+    """(incl int32[n, s], excl int64[n, s]) of a set"""
+    rows = np.array(LARGE_SETS[name], dtype=np.int64)
+    return rows[..., 0].astype(np.int32), rows[..., 1].copy()
+
+
+def in_count_range(a, b, c, d, walk=True):
+    """the range the host entry points accept (include/sdice.h)"""
+    lim = 1 << 53
+    return a + b + c + d <= lim and (not walk or (a * d <= lim and b * c <= lim))
+
+
+def large_pair_list(s):
+    """the list of the large-count tests: every pair reversed (i > j), then the last three pairs again, forwards"""
+    iu, ju = np.triu_indices(s, 1)
+    nat = np.stack([iu, ju], axis=1).astype(np.int32)
+    return np.concatenate([nat[:, ::-1], nat[-3:]])
+
+
+def large_test_tables(name):
+    """every table a GPU test walks for a set, call by call: the distinct tables through sdice_fisher_tables, all pairs
+    and the list through the host and the _dev entry points"""
+    out = large_tables(name)
+    for row in LARGE_SETS[name]:
+        s = len(row)
+        iu, ju = np.triu_indices(s, 1)
+        for pairs in (zip(iu, ju), large_pair_list(s)):
+            out += 2 * [(row[i][0], row[j][0], row[i][1], row[j][1]) for i, j in pairs]
+    return out
