@@ -9,8 +9,7 @@
 //   chi2 = sum (observed - expected)^2 / expected  (row-major order), p = chdtrc(1, chi2)
 //        = erfc(sqrt(chi2 / 2))
 // HBM-bound in principle (8 B per p-value, ~40 flops); same pair enumeration as the Fisher kernel.
-#include "common.h"
-#include <math.h>
+#include "pairs.h"
 
 namespace {
 
@@ -56,20 +55,8 @@ __global__ void __launch_bounds__(256) chi2_pairs_kernel(const int32_t* __restri
         double* out = p + row * n_pairs;
         for (int64_t q = threadIdx.x; q < n_pairs; q += blockDim.x) {
             int i, j;
-            if (LIST) {
-                const unsigned ij = pair_tab[q];
-                i = (int)(ij >> 16);
-                j = (int)(ij & 0xffffu);
-            } else {
-                // invert q = i*s - i(i+1)/2 + (j-i-1)   (pairwise_fisher.py:142-147)
-                const double bb = 2.0 * s - 1.0;
-                i = (int)((bb - sqrt(bb * bb - 8.0 * (double)q)) * 0.5);
-                if (i < 0) i = 0;
-                if (i > s - 2) i = s - 2;
-                while (i > 0 && (int64_t)i * s - (int64_t)i * (i + 1) / 2 > q) --i;
-                while ((int64_t)(i + 1) * s - (int64_t)(i + 1) * (i + 2) / 2 <= q) ++i;
-                j = (int)(q - ((int64_t)i * s - (int64_t)i * (i + 1) / 2)) + i + 1;
-            }
+            if (LIST) sd_pair_unpack(pair_tab[q], i, j);
+            else sd_pair_of(q, s, i, j);
             bool bad = false;
             out[q] = chi2_yates_p(inc[i], inc[j], exc[i], exc[j], bad);
             bad_count += bad ? 1 : 0;
@@ -96,88 +83,27 @@ static int chi2_launch(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* d_in
     return SDICE_OK;
 }
 
+// the launch of a checked call (pairs.h)
+static int chi2_call(const PairCall& c) {
+    return chi2_launch(c.ctx, c.n, c.s, c.incl, c.excl, c.cols(), static_cast<const uint32_t*>(c.tab), c.p, c.n_bad);
+}
+
 extern "C" int sdice_chi2_pairs_dev(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* d_incl, const int64_t* d_excl,
                                     double* d_p, int64_t* d_n_bad) {
-    SD_ARG(ctx, "ctx is NULL");
-    SD_ARG(n >= 0 && s >= 0, "negative size");
-    SD_ARG(d_n_bad, "d_n_bad is NULL");
-    SD_HIP(hipSetDevice(ctx->device));
-    SD_HIP(hipMemsetAsync(d_n_bad, 0, 8, ctx->stream));
-    if (n == 0 || s < 2) return SDICE_OK;
-    SD_ARG(d_incl && d_excl && d_p, "NULL pointer");
-    SD_ARG(s <= 8192, "more than 8192 samples per junction is not supported");
-    return chi2_launch(ctx, n, s, d_incl, d_excl, (int64_t)s * (s - 1) / 2, nullptr, d_p, d_n_bad);
+    return sd_pairs_dev({__func__, ctx, n, s, d_incl, d_excl, false, 0, nullptr, d_p, true, d_n_bad}, chi2_call);
 }
 
 extern "C" int sdice_chi2_pair_list_dev(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* d_incl, const int64_t* d_excl,
                                         int64_t m, const uint32_t* d_tab, double* d_p, int64_t* d_n_bad) {
-    SD_ARG(ctx, "ctx is NULL");
-    SD_ARG(n >= 0 && s >= 0 && m >= 0, "negative size");
-    SD_ARG(d_n_bad, "d_n_bad is NULL");
-    SD_ARG(s <= 8192, "more than 8192 samples per junction is not supported");
-    SD_ARG(m <= SD_MAX_PAIRS, "more than 33550336 pairs in one list is not supported");
-    SD_HIP(hipSetDevice(ctx->device));
-    SD_HIP(hipMemsetAsync(d_n_bad, 0, 8, ctx->stream));
-    if (n == 0 || m == 0) return SDICE_OK;
-    SD_ARG(s >= 2, "a pair list needs at least two samples");
-    SD_ARG(d_incl && d_excl && d_tab && d_p, "NULL pointer");
-    return chi2_launch(ctx, n, s, d_incl, d_excl, m, d_tab, d_p, d_n_bad);
+    return sd_pairs_dev({__func__, ctx, n, s, d_incl, d_excl, true, m, d_tab, d_p, true, d_n_bad}, chi2_call);
 }
 
 extern "C" int sdice_chi2_pairs(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* incl, const int64_t* excl, double* p,
                                 int64_t* n_bad) {
-    SD_ARG(ctx, "ctx is NULL");
-    SD_ARG(n >= 0 && s >= 0, "negative size");
-    SD_ARG(n_bad, "n_bad is NULL");
-    *n_bad = 0;
-    if (n == 0 || s < 2) return SDICE_OK;
-    SD_ARG(incl && excl && p, "NULL pointer");
-    SD_TRY(sd_check_pair_counts(__func__, n, s, incl, excl, false));
-    const int64_t n_pairs = (int64_t)s * (s - 1) / 2;
-    HostStaging st(ctx);
-    int32_t* di;
-    int64_t *de, *db;
-    double* dp;
-    SD_TRY(st.upload(&di, incl, n * s));
-    SD_TRY(st.upload(&de, excl, n * s));
-    SD_TRY(st.alloc(&dp, n * n_pairs));
-    SD_TRY(st.alloc(&db, 1));
-    SD_TRY(sdice_chi2_pairs_dev(ctx, n, s, di, de, dp, db));
-    SD_TRY(st.download(p, dp, n * n_pairs));
-    return st.download(n_bad, db, 1);
+    return sd_pairs_host({__func__, ctx, n, s, incl, excl, false, 0, nullptr, p, true, n_bad}, chi2_call);
 }
 
 extern "C" int sdice_chi2_pair_list(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* incl, const int64_t* excl, int64_t m,
-                                    const int32_t* pairs, double* p, int64_t* n_bad) try {
-    SD_ARG(ctx, "ctx is NULL");
-    SD_ARG(n >= 0 && s >= 0 && m >= 0, "negative size");
-    SD_ARG(n_bad, "n_bad is NULL");
-    *n_bad = 0;
-    SD_ARG(m == 0 || pairs, "NULL pointer");
-    SD_ARG(s <= 8192, "more than 8192 samples per junction is not supported");
-    SD_ARG(m <= SD_MAX_PAIRS, "more than 33550336 pairs in one list is not supported");
-    SD_TRY(sd_check_pair_list(__func__, s, m, pairs));
-    if (n == 0 || m == 0) return SDICE_OK;
-    SD_ARG(incl && excl && p, "NULL pointer");
-    SD_TRY(sd_check_pair_counts(__func__, n, s, incl, excl, false));
-    HostStaging st(ctx);
-    int32_t* di;
-    int64_t *de, *db;
-    uint32_t* dt;
-    double* dp;
-    SD_TRY(st.upload(&di, incl, n * s));
-    SD_TRY(st.upload(&de, excl, n * s));
-    SD_TRY(st.alloc(&dt, m));
-    SD_TRY(sdice_pair_list_pack_dev(ctx, s, m, pairs, dt));
-    SD_TRY(st.alloc(&dp, n * m));
-    SD_TRY(st.alloc(&db, 1));
-    SD_TRY(sdice_chi2_pair_list_dev(ctx, n, s, di, de, m, dt, dp, db));
-    SD_TRY(st.download(p, dp, n * m));
-    return st.download(n_bad, db, 1);
-} catch (const std::exception& e) {
-    sdice_set_error("sdice_chi2_pair_list: %s", e.what());
-    return SDICE_ERR_NOMEM;
-} catch (...) {
-    sdice_set_error("sdice_chi2_pair_list: unknown exception");
-    return SDICE_ERR_STATE;
+                                    const int32_t* pairs, double* p, int64_t* n_bad) {
+    return sd_pairs_host({__func__, ctx, n, s, incl, excl, true, m, pairs, p, true, n_bad}, chi2_call);
 }

@@ -26,13 +26,14 @@ void sdice_set_error(const char* fmt, ...);
         if (_s != SDICE_OK) return _s;                                                 \
     } while (0)
 
-#define SD_ARG(cond, msg)                                                              \
+#define SD_ARG_AS(who, cond, msg)                                                      \
     do {                                                                               \
         if (!(cond)) {                                                                 \
-            sdice_set_error("%s: %s", __func__, msg);                                  \
+            sdice_set_error("%s: %s", (who), msg);                                     \
             return SDICE_ERR_ARG;                                                      \
         }                                                                              \
     } while (0)
+#define SD_ARG(cond, msg) SD_ARG_AS(__func__, cond, msg)
 
 struct ProfPending {
     int name_id;
@@ -165,17 +166,8 @@ class HostStaging {
 // col entry is in [0, n_rows).  Errors are prefixed with `who`.
 int sd_check_csr(const char* who, int64_t n_out, int64_t n_rows, const int64_t* row_ptr, const int32_t* col);
 
-// Pair lists of the pairwise kernels: a column index takes 16 bits of a packed table entry (s <= 8192) and the pair kernel
-// counts pairs in an int below 2^25 -- a list may be as long as every pair of 8192 samples.  sd_check_pair_list: every
-// (i, j) of pairs[m][2] lies in [0, s) and i != j; errors are prefixed with `who`.
-constexpr int64_t SD_MAX_PAIRS = (int64_t)8192 * 8191 / 2;
-int sd_check_pair_list(const char* who, int32_t s, int64_t m, const int32_t* pairs);
-// Count range of the pair tests (host entry points; include/sdice.h): the kernels take the counts as doubles, so for ANY
-// two samples i != j of a junction -- the table [[a, b], [c, d]] = [[incl_i, incl_j], [excl_i, excl_j]] -- the total
-// a + b + c + d must not exceed 2^53 (every count, margin and total an exact double) and, walk (Fisher): neither must
-// a d or b c (the walk's step products, fisher.hip Walk).  Non-negative counts; SDICE_ERR_ARG prefixed with `who`.
-constexpr int64_t SD_MAX_COUNT = (int64_t)1 << 53;
-int sd_check_pair_counts(const char* who, int64_t n, int32_t s, const int32_t* incl, const int64_t* excl, bool walk);
+// the host-side argument checks of the pair tests (paircheck.cpp)
+#include "paircheck.h"
 
 // status of an asynchronous sdice_cluster_dev (synchronises when one is pending)
 int sd_cluster_resolve(sdice_ctx* ctx);

@@ -13,8 +13,7 @@
 // log-gamma difference could.  p = pmf(a) * (1 + sum of the accepted r_k).  Monotone tails are
 // cut once the remaining mass is below 1e-13 of the sum (the pmf is log-concave).
 // The kernel is f64-VALU bound (O(support) steps per p-value), not HBM bound.
-#include "common.h"
-#include <math.h>
+#include "pairs.h"
 #include <algorithm>
 
 namespace {
@@ -217,23 +216,12 @@ __global__ void __launch_bounds__(256) fisher_tables_kernel(const int64_t* __res
     p[i] = fisher_two_sided(abcd[4 * i], abcd[4 * i + 1], abcd[4 * i + 2], abcd[4 * i + 3], t);
 }
 
-// pair index q -> (i, j), i < j, row-major (pairwise_fisher.py:142-147): q = i*s - i(i+1)/2 + (j-i-1)
-__device__ __forceinline__ void pair_of(int64_t q, int s, int& i, int& j) {
-    const double bb = 2.0 * s - 1.0;
-    i = (int)((bb - sqrt(bb * bb - 8.0 * (double)q)) * 0.5);
-    if (i < 0) i = 0;
-    if (i > s - 2) i = s - 2;
-    while (i > 0 && (int64_t)i * s - (int64_t)i * (i + 1) / 2 > q) --i;
-    while ((int64_t)(i + 1) * s - (int64_t)(i + 1) * (i + 2) / 2 <= q) ++i;
-    j = (int)(q - ((int64_t)i * s - (int64_t)i * (i + 1) / 2)) + i + 1;
-}
-
 // (i << 16 | j) of every pair index: the same for every junction, built once per call shape
 __global__ void __launch_bounds__(256) pair_table_kernel(unsigned* __restrict__ tab, int64_t n_pairs, int s) {
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n_pairs) return;
     int i, j;
-    pair_of(q, s, i, j);
+    sd_pair_of(q, s, i, j);
     tab[q] = ((unsigned)i << 16) | (unsigned)j;
 }
 
@@ -256,7 +244,8 @@ __device__ __forceinline__ bool pmf_block(int s, double* __restrict__ out, const
         if (q < n_pairs) {
             const double total = ring[q & 511];
             const unsigned ij = pair_tab[q];
-            const int i = (int)(ij >> 16), j = (int)(ij & 0xffffu);
+            int i, j;
+            sd_pair_unpack(ij, i, j);
             const double a = inc[i], b = inc[j], c = exc[i], d = exc[j];
             const double n1 = a + b, n2 = c + d, nn = a + c, mm = b + d, M = n1 + n2;
             double pv = 1.0;                                           // a zero margin (scipy: p = 1)
@@ -291,7 +280,8 @@ __global__ void __launch_bounds__(256) fisher_beyond_table_kernel(const int32_t*
         const double v = out[q];
         if (v < 0.0) {
             const unsigned ij = pair_tab[q];
-            const int i = (int)(ij >> 16), j = (int)(ij & 0xffffu);
+            int i, j;
+            sd_pair_unpack(ij, i, j);
             const double a = (double)incl[row * s + i], b = (double)incl[row * s + j];
             const double c = (double)excl[row * s + i], d = (double)excl[row * s + j];
             const double pv = exp(log_pmf_beyond_table(a, b, c, d)) * -v;
@@ -379,7 +369,8 @@ fisher_pairs_kernel(const int32_t* __restrict__ incl, const int64_t* __restrict_
                 const unsigned e0 = (unsigned)__shfl((int)tab_cur, dq & 63), e1 = (unsigned)__shfl((int)tab_nxt, dq & 63);
                 if (phase == 0 && q < lim) {
                     const unsigned ij = dq < 64 ? e0 : e1;
-                    const int i = (int)(ij >> 16), j = (int)(ij & 0xffffu);
+                    int i, j;
+                    sd_pair_unpack(ij, i, j);
                     ta = inc[i]; tb = inc[j]; tc = exc[i]; td = exc[j];
                     q_cur = q;
                     w.start(ta, td, tb + 1.0, tc + 1.0, ta < td ? ta : td);   // down from k = a (possibly no step at all)
@@ -461,83 +452,6 @@ static int get_lf_table(sdice_ctx* ctx, LfTable* out) {
     return SDICE_OK;
 }
 
-// A caller's pair list: every (i, j) a pair of different columns of [0, s)
-int sd_check_pair_list(const char* who, int32_t s, int64_t m, const int32_t* pairs) {
-    for (int64_t q = 0; q < m; ++q) {
-        const int32_t i = pairs[2 * q], j = pairs[2 * q + 1];
-        if (i < 0 || j < 0 || i >= s || j >= s) {
-            sdice_set_error("%s: pair %lld is (%d, %d): column indices must lie in [0, %d)", who, (long long)q, i, j, s);
-            return SDICE_ERR_ARG;
-        }
-        if (i == j) {
-            sdice_set_error("%s: pair %lld pairs column %d with itself", who, (long long)q, i);
-            return SDICE_ERR_ARG;
-        }
-    }
-    return SDICE_OK;
-}
-
-// The count range of the pair tests (include/sdice.h): see common.h
-int sd_check_pair_counts(const char* who, int64_t n, int32_t s, const int32_t* incl, const int64_t* excl, bool walk) {
-    typedef unsigned __int128 u128;
-    for (int64_t row = 0; row < n; ++row) {
-        // the two largest sample totals, inclusion counts and exclusion sums of the junction (and whose they are)
-        int64_t t1 = 0, t2 = 0, i1 = 0, i2 = 0, e1 = 0, e2 = 0;
-        int32_t i1k = -1, e1k = -1;
-        for (int32_t k = 0; k < s; ++k) {
-            const int64_t a = incl[row * s + k], c = excl[row * s + k];
-            if (a < 0 || c < 0) {
-                sdice_set_error("%s: counts must be non-negative", who);
-                return SDICE_ERR_ARG;
-            }
-            if (c > SD_MAX_COUNT) {
-                sdice_set_error("%s: junction %lld, sample %d: an exclusion sum of %lld is above 2^53", who, (long long)row, k,
-                                (long long)c);
-                return SDICE_ERR_ARG;
-            }
-            const int64_t t = a + c;
-            if (t > t1) { t2 = t1; t1 = t; } else if (t > t2) t2 = t;
-            if (a > i1) { i2 = i1; i1 = a; i1k = k; } else if (a > i2) i2 = a;
-            if (c > e1) { e2 = e1; e1 = c; e1k = k; } else if (c > e2) e2 = c;
-        }
-        if (t1 + t2 > SD_MAX_COUNT) {
-            sdice_set_error("%s: junction %lld: two samples' counts add up to %lld, above 2^53", who, (long long)row,
-                            (long long)(t1 + t2));
-            return SDICE_ERR_ARG;
-        }
-        if (walk) {
-            // the largest incl_i * excl_j over i != j
-            const u128 prod = i1k != e1k ? (u128)i1 * (u128)e1 : std::max((u128)i1 * (u128)e2, (u128)i2 * (u128)e1);
-            if (prod > (u128)SD_MAX_COUNT) {
-                sdice_set_error("%s: junction %lld: an inclusion count times another sample's exclusion sum is above 2^53 "
-                                "(largest inclusion count %lld, largest exclusion sum %lld)", who, (long long)row, (long long)i1,
-                                (long long)e1);
-                return SDICE_ERR_ARG;
-            }
-        }
-    }
-    return SDICE_OK;
-}
-
-extern "C" int sdice_pair_list_pack_dev(sdice_ctx* ctx, int32_t s, int64_t m, const int32_t* pairs, uint32_t* d_tab) try {
-    SD_ARG(ctx, "ctx is NULL");
-    SD_ARG(s >= 0 && m >= 0, "negative size");
-    SD_ARG(s <= 8192, "more than 8192 samples per junction is not supported");
-    SD_ARG(m <= SD_MAX_PAIRS, "more than 33550336 pairs in one list is not supported");
-    if (m == 0) return SDICE_OK;
-    SD_ARG(pairs && d_tab, "NULL pointer");
-    SD_TRY(sd_check_pair_list(__func__, s, m, pairs));
-    std::vector<uint32_t> tab((size_t)m);
-    for (int64_t q = 0; q < m; ++q) tab[q] = ((uint32_t)pairs[2 * q] << 16) | (uint32_t)pairs[2 * q + 1];
-    return sdice_h2d(ctx, d_tab, tab.data(), m * 4);
-} catch (const std::exception& e) {
-    sdice_set_error("sdice_pair_list_pack_dev: %s", e.what());
-    return SDICE_ERR_NOMEM;
-} catch (...) {
-    sdice_set_error("sdice_pair_list_pack_dev: unknown exception");
-    return SDICE_ERR_STATE;
-}
-
 // The pair kernel and its second pass over n junctions and the n_pairs columns of a pair table: d_list, a caller's
 // packed list, or (d_list == NULL) every pair in row-major order, built here.
 static int fisher_launch(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* d_incl, const int64_t* d_excl,
@@ -591,26 +505,19 @@ static int fisher_launch(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* d_
     return SDICE_OK;
 }
 
+// the launch of a checked call (pairs.h)
+static int fisher_call(const PairCall& c) {
+    return fisher_launch(c.ctx, c.n, c.s, c.incl, c.excl, c.cols(), static_cast<const uint32_t*>(c.tab), c.p);
+}
+
 extern "C" int sdice_fisher_pairs_dev(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* d_incl,
                                       const int64_t* d_excl, double* d_p) {
-    SD_ARG(ctx, "ctx is NULL");
-    SD_ARG(n >= 0 && s >= 0, "negative size");
-    if (n == 0 || s < 2) return SDICE_OK;
-    SD_ARG(d_incl && d_excl && d_p, "NULL pointer");
-    SD_ARG(s <= 8192, "more than 8192 samples per junction is not supported");
-    return fisher_launch(ctx, n, s, d_incl, d_excl, (int64_t)s * (s - 1) / 2, nullptr, d_p);
+    return sd_pairs_dev({__func__, ctx, n, s, d_incl, d_excl, false, 0, nullptr, d_p, false, nullptr}, fisher_call);
 }
 
 extern "C" int sdice_fisher_pair_list_dev(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* d_incl, const int64_t* d_excl,
                                           int64_t m, const uint32_t* d_tab, double* d_p) {
-    SD_ARG(ctx, "ctx is NULL");
-    SD_ARG(n >= 0 && s >= 0 && m >= 0, "negative size");
-    SD_ARG(s <= 8192, "more than 8192 samples per junction is not supported");
-    SD_ARG(m <= SD_MAX_PAIRS, "more than 33550336 pairs in one list is not supported");
-    if (n == 0 || m == 0) return SDICE_OK;
-    SD_ARG(s >= 2, "a pair list needs at least two samples");
-    SD_ARG(d_incl && d_excl && d_tab && d_p, "NULL pointer");
-    return fisher_launch(ctx, n, s, d_incl, d_excl, m, d_tab, d_p);
+    return sd_pairs_dev({__func__, ctx, n, s, d_incl, d_excl, true, m, d_tab, d_p, false, nullptr}, fisher_call);
 }
 
 extern "C" int sdice_fisher_step_stats(sdice_ctx* ctx, uint64_t* useful, uint64_t* issued) {
@@ -622,52 +529,26 @@ extern "C" int sdice_fisher_step_stats(sdice_ctx* ctx, uint64_t* useful, uint64_
 
 extern "C" int sdice_fisher_pairs(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* incl, const int64_t* excl,
                                   double* p) {
-    SD_ARG(ctx, "ctx is NULL");
-    SD_ARG(n >= 0 && s >= 0, "negative size");
-    if (n == 0 || s < 2) return SDICE_OK;
-    SD_ARG(incl && excl && p, "NULL pointer");
-    SD_TRY(sd_check_pair_counts(__func__, n, s, incl, excl, true));
-    const int64_t n_pairs = (int64_t)s * (s - 1) / 2;
-    HostStaging st(ctx);
-    int32_t* di;
-    int64_t* de;
-    double* dp;
-    SD_TRY(st.upload(&di, incl, n * s));
-    SD_TRY(st.upload(&de, excl, n * s));
-    SD_TRY(st.alloc(&dp, n * n_pairs));
-    SD_TRY(sdice_fisher_pairs_dev(ctx, n, s, di, de, dp));
-    return st.download(p, dp, n * n_pairs);
+    return sd_pairs_host({__func__, ctx, n, s, incl, excl, false, 0, nullptr, p, false, nullptr}, fisher_call);
 }
 
 extern "C" int sdice_fisher_pair_list(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* incl, const int64_t* excl,
-                                      int64_t m, const int32_t* pairs, double* p) try {
-    SD_ARG(ctx, "ctx is NULL");
-    SD_ARG(n >= 0 && s >= 0 && m >= 0, "negative size");
-    SD_ARG(m == 0 || pairs, "NULL pointer");
-    SD_ARG(s <= 8192, "more than 8192 samples per junction is not supported");
-    SD_ARG(m <= SD_MAX_PAIRS, "more than 33550336 pairs in one list is not supported");
-    SD_TRY(sd_check_pair_list(__func__, s, m, pairs));
-    if (n == 0 || m == 0) return SDICE_OK;
-    SD_ARG(incl && excl && p, "NULL pointer");
-    SD_TRY(sd_check_pair_counts(__func__, n, s, incl, excl, true));
-    HostStaging st(ctx);
-    int32_t* di;
-    int64_t* de;
-    uint32_t* dt;
-    double* dp;
-    SD_TRY(st.upload(&di, incl, n * s));
-    SD_TRY(st.upload(&de, excl, n * s));
-    SD_TRY(st.alloc(&dt, m));
-    SD_TRY(sdice_pair_list_pack_dev(ctx, s, m, pairs, dt));
-    SD_TRY(st.alloc(&dp, n * m));
-    SD_TRY(sdice_fisher_pair_list_dev(ctx, n, s, di, de, m, dt, dp));
-    return st.download(p, dp, n * m);
-} catch (const std::exception& e) {
-    sdice_set_error("sdice_fisher_pair_list: %s", e.what());
-    return SDICE_ERR_NOMEM;
-} catch (...) {
-    sdice_set_error("sdice_fisher_pair_list: unknown exception");
-    return SDICE_ERR_STATE;
+                                      int64_t m, const int32_t* pairs, double* p) {
+    return sd_pairs_host({__func__, ctx, n, s, incl, excl, true, m, pairs, p, false, nullptr}, fisher_call);
+}
+
+// the pair table of a caller's list, as pair_table_kernel builds it for every pair
+extern "C" int sdice_pair_list_pack_dev(sdice_ctx* ctx, int32_t s, int64_t m, const int32_t* pairs, uint32_t* d_tab) {
+    const char* who = __func__;
+    return sd_no_throw(who, [&]() -> int {
+        SD_ARG_AS(who, ctx, "ctx is NULL");
+        SD_ARG_AS(who, s >= 0 && m >= 0, "negative size");
+        SD_TRY(sd_pair_limits(who, s, m));
+        if (m == 0) return SDICE_OK;
+        SD_ARG_AS(who, pairs && d_tab, "NULL pointer");
+        SD_TRY(sd_check_pair_list(who, s, m, pairs));
+        return sd_pair_tab_upload(ctx, m, pairs, d_tab);
+    });
 }
 
 extern "C" int sdice_fisher_tables(sdice_ctx* ctx, int64_t m, const int64_t* abcd, double* p) {
@@ -675,18 +556,7 @@ extern "C" int sdice_fisher_tables(sdice_ctx* ctx, int64_t m, const int64_t* abc
     SD_ARG(m >= 0, "negative size");
     if (m == 0) return SDICE_OK;
     SD_ARG(abcd && p, "NULL pointer");
-    for (int64_t i = 0; i < 4 * m; ++i) SD_ARG(abcd[i] >= 0, "table entries must be non-negative");
-    for (int64_t i = 0; i < m; ++i) {                                 // the count range of sd_check_pair_counts, per table
-        typedef unsigned __int128 u128;
-        const int64_t* t = abcd + 4 * i;
-        const bool fits = t[0] <= SD_MAX_COUNT && t[1] <= SD_MAX_COUNT && t[2] <= SD_MAX_COUNT && t[3] <= SD_MAX_COUNT &&
-                          (u128)t[0] + (u128)t[1] + (u128)t[2] + (u128)t[3] <= (u128)SD_MAX_COUNT;
-        if (!fits || (u128)t[0] * (u128)t[3] > (u128)SD_MAX_COUNT || (u128)t[1] * (u128)t[2] > (u128)SD_MAX_COUNT) {
-            sdice_set_error("%s: table %lld (%lld, %lld, %lld, %lld): the total, a*d and b*c must not exceed 2^53", __func__,
-                            (long long)i, (long long)t[0], (long long)t[1], (long long)t[2], (long long)t[3]);
-            return SDICE_ERR_ARG;
-        }
-    }
+    SD_TRY(sd_check_tables(__func__, m, abcd));
     SD_HIP(hipSetDevice(ctx->device));
     LfTable t;
     SD_TRY(get_lf_table(ctx, &t));

@@ -447,27 +447,40 @@ def pair_column_ranges(pairs, world):
 CHI2_ZERO_MSG = "The internally computed table of expected frequencies has a zero element"
 
 
-def _chi2_abort(comm, n_bad, n_tables):
+def pair_test_host(engine, test, incl, excl, pair_list=None):
+    """the chosen test of a host-array engine -> (p, n_bad); no list: exactly the calls of an all-pairs run"""
+    kw = {} if pair_list is None else dict(pairs=pair_list)
+    if test == "chi2":
+        return engine.chi2_pairs(incl, excl, **kw)
+    return engine.fisher_pairs(incl, excl, **kw), 0
+
+
+def pair_test_dev(engine, test, d_incl, d_excl, d_p, d_bad, d_tab=None):
+    """the chosen test of a device engine into d_p -> n_bad (chi2: one host round trip, d_bad its device word)"""
+    kw = {} if d_tab is None else dict(pairs=d_tab)
+    if test != "chi2":
+        engine.fisher_pairs_dev(d_incl, d_excl, d_p, **kw)
+        return 0
+    engine.chi2_pairs_dev(d_incl, d_excl, d_p, d_bad, **kw)
+    return int(d_bad.to_host()[0])
+
+
+def chi2_abort(comm, n_bad, n_tables):
     """scipy.stats.chi2_contingency raises on the first table with an empty row or column and the reference run dies
-    with it (pairwise_fisher.py:167-179): every rank takes the same decision from the global count"""
-    total = comm.allsum(n_bad)
+    with it (pairwise_fisher.py:167-179): every rank takes the same decision from the global count (comm None: one process)"""
+    total = n_bad if comm is None else comm.allsum(n_bad)
     if total:
         raise ValueError(f"{CHI2_ZERO_MSG} ({total} of {n_tables} sample-pair tables have an empty row or column)")
 
 
 def _pairwise_host(engine, comm, ext, rp, cl, a0, k, plan, n, pairs, correction, test="fisher", pair_list=None):
-    n_bad = 0
-    kw = {} if pair_list is None else dict(pairs=pair_list)        # (no list: exactly the calls of an all-pairs run)
     if k:
         excl = engine.ps(ext, rp, cl, want_excl=True, want_ps=False)
-        if test == "chi2":
-            p, n_bad = engine.chi2_pairs(ext[a0: a0 + k], excl[a0: a0 + k], **kw)
-        else:
-            p = engine.fisher_pairs(ext[a0: a0 + k], excl[a0: a0 + k], **kw)
+        p, n_bad = pair_test_host(engine, test, ext[a0: a0 + k], excl[a0: a0 + k], pair_list)
     else:
-        p = np.zeros((0, pairs), dtype=np.float64)
+        p, n_bad = np.zeros((0, pairs), dtype=np.float64), 0
     if test == "chi2":
-        _chi2_abort(comm, n_bad, n * pairs)
+        chi2_abort(comm, n_bad, n * pairs)
     rows_of = rows_per_rank(plan)
     maxk = longest(rows_of)
     if correction == "pairwise" and pairs > 0:
@@ -566,17 +579,12 @@ class PairwiseShard(_RowRange):
         every rank (the one host round trip of a step: the count of such tables)"""
         e, k, s, pairs, a0 = self.e, self.k, self.s, self.pairs, self.lo - self.elo
         n_bad = 0
-        kw = {} if self.d_tab is None else dict(pairs=self.d_tab)
         if k and pairs:
             e.ps_dev(self.d_counts, self.d_rp, self.lists(), self.d_excl, None)
             inc, exc = self.d_counts.offset(a0 * s, (k, s)), self.d_excl.offset(a0 * s, (k, s))
-            if self.test == "chi2":
-                e.chi2_pairs_dev(inc, exc, self.d_p.offset(0, (k, pairs)), self.d_bad, **kw)
-                n_bad = int(self.d_bad.to_host()[0])
-            else:
-                e.fisher_pairs_dev(inc, exc, self.d_p.offset(0, (k, pairs)), **kw)
+            n_bad = pair_test_dev(e, self.test, inc, exc, self.d_p.offset(0, (k, pairs)), self.d_bad, self.d_tab)
         if self.test == "chi2":
-            _chi2_abort(self.comm, n_bad, self.n * pairs)
+            chi2_abort(self.comm, n_bad, self.n * pairs)
 
     def _copy_my_rows(self, blocks, G, pack):
         """my rows of every rank's columns, d_p -> blocks (pack) or blocks -> d_p; `blocks` is laid out

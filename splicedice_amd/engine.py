@@ -452,36 +452,30 @@ class Context:
         check(self.lib.sdice_sample_gram(self.h, n, s, _ptr(ps), _ptr(cols), m, *map(_ptr, out.values())), "sdice_sample_gram")
         return out
 
+    def _pair_test(self, test, dev, incl, excl, pairs, p, *bad):
+        """the C call behind the four pair methods: sdice_<test>_pair_list over a list, else sdice_<test>_pairs; dev: the _dev
+        forms on DeviceArrays (pairs: a pair_table()), else p is allocated here; bad: chi2's n_bad argument.  -> p"""
+        if not dev:
+            incl, excl = _c(incl, np.int32), _c(excl, np.int64)
+            pairs = None if pairs is None else pair_array(pairs)
+            s = incl.shape[1]
+            p = np.empty((incl.shape[0], s * (s - 1) // 2 if pairs is None else len(pairs)), dtype=np.float64)
+        ptr = (lambda a: a.ptr) if dev else _ptr
+        sym = "sdice_%s_%s%s" % (test, "pairs" if pairs is None else "pair_list", "_dev" if dev else "")
+        lst = () if pairs is None else (pairs.shape[0], ptr(pairs))
+        check(getattr(self.lib, sym)(self.h, *incl.shape, ptr(incl), ptr(excl), *lst, ptr(p), *bad), sym)
+        return p
+
     def fisher_pairs(self, incl, excl, pairs=None):
         """pairwise_fisher.py:164-179 -> p float64[n, s(s-1)/2]; pairs = [m, 2] column indices: p float64[n, m], column q
         the table [[incl_i, incl_j], [excl_i, excl_j]] of pair q = (i, j) -- any order, i > j and repeats allowed"""
-        incl, excl = _c(incl, np.int32), _c(excl, np.int64)
-        n, s = incl.shape
-        if pairs is not None:
-            pairs = pair_array(pairs)
-            p = np.empty((n, len(pairs)), dtype=np.float64)
-            check(self.lib.sdice_fisher_pair_list(self.h, n, s, _ptr(incl), _ptr(excl), len(pairs), _ptr(pairs), _ptr(p)),
-                  "sdice_fisher_pair_list")
-            return p
-        p = np.empty((n, s * (s - 1) // 2), dtype=np.float64)
-        check(self.lib.sdice_fisher_pairs(self.h, n, s, _ptr(incl), _ptr(excl), _ptr(p)), "sdice_fisher_pairs")
-        return p
+        return self._pair_test("fisher", False, incl, excl, pairs, None)
 
     def chi2_pairs(self, incl, excl, pairs=None):
         """pairwise --chi2 (scipy chi2_contingency per pair) -> (p float64[n, s(s-1)/2], n_bad); pairs as in fisher_pairs:
         (p float64[n, m], n_bad among the listed tables)"""
-        incl, excl = _c(incl, np.int32), _c(excl, np.int64)
-        n, s = incl.shape
         bad = C.c_int64()
-        if pairs is not None:
-            pairs = pair_array(pairs)
-            p = np.empty((n, len(pairs)), dtype=np.float64)
-            check(self.lib.sdice_chi2_pair_list(self.h, n, s, _ptr(incl), _ptr(excl), len(pairs), _ptr(pairs), _ptr(p),
-                                                C.byref(bad)), "sdice_chi2_pair_list")
-            return p, bad.value
-        p = np.empty((n, s * (s - 1) // 2), dtype=np.float64)
-        check(self.lib.sdice_chi2_pairs(self.h, n, s, _ptr(incl), _ptr(excl), _ptr(p), C.byref(bad)), "sdice_chi2_pairs")
-        return p, bad.value
+        return self._pair_test("chi2", False, incl, excl, pairs, None, C.byref(bad)), bad.value
 
     def fisher_tables(self, abcd):
         abcd = _c(abcd, np.int64).reshape(-1, 4)
@@ -632,12 +626,7 @@ class Context:
 
     def fisher_pairs_dev(self, d_incl, d_excl, d_p, pairs=None):
         """pairs: None (every pair) or the device table pair_table() made for these s samples; d_p is [n, m] then"""
-        n, s = d_incl.shape
-        if pairs is not None:
-            check(self.lib.sdice_fisher_pair_list_dev(self.h, n, s, d_incl.ptr, d_excl.ptr, pairs.shape[0], pairs.ptr, d_p.ptr),
-                  "sdice_fisher_pair_list_dev")
-            return
-        check(self.lib.sdice_fisher_pairs_dev(self.h, n, s, d_incl.ptr, d_excl.ptr, d_p.ptr), "sdice_fisher_pairs_dev")
+        self._pair_test("fisher", True, d_incl, d_excl, pairs, d_p)
 
     def fisher_step_stats(self):
         """(useful, issued) lane-steps of the last Fisher launch made with fisher.count_steps = 1"""
@@ -646,12 +635,7 @@ class Context:
         return int(u.value), int(t.value)
 
     def chi2_pairs_dev(self, d_incl, d_excl, d_p, d_n_bad, pairs=None):
-        n, s = d_incl.shape
-        if pairs is not None:
-            check(self.lib.sdice_chi2_pair_list_dev(self.h, n, s, d_incl.ptr, d_excl.ptr, pairs.shape[0], pairs.ptr, d_p.ptr,
-                                                    d_n_bad.ptr), "sdice_chi2_pair_list_dev")
-            return
-        check(self.lib.sdice_chi2_pairs_dev(self.h, n, s, d_incl.ptr, d_excl.ptr, d_p.ptr, d_n_bad.ptr), "sdice_chi2_pairs_dev")
+        self._pair_test("chi2", True, d_incl, d_excl, pairs, d_p, d_n_bad.ptr)
 
     def bh_columns_dev(self, d_p):
         n, cols = d_p.shape

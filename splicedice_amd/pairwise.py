@@ -15,7 +15,7 @@ import numpy as np
 
 from . import textio
 from ._cli import engine_scope
-from .distributed import CHI2_ZERO_MSG
+from .distributed import chi2_abort, pair_test_dev, pair_test_host
 from .engine import Context
 
 
@@ -133,7 +133,6 @@ def device_pipeline(ctx, counts, row_ptr, col, chi2, correction, events, header,
     n, s = counts.shape
     pairs = s * (s - 1) // 2 if pair_list is None else len(pair_list)
     d_tab = None if pair_list is None else ctx.pair_table(s, pair_list)
-    kw = {} if d_tab is None else dict(pairs=d_tab)
     with _stages.stage("h2d"):
         d_counts = ctx.to_device(counts, np.int32)
         d_rp = ctx.to_device(row_ptr, np.int64)
@@ -146,16 +145,9 @@ def device_pipeline(ctx, counts, row_ptr, col, chi2, correction, events, header,
     else:
         d_excl = ctx.to_device(excl, np.int64)            # (fractional table: truncated float sums, fractional_tables)
     d_p = ctx.empty((n, pairs), np.float64)
-    if chi2:
-        d_bad = ctx.empty(1, np.int64)
-        ctx.chi2_pairs_dev(d_counts, d_excl, d_p, d_bad, **kw)
-        n_bad = int(d_bad.to_host()[0])
-        if n_bad:
-            # scipy.stats.chi2_contingency raises on the first such table and the reference
-            # run dies with it (pairwise_fisher.py:167-179)
-            raise ValueError(f"{CHI2_ZERO_MSG} ({n_bad} of {n * pairs} sample-pair tables have an empty row or column)")
-    else:
-        ctx.fisher_pairs_dev(d_counts, d_excl, d_p, **kw)
+    d_bad = ctx.empty(1, np.int64) if chi2 else None
+    n_bad = pair_test_dev(ctx, "chi2" if chi2 else "fisher", d_counts, d_excl, d_p, d_bad, d_tab)
+    chi2_abort(None, n_bad, n * pairs)
     for a in (d_counts, d_rp, d_col, d_excl) + (() if d_tab is None else (d_tab,)):
         a.free()
     if correction == "all":
@@ -244,6 +236,13 @@ def run_with(args, ctx=None):
         print(f"[{n} / {totaln}] events analyzed...")
 
     header = "clusterID\t" + "\t".join(columns) + "\n"
+
+    def corrected(engine, parray):
+        """the Benjamini-Hochberg scope of the command line on a host-array engine"""
+        if args.multiple_test_correction == "all":
+            return engine.bh(parray.ravel()).reshape(parray.shape)
+        return engine.bh_columns(parray) if args.multiple_test_correction == "pairwise" else parray
+
     with engine_scope(ctx, lambda: Context(L.local_rank)) as ctx:
         fractional = counts.dtype != np.int32
         if fractional and args.chi2:
@@ -258,11 +257,7 @@ def run_with(args, ctx=None):
                     device_pipeline(ctx, incl, row_ptr, col, False, args.multiple_test_correction, events, header, args.output, excl,
                                     pair_list=kw.get("pairs"))
                 else:
-                    parray = ctx.fisher_pairs(incl, excl, **kw)
-                    if args.multiple_test_correction == "all":
-                        parray = ctx.bh(parray.ravel()).reshape(parray.shape)
-                    elif args.multiple_test_correction == "pairwise":
-                        parray = ctx.bh_columns(parray)
+                    parray = corrected(ctx, ctx.fisher_pairs(incl, excl, **kw))
                     textio.write_table(args.output, header, events, np.asarray(parray, dtype=np.float64), "repr")
             return
         if L.world > 1 and totaln and pairs:
@@ -287,18 +282,9 @@ def run_with(args, ctx=None):
         # host-array engine (the CPU test double) and empty inputs
         if totaln and pairs:
             excl = ctx.ps(counts, row_ptr, col, want_excl=True, want_ps=False)
-            if args.chi2:
-                parray, n_bad = ctx.chi2_pairs(counts, excl, **kw)
-                if n_bad:
-                    # scipy.stats.chi2_contingency raises on the first such table and the reference
-                    # run dies with it (pairwise_fisher.py:167-179)
-                    raise ValueError(f"{CHI2_ZERO_MSG} ({n_bad} of {parray.size} sample-pair tables have an empty row or column)")
-            else:
-                parray = ctx.fisher_pairs(counts, excl, **kw)
-            if args.multiple_test_correction == "all":
-                parray = ctx.bh(parray.ravel()).reshape(parray.shape)
-            elif args.multiple_test_correction == "pairwise":
-                parray = ctx.bh_columns(parray)
+            parray, n_bad = pair_test_host(ctx, "chi2" if args.chi2 else "fisher", counts, excl, kw.get("pairs"))
+            chi2_abort(None, n_bad, parray.size)
+            parray = corrected(ctx, parray)
         else:
             parray = np.zeros((totaln, len(pairs)))
     # str(numpy.float64) per cell (pairwise_fisher.py:195-200) through the library's formatter

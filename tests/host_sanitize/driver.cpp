@@ -2,8 +2,9 @@
 // built by `make -C splicedice_amd/csrc asan` / `tsan` together with those two files (no HIP, no GPU)
 // and run by tests/test_host_sanitizers.py.  It pushes every host entry point through its threaded
 // path: table writer (3 modes) -> table reader round trip, column writer, cluster writer, junction
-// parser on the golden inputs (all file types) and the row lookup.  Any ASan / UBSan / TSan report
-// makes the process exit non-zero.
+// parser on the golden inputs (all file types) and the row lookup; then the argument checks of the pair
+// tests (csrc/paircheck.cpp) on both sides of their bounds.  Any ASan / UBSan / TSan report makes the
+// process exit non-zero.
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -14,6 +15,7 @@
 #include <thread>
 #include <vector>
 #include "sdice.h"
+#include "paircheck.h"      // splicedice_amd/csrc: the argument checks of the pair tests
 
 static char g_err[1024];
 void sdice_set_error(const char* fmt, ...) {
@@ -132,6 +134,62 @@ int main(int argc, char** argv) {
         CHECK(need == noff[nr] && std::string(nm.data() + noff[1], (size_t)(noff[2] - noff[1])) == "chrA:10-17:-");
         CHECK(sdice_junction_names(nr, cnames, coff, 4, rc.data(), rl.data(), rr.data(), strand.data(), nm.data(), 10, noff.data(), &need) != 0);
         CHECK(sdice_host_threads() >= 1 && sdice_textio_trim() == 0);
+    }
+    {   // the argument checks of the pair tests (csrc/paircheck.cpp) on both sides of every bound; a refusal names its cause
+        const int64_t T = (int64_t)1 << 53, big = INT64_MAX;
+        #define REFUSED(call, word) CHECK((call) == SDICE_ERR_ARG && strstr(g_err, word))
+        for (bool walk : {false, true}) {
+            // the two largest totals add up to 2^53 (accepted) and to 2^53 + 1
+            int32_t i3[3] = {1, 1, 0}; int64_t e3[3] = {(T >> 1) - 1, (T >> 1) - 1, 5};
+            CHECK(sd_check_pair_counts("t", 1, 3, i3, e3, walk) == SDICE_OK);
+            e3[1] += 1;
+            REFUSED(sd_check_pair_counts("t", 1, 3, i3, e3, walk), "add up to");
+            // sample 0 holds the largest inclusion count AND the largest exclusion sum: the products to judge are
+            // 2^20 * 2^33 (its count, the second sum) and 2^13 * 2^40 = 2^53 -- and never 2^20 * 2^40
+            int32_t i2[3] = {1 << 20, 1 << 13, 2}; int64_t e2[3] = {(int64_t)1 << 40, (int64_t)1 << 33, 7};
+            CHECK(sd_check_pair_counts("t", 1, 3, i2, e2, walk) == SDICE_OK);
+            e2[1] += 1;                                               // 2^20 * (2^33 + 1) is above 2^53
+            if (walk) REFUSED(sd_check_pair_counts("t", 1, 3, i2, e2, true), "times another");
+            else CHECK(sd_check_pair_counts("t", 1, 3, i2, e2, false) == SDICE_OK);
+            int32_t i1[2] = {1, 1}; int64_t e1[2] = {big, big};       // no signed overflow on the way to the refusal
+            REFUSED(sd_check_pair_counts("t", 1, 2, i1, e1, walk), "exclusion sum");
+            e1[0] = 4; e1[1] = -1;
+            REFUSED(sd_check_pair_counts("t", 1, 2, i1, e1, walk), "non-negative");
+            i1[0] = -1; e1[1] = 4;
+            REFUSED(sd_check_pair_counts("t", 1, 2, i1, e1, walk), "non-negative");
+            CHECK(sd_check_pair_counts("t", 0, 2, nullptr, nullptr, walk) == SDICE_OK);      // n = 0: nothing is read
+            int64_t e0[1] = {T - 1};
+            CHECK(sd_check_pair_counts("t", 1, 1, i1 + 1, e0, walk) == SDICE_OK);            // s = 1: one sample, no pair
+        }
+        // two rows: the second one is judged on its own maxima
+        int32_t ir[4] = {1 << 30, 0, 1, 1}; int64_t er[4] = {0, 1 << 20, T - 2, 0};
+        CHECK(sd_check_pair_counts("t", 2, 2, ir, er, true) == SDICE_OK);
+        const int32_t self[4] = {0, 1, 2, 2}, past[4] = {0, 1, 5, 2}, neg[4] = {0, 1, -1, 2};
+        CHECK(sd_check_pair_list("t", 5, 1, self) == SDICE_OK);
+        REFUSED(sd_check_pair_list("t", 5, 2, self), "with itself");
+        REFUSED(sd_check_pair_list("t", 5, 2, past), "must lie in");
+        REFUSED(sd_check_pair_list("t", 5, 2, neg), "must lie in");
+        CHECK(sd_check_pair_list("t", 5, 0, nullptr) == SDICE_OK);
+        int64_t tab[8] = {1, 5, 7, 3, (int64_t)1 << 26, 0, 0, (int64_t)1 << 27};            // the second: a d = 2^53
+        CHECK(sd_check_tables("t", 2, tab) == SDICE_OK);
+        tab[4] = 3; tab[7] = 3002399751580331;                                               // a d = 2^53 + 1
+        REFUSED(sd_check_tables("t", 2, tab), "table 1");
+        tab[7] = (int64_t)1 << 27; tab[4] = 0; tab[5] = ((int64_t)1 << 26) + 1; tab[6] = (int64_t)1 << 27;  // b c = 2^53 + 2^27
+        REFUSED(sd_check_tables("t", 2, tab), "table 1");
+        tab[5] = T; tab[6] = 0; tab[7] = 1;                                                  // total 2^53 + 1
+        REFUSED(sd_check_tables("t", 2, tab), "table 1");
+        tab[5] = big; tab[7] = big;                                                          // (no overflow in the total)
+        REFUSED(sd_check_tables("t", 2, tab), "table 1");
+        tab[2] = -7;
+        REFUSED(sd_check_tables("t", 2, tab), "non-negative");
+        CHECK(sd_check_tables("t", 0, nullptr) == SDICE_OK);
+        const int32_t ends[4] = {8191, 0, 0, 8191};
+        std::vector<uint32_t> packed;
+        sd_pack_pair_list(2, ends, packed);
+        CHECK(packed.size() == 2 && packed[0] == 0x1fff0000u && packed[1] == 0x00001fffu);
+        sd_pack_pair_list(0, nullptr, packed);
+        CHECK(packed.empty());
+        #undef REFUSED
     }
     printf("host sanitizer driver: ok\n");
     return 0;
