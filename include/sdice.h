@@ -301,6 +301,40 @@ int sdice_ranksum_strata_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* 
                              uint8_t* d_tested, double* d_p, double* d_z, float* d_med1, float* d_med2,
                              float* d_mean1, float* d_mean2, float* d_delta);
 
+/* ---- compare_sample_sets --ks: the two-sample Kolmogorov-Smirnov test per row (not in the reference): any difference
+ *      between the two empirical distributions, not a shift alone.
+ *  Row rules are sdice_ranksum's: ps[n,s] float32, NaN = no value; NaNs are dropped per group, n1' and n2' kept; the row
+ *  is tested when n1' >= 3 and n2' >= 3, otherwise every output slot is 0.  Any float32 value is legal: signed zeros
+ *  (-0.0 == +0.0 is one value), subnormals (distinct values), values outside [0, 1], +-inf (ordinary values at the ends of
+ *  the order).  1 <= n1, n2 <= 4096, a column at most once over both lists; otherwise SDICE_ERR_ARG before any launch,
+ *  outputs untouched, the reason in sdice_last_error (the host call checks the index range and the one-appearance rule,
+ *  the _dev call n1, n2 and n1 + n2 <= s).
+ *  Per tested row, with c1(v) = #{x in group 1 : x <= v} and c2(v) likewise, by float32 comparison:
+ *      M    = max over the distinct kept values v of |c1(v) n2' - c2(v) n1'|        (an integer, at most 2^24)
+ *      D    = M / (n1' n2')                          one float64 division: bit for bit float(Fraction(M, n1' n2'))
+ *      lam2 = M^2 / (n1' n2' (n1' + n2'))            both integers exact in float64, one division
+ *      p    = min(1, 2 sum_{k>=1} (-1)^(k-1) exp(-2 k^2 lam2))         = scipy.special.kolmogorov(sqrt(lam2))
+ *  The empirical distribution functions are compared at the END of a tie run only, never inside one.  p is Kolmogorov's
+ *  limiting distribution: no Stephens or continuity correction, no finite-n form (scipy's kstwo / method="auto" differ).
+ *  M = 0 (all kept values equal, or identical samples) gives D = 0, p = 1.  p is as accurate as sdice_ranksum's: within
+ *  1e-9 relative down to 1e-280, 0 past the float64 range.
+ *  want_exact != 0: a tested row with N = n1' + n2' <= 32 (C(32, 16) fits 32 bits) gets the exact conditional
+ *  (permutation) p given the row's ties and exact[row] = 1.  With T the tie-run ends of the merged order as cumulative
+ *  counts t, inside = the number of lattice paths (0,0) -> (n1', n2') with |i n2' - (t - i) n1'| < M at every t in T (i =
+ *  group-1 values among the first t), p = (C(N, n1') - inside) / C(N, n1'), both integers, one float64 division.  What
+ *  R >= 4.2 ks.test(exact = TRUE) computes with ties and scipy.stats.ks_2samp(method="exact") on untied rows.  Rows
+ *  with N > 32 keep the asymptotic p and exact[row] = 0; so does every row when want_exact == 0.
+ *  med1 / med2 / mean1 / mean2 / delta: bit for bit sdice_ranksum's on every tested row.  Swapping the groups gives the
+ *  same D and p.  d optional (NULL to skip); exact is required when want_exact != 0 and may be NULL otherwise. */
+int sdice_ks(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps,
+             const int32_t* g1, int32_t n1, const int32_t* g2, int32_t n2, int32_t want_exact,
+             uint8_t* tested, double* p, double* d, float* med1, float* med2,
+             float* mean1, float* mean2, float* delta, uint8_t* exact);
+int sdice_ks_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps,
+                 const int32_t* d_g1, int32_t n1, const int32_t* d_g2, int32_t n2, int32_t want_exact,
+                 uint8_t* d_tested, double* d_p, double* d_d, float* d_med1, float* d_med2,
+                 float* d_mean1, float* d_mean2, float* d_delta, uint8_t* d_exact);
+
 /* ---- correlate: Spearman rank correlation of the PS values of m listed columns with one covariate value per listed
  *      column, per row scipy.stats.spearmanr(x_kept, ps_kept) under the row rules above (not in the reference).
  *  The covariate does not cross the ABI.  cols[m]: the columns sorted by covariate value, ties in table order; xg[m]: the

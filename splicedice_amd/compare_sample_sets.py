@@ -28,6 +28,12 @@ the order given -- and the test becomes the Jonckheere-Terpstra trend test (sdic
 along the order, two-sided asymptotic p.  The columns are the -mx ones with `z` where `H` stood; not with --paired, --exact
 or --strata.
 
+A sixth: `--ks` replaces the rank-sum test by the two-sample Kolmogorov-Smirnov test (sdice_ks), which answers to any
+difference between the two distributions -- a junction switched on in part of a set, a bimodal set with the other's median
+-- where the rank-sum statistic and `delta` stay near 0.  The columns gain `D` (the KS statistic) before `p-value`; with
+`--exact` the rows that keep at most 32 values get the exact conditional p-value.  Not with --paired, -mx, --strata or
+--trend.
+
 On the GPU: the per-row loop :216-232 (NaN drop, <3 skip, scipy ranksums, medians, means)
 -> sdice_ranksum; multipletests(..., "fdr_bh") :235 -> sdice_bh over the tested rows.
 The GTF annotation columns are host string work, as in the reference.
@@ -38,12 +44,14 @@ import numpy as np
 
 from . import _cli
 from ._cli import annotation_suffixes, read_annotation, read_ps_table, samples_from_manifest, table_header_names  # noqa: F401
-from .engine import JONCKHEERE_FIELDS, KRUSKAL_FIELDS, RANKSUM_EXACT_FIELDS, RANKSUM_FIELDS, Context, field_shapes
+from .engine import (JONCKHEERE_FIELDS, KRUSKAL_FIELDS, KS_FIELDS, RANKSUM_EXACT_FIELDS, RANKSUM_FIELDS, Context,
+                     field_shapes)
 
 refuse = _cli.refusal("compare_sample_sets --paired")
 refuse_exact = _cli.refusal("compare_sample_sets --exact")
 refuse_strata = _cli.refusal("compare_sample_sets --strata")
 refuse_trend = _cli.refusal("compare_sample_sets --trend")
+refuse_ks = _cli.refusal("compare_sample_sets --ks")
 MAX_STRATA = 64                     # strata a call accepts (include/sdice.h)
 
 
@@ -92,6 +100,20 @@ def compare_strata(matrix, g1_idx, g2_idx, strat1, strat2, n_strata, ctx):
                                       s1=(strat1, np.int32), s2=(strat2, np.int32)),
                             field_shapes(RANKSUM_FIELDS, matrix.shape[0]),
                             lambda d, out: ctx.ranksum_strata_dev(d["ps"], d["g1"], d["g2"], d["s1"], d["s2"], n_strata, out))
+
+
+def compare_ks(matrix, g1_idx, g2_idx, ctx, exact=False):
+    """compare_dev() for --ks: table and column lists up, the Kolmogorov-Smirnov test + BH over the tested rows on
+    resident vectors, per-row results down (the `exact` marks stay behind)"""
+    if not matrix.shape[0]:
+        res = ctx.ks(matrix, g1_idx, g2_idx, exact)
+        out = {k: res[k][:0] for k in ("p", "d", "med1", "med2", "mean1", "mean2", "delta")}
+        return np.zeros(0, np.int64), {**out, "corrected": np.zeros(0)}
+    keep, r = _cli.tested_rows(ctx, dict(ps=(matrix, np.float32), g1=(g1_idx, np.int32), g2=(g2_idx, np.int32)),
+                               field_shapes(KS_FIELDS, matrix.shape[0]),
+                               lambda d, out: ctx.ks_dev(d["ps"], d["g1"], d["g2"], out, exact))
+    r.pop("exact", None)
+    return keep, r
 
 
 def compare_sets_dev(matrix, set_idx, ctx, trend=False):
@@ -162,6 +184,14 @@ def add_parser(parser):
                              "carries H.  The two-sided p-value is asymptotic only (normal approximation with the "
                              "tie-corrected variance, no exact form).  Not with --paired, --exact or --strata (not part of "
                              "the reference)")
+    parser.add_argument("--ks", action="store_true",
+                        help="The two-sample Kolmogorov-Smirnov test instead of the rank-sum test: it answers to any "
+                             "difference between the two distributions (a junction switched on in part of a set, a "
+                             "bimodal set), not to a shift alone.  The table gains the column D (the KS statistic, 0..1) "
+                             "before p-value.  The p-value is Kolmogorov's limiting distribution "
+                             "(scipy.special.kolmogorov, no finite-n correction); with --exact the rows that keep at "
+                             "most 32 values get the exact conditional p-value given their ties (R's ks.test(exact = "
+                             "TRUE)).  Not with --paired, -mx, --strata or --trend (not part of the reference)")
     parser.add_argument("-a", "--annotation", type=str, required=False, default="",
                         help="Optional GTF file to label known splice junctions and genes")
     parser.add_argument("-o", "--outputFile", type=str, required=True,
@@ -177,6 +207,10 @@ STRATA_MULTI_RANK_REFUSAL = ("compare_sample_sets: --strata is not available und
 
 TREND_MULTI_RANK_REFUSAL = ("compare_sample_sets: --trend is not available under the multi-rank launcher "
                             "(the packed all-gather carries the two-set fields only); run it in one process.")
+
+
+KS_MULTI_RANK_REFUSAL = ("compare_sample_sets: --ks is not available under the multi-rank launcher "
+                         "(the packed all-gather carries the rank-sum fields only); run it in one process.")
 
 
 def strata_columns(g1, g2, header_names, labels):
@@ -228,6 +262,16 @@ def run_with(args, ctx=None):
     paired = bool(getattr(args, "paired", False))
     exact = bool(getattr(args, "exact", False))
     trend = bool(getattr(args, "trend", False))
+    ks = bool(getattr(args, "ks", False))
+    if ks:
+        for on, flag in ((paired, "--paired (the signed-rank test compares matched samples; this test compares two "
+                                  "distributions)"),
+                         (trend, "--trend (the trend test orders three or more sets)"),
+                         (more, "-mx/--moreManifests (there is no k-sample Kolmogorov-Smirnov test here)"),
+                         (getattr(args, "strata", None), "--strata (there is no stratified Kolmogorov-Smirnov test here)")):
+            if on:
+                refuse_ks(f"cannot be combined with {flag}")
+        _cli.refuse_multi_rank(L, KS_MULTI_RANK_REFUSAL)
     if trend:
         if not more:
             refuse_trend("needs -mx/--moreManifests (three or more ordered sets; two sets are the rank-sum test)")
@@ -262,6 +306,8 @@ def run_with(args, ctx=None):
     with _cli.engine_scope(ctx, lambda: Context(L.local_rank)) as ctx:
         if strata:
             keep, r = compare_strata(matrix, *strat, ctx)
+        elif ks:
+            keep, r = compare_ks(matrix, column_indices(g1, cols), column_indices(g2, cols), ctx, exact)
         elif more:
             # k >= 3 sets: Kruskal-Wallis per junction; columns event mean1..meank median1..mediank delta H p-value corrected
             # (--trend: Jonckheere-Terpstra over the sets in this order, z where H stands)
@@ -281,6 +327,9 @@ def run_with(args, ctx=None):
         header = "\t".join(["event"] + [f"mean{i + 1}" for i in range(k)] + [f"median{i + 1}" for i in range(k)] +
                            ["delta", "z" if trend else "H", "p-value", "corrected"])
         columns = [*r["mean"], *r["med"], r["delta"], r["z" if trend else "h"], r["p"], r["corrected"]]
+    elif ks:
+        header = "event\tmean1\tmean2\tmedian1\tmedian2\tdelta\tD\tp-value\tcorrected"
+        columns = [r["mean1"], r["mean2"], r["med1"], r["med2"], r["delta"], r["d"], r["p"], r["corrected"]]
     else:
         header = "event\tmean1\tmean2\tmedian1\tmedian2\tdelta\tp-value\tcorrected"
         columns = [r["mean1"], r["mean2"], r["med1"], r["med2"], r["delta"], r["p"], r["corrected"]]

@@ -22,6 +22,9 @@
 //   strata.hip (K17)      PsKey, f32_ord, LaneGroup, group_add / group_sum / group_sort / group_median, block_compact,
 //                         block_pairwise_sum, block_bitonic, run_bounds, median_of_ord, store_two_sample, the launch sizes;
 //                         TwoSampleOut, zero_two_sample, TwoSampleStaging
+//   ks.hip (K19)          PsKey, f32_ord, LaneGroup, group_sum / group_sort / group_median, block_compact,
+//                         block_pairwise_sum, block_bitonic, median_of_ord, store_two_sample, the launch sizes;
+//                         TwoSampleOut (D in the z slot), zero_two_sample, TwoSampleStaging (with `exact`)
 // Every helper is inlined into the kernels that call it and the kernels themselves stay in their .hip files, so a change
 // to a helper here is a change to each kernel that uses it -- ranksum.hip's pairq and count kernels among them, whose
 // committed counter pass is stamped with the hash of ranksum.hip alone and will not notice.

@@ -22,6 +22,8 @@ PER_SET = "per set"
 RANKSUM_FIELDS = [("tested", np.uint8), ("p", np.float64), ("z", np.float64), ("med1", np.float32), ("med2", np.float32),
                   ("mean1", np.float32), ("mean2", np.float32), ("delta", np.float32)]       # (ranksum and signedrank)
 RANKSUM_EXACT_FIELDS = RANKSUM_FIELDS + [("exact", np.uint8)]                                # (the two --exact calls)
+KS_FIELDS = [("tested", np.uint8), ("p", np.float64), ("d", np.float64), ("med1", np.float32), ("med2", np.float32),
+             ("mean1", np.float32), ("mean2", np.float32), ("delta", np.float32), ("exact", np.uint8)]
 KRUSKAL_FIELDS = [("tested", np.uint8), ("p", np.float64), ("h", np.float64), ("med", np.float32, PER_SET),
                   ("mean", np.float32, PER_SET), ("delta", np.float32)]
 JONCKHEERE_FIELDS = [("tested", np.uint8), ("p", np.float64), ("z", np.float64), ("j", np.float64),
@@ -382,6 +384,18 @@ class Context:
                                             _ptr(strat2), n_strata, *map(_ptr, out.values())), "sdice_ranksum_strata")
         return out
 
+    def ks(self, ps, g1, g2, exact=False):
+        """the two-sample Kolmogorov-Smirnov test per row (include/sdice.h): un-compacted tested, p, d (the statistic D),
+        the medians, means and delta of ranksum(), and exact (1 where p is the exact conditional value: with exact=True,
+        on the tested rows that keep at most 32 values; all 0 otherwise)."""
+        ps = _c(ps, np.float32)
+        n, s = ps.shape
+        g1, g2 = _c(g1, np.int32).reshape(-1), _c(g2, np.int32).reshape(-1)
+        out = _zeros(KS_FIELDS, n)
+        check(self.lib.sdice_ks(self.h, n, s, _ptr(ps), _ptr(g1), g1.size, _ptr(g2), g2.size, int(bool(exact)),
+                                *map(_ptr, out.values())), "sdice_ks")
+        return out
+
     def kruskal(self, ps, sets):
         """scipy.stats.kruskal per row across the k column sets under the row rules of ranksum(); un-compacted outputs:
         tested, p, h [n], med, mean [k, n] (set-major), delta [n] = largest minus smallest set median."""
@@ -566,6 +580,15 @@ class Context:
         check(self.lib.sdice_ranksum_strata_dev(self.h, n, s, d_ps.ptr, d_g1.ptr, d_g1.shape[0], d_g2.ptr, d_g2.shape[0],
                                                 d_strat1.ptr, d_strat2.ptr, int(n_strata),
                                                 *_dev_ptrs(RANKSUM_FIELDS, out, "z")), "sdice_ranksum_strata_dev")
+
+    def ks_dev(self, d_ps, d_g1, d_g2, out, exact=False):
+        """out: the device fields of KS_FIELDS (d optional; exact optional unless exact=True)"""
+        n, s = d_ps.shape
+        ptrs = [out[f[0]].ptr if out.get(f[0]) else None for f in KS_FIELDS]
+        if any(p is None for f, p in zip(KS_FIELDS, ptrs) if f[0] not in ("d", "exact")):
+            raise ValueError("ks_dev: every field of KS_FIELDS but d and exact is required")
+        check(self.lib.sdice_ks_dev(self.h, n, s, d_ps.ptr, d_g1.ptr, d_g1.shape[0], d_g2.ptr, d_g2.shape[0],
+                                    int(bool(exact)), *ptrs), "sdice_ks_dev")
 
     def signedrank_dev(self, d_ps, d_a, d_b, out):
         n, s = d_ps.shape
