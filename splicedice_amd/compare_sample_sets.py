@@ -38,7 +38,9 @@ On the GPU: the per-row loop :216-232 (NaN drop, <3 skip, scipy ranksums, median
 -> sdice_ranksum; multipletests(..., "fdr_bh") :235 -> sdice_bh over the tested rows.
 The GTF annotation columns are host string work, as in the reference.
 """
+import argparse
 import sys
+import typing
 
 import numpy as np
 
@@ -47,11 +49,6 @@ from ._cli import annotation_suffixes, read_annotation, read_ps_table, samples_f
 from .engine import (JONCKHEERE_FIELDS, KRUSKAL_FIELDS, KS_FIELDS, RANKSUM_EXACT_FIELDS, RANKSUM_FIELDS, Context,
                      field_shapes)
 
-refuse = _cli.refusal("compare_sample_sets --paired")
-refuse_exact = _cli.refusal("compare_sample_sets --exact")
-refuse_strata = _cli.refusal("compare_sample_sets --strata")
-refuse_trend = _cli.refusal("compare_sample_sets --trend")
-refuse_ks = _cli.refusal("compare_sample_sets --ks")
 MAX_STRATA = 64                     # strata a call accepts (include/sdice.h)
 
 
@@ -65,68 +62,35 @@ def column_indices(group, cols):
     return np.nonzero(np.isin(cols, group))[0].astype(np.int32)
 
 
-def compare_dev(matrix, g1_idx, g2_idx, ctx, paired=False, exact=False):
-    """compare() on the HIP engine stage by stage: table up, rank-sum (paired: signed-rank) + BH over the tested rows on
-    resident vectors, per-row results down (sdice_ranksum + sdice_bh do the same steps inside two host calls).  exact:
-    the _exact calls; BH runs over the mixed p vector and the `exact` marks stay behind."""
-    test = row_test(ctx, paired, exact, dev=True)
-    keep, r = _cli.tested_rows(ctx, dict(ps=(matrix, np.float32), g1=(g1_idx, np.int32), g2=(g2_idx, np.int32)),
-                               field_shapes(RANKSUM_EXACT_FIELDS if exact else RANKSUM_FIELDS, matrix.shape[0]),
-                               lambda d, out: test(d["ps"], d["g1"], d["g2"], out))
+def tested(ctx, matrix, fields, inputs, dev, host=None, k=None):
+    """The pipeline of every test on the HIP engine, stage by stage: table and `inputs` (name -> (host array, dtype)) up,
+    dev(d_in, d_out) + BH over the tested rows on resident vectors, per-row results down (the host calls do the same
+    steps inside two calls) -> (kept row indices, dict of the fields at those rows and `corrected`; the `exact` marks stay
+    behind).  A table without rows: host() checks the arguments as the device call would and every result is empty."""
+    n = matrix.shape[0]
+    if n:
+        keep, r = _cli.tested_rows(ctx, dict(ps=(matrix, np.float32), **inputs), field_shapes(fields, n, k), dev)
+    else:
+        keep = np.zeros(0, np.int64)
+        r = {name: v[..., :0] for name, v in host().items() if name != "tested"}
+        r["corrected"] = np.zeros(0)
     r.pop("exact", None)
     return keep, r
 
 
 def compare(matrix, g1_idx, g2_idx, ctx, paired=False, exact=False):
     """-> (kept row indices, dict of compacted per-row results incl. BH-corrected p).  paired: g1_idx[q] and g2_idx[q]
-    are the columns of pair q and the test is the signed-rank test.  exact: exact p-values on the small rows."""
+    are the columns of pair q and the test is the signed-rank test.  exact: exact p-values on the small rows (BH runs
+    over the mixed p vector)."""
     if hasattr(ctx, "ranksum_dev") and matrix.shape[0]:
-        return compare_dev(matrix, g1_idx, g2_idx, ctx, paired, exact)
+        test = row_test(ctx, paired, exact, dev=True)
+        return tested(ctx, matrix, RANKSUM_EXACT_FIELDS if exact else RANKSUM_FIELDS,
+                      dict(g1=(g1_idx, np.int32), g2=(g2_idx, np.int32)), lambda d, out: test(d["ps"], d["g1"], d["g2"], out))
     res = row_test(ctx, paired, exact)(matrix, g1_idx, g2_idx)
     keep = np.flatnonzero(res["tested"])
     out = {k: res[k][keep] for k in ("p", "med1", "med2", "mean1", "mean2", "delta")}
     out["corrected"] = ctx.bh(out["p"]) if keep.size else np.zeros(0)
     return keep, out
-
-
-def compare_strata(matrix, g1_idx, g2_idx, strat1, strat2, n_strata, ctx):
-    """compare_dev() for --strata: table, column lists and their stratum ids up, the stratified rank-sum test + BH over
-    the tested rows on resident vectors, per-row results down"""
-    if not matrix.shape[0]:
-        res = ctx.ranksum_strata(matrix, g1_idx, g2_idx, strat1, strat2)
-        out = {k: res[k][:0] for k in ("p", "z", "med1", "med2", "mean1", "mean2", "delta")}
-        return np.zeros(0, np.int64), {**out, "corrected": np.zeros(0)}
-    return _cli.tested_rows(ctx, dict(ps=(matrix, np.float32), g1=(g1_idx, np.int32), g2=(g2_idx, np.int32),
-                                      s1=(strat1, np.int32), s2=(strat2, np.int32)),
-                            field_shapes(RANKSUM_FIELDS, matrix.shape[0]),
-                            lambda d, out: ctx.ranksum_strata_dev(d["ps"], d["g1"], d["g2"], d["s1"], d["s2"], n_strata, out))
-
-
-def compare_ks(matrix, g1_idx, g2_idx, ctx, exact=False):
-    """compare_dev() for --ks: table and column lists up, the Kolmogorov-Smirnov test + BH over the tested rows on
-    resident vectors, per-row results down (the `exact` marks stay behind)"""
-    if not matrix.shape[0]:
-        res = ctx.ks(matrix, g1_idx, g2_idx, exact)
-        out = {k: res[k][:0] for k in ("p", "d", "med1", "med2", "mean1", "mean2", "delta")}
-        return np.zeros(0, np.int64), {**out, "corrected": np.zeros(0)}
-    keep, r = _cli.tested_rows(ctx, dict(ps=(matrix, np.float32), g1=(g1_idx, np.int32), g2=(g2_idx, np.int32)),
-                               field_shapes(KS_FIELDS, matrix.shape[0]),
-                               lambda d, out: ctx.ks_dev(d["ps"], d["g1"], d["g2"], out, exact))
-    r.pop("exact", None)
-    return keep, r
-
-
-def compare_sets_dev(matrix, set_idx, ctx, trend=False):
-    """the k-set pipeline (-mx): table up, Kruskal-Wallis (trend: Jonckheere-Terpstra over the sets in their order) + BH
-    over the tested rows on resident vectors, per-row results down -> (kept row indices, dict: mean / med float32
-    [k, kept], delta, h (trend: z, j), p, corrected)"""
-    from .engine import kruskal_sets
-    n, s = matrix.shape
-    cols, set_ptr = kruskal_sets(set_idx, s)          # (raises on a column in two sets, before any launch)
-    test = ctx.jonckheere_dev if trend else ctx.kruskal_dev
-    return _cli.tested_rows(ctx, dict(ps=(matrix, np.float32), cols=(cols, np.int32)),
-                            field_shapes(JONCKHEERE_FIELDS if trend else KRUSKAL_FIELDS, n, len(set_idx)),
-                            lambda d, out: test(d["ps"], d["cols"], set_ptr, out))
 
 
 def compare_sharded(matrix, g1_idx, g2_idx, ctx, L, paired=False, exact=False):
@@ -198,21 +162,6 @@ def add_parser(parser):
                         help="Output filename for tab-separated table")
 
 
-MULTI_RANK_REFUSAL = ("compare_sample_sets: -mx/--moreManifests is not available under the multi-rank launcher "
-                      "(the packed all-gather carries the two-set fields only); run it in one process.")
-
-STRATA_MULTI_RANK_REFUSAL = ("compare_sample_sets: --strata is not available under the multi-rank launcher "
-                             "(the sharded two-set path does not carry the stratum ids); run it in one process.")
-
-
-TREND_MULTI_RANK_REFUSAL = ("compare_sample_sets: --trend is not available under the multi-rank launcher "
-                            "(the packed all-gather carries the two-set fields only); run it in one process.")
-
-
-KS_MULTI_RANK_REFUSAL = ("compare_sample_sets: --ks is not available under the multi-rank launcher "
-                         "(the packed all-gather carries the rank-sum fields only); run it in one process.")
-
-
 def strata_columns(g1, g2, header_names, labels):
     """--strata: the manifests' sample lists, the table's column names and the label file's sample -> [labels] ->
     (g1_idx, g2_idx in table order, strat1, strat2 int32 dense ids by first appearance, the number of strata); prints why
@@ -253,91 +202,140 @@ def paired_columns(g1, g2, header_names):
     return idx[:len(g1)], idx[len(g1):]
 
 
+class Test(typing.NamedTuple):
+    """One row per flag that changes the test.  The refusals: `needs` another flag (flag, why); `conflicts`, the ordered
+    (other flag, why) it cannot be combined with; `multi_rank`, why it does not run under the multi-rank launcher.  A row
+    that replaces the rank-sum pipeline (--exact and --paired are forms of it: compare()) says how: `fields`, the
+    engine's table of its _dev call; sel -> `inputs`, the device inputs beside the table; (ctx, sel) -> `dev`, the launch
+    on them; (ctx, matrix, sel) -> `host`, the host call; sel -> `k`, the number of sets of its per-set fields; `stat`, the
+    header cell and the result key of its statistic column."""
+    flag: str
+    conflicts: tuple = ()
+    needs: tuple = None
+    multi_rank: str = None
+    fields: list = None
+    inputs: typing.Callable = None
+    dev: typing.Callable = None
+    host: typing.Callable = None
+    k: typing.Callable = lambda sel: None
+    stat: tuple = None
+
+    def refuse(self, why):
+        _cli.refusal(f"compare_sample_sets {self.flag.split('/')[0]}")(why)
+
+
+def _multi_rank(flag, carries):
+    return (f"compare_sample_sets: {flag} is not available under the multi-rank launcher ({carries}); "
+            f"run it in one process.")
+
+
+def _two_sets(sel):
+    return dict(g1=(sel.g1_idx, np.int32), g2=(sel.g2_idx, np.int32))
+
+
+def _k_sets(test):
+    """the rest of a row over k >= 3 sets; test: the engine's name of the call"""
+    return dict(inputs=lambda sel: dict(cols=(sel.cols, np.int32)), k=lambda sel: len(sel.set_idx),
+                dev=lambda ctx, sel: lambda d, out: getattr(ctx, test + "_dev")(d["ps"], d["cols"], sel.set_ptr, out),
+                host=lambda ctx, matrix, sel: getattr(ctx, test)(matrix, sel.set_idx))
+
+
+PAIRED, EXACT, STRATA, TREND, KS, MX = "--paired", "--exact", "--strata", "--trend", "--ks", "-mx/--moreManifests"
+# in the order the refusals are made; the first selected row with a pipeline is the test that runs
+TESTS = (
+    Test(KS, conflicts=((PAIRED, "the signed-rank test compares matched samples; this test compares two distributions"),
+                        (TREND, "the trend test orders three or more sets"),
+                        (MX, "there is no k-sample Kolmogorov-Smirnov test here"),
+                        (STRATA, "there is no stratified Kolmogorov-Smirnov test here")),
+         multi_rank=_multi_rank(KS, "the packed all-gather carries the rank-sum fields only"),
+         fields=KS_FIELDS, inputs=_two_sets, stat=("D", "d"),
+         dev=lambda ctx, sel: lambda d, out: ctx.ks_dev(d["ps"], d["g1"], d["g2"], out, sel.exact),
+         host=lambda ctx, matrix, sel: ctx.ks(matrix, sel.g1_idx, sel.g2_idx, sel.exact)),
+    Test(TREND, needs=(MX, "three or more ordered sets; two sets are the rank-sum test"),
+         conflicts=((PAIRED, "the signed-rank test compares two matched sets"),
+                    (EXACT, "the trend test is asymptotic only"),
+                    (STRATA, "there is no stratified trend test here")),
+         multi_rank=_multi_rank(TREND, "the packed all-gather carries the two-set fields only"),
+         fields=JONCKHEERE_FIELDS, stat=("z", "z"), **_k_sets("jonckheere")),
+    Test(EXACT, conflicts=((MX, "there is no exact Kruskal-Wallis test here"),)),
+    Test(STRATA, conflicts=((PAIRED, "the signed-rank test pairs samples one to one"),
+                            (MX, "there is no stratified Kruskal-Wallis test here"),
+                            (EXACT, "there is no exact stratified test here")),
+         multi_rank=_multi_rank(STRATA, "the sharded two-set path does not carry the stratum ids"),
+         fields=RANKSUM_FIELDS, inputs=lambda sel: dict(_two_sets(sel), s1=(sel.strat1, np.int32), s2=(sel.strat2, np.int32)),
+         dev=lambda ctx, sel: lambda d, out: ctx.ranksum_strata_dev(d["ps"], d["g1"], d["g2"], d["s1"], d["s2"],
+                                                                    sel.n_strata, out),
+         host=lambda ctx, matrix, sel: ctx.ranksum_strata(matrix, sel.g1_idx, sel.g2_idx, sel.strat1, sel.strat2)),
+    Test(PAIRED, conflicts=((MX, "the signed-rank test compares two matched sets"),)),
+    # k >= 3 sets: Kruskal-Wallis per junction (--trend above: Jonckheere-Terpstra over the sets in this order)
+    Test(MX, multi_rank=_multi_rank(MX, "the packed all-gather carries the two-set fields only"),
+         fields=KRUSKAL_FIELDS, stat=("H", "h"), **_k_sets("kruskal")),
+)
+BY_FLAG = {t.flag: t for t in TESTS}
+KS_MULTI_RANK_REFUSAL, TREND_MULTI_RANK_REFUSAL, STRATA_MULTI_RANK_REFUSAL, MULTI_RANK_REFUSAL = (
+    BY_FLAG[f].multi_rank for f in (KS, TREND, STRATA, MX))
+refuse, refuse_strata = BY_FLAG[PAIRED].refuse, BY_FLAG[STRATA].refuse
+
+
 def run_with(args, ctx=None):
     from . import _stages, mgpu
+    from .engine import kruskal_sets
     L = mgpu.launcher()             # (reads the torchrun environment before any GPU call)
     g1 = samples_from_manifest(args.manifest1)
     g2 = samples_from_manifest(args.manifest2)
     more = [samples_from_manifest(m) for m in (getattr(args, "moreManifests", None) or [])]
-    paired = bool(getattr(args, "paired", False))
-    exact = bool(getattr(args, "exact", False))
-    trend = bool(getattr(args, "trend", False))
-    ks = bool(getattr(args, "ks", False))
-    if ks:
-        for on, flag in ((paired, "--paired (the signed-rank test compares matched samples; this test compares two "
-                                  "distributions)"),
-                         (trend, "--trend (the trend test orders three or more sets)"),
-                         (more, "-mx/--moreManifests (there is no k-sample Kolmogorov-Smirnov test here)"),
-                         (getattr(args, "strata", None), "--strata (there is no stratified Kolmogorov-Smirnov test here)")):
-            if on:
-                refuse_ks(f"cannot be combined with {flag}")
-        _cli.refuse_multi_rank(L, KS_MULTI_RANK_REFUSAL)
-    if trend:
-        if not more:
-            refuse_trend("needs -mx/--moreManifests (three or more ordered sets; two sets are the rank-sum test)")
-        for on, flag in ((paired, "--paired (the signed-rank test compares two matched sets)"),
-                         (exact, "--exact (the trend test is asymptotic only)"),
-                         (getattr(args, "strata", None), "--strata (there is no stratified trend test here)")):
-            if on:
-                refuse_trend(f"cannot be combined with {flag}")
-        _cli.refuse_multi_rank(L, TREND_MULTI_RANK_REFUSAL)
-    if exact and more:
-        refuse_exact("cannot be combined with -mx/--moreManifests (there is no exact Kruskal-Wallis test here)")
-    strata = getattr(args, "strata", None)
-    if strata:
-        for on, flag in ((paired, "--paired (the signed-rank test pairs samples one to one)"),
-                         (more, "-mx/--moreManifests (there is no stratified Kruskal-Wallis test here)"),
-                         (exact, "--exact (there is no exact stratified test here)")):
-            if on:
-                refuse_strata(f"cannot be combined with {flag}")
-        _cli.refuse_multi_rank(L, STRATA_MULTI_RANK_REFUSAL)
-        strat = strata_columns(g1, g2, table_header_names(args.psiSPLICEDICE), _cli.read_labels(strata, refuse_strata))
-    if paired:
-        if more:
-            refuse("cannot be combined with -mx/--moreManifests (the signed-rank test compares two matched sets)")
-        pair_idx = paired_columns(g1, g2, table_header_names(args.psiSPLICEDICE))      # (exits before any GPU call)
+    on = {PAIRED: getattr(args, "paired", False), EXACT: getattr(args, "exact", False), STRATA: getattr(args, "strata", None),
+          TREND: getattr(args, "trend", False), KS: getattr(args, "ks", False), MX: more}
+    chosen = [t for t in TESTS if on[t.flag]]
+    sel = argparse.Namespace(exact=bool(on[EXACT]))
+    for t in chosen:
+        if t.needs and not on[t.needs[0]]:
+            t.refuse(f"needs {t.needs[0]} ({t.needs[1]})")
+        for other, why in t.conflicts:
+            if on[other]:
+                t.refuse(f"cannot be combined with {other} ({why})")
+        if t.multi_rank and t.flag != MX:        # (-mx alone is refused after the size check below, as it always was)
+            _cli.refuse_multi_rank(L, t.multi_rank)
+    if on[STRATA]:                   # (the two that pick their columns from the header alone: they exit before any GPU call)
+        sel.g1_idx, sel.g2_idx, sel.strat1, sel.strat2, sel.n_strata = strata_columns(
+            g1, g2, table_header_names(args.psiSPLICEDICE), _cli.read_labels(on[STRATA], refuse_strata))
+    if on[PAIRED]:
+        sel.g1_idx, sel.g2_idx = paired_columns(g1, g2, table_header_names(args.psiSPLICEDICE))
     if len(g1) < 3 or len(g2) < 3 or any(len(g) < 3 for g in more):
         print("Cannot conduct wilcoxon with less than 3 samples in either group. Exit.", file=sys.stderr)
         sys.exit(1)
     if more:
         _cli.refuse_multi_rank(L, MULTI_RANK_REFUSAL)
+    test = next((t for t in chosen if t.dev), None)
     with _stages.stage("parse"):
         rows, cols, matrix = read_ps_table(args.psiSPLICEDICE, as_table=True)
+    if not hasattr(sel, "g1_idx"):
+        sel.g1_idx, sel.g2_idx = column_indices(g1, cols), column_indices(g2, cols)
+    if more:
+        sel.set_idx = [sel.g1_idx, sel.g2_idx] + [column_indices(g, cols) for g in more]
+        sel.cols, sel.set_ptr = kruskal_sets(sel.set_idx, matrix.shape[1])       # (raises on a column in two sets)
     with _cli.engine_scope(ctx, lambda: Context(L.local_rank)) as ctx:
-        if strata:
-            keep, r = compare_strata(matrix, *strat, ctx)
-        elif ks:
-            keep, r = compare_ks(matrix, column_indices(g1, cols), column_indices(g2, cols), ctx, exact)
-        elif more:
-            # k >= 3 sets: Kruskal-Wallis per junction; columns event mean1..meank median1..mediank delta H p-value corrected
-            # (--trend: Jonckheere-Terpstra over the sets in this order, z where H stands)
-            keep, r = compare_sets_dev(matrix, [column_indices(g, cols) for g in [g1, g2] + more], ctx, trend)
+        if test:
+            keep, r = tested(ctx, matrix, test.fields, test.inputs(sel), test.dev(ctx, sel),
+                             lambda: test.host(ctx, matrix, sel), test.k(sel))
+        elif L.world > 1:
+            keep, r = compare_sharded(matrix, sel.g1_idx, sel.g2_idx, ctx, L, bool(on[PAIRED]), sel.exact)
         else:
-            g1_idx, g2_idx = pair_idx if paired else (column_indices(g1, cols), column_indices(g2, cols))
-            if L.world > 1:
-                keep, r = compare_sharded(matrix, g1_idx, g2_idx, ctx, L, paired, exact)
-            else:
-                keep, r = compare(matrix, g1_idx, g2_idx, ctx, paired, exact)
+            keep, r = compare(matrix, sel.g1_idx, sel.g2_idx, ctx, bool(on[PAIRED]), sel.exact)
     if not L.root:
         return                       # one set of output files: rank 0 writes the table
     # the library's multithreaded formatter (numpy str() of float32 / float64 per column, byte-identical to the
-    # reference's print(*fields, sep="\t"))
-    if more:
-        k = 2 + len(more)
-        header = "\t".join(["event"] + [f"mean{i + 1}" for i in range(k)] + [f"median{i + 1}" for i in range(k)] +
-                           ["delta", "z" if trend else "H", "p-value", "corrected"])
-        columns = [*r["mean"], *r["med"], r["delta"], r["z" if trend else "h"], r["p"], r["corrected"]]
-    elif ks:
-        header = "event\tmean1\tmean2\tmedian1\tmedian2\tdelta\tD\tp-value\tcorrected"
-        columns = [r["mean1"], r["mean2"], r["med1"], r["med2"], r["delta"], r["d"], r["p"], r["corrected"]]
-    else:
-        header = "event\tmean1\tmean2\tmedian1\tmedian2\tdelta\tp-value\tcorrected"
-        columns = [r["mean1"], r["mean2"], r["med1"], r["med2"], r["delta"], r["p"], r["corrected"]]
+    # reference's print(*fields, sep="\t")); columns: event mean1..meank median1..mediank delta [statistic] p-value corrected
+    k = 2 + len(more)
+    means, medians = (r["mean"], r["med"]) if more else ((r["mean1"], r["mean2"]), (r["med1"], r["med2"]))
+    stat = test.stat if test and test.stat else None
+    header = "\t".join(["event"] + [f"mean{i + 1}" for i in range(k)] + [f"median{i + 1}" for i in range(k)] + ["delta"] +
+                       ([stat[0]] if stat else []) + ["p-value", "corrected"])
+    columns = [*means, *medians, r["delta"]] + ([r[stat[1]]] if stat else []) + [r["p"], r["corrected"]]
     _cli.write_event_table(args.outputFile, header, rows, keep, columns, ["repr"] * len(columns), args.annotation)
 
 
 if __name__ == "__main__":
-    import argparse
     p = argparse.ArgumentParser()
     add_parser(p)
     run_with(p.parse_args())

@@ -67,7 +67,7 @@ def covariate_columns(names, header_names):
 
 
 def correlate_dev(matrix, cols, xg, ctx):
-    """the pipeline of compare_sample_sets.compare_dev: table up, Spearman + BH over the tested rows on resident vectors,
+    """the pipeline of compare_sample_sets.tested: table up, Spearman + BH over the tested rows on resident vectors,
     per-row results down -> (kept row indices, dict of compacted per-row results incl. BH-corrected p)"""
     return _cli.tested_rows(ctx, dict(ps=(matrix, np.float32), cols=(cols, np.int32), xg=(xg, np.int32)),
                             field_shapes(SPEARMAN_FIELDS, matrix.shape[0]),

@@ -42,11 +42,10 @@
 //       checkpoints (t = c1 + c2 is a run end) with an LDS atomicOr and every wave runs the recurrence.
 //
 // rowsum.h: PsKey, order bits, lane groups with group_sum, group_sort (both key widths) and group_median, the block's
-// compaction, pairwise sum and bitonic network, the stores of a row, the output pointers with their zeroing and staging
-// (D rides in the z slot), launch sizes.
+// compaction, pairwise sum and bitonic network, the median key, the stores of a row, the output pointers with their
+// zeroing and staging (D rides in the z slot), launch sizes and the width ladder; colcheck.h: the check of the two groups.
 #include "common.h"
 #include <math.h>
-#include <vector>
 #include "rowsum.h"
 #include "dd.h"
 
@@ -205,6 +204,7 @@ __global__ void __launch_bounds__(256) ks_group_kernel(const float* __restrict__
         const int ri = r0 + g;
         float x = __builtin_nanf("");
         if (ri < rows_here && gl < m) x = __builtin_nontemporal_load(ps + (row0 + ri) * s + col);
+        // (this front is strata.hip's, written out in both: as a helper it changed the kernels and strata's timed slower, A.17)
         const bool kept = x == x;
         const unsigned long long km = (__ballot(kept) >> g0) & G::MASK;
         const unsigned long long k1 = km & mask1, k2 = km >> n1;
@@ -283,6 +283,7 @@ __global__ void __launch_bounds__(RB_THREADS) ks_block_kernel(const float* __res
     for (int64_t row = blockIdx.x; row < n; row += gridDim.x) {
         const float* prow = ps + row * s;
         // ---- per group: ordered compaction + numpy pairwise sum (np.sum: the identity 0 plus the tree)
+        // (written out in strata.hip and ks.hip: as a struct + helper of rowsum.h the LDS layout and the kernel changed, A.17)
         const int nv1 = block_compact(prow, g1, n1, F, wcnt);
         const float sum1 = 0.0f + block_pairwise_sum<PW_DEPTH>(F, nv1, leaf_off, leaf_sum, scratch8, KS_LEAF_MAX);
         const int nv2 = block_compact(prow, g2, n2, F, wcnt);
@@ -297,8 +298,7 @@ __global__ void __launch_bounds__(RB_THREADS) ks_block_kernel(const float* __res
                 unsigned long long a = ~0ull;
                 if (j < m) {
                     const bool in1 = j < n1;
-                    const float v = prow[in1 ? g1[j] : g2[j - n1]];
-                    if (v == v) a = ((unsigned long long)(in1 ? 0u : 1u) << 32) | f32_ord(v);
+                    a = two_group_median_key(prow[in1 ? g1[j] : g2[j - n1]], in1);
                 }
                 A[j] = a;
             }
@@ -348,34 +348,6 @@ __global__ void __launch_bounds__(RB_THREADS) ks_block_kernel(const float* __res
     }
 }
 
-template <int P>
-int ks_launch_group(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* d_g1, int n1, const int32_t* d_g2,
-                    int n2, int want_exact, TwoSampleOut o, uint8_t* d_exact) {
-    const int waves = 4;
-    const int ch = rows_per_chunk(ctx->n_cu, n);
-    const int64_t blocks = wave_launch_blocks(ctx, n, ch, waves);
-    SD_LAUNCH(ctx, "ks_group_kernel", (ks_group_kernel<P>), dim3((unsigned)blocks), dim3(waves * 64), 0, d_ps, n, s, d_g1, n1,
-              d_g2, n2, want_exact, ch, o, d_exact);
-    return SDICE_OK;
-}
-
-// the checks both entry points share
-int ks_check_counts(int32_t n1, int32_t n2, int32_t s) {
-    if (n1 > KS_MAX_GROUP || n2 > KS_MAX_GROUP) {
-        sdice_set_error("sdice_ks: groups of %d and %d columns, at most %d each are supported", (int)n1, (int)n2, KS_MAX_GROUP);
-        return SDICE_ERR_ARG;
-    }
-    if (n1 < 1 || n2 < 1) {
-        sdice_set_error("sdice_ks: groups of %d and %d columns, each needs 1..%d", (int)n1, (int)n2, KS_MAX_GROUP);
-        return SDICE_ERR_ARG;
-    }
-    if ((int64_t)n1 + n2 > s) {
-        sdice_set_error("sdice_ks: more selected columns than the table has (a column may appear once over both lists)");
-        return SDICE_ERR_ARG;
-    }
-    return SDICE_OK;
-}
-
 }  // namespace
 
 extern "C" int sdice_ks_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, const int32_t* d_g1, int32_t n1,
@@ -383,7 +355,7 @@ extern "C" int sdice_ks_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d
                             float* d_med1, float* d_med2, float* d_mean1, float* d_mean2, float* d_delta, uint8_t* d_exact) {
     SD_ARG(ctx, "ctx is NULL");
     SD_ARG(n >= 0 && s >= 0, "negative size");
-    SD_TRY(ks_check_counts(n1, n2, s));
+    SD_TRY(check_two_groups("sdice_ks", nullptr, n1, nullptr, n2, s, KS_MAX_GROUP));      // (device lists: the counts)
     if (n == 0) return SDICE_OK;
     SD_ARG(d_tested && d_p && d_med1 && d_med2 && d_mean1 && d_mean2 && d_delta, "NULL output");
     SD_ARG(!want_exact || d_exact, "NULL output: exact is required with want_exact");
@@ -397,12 +369,15 @@ extern "C" int sdice_ks_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d
         if (d_exact) SD_HIP(hipMemsetAsync(d_exact, 0, (size_t)n, ctx->stream));
         return zero_two_sample(ctx, n, o);
     }
-    if (m <= KS_GROUP_MAX) {                                   // (a ladder per file: the launches differ in their arguments)
-        if (m <= 8) return ks_launch_group<8>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, we, o, d_exact);
-        if (m <= 16) return ks_launch_group<16>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, we, o, d_exact);
-        if (m <= 32) return ks_launch_group<32>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, we, o, d_exact);
-        return ks_launch_group<64>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, we, o, d_exact);
-    }
+    if (m <= KS_GROUP_MAX)
+        return with_group_width(m, [&](auto width) -> int {
+            const int waves = 4;
+            const int ch = rows_per_chunk(ctx->n_cu, n);
+            const int64_t blocks = wave_launch_blocks(ctx, n, ch, waves);
+            SD_LAUNCH(ctx, "ks_group_kernel", (ks_group_kernel<decltype(width)::value>), dim3((unsigned)blocks),
+                      dim3(waves * 64), 0, d_ps, n, (int)s, d_g1, (int)n1, d_g2, (int)n2, we, ch, o, d_exact);
+            return SDICE_OK;
+        });
     const int P = next_pow2(m, 128);
     const size_t lds = (size_t)P * 8;
     const int64_t blocks = row_launch_blocks(ctx, n);
@@ -419,21 +394,7 @@ extern "C" int sdice_ks(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps, c
     SD_ARG(ctx, "ctx is NULL");
     SD_ARG(n >= 0 && s >= 0, "negative size");
     SD_ARG(g1 && g2, "index list is NULL");
-    {   // ranges and the one-appearance rule, before the counts are compared with s: the message names the first violation
-        if (n1 >= 1 && n1 <= KS_MAX_GROUP && n2 >= 1 && n2 <= KS_MAX_GROUP) {
-            std::vector<char> seen((size_t)s, 0);
-            const int32_t* lists[2] = {g1, g2};
-            const int32_t counts[2] = {n1, n2};
-            for (int l = 0; l < 2; ++l)
-                for (int q = 0; q < counts[l]; ++q) {
-                    const int32_t c = lists[l][q];
-                    SD_ARG(c >= 0 && c < s, "column index out of range");
-                    SD_ARG(!seen[c], "a column may appear once over both lists");
-                    seen[c] = 1;
-                }
-        }
-    }
-    SD_TRY(ks_check_counts(n1, n2, s));
+    SD_TRY(check_two_groups(__func__, g1, n1, g2, n2, s, KS_MAX_GROUP));
     if (n == 0) return SDICE_OK;
     SD_ARG(tested && p && med1 && med2 && mean1 && mean2 && delta, "NULL output");
     SD_ARG(!want_exact || exact, "NULL output: exact is required with want_exact");

@@ -5,33 +5,39 @@
 // network, the tie-run bounds of a sorted array, the median search in the 16-bins-per-lane histograms of the counting
 // kernels, the stores of a two-sample row.  Host: the eight output pointers of the two-sample tests, their "no row can be
 // tested" block and their staging for a host entry point, the launch sizes of the wave-per-chunk and row-per-workgroup
-// kernels, the check of a column list.  What each file takes:
+// kernels, the width ladder of the lane-group kernels; the checks of the column lists and the k-set limits are
+// colcheck.h's (host only, no HIP), included here.  What each file takes:
 //   ranksum.hip (K5)      PsKey, median_sorted, block_compact, the pairwise sums, find_bin, lanes_below; TwoSampleOut (as
 //                         RsOut), zero_two_sample, TwoSampleStaging
 //   kruskal.hip (K12)     as ranksum.hip's kernels + f32_ord, median_of_ord, block_bitonic
 //                         + the k-set section: the limits, KwSets, kw_stage_row / kw_walk_set (the first walk of the grid
-//                         kernel), kw_block_sort_sets (the block kernel up to its medians), kw_check_sets, kw_plan
-//   jonckheere.hip (K18)  the k-set section as kruskal.hip, kw_load_bins / kw_scan_bins, the launch sizes, check_columns
+//                         kernel), kw_block_sort_sets (the block kernel up to its medians), kw_plan, kw_check_sets, check_columns
+//   jonckheere.hip (K18)  as kruskal.hip's k-set section + kw_load_bins / kw_scan_bins, the launch sizes
 //   signedrank.hip (K13)  PsKey, f32_ord, LaneGroup, group_add / group_sum / group_sort / group_median, pair_diff_key,
 //                         block_compact_by, block_pairwise_sum, block_bitonic, run_bounds, median_of_ord, store_two_sample,
-//                         the launch sizes, check_columns; TwoSampleOut, zero_two_sample, TwoSampleStaging
+//                         the launch sizes, with_group_width; TwoSampleOut, zero_two_sample, TwoSampleStaging, check_columns
 //   spearman.hip (K14)    PsKey, f32_ord, LaneGroup and its sums, the block's compaction, sum, network and run bounds, the
-//                         launch sizes, check_columns
+//                         launch sizes, with_group_width, check_columns
 //   gram.hip              check_columns
-//   exactrank.hip (K16)   PsKey, pair_diff_key, SD_WAVE_SYNC, row_launch_blocks, check_columns; TwoSampleStaging
+//   exactrank.hip (K16)   PsKey, pair_diff_key, SD_WAVE_SYNC, row_launch_blocks; TwoSampleStaging, check_columns
 //   strata.hip (K17)      PsKey, f32_ord, LaneGroup, group_add / group_sum / group_sort / group_median, block_compact,
-//                         block_pairwise_sum, block_bitonic, run_bounds, median_of_ord, store_two_sample, the launch sizes;
-//                         TwoSampleOut, zero_two_sample, TwoSampleStaging
+//                         block_pairwise_sum, block_bitonic, run_bounds, two_group_median_key, median_of_ord,
+//                         store_two_sample, the launch sizes, with_group_width; TwoSampleOut, zero_two_sample,
+//                         TwoSampleStaging, check_two_groups (with the stratum ids)
 //   ks.hip (K19)          PsKey, f32_ord, LaneGroup, group_sum / group_sort / group_median, block_compact,
-//                         block_pairwise_sum, block_bitonic, median_of_ord, store_two_sample, the launch sizes;
-//                         TwoSampleOut (D in the z slot), zero_two_sample, TwoSampleStaging (with `exact`)
+//                         block_pairwise_sum, block_bitonic, two_group_median_key, median_of_ord, store_two_sample, the
+//                         launch sizes, with_group_width; TwoSampleOut (D in the z slot), zero_two_sample,
+//                         TwoSampleStaging (with `exact`), check_two_groups
+// (strata.hip and ks.hip: the pass front of the group kernels and the LDS + sums of the block kernels stay written out, A.17)
 // Every helper is inlined into the kernels that call it and the kernels themselves stay in their .hip files, so a change
 // to a helper here is a change to each kernel that uses it -- ranksum.hip's pairq and count kernels among them, whose
 // committed counter pass is stamped with the hash of ranksum.hip alone and will not notice.
 #pragma once
 #include "common.h"
+#include "colcheck.h"
 #include <algorithm>
 #include <initializer_list>
+#include <type_traits>
 
 #define SD_WAVE_SYNC()                                        \
     do {                                                      \
@@ -417,10 +423,14 @@ __device__ __forceinline__ RunBounds run_bounds(const T* K, int n, C code, Proj 
     return {first, lo};
 }
 
+// Two column groups by the workgroup (strata.hip, ks.hip): the key the medians are sorted by -- (group << 32 | order
+// bits) of a selected value, a NaN last with the padding
+__device__ __forceinline__ unsigned long long two_group_median_key(float v, bool in1) {
+    return v == v ? ((unsigned long long)(in1 ? 0u : 1u) << 32) | f32_ord(v) : ~0ull;
+}
+
 // ---- k sample sets (kruskal.hip, jonckheere.hip): the limits, the sets as a kernel argument, the first walk of a wave
 // over a row of 3-decimal values and the (set, value) sort of a workgroup over any row
-constexpr int KW_MAX_SETS = 64;
-constexpr int KW_MAX_N = 16384;          // selected columns per row, both kernels (block kernel: 8 B of LDS per column)
 constexpr int KW_BINS = 1024;            // 1001 used
 constexpr int KW_SUM_PIECE = 8192;       // np.add.reduce hands the pairwise loop at most np.getbufsize() = 8192 values at a time
 constexpr int KW_PW_DEPTH = 7;           // levels of numpy's pairwise recursion inside a piece (7689 values are the first to need 7)
@@ -644,27 +654,16 @@ inline int next_pow2(int v, int from) {
     return from;
 }
 
-// Host: the checks the k-set entry points share (`fn` names the public call in the error); set_ptr is a HOST array
-inline int kw_check_sets(const char* fn, const int32_t* set_ptr, int32_t k, int32_t s) {
-    const char* msg = nullptr;
-    if (!set_ptr) msg = "set_ptr is NULL";
-    else if (!(k >= 2 && k <= KW_MAX_SETS)) msg = "the number of sets must be 2..64";
-    else if (set_ptr[0] != 0) msg = "set_ptr[0] must be 0";
-    for (int i = 0; !msg && i < k; ++i)
-        if (!(set_ptr[i + 1] > set_ptr[i])) msg = "empty set (set_ptr must increase)";
-    if (msg) {
-        sdice_set_error("kw_check_sets: %s", msg);
-        return SDICE_ERR_ARG;
-    }
-    if (set_ptr[k] > KW_MAX_N) {
-        sdice_set_error("%s: %d selected columns, at most %d are supported", fn, (int)set_ptr[k], KW_MAX_N);
-        return SDICE_ERR_ARG;
-    }
-    if (set_ptr[k] > s) {
-        sdice_set_error("kw_check_sets: more selected columns than the table has (a column belongs to one set only)");
-        return SDICE_ERR_ARG;
-    }
-    return SDICE_OK;
+// Host: the lane-group width of m <= 64 selected columns -- 8, 16, 32 or 64, none below FROM -- handed to launch as a
+// std::integral_constant, so that a generic lambda picks its kernel<P> and keeps its own argument list
+template <int FROM = 8, class Launch>
+inline int with_group_width(int m, Launch launch) {
+    if constexpr (FROM <= 8)
+        if (m <= 8) return launch(std::integral_constant<int, 8>{});
+    if constexpr (FROM <= 16)
+        if (m <= 16) return launch(std::integral_constant<int, 16>{});
+    if (m <= 32) return launch(std::integral_constant<int, 32>{});
+    return launch(std::integral_constant<int, 64>{});
 }
 
 // Host: the sets as the kernels take them, the launch shape of a grid kernel over KwWaveLds and the sort length of a
@@ -736,21 +735,4 @@ class TwoSampleStaging {
     double* dd_ = nullptr;
     float* df_ = nullptr;
 };
-
-// Host: every one of the m entries of each list is a column of the table (0 .. s) and no column is listed twice, in one
-// list or two; `fn` is the entry point the error names, with the wording it has always had
-inline int check_columns(const char* fn, std::initializer_list<const int32_t*> lists, int m, int s, const char* range_msg,
-                         const char* once_msg) {
-    std::vector<char> seen((size_t)s, 0);
-    for (const int32_t* l : lists)
-        for (int q = 0; q < m; ++q) {
-            const char* msg = (l[q] < 0 || l[q] >= s) ? range_msg : (seen[l[q]] ? once_msg : nullptr);
-            if (msg) {
-                sdice_set_error("%s: %s", fn, msg);
-                return SDICE_ERR_ARG;
-            }
-            seen[l[q]] = 1;
-        }
-    return SDICE_OK;
-}
 }  // namespace

@@ -369,16 +369,6 @@ __global__ void __launch_bounds__(RB_THREADS) signedrank_block_kernel(const floa
 }
 
 template <int P>
-int sr_launch_group(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* d_a, const int32_t* d_b, int m, TwoSampleOut o) {
-    const int waves = 4;
-    const int ch = rows_per_chunk(ctx->n_cu, n);
-    const int64_t blocks = wave_launch_blocks(ctx, n, ch, waves);
-    SD_LAUNCH(ctx, "signedrank_group_kernel", (signedrank_group_kernel<P>), dim3((unsigned)blocks), dim3(waves * 64), 0, d_ps,
-              n, s, d_a, d_b, m, ch, o);
-    return SDICE_OK;
-}
-
-template <int P>
 int sr_launch_lane(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* d_a, const int32_t* d_b, int m, TwoSampleOut o) {
     const int64_t blocks = row_launch_blocks(ctx, sd_ceil_div(n, 256));
     SD_LAUNCH(ctx, "signedrank_lane_kernel", (signedrank_lane_kernel<P>), dim3((unsigned)blocks), dim3(256), 0, d_ps, n, s,
@@ -411,13 +401,17 @@ extern "C" int sdice_signedrank_dev(sdice_ctx* ctx, int64_t n, int32_t s, const 
     SD_TRY(ctx->arena.reset(ctx->stream));
     TwoSampleOut o{d_tested, d_p, d_z, d_med1, d_med2, d_mean1, d_mean2, d_delta};
     if (m < 3) return zero_two_sample(ctx, n, o);            // no row can be tested
-    if (m <= SR_GROUP_MAX) {                                   // (a ladder per file: the launches differ in their arguments)
-        if (m <= 4) return sr_launch_lane<4>(ctx, d_ps, n, s, d_a, d_b, m, o);
-        if (m <= 8) return sr_launch_lane<8>(ctx, d_ps, n, s, d_a, d_b, m, o);
-        if (m <= 16) return sr_launch_group<16>(ctx, d_ps, n, s, d_a, d_b, m, o);
-        if (m <= 32) return sr_launch_group<32>(ctx, d_ps, n, s, d_a, d_b, m, o);
-        return sr_launch_group<64>(ctx, d_ps, n, s, d_a, d_b, m, o);
-    }
+    if (m <= 4) return sr_launch_lane<4>(ctx, d_ps, n, s, d_a, d_b, m, o);
+    if (m <= 8) return sr_launch_lane<8>(ctx, d_ps, n, s, d_a, d_b, m, o);
+    if (m <= SR_GROUP_MAX)
+        return with_group_width<16>(m, [&](auto width) -> int {
+            const int waves = 4;
+            const int ch = rows_per_chunk(ctx->n_cu, n);
+            const int64_t blocks = wave_launch_blocks(ctx, n, ch, waves);
+            SD_LAUNCH(ctx, "signedrank_group_kernel", (signedrank_group_kernel<decltype(width)::value>), dim3((unsigned)blocks),
+                      dim3(waves * 64), 0, d_ps, n, (int)s, d_a, d_b, (int)m, ch, o);
+            return SDICE_OK;
+        });
     const int P = next_pow2(m, 128);
     const size_t lds = (size_t)P * 3 * 4;
     const int64_t blocks = row_launch_blocks(ctx, n);

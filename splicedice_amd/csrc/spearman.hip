@@ -486,17 +486,6 @@ __global__ void __launch_bounds__(RB_THREADS) spearman_block_kernel(const float*
     }
 }
 
-template <int P>
-int sp_launch_group(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* d_cols, const int32_t* d_xg, int m,
-                    SpOut o) {
-    const int waves = 4;
-    const int ch = rows_per_chunk(ctx->n_cu, n);
-    const int64_t blocks = wave_launch_blocks(ctx, n, ch, waves);
-    SD_LAUNCH(ctx, "spearman_group_kernel", (spearman_group_kernel<P>), dim3((unsigned)blocks), dim3(waves * 64), 0, d_ps, n,
-              s, d_cols, d_xg, m, ch, o);
-    return SDICE_OK;
-}
-
 template <int E>
 int sp_launch_wave(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* d_cols, const int32_t* d_xg, int m,
                    SpOut o) {
@@ -531,12 +520,15 @@ extern "C" int sdice_spearman_dev(sdice_ctx* ctx, int64_t n, int32_t s, const fl
     SD_HIP(hipSetDevice(ctx->device));
     SD_TRY(ctx->arena.reset(ctx->stream));
     SpOut o{d_tested, d_p, d_rho, d_n_kept, d_med, d_mean};
-    if (m <= SP_GROUP_MAX) {
-        if (m <= 8) return sp_launch_group<8>(ctx, d_ps, n, s, d_cols, d_xg, m, o);
-        if (m <= 16) return sp_launch_group<16>(ctx, d_ps, n, s, d_cols, d_xg, m, o);
-        if (m <= 32) return sp_launch_group<32>(ctx, d_ps, n, s, d_cols, d_xg, m, o);
-        return sp_launch_group<64>(ctx, d_ps, n, s, d_cols, d_xg, m, o);
-    }
+    if (m <= SP_GROUP_MAX)
+        return with_group_width(m, [&](auto width) -> int {
+            const int waves = 4;
+            const int ch = rows_per_chunk(ctx->n_cu, n);
+            const int64_t blocks = wave_launch_blocks(ctx, n, ch, waves);
+            SD_LAUNCH(ctx, "spearman_group_kernel", (spearman_group_kernel<decltype(width)::value>), dim3((unsigned)blocks),
+                      dim3(waves * 64), 0, d_ps, n, (int)s, d_cols, d_xg, (int)m, ch, o);
+            return SDICE_OK;
+        });
     if (m <= SP_WAVE_MAX / 2) return sp_launch_wave<2>(ctx, d_ps, n, s, d_cols, d_xg, m, o);
     if (m <= SP_WAVE_MAX) return sp_launch_wave<4>(ctx, d_ps, n, s, d_cols, d_xg, m, o);
     const int P = next_pow2(m, 512);

@@ -39,11 +39,11 @@
 //       medians and the rank keys --, run and segment bounds by binary search, the stratum sums in LDS, one wave finishes.
 //
 // rowsum.h: PsKey, order bits, lane groups with group_sum, group_sort (both key widths) and group_median, the block's
-// compaction, pairwise sum, bitonic network, run bounds, the stores of a row, the output pointers with their zeroing and
-// staging, launch sizes; dd.h: the double-double sum.
+// compaction, pairwise sum, bitonic network, run bounds, the median key, the stores of a row, the output pointers with
+// their zeroing and staging, launch sizes and the width ladder; colcheck.h: the check of the two groups and their stratum
+// ids; dd.h: the double-double sum.
 #include "common.h"
 #include <math.h>
-#include <vector>
 #include "rowsum.h"
 #include "dd.h"
 
@@ -187,6 +187,7 @@ __global__ void __launch_bounds__(256) strata_group_kernel(const float* __restri
         const int ri = r0 + g;
         float x = __builtin_nanf("");
         if (ri < rows_here && gl < m) x = __builtin_nontemporal_load(ps + (row0 + ri) * s + col);
+        // (this front is ks.hip's, written out in both: as a helper it changed the kernels and strata's timed slower, A.17)
         const bool kept = x == x;
         const unsigned long long km = (__ballot(kept) >> g0) & G::MASK;
         const unsigned long long k1 = km & mask1, k2 = km >> n1;
@@ -320,6 +321,7 @@ __global__ void __launch_bounds__(RB_THREADS) strata_block_kernel(const float* _
     for (int64_t row = blockIdx.x; row < n; row += gridDim.x) {
         const float* prow = ps + row * s;
         // ---- per group: ordered compaction + numpy pairwise sum (np.sum: the identity 0 plus the tree)
+        // (written out in strata.hip and ks.hip: as a struct + helper of rowsum.h the LDS layout and the kernel changed, A.17)
         const int nv1 = block_compact(prow, g1, n1, F, wcnt);
         const float sum1 = 0.0f + block_pairwise_sum<PW_DEPTH>(F, nv1, leaf_off, leaf_sum, scratch8, ST_LEAF_MAX);
         const int nv2 = block_compact(prow, g2, n2, F, wcnt);
@@ -342,7 +344,7 @@ __global__ void __launch_bounds__(RB_THREADS) strata_block_kernel(const float* _
                     const float v = prow[in1 ? g1[j] : g2[j - n1]];
                     if (v == v) {
                         const uint32_t st = (uint32_t)(in1 ? st1[j] : st2[j - n1]) & 63u;
-                        a = ((unsigned long long)(in1 ? 0u : 1u) << 32) | f32_ord(v);
+                        a = two_group_median_key(v, in1);
                         if (grid) b32 = StKey<uint32_t>::make(st, v, in1);
                         else b64 = StKey<unsigned long long>::make(st, v, in1);
                     }
@@ -393,39 +395,6 @@ __global__ void __launch_bounds__(RB_THREADS) strata_block_kernel(const float* _
     }
 }
 
-template <int P>
-int st_launch_group(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* d_g1, int n1, const int32_t* d_g2,
-                    int n2, const int32_t* d_st1, const int32_t* d_st2, TwoSampleOut o) {
-    const int waves = 4;
-    const int ch = rows_per_chunk(ctx->n_cu, n);
-    const int64_t blocks = wave_launch_blocks(ctx, n, ch, waves);
-    SD_LAUNCH(ctx, "strata_group_kernel", (strata_group_kernel<P>), dim3((unsigned)blocks), dim3(waves * 64), 0, d_ps, n, s,
-              d_g1, n1, d_g2, n2, d_st1, d_st2, ch, o);
-    return SDICE_OK;
-}
-
-// the checks both entry points share
-int st_check_counts(int32_t n1, int32_t n2, int32_t n_strata, int32_t s) {
-    if (n1 > ST_MAX_GROUP || n2 > ST_MAX_GROUP) {
-        sdice_set_error("sdice_ranksum_strata: groups of %d and %d columns, at most %d each are supported", (int)n1, (int)n2,
-                        ST_MAX_GROUP);
-        return SDICE_ERR_ARG;
-    }
-    if (n1 < 1 || n2 < 1) {
-        sdice_set_error("sdice_ranksum_strata: groups of %d and %d columns, each needs 1..%d", (int)n1, (int)n2, ST_MAX_GROUP);
-        return SDICE_ERR_ARG;
-    }
-    if (n_strata < 1 || n_strata > ST_MAX_STRATA) {
-        sdice_set_error("sdice_ranksum_strata: %d strata, the number of strata must be 1..%d", (int)n_strata, ST_MAX_STRATA);
-        return SDICE_ERR_ARG;
-    }
-    if ((int64_t)n1 + n2 > s) {
-        sdice_set_error("sdice_ranksum_strata: more selected columns than the table has (a column may appear once over both lists)");
-        return SDICE_ERR_ARG;
-    }
-    return SDICE_OK;
-}
-
 }  // namespace
 
 extern "C" int sdice_ranksum_strata_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, const int32_t* d_g1,
@@ -435,7 +404,8 @@ extern "C" int sdice_ranksum_strata_dev(sdice_ctx* ctx, int64_t n, int32_t s, co
                                         float* d_delta) {
     SD_ARG(ctx, "ctx is NULL");
     SD_ARG(n >= 0 && s >= 0, "negative size");
-    SD_TRY(st_check_counts(n1, n2, n_strata, s));
+    SD_TRY(check_two_groups("sdice_ranksum_strata", nullptr, n1, nullptr, n2, s, ST_MAX_GROUP, nullptr, nullptr, n_strata,
+                            ST_MAX_STRATA));                   // (device lists: the counts)
     if (n == 0) return SDICE_OK;
     SD_ARG(d_tested && d_p && d_med1 && d_med2 && d_mean1 && d_mean2 && d_delta, "NULL output");
     SD_ARG(d_ps && d_g1 && d_g2 && d_strat1 && d_strat2, "NULL input");
@@ -444,12 +414,15 @@ extern "C" int sdice_ranksum_strata_dev(sdice_ctx* ctx, int64_t n, int32_t s, co
     TwoSampleOut o{d_tested, d_p, d_z, d_med1, d_med2, d_mean1, d_mean2, d_delta};
     const int m = n1 + n2;
     if (n1 < 3 || n2 < 3) return zero_two_sample(ctx, n, o);         // no row can be tested
-    if (m <= ST_GROUP_MAX) {                                   // (a ladder per file: the launches differ in their arguments)
-        if (m <= 8) return st_launch_group<8>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, d_strat1, d_strat2, o);
-        if (m <= 16) return st_launch_group<16>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, d_strat1, d_strat2, o);
-        if (m <= 32) return st_launch_group<32>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, d_strat1, d_strat2, o);
-        return st_launch_group<64>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, d_strat1, d_strat2, o);
-    }
+    if (m <= ST_GROUP_MAX)
+        return with_group_width(m, [&](auto width) -> int {
+            const int waves = 4;
+            const int ch = rows_per_chunk(ctx->n_cu, n);
+            const int64_t blocks = wave_launch_blocks(ctx, n, ch, waves);
+            SD_LAUNCH(ctx, "strata_group_kernel", (strata_group_kernel<decltype(width)::value>), dim3((unsigned)blocks),
+                      dim3(waves * 64), 0, d_ps, n, (int)s, d_g1, (int)n1, d_g2, (int)n2, d_strat1, d_strat2, ch, o);
+            return SDICE_OK;
+        });
     const int P = next_pow2(m, 128);
     const size_t lds = (size_t)P * 16;
     const int64_t blocks = row_launch_blocks(ctx, n);
@@ -467,23 +440,7 @@ extern "C" int sdice_ranksum_strata(sdice_ctx* ctx, int64_t n, int32_t s, const 
     SD_ARG(ctx, "ctx is NULL");
     SD_ARG(n >= 0 && s >= 0, "negative size");
     SD_ARG(g1 && g2 && strat1 && strat2, "index or stratum list is NULL");
-    {   // ranges and the one-appearance rule, before the counts are compared with s: the message names the first violation
-        if (n1 >= 1 && n1 <= ST_MAX_GROUP && n2 >= 1 && n2 <= ST_MAX_GROUP && n_strata >= 1 && n_strata <= ST_MAX_STRATA) {
-            std::vector<char> seen((size_t)s, 0);
-            const int32_t* lists[2] = {g1, g2};
-            const int32_t* strats[2] = {strat1, strat2};
-            const int32_t counts[2] = {n1, n2};
-            for (int l = 0; l < 2; ++l)
-                for (int q = 0; q < counts[l]; ++q) {
-                    const int32_t c = lists[l][q];
-                    SD_ARG(c >= 0 && c < s, "column index out of range");
-                    SD_ARG(!seen[c], "a column may appear once over both lists");
-                    seen[c] = 1;
-                    SD_ARG(strats[l][q] >= 0 && strats[l][q] < n_strata, "stratum id outside [0, n_strata)");
-                }
-        }
-    }
-    SD_TRY(st_check_counts(n1, n2, n_strata, s));
+    SD_TRY(check_two_groups(__func__, g1, n1, g2, n2, s, ST_MAX_GROUP, strat1, strat2, n_strata, ST_MAX_STRATA));
     if (n == 0) return SDICE_OK;
     SD_ARG(tested && p && med1 && med2 && mean1 && mean2 && delta, "NULL output");
     SD_ARG(ps, "ps is NULL");

@@ -42,9 +42,10 @@ def _zeros(fields, shape, k=None):
     return {name: np.zeros(sh, dt) for name, (sh, dt) in field_shapes(fields, shape, k).items()}
 
 
-def _dev_ptrs(fields, out, optional):
-    """the device pointers of a _dev call in the order of its field table; None for the field `optional` when `out` lacks it"""
-    return [out[f[0]].ptr if f[0] != optional or out.get(f[0]) else None for f in fields]
+def _dev_ptrs(fields, out, optional=()):
+    """the device pointers of a _dev call in the order of its field table; None for a field named in `optional` (a tuple)
+    when `out` lacks it"""
+    return [out[f[0]].ptr if f[0] not in optional or out.get(f[0]) else None for f in fields]
 
 
 def pair_array(pairs):
@@ -571,7 +572,7 @@ class Context:
     def ranksum_dev(self, d_ps, d_g1, d_g2, out):
         n, s = d_ps.shape
         check(self.lib.sdice_ranksum_dev(self.h, n, s, d_ps.ptr, d_g1.ptr, d_g1.shape[0], d_g2.ptr, d_g2.shape[0],
-                                         *_dev_ptrs(RANKSUM_FIELDS, out, "z")), "sdice_ranksum_dev")
+                                         *_dev_ptrs(RANKSUM_FIELDS, out, ("z",))), "sdice_ranksum_dev")
 
     def ranksum_strata_dev(self, d_ps, d_g1, d_g2, d_strat1, d_strat2, n_strata, out):
         """d_strat1, d_strat2: the device copies of the stratum ids of d_g1, d_g2 (checked by the caller: the host call
@@ -579,45 +580,45 @@ class Context:
         n, s = d_ps.shape
         check(self.lib.sdice_ranksum_strata_dev(self.h, n, s, d_ps.ptr, d_g1.ptr, d_g1.shape[0], d_g2.ptr, d_g2.shape[0],
                                                 d_strat1.ptr, d_strat2.ptr, int(n_strata),
-                                                *_dev_ptrs(RANKSUM_FIELDS, out, "z")), "sdice_ranksum_strata_dev")
+                                                *_dev_ptrs(RANKSUM_FIELDS, out, ("z",))), "sdice_ranksum_strata_dev")
 
     def ks_dev(self, d_ps, d_g1, d_g2, out, exact=False):
         """out: the device fields of KS_FIELDS (d optional; exact optional unless exact=True)"""
         n, s = d_ps.shape
-        ptrs = [out[f[0]].ptr if out.get(f[0]) else None for f in KS_FIELDS]
-        if any(p is None for f, p in zip(KS_FIELDS, ptrs) if f[0] not in ("d", "exact")):
+        optional = ("d", "exact")
+        if any(not out.get(f[0]) for f in KS_FIELDS if f[0] not in optional):
             raise ValueError("ks_dev: every field of KS_FIELDS but d and exact is required")
         check(self.lib.sdice_ks_dev(self.h, n, s, d_ps.ptr, d_g1.ptr, d_g1.shape[0], d_g2.ptr, d_g2.shape[0],
-                                    int(bool(exact)), *ptrs), "sdice_ks_dev")
+                                    int(bool(exact)), *_dev_ptrs(KS_FIELDS, out, optional)), "sdice_ks_dev")
 
     def signedrank_dev(self, d_ps, d_a, d_b, out):
         n, s = d_ps.shape
         check(self.lib.sdice_signedrank_dev(self.h, n, s, d_ps.ptr, d_a.ptr, d_b.ptr, d_a.shape[0],
-                                            *_dev_ptrs(RANKSUM_FIELDS, out, "z")), "sdice_signedrank_dev")
+                                            *_dev_ptrs(RANKSUM_FIELDS, out, ("z",))), "sdice_signedrank_dev")
 
     def ranksum_exact_dev(self, d_ps, d_g1, d_g2, out):
         """out: the device fields of RANKSUM_EXACT_FIELDS (z optional)"""
         n, s = d_ps.shape
         check(self.lib.sdice_ranksum_exact_dev(self.h, n, s, d_ps.ptr, d_g1.ptr, d_g1.shape[0], d_g2.ptr, d_g2.shape[0],
-                                               *_dev_ptrs(RANKSUM_EXACT_FIELDS, out, "z")), "sdice_ranksum_exact_dev")
+                                               *_dev_ptrs(RANKSUM_EXACT_FIELDS, out, ("z",))), "sdice_ranksum_exact_dev")
 
     def signedrank_exact_dev(self, d_ps, d_a, d_b, out):
         n, s = d_ps.shape
         check(self.lib.sdice_signedrank_exact_dev(self.h, n, s, d_ps.ptr, d_a.ptr, d_b.ptr, d_a.shape[0],
-                                                  *_dev_ptrs(RANKSUM_EXACT_FIELDS, out, "z")), "sdice_signedrank_exact_dev")
+                                                  *_dev_ptrs(RANKSUM_EXACT_FIELDS, out, ("z",))), "sdice_signedrank_exact_dev")
 
     def spearman_dev(self, d_ps, d_cols, d_xg, out):
         """d_cols, d_xg: the device copies of spearman_order()'s pair; out: device tested, p, (rho), n_kept, med, mean"""
         n, s = d_ps.shape
         check(self.lib.sdice_spearman_dev(self.h, n, s, d_ps.ptr, d_cols.ptr, d_xg.ptr, d_cols.shape[0],
-                                          *_dev_ptrs(SPEARMAN_FIELDS, out, "rho")), "sdice_spearman_dev")
+                                          *_dev_ptrs(SPEARMAN_FIELDS, out, ("rho",))), "sdice_spearman_dev")
 
     def sample_gram_dev(self, d_ps, d_cols, out):
         """d_cols: the device copy of gram_columns(); out: device shared, sum1, sum2, prod, int64 [m, m] each.  Synchronises
         once (the bad-value check of the pre-pass); the sums are queued."""
         n, s = d_ps.shape
         check(self.lib.sdice_sample_gram_dev(self.h, n, s, d_ps.ptr, d_cols.ptr, d_cols.shape[0],
-                                             *_dev_ptrs(GRAM_FIELDS, out, None)), "sdice_sample_gram_dev")
+                                             *_dev_ptrs(GRAM_FIELDS, out)), "sdice_sample_gram_dev")
 
     def kruskal_dev(self, d_ps, d_cols, set_ptr, out):
         """d_cols: the device copy of kruskal_sets()'s cols; set_ptr: its HOST offsets; out: device tested, p, (h), med and
@@ -625,7 +626,7 @@ class Context:
         n, s = d_ps.shape
         set_ptr = _c(set_ptr, np.int32)
         check(self.lib.sdice_kruskal_dev(self.h, n, s, d_ps.ptr, d_cols.ptr, _ptr(set_ptr), set_ptr.size - 1,
-                                         *_dev_ptrs(KRUSKAL_FIELDS, out, "h")), "sdice_kruskal_dev")
+                                         *_dev_ptrs(KRUSKAL_FIELDS, out, ("h",))), "sdice_kruskal_dev")
 
     def jonckheere_dev(self, d_ps, d_cols, set_ptr, out):
         """d_cols: the device copy of kruskal_sets()'s cols; set_ptr: its HOST offsets; out: device tested, p, z, (j), med and
@@ -633,7 +634,7 @@ class Context:
         n, s = d_ps.shape
         set_ptr = _c(set_ptr, np.int32)
         check(self.lib.sdice_jonckheere_dev(self.h, n, s, d_ps.ptr, d_cols.ptr, _ptr(set_ptr), set_ptr.size - 1,
-                                            *_dev_ptrs(JONCKHEERE_FIELDS, out, "j")), "sdice_jonckheere_dev")
+                                            *_dev_ptrs(JONCKHEERE_FIELDS, out, ("j",))), "sdice_jonckheere_dev")
 
     def pair_table(self, s, pairs):
         """a pair list for the _dev calls: checked against s samples, packed and uploaded once -> DeviceArray uint32[m]

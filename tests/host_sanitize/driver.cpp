@@ -3,8 +3,8 @@
 // and run by tests/test_host_sanitizers.py.  It pushes every host entry point through its threaded
 // path: table writer (3 modes) -> table reader round trip, column writer, cluster writer, junction
 // parser on the golden inputs (all file types) and the row lookup; then the argument checks of the pair
-// tests (csrc/paircheck.cpp) on both sides of their bounds.  Any ASan / UBSan / TSan report makes the
-// process exit non-zero.
+// tests (csrc/paircheck.cpp) and of the column lists (csrc/colcheck.cpp) on both sides of their bounds.
+// Any ASan / UBSan / TSan report makes the process exit non-zero.
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -16,6 +16,7 @@
 #include <vector>
 #include "sdice.h"
 #include "paircheck.h"      // splicedice_amd/csrc: the argument checks of the pair tests
+#include "colcheck.h"       //                      ... and of the column lists
 
 static char g_err[1024];
 void sdice_set_error(const char* fmt, ...) {
@@ -189,6 +190,65 @@ int main(int argc, char** argv) {
         CHECK(packed.size() == 2 && packed[0] == 0x1fff0000u && packed[1] == 0x00001fffu);
         sd_pack_pair_list(0, nullptr, packed);
         CHECK(packed.empty());
+        #undef REFUSED
+    }
+    {   // the argument checks of the column lists (csrc/colcheck.cpp) on both sides of every bound; a refusal names its cause
+        #define REFUSED(call, word) CHECK((call) == SDICE_ERR_ARG && strstr(g_err, word) && strstr(g_err, "fn: ") == g_err)
+        const int s = 9;
+        const int32_t a[3] = {0, 4, s - 1}, b[3] = {1, 2, 3}, low[3] = {6, -1, 2}, past[3] = {6, s, 2}, twice[3] = {5, 6, 5},
+                      shared[3] = {7, 4, 6};
+        CHECK(check_columns("fn", {a, b}, 3, s, "range", "once") == SDICE_OK);            // 0 and s - 1 are columns
+        CHECK(check_columns("fn", {a}, 0, 0, "range", "once") == SDICE_OK);               // nothing listed, no table
+        REFUSED(check_columns("fn", {low}, 3, s, "range", "once"), "range");
+        REFUSED(check_columns("fn", {b, past}, 3, s, "range", "once"), "range");
+        REFUSED(check_columns("fn", {twice}, 3, s, "range", "once"), "once");
+        REFUSED(check_columns("fn", {a, shared}, 3, s, "range", "once"), "once");
+        CHECK(check_columns("fn", {a}, 3, s - 1, "range", "once") == SDICE_ERR_ARG);      // s - 1 is no column of s - 1
+        // two groups of their own lengths, limit 4: the lists first, then the counts
+        const int32_t st1[3] = {0, 1, 2}, st2[3] = {2, 2, 0}, neg[3] = {0, -1, 0}, zero[3] = {0, 0, 0}, four[4] = {1, 2, 3, 5}, five[5] = {1, 2, 3, 5, 6};
+        CHECK(check_two_groups("fn", a, 3, b, 3, s, 4) == SDICE_OK);
+        CHECK(check_two_groups("fn", a, 1, four, 4, s, 4) == SDICE_OK);                   // counts 1 and the limit
+        CHECK(check_two_groups("fn", a, 3, b, 3, 6, 4) == SDICE_ERR_ARG);                 // (s - 1 = 8 is no column of 6)
+        REFUSED(check_two_groups("fn", a, 3, low, 3, s, 4), "index out of range");
+        REFUSED(check_two_groups("fn", past, 3, b, 3, s, 4), "index out of range");
+        REFUSED(check_two_groups("fn", twice, 3, b, 3, s, 4), "once over both lists");
+        REFUSED(check_two_groups("fn", a, 3, shared, 3, s, 4), "once over both lists");
+        REFUSED(check_two_groups("fn", a, 3, five, 5, s, 4), "at most 4 each");           // limit + 1: the lists are not read
+        REFUSED(check_two_groups("fn", past, 5, b, 3, s, 4), "at most 4 each");
+        REFUSED(check_two_groups("fn", a, 0, b, 3, s, 4), "each needs 1..4");
+        REFUSED(check_two_groups("fn", low, 3, b, 0, s, 4), "each needs 1..4");
+        REFUSED(check_two_groups("fn", a, -1, b, 3, s, 4), "each needs 1..4");
+        REFUSED(check_two_groups("fn", a, 3, four, 4, 6, 4), "index out of range");       // the list's fault comes first
+        REFUSED(check_two_groups("fn", b, 3, four + 3, 1, 3, 4), "index out of range");
+        REFUSED(check_two_groups("fn", nullptr, 3, nullptr, 4, 6, 4), "more selected columns than the table has");
+        CHECK(check_two_groups("fn", nullptr, 3, nullptr, 3, 6, 4) == SDICE_OK);          // device lists: the counts alone
+        // ... with stratum ids in [0, n_strata), n_strata in 1..3
+        CHECK(check_two_groups("fn", a, 3, b, 3, s, 4, st1, st2, 3, 3) == SDICE_OK);
+        CHECK(check_two_groups("fn", a, 3, b, 3, s, 4, zero, zero, 1, 3) == SDICE_OK);               // one stratum
+        REFUSED(check_two_groups("fn", a, 3, b, 3, s, 4, st1, st2, 2, 3), "stratum id outside");      // id == n_strata
+        REFUSED(check_two_groups("fn", a, 3, b, 3, s, 4, st2, neg, 3, 3), "stratum id outside");      // id -1
+        REFUSED(check_two_groups("fn", a, 3, low, 3, s, 4, neg, st2, 3, 3), "stratum id outside");    // (entry by entry, g1 first)
+        REFUSED(check_two_groups("fn", a, 3, b, 3, s, 4, st1, st2, 0, 3), "0 strata");
+        REFUSED(check_two_groups("fn", a, 3, low, 3, s, 4, neg, neg, 4, 3), "4 strata");              // (the lists are not read)
+        REFUSED(check_two_groups("fn", a, 0, b, 3, s, 4, st1, st2, 0, 3), "each needs 1..4");         // (the counts before the strata)
+        CHECK(check_two_groups("fn", nullptr, 3, nullptr, 3, s, 4, nullptr, nullptr, 3, 3) == SDICE_OK);
+        // the sets of the k-set tests
+        #undef REFUSED
+        #define REFUSED(call, word) CHECK((call) == SDICE_ERR_ARG && strstr(g_err, word))
+        std::vector<int32_t> sp(KW_MAX_SETS + 2);
+        for (int i = 0; i <= KW_MAX_SETS + 1; ++i) sp[i] = 3 * i;
+        CHECK(kw_check_sets("fn", sp.data(), 2, 6) == SDICE_OK);
+        CHECK(kw_check_sets("fn", sp.data(), KW_MAX_SETS, 3 * KW_MAX_SETS) == SDICE_OK);
+        REFUSED(kw_check_sets("fn", nullptr, 2, 6), "set_ptr is NULL");
+        REFUSED(kw_check_sets("fn", sp.data(), 1, 6), "must be 2..64");
+        REFUSED(kw_check_sets("fn", sp.data(), KW_MAX_SETS + 1, 1000), "must be 2..64");
+        REFUSED(kw_check_sets("fn", sp.data() + 1, 2, 100), "set_ptr[0] must be 0");       // (starts at 3)
+        REFUSED(kw_check_sets("fn", sp.data(), 2, 5), "more selected columns than the table has");
+        int32_t flat[4] = {0, 3, 3, 7}, back[4] = {0, 4, 3, 7}, wide[3] = {0, 3, KW_MAX_N}, wider[3] = {0, 3, KW_MAX_N + 1};
+        REFUSED(kw_check_sets("fn", flat, 3, 9), "must increase");
+        REFUSED(kw_check_sets("fn", back, 3, 9), "must increase");
+        CHECK(kw_check_sets("fn", wide, 2, KW_MAX_N) == SDICE_OK);
+        REFUSED(kw_check_sets("fn", wider, 2, KW_MAX_N + 1), "fn: 16385 selected columns");
         #undef REFUSED
     }
     printf("host sanitizer driver: ok\n");

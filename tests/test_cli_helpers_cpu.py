@@ -7,7 +7,9 @@
 - columns_in_header: manifest order, dtype, the two refusal sentences;
 - device_call / tested_rows on a context double whose arrays record free(): everything freed on success and when the
   launch raises; the compaction rule;
-- the packed all-gather layout of distributed is the rank-sum field table.
+- the packed all-gather layout of distributed is the rank-sum field table;
+- compare_sample_sets.run_with on every subset of the six flags that change the test: the refusal it prints, or that it
+  goes on to read the table.
 """
 import argparse
 import os
@@ -311,3 +313,231 @@ def test_field_shapes_gives_per_set_fields_one_row_per_set():
     assert list(shapes) == ["tested", "p", "h", "med", "mean", "delta"]
     assert shapes["med"] == ((3, 5), np.float32) and shapes["mean"] == ((3, 5), np.float32) and shapes["h"] == (5, np.float64)
     assert engine.field_shapes(engine.GRAM_FIELDS, (4, 4))["prod"] == ((4, 4), np.int64)
+
+
+# ------------------------------------------------------------------------------ compare_sample_sets: which flags go together
+CSS_FLAGS = ("--paired", "--exact", "--strata", "--trend", "--ks", "-mx")
+CSS_SUBSETS = [tuple(f for i, f in enumerate(CSS_FLAGS) if bits >> i & 1) for bits in range(1 << len(CSS_FLAGS))]
+READS_THE_TABLE = "reads the table"
+# subset of CSS_FLAGS -> the first line of stderr at exit status 1, or READS_THE_TABLE when the command gets as far as
+# read_ps_table.  Recorded from run_with before the refusals became a table (one row per test): texts and precedence are
+# that version's, byte for byte.
+CSS_OUTCOMES = {
+    (): READS_THE_TABLE,
+    ('--paired',): READS_THE_TABLE,
+    ('--exact',): READS_THE_TABLE,
+    ('--paired', '--exact'): READS_THE_TABLE,
+    ('--strata',): READS_THE_TABLE,
+    ('--paired', '--strata'):
+        'compare_sample_sets --strata: cannot be combined with --paired (the signed-rank test pairs samples '
+        'one to one). Exit.',
+    ('--exact', '--strata'):
+        'compare_sample_sets --strata: cannot be combined with --exact (there is no exact stratified test '
+        'here). Exit.',
+    ('--paired', '--exact', '--strata'):
+        'compare_sample_sets --strata: cannot be combined with --paired (the signed-rank test pairs samples '
+        'one to one). Exit.',
+    ('--trend',):
+        'compare_sample_sets --trend: needs -mx/--moreManifests (three or more ordered sets; two sets are the '
+        'rank-sum test). Exit.',
+    ('--paired', '--trend'):
+        'compare_sample_sets --trend: needs -mx/--moreManifests (three or more ordered sets; two sets are the '
+        'rank-sum test). Exit.',
+    ('--exact', '--trend'):
+        'compare_sample_sets --trend: needs -mx/--moreManifests (three or more ordered sets; two sets are the '
+        'rank-sum test). Exit.',
+    ('--paired', '--exact', '--trend'):
+        'compare_sample_sets --trend: needs -mx/--moreManifests (three or more ordered sets; two sets are the '
+        'rank-sum test). Exit.',
+    ('--strata', '--trend'):
+        'compare_sample_sets --trend: needs -mx/--moreManifests (three or more ordered sets; two sets are the '
+        'rank-sum test). Exit.',
+    ('--paired', '--strata', '--trend'):
+        'compare_sample_sets --trend: needs -mx/--moreManifests (three or more ordered sets; two sets are the '
+        'rank-sum test). Exit.',
+    ('--exact', '--strata', '--trend'):
+        'compare_sample_sets --trend: needs -mx/--moreManifests (three or more ordered sets; two sets are the '
+        'rank-sum test). Exit.',
+    ('--paired', '--exact', '--strata', '--trend'):
+        'compare_sample_sets --trend: needs -mx/--moreManifests (three or more ordered sets; two sets are the '
+        'rank-sum test). Exit.',
+    ('--ks',): READS_THE_TABLE,
+    ('--paired', '--ks'):
+        'compare_sample_sets --ks: cannot be combined with --paired (the signed-rank test compares matched '
+        'samples; this test compares two distributions). Exit.',
+    ('--exact', '--ks'): READS_THE_TABLE,
+    ('--paired', '--exact', '--ks'):
+        'compare_sample_sets --ks: cannot be combined with --paired (the signed-rank test compares matched '
+        'samples; this test compares two distributions). Exit.',
+    ('--strata', '--ks'):
+        'compare_sample_sets --ks: cannot be combined with --strata (there is no stratified '
+        'Kolmogorov-Smirnov test here). Exit.',
+    ('--paired', '--strata', '--ks'):
+        'compare_sample_sets --ks: cannot be combined with --paired (the signed-rank test compares matched '
+        'samples; this test compares two distributions). Exit.',
+    ('--exact', '--strata', '--ks'):
+        'compare_sample_sets --ks: cannot be combined with --strata (there is no stratified '
+        'Kolmogorov-Smirnov test here). Exit.',
+    ('--paired', '--exact', '--strata', '--ks'):
+        'compare_sample_sets --ks: cannot be combined with --paired (the signed-rank test compares matched '
+        'samples; this test compares two distributions). Exit.',
+    ('--trend', '--ks'):
+        'compare_sample_sets --ks: cannot be combined with --trend (the trend test orders three or more '
+        'sets). Exit.',
+    ('--paired', '--trend', '--ks'):
+        'compare_sample_sets --ks: cannot be combined with --paired (the signed-rank test compares matched '
+        'samples; this test compares two distributions). Exit.',
+    ('--exact', '--trend', '--ks'):
+        'compare_sample_sets --ks: cannot be combined with --trend (the trend test orders three or more '
+        'sets). Exit.',
+    ('--paired', '--exact', '--trend', '--ks'):
+        'compare_sample_sets --ks: cannot be combined with --paired (the signed-rank test compares matched '
+        'samples; this test compares two distributions). Exit.',
+    ('--strata', '--trend', '--ks'):
+        'compare_sample_sets --ks: cannot be combined with --trend (the trend test orders three or more '
+        'sets). Exit.',
+    ('--paired', '--strata', '--trend', '--ks'):
+        'compare_sample_sets --ks: cannot be combined with --paired (the signed-rank test compares matched '
+        'samples; this test compares two distributions). Exit.',
+    ('--exact', '--strata', '--trend', '--ks'):
+        'compare_sample_sets --ks: cannot be combined with --trend (the trend test orders three or more '
+        'sets). Exit.',
+    ('--paired', '--exact', '--strata', '--trend', '--ks'):
+        'compare_sample_sets --ks: cannot be combined with --paired (the signed-rank test compares matched '
+        'samples; this test compares two distributions). Exit.',
+    ('-mx',): READS_THE_TABLE,
+    ('--paired', '-mx'):
+        'compare_sample_sets --paired: cannot be combined with -mx/--moreManifests (the signed-rank test '
+        'compares two matched sets). Exit.',
+    ('--exact', '-mx'):
+        'compare_sample_sets --exact: cannot be combined with -mx/--moreManifests (there is no exact '
+        'Kruskal-Wallis test here). Exit.',
+    ('--paired', '--exact', '-mx'):
+        'compare_sample_sets --exact: cannot be combined with -mx/--moreManifests (there is no exact '
+        'Kruskal-Wallis test here). Exit.',
+    ('--strata', '-mx'):
+        'compare_sample_sets --strata: cannot be combined with -mx/--moreManifests (there is no stratified '
+        'Kruskal-Wallis test here). Exit.',
+    ('--paired', '--strata', '-mx'):
+        'compare_sample_sets --strata: cannot be combined with --paired (the signed-rank test pairs samples '
+        'one to one). Exit.',
+    ('--exact', '--strata', '-mx'):
+        'compare_sample_sets --exact: cannot be combined with -mx/--moreManifests (there is no exact '
+        'Kruskal-Wallis test here). Exit.',
+    ('--paired', '--exact', '--strata', '-mx'):
+        'compare_sample_sets --exact: cannot be combined with -mx/--moreManifests (there is no exact '
+        'Kruskal-Wallis test here). Exit.',
+    ('--trend', '-mx'): READS_THE_TABLE,
+    ('--paired', '--trend', '-mx'):
+        'compare_sample_sets --trend: cannot be combined with --paired (the signed-rank test compares two '
+        'matched sets). Exit.',
+    ('--exact', '--trend', '-mx'):
+        'compare_sample_sets --trend: cannot be combined with --exact (the trend test is asymptotic only). '
+        'Exit.',
+    ('--paired', '--exact', '--trend', '-mx'):
+        'compare_sample_sets --trend: cannot be combined with --paired (the signed-rank test compares two '
+        'matched sets). Exit.',
+    ('--strata', '--trend', '-mx'):
+        'compare_sample_sets --trend: cannot be combined with --strata (there is no stratified trend test '
+        'here). Exit.',
+    ('--paired', '--strata', '--trend', '-mx'):
+        'compare_sample_sets --trend: cannot be combined with --paired (the signed-rank test compares two '
+        'matched sets). Exit.',
+    ('--exact', '--strata', '--trend', '-mx'):
+        'compare_sample_sets --trend: cannot be combined with --exact (the trend test is asymptotic only). '
+        'Exit.',
+    ('--paired', '--exact', '--strata', '--trend', '-mx'):
+        'compare_sample_sets --trend: cannot be combined with --paired (the signed-rank test compares two '
+        'matched sets). Exit.',
+    ('--ks', '-mx'):
+        'compare_sample_sets --ks: cannot be combined with -mx/--moreManifests (there is no k-sample '
+        'Kolmogorov-Smirnov test here). Exit.',
+    ('--paired', '--ks', '-mx'):
+        'compare_sample_sets --ks: cannot be combined with --paired (the signed-rank test compares matched '
+        'samples; this test compares two distributions). Exit.',
+    ('--exact', '--ks', '-mx'):
+        'compare_sample_sets --ks: cannot be combined with -mx/--moreManifests (there is no k-sample '
+        'Kolmogorov-Smirnov test here). Exit.',
+    ('--paired', '--exact', '--ks', '-mx'):
+        'compare_sample_sets --ks: cannot be combined with --paired (the signed-rank test compares matched '
+        'samples; this test compares two distributions). Exit.',
+    ('--strata', '--ks', '-mx'):
+        'compare_sample_sets --ks: cannot be combined with -mx/--moreManifests (there is no k-sample '
+        'Kolmogorov-Smirnov test here). Exit.',
+    ('--paired', '--strata', '--ks', '-mx'):
+        'compare_sample_sets --ks: cannot be combined with --paired (the signed-rank test compares matched '
+        'samples; this test compares two distributions). Exit.',
+    ('--exact', '--strata', '--ks', '-mx'):
+        'compare_sample_sets --ks: cannot be combined with -mx/--moreManifests (there is no k-sample '
+        'Kolmogorov-Smirnov test here). Exit.',
+    ('--paired', '--exact', '--strata', '--ks', '-mx'):
+        'compare_sample_sets --ks: cannot be combined with --paired (the signed-rank test compares matched '
+        'samples; this test compares two distributions). Exit.',
+    ('--trend', '--ks', '-mx'):
+        'compare_sample_sets --ks: cannot be combined with --trend (the trend test orders three or more '
+        'sets). Exit.',
+    ('--paired', '--trend', '--ks', '-mx'):
+        'compare_sample_sets --ks: cannot be combined with --paired (the signed-rank test compares matched '
+        'samples; this test compares two distributions). Exit.',
+    ('--exact', '--trend', '--ks', '-mx'):
+        'compare_sample_sets --ks: cannot be combined with --trend (the trend test orders three or more '
+        'sets). Exit.',
+    ('--paired', '--exact', '--trend', '--ks', '-mx'):
+        'compare_sample_sets --ks: cannot be combined with --paired (the signed-rank test compares matched '
+        'samples; this test compares two distributions). Exit.',
+    ('--strata', '--trend', '--ks', '-mx'):
+        'compare_sample_sets --ks: cannot be combined with --trend (the trend test orders three or more '
+        'sets). Exit.',
+    ('--paired', '--strata', '--trend', '--ks', '-mx'):
+        'compare_sample_sets --ks: cannot be combined with --paired (the signed-rank test compares matched '
+        'samples; this test compares two distributions). Exit.',
+    ('--exact', '--strata', '--trend', '--ks', '-mx'):
+        'compare_sample_sets --ks: cannot be combined with --trend (the trend test orders three or more '
+        'sets). Exit.',
+    ('--paired', '--exact', '--strata', '--trend', '--ks', '-mx'):
+        'compare_sample_sets --ks: cannot be combined with --paired (the signed-rank test compares matched '
+        'samples; this test compares two distributions). Exit.',
+}
+
+
+class _ReadsTheTable(Exception):
+    pass
+
+
+def _css_outcome(flags, tmp_path, monkeypatch, capsys):
+    """run_with on three sets of three samples, a label file and a header-only table; read_ps_table raises the sentinel"""
+    from splicedice_amd import compare_sample_sets as css
+    sets = [[f"s{3 * g + i}" for i in range(3)] for g in range(3)]
+    paths = []
+    for g, names in enumerate(sets):
+        paths.append(tmp_path / f"m{g + 1}.txt")
+        paths[-1].write_text("".join(f"{name}\tbam\n" for name in names))
+    strata = tmp_path / "strata.tsv"
+    strata.write_text("".join(f"{name}\tbatch{i % 2}\n" for names in sets for i, name in enumerate(names)))
+    table = tmp_path / "in_allPS.tsv"
+    table.write_text("\t".join(["cluster"] + [name for names in sets for name in names]) + "\n")
+
+    def reads_the_table(*a, **k):
+        raise _ReadsTheTable()
+
+    monkeypatch.setattr(css, "read_ps_table", reads_the_table)
+    for name in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(name, raising=False)
+    args = argparse.Namespace(psiSPLICEDICE=str(table), manifest1=str(paths[0]), manifest2=str(paths[1]),
+                              moreManifests=[str(paths[2])] if "-mx" in flags else None, paired="--paired" in flags,
+                              exact="--exact" in flags, strata=str(strata) if "--strata" in flags else None,
+                              trend="--trend" in flags, ks="--ks" in flags, annotation="", outputFile=str(tmp_path / "out.tsv"))
+    try:
+        css.run_with(args, ctx=object())
+    except _ReadsTheTable:
+        return READS_THE_TABLE
+    except SystemExit as e:
+        assert e.code == 1
+        return capsys.readouterr().err.splitlines()[0]
+    raise AssertionError("run_with returned without reading the table")
+
+
+@pytest.mark.parametrize("flags", CSS_SUBSETS, ids=lambda f: "+".join(f) or "plain")
+def test_compare_sample_sets_refuses_or_runs_every_flag_combination_as_before(flags, tmp_path, monkeypatch, capsys):
+    assert _css_outcome(flags, tmp_path, monkeypatch, capsys) == CSS_OUTCOMES[flags]
+    assert not (tmp_path / "out.tsv").exists()

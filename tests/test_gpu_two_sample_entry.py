@@ -1,4 +1,4 @@
-"""The host code that the five two-sample entry points share (rowsum.h: zero_two_sample, TwoSampleStaging; engine.py: the
+"""The host code that the two-sample entry points share (rowsum.h: zero_two_sample, TwoSampleStaging; engine.py: the
 pointer list of a _dev call), through the engine, at the smallest shapes where it can go wrong: n = 131 rows (no
 multiple of 64).
 
@@ -6,20 +6,23 @@ multiple of 64).
   that held 0xAA, with z passed and without; a z buffer that is not passed keeps its 0xAA.
 * The host form gives the _dev form's bytes in every field: 3-decimal values with about 10 % NaN, a row of NaNs and an
   off-grid row, at 3 v 4 columns (3 pairs: the lane and lane-group kernels) and at 40 v 30 columns (70 pairs: the
-  workgroup-per-row kernels of signedrank.hip and strata.hip, the 64-lane rank-sum path).  Stratum ids are column % 3."""
+  workgroup-per-row kernels of signedrank.hip, strata.hip and ks.hip, the 64-lane rank-sum path).  Stratum ids are
+  column % 3.  sdice_ks (`ks`, and `ks_exact` = exact=True): d rides in the z slot, `exact` is an output of both."""
 import numpy as np
 import pytest
 
-from splicedice_amd.engine import RANKSUM_EXACT_FIELDS, RANKSUM_FIELDS
+from splicedice_amd.engine import KS_FIELDS, RANKSUM_EXACT_FIELDS, RANKSUM_FIELDS
 
 gpu = pytest.mark.gpu
 
 N = 131
-ENTRIES = ("ranksum", "ranksum_exact", "ranksum_strata", "signedrank", "signedrank_exact")
+ENTRIES = ("ranksum", "ranksum_exact", "ranksum_strata", "signedrank", "signedrank_exact", "ks", "ks_exact")
 SHAPES = ((3, 4, 3), (40, 30, 70))          # group 1, group 2, pairs
 
 
 def fields_of(entry):
+    if entry.startswith("ks"):
+        return KS_FIELDS
     return RANKSUM_EXACT_FIELDS if entry.endswith("_exact") else RANKSUM_FIELDS
 
 
@@ -34,8 +37,16 @@ def lists_of(entry, n1, n2, m):
 def call_dev(ctx, entry, d_ps, d_lists, out):
     if entry == "ranksum_strata":
         ctx.ranksum_strata_dev(d_ps, *d_lists, 3, out)
+    elif entry.startswith("ks"):
+        ctx.ks_dev(d_ps, *d_lists, out, exact=entry == "ks_exact")
     else:
         getattr(ctx, entry + "_dev")(d_ps, *d_lists, out)
+
+
+def call_host(ctx, entry, ps, lists):
+    if entry.startswith("ks"):
+        return ctx.ks(ps, *lists, exact=entry == "ks_exact")
+    return getattr(ctx, entry)(ps, *lists)
 
 
 def device_fields(ctx, entry, byte):
@@ -60,9 +71,10 @@ def test_nothing_testable_zeroes_every_field(ctx, entry, with_z):
     d_ps = ctx.to_device(ps)
     d_lists = [ctx.to_device(v) for v in lists_of(entry, 2, 5, 2)]
     out = device_fields(ctx, entry, 0xAA)
-    d_z = out["z"]
+    z = "d" if entry.startswith("ks") else "z"
+    d_z = out[z]
     if not with_z:
-        del out["z"]
+        del out[z]
     call_dev(ctx, entry, d_ps, d_lists, out)
     for name, d in out.items():
         assert not np.frombuffer(d.to_host().tobytes(), np.uint8).any(), name
@@ -78,7 +90,7 @@ def test_nothing_testable_zeroes_every_field(ctx, entry, with_z):
 def test_host_form_gives_the_dev_form_bytes(ctx, entry, shape):
     ps = make_table(*shape)
     lists = lists_of(entry, *shape)
-    host = getattr(ctx, entry)(ps, *lists)
+    host = call_host(ctx, entry, ps, lists)
     d_ps = ctx.to_device(ps)
     d_lists = [ctx.to_device(v) for v in lists]
     out = device_fields(ctx, entry, 0xAA)
