@@ -577,7 +577,9 @@ int sdice_sort_unique_u64(sdice_ctx* ctx, int64_t n, uint64_t* keys_inout, int64
 /* ---- K8: `similarity` scoring (similarity.py:25-47).  For every row with sign != 0 (event
  * significant in the comparison table: p <= 0.05 and delta != 0, similarity.py:13-20) and every
  * column with a non-NaN PS: counts[c] += 1; scores[c] += (ps < mid) if sign < 0 else (ps > mid).
- * PS and midpoints are float64: the reference compares Python floats parsed from both tables. */
+ * PS and midpoints are float64: the reference compares Python floats parsed from both tables.
+ * The _dev call zeroes d_scores / d_counts before it adds (s == 0: nothing is written).  NULL ctx, a negative size, a
+ * NULL output with s > 0 or a NULL input with n > 0: SDICE_ERR_ARG before anything is written. */
 int sdice_similarity(sdice_ctx* ctx, int64_t n, int32_t s, const double* ps, const double* mid, const int8_t* sign,
                      int64_t* scores, int64_t* counts);
 int sdice_similarity_dev(sdice_ctx* ctx, int64_t n, int32_t s, const double* d_ps, const double* d_mid,
@@ -586,7 +588,11 @@ int sdice_similarity_dev(sdice_ctx* ctx, int64_t n, int32_t s, const double* d_p
 /* ---- K9: per-row np.nanmean / np.nanstd over k selected columns (findOutliers.py:125-135), in the
  * matrix's own dtype (0 float32, 1 float64), bit-identical to numpy: NaNs replaced by zero in place,
  * numpy's pairwise summation, both divisions by the valid count in float64 then rounded.
- * mean / std are arrays of that dtype, n_nan the number of NaNs among the selected columns. */
+ * mean / std are arrays of that dtype, n_nan the number of NaNs among the selected columns.  Bit-identical means NaN
+ * where numpy has NaN and numpy's bit pattern everywhere else, the sign of a zero included (np.sum starts from +0).
+ * idx may be in any order and repeat a column: the sums run in idx order, as numpy's r[idx] does.  1 <= k <= 1024,
+ * dtype 0 or 1, no NULL pointer with n > 0 (the host call also checks 0 <= idx < s); otherwise SDICE_ERR_ARG before any
+ * launch, outputs untouched. */
 int sdice_rowstats(sdice_ctx* ctx, int64_t n, int32_t s, const void* data, int dtype, const int32_t* idx, int32_t k,
                    void* mean, void* std_, int32_t* n_nan);
 int sdice_rowstats_dev(sdice_ctx* ctx, int64_t n, int32_t s, const void* d_data, int dtype, const int32_t* d_idx,

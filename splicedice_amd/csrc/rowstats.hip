@@ -6,7 +6,8 @@
 //   mean = T(f64(pairwise_sum(x0)) / f64(cnt)),
 //   std  = sqrt(T(f64(pairwise_sum(d*d)) / f64(cnt))),  d = (x0 - mean) with the NaN slots back at zero,
 // where pairwise_sum is numpy's 8-accumulator / halving summation in T and the two divisions run in
-// float64 (a float32 value divided by an integer count promotes) before rounding to T.
+// float64 (a float32 value divided by an integer count promotes) before rounding to T.  np.sum starts
+// from +0 (0 + pairwise_sum(x)), so a row of -0.0 alone has the mean +0.0: the tree's result is added to +0.
 //
 // One wave per row, K <= 1024 selected columns; the K values sit in LDS, the sum uses the same
 // lane = leaf * 8 + accumulator layout as the rank-sum kernels (ranksum.hip).
@@ -113,7 +114,7 @@ __global__ void __launch_bounds__(256) rowstats_kernel(const T* __restrict__ dat
         }
         RS_WAVE_SYNC();
         const double cnt = (double)(K - n_nan);
-        const T sum1 = rs_wave_sum<T>(C, K, lane, leaf_off, nl, leaf_sum);
+        const T sum1 = (T)0 + rs_wave_sum<T>(C, K, lane, leaf_off, nl, leaf_sum);
         const T avg = (T)((double)sum1 / cnt);
         for (int k0 = 0; k0 < K; k0 += 64) {
             const int k = k0 + lane;
@@ -124,7 +125,7 @@ __global__ void __launch_bounds__(256) rowstats_kernel(const T* __restrict__ dat
             }
         }
         RS_WAVE_SYNC();
-        const T sum2 = rs_wave_sum<T>(C, K, lane, leaf_off, nl, leaf_sum);
+        const T sum2 = (T)0 + rs_wave_sum<T>(C, K, lane, leaf_off, nl, leaf_sum);
         const T var = (T)((double)sum2 / cnt);
         if (lane == 0) {
             mean_out[row] = avg;

@@ -48,11 +48,11 @@ extern "C" int sdice_similarity_dev(sdice_ctx* ctx, int64_t n, int32_t s, const 
     SD_ARG(n >= 0 && s >= 0, "negative size");
     if (s == 0) return SDICE_OK;
     SD_ARG(d_scores && d_counts, "NULL output");
+    SD_ARG(n == 0 || (d_ps && d_mid && d_sign), "NULL input");      // (before the outputs are zeroed: a refusal leaves them)
     SD_HIP(hipSetDevice(ctx->device));
     SD_HIP(hipMemsetAsync(d_scores, 0, (size_t)s * 8, ctx->stream));
     SD_HIP(hipMemsetAsync(d_counts, 0, (size_t)s * 8, ctx->stream));
     if (n == 0) return SDICE_OK;
-    SD_ARG(d_ps && d_mid && d_sign, "NULL input");
     int64_t blocks = (int64_t)ctx->n_cu * 8;
     int64_t rows = sd_ceil_div(n, blocks);
     if (rows < 16) rows = 16;

@@ -669,6 +669,21 @@ class Context:
         """BH down the columns of rows x cols values whose rows are `pitch` elements apart (a column range of a wider table)"""
         check(self.lib.sdice_bh_columns_pitched_dev(self.h, int(n), int(cols), int(pitch), d_p.ptr), "sdice_bh_columns_pitched_dev")
 
+    def similarity_dev(self, d_ps, d_mid, d_sign, d_scores, d_counts):
+        """d_ps float64 [n, s], d_mid float64 [n], d_sign int8 [n]; d_scores / d_counts int64 [s] are zeroed by the call and
+        then added to (queued on the context stream)"""
+        n, s = d_ps.shape
+        check(self.lib.sdice_similarity_dev(self.h, n, s, d_ps.ptr, d_mid.ptr, d_sign.ptr, d_scores.ptr, d_counts.ptr),
+              "sdice_similarity_dev")
+
+    def rowstats_dev(self, d_data, d_idx, d_mean, d_std, d_nan):
+        """d_data float32 / float64 [n, s], d_idx int32 [k]; d_mean / d_std [n] of d_data's dtype, d_nan int32 [n]"""
+        n, s = d_data.shape
+        if d_data.dtype not in (np.float32, np.float64):
+            raise TypeError(f"rowstats_dev: unsupported dtype {d_data.dtype}")
+        check(self.lib.sdice_rowstats_dev(self.h, n, s, d_data.ptr, 0 if d_data.dtype == np.float32 else 1, d_idx.ptr,
+                                          d_idx.shape[0], d_mean.ptr, d_std.ptr, d_nan.ptr), "sdice_rowstats_dev")
+
     def comm_fork(self):
         check(self.lib.sdice_comm_fork(self.h), "sdice_comm_fork")
 

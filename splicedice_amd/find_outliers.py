@@ -12,7 +12,13 @@ thresholds and the report are applied here exactly as the reference does (findOu
   * z = (value - mean) / std in the matrix dtype; a line is printed when z >= --outlierCutoff and
     |z - mean| >= --outlierCutoff  (the reference compares the z-score, not delta-PS, with the
     second threshold and never reads --dpsiThrsh; kept as is)
-  * line: event, sample, z, value, mean, std separated by tabs, numpy scalar formatting
+  * line: event, sample, z, value, mean, std separated by tabs, numpy scalar formatting; the value of an
+    integer matrix is printed as stored (1, not 1.0)
+
+Known divergence: a matrix that is neither float32 nor float64 is converted to float64 before the statistics.  For an
+integer matrix that is what numpy does anyway and the lines are the reference's.  A float16 matrix the reference takes
+through np.nanmean / np.nanstd and the z division in float16, so its lines carry float16 digits and, next to a
+threshold, can be other lines than the float64 ones printed here (tests/test_scoring_cpu.py pins the float64 lines).
 """
 import sys
 
@@ -71,12 +77,12 @@ def run_with(args, ctx=None):
         print("Less than 10 samples detected in null group. Too few. Exit.", file=sys.stderr)
         sys.exit(1)
     data = load_matrix(args.psiSPLICEDICE)
-    cols, rows, matrix = data["cols"], data["rows"], data["data"]
+    cols, rows, stored = data["cols"], data["rows"], data["data"]
     null_idx = np.flatnonzero(np.isin(cols, null))
     sample_idx = np.flatnonzero(np.isin(cols, samples))
-    if matrix.dtype not in (np.float32, np.float64):
-        matrix = matrix.astype(np.float64)
+    matrix = stored if stored.dtype in (np.float32, np.float64) else stored.astype(np.float64)
+    shown = stored if stored.dtype.kind in "iu" else matrix
     with engine_scope(ctx, lambda: Context(0)) as ctx:
         ev, pos, z, mean, std = find_hits(ctx, matrix, null_idx, sample_idx, args.outlierCutoff)
     for e, p in zip(ev.tolist(), pos.tolist()):
-        print(rows[e], cols[sample_idx[p]], z[e, p], matrix[e, sample_idx[p]], mean[e], std[e], sep="\t")
+        print(rows[e], cols[sample_idx[p]], z[e, p], shown[e, sample_idx[p]], mean[e], std[e], sep="\t")

@@ -8,7 +8,8 @@ reading and writing rules (splicedice/similarity.py, line numbers below):
   comparison table (:5-21)  first line skipped; an event is used unless float(p-value) > 0.05 or
                             delta == 0; its midpoint is median1 - delta/2 on Python floats of the text
   PS table (:24-47)         events absent from the comparison are ignored, "nan" fields do not count;
-                            delta < 0 scores ps < midpoint, delta > 0 scores ps > midpoint
+                            delta < 0 scores ps < midpoint, delta > 0 scores ps > midpoint; a delta that reads as
+                            NaN passes the cut-off above and is then neither scored nor counted (sign 0)
   output (:57-66)           samples ordered by (score, name, count) descending; one line
                             name[<TAB>group1<TAB>group2]<TAB>score/count as 0.03f<TAB>score<TAB>count;
                             with a manifest only the samples it names; count == 0 raises
@@ -46,7 +47,7 @@ def row_parameters(names, events):
         hit = events.get(name)
         if hit is not None:
             mid[i] = hit[0]
-            sign[i] = 1 if hit[1] > 0 else -1
+            sign[i] = (hit[1] > 0) - (hit[1] < 0)
     return mid, sign
 
 
