@@ -24,13 +24,17 @@
 //                          {chrom, left, right<<1|strand, input index} elements in LDS (buckets
 //                          beyond the LDS capacity are sorted in place in HBM by the same code);
 //                          writes the row-order arrays, row_of, and 64-row maxima of `right`
-//   neighbours_kernel      one tile of rows per workgroup: window of the row arrays in LDS, count
-//                          walk, workgroup scan, decoupled look-back over the tiles for the global
-//                          offset (8-byte {flag, value} granules, agent-scope relaxed atomics),
-//                          fill walk into an LDS stage, contiguous stores of row_ptr and col
+//   neighbours_kernel      one tile of rows per workgroup: window of the row arrays in LDS, the later
+//                          neighbours of a row by binary search (they are a contiguous run), the
+//                          number of earlier ones by symmetry (histogram of the run ends + scan),
+//                          their list by a walk that ends after that many hits, workgroup scan,
+//                          decoupled look-back over the tiles for the global offset (8-byte
+//                          {flag, value} granules, agent-scope relaxed atomics), lists into an LDS
+//                          stage, contiguous stores of row_ptr and col
 //
-// The backward walk ends at the first row whose left + (maximum junction length) is below the
-// target and skips 64-row blocks whose maximum `right` is below it.
+// Walks outside the window (global memory): the backward one ends at the first row whose left +
+// (maximum junction length) is below the target and skips 64-row blocks whose maximum `right` is
+// below it.
 //
 // Nothing is read back by the host inside the chain: validation results, the total list length and
 // the neighbour reach live in a device status block that is fetched when the caller asks for nnz (or
@@ -707,9 +711,9 @@ struct NbCfg {
     static constexpr int HB = 256;             // rows staged before the tile
     static constexpr int HF = 128;             // rows staged after it
     static constexpr int W = T + HB + HF;
-    static constexpr int STAGE = 11 * T;       // list entries staged in LDS per tile (11, not 12: 40 120 B per workgroup -> FOUR per CU)
-    static constexpr int KMAX = 16;            // entries a row keeps from its (single) walk, as 16-bit row distances
-    static constexpr int WIN_WORDS = 6 * W;    // cL, running maximum (64 bit each), right, window index + position (16 bit each)
+    static constexpr int STAGE = 11 * T;       // list entries staged in LDS per tile (11, not 12: 40 768 B per workgroup -> FOUR per CU)
+    static constexpr int KMAX = 16;            // EARLIER neighbours a row keeps from its walk, as 16-bit row distances
+    static constexpr int WIN_WORDS = 4 * W;    // cL (64 bit), histogram / prefix (32 bit), forward extent + position (16 bit each)
     static constexpr int UNION_WORDS = WIN_WORDS > STAGE ? WIN_WORDS : STAGE;
 };
 
@@ -741,26 +745,29 @@ __global__ void __launch_bounds__(T, 8) neighbours_kernel(FastArgs a) {      // 
     typedef NbCfg<T> Cfg;
     constexpr int W = Cfg::W, KMAX = Cfg::KMAX;
     constexpr int EPT = (W + T - 1) / T;       // window rows per thread while the window is built
-    // The window [wlo, whi) is held COMPACTED BY STRAND, so that a walk only ever visits rows of its own
-    // strand (half the visits of a walk over the interleaved rows): the '+' rows fill the arrays from the
-    // front in row order, the '-' rows from the back in reverse order, position k holds
-    //   cL[k]  = (chrom - chrom[window start]) << 32 | left      forward walks end at cL > (c << 32 | right)
-    //   pm[k]  = running maximum over the window rows of this strand up to this one of (chrom - ..) << 32 | right:
-    //            a backward walk for (c, left) ends at the first row with pm < (c << 32 | left) -- nothing at
-    //            or before it (of this chromosome and strand) reaches `left`
-    //   wR[k]  = right,  rid[k] = window index of the row,  pos[i] = position of window row i.
-    // The same LDS is the list stage afterwards.
+    static_assert(EPT == 2, "the '-' counts of a wave's two sets of window rows are summed as one packed word");
+    // The window [wlo, whi) is held COMPACTED BY STRAND: the '+' rows fill the arrays from the front in row
+    // order, the '-' rows from the back in reverse order.  With u = the index of a row inside its strand
+    // (0 = the strand's first window row), position k holds
+    //   cL[k]  = (chrom - chrom[window start]) << 32 | left, ascending in u: the later neighbours of a row with
+    //            tf = (chrom, right) are exactly the rows u + 1 .. f, f = the last u with cL <= tf (a binary search),
+    //   fu[k]  = that f (clamped at the strand's last window row), for every row up to the tile's last,
+    //   hs[k]  = how many rows of the strand have f + 1 == (the u of position k), then the running sum of it in
+    //            position order: the earlier neighbours of a row are the q < u with f(q) >= u, and their number is
+    //            u - #{q : f(q) < u}.  (An earlier row of another chromosome has tf < cL of this one, so the one
+    //            comparison covers the chromosome test.)
+    //   rid[k] = window index of the row,  pos[i] = position of window row i.
+    // The same LDS is the list stage afterwards, except rid: the later neighbours go from it straight into the stage.
     __shared__ __align__(16) uint32_t u_mem[Cfg::UNION_WORDS];
-    __shared__ int16_t tmp[(KMAX + 1) * T];     // (row KMAX is a dummy target for non-hits)
+    __shared__ int16_t tmp[KMAX * T];
+    __shared__ uint16_t rid[W];
     __shared__ uint32_t wsum[T / 64];
-    __shared__ unsigned long long wmax0[T / 64], wmax1[T / 64];
     __shared__ uint32_t s_misc[4];             // [1] maxlen, [2] reach
     __shared__ unsigned long long s_base;
     unsigned long long* cL = reinterpret_cast<unsigned long long*>(u_mem);
-    unsigned long long* pm = cL + W;
-    uint32_t* wR = reinterpret_cast<uint32_t*>(pm + W);
-    uint16_t* rid = reinterpret_cast<uint16_t*>(wR + W);
-    uint16_t* pos = rid + W;
+    uint32_t* hs = reinterpret_cast<uint32_t*>(cL + W);
+    uint16_t* fu = reinterpret_cast<uint16_t*>(hs + W);
+    uint16_t* pos = fu + W;
     int32_t* stage = reinterpret_cast<int32_t*>(u_mem);
     const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
     const int n = (int)a.n;
@@ -772,6 +779,12 @@ __global__ void __launch_bounds__(T, 8) neighbours_kernel(FastArgs a) {      // 
     __shared__ int s_tile;
     unsigned long long* ticket = a.tile_state + n_tiles;
     if (t == 0) s_tile = failed_chain ? (int)blockIdx.x : (int)atomicAdd(ticket, 1ull);
+    if (t < 64) {                              // the longest junction of the chain: the same for every tile
+        unsigned long long m = t < SB_SLOTS ? a.sb[SB_MAXLEN + t] : 0ull;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const unsigned long long y = __shfl_xor(m, o); m = y > m ? y : m; }
+        if (t == 0) s_misc[1] = (uint32_t)m;
+    }
     __syncthreads();
 #pragma nounroll
     for (int tile = s_tile; tile < n_tiles;) {
@@ -785,154 +798,163 @@ __global__ void __launch_bounds__(T, 8) neighbours_kernel(FastArgs a) {      // 
         continue;
     }
     if (t == 0) s_misc[2] = 0;
-    if (t < 64) {
-        unsigned long long m = t < SB_SLOTS ? a.sb[SB_MAXLEN + t] : 0ull;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { const unsigned long long y = __shfl_xor(m, o); m = y > m ? y : m; }
-        if (t == 0) s_misc[1] = (uint32_t)m;
-    }
     const int wlo = max(0, t0 - Cfg::HB), whi = min(n, t0 + nr + Cfg::HF);
     const int wn = whi - wlo;
+    const int n_srch = t0 + nr - wlo;          // window rows [0, n_srch) need their forward extent (the front halo does not)
     const uint32_t c0w = a.rowC[wlo];
     const uint32_t l0w = a.rowL[wlo];
     const int64_t cap = a.col_cap;
     int n1 = 0;                                // '-' rows in the window
+    unsigned long long tfw[EPT];               // (chrom, right) of this thread's window rows t, t + T
+    uint32_t strw[EPT];                        // ... and their strands
     {
-        // thread t builds window rows t*EPT .. (read straight from the row arrays): scan of the '-' count
-        // (position inside the strand) and of the two running maxima, then the compacted stores
-        unsigned long long comp[EPT], own_cl[EPT], r0 = 0, r1 = 0;
-        uint32_t rr[EPT], str[EPT], c1 = 0;
-        unsigned long long v0[EPT], v1[EPT];
-        uint32_t cb[EPT];
+        // thread t builds window rows t and t + T (read straight from the row arrays): count of the '-' rows before
+        // each (its index inside the strand) by ballot, then the compacted stores
+        unsigned long long own_cl[EPT];
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
-            const int i = t * EPT + e;
-            comp[e] = 0; own_cl[e] = 0; rr[e] = 0; str[e] = 0;
-            cb[e] = c1;
+            const int i = t + e * T;
+            own_cl[e] = 0; tfw[e] = 0; strw[e] = 0;
             if (i < wn) {
                 const uint32_t rc = a.rowC[wlo + i] - c0w, r2 = a.rowR2[wlo + i];
                 own_cl[e] = ((unsigned long long)rc << 32) | a.rowL[wlo + i];
-                rr[e] = r2 >> 1; str[e] = r2 & 1u;
-                comp[e] = ((unsigned long long)rc << 32) | rr[e];
-                if (str[e]) { r1 = comp[e] > r1 ? comp[e] : r1; ++c1; } else { r0 = comp[e] > r0 ? comp[e] : r0; }
+                tfw[e] = ((unsigned long long)rc << 32) | (r2 >> 1);
+                strw[e] = r2 & 1u;
             }
-            v0[e] = r0; v1[e] = r1;
         }
-        unsigned long long x0 = r0, x1 = r1;
-        uint32_t xc = c1;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long y0 = __shfl_up(x0, o), y1 = __shfl_up(x1, o);
-            const uint32_t yc = __shfl_up(xc, o);
-            if (lane >= o) { x0 = y0 > x0 ? y0 : x0; x1 = y1 > x1 ? y1 : x1; xc += yc; }
-        }
-        if (lane == 63) { wmax0[w] = x0; wmax1[w] = x1; wsum[w] = xc; }
+        const unsigned long long b0 = __ballot(strw[0] != 0u), b1 = __ballot(strw[1] != 0u);
+        uint32_t before[EPT];                  // '-' rows before this one among the rows of the same e
+        before[0] = __builtin_amdgcn_mbcnt_hi((uint32_t)(b0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b0, 0u));
+        before[1] = __builtin_amdgcn_mbcnt_hi((uint32_t)(b1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b1, 0u));
+        if (lane == 0) wsum[w] = (uint32_t)__popcll(b0) | ((uint32_t)__popcll(b1) << 16);
+        for (int k = t; k < W; k += T) hs[k] = 0;
         __syncthreads();
-        unsigned long long p0 = __shfl_up(x0, 1), p1 = __shfl_up(x1, 1);      // exclusive over the threads before
-        uint32_t pc = xc - c1;
-        if (lane == 0) { p0 = 0; p1 = 0; }
+        uint32_t tot = 0, pre = 0;
 #pragma unroll
-        for (int k = 0; k < T / 64; ++k) {
-            if (k < w) { p0 = wmax0[k] > p0 ? wmax0[k] : p0; p1 = wmax1[k] > p1 ? wmax1[k] : p1; pc += wsum[k]; }
-            n1 += (int)wsum[k];
-        }
+        for (int k = 0; k < T / 64; ++k) { const uint32_t v = wsum[k]; if (k < w) pre += v; tot += v; }
+        const int tot0 = (int)(tot & 0xffffu);
+        n1 = tot0 + (int)(tot >> 16);
+        before[0] += pre & 0xffffu;
+        before[1] += (uint32_t)tot0 + (pre >> 16);
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
-            const int i = t * EPT + e;
+            const int i = t + e * T;
             if (i < wn) {
-                const int before1 = (int)(pc + cb[e]);             // '-' rows before window row i
-                const int k = str[e] ? W - 1 - before1 : i - before1;
-                const unsigned long long m = str[e] ? (v1[e] > p1 ? v1[e] : p1) : (v0[e] > p0 ? v0[e] : p0);
-                cL[k] = own_cl[e]; pm[k] = m; wR[k] = rr[e]; rid[k] = (uint16_t)i; pos[i] = (uint16_t)k;
+                const int k = strw[e] ? W - 1 - (int)before[e] : i - (int)before[e];
+                cL[k] = own_cl[e]; rid[k] = (uint16_t)i; pos[i] = (uint16_t)k;
             }
         }
     }
-    __syncthreads();                           // (wsum is reused by the degree scan below: all reads above are done)
+    __syncthreads();                           // (wsum is reused by the scans below: all reads above are done)
     const uint32_t maxlen = s_misc[1];
     const int n0 = wn - n1;                    // '+' rows occupy [0, n0), '-' rows [W - n1, W)
+
+    if (!SD_ABL(a, 64)) {
+        // ---- forward extent of every window row up to the tile's last: the number of rows of its strand with
+        // cL <= tf, by a binary search of the same depth for every lane (sum of the steps >= the longer strand)
+        const int top = 1 << (31 - __clz(max(max(n0, n1), 1)));
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) {
+            if (t + e * T < n_srch) {
+                const int ns = strw[e] ? n1 : n0;
+                const int sbase = strw[e] ? W : -1, sdir = strw[e] ? -1 : 1;       // the idx-th row of the strand (from 1) is at sbase + sdir * idx
+                const unsigned long long tf = tfw[e];
+                int cnt = 0;
+#pragma nounroll
+                for (int step = top; step > 0; step >>= 1) {
+                    const int idx = cnt + step;
+                    const unsigned long long v = cL[sbase + sdir * min(idx, ns)];
+                    cnt = ((idx <= ns) & (v <= tf)) ? idx : cnt;
+                }
+                // (cnt >= 1: the row itself.)  f = cnt - 1; rows whose run ends inside the window count at the u after it
+                fu[pos[t + e * T]] = (uint16_t)(cnt - 1);
+                if (cnt < ns) atomicAdd(&hs[sbase + sdir * (cnt + 1)], 1u);
+            }
+        }
+        __syncthreads();
+        // ---- running sum of the histogram over the positions (two per thread), in place
+        {
+            uint32_t h0 = 0, h1 = 0;
+            if (2 * t < W) { h0 = hs[2 * t]; h1 = hs[2 * t + 1]; }
+            uint32_t x = h0 + h1;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(x, o); if (lane >= o) x += y; }
+            if (lane == 63) wsum[w] = x;
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < T / 64; ++k) { const uint32_t v = wsum[k]; if (k < w) x += v; }
+            if (2 * t < W) { hs[2 * t] = x - h1; hs[2 * t + 1] = x; }
+        }
+        __syncthreads();
+    }
 
     const int r = t0 + t;
     const int ri = r - wlo;
     const bool act = t < nr;
     int p = 0;
     unsigned long long own = 0;
-    uint32_t rgt = 0;
-    if (act) { p = pos[ri]; own = cL[p]; rgt = wR[p]; }
+    if (act) { p = pos[ri]; own = cL[p]; }
     const uint32_t st = p >= W - n1 ? 1u : 0u;
     const uint32_t l = (uint32_t)own, crel = (uint32_t)(own >> 32), c = crel + c0w;
-    const unsigned long long tb = own;                                          // (chrom, left)
-    const unsigned long long tf = (own & 0xffffffff00000000ull) | rgt;          // (chrom, right)
-    // the window maxima decide the end of the backward walk iff no row before the window can reach `left`
+    // the window holds every earlier neighbour iff no row before the window can reach `left`
     const bool exact = wlo == 0 || crel != 0 || l0w + maxlen < l;
     // strand-local direction of increasing row number, and the bounds of this strand's region
     const int dfw = st ? -1 : 1;
     const int first = st ? W - 1 : 0;                      // position of the strand's first window row
     const int last = st ? W - n1 : n0 - 1;                 // ... and of its last one
+    const int up = (p - first) * dfw;                      // this row's index inside its strand
 
-    uint32_t deg = 0;
+    uint32_t degb = 0, degf = 0;               // earlier / later neighbours
     int far_b = r, far_f = r;
-    bool redo = false;                         // the 16-bit list of this row is incomplete
-    // rows reached outside the window (rare): distance may not fit 16 bits
-    auto emit_far = [&](int q) {
-        const int d = q - r;
-        if (deg < (uint32_t)KMAX) {
-            if (d >= -32768 && d <= 32767) tmp[deg * T + t] = (int16_t)d; else redo = true;
-        }
-        ++deg;
-        if (d < 0) far_b = q; else far_f = q;
-    };
+    bool redo = false;                         // the list of this row has to come from global memory
     if (act && !SD_ABL(a, 64)) {
-        // The loops are written without conditional statements (loads at a clamped position, a dummy 17th
-        // list row for the non-hits, two rows per trip): as nested ifs they compiled to two serialised LDS
-        // round trips and ~25 exec-mask instructions per row.
-        int16_t* mytmp = tmp + t;
-        auto take = [&](bool hit, int wi) {
-            const uint32_t slot = (hit & (deg < (uint32_t)KMAX)) ? deg : (uint32_t)KMAX;
-            mytmp[slot * T] = (int16_t)(wi - ri);
-            deg += hit ? 1u : 0u;
-            return hit ? wlo + wi : -1;
-        };
-        // in strand-local coordinates u = (position - first) * dfw  (0 = the strand's first window row)
-        const int up = (p - first) * dfw, ulast = (last - first) * dfw;
         // ---- earlier rows of this strand, most recent first
         if (exact) {
+            // (a count that runs into the window's start needs no walk beyond it: `exact` says that no row before
+            // the window reaches `left`)
+            const uint32_t below = st ? hs[W - 1] - (p > 0 ? hs[p - 1] : 0u) : hs[p];       // rows of the strand with f < up
+            const uint32_t want = (uint32_t)up - below;
+            // Steps down from up - 1 and ends after `want` hits; no conditional statements but the two stores (loads at
+            // a clamped position, two rows per trip).  The guard on u only bounds the loop.
+            int16_t* mytmp = tmp + t;
             int u = up - 1;
-            for (;;) {
-                const int q0 = first + dfw * max(u, 0), q1 = first + dfw * max(u - 1, 0);
-                const unsigned long long m0 = pm[q0], m1 = pm[q1];
-                const uint32_t x0 = wR[q0], x1 = wR[q1];
+            while ((degb < want) & (u >= 0)) {
+                const int q0 = first + dfw * u, q1 = first + dfw * max(u - 1, 0);
+                const int f0 = fu[q0], f1 = fu[q1];
                 const int i0 = rid[q0], i1 = rid[q1];
-                if (!((u >= 0) & (m0 >= tb))) break;
-                const int f0 = take(x0 >= l, i0);              // (pm >= target: the row is of this chromosome)
-                far_b = f0 >= 0 ? f0 : far_b;
-                --u;
-                if (!((u >= 0) & (m1 >= tb))) break;
-                const int f1 = take(x1 >= l, i1);
-                far_b = f1 >= 0 ? f1 : far_b;
-                --u;
+                const bool hit0 = f0 >= up, hit1 = (u >= 1) & (f1 >= up);
+                if (hit0) mytmp[min(degb, (uint32_t)KMAX - 1u) * T] = (int16_t)(i0 - ri);
+                degb += hit0 ? 1u : 0u;
+                far_b = hit0 ? wlo + i0 : far_b;
+                if (hit1) mytmp[min(degb, (uint32_t)KMAX - 1u) * T] = (int16_t)(i1 - ri);
+                degb += hit1 ? 1u : 0u;
+                far_b = hit1 ? wlo + i1 : far_b;
+                u -= 2;
             }
-            if (u < 0 && wlo > 0) walk_back_global(a, wlo - 1, c, l, st, maxlen, emit_far);
         } else {
-            walk_back_global(a, r - 1, c, l, st, maxlen, emit_far);
+            // rows reached outside the window (rare): distance may not fit 16 bits
+            walk_back_global(a, r - 1, c, l, st, maxlen, [&](int q) {
+                const int d = q - r;
+                if (degb < (uint32_t)KMAX) {
+                    if (d >= -32768) tmp[degb * T + t] = (int16_t)d; else redo = true;
+                }
+                ++degb;
+                far_b = q;
+            });
         }
-        // ---- later rows of this strand in order: every row up to the first with (chrom, left) > (c, right)
-        {
-            int u = up + 1;
-            for (;;) {
-                const int q0 = first + dfw * min(u, ulast), q1 = first + dfw * min(u + 1, ulast);
-                const unsigned long long c0 = cL[q0], c1 = cL[q1];
-                const int i0 = rid[q0], i1 = rid[q1];
-                if (!((u <= ulast) & (c0 <= tf))) break;
-                far_f = take(true, i0);
-                ++u;
-                if (!((u <= ulast) & (c1 <= tf))) break;
-                far_f = take(true, i1);
-                ++u;
-            }
-            if (u > ulast && whi < n) walk_fwd_global(a, whi, n, c, rgt, st, emit_far);
+        if (degb > (uint32_t)KMAX) redo = true;
+        // ---- later rows of this strand: the run up to the forward extent, never listed before the stage is filled
+        const int f = fu[p];
+        degf = (uint32_t)(f - up);
+        if (degf) far_f = wlo + (int)rid[first + dfw * f];
+        if (f == (last - first) * dfw && whi < n) {
+            // the extent clamped at the window's end: the run may go on beyond it (then the row redoes its list)
+            const uint32_t d0 = degf;
+            walk_fwd_global(a, whi, n, c, a.rowR2[r] >> 1, st, [&](int q) { ++degf; far_f = q; });
+            if (degf != d0) redo = true;
         }
-        if (deg > (uint32_t)KMAX) redo = true;
     }
+    const uint32_t deg = degb + degf;
     uint32_t reach = (uint32_t)max(r - far_b, far_f - r);
     {
         // per 16-row block (tiles start at multiples of 16): how far the lists reach beyond the block on either side
@@ -971,11 +993,14 @@ __global__ void __launch_bounds__(T, 8) neighbours_kernel(FastArgs a) {      // 
     const bool staged = total <= (uint32_t)Cfg::STAGE;
     if (staged && act && deg) {
         if (!redo) {
-            for (uint32_t k = 0; k < deg; ++k) stage[loff + k] = r + (int)tmp[k * T + t];
+            for (uint32_t k = 0; k < degb; ++k) stage[loff + k] = r + (int)tmp[k * T + t];
+            int32_t* fwd = stage + loff + degb;
+            const uint16_t* nxt = rid + first + dfw * (up + 1);            // (rid lies outside the stage)
+            for (uint32_t k = 0; k < degf; ++k) fwd[k] = wlo + (int)nxt[dfw * (int)k];
         } else {
             uint32_t k = loff;
             walk_back_global(a, r - 1, c, l, st, maxlen, [&](int q) { stage[k++] = q; });
-            walk_fwd_global(a, r + 1, n, c, rgt, st, [&](int q) { stage[k++] = q; });
+            walk_fwd_global(a, r + 1, n, c, a.rowR2[r] >> 1, st, [&](int q) { stage[k++] = q; });
         }
     }
     __syncthreads();
@@ -993,7 +1018,7 @@ __global__ void __launch_bounds__(T, 8) neighbours_kernel(FastArgs a) {      // 
         int64_t k = base + loff;
         auto put = [&](int q) { if (k < cap) a.col[k] = q; ++k; };
         walk_back_global(a, r - 1, c, l, st, maxlen, put);
-        walk_fwd_global(a, r + 1, n, c, rgt, st, put);
+        walk_fwd_global(a, r + 1, n, c, a.rowR2[r] >> 1, st, put);
     }
     // next tile (the barrier also says: this tile's readers are done with the LDS)
     if (t == 0) s_tile = (int)atomicAdd(ticket, 1ull);

@@ -1,15 +1,17 @@
 #!/usr/bin/env python3
-"""Same-process A/B of the fast clustering chain: ab_cluster.py n [cluster.param=value,...] ...  (per-kernel us via the
-library's profiling switch, asynchronous calls)."""
+"""Same-process A/B of the fast clustering chain: ab_cluster.py n[@gene_spacing] [cluster.param=value,...] ...  (per-kernel
+us via the library's profiling switch, asynchronous calls).  n@3300: the dense layout (average degree about 40).  Two
+builds are compared by running it once per library (SPLICEDICE_HIP_LIB), alternating."""
 import sys, os, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from splicedice_amd import synth
 from splicedice_amd.engine import Context
-n = int(sys.argv[1])
+n, _, spacing = sys.argv[1].partition("@")
+n = int(n)
 cfgs = sys.argv[2:] or [""]
 ctx = Context(0)
-junc = synth.make_junctions(n, 2)
+junc = synth.make_junctions(n, 2, **({"gene_spacing": int(spacing)} if spacing else {}))
 d = [ctx.to_device(x) for x in junc]
 d_row_of, d_rp = ctx.empty(n, np.int32), ctx.empty(n + 1, np.int64)
 ctx.cluster_dev(*d, d_row_of, d_rp)

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-kernel timing of the fast clustering chain under the cluster.ablate switches (tuning aid; the switches
 exist only in a library built with `make -C splicedice_amd/csrc EXTRA=-DSDICE_CLUSTER_ABLATE=1`).
-Results are wrong under ablation; calls are asynchronous and their status is discarded."""
+Results are wrong under ablation; calls are asynchronous and their status is discarded.
+neighbours_kernel: 64 = no search, count and walk (every list empty), 128 = no look-back."""
 import sys, os, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
