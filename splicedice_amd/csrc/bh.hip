@@ -14,16 +14,8 @@
 // `pairwise` (pairwise_fisher.py:187-191: BH down each of the S(S-1)/2 columns) is one batched
 // pass over the transposed table instead of one sort per column.
 #include "common.h"
+#include "bh.h"
 #include <algorithm>
-
-int sd_inclusive_min_scan_u64(sdice_ctx* ctx, int64_t n, const uint64_t* d_in, uint64_t* d_out);
-// bh_cols.hip
-size_t sd_bh_cols_scratch(int64_t m, int64_t segs);
-bool sd_bh_cols_supported(int64_t m, int64_t segs);
-int sd_bh_cols_samplesort(sdice_ctx* ctx, int64_t m, int64_t segs, double* d_rm, int64_t pitch);
-bool sd_bh_vector_supported(int64_t n);
-size_t sd_bh_vector_scratch(sdice_ctx* ctx, int64_t n);
-int sd_bh_vector_samplesort(sdice_ctx* ctx, int64_t n, const double* d_p, const uint8_t* d_tested, bool masked, double* d_q);
 
 namespace {
 
@@ -170,30 +162,13 @@ __global__ void __launch_bounds__(256) bh_scatter_kernel(const uint64_t* __restr
     q[seg * m + idx[g]] = v;
 }
 
+// out[c, r] = in[r, c] for an in of `rows` x `cols` with row pitch in_pitch, out row pitch out_pitch (elements);
+// 32x32 tiles through LDS
 __global__ void __launch_bounds__(256) transpose_f64_kernel(const double* __restrict__ in, int64_t rows, int64_t cols,
-                                                            double* __restrict__ out) {
-    // out[c, r] = in[r, c]; 32x32 tiles through LDS
+                                                            int64_t in_pitch, double* __restrict__ out, int64_t out_pitch) {
     __shared__ double tile[32][33];
     const int64_t c0 = (int64_t)blockIdx.x * 32, r0 = (int64_t)blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
-    for (int k = ty; k < 32; k += 8) {
-        const int64_t r = r0 + k, c = c0 + tx;
-        if (r < rows && c < cols) tile[k][tx] = in[r * cols + c];
-    }
-    __syncthreads();
-    for (int k = ty; k < 32; k += 8) {
-        const int64_t c = c0 + k, r = r0 + tx;
-        if (r < rows && c < cols) out[c * rows + r] = tile[tx][k];
-    }
-}
-
-// out[c, r] = in[r, c] for an in of `rows` x `cols` with row pitch in_pitch, out row pitch out_pitch (elements)
-__global__ void __launch_bounds__(256) transpose_f64_pitched_kernel(const double* __restrict__ in, int64_t rows, int64_t cols,
-                                                                    int64_t in_pitch, double* __restrict__ out,
-                                                                    int64_t out_pitch) {
-    __shared__ double tile[32][33];
-    const int64_t c0 = (int64_t)blockIdx.x * 32, r0 = (int64_t)blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     for (int k = ty; k < 32; k += 8) {
         const int64_t r = r0 + k, c = c0 + tx;
         if (r < rows && c < cols) tile[k][tx] = in[r * in_pitch + c];
@@ -205,96 +180,104 @@ __global__ void __launch_bounds__(256) transpose_f64_pitched_kernel(const double
     }
 }
 
-int transpose(sdice_ctx* ctx, const double* in, int64_t rows, int64_t cols, double* out) {
+int transpose(sdice_ctx* ctx, const double* in, int64_t rows, int64_t cols, int64_t in_pitch, double* out, int64_t out_pitch) {
     // the grid's y extent is limited to 65535 blocks: tall matrices go in row chunks
     const int64_t chunk = (int64_t)65535 * 32;
     for (int64_t r0 = 0; r0 < rows; r0 += chunk) {
         const int64_t rc = std::min(chunk, rows - r0);
         const int64_t gx = sd_ceil_div(cols, 32), gy = sd_ceil_div(rc, 32);
         if (gx > 0x7fffffff) { sdice_set_error("transpose: too many columns"); return SDICE_ERR_ARG; }
-        SD_LAUNCH(ctx, "transpose_f64_kernel", transpose_f64_pitched_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0,
-                  in + r0 * cols, rc, cols, cols, out + r0, rows);
+        SD_LAUNCH(ctx, "transpose_f64_kernel", transpose_f64_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0,
+                  in + r0 * in_pitch, rc, cols, in_pitch, out + r0, out_pitch);
     }
     return SDICE_OK;
 }
 
 }  // namespace
 
+// The buffers of a radix sort of (p bits, index) pairs: in, out and in between; kA and kC serve the later stages too.
+struct BhRadixScratch {
+    uint64_t *kA, *kB, *kC;
+    uint32_t *vA, *vB, *vC;
+    int alloc(Arena& A, size_t values) {
+        kA = (uint64_t*)A.alloc(values * 8);
+        kB = (uint64_t*)A.alloc(values * 8);
+        kC = (uint64_t*)A.alloc(values * 8);
+        vA = (uint32_t*)A.alloc(values * 4);
+        vB = (uint32_t*)A.alloc(values * 4);
+        vC = (uint32_t*)A.alloc(values * 4);
+        return kA && kB && kC && vA && vB && vC ? SDICE_OK : SDICE_ERR_NOMEM;
+    }
+};
+
+// arena bytes of the radix path for `segs` segments of n values: BhRadixScratch (36 B per value, 37 reserved), per segment
+// the sort's histograms (1 KB per tile of 3072 keys) and bin totals (1 KB), the block sums of the scan and alignment
+static size_t bh_radix_scratch(int64_t n, int64_t segs) {
+    return (size_t)n * (size_t)segs * 37 + (size_t)segs * (size_t)(n / 3072 + 2) * 1024 + (1 << 16);
+}
+
 // BH inside each of `segs` contiguous segments of m p-values: d_p[seg*m + i] -> d_q[seg*m + i]
 static int bh_segments(sdice_ctx* ctx, int64_t m, int64_t segs, const double* d_p, double* d_q) {
-    Arena& A = ctx->arena;
     const int64_t total = m * segs;
-    const size_t M = (size_t)total;
-    uint64_t* kA = (uint64_t*)A.alloc(M * 8);
-    uint64_t* kB = (uint64_t*)A.alloc(M * 8);
-    uint64_t* kC = (uint64_t*)A.alloc(M * 8);
-    uint32_t* vA = (uint32_t*)A.alloc(M * 4);
-    uint32_t* vB = (uint32_t*)A.alloc(M * 4);
-    uint32_t* vC = (uint32_t*)A.alloc(M * 4);
-    if (!kA || !kB || !kC || !vA || !vB || !vC) return SDICE_ERR_NOMEM;
+    BhRadixScratch s;
+    SD_TRY(s.alloc(ctx->arena, (size_t)total));
     const unsigned g = (unsigned)sd_ceil_div(total, 256);
-    SD_LAUNCH(ctx, "bh_keys_kernel", bh_keys_kernel, dim3(g), dim3(256), 0, d_p, m, total, kA, vA);
+    SD_LAUNCH(ctx, "bh_keys_kernel", bh_keys_kernel, dim3(g), dim3(256), 0, d_p, m, total, s.kA, s.vA);
     // p-values live in [0, 1] (or NaN): the sign bit never varies, every other digit may
-    SD_TRY(sd_radix_sort_pairs_segmented(ctx, m, segs, kA, vA, kB, vB, kC, vC, 0x7fffffffffffffffull));
-    SD_LAUNCH(ctx, "bh_raw_kernel", bh_raw_kernel, dim3(g), dim3(256), 0, kB, m, total, kA);
+    SD_TRY(sd_radix_sort_pairs_segmented(ctx, m, segs, s.kA, s.vA, s.kB, s.vB, s.kC, s.vC, 0x7fffffffffffffffull));
+    SD_LAUNCH(ctx, "bh_raw_kernel", bh_raw_kernel, dim3(g), dim3(256), 0, s.kB, m, total, s.kA);
     if (segs == 1) {
-        SD_TRY(sd_inclusive_min_scan_u64(ctx, m, kA, kC));      // one long vector: the grid-wide 3-launch scan
+        SD_TRY(sd_inclusive_min_scan_u64(ctx, m, s.kA, s.kC));      // one long vector: the grid-wide 3-launch scan
     } else {
-        SD_LAUNCH(ctx, "seg_minscan_kernel", seg_minscan_kernel, dim3((unsigned)segs), dim3(256), 0, kA, m, kC);
+        SD_LAUNCH(ctx, "seg_minscan_kernel", seg_minscan_kernel, dim3((unsigned)segs), dim3(256), 0, s.kA, m, s.kC);
     }
-    SD_LAUNCH(ctx, "bh_scatter_kernel", bh_scatter_kernel, dim3(g), dim3(256), 0, kC, vB, m, total, d_q);
+    SD_LAUNCH(ctx, "bh_scatter_kernel", bh_scatter_kernel, dim3(g), dim3(256), 0, s.kC, s.vB, m, total, d_q);
     return SDICE_OK;
 }
 
-extern "C" int sdice_bh_dev(sdice_ctx* ctx, int64_t m, const double* d_p, double* d_q) {
-    SD_ARG(ctx, "ctx is NULL");
-    SD_ARG(m >= 0 && m < ((int64_t)1 << 32), "m out of range");
-    if (m == 0) return SDICE_OK;
-    SD_ARG(d_p && d_q, "NULL pointer");
-    SD_HIP(hipSetDevice(ctx->device));
-    // bh.vector_path: 0 = by size, 1 = radix path, 2 = sample-sort path (bh_cols.hip, four launches)
-    const int64_t vpath = ctx->param(SD_P_BH_VECTOR_PATH);
-    if (vpath != 1 && sd_bh_vector_supported(m)) {
-        SD_TRY(ctx->arena.reserve(sd_bh_vector_scratch(ctx, m), ctx->stream));
-        return sd_bh_vector_samplesort(ctx, m, d_p, nullptr, false, d_q);
-    }
-    SD_ARG(vpath != 2, "bh.vector_path = 2 needs 16384 <= m <= 2 Mi values");
-    SD_TRY(ctx->arena.reserve((size_t)m * 37 + (size_t)(m / 3072 + 2) * 1024 + (1 << 16), ctx->stream));
-    return bh_segments(ctx, m, 1, d_p, d_q);
-}
-
-extern "C" int sdice_bh_masked_dev(sdice_ctx* ctx, int64_t n, const double* d_p, const uint8_t* d_tested, double* d_q) {
-    SD_ARG(ctx, "ctx is NULL");
-    SD_ARG(n >= 0 && n < ((int64_t)1 << 32), "n out of range");
-    if (n == 0) return SDICE_OK;
-    SD_ARG(d_p && d_q, "NULL pointer");
-    SD_HIP(hipSetDevice(ctx->device));
-    const int64_t vpath = ctx->param(SD_P_BH_VECTOR_PATH);
-    if (vpath != 1 && sd_bh_vector_supported(n)) {
-        SD_TRY(ctx->arena.reserve(sd_bh_vector_scratch(ctx, n), ctx->stream));
-        return sd_bh_vector_samplesort(ctx, n, d_p, d_tested, true, d_q);
-    }
-    SD_ARG(vpath != 2, "bh.vector_path = 2 needs 16384 <= n <= 2 Mi values");
-    SD_TRY(ctx->arena.reserve((size_t)n * 37 + (size_t)(n / 3072 + 2) * 1024 + (1 << 16), ctx->stream));
-    Arena& A = ctx->arena;
-    const size_t M = (size_t)n;
-    uint64_t* kA = (uint64_t*)A.alloc(M * 8);
-    uint64_t* kB = (uint64_t*)A.alloc(M * 8);
-    uint64_t* kC = (uint64_t*)A.alloc(M * 8);
-    uint32_t* vA = (uint32_t*)A.alloc(M * 4);
-    uint32_t* vB = (uint32_t*)A.alloc(M * 4);
-    uint32_t* vC = (uint32_t*)A.alloc(M * 4);
-    unsigned long long* m_eff = (unsigned long long*)A.alloc(8);
-    if (!kA || !kB || !kC || !vA || !vB || !vC || !m_eff) return SDICE_ERR_NOMEM;
+// one vector with absent entries (see bh_keys_masked_kernel) on the radix path
+static int bh_masked_radix(sdice_ctx* ctx, int64_t n, const double* d_p, const uint8_t* d_tested, double* d_q) {
+    BhRadixScratch s;
+    SD_TRY(s.alloc(ctx->arena, (size_t)n));
+    unsigned long long* m_eff = (unsigned long long*)ctx->arena.alloc(8);
+    if (!m_eff) return SDICE_ERR_NOMEM;
     SD_HIP(hipMemsetAsync(m_eff, 0, 8, ctx->stream));
     const unsigned g = (unsigned)sd_ceil_div(n, 256);
     SD_LAUNCH(ctx, "bh_keys_masked_kernel", bh_keys_masked_kernel, dim3((unsigned)sd_ceil_div(n, (int64_t)8192)), dim3(1024), 0, d_p,
-              d_tested, n, kA, vA, m_eff);
-    SD_TRY(sd_radix_sort_pairs(ctx, n, kA, vA, kB, vB, kC, vC, ~0ull));
-    SD_LAUNCH(ctx, "bh_raw_masked_kernel", bh_raw_masked_kernel, dim3(g), dim3(256), 0, kB, n, m_eff, kA);
-    SD_TRY(sd_inclusive_min_scan_u64(ctx, n, kA, kC));
-    SD_LAUNCH(ctx, "bh_scatter_masked_kernel", bh_scatter_masked_kernel, dim3(g), dim3(256), 0, kC, vB, n, m_eff, d_q);
+              d_tested, n, s.kA, s.vA, m_eff);
+    SD_TRY(sd_radix_sort_pairs(ctx, n, s.kA, s.vA, s.kB, s.vB, s.kC, s.vC, ~0ull));
+    SD_LAUNCH(ctx, "bh_raw_masked_kernel", bh_raw_masked_kernel, dim3(g), dim3(256), 0, s.kB, n, m_eff, s.kA);
+    SD_TRY(sd_inclusive_min_scan_u64(ctx, n, s.kA, s.kC));
+    SD_LAUNCH(ctx, "bh_scatter_masked_kernel", bh_scatter_masked_kernel, dim3(g), dim3(256), 0, s.kC, s.vB, n, m_eff, d_q);
     return SDICE_OK;
+}
+
+// One vector, behind sdice_bh_dev and sdice_bh_masked_dev (`who`).  masked: entries with tested == 0 -- or, without a
+// mask, with p < 0 -- are absent.
+static int bh_vector(sdice_ctx* ctx, const char* who, int64_t n, const double* d_p, const uint8_t* d_tested, bool masked,
+                     double* d_q) {
+    SD_ARG_AS(who, ctx, "ctx is NULL");
+    SD_ARG_AS(who, n >= 0 && n < ((int64_t)1 << 32), "size out of range");
+    if (n == 0) return SDICE_OK;
+    SD_ARG_AS(who, d_p && d_q, "NULL pointer");
+    SD_HIP(hipSetDevice(ctx->device));
+    // bh.vector_path: 0 = by size, 1 = radix path, 2 = sample-sort path (bh_cols.hip, four launches)
+    const int64_t vpath = ctx->param(SD_P_BH_VECTOR_PATH);
+    if (vpath != 1 && sd_bh_vector_supported(n)) {
+        SD_TRY(ctx->arena.reserve(sd_bh_vector_scratch(ctx, n), ctx->stream));
+        return sd_bh_vector_samplesort(ctx, n, d_p, d_tested, masked, d_q);
+    }
+    SD_ARG_AS(who, vpath != 2, "bh.vector_path = 2 needs 16384 .. 2 Mi values");
+    SD_TRY(ctx->arena.reserve(bh_radix_scratch(n, 1), ctx->stream));
+    return masked ? bh_masked_radix(ctx, n, d_p, d_tested, d_q) : bh_segments(ctx, n, 1, d_p, d_q);
+}
+
+extern "C" int sdice_bh_dev(sdice_ctx* ctx, int64_t m, const double* d_p, double* d_q) {
+    return bh_vector(ctx, __func__, m, d_p, nullptr, false, d_q);
+}
+
+extern "C" int sdice_bh_masked_dev(sdice_ctx* ctx, int64_t n, const double* d_p, const uint8_t* d_tested, double* d_q) {
+    return bh_vector(ctx, __func__, n, d_p, d_tested, true, d_q);
 }
 
 extern "C" int sdice_bh(sdice_ctx* ctx, int64_t m, const double* p, double* q) {
@@ -310,28 +293,57 @@ extern "C" int sdice_bh(sdice_ctx* ctx, int64_t m, const double* p, double* q) {
     return st.download(q, dq, m);
 }
 
-// BH down each column of a row-major [n, cols] device table, in place.
-// Columns of up to 2^18 values: sample-sort path (bh_cols.hip), which reads and writes the row-major table itself;
-// column groups when the scratch (28 B per value) does not fit what is free.
-static int bh_columns_samplesort(sdice_ctx* ctx, int64_t n, int64_t cols, int64_t pitch, double* d_p_inout) {
+// BH down each column of a row-major device table (n rows, row pitch `pitch` elements), in place.  A BhColumnPath is one
+// way of correcting `segs` whole columns at once, at most max_group of them, out of scratch(n, segs) bytes of the context
+// arena; scratch is linear in segs.
+struct BhColumnPath {
+    size_t (*scratch)(int64_t n, int64_t segs);
+    int64_t max_group;
+    int (*run)(sdice_ctx* ctx, int64_t n, int64_t segs, double* d_rm, int64_t pitch);
+};
+
+// generic path: the columns transposed into segments straight from the table, bh_segments, the results transposed back
+static size_t bh_radix_cols_scratch(int64_t n, int64_t segs) {
+    return (size_t)n * (size_t)segs * 16 + bh_radix_scratch(n, segs);
+}
+
+static int bh_radix_cols(sdice_ctx* ctx, int64_t n, int64_t segs, double* d_rm, int64_t pitch) {
+    const size_t vals = (size_t)n * (size_t)segs;
+    double* d_cm = (double*)ctx->arena.alloc(vals * 8);
+    double* d_q = (double*)ctx->arena.alloc(vals * 8);
+    if (!d_cm || !d_q) return SDICE_ERR_NOMEM;
+    SD_TRY(transpose(ctx, d_rm, n, segs, pitch, d_cm, n));
+    SD_TRY(bh_segments(ctx, n, segs, d_cm, d_q));
+    return transpose(ctx, d_q, segs, n, n, d_rm, pitch);
+}
+
+static const BhColumnPath kRadixCols = {bh_radix_cols_scratch, 65535, bh_radix_cols};      // (the sort's grid: segments in y)
+// columns of up to 2^18 values (bh_cols.hip): reads and writes the row-major table itself
+static const BhColumnPath kSampleSortCols = {sd_bh_cols_scratch, 0x7fffffff, sd_bh_cols_samplesort};
+
+// The columns in groups of what fits nine tenths of the free memory plus the arena's chunks, which are reused (param
+// bh.max_group: at most so many).  Everything comes from the context arena, kept between calls: no multi-GB hipMalloc
+// per call.
+static int bh_column_groups(sdice_ctx* ctx, const BhColumnPath& path, int64_t n, int64_t cols, int64_t pitch, double* d_rm) {
     size_t free_b = 0, total_b = 0;
     SD_HIP(hipMemGetInfo(&free_b, &total_b));
     size_t arena_b = 0;
     for (auto& c : ctx->arena.chunks) arena_b += c.cap;
     const int64_t budget = (int64_t)((free_b + arena_b) / 10 * 9);
-    int64_t group = std::max<int64_t>(1, (budget - (1 << 20)) / (n * 28 + 49 * 1025));
-    if (group > cols) group = cols;
-    if (group < cols && group > 16) group &= ~(int64_t)15;      // whole 128-byte lines of the row-major table per group
-    for (int64_t c0 = 0; c0 < cols; c0 += group) {
-        const int64_t gc = std::min(group, cols - c0);
-        int rc = ctx->arena.reserve(sd_bh_cols_scratch(n, group), ctx->stream);
-        if (rc == SDICE_ERR_NOMEM && group > 1) {            // less memory than hipMemGetInfo promised
+    const int64_t fixed = (int64_t)path.scratch(n, 0), per_column = (int64_t)path.scratch(n, 1) - fixed;
+    const int64_t knob = ctx->param(SD_P_BH_MAX_GROUP);
+    int64_t group = sd_bh_column_group(budget, per_column, fixed, cols, knob > 0 ? std::min(knob, path.max_group) : path.max_group);
+    for (int64_t c0 = 0; c0 < cols;) {
+        // the whole group's bytes for the last, partial group too: the arena keeps its chunk
+        const int rc = ctx->arena.reserve(path.scratch(n, group), ctx->stream);
+        if (rc == SDICE_ERR_NOMEM && group > 1) {            // less memory than was reported free: fewer columns at once
             group = (group + 1) / 2;
-            c0 -= group;
             continue;
         }
-        if (rc != SDICE_OK) return rc;
-        SD_TRY(sd_bh_cols_samplesort(ctx, n, gc, d_p_inout + c0, pitch));
+        SD_TRY(rc);
+        const int64_t gc = std::min(group, cols - c0);
+        SD_TRY(path.run(ctx, n, gc, d_rm + c0, pitch));
+        c0 += gc;
     }
     return SDICE_OK;
 }
@@ -349,62 +361,9 @@ extern "C" int sdice_bh_columns_pitched_dev(sdice_ctx* ctx, int64_t n, int64_t c
     SD_HIP(hipSetDevice(ctx->device));
     // bh.columns_path: 0 = by size, 1 = generic radix path, 2 = sample-sort path
     const int64_t path = ctx->param(SD_P_BH_COLUMNS_PATH);
-    if (path != 1 && sd_bh_cols_supported(n, cols)) return bh_columns_samplesort(ctx, n, cols, pitch, d_p_inout);
-    SD_ARG(path != 2, "bh.columns_path = 2 needs columns of at most 2^18 values");
-    // columns per group from what is free right now: per value 2 x 8 B (transposed in / out) + 8 B (dense slab
-    // when the columns go in groups) + 37 B of sort scratch + histograms; a failed reservation halves the group
-    size_t free_b = 0, total_b = 0;
-    SD_HIP(hipMemGetInfo(&free_b, &total_b));
-    size_t arena_b = 0;
-    for (auto& c : ctx->arena.chunks) arena_b += c.cap;         // the arena's own chunk is reused
-    const int64_t budget = (int64_t)((free_b + arena_b) / 10 * 9);
-    int64_t group = budget / (n * 64) > 0 ? budget / (n * 64) : 1;
-    if (group > cols) group = cols;
-    if (group > 65535) group = 65535;
-    int rc = SDICE_OK;
-    for (int64_t c0 = 0; c0 < cols && rc == SDICE_OK; c0 += group) {
-        const int64_t gc = std::min(group, cols - c0);
-        // everything comes from the context arena (kept between calls: no multi-GB hipMalloc per call):
-        // transposed in/out (+ a dense slab when the columns go in groups), 3 x u64 + 3 x u32 per value
-        // for the sort, per-segment histograms (256 x tiles x 4 B) and bin totals
-        const size_t vals = (size_t)n * (size_t)group;
-        const bool slab = group < cols || pitch != cols;     // a column group of the table, or a pitched table: gathered dense first
-        rc = ctx->arena.reserve(vals * (16 + (slab ? 8 : 0) + 37) +
-                                    (size_t)group * ((size_t)(n / 3072 + 2) * 1024 + 1024) + (1 << 16), ctx->stream);
-        if (rc == SDICE_ERR_NOMEM && group > 1) {            // less memory than hipMemGetInfo promised: fewer columns at once
-            group = (group + 1) / 2;
-            c0 -= group;                                      // (the loop increment adds it back: retry this column)
-            rc = SDICE_OK;
-            continue;
-        }
-        if (rc != SDICE_OK) break;
-        double* d_cm = (double*)ctx->arena.alloc(vals * 8);
-        double* d_q = (double*)ctx->arena.alloc(vals * 8);
-        double* d_slab = slab ? (double*)ctx->arena.alloc(vals * 8) : nullptr;
-        if (!d_cm || !d_q || (slab && !d_slab)) return SDICE_ERR_NOMEM;
-        const double* src = d_p_inout;
-        int64_t src_cols = cols;
-        if (rc == SDICE_OK && slab) {
-            // gather the column group [c0, c0+gc) into a dense [n, gc] slab first
-            rc = hipMemcpy2DAsync(d_slab, (size_t)gc * 8, d_p_inout + c0, (size_t)pitch * 8, (size_t)gc * 8, (size_t)n,
-                                  hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess ? SDICE_OK : SDICE_ERR_HIP;
-            src = d_slab;
-            src_cols = gc;
-        }
-        if (rc == SDICE_OK) rc = transpose(ctx, src, n, src_cols, d_cm);
-        if (rc == SDICE_OK) rc = bh_segments(ctx, n, gc, d_cm, d_q);
-        if (rc == SDICE_OK) {
-            if (slab) {
-                rc = transpose(ctx, d_q, gc, n, d_slab);
-                if (rc == SDICE_OK)
-                    rc = hipMemcpy2DAsync(d_p_inout + c0, (size_t)pitch * 8, d_slab, (size_t)gc * 8, (size_t)gc * 8, (size_t)n,
-                                          hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess ? SDICE_OK : SDICE_ERR_HIP;
-            } else {
-                rc = transpose(ctx, d_q, gc, n, d_p_inout);
-            }
-        }
-    }
-    return rc;
+    const bool samplesort = path != 1 && sd_bh_cols_supported(n, cols);
+    SD_ARG(samplesort || path != 2, "bh.columns_path = 2 needs columns of at most 2^18 values");
+    return bh_column_groups(ctx, samplesort ? kSampleSortCols : kRadixCols, n, cols, pitch, d_p_inout);
 }
 
 extern "C" int sdice_bh_columns(sdice_ctx* ctx, int64_t n, int64_t cols, double* p_inout) {

@@ -28,6 +28,7 @@
 // read inside a column's 200 KB of results, which the block -> XCD mapping keeps in one L2.  ~36 B of
 // algorithmic traffic per value; bit-identical to the generic path.
 #include "common.h"
+#include "bh.h"
 #include <algorithm>
 #include <stdio.h>
 

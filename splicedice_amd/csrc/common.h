@@ -188,3 +188,5 @@ int sd_radix_sort_pairs_segmented(sdice_ctx* ctx, int64_t n, int64_t segs, const
                                   uint64_t* d_keys_tmp, uint32_t* d_vals_tmp, uint64_t bit_mask);
 // exclusive scan of int64 values (in place allowed): out[i] = sum_{j<i} in[j]; total to d_total if non-null
 int sd_exclusive_scan_i64(sdice_ctx* ctx, int64_t n, const int64_t* d_in, int64_t* d_out, int64_t* d_total);
+// inclusive running minimum of uint64 values: out[i] = min_{j<=i} in[j]
+int sd_inclusive_min_scan_u64(sdice_ctx* ctx, int64_t n, const uint64_t* d_in, uint64_t* d_out);

@@ -43,6 +43,7 @@
     /* BH correction (bh.hip, bh_cols.hip) */                                                                           \
     X(BH_COLUMNS_PATH, "bh.columns_path", 0, "per-column BH: 0 by size, 1 generic radix path, 2 sample-sort path")      \
     X(BH_VECTOR_PATH, "bh.vector_path", 0, "one vector: 0 by size, 1 radix path, 2 sample-sort path")                   \
+    X(BH_MAX_GROUP, "bh.max_group", 0, "per-column BH: most columns corrected at once; 0 = what fits the free memory (small values: tests)") \
     X(BHV_MEAN, "bhv.mean", 2048, "one vector, sample sort: mean values per bucket (at least 512)")                     \
     X(BHV_CAP, "bhv.cap", 5632, "one vector, sample sort: slot capacity of a bucket (73 KB of LDS: two bucket workgroups per CU)") \
     X(BH_REG_CAP, "bh.reg_cap", 2048, "largest bucket ranked in LDS, 0 .. 2048; beyond it one wave sorts a copy in HBM (small values: tests)") \

@@ -3,7 +3,8 @@
 // and run by tests/test_host_sanitizers.py.  It pushes every host entry point through its threaded
 // path: table writer (3 modes) -> table reader round trip, column writer, cluster writer, junction
 // parser on the golden inputs (all file types) and the row lookup; then the argument checks of the pair
-// tests (csrc/paircheck.cpp) and of the column lists (csrc/colcheck.cpp) on both sides of their bounds.
+// tests (csrc/paircheck.cpp) and of the column lists (csrc/colcheck.cpp) on both sides of their bounds, and the
+// column-group arithmetic of BH (csrc/bhplan.cpp).
 // Any ASan / UBSan / TSan report makes the process exit non-zero.
 #include <math.h>
 #include <stdarg.h>
@@ -17,6 +18,7 @@
 #include "sdice.h"
 #include "paircheck.h"      // splicedice_amd/csrc: the argument checks of the pair tests
 #include "colcheck.h"       //                      ... and of the column lists
+#include "bh.h"             //                      the column groups of BH
 
 static char g_err[1024];
 void sdice_set_error(const char* fmt, ...) {
@@ -250,6 +252,28 @@ int main(int argc, char** argv) {
         CHECK(kw_check_sets("fn", wide, 2, KW_MAX_N) == SDICE_OK);
         REFUSED(kw_check_sets("fn", wider, 2, KW_MAX_N + 1), "fn: 16385 selected columns");
         #undef REFUSED
+    }
+    {   // the column groups of BH (csrc/bhplan.cpp): (budget - fixed) / per_column, at least 1, at most cols and max_group,
+        // a multiple of 16 when it is more than 16 and not the whole table
+        const int64_t T = 1000000000000, BIG = INT64_MAX;
+        struct { int64_t budget, cols, max_group, want; } cases[] = {
+            {T, 37, 65535, 37},                 // everything fits
+            {0, 37, 65535, 1},
+            {999, 37, 65535, 1},                // budget below `fixed`
+            {1000, 37, 65535, 1},
+            {1199, 37, 65535, 1},  {1200, 37, 65535, 2},
+            {3100, 37, 65535, 16},              // room for 21
+            {2700, 37, 65535, 16},              // room for 17
+            {2600, 37, 65535, 16},              // room for 16
+            {2599, 37, 65535, 15},              // room for 15, not rounded
+            {4699, 37, 65535, 32}, {4700, 37, 65535, 37},     // room for 36 | the whole table: not rounded
+            {T, 70000, 65535, 65520},
+            {T, 37, 5, 5}, {T, 37, 1, 1}, {T, 16, 21, 16}, {T, 37, 21, 16}, {T, 37, 37, 37}, {T, 37, 36, 32},
+            {BIG, 37, 65535, 37}, {BIG - 1, 70000, 65535, 65520}, {BIG, BIG, BIG, (BIG - 1000) / 100 & ~(int64_t)15},
+        };
+        for (const auto& c : cases) CHECK(sd_bh_column_group(c.budget, 100, 1000, c.cols, c.max_group) == c.want);
+        CHECK(sd_bh_column_group(BIG, 1, 0, BIG, BIG) == BIG);                             // the whole table at the limit
+        CHECK(sd_bh_column_group(BIG, BIG, BIG, 37, 65535) == 1 && sd_bh_column_group(0, BIG, BIG, 37, 65535) == 1);
     }
     printf("host sanitizer driver: ok\n");
     return 0;

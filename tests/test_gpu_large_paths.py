@@ -6,7 +6,7 @@
   cluster       the hand-over of sdice_cluster_dev to the generic chain above 8 388 608 junctions, and the fast path at
                 exactly 8 388 608 with all 4096 buckets
   radix.hip     digit skipping with gaps and odd / even pass counts; the switch between the two bin-scan kernels
-  bh.hip        the second row chunk of the pitched transpose
+  bh.hip        the second row chunk of the pitched transpose; the column groups of a table that does not fit at once
   ps.hip        the grid-stride passes of quantize3_kernel and mark_low_kernel
 
 Every expected value comes from numpy, oracle_np or the closed form of large_path_fixtures.star_table (proved against the
@@ -32,7 +32,7 @@ B, N0 = LP.SCAN_BLOCK, LP.N0
 ABOVE = N0 + 2 * B + 5
 KERNELS = ("scan_reduce_kernel", "scan_apply_self_kernel", "scan_sums_kernel", "scan_apply_kernel",
            "radix_hist_kernel", "radix_binscan_small_kernel", "radix_binscan_kernel", "transpose_f64_kernel",
-           "bucket_sort_kernel")
+           "bucket_sort_kernel", "bh_keys_kernel", "bhs_finish_kernel")
 
 
 @contextlib.contextmanager
@@ -261,6 +261,49 @@ def test_bh_columns_second_transpose_chunk(ctx):
                 ctx.bh_columns_dev(d)
             assert c["transpose_f64_kernel"] == 2
             np.testing.assert_allclose(d.to_host(), O.bh_columns(one), rtol=1e-14, atol=0)
+    finally:
+        ctx.trim()
+
+
+def _same_bits(a, b):
+    return np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64))
+
+
+def test_bh_columns_in_groups(ctx):
+    """The column-group loop of both column paths, which otherwise runs only when memory is short: bh.max_group cuts the
+    37 columns 2..38 of a [1025, 41] table into 1, 3 (16 + 16 + 5; 21 rounds down to 16), 3, 8 (7 x 5 + 2) and 37 groups.
+    Every grouping gives the oracle's bits, leaves the two guard columns on each side alone and launches once per group;
+    then a dense [1025, 37] table in groups of 16"""
+    n, cols, pitch, c0 = 1025, 37, 41, 2
+    p = _columns(n, cols, 83)
+    want = O.bh_columns(p)
+    table = np.random.default_rng(84).integers(0, 1 << 64, size=(n, pitch), dtype=np.uint64).view(np.float64)
+    table[:, c0:c0 + cols] = p
+    guards = [0, 1, pitch - 2, pitch - 1]
+
+    def check(path, c, groups):
+        if path == 1:
+            assert c["bh_keys_kernel"] == groups and c["transpose_f64_kernel"] == 2 * groups
+        else:
+            assert c["bhs_finish_kernel"] == groups and c["radix_hist_kernel"] == 0
+
+    try:
+        for path in (1, 2):
+            for max_group, groups in ((0, 1), (21, 3), (16, 3), (5, 8), (1, 37)):
+                with ctx.params({"bh.columns_path": path, "bh.max_group": max_group}):
+                    d = ctx.to_device(table)
+                    with _launches(ctx) as c:
+                        ctx.bh_columns_pitched_dev(d.offset(c0, (n * pitch - c0,)), n, cols, pitch)
+                    got = d.to_host()
+                    assert _same_bits(got[:, c0:c0 + cols], want), (path, max_group)
+                    assert _same_bits(got[:, guards], table[:, guards]), (path, max_group)
+                    check(path, c, groups)
+            with ctx.params({"bh.columns_path": path, "bh.max_group": 16}):
+                d = ctx.to_device(p)
+                with _launches(ctx) as c:
+                    ctx.bh_columns_dev(d)
+                assert _same_bits(d.to_host(), want), path
+                check(path, c, 3)
     finally:
         ctx.trim()
 
