@@ -656,6 +656,13 @@ int sdice_get_param(sdice_ctx* ctx, const char* name, int64_t* value);
  * device; past the end -> ERR_ARG */
 int sdice_param_info(int32_t index, const char** name, int64_t* dflt);
 
+/* Test support.  Region `index` (0, 1, ...) of the device memory this context keeps between calls and treats as
+ * scratch: every arena chunk over its whole capacity ("arena"), the neighbour-list buffer over col_cap entries
+ * ("cluster.col"), the block-reach buffer over reach_cap words ("cluster.reach").  Synchronises the context stream.
+ * Not listed, because their contents carry meaning: the clustering status block, the Fisher log-factorial table.
+ * Any out pointer may be NULL.  SDICE_ERR_ARG past the last region.  Changes nothing. */
+int sdice_scratch_region(sdice_ctx* ctx, int32_t index, const char** name, void** dptr, int64_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif

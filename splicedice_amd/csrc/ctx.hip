@@ -211,6 +211,23 @@ HostStaging::~HostStaging() {
     for (void* p : bufs_) (void)hipFree(p);
 }
 
+// Test support: the memory a later call finds as the earlier one left it.  The order is fixed: arena chunks, col, reach.
+extern "C" int sdice_scratch_region(sdice_ctx* ctx, int32_t index, const char** name, void** dptr, int64_t* bytes) {
+    SD_ARG(ctx, "ctx is NULL");
+    SD_HIP(hipSetDevice(ctx->device));
+    SD_HIP(hipStreamSynchronize(ctx->stream));
+    struct Region { const char* name; void* p; int64_t bytes; };
+    std::vector<Region> regions;
+    for (const auto& c : ctx->arena.chunks) regions.push_back({"arena", c.p, (int64_t)c.cap});
+    if (ctx->d_col) regions.push_back({"cluster.col", ctx->d_col, ctx->col_cap * 4});
+    if (ctx->d_reach) regions.push_back({"cluster.reach", ctx->d_reach, ctx->reach_cap * 4});
+    SD_ARG(index >= 0 && (size_t)index < regions.size(), "index past the last scratch region");
+    if (name) *name = regions[index].name;
+    if (dptr) *dptr = regions[index].p;
+    if (bytes) *bytes = regions[index].bytes;
+    return SDICE_OK;
+}
+
 extern "C" int sdice_dmemset(sdice_ctx* ctx, void* dptr, int value, int64_t bytes) {
     SD_ARG(ctx && bytes >= 0, "bad arguments");
     if (bytes == 0) return SDICE_OK;

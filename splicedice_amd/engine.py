@@ -247,6 +247,19 @@ class Context:
         """synchronise and release the cached device scratch"""
         check(self.lib.sdice_trim(self.h), "sdice_trim")
 
+    def scratch_regions(self):
+        """Test support (sdice_scratch_region): the device memory the context keeps between calls and treats as scratch
+        -> [(name, DeviceArray uint8 over the whole region, not owned)]: every "arena" chunk, "cluster.col",
+        "cluster.reach".  Synchronises; changes nothing."""
+        out = []
+        name, p, nbytes = C.c_char_p(), C.c_void_p(), C.c_int64()
+        while True:
+            status = self.lib.sdice_scratch_region(self.h, len(out), C.byref(name), C.byref(p), C.byref(nbytes))
+            if status == -1:          # SDICE_ERR_ARG: past the last region
+                return out
+            check(status, "sdice_scratch_region")
+            out.append((name.value.decode(), DeviceArray(self, (nbytes.value,), np.uint8, ptr=p.value, owned=False)))
+
     def prof_enable(self, on=True):
         """on: False/0 off, True/1 every kernel, 2 dominant kernels only."""
         check(self.lib.sdice_prof_enable(self.h, int(on)), "sdice_prof_enable")

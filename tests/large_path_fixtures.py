@@ -36,6 +36,8 @@ TRANSPOSE_CHUNK = 65535 * 32
 # bh_cols.hip: sd_bh_vector_supported (n <= 2 << 20) and sd_bh_cols_supported (m <= 1 << POS_SHIFT = 2^18): beyond them the
 # radix paths of bh.hip are the only ones
 BH_VECTOR_SAMPLESORT_MAX, BH_COLS_SAMPLESORT_MAX = 2 << 20, 1 << 18
+# sd_bh_vector_supported again: the smallest vector the sample-sort path takes (n >= 16384)
+BH_VECTOR_SAMPLESORT_MIN = 16384
 # ps.hip, sdice_quantize3_dev: at most 2048 workgroups of 256 threads, 4 values per thread and pass
 QUANTIZE_GRID = 2048 * 256 * 4
 # ps.hip, sdice_mark_low_dev: at most 2048 workgroups of 256 threads, one index per thread and pass

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bh_fixtures import bh_columns_values as _bh_columns_values, bh_values as _bh_values  # noqa: E402
 from oracle import oracle_np as O  # noqa: E402
 from rank_support import PLACEMENTS, _kept_positions, _values, tree_sum  # noqa: E402
 
@@ -255,20 +256,6 @@ def test_fractional_tables_truncate_the_table_order_sum(ctx):
 
 
 # ------------------------------------------------------------------------------ BH, bit for bit
-def _bh_values(m, rng):
-    """NaN-free p-values: continuous, a tenth exactly 1, zeros, denormals, exact ties, crowds a few ulps below 1"""
-    p = rng.random(m) ** 3
-    p[rng.random(m) < 0.1] = 1.0
-    special = np.r_[0.0, 5e-324, 1e-310, 2.2250738585072014e-308, 1e-300, 1.0, 0.5, 0.5,
-                    1.0 - np.arange(1, 9) * 2.0 ** -53, np.full(8, 0.03125), np.full(5, 1.0 - 2.0 ** -53)]
-    p[: min(m, special.size)] = special[:m]
-    if m > 4000:
-        p[100:1100] = 0.25                                                    # one value over a whole bucket
-        p[2000:2400] = 1.0 - rng.integers(1, 6, size=400) * 2.0 ** -53         # crowd just below 1
-        p[3000:3100] = rng.choice([5e-324, 1e-320, 0.0], size=100)
-    return p[rng.permutation(m)]
-
-
 @gpu
 @pytest.mark.parametrize("m", [1, 2, 257, 16_385, 262_145, 1_000_003, 2_097_153])
 def test_bh_vector_paths_bit_exact(ctx, m):
@@ -298,13 +285,6 @@ def test_bh_vector_paths_bit_exact(ctx, m):
             assert np.array_equal(d_q.to_host().view(np.uint64), want_masked.view(np.uint64)), path
             ctx.bh_masked_dev(d_neg, None, d_q)
             assert np.array_equal(d_q.to_host().view(np.uint64), want_masked.view(np.uint64)), path
-
-
-def _bh_columns_values(n, cols, rng):
-    p = np.stack([_bh_values(n, rng) for _ in range(cols)], axis=1)
-    if cols > 1:
-        p[:, 1] = rng.choice([1.0, 0.5, 0.0286, 0.2, 1e-5, 5e-324], size=n)     # discrete levels: long ties
-    return p
 
 
 @gpu
