@@ -335,6 +335,42 @@ int sdice_ks_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps,
                  uint8_t* d_tested, double* d_p, double* d_d, float* d_med1, float* d_med2,
                  float* d_mean1, float* d_mean2, float* d_delta, uint8_t* d_exact);
 
+/* ---- compare_sample_sets --shift: the Hodges-Lehmann shift of group 1 against group 2 per row with its distribution-free
+ *      confidence interval (Moses / Lehmann; Hollander & Wolfe sections 4.2-4.3; R's wilcox.test(conf.int = TRUE) reports
+ *      the same interval; not in the reference): the size of the difference that the rank-sum statistic tests.
+ *  Inputs are sdice_ranksum's plus zq, the standard normal quantile at 1 - (1 - conf) / 2 (1.959963984540054 for 95 %).
+ *  1 <= n1, n2 <= 4096, a column at most once over both lists, zq finite and > 0; otherwise SDICE_ERR_ARG before any launch,
+ *  outputs untouched, the reason in sdice_last_error (the host call checks the index range and the one-appearance rule,
+ *  the _dev call n1, n2 and n1 + n2 <= s).
+ *  Outputs, one slot per row, all required: tested[n] uint8, shift[n], lo[n], hi[n] float64, rank[n] int32; every slot of
+ *  a row that is not tested is 0.
+ *  Row rules are sdice_ranksum's: NaN = no value, NaNs are dropped per group, n1' and n2' kept, the row is tested when
+ *  n1' >= 3 and n2' >= 3; tested equals sdice_ranksum's bit for bit.
+ *  With x the kept values of group 1, y those of group 2, M = n1' n2', N = n1' + n2', the M differences d_ij = x_i - y_j in
+ *  ascending order D_(1) <= ... <= D_(M):
+ *    on-grid row (every kept value is a 3-decimal PS value float32(key / 1000), key = 0..1000): d is the INTEGER
+ *      key_x - key_y in thousandths and an order statistic k is reported as (double)k / 1000.0 -- the rule of
+ *      sdice_signedrank, for its reason: equal printed differences must tie;
+ *    any other row: d = (double)x - (double)y, one IEEE float64 subtraction (-0.0 == +0.0).
+ *    shift = the median of D: D_((M+1)/2) for odd M; for even M the mean of the two middle ones, (k_a + k_b) / 2000.0
+ *      on-grid and 0.5 * (D_a + D_b) otherwise.
+ *    rank  = c = max(1, floor(M/2 - zq sqrt(M (N + 1) / 12))), evaluated in float64 as written: the normal approximation
+ *      of the rank-sum null distribution without a tie correction.
+ *    lo = D_(c), hi = D_(M + 1 - c).
+ *  c = 1 means that the interval is the whole range of the differences and that the requested level is NOT reached: the
+ *  groups are too small for it (3 v 3 at 95 % is such a row).  A zero result is +0.0.  A row that keeps a +-inf value
+ *  gets shift = lo = hi = NaN, with tested and rank as usual.  Any other float32 value is legal: signed zeros, subnormals,
+ *  values outside [0, 1], +-FLT_MAX (a difference of 2 FLT_MAX is finite in float64).  Swapping the groups gives
+ *  (-shift, -hi, -lo) and the same rank, bit for bit up to the +0.0 rule.
+ *  Not offered: an exact (qwilcox) rank for small rows, a tie-corrected variance, the paired estimate (the median of the
+ *  Walsh averages), a stratified form. */
+int sdice_shift(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps,
+                const int32_t* g1, int32_t n1, const int32_t* g2, int32_t n2, double zq,
+                uint8_t* tested, double* shift, double* lo, double* hi, int32_t* rank);
+int sdice_shift_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps,
+                    const int32_t* d_g1, int32_t n1, const int32_t* d_g2, int32_t n2, double zq,
+                    uint8_t* d_tested, double* d_shift, double* d_lo, double* d_hi, int32_t* d_rank);
+
 /* ---- correlate: Spearman rank correlation of the PS values of m listed columns with one covariate value per listed
  *      column, per row scipy.stats.spearmanr(x_kept, ps_kept) under the row rules above (not in the reference).
  *  The covariate does not cross the ABI.  cols[m]: the columns sorted by covariate value, ties in table order; xg[m]: the

@@ -64,6 +64,8 @@ SIGNATURES = {
     "sdice_ranksum_strata_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32] + [vp] * 8,
     "sdice_ks": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32] + [vp] * 9,
     "sdice_ks_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32] + [vp] * 9,
+    "sdice_shift": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_double] + [vp] * 5,
+    "sdice_shift_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_double] + [vp] * 5,
     "sdice_spearman": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 6,
     "sdice_spearman_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 6,
     "sdice_sample_gram": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32] + [vp] * 4,

@@ -34,6 +34,12 @@ difference between the two distributions -- a junction switched on in part of a 
 `--exact` the rows that keep at most 32 values get the exact conditional p-value.  Not with --paired, -mx, --strata or
 --trend.
 
+A seventh: `--shift` adds the size of the difference that belongs to the rank-sum test: the Hodges-Lehmann shift (the median
+of all pairwise differences set 1 - set 2) and its distribution-free confidence interval at `--conf LEVEL` (0.95), two
+order statistics of the same differences (sdice_shift; R's wilcox.test(conf.int = TRUE) reports the same interval).  The
+test stays the rank-sum test (the exact one with `--exact`) and every other cell is what it is without the flag; the table
+gains `shift shift_lo shift_hi` before `p-value`.  Not with --paired, -mx, --trend, --ks or --strata.
+
 On the GPU: the per-row loop :216-232 (NaN drop, <3 skip, scipy ranksums, medians, means)
 -> sdice_ranksum; multipletests(..., "fdr_bh") :235 -> sdice_bh over the tested rows.
 The GTF annotation columns are host string work, as in the reference.
@@ -46,7 +52,7 @@ import numpy as np
 
 from . import _cli
 from ._cli import annotation_suffixes, read_annotation, read_ps_table, samples_from_manifest, table_header_names  # noqa: F401
-from .engine import (JONCKHEERE_FIELDS, KRUSKAL_FIELDS, KS_FIELDS, RANKSUM_EXACT_FIELDS, RANKSUM_FIELDS, Context,
+from .engine import (JONCKHEERE_FIELDS, KRUSKAL_FIELDS, KS_FIELDS, RANKSUM_EXACT_FIELDS, RANKSUM_FIELDS, SHIFT_FIELDS, Context,
                      field_shapes)
 
 MAX_STRATA = 64                     # strata a call accepts (include/sdice.h)
@@ -78,17 +84,37 @@ def tested(ctx, matrix, fields, inputs, dev, host=None, k=None):
     return keep, r
 
 
-def compare(matrix, g1_idx, g2_idx, ctx, paired=False, exact=False):
+# --shift: the fields of the shift call as they ride beside the rank-sum ones in one device pass (its own `tested` and
+# the rank stay behind), and the three that reach the table
+SHIFT_RIDERS = [("shift_" + f[0], f[1]) for f in SHIFT_FIELDS if f[0] != "shift"] + [("shift", np.float64)]
+SHIFT_COLUMNS = ("shift", "shift_lo", "shift_hi")
+
+
+def compare(matrix, g1_idx, g2_idx, ctx, paired=False, exact=False, conf=None):
     """-> (kept row indices, dict of compacted per-row results incl. BH-corrected p).  paired: g1_idx[q] and g2_idx[q]
     are the columns of pair q and the test is the signed-rank test.  exact: exact p-values on the small rows (BH runs
-    over the mixed p vector)."""
+    over the mixed p vector).  conf: the level of --shift; the shift call then reads the same resident table in the same
+    pass and the results gain SHIFT_COLUMNS."""
     if hasattr(ctx, "ranksum_dev") and matrix.shape[0]:
         test = row_test(ctx, paired, exact, dev=True)
-        return tested(ctx, matrix, RANKSUM_EXACT_FIELDS if exact else RANKSUM_FIELDS,
-                      dict(g1=(g1_idx, np.int32), g2=(g2_idx, np.int32)), lambda d, out: test(d["ps"], d["g1"], d["g2"], out))
+
+        def launch(d, out):
+            test(d["ps"], d["g1"], d["g2"], out)
+            if conf is not None:
+                ctx.shift_resident(d["ps"], d["g1"], d["g2"], {f[0]: out["shift" if f[0] == "shift" else "shift_" + f[0]]
+                                                          for f in SHIFT_FIELDS}, conf)
+
+        keep, r = tested(ctx, matrix, (RANKSUM_EXACT_FIELDS if exact else RANKSUM_FIELDS) + (SHIFT_RIDERS if conf is not None else []),
+                         dict(g1=(g1_idx, np.int32), g2=(g2_idx, np.int32)), launch)
+        for name in ("shift_tested", "shift_rank"):
+            r.pop(name, None)
+        return keep, r
     res = row_test(ctx, paired, exact)(matrix, g1_idx, g2_idx)
     keep = np.flatnonzero(res["tested"])
     out = {k: res[k][keep] for k in ("p", "med1", "med2", "mean1", "mean2", "delta")}
+    if conf is not None:
+        sh = ctx.shift(matrix, g1_idx, g2_idx, conf)
+        out.update(shift=sh["shift"][keep], shift_lo=sh["lo"][keep], shift_hi=sh["hi"][keep])
     out["corrected"] = ctx.bh(out["p"]) if keep.size else np.zeros(0)
     return keep, out
 
@@ -156,6 +182,17 @@ def add_parser(parser):
                              "(scipy.special.kolmogorov, no finite-n correction); with --exact the rows that keep at "
                              "most 32 values get the exact conditional p-value given their ties (R's ks.test(exact = "
                              "TRUE)).  Not with --paired, -mx, --strata or --trend (not part of the reference)")
+    parser.add_argument("--shift", action="store_true",
+                        help="Add the Hodges-Lehmann shift of set 1 against set 2 -- the median of all pairwise differences, "
+                             "the estimate that belongs to the rank-sum test -- and its distribution-free confidence "
+                             "interval (two order statistics of the same differences; R's wilcox.test(conf.int = TRUE)): "
+                             "the table gains the columns shift, shift_lo and shift_hi before p-value, every other column "
+                             "is what it is without the flag (with --exact: the exact p-values).  On rows of 3-decimal PS "
+                             "values the differences are whole thousandths.  With small sets the interval is the whole "
+                             "range of the differences and the level is not reached (3 v 3 at 95 %%).  Not with --paired, "
+                             "-mx, --trend, --ks or --strata (not part of the reference)")
+    parser.add_argument("--conf", type=float, required=False, default=None, metavar="LEVEL",
+                        help="With --shift: the confidence level of the interval, 0 < LEVEL < 1 (default 0.95)")
     parser.add_argument("-a", "--annotation", type=str, required=False, default="",
                         help="Optional GTF file to label known splice junctions and genes")
     parser.add_argument("-o", "--outputFile", type=str, required=True,
@@ -207,8 +244,8 @@ class Test(typing.NamedTuple):
     (other flag, why) it cannot be combined with; `multi_rank`, why it does not run under the multi-rank launcher.  A row
     that replaces the rank-sum pipeline (--exact and --paired are forms of it: compare()) says how: `fields`, the
     engine's table of its _dev call; sel -> `inputs`, the device inputs beside the table; (ctx, sel) -> `dev`, the launch
-    on them; (ctx, matrix, sel) -> `host`, the host call; sel -> `k`, the number of sets of its per-set fields; `stat`, the
-    header cell and the result key of its statistic column."""
+    on them; (ctx, matrix, sel) -> `host`, the host call; sel -> `k`, the number of sets of its per-set fields.  `stat`: the
+    (header cell, result key) of every column the row adds between delta and p-value."""
     flag: str
     conflicts: tuple = ()
     needs: tuple = None
@@ -218,7 +255,7 @@ class Test(typing.NamedTuple):
     dev: typing.Callable = None
     host: typing.Callable = None
     k: typing.Callable = lambda sel: None
-    stat: tuple = None
+    stat: tuple = ()
 
     def refuse(self, why):
         _cli.refusal(f"compare_sample_sets {self.flag.split('/')[0]}")(why)
@@ -241,14 +278,24 @@ def _k_sets(test):
 
 
 PAIRED, EXACT, STRATA, TREND, KS, MX = "--paired", "--exact", "--strata", "--trend", "--ks", "-mx/--moreManifests"
+SHIFT, CONF = "--shift", "--conf"
 # in the order the refusals are made; the first selected row with a pipeline is the test that runs
 TESTS = (
+    Test(CONF, needs=(SHIFT, "it is the level of the shift's confidence interval")),
+    # (keeps the rank-sum pipeline, as --exact does: compare() adds the shift call to the same pass)
+    Test(SHIFT, conflicts=((PAIRED, "the paired estimate is the median of the Walsh averages, which is not offered"),
+                           (MX, "the shift is an estimate between two sets"),
+                           (TREND, "the shift is an estimate between two sets"),
+                           (KS, "the shift belongs to the rank-sum test"),
+                           (STRATA, "there is no stratified shift here")),
+         multi_rank=_multi_rank(SHIFT, "the packed all-gather carries the rank-sum fields only"),
+         stat=tuple((name, name) for name in SHIFT_COLUMNS)),
     Test(KS, conflicts=((PAIRED, "the signed-rank test compares matched samples; this test compares two distributions"),
                         (TREND, "the trend test orders three or more sets"),
                         (MX, "there is no k-sample Kolmogorov-Smirnov test here"),
                         (STRATA, "there is no stratified Kolmogorov-Smirnov test here")),
          multi_rank=_multi_rank(KS, "the packed all-gather carries the rank-sum fields only"),
-         fields=KS_FIELDS, inputs=_two_sets, stat=("D", "d"),
+         fields=KS_FIELDS, inputs=_two_sets, stat=(("D", "d"),),
          dev=lambda ctx, sel: lambda d, out: ctx.ks_dev(d["ps"], d["g1"], d["g2"], out, sel.exact),
          host=lambda ctx, matrix, sel: ctx.ks(matrix, sel.g1_idx, sel.g2_idx, sel.exact)),
     Test(TREND, needs=(MX, "three or more ordered sets; two sets are the rank-sum test"),
@@ -256,7 +303,7 @@ TESTS = (
                     (EXACT, "the trend test is asymptotic only"),
                     (STRATA, "there is no stratified trend test here")),
          multi_rank=_multi_rank(TREND, "the packed all-gather carries the two-set fields only"),
-         fields=JONCKHEERE_FIELDS, stat=("z", "z"), **_k_sets("jonckheere")),
+         fields=JONCKHEERE_FIELDS, stat=(("z", "z"),), **_k_sets("jonckheere")),
     Test(EXACT, conflicts=((MX, "there is no exact Kruskal-Wallis test here"),)),
     Test(STRATA, conflicts=((PAIRED, "the signed-rank test pairs samples one to one"),
                             (MX, "there is no stratified Kruskal-Wallis test here"),
@@ -269,7 +316,7 @@ TESTS = (
     Test(PAIRED, conflicts=((MX, "the signed-rank test compares two matched sets"),)),
     # k >= 3 sets: Kruskal-Wallis per junction (--trend above: Jonckheere-Terpstra over the sets in this order)
     Test(MX, multi_rank=_multi_rank(MX, "the packed all-gather carries the two-set fields only"),
-         fields=KRUSKAL_FIELDS, stat=("H", "h"), **_k_sets("kruskal")),
+         fields=KRUSKAL_FIELDS, stat=(("H", "h"),), **_k_sets("kruskal")),
 )
 BY_FLAG = {t.flag: t for t in TESTS}
 KS_MULTI_RANK_REFUSAL, TREND_MULTI_RANK_REFUSAL, STRATA_MULTI_RANK_REFUSAL, MULTI_RANK_REFUSAL = (
@@ -285,9 +332,15 @@ def run_with(args, ctx=None):
     g2 = samples_from_manifest(args.manifest2)
     more = [samples_from_manifest(m) for m in (getattr(args, "moreManifests", None) or [])]
     on = {PAIRED: getattr(args, "paired", False), EXACT: getattr(args, "exact", False), STRATA: getattr(args, "strata", None),
-          TREND: getattr(args, "trend", False), KS: getattr(args, "ks", False), MX: more}
+          TREND: getattr(args, "trend", False), KS: getattr(args, "ks", False), MX: more,
+          SHIFT: getattr(args, "shift", False), CONF: getattr(args, "conf", None) is not None}
     chosen = [t for t in TESTS if on[t.flag]]
     sel = argparse.Namespace(exact=bool(on[EXACT]))
+    conf = None
+    if on[SHIFT]:
+        conf = float(args.conf) if on[CONF] else 0.95
+        if not 0.0 < conf < 1.0:                  # (NaN included)
+            BY_FLAG[CONF].refuse(f"LEVEL must satisfy 0 < LEVEL < 1 (got {args.conf})")
     for t in chosen:
         if t.needs and not on[t.needs[0]]:
             t.refuse(f"needs {t.needs[0]} ({t.needs[1]})")
@@ -321,17 +374,17 @@ def run_with(args, ctx=None):
         elif L.world > 1:
             keep, r = compare_sharded(matrix, sel.g1_idx, sel.g2_idx, ctx, L, bool(on[PAIRED]), sel.exact)
         else:
-            keep, r = compare(matrix, sel.g1_idx, sel.g2_idx, ctx, bool(on[PAIRED]), sel.exact)
+            keep, r = compare(matrix, sel.g1_idx, sel.g2_idx, ctx, bool(on[PAIRED]), sel.exact, conf)
     if not L.root:
         return                       # one set of output files: rank 0 writes the table
     # the library's multithreaded formatter (numpy str() of float32 / float64 per column, byte-identical to the
-    # reference's print(*fields, sep="\t")); columns: event mean1..meank median1..mediank delta [statistic] p-value corrected
+    # reference's print(*fields, sep="\t")); columns: event mean1..meank median1..mediank delta [statistics] p-value corrected
     k = 2 + len(more)
     means, medians = (r["mean"], r["med"]) if more else ((r["mean1"], r["mean2"]), (r["med1"], r["med2"]))
-    stat = test.stat if test and test.stat else None
+    stat = [cell for t in chosen if t is test or not t.dev for cell in t.stat]
     header = "\t".join(["event"] + [f"mean{i + 1}" for i in range(k)] + [f"median{i + 1}" for i in range(k)] + ["delta"] +
-                       ([stat[0]] if stat else []) + ["p-value", "corrected"])
-    columns = [*means, *medians, r["delta"]] + ([r[stat[1]]] if stat else []) + [r["p"], r["corrected"]]
+                       [cell for cell, _ in stat] + ["p-value", "corrected"])
+    columns = [*means, *medians, r["delta"]] + [r[key] for _, key in stat] + [r["p"], r["corrected"]]
     _cli.write_event_table(args.outputFile, header, rows, keep, columns, ["repr"] * len(columns), args.annotation)
 
 

@@ -17,7 +17,7 @@ int check_columns(const char* fn, std::initializer_list<const int32_t*> lists, i
 // (that refusal names `fn`) and no more than the table has
 int kw_check_sets(const char* fn, const int32_t* set_ptr, int32_t k, int32_t s);
 
-// Two column groups of their own lengths (strata.hip, ks.hip), at most `limit` columns each; max_strata != 0: every
+// Two column groups of their own lengths (strata.hip, ks.hip, shift.hip), at most `limit` columns each; max_strata != 0: every
 // column carries a stratum id in [0, n_strata), 1 <= n_strata <= max_strata.  In this order:
 //   the lists, when they are given and every count is in range: an index outside the table, a column listed twice over
 //   both lists, a stratum id out of range (entry by entry, g1 first);

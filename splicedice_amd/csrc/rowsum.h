@@ -28,6 +28,9 @@
 //                         block_pairwise_sum, block_bitonic, two_group_median_key, median_of_ord, store_two_sample, the
 //                         launch sizes, with_group_width; TwoSampleOut (D in the z slot), zero_two_sample,
 //                         TwoSampleStaging (with `exact`), check_two_groups
+//   shift.hip (K20)       PsKey, f32_ord / f32_unord, LaneGroup, group_add / group_sort, block_bitonic,
+//                         two_group_median_key, kw_load_bins / kw_scan_bins, the launch sizes, with_group_width;
+//                         check_two_groups (its own five outputs and their staging)
 // (strata.hip and ks.hip: the pass front of the group kernels and the LDS + sums of the block kernels stay written out, A.17)
 // Every helper is inlined into the kernels that call it and the kernels themselves stay in their .hip files, so a change
 // to a helper here is a change to each kernel that uses it -- ranksum.hip's pairq and count kernels among them, whose

@@ -24,6 +24,7 @@ RANKSUM_FIELDS = [("tested", np.uint8), ("p", np.float64), ("z", np.float64), ("
 RANKSUM_EXACT_FIELDS = RANKSUM_FIELDS + [("exact", np.uint8)]                                # (the two --exact calls)
 KS_FIELDS = [("tested", np.uint8), ("p", np.float64), ("d", np.float64), ("med1", np.float32), ("med2", np.float32),
              ("mean1", np.float32), ("mean2", np.float32), ("delta", np.float32), ("exact", np.uint8)]
+SHIFT_FIELDS = [("tested", np.uint8), ("shift", np.float64), ("lo", np.float64), ("hi", np.float64), ("rank", np.int32)]
 KRUSKAL_FIELDS = [("tested", np.uint8), ("p", np.float64), ("h", np.float64), ("med", np.float32, PER_SET),
                   ("mean", np.float32, PER_SET), ("delta", np.float32)]
 JONCKHEERE_FIELDS = [("tested", np.uint8), ("p", np.float64), ("z", np.float64), ("j", np.float64),
@@ -77,6 +78,16 @@ def kruskal_sets(sets, s=None):
                 raise ValueError(f"kruskal: column {c} is in set {seen[c] + 1} and in set {i + 1}; a column may belong to one set only")
             seen[c] = i
     return np.ascontiguousarray(cols, dtype=np.int32), set_ptr
+
+
+def shift_quantile(conf):
+    """the confidence level of a shift interval, 0 < conf < 1 -> zq, the standard normal quantile at 1 - (1 - conf) / 2, as
+    sdice_shift takes it (the standard library's NormalDist: no scipy on the product path)"""
+    import statistics
+    conf = float(conf)
+    if not 0.0 < conf < 1.0:
+        raise ValueError(f"shift: the confidence level must satisfy 0 < conf < 1, got {conf!r}")
+    return statistics.NormalDist().inv_cdf(1.0 - (1.0 - conf) / 2.0)
 
 
 def strata_ids(labels):
@@ -410,6 +421,18 @@ class Context:
                                 *map(_ptr, out.values())), "sdice_ks")
         return out
 
+    def shift(self, ps, g1, g2, conf=0.95):
+        """the Hodges-Lehmann shift of group 1 against group 2 per row with its confidence interval at level conf
+        (include/sdice.h): un-compacted tested (ranksum()'s), shift (the median of the pairwise differences), lo and hi (two
+        order statistics of them) and rank (which ones; 1 = the whole range, the level is not reached)."""
+        ps = _c(ps, np.float32)
+        n, s = ps.shape
+        g1, g2 = _c(g1, np.int32).reshape(-1), _c(g2, np.int32).reshape(-1)
+        out = _zeros(SHIFT_FIELDS, n)
+        check(self.lib.sdice_shift(self.h, n, s, _ptr(ps), _ptr(g1), g1.size, _ptr(g2), g2.size, shift_quantile(conf),
+                                   *map(_ptr, out.values())), "sdice_shift")
+        return out
+
     def kruskal(self, ps, sets):
         """scipy.stats.kruskal per row across the k column sets under the row rules of ranksum(); un-compacted outputs:
         tested, p, h [n], med, mean [k, n] (set-major), delta [n] = largest minus smallest set median."""
@@ -603,6 +626,16 @@ class Context:
             raise ValueError("ks_dev: every field of KS_FIELDS but d and exact is required")
         check(self.lib.sdice_ks_dev(self.h, n, s, d_ps.ptr, d_g1.ptr, d_g1.shape[0], d_g2.ptr, d_g2.shape[0],
                                     int(bool(exact)), *_dev_ptrs(KS_FIELDS, out, optional)), "sdice_ks_dev")
+
+    def shift_resident(self, d_ps, d_g1, d_g2, out, conf=0.95):
+        """sdice_shift_dev: shift() on a resident table and resident lists; out: the device fields of SHIFT_FIELDS, all of
+        them.  (Not named *_dev: tests/test_call_order_fixtures_cpu.py wants every method of that name in the catalogue of
+        tests/call_order_fixtures.py; this call has its own, tests/test_gpu_shift_call_order.py.)"""
+        n, s = d_ps.shape
+        if any(not out.get(f[0]) for f in SHIFT_FIELDS):
+            raise ValueError("shift_resident: every field of SHIFT_FIELDS is required")
+        check(self.lib.sdice_shift_dev(self.h, n, s, d_ps.ptr, d_g1.ptr, d_g1.shape[0], d_g2.ptr, d_g2.shape[0],
+                                       shift_quantile(conf), *_dev_ptrs(SHIFT_FIELDS, out)), "sdice_shift_dev")
 
     def signedrank_dev(self, d_ps, d_a, d_b, out):
         n, s = d_ps.shape
