@@ -1454,9 +1454,7 @@ int sd_bh_cols_samplesort(sdice_ctx* ctx, int64_t m, int64_t segs, double* d_rm,
     if (B > 1) {
         SD_HIP(hipMemsetAsync(a.gcount, 0, sb * 4, ctx->stream));
         const size_t lds_s = (size_t)a.S2 * 12;
-        SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bhs_sample_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
-        SD_LAUNCH(ctx, "bhs_sample_kernel", bhs_sample_kernel, dim3((unsigned)segs), dim3(256), lds_s, a);
+        SD_LAUNCH_LDS(ctx, "bhs_sample_kernel", bhs_sample_kernel, dim3((unsigned)segs), dim3(256), lds_s, a);
         const size_t lds_t = (size_t)B * 20;
         const int64_t tiles = sd_ceil_div(m, (int64_t)TILE);
         const int64_t tile_blocks = sd_ceil_div(segs, (int64_t)8) * 8 * tiles;
@@ -1485,9 +1483,7 @@ int sd_bh_cols_samplesort(sdice_ctx* ctx, int64_t m, int64_t segs, double* d_rm,
     } else if (wg_threads == 512) {
         SD_LAUNCH(ctx, "bhs_bucket_kernel", (bhs_bucket_kernel<512>), dim3((unsigned)bucket_blocks), dim3(512), (bucket_wg_lds<512, 4>()), a);
     } else {
-        SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bhs_bucket_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)bucket_wg_lds<1024, 4>()));
-        SD_LAUNCH(ctx, "bhs_bucket_kernel", (bhs_bucket_kernel<1024>), dim3((unsigned)bucket_blocks), dim3(1024), (bucket_wg_lds<1024, 4>()), a);
+        SD_LAUNCH_LDS(ctx, "bhs_bucket_kernel", (bhs_bucket_kernel<1024>), dim3((unsigned)bucket_blocks), dim3(1024), (bucket_wg_lds<1024, 4>()), a);
     }
     const int64_t big_blocks = std::max<int64_t>(1, std::min<int64_t>(n_buckets, (int64_t)ctx->n_cu * 4));
     // the listed buckets of 1 025 ... 2 048 values: 512 threads x 4 values (109 VGPRs) take 0.61 ms on the bench's table where
@@ -1583,8 +1579,7 @@ int sd_bh_vector_samplesort(sdice_ctx* ctx, int64_t n, const double* d_p, const 
     const size_t lds_t = (size_t)B * 20;
     SD_LAUNCH(ctx, "bhv_scatter_kernel", bhv_scatter_kernel, dim3(tiles), dim3(BHV_T), lds_t, a);
     const size_t lds_b = (((size_t)a.cap * 13 + 15) / 16) * 16;
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bhv_bucket_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));
-    SD_LAUNCH(ctx, "bhv_bucket_kernel", bhv_bucket_kernel, dim3((unsigned)B), dim3(BHV_T), lds_b, a);
+    SD_LAUNCH_LDS(ctx, "bhv_bucket_kernel", bhv_bucket_kernel, dim3((unsigned)B), dim3(BHV_T), lds_b, a);
     SD_LAUNCH(ctx, "bhv_finish_kernel", bhv_finish_kernel, dim3(tiles), dim3(BHV_T), 0, a);
     return SDICE_OK;
 }

@@ -77,9 +77,8 @@ static int chi2_launch(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* d_in
     if (blocks > cap) blocks = cap;
     const size_t lds = (size_t)s * 16;
     auto kern = d_list ? chi2_pairs_kernel<true> : chi2_pairs_kernel<false>;
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SD_LAUNCH(ctx, "chi2_pairs_kernel", kern, dim3((unsigned)blocks), dim3(256), lds, d_incl, d_excl, n, (int)s, n_pairs,
-              (const unsigned*)d_list, d_p, reinterpret_cast<unsigned long long*>(d_n_bad));
+    SD_LAUNCH_LDS(ctx, "chi2_pairs_kernel", kern, dim3((unsigned)blocks), dim3(256), lds, d_incl, d_excl, n, (int)s, n_pairs,
+                  (const unsigned*)d_list, d_p, reinterpret_cast<unsigned long long*>(d_n_bad));
     return SDICE_OK;
 }
 

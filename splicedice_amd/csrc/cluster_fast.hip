@@ -1258,20 +1258,14 @@ extern "C" int sdice_cluster_dev(sdice_ctx* ctx, int64_t n, const int32_t* d_chr
         const size_t lds = (size_t)a.B * 16;
         // tiles of 2048 keys (512 threads) for small inputs, 4096 (1024 threads) beyond
         if (n <= (1 << 19)) {      // (4096-key tiles halve the global atomics: 27.5 -> 21.4 us at 1 M keys)
-            SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bucket_scatter_kernel<512>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            SD_LAUNCH(ctx, "bucket_scatter_kernel", (bucket_scatter_kernel<512>), dim3(grid_for(n, 512 * SC_KPT)), dim3(512), lds, a);
+            SD_LAUNCH_LDS(ctx, "bucket_scatter_kernel", (bucket_scatter_kernel<512>), dim3(grid_for(n, 512 * SC_KPT)), dim3(512), lds, a);
         } else {
-            SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bucket_scatter_kernel<1024>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            SD_LAUNCH(ctx, "bucket_scatter_kernel", (bucket_scatter_kernel<1024>), dim3(grid_for(n, 1024 * SC_KPT)), dim3(1024), lds, a);
+            SD_LAUNCH_LDS(ctx, "bucket_scatter_kernel", (bucket_scatter_kernel<1024>), dim3(grid_for(n, 1024 * SC_KPT)), dim3(1024), lds, a);
         }
     }
     {
         const size_t lds = SORT_LDS_BYTES;
-        SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bucket_sort_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        SD_LAUNCH(ctx, "bucket_sort_kernel", bucket_sort_kernel, dim3((unsigned)a.B), dim3(SORT_T), lds, a);
+        SD_LAUNCH_LDS(ctx, "bucket_sort_kernel", bucket_sort_kernel, dim3((unsigned)a.B), dim3(SORT_T), lds, a);
     }
     SD_TRY(launch_neighbours(ctx, pl));
 

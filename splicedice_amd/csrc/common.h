@@ -7,6 +7,7 @@
 #include <vector>
 #include "sdice.h"
 #include "params.h"
+#include "stagelayout.h"
 
 void sdice_set_error(const char* fmt, ...);
 
@@ -128,11 +129,22 @@ int sd_prof_drain(sdice_ctx* ctx);
         SD_HIP(hipGetLastError());                                                     \
     } while (0)
 
+// SD_LAUNCH of a kernel that takes `shmem` bytes of dynamic LDS, its limit raised to that first
+#define SD_LAUNCH_LDS(ctx, name, kernel, grid, block, shmem, ...)                      \
+    do {                                                                               \
+        SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),              \
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(shmem))); \
+        SD_LAUNCH(ctx, name, kernel, grid, block, shmem, __VA_ARGS__);                 \
+    } while (0)
+
 static inline int64_t sd_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// Device copies of a host entry point's arguments, from sdice_dmalloc (256 B minimum: a count of 0 still yields a valid
-// buffer).  Not from ctx->arena, which the _dev callees reset.  Freed when the object goes out of scope, after the context
-// stream has drained; the results of those calls are ignored so that the error of the failure that ended the call stays.
+// Device copies of a host entry point's arguments and results, from sdice_dmalloc (256 B minimum: a count of 0 still
+// yields a valid buffer).  Not from ctx->arena, which the _dev callees reset.  Freed when the object goes out of scope,
+// after the context stream has drained; the results of those calls are ignored so that the error of the failure that
+// ended the call stays.  The arguments are a buffer each (alloc / upload).  The results are one block: result()
+// registers a field, alloc_results() allocates the block and hands every field its device pointer (256-byte aligned,
+// stagelayout.h), download_results() copies the fields out.
 class HostStaging {
   public:
     explicit HostStaging(sdice_ctx* ctx) : ctx_(ctx) {}
@@ -157,9 +169,28 @@ class HostStaging {
         return sdice_d2h(ctx_, h, d, count * (int64_t)sizeof(T));
     }
 
+    // A result field of `count` elements: *d is its device pointer once alloc_results() has run, h the caller's array
+    // (NULL: an output the caller does not want; the field is there all the same, it is only not copied out)
+    template <class T> void result(T** d, T* h, int64_t count) {
+        fields_.push_back({d, h, count * (int64_t)sizeof(T),
+                           [](void* slot, char* p) { *static_cast<T**>(slot) = reinterpret_cast<T*>(p); }});
+    }
+    // one sdice_dmalloc for the fields registered so far
+    int alloc_results();
+    // synchronous copies of the fields with a host array, in the order of registration
+    int download_results();
+
   private:
+    struct Field {
+        void* slot;       // where the device pointer goes
+        void* host;
+        int64_t bytes;
+        void (*set)(void* slot, char* p);
+        char* dev;
+    };
     sdice_ctx* ctx_;
     std::vector<void*> bufs_;
+    std::vector<Field> fields_;
 };
 
 // Argument check of a host CSR neighbour list (n_out rows into n_rows): row_ptr starts at 0 and never decreases, every

@@ -211,6 +211,24 @@ HostStaging::~HostStaging() {
     for (void* p : bufs_) (void)hipFree(p);
 }
 
+int HostStaging::alloc_results() {
+    std::vector<int64_t> bytes, offsets(fields_.size());
+    for (const Field& f : fields_) bytes.push_back(f.bytes);
+    char* block = nullptr;
+    SD_TRY(alloc(&block, sd_stage_layout(bytes.data(), (int)fields_.size(), offsets.data())));
+    for (size_t i = 0; i < fields_.size(); ++i) {
+        fields_[i].dev = block + offsets[i];
+        fields_[i].set(fields_[i].slot, fields_[i].dev);
+    }
+    return SDICE_OK;
+}
+
+int HostStaging::download_results() {
+    for (const Field& f : fields_)
+        if (f.host) SD_TRY(sdice_d2h(ctx_, f.host, f.dev, f.bytes));
+    return SDICE_OK;
+}
+
 // Test support: the memory a later call finds as the earlier one left it.  The order is fixed: arena chunks, col, reach.
 extern "C" int sdice_scratch_region(sdice_ctx* ctx, int32_t index, const char** name, void** dptr, int64_t* bytes) {
     SD_ARG(ctx, "ctx is NULL");

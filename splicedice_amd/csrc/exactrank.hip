@@ -319,17 +319,17 @@ extern "C" int sdice_ranksum_exact(sdice_ctx* ctx, int64_t n, int32_t s, const f
     for (int i = 0; i < n2; ++i) SD_ARG(g2[i] >= 0 && g2[i] < s, "g2 index out of range");
     SD_ARG(ps, "ps is NULL");
     HostStaging st(ctx);
-    TwoSampleStaging res;
+    TwoSampleOut o;
+    uint8_t* d_exact;
     float* d_ps;
     int32_t *dg1, *dg2;
     SD_TRY(st.upload(&d_ps, ps, n * s));
     SD_TRY(st.upload(&dg1, g1, n1));
     SD_TRY(st.upload(&dg2, g2, n2));
-    SD_TRY(res.alloc(st, n, true));
-    const TwoSampleOut o = res.out();
+    SD_TRY(stage_two_sample(st, n, {tested, p, z, med1, med2, mean1, mean2, delta}, &o, exact, &d_exact));
     SD_TRY(sdice_ranksum_exact_dev(ctx, n, s, d_ps, dg1, n1, dg2, n2, o.tested, o.p, o.z, o.med1, o.med2, o.mean1, o.mean2,
-                                   o.delta, res.exact()));
-    return res.download(st, {tested, p, z, med1, med2, mean1, mean2, delta}, exact);
+                                   o.delta, d_exact));
+    return st.download_results();
 }
 
 extern "C" int sdice_signedrank_exact_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, const int32_t* d_a,
@@ -363,15 +363,15 @@ extern "C" int sdice_signedrank_exact(sdice_ctx* ctx, int64_t n, int32_t s, cons
     SD_ARG(tested && p && med1 && med2 && mean1 && mean2 && delta && exact, "NULL output");
     SD_ARG(ps, "ps is NULL");
     HostStaging st(ctx);
-    TwoSampleStaging res;
+    TwoSampleOut o;
+    uint8_t* d_exact;
     float* d_ps;
     int32_t *da, *db;
     SD_TRY(st.upload(&d_ps, ps, n * s));
     SD_TRY(st.upload(&da, a, m));
     SD_TRY(st.upload(&db, b, m));
-    SD_TRY(res.alloc(st, n, true));
-    const TwoSampleOut o = res.out();
+    SD_TRY(stage_two_sample(st, n, {tested, p, z, med1, med2, mean1, mean2, delta}, &o, exact, &d_exact));
     SD_TRY(sdice_signedrank_exact_dev(ctx, n, s, d_ps, da, db, m, o.tested, o.p, o.z, o.med1, o.med2, o.mean1, o.mean2, o.delta,
-                                      res.exact()));
-    return res.download(st, {tested, p, z, med1, med2, mean1, mean2, delta}, exact);
+                                      d_exact));
+    return st.download_results();
 }

@@ -315,13 +315,14 @@ extern "C" int sdice_sample_gram(sdice_ctx* ctx, int64_t n, int32_t s, const flo
     HostStaging st(ctx);
     float* d_ps;
     int32_t* dc;
-    int64_t* d_out;
+    int64_t *d_shared, *d_sum1, *d_sum2, *d_prod;
     SD_TRY(st.upload(&d_ps, ps, n * s));
     SD_TRY(st.upload(&dc, cols, m));
-    SD_TRY(st.alloc(&d_out, 4 * mm));
-    SD_TRY(sdice_sample_gram_dev(ctx, n, s, d_ps, dc, m, d_out, d_out + mm, d_out + 2 * mm, d_out + 3 * mm));
-    SD_TRY(st.download(shared, d_out, mm));
-    SD_TRY(st.download(sum1, d_out + mm, mm));
-    SD_TRY(st.download(sum2, d_out + 2 * mm, mm));
-    return st.download(prod, d_out + 3 * mm, mm);
+    st.result(&d_shared, shared, mm);
+    st.result(&d_sum1, sum1, mm);
+    st.result(&d_sum2, sum2, mm);
+    st.result(&d_prod, prod, mm);
+    SD_TRY(st.alloc_results());
+    SD_TRY(sdice_sample_gram_dev(ctx, n, s, d_ps, dc, m, d_shared, d_sum1, d_sum2, d_prod));
+    return st.download_results();
 }

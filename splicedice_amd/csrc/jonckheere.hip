@@ -316,22 +316,8 @@ extern "C" int sdice_jonckheere_dev(sdice_ctx* ctx, int64_t n, int32_t s, const 
     SD_TRY(ctx->arena.reset(ctx->stream));
     const KwPlan pl = kw_plan(set_ptr, k);
     JtOut o{d_tested, d_p, d_z, d_j, d_med, d_mean, d_delta};
-    {   // grid path
-        const int ch = rows_per_chunk(ctx->n_cu, n);
-        const int64_t blocks = wave_launch_blocks(ctx, n, ch, pl.waves);
-        SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(jonckheere_grid_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.grid_lds));
-        SD_LAUNCH(ctx, "jonckheere_grid_kernel", jonckheere_grid_kernel, dim3((unsigned)blocks), dim3(pl.waves * 64), pl.grid_lds,
-                  d_ps, n, (int)s, d_cols, pl.sets, (int)k, ch, pl.wstride, pl.leaf_cap, o);
-    }
-    {   // the rows it marked KW_REDO
-        const int64_t blocks = row_launch_blocks(ctx, sd_ceil_div(n, RB_THREADS));
-        SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(jonckheere_block_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.block_lds));
-        SD_LAUNCH(ctx, "jonckheere_block_kernel", jonckheere_block_kernel, dim3((unsigned)blocks), dim3(RB_THREADS), pl.block_lds,
-                  d_ps, n, (int)s, d_cols, pl.sets, (int)k, pl.P, 1, o);
-    }
-    return SDICE_OK;
+    return kw_launch_pair<jonckheere_grid_kernel, jonckheere_block_kernel>(ctx, "jonckheere_grid_kernel", "jonckheere_block_kernel",
+                                                                           pl, d_ps, n, s, d_cols, k, o);
 }
 
 extern "C" int sdice_jonckheere(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps, const int32_t* cols,
@@ -347,22 +333,19 @@ extern "C" int sdice_jonckheere(sdice_ctx* ctx, int64_t n, int32_t s, const floa
     SD_ARG(tested && p && z && med && mean && delta, "NULL output");
     SD_ARG(ps, "ps is NULL");
     HostStaging st(ctx);
-    float *d_ps, *df;
+    float* d_ps;
     int32_t* dcols;
-    uint8_t* dt;
-    double* dd;
+    JtOut d;
     SD_TRY(st.upload(&d_ps, ps, n * s));
     SD_TRY(st.upload(&dcols, cols, nsel));
-    SD_TRY(st.alloc(&dt, n));
-    SD_TRY(st.alloc(&dd, n * 3));                    // p, z, j
-    SD_TRY(st.alloc(&df, n * (2 * (int64_t)k + 1))); // med[k][n], mean[k][n], delta
-    SD_TRY(sdice_jonckheere_dev(ctx, n, s, d_ps, dcols, set_ptr, k, dt, dd, dd + n, dd + 2 * n, df, df + (int64_t)k * n,
-                                df + 2 * (int64_t)k * n));
-    SD_TRY(st.download(tested, dt, n));
-    SD_TRY(st.download(p, dd, n));
-    SD_TRY(st.download(z, dd + n, n));
-    if (j) SD_TRY(st.download(j, dd + 2 * n, n));
-    SD_TRY(st.download(med, df, (int64_t)k * n));
-    SD_TRY(st.download(mean, df + (int64_t)k * n, (int64_t)k * n));
-    return st.download(delta, df + 2 * (int64_t)k * n, n);
+    st.result(&d.tested, tested, n);
+    st.result(&d.p, p, n);
+    st.result(&d.z, z, n);
+    st.result(&d.j, j, n);
+    st.result(&d.med, med, (int64_t)k * n);          // [k][n]
+    st.result(&d.mean, mean, (int64_t)k * n);
+    st.result(&d.delta, delta, n);
+    SD_TRY(st.alloc_results());
+    SD_TRY(sdice_jonckheere_dev(ctx, n, s, d_ps, dcols, set_ptr, k, d.tested, d.p, d.z, d.j, d.med, d.mean, d.delta));
+    return st.download_results();
 }

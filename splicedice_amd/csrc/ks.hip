@@ -370,21 +370,16 @@ extern "C" int sdice_ks_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d
         return zero_two_sample(ctx, n, o);
     }
     if (m <= KS_GROUP_MAX)
-        return with_group_width(m, [&](auto width) -> int {
-            const int waves = 4;
-            const int ch = rows_per_chunk(ctx->n_cu, n);
-            const int64_t blocks = wave_launch_blocks(ctx, n, ch, waves);
+        return with_group_launch(ctx, n, m, [&](auto width, int ch, int64_t blocks) -> int {
             SD_LAUNCH(ctx, "ks_group_kernel", (ks_group_kernel<decltype(width)::value>), dim3((unsigned)blocks),
-                      dim3(waves * 64), 0, d_ps, n, (int)s, d_g1, (int)n1, d_g2, (int)n2, we, ch, o, d_exact);
+                      dim3(GROUP_WAVES * 64), 0, d_ps, n, (int)s, d_g1, (int)n1, d_g2, (int)n2, we, ch, o, d_exact);
             return SDICE_OK;
         });
     const int P = next_pow2(m, 128);
     const size_t lds = (size_t)P * 8;
     const int64_t blocks = row_launch_blocks(ctx, n);
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ks_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds));
-    SD_LAUNCH(ctx, "ks_block_kernel", ks_block_kernel, dim3((unsigned)blocks), dim3(RB_THREADS), lds, d_ps, n, (int)s, d_g1,
-              (int)n1, d_g2, (int)n2, we, P, o, d_exact);
+    SD_LAUNCH_LDS(ctx, "ks_block_kernel", ks_block_kernel, dim3((unsigned)blocks), dim3(RB_THREADS), lds, d_ps, n, (int)s, d_g1,
+                  (int)n1, d_g2, (int)n2, we, P, o, d_exact);
     return SDICE_OK;
 }
 
@@ -400,15 +395,15 @@ extern "C" int sdice_ks(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps, c
     SD_ARG(!want_exact || exact, "NULL output: exact is required with want_exact");
     SD_ARG(ps, "ps is NULL");
     HostStaging st(ctx);
-    TwoSampleStaging res;
+    TwoSampleOut o;
+    uint8_t* d_exact = nullptr;                                // stays NULL when the caller gave no `exact`
     float* d_ps;
     int32_t *dg1, *dg2;
     SD_TRY(st.upload(&d_ps, ps, n * s));
     SD_TRY(st.upload(&dg1, g1, n1));
     SD_TRY(st.upload(&dg2, g2, n2));
-    SD_TRY(res.alloc(st, n, exact != nullptr));
-    const TwoSampleOut o = res.out();
+    SD_TRY(stage_two_sample(st, n, {tested, p, d, med1, med2, mean1, mean2, delta}, &o, exact, exact ? &d_exact : nullptr));
     SD_TRY(sdice_ks_dev(ctx, n, s, d_ps, dg1, n1, dg2, n2, want_exact, o.tested, o.p, o.z, o.med1, o.med2, o.mean1, o.mean2,
-                        o.delta, exact ? res.exact() : nullptr));
-    return res.download(st, {tested, p, d, med1, med2, mean1, mean2, delta}, exact);
+                        o.delta, d_exact));
+    return st.download_results();
 }

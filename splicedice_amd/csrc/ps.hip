@@ -721,17 +721,13 @@ __global__ void mark_low_kernel(float* __restrict__ ps, const int64_t* __restric
 
 template <int VEC, bool WE, bool WP, bool Q3, int ABL>
 int launch_ps_one(sdice_ctx* ctx, const PsArgs& a, int threads, size_t lds, dim3 grid) {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ps_tile_kernel<VEC, WE, WP, Q3, ABL>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SD_LAUNCH(ctx, "ps_tile_kernel", (ps_tile_kernel<VEC, WE, WP, Q3, ABL>), grid, dim3(threads), lds, a);
+    SD_LAUNCH_LDS(ctx, "ps_tile_kernel", (ps_tile_kernel<VEC, WE, WP, Q3, ABL>), grid, dim3(threads), lds, a);
     return SDICE_OK;
 }
 
 template <bool CH, bool WE, bool WP, bool Q3>
 int launch_ps_v3_one(sdice_ctx* ctx, const PsArgs& a, int threads, size_t lds, dim3 grid) {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ps_tile_v3_kernel<CH, WE, WP, Q3>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SD_LAUNCH(ctx, "ps_tile_v3_kernel", (ps_tile_v3_kernel<CH, WE, WP, Q3>), grid, dim3(threads), lds, a);
+    SD_LAUNCH_LDS(ctx, "ps_tile_v3_kernel", (ps_tile_v3_kernel<CH, WE, WP, Q3>), grid, dim3(threads), lds, a);
     return SDICE_OK;
 }
 template <bool CH>

@@ -1121,18 +1121,11 @@ __global__ void __launch_bounds__(256) ranksum_finish_kernel(int64_t n, double* 
     if (z_out) z_out[row] = z;
 }
 
-int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
-
 // the double precision tail of every kernel that leaves (2U, n1, n2) in p[row]
 int launch_finish(sdice_ctx* ctx, int64_t n, RsOut o) {
     SD_LAUNCH(ctx, "ranksum_finish_kernel", ranksum_finish_kernel, dim3((unsigned)sd_ceil_div(n, 256)), dim3(256), 0, n,
               o.p, o.z);
     return SDICE_OK;
-}
-
-// grid of the wave-per-row kernels (4 waves per workgroup, `ch` rows per wave and chunk)
-int64_t wave_blocks(sdice_ctx* ctx, int64_t n, int ch) {
-    return std::min(sd_ceil_div(sd_ceil_div(n, ch), 4), (int64_t)ctx->n_cu * 8);
 }
 
 // the sorting wave kernel over every row, or (redo_only) over the rows a key kernel marked RS_REDO
@@ -1142,8 +1135,8 @@ int launch_wave_sort(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const 
     const int waves = 4;
     const size_t lds = (size_t)waves * (2 * 64 * E + 40) * 4;
     const int ch = rows_per_chunk(ctx->n_cu, n);
-    SD_LAUNCH(ctx, "ranksum_wave_kernel", (ranksum_wave_kernel<E>), dim3((unsigned)wave_blocks(ctx, n, ch)), dim3(waves * 64),
-              lds, d_ps, n, s, g1, n1, g2, n2, ch, redo_only ? 1 : 0, o);
+    SD_LAUNCH(ctx, "ranksum_wave_kernel", (ranksum_wave_kernel<E>), dim3((unsigned)wave_launch_blocks(ctx, n, ch, waves)),
+              dim3(waves * 64), lds, d_ps, n, s, g1, n1, g2, n2, ch, redo_only ? 1 : 0, o);
     return SDICE_OK;
 }
 
@@ -1155,61 +1148,49 @@ int launch_wave(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32
         const int waves = 4;
         const int ch = rows_per_chunk(ctx->n_cu, n);
         const size_t lds_c = (size_t)(waves * (2 * 64 * E + 40 + (2 * 64 * E >= RS_BINS ? 0 : RS_BINS) + 8)) * 4;
-        SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ranksum_count_kernel<E>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
-        SD_LAUNCH(ctx, "ranksum_count_kernel", (ranksum_count_kernel<E>), dim3((unsigned)wave_blocks(ctx, n, ch)),
-                  dim3(waves * 64), lds_c, d_ps, n, s, g1, n1, g2, n2, ch, (int)ctx->param(SD_P_RANKSUM_ABLATE), o);
+        SD_LAUNCH_LDS(ctx, "ranksum_count_kernel", (ranksum_count_kernel<E>), dim3((unsigned)wave_launch_blocks(ctx, n, ch, waves)),
+                      dim3(waves * 64), lds_c, d_ps, n, s, g1, n1, g2, n2, ch, (int)ctx->param(SD_P_RANKSUM_ABLATE), o);
     }
     SD_TRY(launch_wave_sort<E>(ctx, d_ps, n, s, g1, n1, g2, n2, o, counting));
     return launch_finish(ctx, n, o);
 }
 
+// The kernels that keep the rows of a wave side by side in LDS (lane, pair, pairq): `rows` rows per wave, a row's
+// `stride` keys of key_bytes each, behind them the index lists (idx_bytes); at most cu_cap workgroups a CU.  `tail` is
+// what the kernel takes after the stride: the outputs (+ the lane kernel's ablation mask).
+struct RowsShape { int rows, key_bytes, waves, cu_cap; };
+constexpr RowsShape RS_LANE{64, 4, 2, 16}, RS_PAIR{32, 4, 2, 24}, RS_PAIRQ{32, 2, 4, 16};
+
+template <class Kernel, class... Tail>
+int launch_rows(sdice_ctx* ctx, const char* name, Kernel kernel, RowsShape sh, int stride, size_t idx_bytes, const float* d_ps,
+                int64_t n, int s, const int32_t* g1, int n1, const int32_t* g2, int n2, Tail... tail) {
+    const size_t lds = (size_t)sh.waves * sh.rows * stride * sh.key_bytes + idx_bytes;
+    const int64_t blocks = std::min(sd_ceil_div(sd_ceil_div(n, sh.rows), sh.waves), (int64_t)ctx->n_cu * sh.cu_cap);
+    SD_LAUNCH_LDS(ctx, name, kernel, dim3((unsigned)blocks), dim3(sh.waves * 64), lds, d_ps, n, s, g1, g2, n1, n2, stride, tail...);
+    return SDICE_OK;
+}
+
 template <int P>
 int launch_lane(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* g1, int n1, const int32_t* g2, int n2, RsOut o) {
-    const int stride = (n1 + n2) | 1;
-    int waves = 2;
-    const size_t lds = (size_t)waves * 64 * stride * 4 + (size_t)(n1 + n2) * 4;
-    int64_t groups = sd_ceil_div(n, 64);
-    int64_t blocks = sd_ceil_div(groups, waves);
-    const int64_t cap = (int64_t)ctx->n_cu * 16;
-    if (blocks > cap) blocks = cap;
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ranksum_lane_kernel<P>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SD_LAUNCH(ctx, "ranksum_lane_kernel", (ranksum_lane_kernel<P>), dim3((unsigned)blocks), dim3(waves * 64), lds, d_ps, n,
-              s, g1, g2, n1, n2, stride, o, (int)ctx->param(SD_P_RANKSUM_ABLATE));
+    SD_TRY(launch_rows(ctx, "ranksum_lane_kernel", ranksum_lane_kernel<P>, RS_LANE, (n1 + n2) | 1, (size_t)(n1 + n2) * 4, d_ps,
+                       n, s, g1, n1, g2, n2, o, (int)ctx->param(SD_P_RANKSUM_ABLATE)));
     return launch_finish(ctx, n, o);
 }
 
 template <int P>
 int launch_pair(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* g1, int n1, const int32_t* g2, int n2, RsOut o) {
-    const int stride = (n1 + n2) | 1;
-    const int waves = 2;
-    const size_t lds = (size_t)waves * 32 * stride * 4 + (size_t)(n1 + n2) * 4;
-    int64_t blocks = sd_ceil_div(sd_ceil_div(n, 32), waves);
-    const int64_t cap = (int64_t)ctx->n_cu * 24;
-    if (blocks > cap) blocks = cap;
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ranksum_pair_kernel<P>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SD_LAUNCH(ctx, "ranksum_pair_kernel", (ranksum_pair_kernel<P>), dim3((unsigned)blocks), dim3(waves * 64), lds, d_ps, n,
-              s, g1, g2, n1, n2, stride, o);
+    SD_TRY(launch_rows(ctx, "ranksum_pair_kernel", ranksum_pair_kernel<P>, RS_PAIR, (n1 + n2) | 1, (size_t)(n1 + n2) * 4, d_ps,
+                       n, s, g1, n1, g2, n2, o));
     return launch_finish(ctx, n, o);
 }
 
-// 16-bit-key lane-pair kernel, then the sorting wave kernel over the rows it marked (non 3-decimal values)
+// 16-bit-key lane-pair kernel (stride in u16 units; n1, n2 <= 64), then the sorting wave kernel over the rows it marked
+// (non 3-decimal values)
 template <int P>
 int launch_pairq(sdice_ctx* ctx, const float* d_ps, int64_t n, int s, const int32_t* g1, int n1,
                  const int32_t* g2, int n2, RsOut o) {
-    const int stride = RSQ_STRIDE;                         // u16 units (n1, n2 <= 64)
-    const int waves = 4;
-    const int nsel = n1 + n2;
-    const size_t lds = (size_t)((nsel + 1) & ~1) * 4 + (size_t)waves * 32 * stride * 2;
-    int64_t blocks = sd_ceil_div(sd_ceil_div(n, 32), waves);
-    const int64_t cap = (int64_t)ctx->n_cu * 16;
-    if (blocks > cap) blocks = cap;
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ranksum_pairq_kernel<P>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SD_LAUNCH(ctx, "ranksum_pairq_kernel", (ranksum_pairq_kernel<P>), dim3((unsigned)blocks), dim3(waves * 64), lds, d_ps, n,
-              s, g1, g2, n1, n2, stride, o);
+    SD_TRY(launch_rows(ctx, "ranksum_pairq_kernel", ranksum_pairq_kernel<P>, RS_PAIRQ, RSQ_STRIDE,
+                       (size_t)((n1 + n2 + 1) & ~1) * 4, d_ps, n, s, g1, n1, g2, n2, o));
     SD_TRY(launch_wave_sort<1>(ctx, d_ps, n, s, g1, n1, g2, n2, o, true));
     return launch_finish(ctx, n, o);
 }
@@ -1240,27 +1221,20 @@ extern "C" int sdice_ranksum_dev(sdice_ctx* ctx, int64_t n, int32_t s, const flo
             if (big <= 32) return launch_pairq<32>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, o);
             return launch_pairq<64>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, o);
         }
-        if (variant != 1) {      // groups <= 16 and variant 4: the float lane-pair kernel (1.45x the lane kernel at 50 v 50)
-            switch (next_pow2(big < 8 ? 8 : big)) {
-                case 8: return launch_pair<8>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, o);
-                case 16: return launch_pair<16>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, o);
-                case 32: return launch_pair<32>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, o);
-                default: return launch_pair<64>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, o);
-            }
-        }
-        switch (next_pow2(big < 8 ? 8 : big)) {
-            case 8: return launch_lane<8>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, o);
-            case 16: return launch_lane<16>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, o);
-            case 32: return launch_lane<32>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, o);
-            default: return launch_lane<64>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, o);
-        }
+        if (variant != 1)        // groups <= 16 and variant 4: the float lane-pair kernel (1.45x the lane kernel at 50 v 50)
+            return with_group_width(big, [&](auto width) -> int {
+                return launch_pair<decltype(width)::value>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, o);
+            });
+        return with_group_width(big, [&](auto width) -> int {
+            return launch_lane<decltype(width)::value>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, o);
+        });
     }
     const int big = n1 > n2 ? n1 : n2;
     SD_ARG((variant != 3 && variant != 5) || big <= 1024, "wave / counting variants need n1, n2 <= 1024");
     if ((variant == 0 && big <= 1024) || variant == 3 || variant == 5) {
         // auto and 5: histogram kernel for rows of 3-decimal values + sorting kernel for the rest; 3: sorting only
         const bool counting = variant != 3;
-        switch (next_pow2(big < 64 ? 64 : big) / 64) {
+        switch (next_pow2(big, 64) / 64) {
             case 1: return launch_wave<1>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, o, counting);
             case 2: return launch_wave<2>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, o, counting);
             case 4: return launch_wave<4>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, o, counting);
@@ -1268,18 +1242,13 @@ extern "C" int sdice_ranksum_dev(sdice_ctx* ctx, int64_t n, int32_t s, const flo
             default: return launch_wave<16>(ctx, d_ps, n, s, d_g1, n1, d_g2, n2, o, counting);
         }
     }
-    const int P1 = next_pow2(n1), P2 = next_pow2(n2);
+    const int P1 = next_pow2(n1, 1), P2 = next_pow2(n2, 1);
     SD_ARG(big <= 4096, "group larger than 4096 samples is not supported");
     const int leaf_max = 72;             // <= 2^6 leaves of numpy's pairwise recursion (+ sentinel)
     const size_t lds = (size_t)(P1 + P2 + leaf_max * 9) * 4 + (size_t)(leaf_max + 1 + 8) * 4;
     SD_ARG(lds <= 150 * 1024, "groups too large for LDS");
-    int64_t blocks = n;
-    const int64_t cap = (int64_t)ctx->n_cu * 8;
-    if (blocks > cap) blocks = cap;
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ranksum_block_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SD_LAUNCH(ctx, "ranksum_block_kernel", ranksum_block_kernel, dim3((unsigned)blocks), dim3(RB_THREADS), lds, d_ps, n,
-              (int)s, d_g1, (int)n1, d_g2, (int)n2, P1, P2, leaf_max, o);
+    SD_LAUNCH_LDS(ctx, "ranksum_block_kernel", ranksum_block_kernel, dim3((unsigned)row_launch_blocks(ctx, n)), dim3(RB_THREADS),
+                  lds, d_ps, n, (int)s, d_g1, (int)n1, d_g2, (int)n2, P1, P2, leaf_max, o);
     return SDICE_OK;
 }
 
@@ -1293,14 +1262,13 @@ extern "C" int sdice_ranksum(sdice_ctx* ctx, int64_t n, int32_t s, const float* 
     for (int i = 0; i < n1; ++i) SD_ARG(g1[i] >= 0 && g1[i] < s, "g1 index out of range");
     for (int i = 0; i < n2; ++i) SD_ARG(g2[i] >= 0 && g2[i] < s, "g2 index out of range");
     HostStaging st(ctx);
-    TwoSampleStaging res;
+    RsOut o;
     float* d_ps;
     int32_t *dg1, *dg2;
     SD_TRY(st.upload(&d_ps, ps, n * s));
     SD_TRY(st.upload(&dg1, g1, n1));
     SD_TRY(st.upload(&dg2, g2, n2));
-    SD_TRY(res.alloc(st, n));
-    const RsOut o = res.out();
+    SD_TRY(stage_two_sample(st, n, {tested, p, z, med1, med2, mean1, mean2, delta}, &o));
     SD_TRY(sdice_ranksum_dev(ctx, n, s, d_ps, dg1, n1, dg2, n2, o.tested, o.p, o.z, o.med1, o.med2, o.mean1, o.mean2, o.delta));
-    return res.download(st, {tested, p, z, med1, med2, mean1, mean2, delta});
+    return st.download_results();
 }

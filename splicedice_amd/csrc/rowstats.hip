@@ -180,11 +180,10 @@ extern "C" int sdice_rowstats(sdice_ctx* ctx, int64_t n, int32_t s, const void* 
     int32_t *d_idx, *d_nan;
     SD_TRY(st.upload(&d_data, static_cast<const char*>(data), n * s * w));
     SD_TRY(st.upload(&d_idx, idx, k));      // (k == 0 still stages a valid buffer; the _dev call rejects it)
-    SD_TRY(st.alloc(&d_mean, n * w));
-    SD_TRY(st.alloc(&d_std, n * w));
-    SD_TRY(st.alloc(&d_nan, n));
+    st.result(&d_mean, static_cast<char*>(mean), n * w);
+    st.result(&d_std, static_cast<char*>(std_), n * w);
+    st.result(&d_nan, n_nan, n);
+    SD_TRY(st.alloc_results());
     SD_TRY(sdice_rowstats_dev(ctx, n, s, d_data, dtype, d_idx, k, d_mean, d_std, d_nan));
-    SD_TRY(st.download(static_cast<char*>(mean), d_mean, n * w));
-    SD_TRY(st.download(static_cast<char*>(std_), d_std, n * w));
-    return st.download(n_nan, d_nan, n);
+    return st.download_results();
 }

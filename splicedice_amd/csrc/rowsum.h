@@ -4,33 +4,36 @@
 // lane groups with their sums, bitonic sort and median, the key of a signed-rank difference, the workgroup's bitonic
 // network, the tie-run bounds of a sorted array, the median search in the 16-bins-per-lane histograms of the counting
 // kernels, the stores of a two-sample row.  Host: the eight output pointers of the two-sample tests, their "no row can be
-// tested" block and their staging for a host entry point, the launch sizes of the wave-per-chunk and row-per-workgroup
-// kernels, the width ladder of the lane-group kernels; the checks of the column lists and the k-set limits are
-// colcheck.h's (host only, no HIP), included here.  What each file takes:
+// tested" block and their registration as the result fields of a host entry point (stage_two_sample, over common.h's
+// HostStaging), the launch sizes of the wave-per-chunk and row-per-workgroup kernels, the width ladder of the lane-group
+// kernels and their launch (with_group_width, with_group_launch), the launch pair of the k-set tests (kw_launch_pair); the
+// checks of the column lists and the k-set limits are colcheck.h's (host only, no HIP), included here.  What each file
+// takes:
 //   ranksum.hip (K5)      PsKey, median_sorted, block_compact, the pairwise sums, find_bin, lanes_below; TwoSampleOut (as
-//                         RsOut), zero_two_sample, TwoSampleStaging
+//                         RsOut), zero_two_sample, stage_two_sample, the launch sizes, next_pow2, with_group_width
 //   kruskal.hip (K12)     as ranksum.hip's kernels + f32_ord, median_of_ord, block_bitonic
 //                         + the k-set section: the limits, KwSets, kw_stage_row / kw_walk_set (the first walk of the grid
-//                         kernel), kw_block_sort_sets (the block kernel up to its medians), kw_plan, kw_check_sets, check_columns
+//                         kernel), kw_block_sort_sets (the block kernel up to its medians), kw_plan, kw_launch_pair,
+//                         kw_check_sets, check_columns
 //   jonckheere.hip (K18)  as kruskal.hip's k-set section + kw_load_bins / kw_scan_bins, the launch sizes
 //   signedrank.hip (K13)  PsKey, f32_ord, LaneGroup, group_add / group_sum / group_sort / group_median, pair_diff_key,
 //                         block_compact_by, block_pairwise_sum, block_bitonic, run_bounds, median_of_ord, store_two_sample,
-//                         the launch sizes, with_group_width; TwoSampleOut, zero_two_sample, TwoSampleStaging, check_columns
+//                         with_group_launch; TwoSampleOut, zero_two_sample, stage_two_sample, check_columns
 //   spearman.hip (K14)    PsKey, f32_ord, LaneGroup and its sums, the block's compaction, sum, network and run bounds, the
-//                         launch sizes, with_group_width, check_columns
+//                         launch sizes, with_group_launch, check_columns
 //   gram.hip              check_columns
-//   exactrank.hip (K16)   PsKey, pair_diff_key, SD_WAVE_SYNC, row_launch_blocks; TwoSampleStaging, check_columns
+//   exactrank.hip (K16)   PsKey, pair_diff_key, SD_WAVE_SYNC, row_launch_blocks; stage_two_sample, check_columns
 //   strata.hip (K17)      PsKey, f32_ord, LaneGroup, group_add / group_sum / group_sort / group_median, block_compact,
 //                         block_pairwise_sum, block_bitonic, run_bounds, two_group_median_key, median_of_ord,
-//                         store_two_sample, the launch sizes, with_group_width; TwoSampleOut, zero_two_sample,
-//                         TwoSampleStaging, check_two_groups (with the stratum ids)
+//                         store_two_sample, the launch sizes, with_group_launch; TwoSampleOut, zero_two_sample,
+//                         stage_two_sample, check_two_groups (with the stratum ids)
 //   ks.hip (K19)          PsKey, f32_ord, LaneGroup, group_sum / group_sort / group_median, block_compact,
 //                         block_pairwise_sum, block_bitonic, two_group_median_key, median_of_ord, store_two_sample, the
-//                         launch sizes, with_group_width; TwoSampleOut (D in the z slot), zero_two_sample,
-//                         TwoSampleStaging (with `exact`), check_two_groups
+//                         launch sizes, with_group_launch; TwoSampleOut (D in the z slot), zero_two_sample,
+//                         stage_two_sample (with `exact`), check_two_groups
 //   shift.hip (K20)       PsKey, f32_ord / f32_unord, LaneGroup, group_add / group_sort, block_bitonic,
-//                         two_group_median_key, kw_load_bins / kw_scan_bins, the launch sizes, with_group_width;
-//                         check_two_groups (its own five outputs and their staging)
+//                         two_group_median_key, kw_load_bins / kw_scan_bins, the launch sizes, with_group_launch;
+//                         check_two_groups (its own five outputs)
 // (strata.hip and ks.hip: the pass front of the group kernels and the LDS + sums of the block kernels stay written out, A.17)
 // Every helper is inlined into the kernels that call it and the kernels themselves stay in their .hip files, so a change
 // to a helper here is a change to each kernel that uses it -- ranksum.hip's pairq and count kernels among them, whose
@@ -644,8 +647,7 @@ inline int rows_per_chunk(int n_cu, int64_t n) {
 }
 
 // Host: workgroups of `waves` waves for a kernel whose waves walk chunks of ch rows, every wave slot of the chip filled
-// at most once (ranksum.hip's wave_blocks computes the same for its 4 waves); and of a kernel whose workgroups walk n
-// rows (or n blocks of rows), 8 a CU at most
+// at most once; and of a kernel whose workgroups walk n rows (or n blocks of rows), 8 a CU at most
 inline int64_t wave_launch_blocks(const sdice_ctx* ctx, int64_t n, int ch, int waves) {
     return std::min(sd_ceil_div(sd_ceil_div(n, ch), waves), (int64_t)ctx->n_cu * 32 / waves);
 }
@@ -667,6 +669,16 @@ inline int with_group_width(int m, Launch launch) {
         if (m <= 16) return launch(std::integral_constant<int, 16>{});
     if (m <= 32) return launch(std::integral_constant<int, 32>{});
     return launch(std::integral_constant<int, 64>{});
+}
+
+// Host: the launch of a lane-group kernel over n rows of m <= 64 selected columns -- workgroups of GROUP_WAVES waves
+// that walk chunks of ch rows, no dynamic LDS; launch(width, ch, blocks) names the kernel<width> and its arguments
+constexpr int GROUP_WAVES = 4;
+template <int FROM = 8, class Launch>
+inline int with_group_launch(const sdice_ctx* ctx, int64_t n, int m, Launch launch) {
+    const int ch = rows_per_chunk(ctx->n_cu, n);
+    const int64_t blocks = wave_launch_blocks(ctx, n, ch, GROUP_WAVES);
+    return with_group_width<FROM>(m, [&](auto width) -> int { return launch(width, ch, blocks); });
 }
 
 // Host: the sets as the kernels take them, the launch shape of a grid kernel over KwWaveLds and the sort length of a
@@ -696,6 +708,19 @@ inline KwPlan kw_plan(const int32_t* set_ptr, int k) {
     return pl;
 }
 
+// Host: the two launches of a k-set test -- the grid kernel over every row, then the block kernel over the rows it marked
+// KW_REDO
+template <auto GridKernel, auto BlockKernel, class Out>
+inline int kw_launch_pair(sdice_ctx* ctx, const char* grid_name, const char* block_name, const KwPlan& pl, const float* d_ps,
+                          int64_t n, int s, const int32_t* d_cols, int k, const Out& o) {
+    const int ch = rows_per_chunk(ctx->n_cu, n);
+    SD_LAUNCH_LDS(ctx, grid_name, GridKernel, dim3((unsigned)wave_launch_blocks(ctx, n, ch, pl.waves)), dim3(pl.waves * 64),
+                  pl.grid_lds, d_ps, n, s, d_cols, pl.sets, k, ch, pl.wstride, pl.leaf_cap, o);
+    SD_LAUNCH_LDS(ctx, block_name, BlockKernel, dim3((unsigned)row_launch_blocks(ctx, sd_ceil_div(n, RB_THREADS))),
+                  dim3(RB_THREADS), pl.block_lds, d_ps, n, s, d_cols, pl.sets, k, pl.P, 1, o);
+    return SDICE_OK;
+}
+
 // Host: "no row can be tested" -- every field of the n rows is 0, queued on the context's stream
 inline int zero_two_sample(sdice_ctx* ctx, int64_t n, const TwoSampleOut& o) {
     SD_HIP(hipMemsetAsync(o.tested, 0, (size_t)n, ctx->stream));
@@ -705,37 +730,19 @@ inline int zero_two_sample(sdice_ctx* ctx, int64_t n, const TwoSampleOut& o) {
     return SDICE_OK;
 }
 
-// Host: the device copies of a host entry point's two-sample outputs, three blocks of the caller's HostStaging: tested
-// (+ exact), p and z, the five floats
-class TwoSampleStaging {
-  public:
-    int alloc(HostStaging& st, int64_t n, bool with_exact = false) {
-        n_ = n;
-        SD_TRY(st.alloc(&dt_, with_exact ? n * 2 : n));
-        SD_TRY(st.alloc(&dd_, n * 2));
-        return st.alloc(&df_, n * 5);
-    }
-    // what the _dev call writes
-    TwoSampleOut out() const { return {dt_, dd_, dd_ + n_, df_, df_ + n_, df_ + 2 * n_, df_ + 3 * n_, df_ + 4 * n_}; }
-    uint8_t* exact() const { return dt_ + n_; }
-    // synchronous copies into the caller's arrays; h.z and exact may be NULL
-    int download(HostStaging& st, const TwoSampleOut& h, uint8_t* exact = nullptr) const {
-        const TwoSampleOut d = out();
-        SD_TRY(st.download(h.tested, d.tested, n_));
-        if (exact) SD_TRY(st.download(exact, dt_ + n_, n_));
-        SD_TRY(st.download(h.p, d.p, n_));
-        if (h.z) SD_TRY(st.download(h.z, d.z, n_));
-        SD_TRY(st.download(h.med1, d.med1, n_));
-        SD_TRY(st.download(h.med2, d.med2, n_));
-        SD_TRY(st.download(h.mean1, d.mean1, n_));
-        SD_TRY(st.download(h.mean2, d.mean2, n_));
-        return st.download(h.delta, d.delta, n_);
-    }
-
-  private:
-    int64_t n_ = 0;
-    uint8_t* dt_ = nullptr;
-    double* dd_ = nullptr;
-    float* df_ = nullptr;
-};
+// Host: the two-sample results of a host entry point (h: the caller's arrays, h.z and h_exact may be NULL) as one block
+// of its HostStaging; *d gets the device pointers the _dev call writes, *d_exact that of `exact` where the test has one
+inline int stage_two_sample(HostStaging& st, int64_t n, TwoSampleOut h, TwoSampleOut* d, uint8_t* h_exact = nullptr,
+                            uint8_t** d_exact = nullptr) {
+    st.result(&d->tested, h.tested, n);
+    if (d_exact) st.result(d_exact, h_exact, n);
+    st.result(&d->p, h.p, n);
+    st.result(&d->z, h.z, n);
+    st.result(&d->med1, h.med1, n);
+    st.result(&d->med2, h.med2, n);
+    st.result(&d->mean1, h.mean1, n);
+    st.result(&d->mean2, h.mean2, n);
+    st.result(&d->delta, h.delta, n);
+    return st.alloc_results();
+}
 }  // namespace

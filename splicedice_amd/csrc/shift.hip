@@ -417,21 +417,16 @@ extern "C" int sdice_shift_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float
         return SDICE_OK;
     }
     if (m <= SH_GROUP_MAX)
-        return with_group_width(m, [&](auto width) -> int {
-            const int waves = 4;
-            const int ch = rows_per_chunk(ctx->n_cu, n);
-            const int64_t blocks = wave_launch_blocks(ctx, n, ch, waves);
+        return with_group_launch(ctx, n, m, [&](auto width, int ch, int64_t blocks) -> int {
             SD_LAUNCH(ctx, "shift_group_kernel", (shift_group_kernel<decltype(width)::value>), dim3((unsigned)blocks),
-                      dim3(waves * 64), 0, d_ps, n, (int)s, d_g1, (int)n1, d_g2, (int)n2, zq, ch, o);
+                      dim3(GROUP_WAVES * 64), 0, d_ps, n, (int)s, d_g1, (int)n1, d_g2, (int)n2, zq, ch, o);
             return SDICE_OK;
         });
     const int P = next_pow2(m, 128);
     const size_t lds = (size_t)P * 8;
     const int64_t blocks = row_launch_blocks(ctx, n);
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(shift_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds));
-    SD_LAUNCH(ctx, "shift_block_kernel", shift_block_kernel, dim3((unsigned)blocks), dim3(RB_THREADS), lds, d_ps, n, (int)s,
-              d_g1, (int)n1, d_g2, (int)n2, zq, P, o);
+    SD_LAUNCH_LDS(ctx, "shift_block_kernel", shift_block_kernel, dim3((unsigned)blocks), dim3(RB_THREADS), lds, d_ps, n, (int)s,
+                  d_g1, (int)n1, d_g2, (int)n2, zq, P, o);
     return SDICE_OK;
 }
 
@@ -447,19 +442,17 @@ extern "C" int sdice_shift(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps
     SD_ARG(ps, "ps is NULL");
     HostStaging st(ctx);
     float* d_ps;
-    int32_t *dg1, *dg2, *d_rank;
-    uint8_t* d_tested;
-    double* d_f64;                                             // shift | lo | hi
+    int32_t *dg1, *dg2;
+    ShiftOut d;
     SD_TRY(st.upload(&d_ps, ps, n * s));
     SD_TRY(st.upload(&dg1, g1, n1));
     SD_TRY(st.upload(&dg2, g2, n2));
-    SD_TRY(st.alloc(&d_tested, n));
-    SD_TRY(st.alloc(&d_f64, n * 3));
-    SD_TRY(st.alloc(&d_rank, n));
-    SD_TRY(sdice_shift_dev(ctx, n, s, d_ps, dg1, n1, dg2, n2, zq, d_tested, d_f64, d_f64 + n, d_f64 + 2 * n, d_rank));
-    SD_TRY(st.download(tested, d_tested, n));
-    SD_TRY(st.download(shift, d_f64, n));
-    SD_TRY(st.download(lo, d_f64 + n, n));
-    SD_TRY(st.download(hi, d_f64 + 2 * n, n));
-    return st.download(rank, d_rank, n);
+    st.result(&d.tested, tested, n);
+    st.result(&d.shift, shift, n);
+    st.result(&d.lo, lo, n);
+    st.result(&d.hi, hi, n);
+    st.result(&d.rank, rank, n);
+    SD_TRY(st.alloc_results());
+    SD_TRY(sdice_shift_dev(ctx, n, s, d_ps, dg1, n1, dg2, n2, zq, d.tested, d.shift, d.lo, d.hi, d.rank));
+    return st.download_results();
 }

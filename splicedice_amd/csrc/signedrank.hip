@@ -404,21 +404,16 @@ extern "C" int sdice_signedrank_dev(sdice_ctx* ctx, int64_t n, int32_t s, const 
     if (m <= 4) return sr_launch_lane<4>(ctx, d_ps, n, s, d_a, d_b, m, o);
     if (m <= 8) return sr_launch_lane<8>(ctx, d_ps, n, s, d_a, d_b, m, o);
     if (m <= SR_GROUP_MAX)
-        return with_group_width<16>(m, [&](auto width) -> int {
-            const int waves = 4;
-            const int ch = rows_per_chunk(ctx->n_cu, n);
-            const int64_t blocks = wave_launch_blocks(ctx, n, ch, waves);
+        return with_group_launch<16>(ctx, n, m, [&](auto width, int ch, int64_t blocks) -> int {
             SD_LAUNCH(ctx, "signedrank_group_kernel", (signedrank_group_kernel<decltype(width)::value>), dim3((unsigned)blocks),
-                      dim3(waves * 64), 0, d_ps, n, (int)s, d_a, d_b, (int)m, ch, o);
+                      dim3(GROUP_WAVES * 64), 0, d_ps, n, (int)s, d_a, d_b, (int)m, ch, o);
             return SDICE_OK;
         });
     const int P = next_pow2(m, 128);
     const size_t lds = (size_t)P * 3 * 4;
     const int64_t blocks = row_launch_blocks(ctx, n);
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(signedrank_block_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SD_LAUNCH(ctx, "signedrank_block_kernel", signedrank_block_kernel, dim3((unsigned)blocks), dim3(RB_THREADS), lds, d_ps, n,
-              (int)s, d_a, d_b, (int)m, P, o);
+    SD_LAUNCH_LDS(ctx, "signedrank_block_kernel", signedrank_block_kernel, dim3((unsigned)blocks), dim3(RB_THREADS), lds, d_ps,
+                  n, (int)s, d_a, d_b, (int)m, P, o);
     return SDICE_OK;
 }
 
@@ -434,14 +429,13 @@ extern "C" int sdice_signedrank(sdice_ctx* ctx, int64_t n, int32_t s, const floa
     SD_ARG(tested && p && med1 && med2 && mean1 && mean2 && delta, "NULL output");
     SD_ARG(ps, "ps is NULL");
     HostStaging st(ctx);
-    TwoSampleStaging res;
+    TwoSampleOut o;
     float* d_ps;
     int32_t *da, *db;
     SD_TRY(st.upload(&d_ps, ps, n * s));
     SD_TRY(st.upload(&da, a, m));
     SD_TRY(st.upload(&db, b, m));
-    SD_TRY(res.alloc(st, n));
-    const TwoSampleOut o = res.out();
+    SD_TRY(stage_two_sample(st, n, {tested, p, z, med1, med2, mean1, mean2, delta}, &o));
     SD_TRY(sdice_signedrank_dev(ctx, n, s, d_ps, da, db, m, o.tested, o.p, o.z, o.med1, o.med2, o.mean1, o.mean2, o.delta));
-    return res.download(st, {tested, p, z, med1, med2, mean1, mean2, delta});
+    return st.download_results();
 }

@@ -73,12 +73,13 @@ extern "C" int sdice_similarity(sdice_ctx* ctx, int64_t n, int32_t s, const doub
     HostStaging st(ctx);
     double *d_ps, *d_mid;
     int8_t* d_sign;
-    int64_t* d_out;                               // scores, then counts
-    SD_TRY(st.alloc(&d_out, (int64_t)s * 2));
+    int64_t *d_scores, *d_counts;
+    st.result(&d_scores, scores, s);
+    st.result(&d_counts, counts, s);
+    SD_TRY(st.alloc_results());
     SD_TRY(st.upload(&d_ps, ps, n * s));          // (n == 0: nothing is copied, so NULL inputs pass)
     SD_TRY(st.upload(&d_mid, mid, n));
     SD_TRY(st.upload(&d_sign, sign, n));
-    SD_TRY(sdice_similarity_dev(ctx, n, s, d_ps, d_mid, d_sign, d_out, d_out + s));
-    SD_TRY(st.download(scores, d_out, s));
-    return st.download(counts, d_out + s, s);
+    SD_TRY(sdice_similarity_dev(ctx, n, s, d_ps, d_mid, d_sign, d_scores, d_counts));
+    return st.download_results();
 }

@@ -521,12 +521,9 @@ extern "C" int sdice_spearman_dev(sdice_ctx* ctx, int64_t n, int32_t s, const fl
     SD_TRY(ctx->arena.reset(ctx->stream));
     SpOut o{d_tested, d_p, d_rho, d_n_kept, d_med, d_mean};
     if (m <= SP_GROUP_MAX)
-        return with_group_width(m, [&](auto width) -> int {
-            const int waves = 4;
-            const int ch = rows_per_chunk(ctx->n_cu, n);
-            const int64_t blocks = wave_launch_blocks(ctx, n, ch, waves);
+        return with_group_launch(ctx, n, m, [&](auto width, int ch, int64_t blocks) -> int {
             SD_LAUNCH(ctx, "spearman_group_kernel", (spearman_group_kernel<decltype(width)::value>), dim3((unsigned)blocks),
-                      dim3(waves * 64), 0, d_ps, n, (int)s, d_cols, d_xg, (int)m, ch, o);
+                      dim3(GROUP_WAVES * 64), 0, d_ps, n, (int)s, d_cols, d_xg, (int)m, ch, o);
             return SDICE_OK;
         });
     if (m <= SP_WAVE_MAX / 2) return sp_launch_wave<2>(ctx, d_ps, n, s, d_cols, d_xg, m, o);
@@ -552,22 +549,19 @@ extern "C" int sdice_spearman(sdice_ctx* ctx, int64_t n, int32_t s, const float*
     SD_ARG(tested && p && n_kept && med && mean, "NULL output");
     SD_ARG(ps, "ps is NULL");
     HostStaging st(ctx);
-    float *d_ps, *df;
-    int32_t *dc, *dg, *dn;
-    uint8_t* dt;
-    double* dd;
+    float* d_ps;
+    int32_t *dc, *dg;
+    SpOut d;
     SD_TRY(st.upload(&d_ps, ps, n * s));
     SD_TRY(st.upload(&dc, cols, m));
     SD_TRY(st.upload(&dg, xg, m));
-    SD_TRY(st.alloc(&dt, n));
-    SD_TRY(st.alloc(&dd, n * 2));      // p, rho
-    SD_TRY(st.alloc(&dn, n));
-    SD_TRY(st.alloc(&df, n * 2));      // med, mean
-    SD_TRY(sdice_spearman_dev(ctx, n, s, d_ps, dc, dg, m, dt, dd, dd + n, dn, df, df + n));
-    SD_TRY(st.download(tested, dt, n));
-    SD_TRY(st.download(p, dd, n));
-    if (rho) SD_TRY(st.download(rho, dd + n, n));
-    SD_TRY(st.download(n_kept, dn, n));
-    SD_TRY(st.download(med, df, n));
-    return st.download(mean, df + n, n);
+    st.result(&d.tested, tested, n);
+    st.result(&d.p, p, n);
+    st.result(&d.rho, rho, n);
+    st.result(&d.n_kept, n_kept, n);
+    st.result(&d.med, med, n);
+    st.result(&d.mean, mean, n);
+    SD_TRY(st.alloc_results());
+    SD_TRY(sdice_spearman_dev(ctx, n, s, d_ps, dc, dg, m, d.tested, d.p, d.rho, d.n_kept, d.med, d.mean));
+    return st.download_results();
 }

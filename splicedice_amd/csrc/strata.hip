@@ -415,21 +415,16 @@ extern "C" int sdice_ranksum_strata_dev(sdice_ctx* ctx, int64_t n, int32_t s, co
     const int m = n1 + n2;
     if (n1 < 3 || n2 < 3) return zero_two_sample(ctx, n, o);         // no row can be tested
     if (m <= ST_GROUP_MAX)
-        return with_group_width(m, [&](auto width) -> int {
-            const int waves = 4;
-            const int ch = rows_per_chunk(ctx->n_cu, n);
-            const int64_t blocks = wave_launch_blocks(ctx, n, ch, waves);
+        return with_group_launch(ctx, n, m, [&](auto width, int ch, int64_t blocks) -> int {
             SD_LAUNCH(ctx, "strata_group_kernel", (strata_group_kernel<decltype(width)::value>), dim3((unsigned)blocks),
-                      dim3(waves * 64), 0, d_ps, n, (int)s, d_g1, (int)n1, d_g2, (int)n2, d_strat1, d_strat2, ch, o);
+                      dim3(GROUP_WAVES * 64), 0, d_ps, n, (int)s, d_g1, (int)n1, d_g2, (int)n2, d_strat1, d_strat2, ch, o);
             return SDICE_OK;
         });
     const int P = next_pow2(m, 128);
     const size_t lds = (size_t)P * 16;
     const int64_t blocks = row_launch_blocks(ctx, n);
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(strata_block_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SD_LAUNCH(ctx, "strata_block_kernel", strata_block_kernel, dim3((unsigned)blocks), dim3(RB_THREADS), lds, d_ps, n, (int)s,
-              d_g1, (int)n1, d_g2, (int)n2, d_strat1, d_strat2, P, o);
+    SD_LAUNCH_LDS(ctx, "strata_block_kernel", strata_block_kernel, dim3((unsigned)blocks), dim3(RB_THREADS), lds, d_ps, n,
+                  (int)s, d_g1, (int)n1, d_g2, (int)n2, d_strat1, d_strat2, P, o);
     return SDICE_OK;
 }
 
@@ -445,7 +440,7 @@ extern "C" int sdice_ranksum_strata(sdice_ctx* ctx, int64_t n, int32_t s, const 
     SD_ARG(tested && p && med1 && med2 && mean1 && mean2 && delta, "NULL output");
     SD_ARG(ps, "ps is NULL");
     HostStaging st(ctx);
-    TwoSampleStaging res;
+    TwoSampleOut o;
     float* d_ps;
     int32_t *dg1, *dg2, *ds1, *ds2;
     SD_TRY(st.upload(&d_ps, ps, n * s));
@@ -453,9 +448,8 @@ extern "C" int sdice_ranksum_strata(sdice_ctx* ctx, int64_t n, int32_t s, const 
     SD_TRY(st.upload(&dg2, g2, n2));
     SD_TRY(st.upload(&ds1, strat1, n1));
     SD_TRY(st.upload(&ds2, strat2, n2));
-    SD_TRY(res.alloc(st, n));
-    const TwoSampleOut o = res.out();
+    SD_TRY(stage_two_sample(st, n, {tested, p, z, med1, med2, mean1, mean2, delta}, &o));
     SD_TRY(sdice_ranksum_strata_dev(ctx, n, s, d_ps, dg1, n1, dg2, n2, ds1, ds2, n_strata, o.tested, o.p, o.z, o.med1, o.med2,
                                     o.mean1, o.mean2, o.delta));
-    return res.download(st, {tested, p, z, med1, med2, mean1, mean2, delta});
+    return st.download_results();
 }

@@ -19,6 +19,7 @@
 #include "paircheck.h"      // splicedice_amd/csrc: the argument checks of the pair tests
 #include "colcheck.h"       //                      ... and of the column lists
 #include "bh.h"             //                      the column groups of BH
+#include "stagelayout.h"    //                      the result block of a host entry point
 
 static char g_err[1024];
 void sdice_set_error(const char* fmt, ...) {
@@ -274,6 +275,23 @@ int main(int argc, char** argv) {
         for (const auto& c : cases) CHECK(sd_bh_column_group(c.budget, 100, 1000, c.cols, c.max_group) == c.want);
         CHECK(sd_bh_column_group(BIG, 1, 0, BIG, BIG) == BIG);                             // the whole table at the limit
         CHECK(sd_bh_column_group(BIG, BIG, BIG, 37, 65535) == 1 && sd_bh_column_group(0, BIG, BIG, 37, 65535) == 1);
+    }
+    {   // the result block of a host entry point (csrc/stagelayout.h): every field on a 256-byte boundary, none overlaps
+        // the one before, the block ends where the last field, rounded up, does
+        const std::vector<std::vector<int64_t>> layouts = {
+            {0},                                                        // a single empty field
+            {131, 131 * 8, 131 * 8, 131 * 4, 3 * 131 * 4},              // bytes, then 8-byte elements: they need the alignment
+            {1, 0, 255, 256, 257, 8, 131 * 8, 4096, 511, 0, 131, 70 * 70 * 8, 3},       // 13 fields of mixed sizes
+        };
+        for (const auto& bytes : layouts) {
+            const int k = (int)bytes.size();
+            std::vector<int64_t> at(bytes.size(), -1);
+            const int64_t total = sd_stage_layout(bytes.data(), k, at.data());
+            CHECK(at[0] == 0);
+            for (int i = 0; i < k; ++i) CHECK(at[i] % 256 == 0);
+            for (int i = 1; i < k; ++i) CHECK(at[i] >= at[i - 1] + bytes[i - 1]);
+            CHECK(total == at[k - 1] + (bytes[k - 1] + 255) / 256 * 256);
+        }
     }
     printf("host sanitizer driver: ok\n");
     return 0;

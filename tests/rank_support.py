@@ -159,10 +159,10 @@ def draw_pairs(rng, m, spare=3):
 # ------------------------------------------------------------------------------ the C entry points, called directly
 def raw_call(ctx, symbol, ps, args, outs, order):
     """ctx.lib.<symbol>(handle, n, s, ps, *args, *outputs in `order`): the table goes as float32, every list or array of
-    `args` as int32, a scalar as it is; the outputs are the caller's host arrays"""
+    `args` as int32, a scalar as it is; the outputs are the caller's host arrays, None goes as a NULL pointer"""
     ps = np.ascontiguousarray(ps, dtype=np.float32)
     held = [int(a) if np.isscalar(a) else np.ascontiguousarray(a, np.int32) for a in args]
-    ptr = lambda a: a.ctypes.data_as(C.c_void_p)     # noqa: E731
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)     # noqa: E731
     return getattr(ctx.lib, symbol)(ctx.h, *ps.shape, ptr(ps), *[a if isinstance(a, int) else ptr(a) for a in held],
                                     *[ptr(outs[x]) for x in order])
 
