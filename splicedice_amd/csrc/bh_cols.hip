@@ -34,11 +34,7 @@
 
 namespace {
 
-constexpr int TILE_T = 512;         // threads of a scatter tile
-constexpr int TILE_E = 8;           // values per thread
-constexpr int TILE = TILE_T * TILE_E;
-constexpr int MAX_B = 1024;
-constexpr int POS_SHIFT = 18;       // pos word: bucket << 18 | slot inside the column (m <= 2^18, buckets <= 2^10)
+// (TILE_T, TILE_E, TILE, MAX_B, POS_SHIFT, TC_*, BHV_*: bh.h, shared with the planners)
 constexpr unsigned POS_MASK = (1u << POS_SHIFT) - 1u;
 
 struct BhsArgs {
@@ -146,7 +142,6 @@ __global__ void __launch_bounds__(256) bhs_sample_kernel(BhsArgs a) {
 // A workgroup owns a strip of TC_COLS columns x rows_per_block rows: row segments of 128 bytes in, runs of TC_ROWS
 // doubles per column out.  COUNT: every value is classified against its column's splitters (LDS) on the way; the
 // histogram stays in LDS until the workgroup is through its rows.
-constexpr int TC_COLS = 16, TC_ROWS = 128, TC_T = 256;
 // 1-D grid, workgroups dealt round-robin over the 8 XCDs: XCD x takes the strips [x spx, (x + 1) spx), neighbouring
 // strips of one row block back to back -- a 128-byte row piece starts wherever (row x pitch) mod 128 puts it, so every
 // piece shares its first and last line with the neighbouring strips, and those lines should meet in ONE L2.
@@ -767,7 +762,6 @@ __device__ __forceinline__ bool bucket_wg_rank(const BhsArgs& a, const BucketRef
         if (ok[k]) r.ks[k * T + tid] = L[rank[k]];        // in place: the slot the key came from
     return true;
 }
-template <int T, int K> constexpr size_t bucket_wg_lds() { return (size_t)T * K * 16 + 16 + 32 * 8 + 16 * 4 + 16; }
 
 // one workgroup of T threads per bucket of up to 4 T values; larger ones, and the few with a crowded bin (see ZOOM), go to
 // the work list of the second kernel.
@@ -930,8 +924,6 @@ struct BhvArgs {
     int cap;               // values a bucket workgroup holds in LDS
     double* q;
 };
-constexpr int BHV_T = 1024;           // threads of every bhv kernel but the ranking
-constexpr int BHV_E = 4;              // values per thread in a count / scatter / finish tile
 
 // absent entries sort behind every p-value (NaN patterns included) and in front of the padding (~0) of the register sorts
 constexpr uint64_t BHV_ABSENT = ~0ull - 1;
@@ -1112,10 +1104,7 @@ __device__ uint64_t bhv_sub_in_lds(uint64_t* ks, uint32_t* is, int n_s, int64_t 
 // in registers across a barrier before it overwrites the same arrays in sorted order.  5632 values = 73 KB, so that TWO
 // workgroups share a CU and all ~490 buckets of 1 M values are resident at once (with two copies, 150 KB, the
 // workgroups ran in two rounds: 99 us, half of it waiting).
-constexpr int BHV_EPT = 6;            // values per thread of a bucket workgroup (cap <= 6144)
-// sub-buckets: up to 128 of ~16 values, 2 samples each (sizes ~ Gamma(2): a value meets ~24 candidates on average; with
-// 64 sub-buckets of ~32 and 4 samples each -- Gamma(4) -- it met ~40, and the counting loop is the kernel's VALU load)
-constexpr int BHV_SPS_LOG = 1, BHV_SPS = 1 << BHV_SPS_LOG, BHV_NSB_MAX = 256 / BHV_SPS, BHV_SUB_MEAN = 20;
+// (BHV_EPT values per thread; sub-buckets: BHV_SPS, BHV_NSB_MAX, BHV_SUB_MEAN, bh.h)
 __global__ void __launch_bounds__(BHV_T, 8) bhv_bucket_kernel(BhvArgs a) {
     extern __shared__ uint64_t smem_b[];
     uint64_t* K2 = smem_b;
@@ -1380,206 +1369,122 @@ __global__ void __launch_bounds__(BHV_T) bhv_finish_kernel(BhvArgs a) {
 
 }  // namespace
 
-// scratch bytes the sample-sort path needs for `segs` columns of m values: transposed input (8 B per value), bucketed
-// keys / results (8), position words (4), the in-HBM path's copies (8), per-bucket tables
-size_t sd_bh_cols_scratch(int64_t m, int64_t segs) {
-    const size_t vals = (size_t)m * (size_t)segs;
-    return vals * 28 + (size_t)segs * (size_t)(MAX_B + 1) * 50 + (1 << 16);
-}
-
-bool sd_bh_cols_supported(int64_t m, int64_t segs) {
-    return m >= 1 && m <= ((int64_t)1 << POS_SHIFT) && segs >= 1 && segs <= 0x7fffffff;
-}
-
 // BH down each of the `segs` columns of the row-major table d_rm (m rows, row pitch `pitch` elements), in place.
-// Scratch from the context arena (caller reserved sd_bh_cols_scratch bytes).
+// Scratch from the context arena (caller reserved sd_bh_cols_scratch bytes).  Every size, grid and LDS figure is
+// sd_bhs_plan's (bhplan.cpp).
 int sd_bh_cols_samplesort(sdice_ctx* ctx, int64_t m, int64_t segs, double* d_rm, int64_t pitch) {
+    SdBhsPlan pl;
+    SD_TRY(sd_bhs_plan(ctx->params, SdBhsFacts{m, segs, ctx->n_cu}, &pl));
     Arena& A = ctx->arena;
     BhsArgs a;
     a.p_rm = d_rm;
     a.pitch = pitch;
     a.m = m;
     a.segs = (int)segs;
-    // buckets: bh.wg threads per bucket workgroup (256 / 512 / 1024: buckets of up to 1024 / 2048 / 4096 values), mean bucket
-    // (bh.mean, default: half the workgroup's capacity)
-    int wg_threads = (int)ctx->param(SD_P_BH_WG);
-    wg_threads = wg_threads >= 1024 ? 1024 : wg_threads >= 512 ? 512 : 256;
-    int B = 1;
-    if (m > 4 * (int64_t)wg_threads) {
-        int64_t mean = ctx->param(SD_P_BH_MEAN);
-        // (25 000 x 19 900, 256 threads: mean 400 / 450 / 512 / 600 -> 14.7 / 14.3 / 14.1 / 13.9 ms: fewer, fuller workgroups
-        //  against more buckets beyond the capacity, ~1 % at 0.55 of it)
-        if (mean <= 0) mean = wg_threads * 4 * 55 / 100;
-        mean = std::max<int64_t>(mean, sd_ceil_div(m, (int64_t)MAX_B));
-        B = (int)sd_ceil_div(m, mean);
-        if (B > MAX_B) B = MAX_B;
-    }
-    a.B = B;
-    a.reg_cap = (int)std::min<int64_t>(2048, std::max<int64_t>(0, ctx->param(SD_P_BH_REG_CAP)));
-    a.spb = (int)ctx->param(SD_P_BH_SPB);
-    if (a.spb < 1) a.spb = 1;
-    while (a.spb > 1 && (int64_t)a.spb * B > 8192) a.spb >>= 1;      // the sample is sorted in 96 KB of LDS
-    while (a.spb > 1 && (int64_t)a.spb * B * 2 > m) a.spb >>= 1;
-    a.S = a.spb * B;
-    a.S2 = 1;
-    while (a.S2 < a.S) a.S2 <<= 1;
-    const size_t vals = (size_t)m * (size_t)segs;
-    const size_t sb = (size_t)segs * (size_t)B;
-    a.p_cm = (double*)A.alloc(vals * 8);
-    a.keyS = (uint64_t*)A.alloc(vals * 8);
-    a.spl_k = (uint64_t*)A.alloc(sb * 8);
-    a.bmin = (uint64_t*)A.alloc(sb * 8);
-    a.sfx = (uint64_t*)A.alloc(sb * 8);
-    a.big_list = (int64_t*)A.alloc(sb * 8);
-    a.spl_i = (uint32_t*)A.alloc(sb * 4);
-    a.gcount = (unsigned*)A.alloc(sb * 4);
-    a.cursor = (unsigned*)A.alloc(sb * 4);
-    a.start = (unsigned*)A.alloc((size_t)segs * (size_t)(B + 1) * 4);
-    unsigned long long* zeroed = (unsigned long long*)A.alloc(16);    // spill_n | big_count
-    a.pos_cm = B > 1 ? (uint32_t*)A.alloc(vals * 4) : nullptr;
-    a.spill = B > 1 ? (uint64_t*)A.alloc(vals * 8) : nullptr;
+    a.B = pl.B;
+    a.reg_cap = pl.reg_cap;
+    a.spb = pl.spb;
+    a.S = pl.S;
+    a.S2 = pl.S2;
+    a.p_cm = (double*)A.alloc(pl.p_cm_bytes);
+    a.keyS = (uint64_t*)A.alloc(pl.keyS_bytes);
+    a.spl_k = (uint64_t*)A.alloc(pl.spl_k_bytes);
+    a.bmin = (uint64_t*)A.alloc(pl.bmin_bytes);
+    a.sfx = (uint64_t*)A.alloc(pl.sfx_bytes);
+    a.big_list = (int64_t*)A.alloc(pl.big_list_bytes);
+    a.spl_i = (uint32_t*)A.alloc(pl.spl_i_bytes);
+    a.gcount = (unsigned*)A.alloc(pl.gcount_bytes);
+    a.cursor = (unsigned*)A.alloc(pl.cursor_bytes);
+    a.start = (unsigned*)A.alloc(pl.start_bytes);
+    unsigned long long* zeroed = (unsigned long long*)A.alloc(pl.zeroed_bytes);    // spill_n | big_count
+    a.pos_cm = pl.B > 1 ? (uint32_t*)A.alloc(pl.pos_cm_bytes) : nullptr;
+    a.spill = pl.B > 1 ? (uint64_t*)A.alloc(pl.spill_bytes) : nullptr;
     if (!a.p_cm || !a.keyS || !a.spl_k || !a.bmin || !a.sfx || !a.big_list || !a.spl_i || !a.gcount || !a.cursor || !a.start || !zeroed ||
-        (B > 1 && (!a.pos_cm || !a.spill)))
+        (pl.B > 1 && (!a.pos_cm || !a.spill)))
         return SDICE_ERR_NOMEM;
     a.spill_n = zeroed;
     a.big_count = reinterpret_cast<unsigned*>(zeroed + 1);
-    SD_HIP(hipMemsetAsync(zeroed, 0, 16, ctx->stream));
-    const int64_t strips = sd_ceil_div(segs, (int64_t)TC_COLS);
-    SD_ARG(strips < ((int64_t)1 << 31), "bh: too many columns");
-    const int rows_per_block = (int)std::max<int64_t>(TC_ROWS, std::min<int64_t>(ctx->param(SD_P_BH_ROWS_PER_BLOCK), m));
-    const int strips_per_xcd = (int)sd_ceil_div(strips, (int64_t)8);
-    const int64_t tblocks = (int64_t)strips_per_xcd * 8 * sd_ceil_div(m, (int64_t)rows_per_block);
-    SD_ARG(tblocks < ((int64_t)1 << 31), "bh: too many tiles");
-    const dim3 tgrid((unsigned)tblocks);
-    if (B > 1) {
-        SD_HIP(hipMemsetAsync(a.gcount, 0, sb * 4, ctx->stream));
-        const size_t lds_s = (size_t)a.S2 * 12;
-        SD_LAUNCH_LDS(ctx, "bhs_sample_kernel", bhs_sample_kernel, dim3((unsigned)segs), dim3(256), lds_s, a);
-        const size_t lds_t = (size_t)B * 20;
-        const int64_t tiles = sd_ceil_div(m, (int64_t)TILE);
-        const int64_t tile_blocks = sd_ceil_div(segs, (int64_t)8) * 8 * tiles;
-        SD_ARG(tile_blocks < ((int64_t)1 << 31), "bh: too many tiles");
-        // the splitters of a 16-column strip beside the transpose tile: up to ~190 buckets per column; beyond, the
-        // transpose runs alone and the tiles of the scatter kernel count first
-        const size_t lds_tc = (size_t)TC_COLS * ((size_t)(B - 1) * 12 + (size_t)B * 4);
-        if (lds_tc <= 48 * 1024 && ctx->param(SD_P_BH_FUSED_COUNT)) {
-            SD_LAUNCH(ctx, "bhs_transpose_count_kernel", (bhs_transpose_kernel<true>), tgrid, dim3(TC_T), lds_tc, a, rows_per_block, strips_per_xcd);
+    SD_HIP(hipMemsetAsync(zeroed, 0, pl.zeroed_bytes, ctx->stream));
+    const dim3 tgrid((unsigned)pl.tgrid), tile_grid((unsigned)pl.tile_blocks), bucket_grid((unsigned)pl.bucket_blocks);
+    if (pl.B > 1) {
+        SD_HIP(hipMemsetAsync(a.gcount, 0, pl.gcount_bytes, ctx->stream));
+        SD_LAUNCH_LDS(ctx, "bhs_sample_kernel", bhs_sample_kernel, dim3((unsigned)segs), dim3(256), pl.lds_sample, a);
+        if (pl.fused_count) {
+            SD_LAUNCH(ctx, "bhs_transpose_count_kernel", (bhs_transpose_kernel<true>), tgrid, dim3(TC_T), pl.lds_tc, a, pl.rows_per_block, pl.strips_per_xcd);
         } else {
-            SD_LAUNCH(ctx, "bhs_transpose_kernel", (bhs_transpose_kernel<false>), tgrid, dim3(TC_T), 0, a, rows_per_block, strips_per_xcd);
-            SD_LAUNCH(ctx, "bhs_count_kernel", (bhs_tile_kernel<false>), dim3((unsigned)tile_blocks), dim3(TILE_T), lds_t, a, (int)tiles);
+            SD_LAUNCH(ctx, "bhs_transpose_kernel", (bhs_transpose_kernel<false>), tgrid, dim3(TC_T), 0, a, pl.rows_per_block, pl.strips_per_xcd);
+            SD_LAUNCH(ctx, "bhs_count_kernel", (bhs_tile_kernel<false>), tile_grid, dim3(TILE_T), pl.lds_tile, a, pl.tiles);
         }
         SD_LAUNCH(ctx, "bhs_scan_kernel", bhs_scan_kernel, dim3((unsigned)segs), dim3(256), 0, a);
-        SD_LAUNCH(ctx, "bhs_scatter_kernel", (bhs_tile_kernel<true>), dim3((unsigned)tile_blocks), dim3(TILE_T), lds_t, a, (int)tiles);
+        SD_LAUNCH(ctx, "bhs_scatter_kernel", (bhs_tile_kernel<true>), tile_grid, dim3(TILE_T), pl.lds_tile, a, pl.tiles);
     } else {
-        SD_LAUNCH(ctx, "bhs_transpose_kernel", (bhs_transpose_kernel<false>), tgrid, dim3(TC_T), 0, a, rows_per_block, strips_per_xcd);
+        SD_LAUNCH(ctx, "bhs_transpose_kernel", (bhs_transpose_kernel<false>), tgrid, dim3(TC_T), 0, a, pl.rows_per_block, pl.strips_per_xcd);
     }
-    const int64_t n_buckets = segs * B;
-    const int64_t bucket_blocks = sd_ceil_div(segs, (int64_t)8) * 8 * B;
-    SD_ARG(bucket_blocks < ((int64_t)1 << 31), "bh: too many buckets");
-    // threads of a bucket workgroup (4 values each): twice the mean bucket, so that ~1 % of the buckets (sizes ~ Gamma(8))
-    // overflow to the second kernel
-    if (wg_threads == 256) {
-        SD_LAUNCH(ctx, "bhs_bucket_kernel", (bhs_bucket_kernel<256>), dim3((unsigned)bucket_blocks), dim3(256), (bucket_wg_lds<256, 4>()), a);
-    } else if (wg_threads == 512) {
-        SD_LAUNCH(ctx, "bhs_bucket_kernel", (bhs_bucket_kernel<512>), dim3((unsigned)bucket_blocks), dim3(512), (bucket_wg_lds<512, 4>()), a);
+    if (pl.wg_threads == 256) {
+        SD_LAUNCH(ctx, "bhs_bucket_kernel", (bhs_bucket_kernel<256>), bucket_grid, dim3(256), pl.lds_bucket, a);
+    } else if (pl.wg_threads == 512) {
+        SD_LAUNCH(ctx, "bhs_bucket_kernel", (bhs_bucket_kernel<512>), bucket_grid, dim3(512), pl.lds_bucket, a);
     } else {
-        SD_LAUNCH_LDS(ctx, "bhs_bucket_kernel", (bhs_bucket_kernel<1024>), dim3((unsigned)bucket_blocks), dim3(1024), (bucket_wg_lds<1024, 4>()), a);
+        SD_LAUNCH_LDS(ctx, "bhs_bucket_kernel", (bhs_bucket_kernel<1024>), bucket_grid, dim3(1024), pl.lds_bucket, a);
     }
-    const int64_t big_blocks = std::max<int64_t>(1, std::min<int64_t>(n_buckets, (int64_t)ctx->n_cu * 4));
-    // the listed buckets of 1 025 ... 2 048 values: 512 threads x 4 values (109 VGPRs) take 0.61 ms on the bench's table where
-    // 256 x 8 (173 VGPRs, two waves per SIMD) take 0.77
-    if (ctx->param(SD_P_BH_BIG_WG) >= 512) {
-        SD_LAUNCH(ctx, "bhs_bucket_big_kernel", (bhs_bucket_big_kernel<512, 4>), dim3((unsigned)big_blocks), dim3(512), (bucket_wg_lds<512, 4>()), a);
+    if (pl.big_wg == 512) {
+        SD_LAUNCH(ctx, "bhs_bucket_big_kernel", (bhs_bucket_big_kernel<512, 4>), dim3((unsigned)pl.big_blocks), dim3(512), pl.lds_big, a);
     } else {
-        SD_LAUNCH(ctx, "bhs_bucket_big_kernel", (bhs_bucket_big_kernel<256, 8>), dim3((unsigned)big_blocks), dim3(256), (bucket_wg_lds<256, 8>()), a);
+        SD_LAUNCH(ctx, "bhs_bucket_big_kernel", (bhs_bucket_big_kernel<256, 8>), dim3((unsigned)pl.big_blocks), dim3(256), pl.lds_big, a);
     }
-    SD_LAUNCH(ctx, "bhs_bucket_zoom_kernel", bhs_bucket_zoom_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(n_buckets, (int64_t)ctx->n_cu * 6))), dim3(256), (bucket_wg_lds<256, 4>()), a);
+    SD_LAUNCH(ctx, "bhs_bucket_zoom_kernel", bhs_bucket_zoom_kernel, dim3((unsigned)pl.zoom_blocks), dim3(256), pl.lds_zoom, a);
     SD_LAUNCH(ctx, "bhs_suffix_kernel", bhs_suffix_kernel, dim3((unsigned)segs), dim3(256), 0, a);
-    // bh.finish_cols: columns per workgroup of the last kernel (16: full 128-byte lines out, 3.2 MB of results per strip
-    // at 25 000 rows; 8: half lines, half the L2 footprint of the gather); bh.finish_nt: non-temporal gather loads
-    const int fcols = ctx->param(SD_P_BH_FINISH_COLS) >= 16 ? 16 : 8;
-    const bool fnt = ctx->param(SD_P_BH_FINISH_NT) != 0;
-    const int64_t fstrips = sd_ceil_div(segs, (int64_t)fcols);
-    const int64_t row_tiles = sd_ceil_div(m, (int64_t)(2048 / fcols));
-    const int64_t fin_blocks = sd_ceil_div(fstrips, (int64_t)8) * 8 * row_tiles;
-    SD_ARG(fin_blocks < ((int64_t)1 << 31), "bh: too many tiles");
-    if (fcols == 16) {
-        if (fnt) SD_LAUNCH(ctx, "bhs_finish_kernel", (bhs_finish_kernel<16, true>), dim3((unsigned)fin_blocks), dim3(TC_T), 0, a, d_rm, (int)row_tiles);
-        else SD_LAUNCH(ctx, "bhs_finish_kernel", (bhs_finish_kernel<16, false>), dim3((unsigned)fin_blocks), dim3(TC_T), 0, a, d_rm, (int)row_tiles);
+    const dim3 fin_grid((unsigned)pl.fin_blocks);
+    if (pl.fcols == 16) {
+        if (pl.fnt) SD_LAUNCH(ctx, "bhs_finish_kernel", (bhs_finish_kernel<16, true>), fin_grid, dim3(TC_T), 0, a, d_rm, pl.row_tiles);
+        else SD_LAUNCH(ctx, "bhs_finish_kernel", (bhs_finish_kernel<16, false>), fin_grid, dim3(TC_T), 0, a, d_rm, pl.row_tiles);
     } else {
-        if (fnt) SD_LAUNCH(ctx, "bhs_finish_kernel", (bhs_finish_kernel<8, true>), dim3((unsigned)fin_blocks), dim3(TC_T), 0, a, d_rm, (int)row_tiles);
-        else SD_LAUNCH(ctx, "bhs_finish_kernel", (bhs_finish_kernel<8, false>), dim3((unsigned)fin_blocks), dim3(TC_T), 0, a, d_rm, (int)row_tiles);
+        if (pl.fnt) SD_LAUNCH(ctx, "bhs_finish_kernel", (bhs_finish_kernel<8, true>), fin_grid, dim3(TC_T), 0, a, d_rm, pl.row_tiles);
+        else SD_LAUNCH(ctx, "bhs_finish_kernel", (bhs_finish_kernel<8, false>), fin_grid, dim3(TC_T), 0, a, d_rm, pl.row_tiles);
     }
     return SDICE_OK;
 }
 
-// One vector of n p-values (masked: entries with tested == 0 -- or p < 0 without a mask -- are absent).  Supported sizes:
-// the sample fits the brute-force ranking and a bucket fits LDS.
-bool sd_bh_vector_supported(int64_t n) { return n >= 16384 && n <= ((int64_t)2 << 20); }      // (up to 1024 buckets of 2048 on average)
-// geometry of the one-vector path: buckets of ~2048 values, 16 samples per bucket (sizes ~ Gamma(16): sigma = mean / 4);
-// a bucket beyond its slot / the LDS capacity (5632 = mean + 7 sigma) practically never occurs (slow path: one wave, HBM)
-static void bhv_geometry(sdice_ctx* ctx, int64_t n, int* B_out, int* cap_out) {
-    int64_t mean = ctx->param(SD_P_BHV_MEAN);
-    if (mean < 512) mean = 512;
-    if (mean < sd_ceil_div(n, (int64_t)1024)) mean = sd_ceil_div(n, (int64_t)1024);
-    int B = (int)sd_ceil_div(n, mean);
-    if (B < 2) B = 2;
-    if (B > 1024) B = 1024;
-    int cap = (int)ctx->param(SD_P_BHV_CAP);     // 5632 x 13 B = 73 KB of LDS: two bucket workgroups per CU
-    if (cap < 64) cap = 64;
-    if (cap > BHV_T * BHV_EPT) cap = BHV_T * BHV_EPT;
-    *B_out = B; *cap_out = cap;
-}
-// slots (12 B x cap per bucket) + partial results (10 B per value) + the overflow list and the slow path's assembly area
-// (14 + 12 B per value) + the sample ranks
-size_t sd_bh_vector_scratch(sdice_ctx* ctx, int64_t n) {
-    int B, cap;
-    bhv_geometry(ctx, n, &B, &cap);
-    return (size_t)n * 36 + (size_t)B * (size_t)cap * 12 + (size_t)B * 80 + (1 << 16);
-}
+size_t sd_bh_vector_scratch(sdice_ctx* ctx, int64_t n) { return sd_bhv_scratch(ctx->params, n); }
 
+// One vector of n p-values (masked: entries with tested == 0 -- or p < 0 without a mask -- are absent); geometry:
+// sd_bhv_plan (bhplan.cpp).
 int sd_bh_vector_samplesort(sdice_ctx* ctx, int64_t n, const double* d_p, const uint8_t* d_tested, bool masked, double* d_q) {
+    SdBhvPlan pl;
+    sd_bhv_plan(ctx->params, n, &pl);
     Arena& A = ctx->arena;
     BhvArgs a;
     a.p = d_p; a.tested = d_tested; a.masked = masked ? 1 : 0; a.n = n; a.q = d_q;
-    int B;
-    bhv_geometry(ctx, n, &B, &a.cap);
-    a.B = B;
-    a.spb = 16;
-    a.S = a.spb * B;
-    const size_t N = (size_t)n;
-    // one zeroed block: rank[S] | cursor[B] | tile_done[S / 256] | m_eff | ovf_n | spill_n
-    const unsigned gs = (unsigned)sd_ceil_div(a.S, 256);
-    const size_t zwords = (size_t)a.S + (size_t)B + gs + 8;
-    unsigned* z = (unsigned*)A.alloc(zwords * 4);
-    a.keyS = (uint64_t*)A.alloc((size_t)B * a.cap * 8);
-    a.qpart = (uint64_t*)A.alloc(N * 8);
-    a.ovfK = (uint64_t*)A.alloc(N * 8);
-    a.spillK = (uint64_t*)A.alloc(N * 8);
-    a.bmin = (uint64_t*)A.alloc((size_t)B * 8);
-    a.idxS = (uint32_t*)A.alloc((size_t)B * a.cap * 4);
-    a.ovfI = (uint32_t*)A.alloc(N * 4);
-    a.spillI = (uint32_t*)A.alloc(N * 4);
-    a.bid = (uint16_t*)A.alloc(N * 2);
-    a.ovfB = (uint16_t*)A.alloc(N * 2);
+    a.B = pl.B;
+    a.cap = pl.cap;
+    a.spb = BHV_SPB;
+    a.S = pl.S;
+    unsigned* z = (unsigned*)A.alloc(pl.z_bytes);
+    a.keyS = (uint64_t*)A.alloc(pl.keyS_bytes);
+    a.qpart = (uint64_t*)A.alloc(pl.qpart_bytes);
+    a.ovfK = (uint64_t*)A.alloc(pl.ovfK_bytes);
+    a.spillK = (uint64_t*)A.alloc(pl.spillK_bytes);
+    a.bmin = (uint64_t*)A.alloc(pl.bmin_bytes);
+    a.idxS = (uint32_t*)A.alloc(pl.idxS_bytes);
+    a.ovfI = (uint32_t*)A.alloc(pl.ovfI_bytes);
+    a.spillI = (uint32_t*)A.alloc(pl.spillI_bytes);
+    a.bid = (uint16_t*)A.alloc(pl.bid_bytes);
+    a.ovfB = (uint16_t*)A.alloc(pl.ovfB_bytes);
     if (!z || !a.keyS || !a.qpart || !a.ovfK || !a.spillK || !a.bmin || !a.idxS || !a.ovfI || !a.spillI || !a.bid || !a.ovfB)
         return SDICE_ERR_NOMEM;
     a.rank = z;
-    a.cursor = z + a.S;
-    a.tile_done = a.cursor + B;
-    a.m_eff = (unsigned long long*)(a.tile_done + gs + ((a.S + B + gs) & 1));      // 8-byte aligned
-    a.spl_k = (uint64_t*)A.alloc((size_t)B * 8);
-    a.spl_i = (uint32_t*)A.alloc((size_t)B * 4);
+    a.cursor = z + pl.S;
+    a.tile_done = a.cursor + pl.B;
+    a.m_eff = (unsigned long long*)(z + pl.m_eff_word);      // 8-byte aligned
+    a.spl_k = (uint64_t*)A.alloc(pl.spl_k_bytes);
+    a.spl_i = (uint32_t*)A.alloc(pl.spl_i_bytes);
     if (!a.spl_k || !a.spl_i) return SDICE_ERR_NOMEM;
     a.ovf_n = a.m_eff + 1;
     a.spill_n = a.m_eff + 2;
-    SD_HIP(hipMemsetAsync(z, 0, zwords * 4, ctx->stream));
-    SD_LAUNCH(ctx, "bhv_rank_kernel", bhv_rank_kernel, dim3(gs, gs), dim3(256), 0, a);
-    const unsigned tiles = (unsigned)sd_ceil_div(n, (int64_t)(BHV_T * BHV_E));
-    const size_t lds_t = (size_t)B * 20;
-    SD_LAUNCH(ctx, "bhv_scatter_kernel", bhv_scatter_kernel, dim3(tiles), dim3(BHV_T), lds_t, a);
-    const size_t lds_b = (((size_t)a.cap * 13 + 15) / 16) * 16;
-    SD_LAUNCH_LDS(ctx, "bhv_bucket_kernel", bhv_bucket_kernel, dim3((unsigned)B), dim3(BHV_T), lds_b, a);
-    SD_LAUNCH(ctx, "bhv_finish_kernel", bhv_finish_kernel, dim3(tiles), dim3(BHV_T), 0, a);
+    SD_HIP(hipMemsetAsync(z, 0, pl.z_bytes, ctx->stream));
+    SD_LAUNCH(ctx, "bhv_rank_kernel", bhv_rank_kernel, dim3(pl.rank_grid, pl.rank_grid), dim3(256), 0, a);
+    SD_LAUNCH(ctx, "bhv_scatter_kernel", bhv_scatter_kernel, dim3(pl.tiles), dim3(BHV_T), pl.lds_tile, a);
+    SD_LAUNCH_LDS(ctx, "bhv_bucket_kernel", bhv_bucket_kernel, dim3((unsigned)pl.B), dim3(BHV_T), pl.lds_bucket, a);
+    SD_LAUNCH(ctx, "bhv_finish_kernel", bhv_finish_kernel, dim3(pl.tiles), dim3(BHV_T), 0, a);
     return SDICE_OK;
 }

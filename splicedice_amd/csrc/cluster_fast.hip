@@ -41,6 +41,7 @@
 // at the next sdice_sync / sdice_cluster_status); a failed chain leaves row_ptr all zero (safe for a
 // dependent PS launch) and the failure is reported then.
 #include "common.h"
+#include "cluster.h"
 
 // Timing experiments (tools/ablate_cluster.py, param cluster.ablate) are compiled in only with
 // `make EXTRA=-DSDICE_CLUSTER_ABLATE=1`; the shipped kernels carry no trace of them.
@@ -54,19 +55,8 @@ int sd_cluster_legacy(sdice_ctx* ctx, int64_t n, const int32_t* d_chrom, const i
 
 namespace {
 
-constexpr int SPB = 8;                 // sample keys per bucket
-constexpr int BUCKET_MEAN = 2048;      // keys per bucket (mean)
-constexpr int MAX_BUCKETS = 4096;      // splitters + per-bucket counters must fit LDS of the scatter kernel
-constexpr int SLOT_FACTOR = 8;         // bucket slot capacity in HBM = 8 x mean
-constexpr int64_t FAST_MAX_N = (int64_t)MAX_BUCKETS * BUCKET_MEAN;
-
+// (bucket and sample constants, the words of the status block, SC_KPT, SORT_T, RDX_CAP, NB_T: cluster.h, shared with the planner)
 enum : unsigned long long { ST_INVALID = 1, ST_SLOT_OVERFLOW = 2, ST_DUP = 4, ST_COL_OVERFLOW = 8, ST_LOOKBACK = 16 };
-// status block (uint64 words)
-constexpr int SB_FLAGS = 0, SB_NNZ = 2, SB_MAXLEN = 32, SB_REACH = 64, SB_WORDS = 96;
-// word SB_STICKY lies BEHIND the words a chain clears: every flag is also OR-ed into it, and only the call that reports
-// the status clears it -- the failure of an asynchronous chain survives the chains enqueued behind it
-constexpr int SB_STICKY = SB_WORDS, SB_ALLOC_WORDS = SB_WORDS + 8;
-constexpr int SB_SLOTS = 32;
 
 struct FastArgs {
     const int32_t* chrom; const int32_t* left; const int32_t* right; const int8_t* strand;
@@ -163,7 +153,6 @@ __global__ void __launch_bounds__(256) sample_rank_kernel(FastArgs a) {
 }
 
 // ------------------------------------------------------------------ 2. classify + scatter into slots
-constexpr int SC_KPT = 4;
 template <int T>
 __global__ void __launch_bounds__(T) bucket_scatter_kernel(FastArgs a) {
     extern __shared__ uint64_t sm64[];
@@ -353,7 +342,7 @@ __device__ __forceinline__ void bitonic_sort_u64(uint64_t* buf, int count, int P
     __syncthreads();
 }
 
-constexpr int SORT_T_ = 1024;
+constexpr int SORT_T_ = SORT_T;
 // ---- sorting a bucket's packed keys WITHOUT the workgroup-wide network: an LDS-local sample sort.
 // The network above costs ~66 dependent LDS round trips for a 2 048-key bucket, most of them behind a
 // workgroup barrier -- ~50 us per workgroup, and the whole grid is one round of workgroups, so that IS
@@ -520,12 +509,9 @@ __device__ __forceinline__ bool lds_sample_sort(uint64_t* kb, int count, int t) 
     return true;
 }
 
-constexpr int SORT_T = SORT_T_;
 constexpr int SORT_WAVES = SORT_T / 64;
-constexpr int RDX_CAP = 8192;                    // packed 64-bit keys a bucket may hold in LDS
 constexpr int RDX_IDX_BITS = 13;                 // slot index of an element rides in the low bits of its key
 constexpr int SORT_LDS_ELEMS = 4096;             // 16-byte elements of the unpacked fallback (same LDS)
-constexpr size_t SORT_LDS_BYTES = (size_t)RDX_CAP * 8;     // 64 KB: two workgroups per CU
 static_assert(SORT_LDS_BYTES >= (size_t)SORT_LDS_ELEMS * 16, "unpacked fallback must fit");
 
 __device__ __forceinline__ int bits_u32(uint32_t v) { return v ? 32 - __clz(v) : 0; }
@@ -1027,43 +1013,34 @@ __global__ void __launch_bounds__(T, 8) neighbours_kernel(FastArgs a) {      // 
     }   // tile loop
 }
 
-inline unsigned grid_for(int64_t n, int threads) { return (unsigned)sd_ceil_div(n, threads); }
-
 struct FastPlan {
     FastArgs a;
-    size_t zero_bytes;     // the region cleared before every run (status block .. tile states)
-    void* zero_base;
-    size_t k4_zero_bytes;  // part of it needed again when only the neighbour kernel is re-run
-    int n_tiles;
+    SdClusterPlan g;       // the geometry (clusterplan.cpp)
+    void* zero_base;       // the region cleared before every run (tile states .. col_done)
 };
 
-constexpr int NB_T = 512;
+// workgroups of the neighbour kernel a CU holds at once
+int neighbours_per_cu(int* out) {
+    static int per_cu = 0;
+    if (per_cu == 0) {
+        int occ = 0;
+        SD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(neighbours_kernel<NB_T>), NB_T, 0));
+        per_cu = occ > 0 ? occ : 1;
+    }
+    *out = per_cu;
+    return SDICE_OK;
+}
 
+// the plan, the status block and the plan's byte counts turned into pointers
 int fast_plan(sdice_ctx* ctx, int64_t n, const int32_t* d_chrom, const int32_t* d_left, const int32_t* d_right,
               const int8_t* d_strand, int32_t* d_row_of, int64_t* d_row_ptr, FastPlan& pl) {
+    int per_cu = 0;
+    SD_TRY(neighbours_per_cu(&per_cu));
+    SdClusterPlan& g = pl.g;
+    sd_cluster_fast_plan(ctx->params, SdClusterFacts{n, per_cu, ctx->n_cu}, &g);
     FastArgs& a = pl.a;
     a.chrom = d_chrom; a.left = d_left; a.right = d_right; a.strand = d_strand; a.n = n;
-    static_assert(kSdParams[SD_P_CLUSTER_BUCKET_MEAN].dflt == BUCKET_MEAN, "the default is the largest mean the kernels take");
-    int64_t bucket_mean = ctx->param(SD_P_CLUSTER_BUCKET_MEAN);
-    if (bucket_mean < 256 || bucket_mean > BUCKET_MEAN) bucket_mean = BUCKET_MEAN;
-    int64_t B = sd_ceil_div(n, bucket_mean);
-    if (B < 1) B = 1;
-    if (B > MAX_BUCKETS) B = MAX_BUCKETS;
-    a.B = (int)B;
-    // samples per bucket: 12 up to 2 M junctions (tighter bucket sizes: the largest bucket IS the sort kernel's time; -1.4 % on
-    // the whole quant step at 1 M), 8 beyond (the sample is ranked by brute force, O(S^2))
-    a.spb = (int)ctx->param(SD_P_CLUSTER_SPB);
-    if (a.spb < 2 || a.spb > 64) a.spb = n <= ((int64_t)2 << 20) ? 12 : SPB;
-    a.S = B > 1 ? (int)(B * a.spb) : 0;
-    const int64_t mean = sd_ceil_div(n, B);
-    a.slot_cap = B > 1 ? (mean * SLOT_FACTOR < n ? mean * SLOT_FACTOR : n) : n;
-    int64_t lds_cap = ctx->param(SD_P_CLUSTER_LDS_CAP);      // (test knob: 0 = default; small values force the HBM sort)
-    if (lds_cap <= 0 || lds_cap > 8192) lds_cap = 8192;
-    if (lds_cap < 2) lds_cap = 2;
-    a.lds_cap = (int)lds_cap;
-    a.sample_sort = ctx->param(SD_P_CLUSTER_SAMPLE_SORT) != 0;
-    pl.n_tiles = (int)sd_ceil_div(n, NB_T);
-    const size_t nb64 = (size_t)sd_ceil_div(n, 64) + 2;
+    a.B = g.B; a.spb = g.spb; a.S = g.S; a.slot_cap = g.slot_cap; a.lds_cap = g.lds_cap; a.sample_sort = g.sample_sort;
     // The status block is a small persistent allocation of the context (an asynchronous call is
     // resolved later, when the arena may already hold another call's scratch).
     if (!ctx->cluster_sb) {
@@ -1074,30 +1051,22 @@ int fast_plan(sdice_ctx* ctx, int64_t n, const int32_t* d_chrom, const int32_t* 
         }
         SD_HIP(hipMemsetAsync(ctx->cluster_sb, 0, (size_t)SB_ALLOC_WORDS * 8, ctx->stream));
     }
-    // zero region: [tile states] (needed by every neighbour run) then [cursor | rank | bmax64]
-    const size_t zk4 = ((size_t)pl.n_tiles + 2) * 8;      // (+ the ticket counter of the tile loop behind the tile states)
-    const size_t n_cd = (size_t)(a.S + 255) / 256 + 4;
-    const size_t zrest = (size_t)a.B * 4 + (size_t)(a.S + 4) * 4 + nb64 * 4 + n_cd * 4;     // cursor | rank | bmax64 | col_done
-    const size_t slots_bytes = (size_t)a.B * (size_t)a.slot_cap * 16;
-    const size_t total = zk4 + zrest + slots_bytes + (size_t)n * 12 + (size_t)a.B * 16 + 16 * 4096;
-    SD_TRY(ctx->arena.reserve(total, ctx->stream));
+    SD_TRY(ctx->arena.reserve(g.reserve_bytes, ctx->stream));
     Arena& A = ctx->arena;
-    char* z = (char*)A.alloc(zk4 + zrest + 1024);
-    a.slots = (uint4*)A.alloc(slots_bytes);
-    a.rowC = (uint32_t*)A.alloc((size_t)n * 4);
-    a.rowL = (uint32_t*)A.alloc((size_t)n * 4);
-    a.rowR2 = (uint32_t*)A.alloc((size_t)n * 4);
-    a.spl = (uint64_t*)A.alloc((size_t)a.B * 8 + 8);
+    char* z = (char*)A.alloc(g.z_alloc_bytes);
+    a.slots = (uint4*)A.alloc(g.slots_bytes);
+    a.rowC = (uint32_t*)A.alloc(g.row_bytes);
+    a.rowL = (uint32_t*)A.alloc(g.row_bytes);
+    a.rowR2 = (uint32_t*)A.alloc(g.row_bytes);
+    a.spl = (uint64_t*)A.alloc(g.spl_bytes);
     if (!z || !a.slots || !a.rowC || !a.rowL || !a.rowR2 || !a.spl) return SDICE_ERR_NOMEM;
     pl.zero_base = z;
-    pl.k4_zero_bytes = zk4;
-    pl.zero_bytes = zk4 + zrest;
     a.sb = (unsigned long long*)ctx->cluster_sb;
     a.tile_state = (unsigned long long*)z;
-    a.cursor = (uint32_t*)(z + zk4);
-    a.rank = a.cursor + a.B;
-    a.bmax64 = a.rank + a.S + 4;
-    a.col_done = a.bmax64 + nb64;
+    a.cursor = (uint32_t*)(z + g.cursor_off);
+    a.rank = (uint32_t*)(z + g.rank_off);
+    a.bmax64 = (uint32_t*)(z + g.bmax64_off);
+    a.col_done = (uint32_t*)(z + g.col_done_off);
     a.row_of = d_row_of; a.row_ptr = d_row_ptr;
     a.ablate = (int)ctx->param(SD_P_CLUSTER_ABLATE);
     return SDICE_OK;
@@ -1107,18 +1076,7 @@ int launch_neighbours(sdice_ctx* ctx, FastPlan& pl) {
     pl.a.col = ctx->d_col;
     pl.a.col_cap = ctx->col_cap;
     pl.a.blkneed = ctx->d_reach;
-    // at most as many workgroups as the device holds at once (what the look-back's forward progress rests on); cluster.nb_grid
-    // overrides it downwards (tests: a handful of workgroups walking many tiles each)
-    static int per_cu = 0;
-    if (per_cu == 0) {
-        int occ = 0;
-        SD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(neighbours_kernel<NB_T>), NB_T, 0));
-        per_cu = occ > 0 ? occ : 1;
-    }
-    int64_t grid = std::min<int64_t>(pl.n_tiles, (int64_t)per_cu * ctx->n_cu);
-    const int64_t forced = ctx->param(SD_P_CLUSTER_NB_GRID);
-    if (forced > 0) grid = std::min<int64_t>(grid, forced);
-    SD_LAUNCH(ctx, "neighbours_kernel", (neighbours_kernel<NB_T>), dim3((unsigned)std::max<int64_t>(grid, 1)), dim3(NB_T), 0, pl.a);
+    SD_LAUNCH(ctx, "neighbours_kernel", (neighbours_kernel<NB_T>), dim3((unsigned)pl.g.nb_grid), dim3(NB_T), 0, pl.a);
     return SDICE_OK;
 }
 
@@ -1233,7 +1191,7 @@ extern "C" int sdice_cluster_dev(sdice_ctx* ctx, int64_t n, const int32_t* d_chr
     // one leaves their status pending: failures accumulate in the sticky word of the status block
     if (nnz_out && ctx->cluster_pending) SD_TRY(sd_cluster_resolve(ctx));
     ctx->reach_n = 0;
-    const bool legacy = n > FAST_MAX_N || ctx->param(SD_P_CLUSTER_GENERIC) || ctx->param(SD_P_CLUSTER_LEGACY);
+    const bool legacy = sd_cluster_takes_legacy(ctx->params, n);
     if ((legacy || n == 0) && ctx->cluster_pending) SD_TRY(sd_cluster_resolve(ctx));     // (the generic path synchronises)
     if (legacy || n == 0) return sd_cluster_legacy(ctx, n, d_chrom, d_left, d_right, d_strand, d_row_of, d_row_ptr, nnz_out);
     SD_ARG(d_chrom && d_left && d_right && d_strand && d_row_of && d_row_ptr, "NULL pointer");
@@ -1244,29 +1202,21 @@ extern "C" int sdice_cluster_dev(sdice_ctx* ctx, int64_t n, const int32_t* d_chr
     FastPlan pl;
     SD_TRY(fast_plan(ctx, n, d_chrom, d_left, d_right, d_strand, d_row_of, d_row_ptr, pl));
     FastArgs& a = pl.a;
+    const SdClusterPlan& g = pl.g;
     // list capacity: what the last clustering needed, at least 16 entries per junction
     SD_TRY(ensure_col(ctx, 16 * n + 1024));
     SD_TRY(ensure_reach(ctx, n));
 
-    SD_HIP(hipMemsetAsync(pl.zero_base, 0, pl.zero_bytes, ctx->stream));
-    if (a.S == 0) SD_HIP(hipMemsetAsync(a.sb, 0, (size_t)SB_WORDS * 8, ctx->stream));   // (else cleared by the rank kernel)
-    if (a.S > 0) {
-        const unsigned g = grid_for(a.S, 256);
-        SD_LAUNCH(ctx, "sample_rank_kernel", sample_rank_kernel, dim3(g, g), dim3(256), 0, a);
+    SD_HIP(hipMemsetAsync(pl.zero_base, 0, g.zero_bytes, ctx->stream));
+    if (g.S == 0) SD_HIP(hipMemsetAsync(a.sb, 0, (size_t)SB_WORDS * 8, ctx->stream));   // (else cleared by the rank kernel)
+    if (g.S > 0)
+        SD_LAUNCH(ctx, "sample_rank_kernel", sample_rank_kernel, dim3(g.rank_grid, g.rank_grid), dim3(256), 0, a);
+    if (g.scatter_wg == 512) {
+        SD_LAUNCH_LDS(ctx, "bucket_scatter_kernel", (bucket_scatter_kernel<512>), dim3((unsigned)g.scatter_grid), dim3(512), g.scatter_lds, a);
+    } else {
+        SD_LAUNCH_LDS(ctx, "bucket_scatter_kernel", (bucket_scatter_kernel<1024>), dim3((unsigned)g.scatter_grid), dim3(1024), g.scatter_lds, a);
     }
-    {
-        const size_t lds = (size_t)a.B * 16;
-        // tiles of 2048 keys (512 threads) for small inputs, 4096 (1024 threads) beyond
-        if (n <= (1 << 19)) {      // (4096-key tiles halve the global atomics: 27.5 -> 21.4 us at 1 M keys)
-            SD_LAUNCH_LDS(ctx, "bucket_scatter_kernel", (bucket_scatter_kernel<512>), dim3(grid_for(n, 512 * SC_KPT)), dim3(512), lds, a);
-        } else {
-            SD_LAUNCH_LDS(ctx, "bucket_scatter_kernel", (bucket_scatter_kernel<1024>), dim3(grid_for(n, 1024 * SC_KPT)), dim3(1024), lds, a);
-        }
-    }
-    {
-        const size_t lds = SORT_LDS_BYTES;
-        SD_LAUNCH_LDS(ctx, "bucket_sort_kernel", bucket_sort_kernel, dim3((unsigned)a.B), dim3(SORT_T), lds, a);
-    }
+    SD_LAUNCH_LDS(ctx, "bucket_sort_kernel", bucket_sort_kernel, dim3((unsigned)g.sort_grid), dim3(SORT_T), SORT_LDS_BYTES, a);
     SD_TRY(launch_neighbours(ctx, pl));
 
     if (!nnz_out) {          // asynchronous: the status is resolved at the next synchronising call
@@ -1283,7 +1233,7 @@ extern "C" int sdice_cluster_dev(sdice_ctx* ctx, int64_t n, const int32_t* d_chr
     if (flags & ST_COL_OVERFLOW) {
         SD_TRY(sd_cluster_check_nnz(ctx, nnz, false));
         SD_TRY(ensure_col(ctx, nnz + nnz / 8 + 1024));
-        SD_HIP(hipMemsetAsync(pl.zero_base, 0, pl.k4_zero_bytes, ctx->stream));
+        SD_HIP(hipMemsetAsync(pl.zero_base, 0, g.zk4_bytes, ctx->stream));
         // flags, total and reach start over; the maximum length (words SB_MAXLEN..) stays
         SD_HIP(hipMemsetAsync(a.sb, 0, (size_t)SB_MAXLEN * 8, ctx->stream));
         SD_HIP(hipMemsetAsync(a.sb + SB_REACH, 0, (size_t)SB_SLOTS * 8, ctx->stream));

@@ -31,6 +31,7 @@
 // if the exact quotient were within 2^-53 of a float32 midpoint, impossible for a
 // denominator below 2^24).  Otherwise 64-bit sums and the float64 division are used.
 #include "common.h"
+#include "ps.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -772,125 +773,37 @@ extern "C" int sdice_ps_dev(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t*
     SD_ARG(d_counts && d_row_ptr, "NULL input");
     SD_HIP(hipSetDevice(ctx->device));
 
-    const bool aligned = ((uintptr_t)d_counts % 16 == 0) && (!d_ps || (uintptr_t)d_ps % 16 == 0) &&
-                         (!d_excl || (uintptr_t)d_excl % 16 == 0);
-    const int vec = (s % 4 == 0 && aligned) ? 4 : 1;
-    const int abl = (int)ctx->param(SD_P_PS_ABLATE);
-    int cw = s;
-    const int64_t chunk_param = ctx->param(SD_P_PS_CHUNK_COLS);
-    if (chunk_param > 0) cw = (int)chunk_param;
-    else if (s > 256) cw = 128;
-    if (cw > s) cw = s;
-    if (vec == 4) cw = (cw / 4) * 4;
-    if (cw < vec) cw = vec;
-    // kernel: 0 = second-generation register-staged kernel (ps_tile_v3_kernel, the default), 2 = first-generation kernel
-    // (ps_tile_kernel; also serves tables whose rows are not 16-byte vectors, column chunks whose vectors do not divide
-    // 64, tile shapes beyond the register staging of the newer kernel, and the timing experiments)
-    const bool pow2chunk = cw == s || (cw / 4 <= 64 && 64 % (cw / 4) == 0);
-    int kern = ctx->param(SD_P_PS_GEN1) != 0 ? 2 : 0;
-    if (vec != 4 || abl != 0 || !pow2chunk) kern = 2;
-    if ((int64_t)s * 2048 >= ((int64_t)1 << 30)) kern = 2;       // (the newer kernel addresses a tile's outputs by 32-bit offsets)
-    int64_t lds = ctx->param(SD_P_PS_LDS_BYTES);   // two workgroups per CU (160 KiB LDS)
-    if (lds > 160 * 1024) lds = 160 * 1024;
-    if (lds < 8 * 1024) lds = 8 * 1024;
-    int threads = (int)ctx->param(SD_P_PS_THREADS);
-    threads = (threads / 64) * 64;
-    if (threads < 64) threads = 64;
-    if (threads > 1024) threads = 1024;
-    const int64_t LV = vec == 4 ? cw / 4 : cw;              // 16-byte vectors of a window row
-
-    int64_t R = 0, H = 0;
-    bool have_reach = false;
-    // tile geometry; a shape that the register staging of the second-generation kernel cannot hold (it stages FOUR
-    // vectors of the tile's own rows, TWO of each halo run and the low words of TWO row pointers per thread) falls back
-    // to the first-generation kernel, whose loops take any shape
-    for (;;) {
-        const bool newk = kern == 0;
-        // LDS budget (ints): (R + 2H + 1) * cw window + 16 R staged neighbour offsets + (R + 1) row pointers + scratch
-        const int64_t L = lds / 4 - (newk ? 64 : 16);      // (the newer kernel keeps 16 per-wave words behind the row pointers)
-        have_reach = newk && d_col != nullptr && d_col == ctx->d_col && ctx->reach_n == n && ctx->d_reach != nullptr &&
-                     ctx->param(SD_P_PS_USE_REACH) != 0;
-        H = ctx->param(SD_P_PS_HALO_ROWS);
-        const bool h_auto = H < 0;
-        if (h_auto) {
-            // rows further than the halo are still summed exactly (global-memory path).  With reach bytes H is the
-            // CAPACITY of the window on each side (a tile stages what its lists reach, 8 + 8 rows on average on
-            // gene-shaped data, 22 at most); without them H rows are staged on each side: 16 cover >99.9 % of the
-            // neighbours of gene-shaped data, less if the clustering saw a smaller reach
-            H = 16;
-            if (!have_reach && d_col != nullptr && d_col == ctx->d_col && ctx->cluster_reach > 0 && ctx->cluster_reach < H)
-                H = ctx->cluster_reach;
-        }
-        // (a software-pipelined persistent variant -- one workgroup per CU, two LDS buffers, next tile's
-        //  loads in flight during the gather -- was built and measured 30 % slower: the kernel is VALU-issue
-        //  bound, and halving the resident waves costs more than hiding the load latency gains)
-        // caps of the register staging: rows <= 4 T / LV (own rows), rows <= 2 T - 1 (row pointers: nr + 1 of them),
-        // halo <= T / LV (each of the two runs takes one vector per thread)
-        const int64_t r_cap = newk ? std::min<int64_t>(4 * (int64_t)threads / LV, 2 * (int64_t)threads - 1) : 2 * (int64_t)threads;
-        const int64_t h_cap = newk ? (int64_t)threads / LV : (int64_t)1 << 20;
-        if (H > h_cap) H = h_cap;
-        const int64_t per_row = 17;      // 16 staged neighbour offsets + the row pointer
-        const int64_t r_param = ctx->param(SD_P_PS_TILE_ROWS);
-        auto fit_rows = [&](int64_t h) {
-            int64_t r = r_param > 0 ? r_param : (L - (2 * h + 1) * cw) / (cw + per_row);
-            return std::min(r, r_cap);
-        };
-        R = fit_rows(H);
-        while (H > 0 && (R < std::min<int64_t>(8, r_cap) || (R + 2 * H + 1) * cw + per_row * R > L)) {
-            // window does not fit: shrink the halo first (misses fall back to global loads), then the tile
-            H = H / 2;
-            R = fit_rows(H);
-        }
-        if (R < 1) R = 1;
-        while (R > 1 && (R + 2 * H + 1) * cw + per_row * R > L) R -= 1;
-        if (newk && (r_cap < 1 || R > r_cap || (R + 2 * H + 1) * cw + per_row * R > L)) { kern = 2; continue; }
-        SD_ARG((R + 2 * H + 1) * cw + per_row * R <= L, "row chunk does not fit LDS; lower ps.chunk_cols");
-        // (trimming R so that R * V is a multiple of the block size was measured: slower -- the per-tile
-        //  fixed cost outweighs the idle lanes of the last pass over the items)
-        if (have_reach && R >= 16 && r_param <= 0) R &= ~(int64_t)15;   // tiles are whole 16-row reach blocks
-        have_reach = have_reach && R % 16 == 0;
-        if (have_reach && h_auto) {
-            // the rows lost to the rounding are window capacity: a tile stages only what its reach words ask for, so a
-            // larger capacity costs nothing and keeps the rare far-reaching tile off the global-memory path
-            // (2 M x 500: 96-row tiles either way, capacity 16 -> 24, 1.686 -> 1.650 ms)
-            while (H < 32 && H + 1 <= h_cap && (R + 2 * (H + 1) + 1) * cw + per_row * R <= L) H += 1;
-        }
-        break;
-    }
-    const bool use_reach = have_reach;
-    if (R > n) { R = n; }
+    SdPsFacts f;
+    f.n = n; f.s = s;
+    f.aligned = ((uintptr_t)d_counts % 16 == 0) && (!d_ps || (uintptr_t)d_ps % 16 == 0) && (!d_excl || (uintptr_t)d_excl % 16 == 0);
+    f.want_excl = d_excl != nullptr; f.want_ps = d_ps != nullptr;
+    f.ctx_list = d_col != nullptr && d_col == ctx->d_col;
+    f.reach_rows_match = ctx->reach_n == n;
+    f.have_reach_words = ctx->d_reach != nullptr;
+    f.cluster_reach = ctx->cluster_reach;
+    SdPsPlan pl;                                           // tile shape, kernel generation, grid: psplan.cpp
+    SD_TRY(sd_ps_plan(ctx->params, f, &pl));
 
     PsArgs a;
     a.counts = d_counts; a.row_ptr = d_row_ptr; a.col = d_col; a.excl = d_excl; a.ps = d_ps;
     a.n = n; a.s = s;
-    a.tile_rows = (int)R;
-    a.halo = (int)H;
-    a.chunk_cols = cw;
-    a.col_cap = (int)(16 * R);
-    a.n_tiles = (int)sd_ceil_div(n, R);
-    const int n_chunks = (int)sd_ceil_div(s, cw);
-    a.n_chunks = n_chunks;
-    a.prio = ctx->param(SD_P_PS_PRIO) != 0;
-    // window loads that do not linger in the L2: -4 % at 1 M x 100 (0.179 -> 0.172 ms in one process); with column chunks
-    // the lines shared by two chunks and the halo rows want the L2 (+1.7 % at 2 M x 500): unchunked tables only
-    a.nt = ctx->param(SD_P_PS_NT_LOADS) != 0 && n_chunks == 1;
-    a.reach = use_reach ? ctx->d_reach : nullptr;
-    a.lv_shift = 0;                                        // column chunks: log2(row segments per 1 KiB piece)
-    for (int b = 0; b <= 6; ++b) if ((cw / 4) == (64 >> b)) a.lv_shift = b;
-    int gx = a.n_tiles;
-    a.tiles_per_xcd = 0;
-    const bool q3 = ctx->param(SD_P_PS_QUANTIZE3) != 0;
-    if (ctx->param(SD_P_PS_XCD_REMAP) && a.n_tiles >= 64) {
-        a.tiles_per_xcd = (int)sd_ceil_div(a.n_tiles, 8);
-        gx = a.tiles_per_xcd * 8;
-    }
-    const size_t lds_bytes = (size_t)lds;
-    SD_ARG((int64_t)gx * n_chunks < (int64_t)1 << 31, "grid too large");
-    dim3 grid((unsigned)((int64_t)gx * n_chunks));
-    if (kern == 0) return n_chunks == 1 && cw == s ? launch_ps_v3<false>(ctx, a, threads, lds_bytes, grid, d_excl != nullptr, d_ps != nullptr, q3)
-                                                   : launch_ps_v3<true>(ctx, a, threads, lds_bytes, grid, d_excl != nullptr, d_ps != nullptr, q3);
-    if (vec == 4) return launch_ps<4>(ctx, a, threads, lds_bytes, grid, d_excl != nullptr, d_ps != nullptr, q3, abl);
-    return launch_ps<1>(ctx, a, threads, lds_bytes, grid, d_excl != nullptr, d_ps != nullptr, q3, abl);
+    a.tile_rows = pl.tile_rows;
+    a.halo = pl.halo;
+    a.chunk_cols = pl.chunk_cols;
+    a.col_cap = pl.col_cap;
+    a.n_tiles = pl.n_tiles;
+    a.tiles_per_xcd = pl.tiles_per_xcd;
+    a.n_chunks = pl.n_chunks;
+    a.prio = pl.prio;
+    a.nt = pl.nt;
+    a.reach = pl.use_reach ? ctx->d_reach : nullptr;
+    a.lv_shift = pl.lv_shift;
+    const size_t lds_bytes = (size_t)pl.lds_bytes;
+    const dim3 grid((unsigned)pl.grid);
+    if (pl.kern == 0) return pl.n_chunks == 1 && pl.chunk_cols == s ? launch_ps_v3<false>(ctx, a, pl.threads, lds_bytes, grid, f.want_excl, f.want_ps, pl.q3)
+                                                                    : launch_ps_v3<true>(ctx, a, pl.threads, lds_bytes, grid, f.want_excl, f.want_ps, pl.q3);
+    if (pl.vec == 4) return launch_ps<4>(ctx, a, pl.threads, lds_bytes, grid, f.want_excl, f.want_ps, pl.q3, pl.ablate);
+    return launch_ps<1>(ctx, a, pl.threads, lds_bytes, grid, f.want_excl, f.want_ps, pl.q3, pl.ablate);
 }
 
 int sd_check_csr(const char* who, int64_t n_out, int64_t n_rows, const int64_t* row_ptr, const int32_t* col) {

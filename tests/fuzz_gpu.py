@@ -259,7 +259,7 @@ def gen_fisher(ctx, rng):
 
 
 def gen_bh(ctx, rng):
-    n = int(rng.choice([1, 2, 63, 64, 65, 255, 257, 1023, 1025, 4097, 20000, 70000]))
+    n = int(rng.choice([1, 2, 63, 64, 65, 255, 257, 1023, 1025, 2049, 3000, 4096, 4097, 20000, 70000]))
     cols = int(rng.choice([1, 2, 7, 8, 9, 40]))
     if n * cols > 1_500_000:
         cols = max(1, 1_500_000 // n)

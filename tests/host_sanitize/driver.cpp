@@ -3,14 +3,17 @@
 // and run by tests/test_host_sanitizers.py.  It pushes every host entry point through its threaded
 // path: table writer (3 modes) -> table reader round trip, column writer, cluster writer, junction
 // parser on the golden inputs (all file types) and the row lookup; then the argument checks of the pair
-// tests (csrc/paircheck.cpp) and of the column lists (csrc/colcheck.cpp) on both sides of their bounds, and the
-// column-group arithmetic of BH (csrc/bhplan.cpp).
+// tests (csrc/paircheck.cpp) and of the column lists (csrc/colcheck.cpp) on both sides of their bounds, the
+// column-group arithmetic of BH (csrc/bhplan.cpp), and the launch planners of PS, clustering and BH (csrc/psplan.cpp,
+// clusterplan.cpp, bhplan.cpp): every plan of the sweeps in plan_sweeps.h must keep inside the limits the kernels rest
+// on, and a table of plans is pinned field for field.
 // Any ASan / UBSan / TSan report makes the process exit non-zero.
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <atomic>
 #include <string>
 #include <thread>
@@ -20,12 +23,155 @@
 #include "colcheck.h"       //                      ... and of the column lists
 #include "bh.h"             //                      the column groups of BH
 #include "stagelayout.h"    //                      the result block of a host entry point
+#include "plan_sweeps.h"    // ps.h, cluster.h, bh.h: the launch planners and the inputs they are walked over
 
 static char g_err[1024];
 void sdice_set_error(const char* fmt, ...) {
     va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap);
 }
 #define CHECK(x) do { if (!(x)) { fprintf(stderr, "FAILED %s:%d: %s (%s)\n", __FILE__, __LINE__, #x, g_err); return 1; } } while (0)
+#define CHECK_V(x) do { if (!(x)) { fprintf(stderr, "FAILED %s:%d: %s (%s)\n", __FILE__, __LINE__, #x, g_err); ++bad; return; } } while (0)
+
+// ---- what the kernels rest on, per plan (0 = holds)
+static const int64_t LDS_MAX = 160 * 1024, GRID_MAX = (int64_t)1 << 31;
+static int64_t round256(int64_t b) { return b == 0 ? 256 : (b + 255) / 256 * 256; }      // as Arena::alloc rounds
+
+static int ps_plan_holds(const int64_t* k, const SdPsFacts& f, const SdPsPlan& p) {
+    const int64_t R = p.tile_rows, H = p.halo, cw = p.chunk_cols, T = p.threads, s = f.s;
+    CHECK(p.vec == 4 || p.vec == 1);
+    CHECK(T >= 64 && T <= PS_THREADS_MAX && T % 64 == 0);
+    CHECK(p.lds_bytes >= PS_LDS_MIN && p.lds_bytes <= PS_LDS_MAX && p.lds_bytes <= LDS_MAX);
+    CHECK(cw >= p.vec && cw <= s && cw % p.vec == 0 && (int64_t)p.n_chunks * cw >= s && ((int64_t)p.n_chunks - 1) * cw < s);
+    CHECK(H >= 0);
+    const int64_t window = (R + 2 * H + 1) * cw + PS_WORDS_PER_ROW * R;
+    if (p.kern == 0) {                  // the register-staged kernel
+        const int64_t LV = cw / 4;
+        CHECK(p.vec == 4 && f.aligned && s % 4 == 0 && p.ablate == 0);
+        CHECK(cw == s || (LV <= 64 && 64 % LV == 0));
+        CHECK(s * 2048 < (int64_t)1 << 30);
+        CHECK(R <= std::min<int64_t>(4 * T / LV, 2 * T - 1) && H <= T / LV);
+        CHECK(window <= p.lds_bytes / 4 - 64);
+        // tiles begin on whole 16-row reach blocks (a table shorter than a tile is ONE tile, cut to its n rows)
+        CHECK(!p.use_reach || R % 16 == 0 || (p.n_tiles == 1 && R == f.n));
+        if (p.n_chunks > 1 || cw != s) CHECK(LV == (64 >> p.lv_shift));
+    } else {                            // the first-generation kernel
+        CHECK(p.kern == 2 && !p.use_reach);
+        CHECK(R <= 2 * T);
+        CHECK(window <= p.lds_bytes / 4 - 16);
+    }
+    CHECK(!p.use_reach || (f.ctx_list && f.reach_rows_match && f.have_reach_words && k[SD_P_PS_USE_REACH] != 0));
+    CHECK(R >= 1 && R <= f.n && p.col_cap == 16 * R && (int64_t)p.n_tiles * R >= f.n && ((int64_t)p.n_tiles - 1) * R < f.n);
+    CHECK(p.grid >= 1 && p.grid < GRID_MAX);
+    if (p.tiles_per_xcd) CHECK((int64_t)p.tiles_per_xcd * 8 >= p.n_tiles && p.grid == (int64_t)p.tiles_per_xcd * 8 * p.n_chunks);
+    else CHECK(p.grid == (int64_t)p.n_tiles * p.n_chunks);
+    CHECK(!p.nt || p.n_chunks == 1);
+    return 0;
+}
+
+static int cluster_plan_holds(const SdClusterFacts& f, const SdClusterPlan& p) {
+    const int64_t n = f.n;
+    CHECK(p.B >= 1 && p.B <= MAX_BUCKETS);
+    CHECK((p.S == 0) == (p.B == 1));
+    CHECK(p.spb >= 2 && p.spb <= 64 && (p.S == 0 || p.S == p.B * p.spb));
+    if (p.S >= 1) CHECK(n / p.S >= 1);                    // the stride sample_pos divides by
+    CHECK(p.slot_cap >= 1 && p.slot_cap <= n && (p.B > 1 || p.slot_cap == n));
+    CHECK(p.lds_cap >= 2 && p.lds_cap <= RDX_CAP);
+    CHECK(p.scatter_lds == (int64_t)p.B * 16 && p.scatter_lds <= LDS_MAX);
+    CHECK((p.scatter_wg == 512 || p.scatter_wg == 1024) && p.scatter_grid * p.scatter_wg * SC_KPT >= n && p.scatter_grid < GRID_MAX);
+    CHECK(p.sort_grid == p.B);
+    CHECK((int64_t)p.rank_grid * 256 >= p.S && (int64_t)p.rank_grid * p.rank_grid < GRID_MAX);
+    CHECK((int64_t)p.n_tiles * NB_T >= n);
+    // the look-back's forward progress: never more workgroups than the device holds at once
+    CHECK(p.nb_grid >= 1 && p.nb_grid <= std::max<int64_t>(1, std::min<int64_t>(p.n_tiles, (int64_t)f.nb_per_cu * f.n_cu)));
+    // the zero region: tile_state (+ ticket) | cursor | rank | bmax64 | col_done, in that order, none overlapping
+    CHECK(((int64_t)p.n_tiles + 1) * 8 <= p.zk4_bytes && p.zk4_bytes % 8 == 0);
+    CHECK(p.cursor_off == p.zk4_bytes);
+    CHECK(p.rank_off >= p.cursor_off + (int64_t)p.B * 4);
+    CHECK(p.bmax64_off >= p.rank_off + (int64_t)p.S * 4);
+    CHECK(p.col_done_off >= p.bmax64_off + (n + 63) / 64 * 4);
+    CHECK(p.zero_bytes >= p.col_done_off + (int64_t)p.rank_grid * 4 && p.zero_bytes <= p.z_alloc_bytes);
+    CHECK(p.slots_bytes == (int64_t)p.B * p.slot_cap * 16 && p.row_bytes == n * 4 && p.spl_bytes >= (int64_t)p.B * 8);
+    CHECK(p.reserve_bytes >= round256(p.z_alloc_bytes) + round256(p.slots_bytes) + 3 * round256(p.row_bytes) + round256(p.spl_bytes));
+    return 0;
+}
+
+static int bhs_plan_holds(const SdBhsFacts& f, const SdBhsPlan& p) {
+    const int64_t m = f.m, segs = f.segs;
+    CHECK(m <= (int64_t)1 << POS_SHIFT);
+    CHECK(p.wg_threads == 256 || p.wg_threads == 512 || p.wg_threads == 1024);
+    CHECK(p.B >= 1 && p.B <= MAX_B);
+    CHECK(p.spb >= 1 && p.S == p.spb * p.B && p.S <= BHS_SAMPLE_MAX);
+    if (p.B > 1) CHECK(2 * (int64_t)p.S <= m);           // every sample stride of bhs_sample_kernel has a row
+    CHECK(p.S2 >= p.S && (p.S2 & (p.S2 - 1)) == 0 && (p.S2 == 1 || p.S2 / 2 < p.S) && (int64_t)p.S2 * 12 <= LDS_MAX);
+    CHECK(p.reg_cap >= 0 && p.reg_cap <= BHS_REG_MAX);
+    // one bucket: ranked in LDS from the p-values (the in-HBM path would write through the spill buffer B == 1 lacks)
+    if (p.B == 1) CHECK(m <= std::min<int64_t>(4 * p.wg_threads, BHS_REG_MAX));
+    if (p.B > 1) {
+        CHECK(p.lds_sample == (int64_t)p.S2 * 12 && p.lds_tile == (int64_t)p.B * 20 && p.lds_tile <= 64 * 1024);
+        CHECK((int64_t)p.tiles * TILE >= m && p.tile_blocks >= segs * p.tiles && p.tile_blocks < GRID_MAX);
+        if (p.fused_count) CHECK(p.lds_tc == TC_COLS * ((int64_t)(p.B - 1) * 12 + (int64_t)p.B * 4) && p.lds_tc <= BHS_FUSED_LDS_MAX);
+        CHECK(p.pos_cm_bytes == m * segs * 4 && p.spill_bytes == m * segs * 8);
+    } else {
+        CHECK(!p.fused_count && p.pos_cm_bytes == 0 && p.spill_bytes == 0);
+    }
+    CHECK(p.rows_per_block >= TC_ROWS);
+    CHECK((int64_t)p.strips_per_xcd * 8 * TC_COLS >= segs && p.tgrid >= 1 && p.tgrid < GRID_MAX);
+    CHECK(p.tgrid / ((int64_t)p.strips_per_xcd * 8) * p.rows_per_block >= m);
+    CHECK(p.bucket_blocks >= segs * p.B && p.bucket_blocks < GRID_MAX);
+    CHECK(p.big_blocks >= 1 && p.big_blocks <= std::max<int64_t>(1, segs * p.B) && p.zoom_blocks >= 1 && p.zoom_blocks < GRID_MAX);
+    CHECK(p.lds_bucket == (int64_t)sd_bhs_bucket_lds(p.wg_threads, 4) && p.lds_bucket <= LDS_MAX);
+    CHECK((p.big_wg == 512 || p.big_wg == 256) && p.lds_big == (int64_t)sd_bhs_bucket_lds(512, 4) && p.lds_zoom <= p.lds_big);
+    CHECK((p.fcols == 16 || p.fcols == 8) && (int64_t)p.row_tiles * (2048 / p.fcols) >= m && p.fin_blocks < GRID_MAX);
+    CHECK(p.fin_blocks >= (segs + p.fcols - 1) / p.fcols * p.row_tiles);
+    CHECK(p.p_cm_bytes == m * segs * 8 && p.keyS_bytes == m * segs * 8 && p.zeroed_bytes == 16);
+    CHECK(p.start_bytes == segs * (p.B + 1) * 4 && p.gcount_bytes == segs * p.B * 4 && p.big_list_bytes == segs * p.B * 8);
+    const int64_t pieces[] = {p.p_cm_bytes, p.keyS_bytes, p.spl_k_bytes, p.bmin_bytes, p.sfx_bytes, p.big_list_bytes, p.spl_i_bytes,
+                              p.gcount_bytes, p.cursor_bytes, p.start_bytes, p.zeroed_bytes};
+    int64_t sum = p.B > 1 ? round256(p.pos_cm_bytes) + round256(p.spill_bytes) : 0;
+    for (int64_t b : pieces) sum += round256(b);
+    CHECK((int64_t)sd_bh_cols_scratch(m, segs) >= sum);
+    return 0;
+}
+
+static int bhv_plan_holds(const int64_t* k, int64_t n, const SdBhvPlan& p) {
+    CHECK(sd_bh_vector_supported(n));
+    CHECK(p.B >= 2 && p.B <= BHV_T && p.B <= MAX_B);
+    CHECK(p.S == BHV_SPB * p.B && n / p.S >= 1 && n / p.S <= UINT32_MAX && n <= UINT32_MAX);     // bhv_sample_pos: 32 bits
+    CHECK(p.cap >= 64 && p.cap <= BHV_T * BHV_EPT);
+    CHECK(p.lds_bucket >= (int64_t)p.cap * 13 && p.lds_bucket % 16 == 0 && p.lds_bucket + (int64_t)BHV_BUCKET_STATIC_LDS <= LDS_MAX);
+    CHECK(p.lds_tile == (int64_t)p.B * 20 && p.lds_tile <= 64 * 1024);
+    CHECK((int64_t)p.rank_grid * 256 >= p.S && (int64_t)p.tiles * BHV_T * BHV_E >= n);
+    CHECK(p.m_eff_word % 2 == 0 && p.m_eff_word >= p.S + p.B + p.rank_grid && p.zwords >= p.m_eff_word + 6 && p.z_bytes == p.zwords * 4);
+    CHECK(p.keyS_bytes == (int64_t)p.B * p.cap * 8 && p.idxS_bytes == (int64_t)p.B * p.cap * 4 && p.qpart_bytes == n * 8 && p.bid_bytes == n * 2);
+    const int64_t pieces[] = {p.z_bytes, p.keyS_bytes, p.qpart_bytes, p.ovfK_bytes, p.spillK_bytes, p.bmin_bytes, p.idxS_bytes,
+                              p.ovfI_bytes, p.spillI_bytes, p.bid_bytes, p.ovfB_bytes, p.spl_k_bytes, p.spl_i_bytes};
+    int64_t sum = 0;
+    for (int64_t b : pieces) sum += round256(b);
+    CHECK((int64_t)sd_bhv_scratch(k, n) >= sum);
+    return 0;
+}
+
+// a plan as the list of its fields, in the order of the struct
+static Vals fields(const SdPsPlan& p) {
+    return {p.kern, p.vec, p.chunk_cols, p.tile_rows, p.halo, p.col_cap, p.n_tiles, p.n_chunks, p.lv_shift, p.tiles_per_xcd, p.use_reach, p.nt,
+            p.prio, p.q3, p.ablate, p.threads, p.lds_bytes, p.grid};
+}
+static Vals fields(const SdClusterPlan& p) {
+    return {p.B, p.spb, p.S, p.slot_cap, p.lds_cap, p.sample_sort, p.n_tiles, p.zk4_bytes, p.zero_bytes, p.cursor_off, p.rank_off, p.bmax64_off,
+            p.col_done_off, p.z_alloc_bytes, p.slots_bytes, p.row_bytes, p.spl_bytes, p.reserve_bytes, p.rank_grid, p.scatter_wg, p.scatter_grid,
+            p.scatter_lds, p.sort_grid, p.nb_grid};
+}
+static Vals fields(const SdBhsPlan& p) {
+    return {p.wg_threads, p.B, p.reg_cap, p.spb, p.S, p.S2, p.fused_count, p.rows_per_block, p.strips_per_xcd, p.tiles, p.big_wg, p.fcols, p.fnt,
+            p.row_tiles, p.tgrid, p.tile_blocks, p.bucket_blocks, p.big_blocks, p.zoom_blocks, p.fin_blocks, p.lds_sample, p.lds_tile, p.lds_tc,
+            p.lds_bucket, p.lds_big, p.lds_zoom, p.p_cm_bytes, p.keyS_bytes, p.spl_k_bytes, p.bmin_bytes, p.sfx_bytes, p.big_list_bytes,
+            p.spl_i_bytes, p.gcount_bytes, p.cursor_bytes, p.start_bytes, p.zeroed_bytes, p.pos_cm_bytes, p.spill_bytes};
+}
+static Vals fields(const SdBhvPlan& p) {
+    return {p.B, p.cap, p.S, p.rank_grid, p.tiles, p.lds_tile, p.lds_bucket, p.zwords, p.m_eff_word, p.z_bytes, p.keyS_bytes, p.qpart_bytes,
+            p.ovfK_bytes, p.spillK_bytes, p.bmin_bytes, p.idxS_bytes, p.ovfI_bytes, p.spillI_bytes, p.bid_bytes, p.ovfB_bytes, p.spl_k_bytes,
+            p.spl_i_bytes};
+}
 
 int main(int argc, char** argv) {
     if (argc < 3) { fprintf(stderr, "usage: driver <tmpdir> <junction file>:<type> ...\n"); return 2; }
@@ -291,6 +437,98 @@ int main(int argc, char** argv) {
             for (int i = 0; i < k; ++i) CHECK(at[i] % 256 == 0);
             for (int i = 1; i < k; ++i) CHECK(at[i] >= at[i - 1] + bytes[i - 1]);
             CHECK(total == at[k - 1] + (bytes[k - 1] + 255) / 256 * 256);
+        }
+    }
+    {   // the launch planners over the sweeps of plan_sweeps.h: every plan keeps inside what the kernels rest on
+        int64_t plans = 0, refused = 0, bad = 0;
+        sweep_ps(true, [&](const int64_t* k, const SdPsFacts& f) {
+            SdPsPlan p;
+            const int rc = sd_ps_plan(k, f, &p);
+            ++plans;
+            if (rc == SDICE_OK) bad += ps_plan_holds(k, f, p);
+            else { ++refused; bad += !(rc == SDICE_ERR_ARG && (strstr(g_err, "sdice_ps_dev: row chunk does not fit LDS") || strstr(g_err, "sdice_ps_dev: grid too large"))); }
+        });
+        CHECK(bad == 0 && refused > 0 && refused < plans / 2);
+        sweep_cluster(true, [&](const int64_t* k, const SdClusterFacts& f) {
+            SdClusterPlan p;
+            CHECK_V(!sd_cluster_takes_legacy(k, f.n));
+            sd_cluster_fast_plan(k, f, &p);
+            bad += cluster_plan_holds(f, p);
+        });
+        CHECK(bad == 0);
+        {
+            Knobs k;
+            CHECK(!sd_cluster_takes_legacy(k.v, FAST_MAX_N) && sd_cluster_takes_legacy(k.v, FAST_MAX_N + 1));
+            CHECK(sd_cluster_takes_legacy(Knobs().set(SD_P_CLUSTER_LEGACY, 1).v, 1000) && sd_cluster_takes_legacy(Knobs().set(SD_P_CLUSTER_GENERIC, 1).v, 1000));
+        }
+        plans = refused = 0;
+        sweep_bhs(true, [&](const int64_t* k, const SdBhsFacts& f) {
+            SdBhsPlan p;
+            CHECK_V(sd_bh_cols_supported(f.m, f.segs));
+            const int rc = sd_bhs_plan(k, f, &p);
+            ++plans;
+            if (rc == SDICE_OK) bad += bhs_plan_holds(f, p);
+            else { ++refused; bad += !(rc == SDICE_ERR_ARG && strstr(g_err, "sd_bh_cols_samplesort: bh: too many")); }
+        });
+        CHECK(bad == 0 && refused > 0 && refused < plans / 2);
+        CHECK(!sd_bh_cols_supported(((int64_t)1 << POS_SHIFT) + 1, 1) && !sd_bh_cols_supported(0, 1) && !sd_bh_cols_supported(1, 0));
+        sweep_bhv(true, [&](const int64_t* k, int64_t n) {
+            SdBhvPlan p;
+            sd_bhv_plan(k, n, &p);
+            bad += bhv_plan_holds(k, n, p);
+        });
+        CHECK(bad == 0);
+        CHECK(!sd_bh_vector_supported(BHV_MIN_N - 1) && !sd_bh_vector_supported(BHV_MAX_N + 1));
+    }
+    {   // pinned plans, whole structs (fields in the order of the struct): the default knobs at the shapes the benchmark and
+        // DESIGN.md name, and one plan per fallback of the PS kernel choice
+        auto psf = [](int64_t n, int32_t s, bool aligned, bool reach) {
+            SdPsFacts f;
+            f.n = n; f.s = s; f.aligned = aligned; f.want_excl = false; f.want_ps = true;
+            f.ctx_list = f.reach_rows_match = f.have_reach_words = reach; f.cluster_reach = reach ? 22 : 0;
+            return f;
+        };
+        struct { Knobs k; SdPsFacts f; Vals want; } ps_cases[] = {
+            // kern vec cw R H col_cap n_tiles n_chunks lv_shift tiles_per_xcd use_reach nt prio q3 ablate threads lds grid
+            {Knobs(), psf(2000000, 500, true, true), {0, 4, 128, 96, 24, 1536, 20834, 4, 1, 2605, 1, 0, 1, 0, 0, 1024, 81920, 83360}},     // 96-row tiles, capacity 24
+            {Knobs(), psf(2000000, 500, true, false), {0, 4, 128, 111, 16, 1776, 18019, 4, 1, 2253, 0, 0, 1, 0, 0, 1024, 81920, 72096}},
+            {Knobs(), psf(1000000, 100, true, false), {0, 4, 100, 146, 16, 2336, 6850, 1, 0, 857, 0, 1, 1, 0, 0, 1024, 81920, 6856}},
+            {Knobs(), psf(625000, 1000, true, false), {0, 4, 128, 111, 16, 1776, 5631, 8, 1, 704, 0, 0, 1, 0, 0, 1024, 81920, 45056}},
+            {Knobs(), psf(5000000, 1000, true, false), {0, 4, 128, 111, 16, 1776, 45046, 8, 1, 5631, 0, 0, 1, 0, 0, 1024, 81920, 360384}},
+            // the fallbacks to the first-generation kernel (kern 2)
+            {Knobs(), psf(1000000, 99, true, false), {2, 1, 99, 148, 16, 2368, 6757, 1, 0, 845, 0, 1, 1, 0, 0, 1024, 81920, 6760}},                  // s % 4 != 0
+            {Knobs(), psf(1000000, 100, false, false), {2, 1, 100, 146, 16, 2336, 6850, 1, 0, 857, 0, 1, 1, 0, 0, 1024, 81920, 6856}},               // a misaligned table
+            {Knobs().set(SD_P_PS_CHUNK_COLS, 96), psf(2000000, 500, true, false), {2, 4, 96, 153, 16, 2448, 13072, 6, 0, 1634, 0, 0, 1, 0, 0, 1024, 81920, 78432}},
+            {Knobs().set(SD_P_PS_THREADS, 64), psf(2000000, 500, true, false), {0, 4, 128, 8, 2, 128, 250000, 4, 1, 31250, 0, 0, 1, 0, 0, 64, 81920, 1000000}},      // (stays register-staged: 8-row tiles)
+            {Knobs(), psf(1000, 1 << 19, true, false), {2, 4, 128, 112, 16, 1792, 9, 4096, 1, 0, 0, 0, 1, 0, 0, 1024, 81920, 36864}},                  // s >= 2^19
+            {Knobs().set(SD_P_PS_GEN1, 1), psf(1000000, 100, true, true), {2, 4, 100, 146, 16, 2336, 6850, 1, 0, 857, 0, 1, 1, 0, 0, 1024, 81920, 6856}},
+        };
+        for (const auto& c : ps_cases) { SdPsPlan p; CHECK(sd_ps_plan(c.k.v, c.f, &p) == SDICE_OK && fields(p) == c.want); }
+        // B spb S slot_cap lds_cap sample_sort n_tiles zk4 zero cursor rank bmax64 col_done z_alloc slots row spl reserve rank_grid
+        // scatter_wg scatter_grid scatter_lds sort_grid nb_grid (4 neighbour workgroups per CU, 256 CUs)
+        struct { int64_t n; Vals want; } cl_cases[] = {
+            {1000000, {489, 12, 5868, 16360, 8192, 1, 1954, 15648, 103708, 15648, 17604, 41092, 103600, 104732, 128000640, 4000000, 3920, 140177708, 23, 1024, 245, 7824, 489, 1024}},
+            {2000000, {977, 12, 11724, 16384, 8192, 1, 3907, 31272, 207300, 31272, 35180, 82092, 207100, 208324, 256114688, 8000000, 7824, 280403156, 46, 1024, 489, 15632, 977, 1024}},
+        };
+        for (const auto& c : cl_cases) { SdClusterPlan p; sd_cluster_fast_plan(Knobs().v, SdClusterFacts{c.n, 4, 256}, &p); CHECK(fields(p) == c.want); }
+        struct { int64_t m, segs; Vals want; } bhs_cases[] = {      // 256 CUs
+            {25000, 19900, {256, 45, 2048, 8, 360, 512, 1, 2048, 156, 7, 512, 16, 0, 196, 16224, 139328, 895680, 1024, 1536, 244608, 6144, 900, 11328, 16736, 33120, 16736, 3980000000, 3980000000, 7164000, 7164000, 7164000, 7164000, 3582000, 3582000, 3582000, 3661600, 16, 1990000000, 3980000000}},
+            {200000, 200, {256, 356, 2048, 8, 2848, 4096, 0, 2048, 2, 49, 512, 16, 0, 1563, 1568, 9800, 71200, 1024, 1536, 25008, 49152, 7120, 0, 16736, 33120, 16736, 320000000, 320000000, 569600, 569600, 569600, 569600, 284800, 284800, 284800, 285600, 16, 160000000, 320000000}},
+        };
+        for (const auto& c : bhs_cases) { SdBhsPlan p; CHECK(sd_bhs_plan(Knobs().v, SdBhsFacts{c.m, c.segs, 256}, &p) == SDICE_OK && fields(p) == c.want); }
+        {
+            SdBhvPlan p;
+            sd_bhv_plan(Knobs().v, 1000000, &p);
+            CHECK(fields(p) == Vals({489, 5632, 7824, 31, 245, 9780, 73216, 8352, 8344, 33408, 22032384, 8000000, 8000000, 8000000, 3912, 11016192, 4000000, 4000000, 2000000, 2000000, 3912, 1956}) && sd_bhv_scratch(Knobs().v, 1000000) == 69153232);
+        }
+        {   // the one-bucket rule at its edges (bh.wg 1024: 2049 .. 4096 rows were one bucket before the rule)
+            SdBhsPlan p;
+            const Knobs wide_wg = Knobs().set(SD_P_BH_WG, 1024);
+            CHECK(sd_bhs_plan(wide_wg.v, SdBhsFacts{2048, 9, 256}, &p) == SDICE_OK && p.B == 1 && p.spill_bytes == 0);
+            for (int64_t m : {2049, 3000, 4096, 4097})
+                CHECK(sd_bhs_plan(wide_wg.v, SdBhsFacts{m, 9, 256}, &p) == SDICE_OK && p.B == 2 && p.spill_bytes == m * 9 * 8);
+            CHECK(sd_bhs_plan(Knobs().v, SdBhsFacts{1024, 9, 256}, &p) == SDICE_OK && p.B == 1);
+            CHECK(sd_bhs_plan(Knobs().v, SdBhsFacts{1025, 9, 256}, &p) == SDICE_OK && p.B == 2);
         }
     }
     printf("host sanitizer driver: ok\n");

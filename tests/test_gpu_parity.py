@@ -742,8 +742,8 @@ def test_bh_columns_batched(ctx, n, cols):
     np.testing.assert_allclose(d.to_host(), O.bh_columns(p), rtol=1e-14, atol=0)
 
 
-@pytest.mark.parametrize("n,cols", [(1, 3), (64, 5), (257, 40), (1024, 9), (1025, 9), (5000, 33), (25000, 12), (70001, 3),
-                                    (200000, 2)])
+@pytest.mark.parametrize("n,cols", [(1, 3), (64, 5), (257, 40), (1024, 9), (1025, 9), (2048, 3), (2049, 3), (3000, 9), (4096, 9),
+                                    (5000, 33), (25000, 12), (70001, 3), (200000, 2)])
 def test_bh_columns_samplesort_vs_generic(ctx, n, cols):
     """the sample-sort column path (bh_cols.hip) against the generic radix path, bit for bit, and the oracle:
     continuous values, heavy ties (p = 1, a few discrete levels as Fisher gives), one-value and two-value
