@@ -187,6 +187,27 @@ int sdice_kruskal_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, c
                       const int32_t* set_ptr, int32_t k, uint8_t* d_tested, double* d_p, double* d_h,
                       float* d_med, float* d_mean, float* d_delta);
 
+/* ---- compare_sample_sets -mx --posthoc: sdice_kruskal with Dunn's test for every pair of sets, from the same joint
+ *      ranking.  Inputs, row rules, checks and refusals are sdice_kruskal's, and tested, p, h, med, mean, delta are its
+ *      outputs bit for bit; in addition SDICE_ERR_ARG for k > SDICE_DUNN_MAX_SETS and for a NULL pair_z.
+ *  Pairs i < j in the order (0,1), (0,2), .., (k-2,k-1), m = k (k - 1) / 2 of them; pair_z / pair_p / pair_padj are float64
+ *  PAIR-major [m][n] (pair_p and pair_padj optional, NULL to skip).  With R_i-bar the mean joint mid-rank of set i, N the
+ *  kept values of the row and t the sizes of its tie groups:
+ *    z = (R_i-bar - R_j-bar) / sqrt(sigma2 (1 / n_i + 1 / n_j)),  sigma2 = (N^3 - N - sum(t^3 - t)) / (12 (N - 1)),
+ *  no continuity correction, z > 0 where set i ranks above set j, within 1 ulp of the correctly rounded value and +0.0
+ *  where the two mean ranks are equal; p = erfc(|z| / sqrt 2), two-sided, to the p bars of sdice_ranksum; padj: Holm's
+ *  step-down over the row's m p-values, padj_(r) = min(1, max_{t <= r} (m - t + 1) p_(t)) over the p's in ascending order,
+ *  equal p's get equal padj.  A row whose kept values are all equal is tested with z = 0, p = 1, padj = 1 in every pair; a
+ *  row that is not tested carries 0 in every pair slot. */
+#define SDICE_DUNN_MAX_SETS 11 /* 55 pairs: one pair per lane of a 64-lane wave (sdice_kruskal itself takes 64 sets) */
+int sdice_kruskal_dunn(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps, const int32_t* cols,
+                       const int32_t* set_ptr, int32_t k, uint8_t* tested, double* p, double* h,
+                       float* med, float* mean, float* delta, double* pair_z, double* pair_p, double* pair_padj);
+int sdice_kruskal_dunn_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, const int32_t* d_cols,
+                           const int32_t* set_ptr, int32_t k, uint8_t* d_tested, double* d_p, double* d_h,
+                           float* d_med, float* d_mean, float* d_delta, double* d_pair_z, double* d_pair_p,
+                           double* d_pair_padj);
+
 /* ---- compare_sample_sets -mx --trend: Jonckheere-Terpstra trend test across k ORDERED sets (set 0 < set 1 < ... as
  *      given) under the row rules, the inputs, the checks and the refusals of sdice_kruskal above.
  *  J = sum over the set pairs i < j of #{x in i, y in j: x < y} + #{x == y} / 2; E[J] = sum_{i<j} n_i n_j / 2; Var(J) is the

@@ -52,6 +52,8 @@ SIGNATURES = {
     "sdice_ranksum_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32] + [vp] * 8,
     "sdice_kruskal": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 6,
     "sdice_kruskal_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 6,
+    "sdice_kruskal_dunn": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 9,
+    "sdice_kruskal_dunn_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 9,
     "sdice_jonckheere": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 7,
     "sdice_jonckheere_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 7,
     "sdice_signedrank": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 8,

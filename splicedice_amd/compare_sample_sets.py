@@ -40,6 +40,12 @@ order statistics of the same differences (sdice_shift; R's wilcox.test(conf.int 
 test stays the rank-sum test (the exact one with `--exact`) and every other cell is what it is without the flag; the table
 gains `shift shift_lo shift_hi` before `p-value`.  Not with --paired, -mx, --trend, --ks or --strata.
 
+An eighth: `--posthoc` (with -mx) answers WHICH sets differ: Dunn's test for every pair of sets, taken from the joint ranking
+of the Kruskal-Wallis test in the same pass (sdice_kruskal_dunn).  Every -mx column stays where it is and what it is; between
+`H` and `p-value` the table gains, per pair of sets i < j in the order 1v2, 1v3, .., `z{i}v{j}` (> 0 where set i ranks above
+set j) and `padj{i}v{j}`, the pair's two-sided p-value after Holm's step-down correction over the pairs of the row.  At most
+11 sets; not with --trend.
+
 On the GPU: the per-row loop :216-232 (NaN drop, <3 skip, scipy ranksums, medians, means)
 -> sdice_ranksum; multipletests(..., "fdr_bh") :235 -> sdice_bh over the tested rows.
 The GTF annotation columns are host string work, as in the reference.
@@ -52,8 +58,8 @@ import numpy as np
 
 from . import _cli
 from ._cli import annotation_suffixes, read_annotation, read_ps_table, samples_from_manifest, table_header_names  # noqa: F401
-from .engine import (JONCKHEERE_FIELDS, KRUSKAL_FIELDS, KS_FIELDS, RANKSUM_EXACT_FIELDS, RANKSUM_FIELDS, SHIFT_FIELDS, Context,
-                     field_shapes)
+from .engine import (DUNN_MAX_SETS, JONCKHEERE_FIELDS, KRUSKAL_DUNN_FIELDS, KRUSKAL_FIELDS, KS_FIELDS, RANKSUM_EXACT_FIELDS,
+                     RANKSUM_FIELDS, SHIFT_FIELDS, Context, dunn_pairs, field_shapes)
 
 MAX_STRATA = 64                     # strata a call accepts (include/sdice.h)
 
@@ -174,6 +180,14 @@ def add_parser(parser):
                              "carries H.  The two-sided p-value is asymptotic only (normal approximation with the "
                              "tie-corrected variance, no exact form).  Not with --paired, --exact or --strata (not part of "
                              "the reference)")
+    parser.add_argument("--posthoc", action="store_true",
+                        help="With -mx: which sets differ -- Dunn's test for every pair of sets, from the joint ranking of "
+                             "the Kruskal-Wallis test.  Between H and p-value the table gains, per pair of sets i < j (1v2, "
+                             "1v3, ..), the columns z{i}v{j} (> 0 where set i ranks above set j, tie-corrected, no "
+                             "continuity correction) and padj{i}v{j}, the pair's two-sided p-value after Holm's step-down "
+                             "correction over the pairs of the row (not across rows: `corrected` stays the Benjamini-"
+                             "Hochberg value of the H test).  At most 11 sets.  Not with --trend (not part of the "
+                             "reference)")
     parser.add_argument("--ks", action="store_true",
                         help="The two-sample Kolmogorov-Smirnov test instead of the rank-sum test: it answers to any "
                              "difference between the two distributions (a junction switched on in part of a set, a "
@@ -245,7 +259,8 @@ class Test(typing.NamedTuple):
     that replaces the rank-sum pipeline (--exact and --paired are forms of it: compare()) says how: `fields`, the
     engine's table of its _dev call; sel -> `inputs`, the device inputs beside the table; (ctx, sel) -> `dev`, the launch
     on them; (ctx, matrix, sel) -> `host`, the host call; sel -> `k`, the number of sets of its per-set fields.  `stat`: the
-    (header cell, result key) of every column the row adds between delta and p-value."""
+    (header cell, result key) of every column the row adds between delta and p-value, or a function of the number of
+    sets that returns them; a result key is a field's name or (name, i) for row i of a per-set or per-pair field."""
     flag: str
     conflicts: tuple = ()
     needs: tuple = None
@@ -260,6 +275,10 @@ class Test(typing.NamedTuple):
     def refuse(self, why):
         _cli.refusal(f"compare_sample_sets {self.flag.split('/')[0]}")(why)
 
+    def columns(self, k):
+        """`stat` for k sets"""
+        return tuple(self.stat(k)) if callable(self.stat) else self.stat
+
 
 def _multi_rank(flag, carries):
     return (f"compare_sample_sets: {flag} is not available under the multi-rank launcher ({carries}); "
@@ -270,15 +289,24 @@ def _two_sets(sel):
     return dict(g1=(sel.g1_idx, np.int32), g2=(sel.g2_idx, np.int32))
 
 
-def _k_sets(test):
-    """the rest of a row over k >= 3 sets; test: the engine's name of the call"""
+def _k_sets(test, resident=None):
+    """the rest of a row over k >= 3 sets; test: the engine's name of the call, resident: that of its form on resident
+    data where it is not `<test>_dev`"""
     return dict(inputs=lambda sel: dict(cols=(sel.cols, np.int32)), k=lambda sel: len(sel.set_idx),
-                dev=lambda ctx, sel: lambda d, out: getattr(ctx, test + "_dev")(d["ps"], d["cols"], sel.set_ptr, out),
+                dev=lambda ctx, sel: lambda d, out: getattr(ctx, resident or test + "_dev")(d["ps"], d["cols"], sel.set_ptr, out),
                 host=lambda ctx, matrix, sel: getattr(ctx, test)(matrix, sel.set_idx))
 
 
+def _dunn_columns(k):
+    """H, then z and the Holm-adjusted p of every pair of sets in the engine's order, sets numbered from 1"""
+    yield "H", "h"
+    for q, (i, j) in enumerate(dunn_pairs(k)):
+        yield f"z{i + 1}v{j + 1}", ("pair_z", q)
+        yield f"padj{i + 1}v{j + 1}", ("pair_padj", q)
+
+
 PAIRED, EXACT, STRATA, TREND, KS, MX = "--paired", "--exact", "--strata", "--trend", "--ks", "-mx/--moreManifests"
-SHIFT, CONF = "--shift", "--conf"
+SHIFT, CONF, POSTHOC = "--shift", "--conf", "--posthoc"
 # in the order the refusals are made; the first selected row with a pipeline is the test that runs
 TESTS = (
     Test(CONF, needs=(SHIFT, "it is the level of the shift's confidence interval")),
@@ -314,6 +342,12 @@ TESTS = (
                                                                     sel.n_strata, out),
          host=lambda ctx, matrix, sel: ctx.ranksum_strata(matrix, sel.g1_idx, sel.g2_idx, sel.strat1, sel.strat2)),
     Test(PAIRED, conflicts=((MX, "the signed-rank test compares two matched sets"),)),
+    # (before -mx: the Kruskal-Wallis pipeline with the pair epilogue is the one that runs)
+    Test(POSTHOC, needs=(MX, "Dunn's test compares the pairs of three or more sets; two sets are the rank-sum test"),
+         conflicts=((TREND, "the trend test has one ordered alternative, not pairs"),),
+         multi_rank=_multi_rank(POSTHOC, "the packed all-gather carries the two-set fields only"),
+         fields=[f for f in KRUSKAL_DUNN_FIELDS if f[0] != "pair_p"],        # (the table prints z and padj: pair_p stays NULL)
+         stat=_dunn_columns, **_k_sets("kruskal_dunn", "kruskal_dunn_resident")),
     # k >= 3 sets: Kruskal-Wallis per junction (--trend above: Jonckheere-Terpstra over the sets in this order)
     Test(MX, multi_rank=_multi_rank(MX, "the packed all-gather carries the two-set fields only"),
          fields=KRUSKAL_FIELDS, stat=(("H", "h"),), **_k_sets("kruskal")),
@@ -333,7 +367,8 @@ def run_with(args, ctx=None):
     more = [samples_from_manifest(m) for m in (getattr(args, "moreManifests", None) or [])]
     on = {PAIRED: getattr(args, "paired", False), EXACT: getattr(args, "exact", False), STRATA: getattr(args, "strata", None),
           TREND: getattr(args, "trend", False), KS: getattr(args, "ks", False), MX: more,
-          SHIFT: getattr(args, "shift", False), CONF: getattr(args, "conf", None) is not None}
+          SHIFT: getattr(args, "shift", False), CONF: getattr(args, "conf", None) is not None,
+          POSTHOC: getattr(args, "posthoc", False)}
     chosen = [t for t in TESTS if on[t.flag]]
     sel = argparse.Namespace(exact=bool(on[EXACT]))
     conf = None
@@ -359,6 +394,9 @@ def run_with(args, ctx=None):
         sys.exit(1)
     if more:
         _cli.refuse_multi_rank(L, MULTI_RANK_REFUSAL)
+    if on[POSTHOC] and 2 + len(more) > DUNN_MAX_SETS:
+        BY_FLAG[POSTHOC].refuse(f"{2 + len(more)} sample sets, at most {DUNN_MAX_SETS} are supported (their "
+                                f"{(2 + len(more)) * (1 + len(more)) // 2} pairs do not fit the 64 lanes of a wave)")
     test = next((t for t in chosen if t.dev), None)
     with _stages.stage("parse"):
         rows, cols, matrix = read_ps_table(args.psiSPLICEDICE, as_table=True)
@@ -381,10 +419,11 @@ def run_with(args, ctx=None):
     # reference's print(*fields, sep="\t")); columns: event mean1..meank median1..mediank delta [statistics] p-value corrected
     k = 2 + len(more)
     means, medians = (r["mean"], r["med"]) if more else ((r["mean1"], r["mean2"]), (r["med1"], r["med2"]))
-    stat = [cell for t in chosen if t is test or not t.dev for cell in t.stat]
+    stat = [cell for t in chosen if t is test or not t.dev for cell in t.columns(k)]
     header = "\t".join(["event"] + [f"mean{i + 1}" for i in range(k)] + [f"median{i + 1}" for i in range(k)] + ["delta"] +
                        [cell for cell, _ in stat] + ["p-value", "corrected"])
-    columns = [*means, *medians, r["delta"]] + [r[key] for _, key in stat] + [r["p"], r["corrected"]]
+    columns = ([*means, *medians, r["delta"]] + [r[key] if isinstance(key, str) else r[key[0]][key[1]] for _, key in stat] +
+               [r["p"], r["corrected"]])
     _cli.write_event_table(args.outputFile, header, rows, keep, columns, ["repr"] * len(columns), args.annotation)
 
 

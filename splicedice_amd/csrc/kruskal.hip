@@ -25,6 +25,28 @@
 //       compaction + numpy pairwise sum), then two bitonic sorts of 64-bit keys in LDS: by (set, value) for the
 //       medians, by (value, set) for the ranks (run bounds by binary search, r2 summed per set with LDS atomics).
 //
+// Dunn's test (sdice_kruskal_dunn): both kernels carry a pair epilogue behind `template <bool DUNN>`; the DUNN = false
+// instantiations are sdice_kruskal's kernels as they were.  For every pair of sets i < j, in the order (0,1), (0,2), ..,
+// (k-2,k-1), pair index q of m = k (k - 1) / 2, from the row's integers alone (den = N^3 - N - sum(t^3 - t)):
+//   num = D_i n_j - D_j n_i                      (64-bit integer, |num| <= N^3 / 2 < 2^41: exact as a float64)
+//   z^2 = 3 (N - 1) num^2 / (n_i n_j (n_i + n_j) den)        (R_i-bar - R_j-bar over its standard error, no continuity term)
+//   z   = num / sqrt(den * (n_i n_j (n_i + n_j)) / (3 (N - 1)))
+// The exact floating-point form: den < 2^42, n_i n_j (n_i + n_j) < 2^41 and 3 (N - 1) are exact float64; their product is
+// an exact double-double (one fma), the quotient, the root and num / root run in double-double arithmetic (dd.h, each
+// good to about 2^-100) and z = hi + lo is the ONE rounding of the chain: rounding count 1, so z is within 1 ulp of the
+// correctly rounded value (equal to it but for a value within 2^-100 of a rounding boundary).  num == 0 gives z = +0.0 by
+// a test on the integer.  z > 0: set i ranks above set j.  Swapping or renumbering sets negates num and nothing else, so
+// z negates bit for bit.
+//   p    = erfc(|z| / sqrt 2): the library erfc of the rounded z, |z| * 0.7071.. rounded once before it
+//   padj = Holm's step-down inside the row: rank_q = #{t: p_t < p_q or (p_t == p_q and t < q)},
+//          padj_q = min(1, max over the pairs t with rank_t <= rank_q of (m - rank_t) p_t); (m - rank) p is one float64
+//          product, max and min are exact.  Equal p's get equal padj: of two equal p's the later rank has the smaller factor.
+// A row with den == 0 (every kept value equal): z = 0, p = 1, padj = 1 for every pair; an untested row: 0 in every slot.
+// One pair per lane of one wave (dunn_pairs): lane q fetches (D_i, n_i, D_j, n_j) from the lanes (grid kernel) or the LDS
+// slots (block kernel) of its two sets; the ranks by counting over m rounds of __shfl, then (m - rank) p goes to the lane of
+// its rank (ds_permute), a max scan runs up the lanes and every lane reads back its rank's -- no atomics, nothing depends
+// on an order of arrival.  m <= 64 lanes: k <= SDICE_DUNN_MAX_SETS = 11 (55 pairs) for this entry point.
+//
 // rowsum.h: the compaction, the pairwise sums, find_bin, the order bits of a float, np.median of sorted order bits, the
 // block's bitonic network, the launch sizes and the column check; and, shared with jonckheere.hip (K18), the limits, the
 // staging and first walk of the grid kernel (kw_stage_row, kw_walk_set), the block kernel up to its medians
@@ -33,6 +55,7 @@
 #include <math.h>
 #include <algorithm>
 #include "rowsum.h"
+#include "dd.h"
 
 namespace {
 
@@ -44,6 +67,79 @@ struct KwOut {
     float* mean;     // [k][n]
     float* delta;
 };
+
+// sdice_kruskal_dunn: KwOut and the pair outputs, pair-major [m][n]; pair_p and pair_padj may be NULL
+struct DunnOut : KwOut {
+    double* pair_z;
+    double* pair_p;
+    double* pair_padj;
+};
+template <bool DUNN> using KwOutOf = std::conditional_t<DUNN, DunnOut, KwOut>;
+constexpr int DUNN_MAX_SETS = SDICE_DUNN_MAX_SETS;
+static_assert(DUNN_MAX_SETS * (DUNN_MAX_SETS - 1) / 2 <= 64, "one pair per lane of a wave");
+
+// the sets (i, j), i < j, of pair q in the order (0,1), (0,2), .., (k-2,k-1); (0, 0) from q = k (k - 1) / 2 on
+__device__ __forceinline__ int2 dunn_pair_of(int q, int k) {
+    int i = 0;
+    while (i < k - 1 && q >= k - 1 - i) { q -= k - 1 - i; ++i; }
+    return i < k - 1 ? make_int2(i, i + 1 + q) : make_int2(0, 0);
+}
+
+// 0 in every pair slot of a row that is not tested; called by the lanes of one wave
+__device__ __forceinline__ void dunn_zero(const DunnOut& o, int lane, int m, int64_t n, int64_t row) {
+    if (lane < m) {
+        o.pair_z[(int64_t)lane * n + row] = 0.0;
+        if (o.pair_p) o.pair_p[(int64_t)lane * n + row] = 0.0;
+        if (o.pair_padj) o.pair_padj[(int64_t)lane * n + row] = 0.0;
+    }
+}
+
+// The pair epilogue of a tested row, one pair per lane of ONE whole wave (file comment): pr = dunn_pair_of(lane, k);
+// fetch(i, D, nv) hands every lane D_i and n_i of the set i it names (all 64 lanes call it together).
+template <class Fetch>
+__device__ __forceinline__ void dunn_pairs(const DunnOut& o, int lane, int m, int2 pr, long long N, long long den, int64_t n,
+                                           int64_t row, Fetch fetch) {
+    long long Di, Dj;
+    int ni, nj;
+    fetch(pr.x, Di, ni);
+    fetch(pr.y, Dj, nj);
+    double z = 0.0, p = 1.0;
+    const long long num = Di * nj - Dj * ni;
+    if (den != 0 && num != 0) {                      // (den: wave-uniform)
+        const double a = (double)den, b = (double)((long long)ni * nj * (ni + nj));
+        const double ab = a * b;
+        const DD v = dd_div_d(dd_fast2sum(ab, __builtin_fma(a, b, -ab)), (double)(3 * (N - 1)));
+        const DD zz = dd_div({(double)num, 0.0}, dd_sqrt(v));
+        z = zz.hi + zz.lo;
+        if (o.pair_p || o.pair_padj) p = erfc(fabs(z) * 0.70710678118654752440);       // (uniform)
+    }
+    const bool mine = lane < m;
+    if (mine) {
+        o.pair_z[(int64_t)lane * n + row] = z;
+        if (o.pair_p) o.pair_p[(int64_t)lane * n + row] = p;
+    }
+    if (!o.pair_padj) return;                        // (uniform)
+    int rank = 0;
+    for (int t = 0; t < m; ++t) {
+        const double pt = __shfl(p, t);
+        rank += (pt < p || (pt == p && t < lane)) ? 1 : 0;
+    }
+    // the ranks of the m pairs are a permutation of 0..m-1; with rank = lane on the idle lanes, of 0..63: every lane
+    // sends (m - rank) p to the lane of its rank, an inclusive max scan runs up the lanes, every lane reads its rank's
+    if (!mine) rank = lane;
+    const double mine_v = mine ? (double)(m - rank) * p : 0.0;
+    const long long bits = __double_as_longlong(mine_v);
+    const int lo = __builtin_amdgcn_ds_permute(rank << 2, (int)bits);
+    const int hi = __builtin_amdgcn_ds_permute(rank << 2, (int)(bits >> 32));
+    double run = __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
+#pragma unroll
+    for (int ofs = 1; ofs < 64; ofs <<= 1) {
+        const double up = __shfl_up(run, ofs);
+        if (lane >= ofs) run = fmax(run, up);
+    }
+    const double best = __shfl(run, rank);
+    if (mine) o.pair_padj[(int64_t)lane * n + row] = fmin(1.0, best);
+}
 
 // chi2.sf(h, df), integer df >= 1: the closed series (see the file comment)
 __device__ double kw_chi2_sf(double h, int df) {
@@ -98,9 +194,12 @@ __device__ __forceinline__ double kw_sorted_sum(double v, int lane) {
 
 // ------------------------------------------------------------------ grid path: one wave per row
 // LDS per wave (wstride bytes): Htot[1024] | Hset[1024] | leaf_sum[leaf_cap] | leaf_off[leaf_cap + 1] | keys[nsel] u16
-__global__ void __launch_bounds__(256) kruskal_grid_kernel(const float* __restrict__ ps, int64_t n, int s,
+// (DUNN: 3 waves per SIMD asked for -- with the epilogue the kernel came out at 178 VGPRs and 2 waves, which cost more than
+// the epilogue's instructions; it now takes 168 and 20 bytes of scratch per lane.  The bound leaves DUNN = false as it was.)
+template <bool DUNN>
+__global__ void __launch_bounds__(256, DUNN ? 3 : 1) kruskal_grid_kernel(const float* __restrict__ ps, int64_t n, int s,
                                                            const int32_t* __restrict__ cols, KwSets sets, int k, int ch,
-                                                           int wstride, int leaf_cap, KwOut o) {
+                                                           int wstride, int leaf_cap, KwOutOf<DUNN> o) {
     extern __shared__ __align__(16) unsigned char smemk[];
     __shared__ int sptr[KW_MAX_SETS + 1];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -112,6 +211,9 @@ __global__ void __launch_bounds__(256) kruskal_grid_kernel(const float* __restri
     __syncthreads();
     const int nsel = sptr[k];
     const int64_t n_chunks = (n + ch - 1) / ch;
+    [[maybe_unused]] const int m = k * (k - 1) / 2;
+    [[maybe_unused]] int2 pr = make_int2(0, 0);
+    if constexpr (DUNN) pr = dunn_pair_of(lane, k);
     for (int64_t c = (int64_t)blockIdx.x * wpb + wave; c < n_chunks; c += (int64_t)gridDim.x * wpb) {
       const int64_t row0 = c * ch;
       const int rows_here = (int)min((int64_t)ch, n - row0);
@@ -146,6 +248,7 @@ __global__ void __launch_bounds__(256) kruskal_grid_kernel(const float* __restri
                 o.med[(int64_t)lane * n + row] = 0.f;
                 o.mean[(int64_t)lane * n + row] = 0.f;
             }
+            if constexpr (DUNN) dunn_zero(o, lane, m, n, row);
             continue;
         }
         // ---- total histogram -> r2 per bin, N, sum(t^3 - t)
@@ -198,6 +301,14 @@ __global__ void __launch_bounds__(256) kruskal_grid_kernel(const float* __restri
             o.mean[(int64_t)lane * n + row] = my_mean;
         }
         if (lane == ri) { s_flag = 1; s_S = S; s_tie = tie; s_N = N; s_delta = dl; }
+        if constexpr (DUNN) {
+            const long long NN = N;
+            const long long myD = (long long)my_r2 - (long long)my_nv * (NN + 1);
+            dunn_pairs(o, lane, m, pr, NN, NN * NN * NN - NN - tie, n, row, [myD, my_nv](int i, long long& D, int& nv) {
+                D = __shfl(myD, i);
+                nv = __shfl(my_nv, i);
+            });
+        }
       }
       if (lane < rows_here) {
         const int64_t row = row0 + lane;
@@ -216,9 +327,10 @@ __global__ void __launch_bounds__(256) kruskal_grid_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------ general path: one workgroup per row
+template <bool DUNN>
 __global__ void __launch_bounds__(RB_THREADS) kruskal_block_kernel(const float* __restrict__ ps, int64_t n, int s,
                                                                    const int32_t* __restrict__ cols, KwSets sets, int k, int P,
-                                                                   int redo_only, KwOut o) {
+                                                                   int redo_only, KwOutOf<DUNN> o) {
     extern __shared__ __align__(16) unsigned char smemb[];
     unsigned long long* K = reinterpret_cast<unsigned long long*>(smemb);       // [P]; first the compaction buffer of the means
     __shared__ KwBlockLds sh;
@@ -226,6 +338,9 @@ __global__ void __launch_bounds__(RB_THREADS) kruskal_block_kernel(const float* 
     __shared__ unsigned long long tieS;
     __shared__ unsigned char flags[RB_THREADS];
     const int tid = threadIdx.x, lane = tid & 63;
+    [[maybe_unused]] const int m = k * (k - 1) / 2;
+    [[maybe_unused]] int2 pr = make_int2(0, 0);
+    if constexpr (DUNN) pr = dunn_pair_of(lane, k);
     for (int i = tid; i <= k; i += RB_THREADS) sh.sptr[i] = sets.ptr[i];
     __syncthreads();
     const int64_t n_chunks = (n + RB_THREADS - 1) / RB_THREADS;
@@ -251,6 +366,8 @@ __global__ void __launch_bounds__(RB_THREADS) kruskal_block_kernel(const float* 
                 if (o.h) o.h[row] = 0.0;
                 o.delta[row] = 0.f;
             }
+            if constexpr (DUNN)
+                if (tid < 64) dunn_zero(o, tid, m, n, row);
             __syncthreads();
             continue;
         }
@@ -310,6 +427,13 @@ __global__ void __launch_bounds__(RB_THREADS) kruskal_block_kernel(const float* 
                 if (o.h) o.h[row] = H;
                 o.delta[row] = dl;
             }
+            if constexpr (DUNN) {
+                const long long NN = N;
+                dunn_pairs(o, lane, m, pr, NN, NN * NN * NN - NN - (long long)tieS, n, row, [&](int i, long long& D, int& nv) {
+                    nv = sh.nvs[i];
+                    D = (long long)r2S[i] - (long long)nv * (NN + 1);
+                });
+            }
         }
         __syncthreads();
       }
@@ -332,8 +456,8 @@ extern "C" int sdice_kruskal_dev(sdice_ctx* ctx, int64_t n, int32_t s, const flo
     SD_TRY(ctx->arena.reset(ctx->stream));
     const KwPlan pl = kw_plan(set_ptr, k);
     KwOut o{d_tested, d_p, d_h, d_med, d_mean, d_delta};
-    return kw_launch_pair<kruskal_grid_kernel, kruskal_block_kernel>(ctx, "kruskal_grid_kernel", "kruskal_block_kernel", pl, d_ps,
-                                                                     n, s, d_cols, k, o);
+    return kw_launch_pair<kruskal_grid_kernel<false>, kruskal_block_kernel<false>>(ctx, "kruskal_grid_kernel", "kruskal_block_kernel",
+                                                                                   pl, d_ps, n, s, d_cols, k, o);
 }
 
 extern "C" int sdice_kruskal(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps, const int32_t* cols,
@@ -362,5 +486,59 @@ extern "C" int sdice_kruskal(sdice_ctx* ctx, int64_t n, int32_t s, const float* 
     st.result(&d.delta, delta, n);
     SD_TRY(st.alloc_results());
     SD_TRY(sdice_kruskal_dev(ctx, n, s, d_ps, dcols, set_ptr, k, d.tested, d.p, d.h, d.med, d.mean, d.delta));
+    return st.download_results();
+}
+
+extern "C" int sdice_kruskal_dunn_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, const int32_t* d_cols,
+                                      const int32_t* set_ptr, int32_t k, uint8_t* d_tested, double* d_p, double* d_h,
+                                      float* d_med, float* d_mean, float* d_delta, double* d_pair_z, double* d_pair_p,
+                                      double* d_pair_padj) {
+    SD_ARG(ctx, "ctx is NULL");
+    SD_ARG(n >= 0 && s >= 0, "negative size");
+    SD_TRY(kw_check_sets("sdice_kruskal_dunn", set_ptr, k, s));
+    SD_ARG(k <= DUNN_MAX_SETS, "the number of sets must be 2..11 (one pair of sets per lane of a wave)");
+    if (n == 0) return SDICE_OK;
+    SD_ARG(d_tested && d_p && d_med && d_mean && d_delta && d_pair_z, "NULL output");
+    SD_ARG(d_ps && d_cols, "NULL input");
+    SD_HIP(hipSetDevice(ctx->device));
+    SD_TRY(ctx->arena.reset(ctx->stream));
+    const KwPlan pl = kw_plan(set_ptr, k);
+    DunnOut o{{d_tested, d_p, d_h, d_med, d_mean, d_delta}, d_pair_z, d_pair_p, d_pair_padj};
+    return kw_launch_pair<kruskal_grid_kernel<true>, kruskal_block_kernel<true>>(ctx, "kruskal_dunn_grid_kernel",
+                                                                                 "kruskal_dunn_block_kernel", pl, d_ps, n, s, d_cols, k, o);
+}
+
+extern "C" int sdice_kruskal_dunn(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps, const int32_t* cols,
+                                  const int32_t* set_ptr, int32_t k, uint8_t* tested, double* p, double* h, float* med,
+                                  float* mean, float* delta, double* pair_z, double* pair_p, double* pair_padj) {
+    SD_ARG(ctx, "ctx is NULL");
+    SD_ARG(n >= 0 && s >= 0, "negative size");
+    SD_TRY(kw_check_sets("sdice_kruskal_dunn", set_ptr, k, s));
+    SD_ARG(k <= DUNN_MAX_SETS, "the number of sets must be 2..11 (one pair of sets per lane of a wave)");
+    SD_ARG(cols, "cols is NULL");
+    const int nsel = set_ptr[k];
+    SD_TRY(check_columns(__func__, {cols}, nsel, s, "column index out of range", "a column may belong to one set only"));
+    if (n == 0) return SDICE_OK;
+    SD_ARG(tested && p && med && mean && delta && pair_z, "NULL output");
+    SD_ARG(ps, "ps is NULL");
+    HostStaging st(ctx);
+    float* d_ps;
+    int32_t* dcols;
+    DunnOut d;
+    const int64_t m = (int64_t)k * (k - 1) / 2;
+    SD_TRY(st.upload(&d_ps, ps, n * s));
+    SD_TRY(st.upload(&dcols, cols, nsel));
+    st.result(&d.tested, tested, n);
+    st.result(&d.p, p, n);
+    st.result(&d.h, h, n);
+    st.result(&d.med, med, (int64_t)k * n);          // [k][n]
+    st.result(&d.mean, mean, (int64_t)k * n);
+    st.result(&d.delta, delta, n);
+    st.result(&d.pair_z, pair_z, m * n);             // [m][n]
+    st.result(&d.pair_p, pair_p, m * n);
+    st.result(&d.pair_padj, pair_padj, m * n);
+    SD_TRY(st.alloc_results());
+    SD_TRY(sdice_kruskal_dunn_dev(ctx, n, s, d_ps, dcols, set_ptr, k, d.tested, d.p, d.h, d.med, d.mean, d.delta, d.pair_z,
+                                  d.pair_p, d.pair_padj));
     return st.download_results();
 }

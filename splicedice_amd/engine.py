@@ -17,8 +17,11 @@ def _c(a, dtype):
 
 
 # The result fields of every per-row test, in the order of its C entry point (include/sdice.h).  A field is [n]; one marked
-# PER_SET is [k, n], one row per sample set.  GRAM_FIELDS: the four [m, m] matrices of sample_gram.
+# PER_SET is [k, n], one row per sample set, one marked PER_PAIR [k (k - 1) / 2, n], one row per pair of sets in the order
+# of dunn_pairs(k).  GRAM_FIELDS: the four [m, m] matrices of sample_gram.
 PER_SET = "per set"
+PER_PAIR = "per pair"
+DUNN_MAX_SETS = 11                  # sets a kruskal_dunn call accepts (include/sdice.h, SDICE_DUNN_MAX_SETS)
 RANKSUM_FIELDS = [("tested", np.uint8), ("p", np.float64), ("z", np.float64), ("med1", np.float32), ("med2", np.float32),
                   ("mean1", np.float32), ("mean2", np.float32), ("delta", np.float32)]       # (ranksum and signedrank)
 RANKSUM_EXACT_FIELDS = RANKSUM_FIELDS + [("exact", np.uint8)]                                # (the two --exact calls)
@@ -27,6 +30,8 @@ KS_FIELDS = [("tested", np.uint8), ("p", np.float64), ("d", np.float64), ("med1"
 SHIFT_FIELDS = [("tested", np.uint8), ("shift", np.float64), ("lo", np.float64), ("hi", np.float64), ("rank", np.int32)]
 KRUSKAL_FIELDS = [("tested", np.uint8), ("p", np.float64), ("h", np.float64), ("med", np.float32, PER_SET),
                   ("mean", np.float32, PER_SET), ("delta", np.float32)]
+KRUSKAL_DUNN_FIELDS = KRUSKAL_FIELDS + [("pair_z", np.float64, PER_PAIR), ("pair_p", np.float64, PER_PAIR),
+                                        ("pair_padj", np.float64, PER_PAIR)]
 JONCKHEERE_FIELDS = [("tested", np.uint8), ("p", np.float64), ("z", np.float64), ("j", np.float64),
                      ("med", np.float32, PER_SET), ("mean", np.float32, PER_SET), ("delta", np.float32)]
 SPEARMAN_FIELDS = [("tested", np.uint8), ("p", np.float64), ("rho", np.float64), ("n_kept", np.int32), ("med", np.float32),
@@ -35,8 +40,15 @@ GRAM_FIELDS = [("shared", np.int64), ("sum1", np.int64), ("sum2", np.int64), ("p
 
 
 def field_shapes(fields, shape, k=None):
-    """a field table -> name: (shape, dtype) in its order; `shape` for a plain field, (k, shape) for one marked PER_SET"""
-    return {f[0]: ((k, shape) if f[2:] else shape, f[1]) for f in fields}
+    """a field table -> name: (shape, dtype) in its order; `shape` for a plain field, (k, shape) for one marked PER_SET,
+    (k (k - 1) / 2, shape) for one marked PER_PAIR"""
+    lead = {PER_SET: lambda: k, PER_PAIR: lambda: k * (k - 1) // 2}
+    return {f[0]: ((lead[f[2]](), shape) if f[2:] else shape, f[1]) for f in fields}
+
+
+def dunn_pairs(k):
+    """the pairs of sets (i, j), i < j, in the order of the PER_PAIR outputs: (0, 1), (0, 2), .., (k - 2, k - 1)"""
+    return [(i, j) for i in range(k) for j in range(i + 1, k)]
 
 
 def _zeros(fields, shape, k=None):
@@ -445,6 +457,24 @@ class Context:
               "sdice_kruskal")
         return out
 
+    def kruskal_dunn(self, ps, sets, pair_p=True, pair_padj=True):
+        """kruskal() with Dunn's test for every pair of sets from the same joint ranking (include/sdice.h): kruskal()'s
+        outputs bit for bit, and pair_z, pair_p, pair_padj float64 [k (k - 1) / 2, n] in the order of dunn_pairs(k): z > 0
+        where set i ranks above set j, p two-sided, padj Holm's step-down inside the row.  At most DUNN_MAX_SETS sets.
+        pair_p / pair_padj False: the library is handed NULL for that output and the result lacks it."""
+        ps = _c(ps, np.float32)
+        n, s = ps.shape
+        cols, set_ptr = kruskal_sets(sets, s)
+        k = len(set_ptr) - 1
+        out = _zeros(KRUSKAL_DUNN_FIELDS, n, k)          # (the library refuses k > DUNN_MAX_SETS)
+        skipped = [name for name, on in (("pair_p", pair_p), ("pair_padj", pair_padj)) if not on]
+        check(self.lib.sdice_kruskal_dunn(self.h, n, s, _ptr(ps), _ptr(cols), _ptr(set_ptr), k,
+                                          *[None if name in skipped else _ptr(a) for name, a in out.items()]),
+              "sdice_kruskal_dunn")
+        for name in skipped:
+            del out[name]
+        return out
+
     def jonckheere(self, ps, sets):
         """Jonckheere-Terpstra trend test per row across the k ORDERED column sets (set 0 < set 1 < ...) under the row rules
         of kruskal(); un-compacted outputs: tested, p, z (> 0: the values rise along the order), j = J [n], med, mean
@@ -673,6 +703,17 @@ class Context:
         set_ptr = _c(set_ptr, np.int32)
         check(self.lib.sdice_kruskal_dev(self.h, n, s, d_ps.ptr, d_cols.ptr, _ptr(set_ptr), set_ptr.size - 1,
                                          *_dev_ptrs(KRUSKAL_FIELDS, out, ("h",))), "sdice_kruskal_dev")
+
+    def kruskal_dunn_resident(self, d_ps, d_cols, set_ptr, out):
+        """sdice_kruskal_dunn_dev: kruskal_dunn() on a resident table; d_cols and set_ptr as kruskal_dev takes them; out: the
+        device fields of KRUSKAL_DUNN_FIELDS, h, pair_p and pair_padj optional, the pair fields [k (k - 1) / 2, n].  (Not
+        named *_dev: tests/test_call_order_fixtures_cpu.py wants every method of that name in the catalogue of
+        tests/call_order_fixtures.py; this call has its own, tests/test_gpu_dunn_call_order.py.)"""
+        n, s = d_ps.shape
+        set_ptr = _c(set_ptr, np.int32)
+        check(self.lib.sdice_kruskal_dunn_dev(self.h, n, s, d_ps.ptr, d_cols.ptr, _ptr(set_ptr), set_ptr.size - 1,
+                                              *_dev_ptrs(KRUSKAL_DUNN_FIELDS, out, ("h", "pair_p", "pair_padj"))),
+              "sdice_kruskal_dunn_dev")
 
     def jonckheere_dev(self, d_ps, d_cols, set_ptr, out):
         """d_cols: the device copy of kruskal_sets()'s cols; set_ptr: its HOST offsets; out: device tested, p, z, (j), med and
