@@ -144,7 +144,8 @@ int sdice_mark_low_dev(sdice_ctx* ctx, int64_t n_elems, float* d_ps, const int64
                        int64_t n_low);
 
 /* the `_allPS.tsv` text round trip between quant and compare_sample_sets:
- * f'{x:.3f}' (SPLICEDICE.py:353) re-read as float32 (compareSampleSets.py:202) */
+ * f'{x:.3f}' (SPLICEDICE.py:353) re-read as float32 (compareSampleSets.py:202).  The device variant takes any
+ * 4-byte-aligned float pointer, e.g. a row-range view of a resident table with odd s. */
 int sdice_quantize3(sdice_ctx* ctx, int64_t n_elems, float* ps_inout);
 int sdice_quantize3_dev(sdice_ctx* ctx, int64_t n_elems, float* d_ps_inout);
 
@@ -719,6 +720,21 @@ int sdice_param_info(int32_t index, const char** name, int64_t* dflt);
  * Not listed, because their contents carry meaning: the clustering status block, the Fisher log-factorial table.
  * Any out pointer may be NULL.  SDICE_ERR_ARG past the last region.  Changes nothing. */
 int sdice_scratch_region(sdice_ctx* ctx, int32_t index, const char** name, void** dptr, int64_t* bytes);
+
+/* Test support.  The launch plan of this context's last sdice_ps_dev launch (sdice_ps goes through it), as int32
+ * fields in this fixed order:
+ *    0 kern           0 = register-staged kernel (ps_tile_v3_kernel), 2 = first-generation kernel (ps_tile_kernel)
+ *    1 vec            columns per item: 4 or 1
+ *    2 chunk_cols     columns per column chunk (= s: unchunked)
+ *    3 tile_rows      4 halo          5 n_tiles       6 n_chunks
+ *    7 lv_shift       6 - log2(16-byte vectors per chunk row) where that is a power of two up to 64, else 0
+ *    8 tiles_per_xcd  0 = no XCD remap
+ *    9 use_reach     10 nt           11 prio         12 q3          13 threads
+ * *n_fields (may be NULL) = 14; the first min(cap, 14) fields go to out (may be NULL when cap = 0).  A call that was
+ * refused or had nothing to do (n = 0, s = 0) leaves the plan of the launch before it.  SDICE_ERR_STATE before the
+ * first launch.  Changes nothing and launches nothing. */
+#define SDICE_PS_PLAN_FIELDS 14
+int sdice_ps_last_plan(sdice_ctx* ctx, int32_t* out, int32_t cap, int32_t* n_fields);
 
 #ifdef __cplusplus
 }

@@ -136,6 +136,7 @@ SIGNATURES = {
     "sdice_get_param": [ctxp, C.c_char_p, c_i64p],
     "sdice_param_info": [C.c_int32, C.POINTER(C.c_char_p), c_i64p],
     "sdice_scratch_region": [ctxp, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(vp), c_i64p],
+    "sdice_ps_last_plan": [ctxp, c_i32p, C.c_int32, c_i32p],
 }
 _RESTYPE = {"sdice_last_error": C.c_char_p}
 

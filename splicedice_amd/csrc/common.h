@@ -83,6 +83,10 @@ struct sdice_ctx {
     void* cluster_sb = nullptr;   // device status block of the fast clustering path (persistent, 768 B)
     bool cluster_pending = false; // an asynchronous sdice_cluster_dev has not been resolved yet
 
+    // test support (sdice_ps_last_plan): the plan of the last sdice_ps_dev launch, fields in the header's order
+    int32_t ps_plan[SDICE_PS_PLAN_FIELDS] = {0};
+    bool ps_planned = false;
+
     // log-factorial table of the Fisher kernel: lf[k] = lgamma(k+1)
     double* d_lf = nullptr;
     int64_t lf_n = 0;

@@ -696,10 +696,15 @@ __global__ void quantize3_kernel(float* __restrict__ x, int64_t n) {
     // f'{x:.3f}' -> float32: x*1000 is exact in float64 for a float32 x (24+10 bits), rint
     // is round-half-even like the decimal formatter, k/1000 -> f32 has no double-rounding
     // hazard (k/1000 is >= 2^-35 away from every f32 rounding boundary).
+    // Any 4-byte-aligned pointer: up to three leading scalars bring x to a 16-byte boundary, float4 body, scalar tail.
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t lead = min((int64_t)((16u - (unsigned)((uintptr_t)x & 15u)) & 15u) >> 2, n);
+    if (gid < lead) x[gid] = (float)(rint((double)x[gid] * 1000.0) / 1000.0);
+    x += lead; n -= lead;
     const int64_t n4 = n >> 2;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     float4* x4 = reinterpret_cast<float4*>(x);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    for (int64_t i = gid; i < n4; i += stride) {
         float4 v = x4[i];
         v.x = (float)(rint((double)v.x * 1000.0) / 1000.0);
         v.y = (float)(rint((double)v.y * 1000.0) / 1000.0);
@@ -783,6 +788,12 @@ extern "C" int sdice_ps_dev(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t*
     f.cluster_reach = ctx->cluster_reach;
     SdPsPlan pl;                                           // tile shape, kernel generation, grid: psplan.cpp
     SD_TRY(sd_ps_plan(ctx->params, f, &pl));
+    {
+        const int32_t fields[SDICE_PS_PLAN_FIELDS] = {pl.kern, pl.vec, pl.chunk_cols, pl.tile_rows, pl.halo, pl.n_tiles, pl.n_chunks,
+                                                      pl.lv_shift, pl.tiles_per_xcd, pl.use_reach, pl.nt, pl.prio, pl.q3, pl.threads};
+        std::copy(fields, fields + SDICE_PS_PLAN_FIELDS, ctx->ps_plan);     // (test support: sdice_ps_last_plan)
+        ctx->ps_planned = true;
+    }
 
     PsArgs a;
     a.counts = d_counts; a.row_ptr = d_row_ptr; a.col = d_col; a.excl = d_excl; a.ps = d_ps;
@@ -804,6 +815,19 @@ extern "C" int sdice_ps_dev(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t*
                                                                     : launch_ps_v3<true>(ctx, a, pl.threads, lds_bytes, grid, f.want_excl, f.want_ps, pl.q3);
     if (pl.vec == 4) return launch_ps<4>(ctx, a, pl.threads, lds_bytes, grid, f.want_excl, f.want_ps, pl.q3, pl.ablate);
     return launch_ps<1>(ctx, a, pl.threads, lds_bytes, grid, f.want_excl, f.want_ps, pl.q3, pl.ablate);
+}
+
+// Test support: which path the last launch took (the fields and their order: sdice.h).
+extern "C" int sdice_ps_last_plan(sdice_ctx* ctx, int32_t* out, int32_t cap, int32_t* n_fields) {
+    SD_ARG(ctx, "ctx is NULL");
+    SD_ARG(cap >= 0 && (out || cap == 0), "bad arguments");
+    if (!ctx->ps_planned) {
+        sdice_set_error("%s: no sdice_ps_dev launch yet", __func__);
+        return SDICE_ERR_STATE;
+    }
+    if (n_fields) *n_fields = SDICE_PS_PLAN_FIELDS;
+    for (int i = 0; i < cap && i < SDICE_PS_PLAN_FIELDS; ++i) out[i] = ctx->ps_plan[i];
+    return SDICE_OK;
 }
 
 int sd_check_csr(const char* who, int64_t n_out, int64_t n_rows, const int64_t* row_ptr, const int32_t* col) {
@@ -847,7 +871,7 @@ extern "C" int sdice_ps(sdice_ctx* ctx, int64_t n, int32_t s, const int32_t* cou
 extern "C" int sdice_quantize3_dev(sdice_ctx* ctx, int64_t n_elems, float* d_ps_inout) {
     SD_ARG(ctx && n_elems >= 0, "bad arguments");
     if (n_elems == 0) return SDICE_OK;
-    SD_ARG(d_ps_inout && (uintptr_t)d_ps_inout % 16 == 0, "pointer must be 16-byte aligned");
+    SD_ARG(d_ps_inout && (uintptr_t)d_ps_inout % 4 == 0, "pointer must be a float pointer (4-byte aligned)");
     int64_t blocks = sd_ceil_div(sd_ceil_div(n_elems, 4), 256);
     if (blocks > 2048) blocks = 2048;
     SD_LAUNCH(ctx, "quantize3_kernel", quantize3_kernel, dim3((unsigned)blocks), dim3(256), 0, d_ps_inout, n_elems);

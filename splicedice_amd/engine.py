@@ -632,6 +632,17 @@ class Context:
                                     d_excl.ptr if d_excl is not None else None,
                                     d_ps.ptr if d_ps is not None else None), "sdice_ps_dev")
 
+    PS_PLAN_FIELDS = ("kern", "vec", "chunk_cols", "tile_rows", "halo", "n_tiles", "n_chunks", "lv_shift", "tiles_per_xcd",
+                      "use_reach", "nt", "prio", "q3", "threads")
+
+    def ps_last_plan(self):
+        """Test support (sdice_ps_last_plan): the launch plan of the last ps_dev / ps launch -> {field: int}"""
+        out = (C.c_int32 * len(self.PS_PLAN_FIELDS))()
+        n = C.c_int32()
+        check(self.lib.sdice_ps_last_plan(self.h, out, len(out), C.byref(n)), "sdice_ps_last_plan")
+        assert n.value == len(self.PS_PLAN_FIELDS), n.value
+        return dict(zip(self.PS_PLAN_FIELDS, out))
+
     def quantize3_dev(self, d_ps):
         check(self.lib.sdice_quantize3_dev(self.h, int(np.prod(d_ps.shape)), d_ps.ptr), "sdice_quantize3_dev")
 

@@ -32,6 +32,8 @@ import numpy as np
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tests"))
+import ps_count_fixtures as PC  # noqa: E402   (the integer PS oracle)
 from oracle import oracle_np as O  # noqa: E402
 from splicedice_amd import synth  # noqa: E402
 from splicedice_amd.engine import Context  # noqa: E402
@@ -173,9 +175,14 @@ def gen_ps(ctx, rng):
     near = np.repeat(np.arange(n), deg) + rng.integers(-40, 41, size=int(row_ptr[-1]))
     far = rng.integers(0, n, size=near.size)
     col = np.clip(np.where(rng.random(near.size) < 0.85, near, far), 0, n - 1).astype(np.int32)
-    scale = int(rng.choice([1, 1, 1000, 200000]))
-    counts = (synth.make_counts(n, s, seed=int(rng.integers(1 << 30))).astype(np.int64) * scale).clip(0, (1 << 24) - 1).astype(np.int32)
-    want_ps, want_excl = O.calculate_psi_vectorised(counts, row_ptr, col)
+    # the whole int32 range (counts[n,s] int32, sdice.h): scales that leave every tile below 2^24, that straddle it, and
+    # that put most counts between 2^24 and 2^31 - 1; a few cells at the largest values
+    scale = int(rng.choice([1, 1, 1000, 200000, 1 << 20, 1 << 25]))
+    counts = (synth.make_counts(n, s, seed=int(rng.integers(1 << 30))).astype(np.int64) * scale).clip(0, (1 << 31) - 1)
+    hits = rng.random((n, s)) < 0.002
+    counts[hits] = rng.choice([(1 << 24) - 1, 1 << 24, (1 << 24) + 1, 1 << 30, (1 << 31) - 2, (1 << 31) - 1], size=int(hits.sum()))
+    counts = counts.astype(np.int32)
+    want_ps, want_excl = PC.oracle(counts, row_ptr, col)
     ps, excl = ctx.ps(counts, row_ptr, col, want_excl=True)
     if not np.array_equal(excl, want_excl):
         return f"ps excl differs (n={n} s={s} scale={scale})"

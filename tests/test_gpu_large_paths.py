@@ -347,6 +347,22 @@ def test_quantize3_grid_stride(ctx, n):
     d = ctx.to_device(vals)
     ctx.quantize3_dev(d)
     assert np.array_equal(d.to_host().view(np.uint32), want.view(np.uint32))
+    # views that start 1, 2 and 3 floats past a 16-byte boundary (the kernel peels scalars up to the next one), with
+    # every length modulo 4, below one grid pass and at this case's size, and views shorter than the peel: the view is
+    # quantised bit for bit, the cells on either side of it keep their values
+    raw, qraw = vals.view(np.uint32), want.view(np.uint32)
+    assert d.ptr % 16 == 0
+    for off in (1, 2, 3):
+        lengths = [1024 + r for r in range(4)] + [(n - 8) // 4 * 4 + r for r in range(4)] + [1, 2]
+        for m in lengths:
+            assert off + m < n
+            d.upload(vals)
+            ctx.quantize3_dev(d.offset(off, (m,)))
+            expect = raw.copy()
+            expect[off:off + m] = qraw[off:off + m]
+            got = d.to_host().view(np.uint32)
+            assert np.array_equal(got[:off], raw[:off]) and np.array_equal(got[off + m:], raw[off + m:]), (off, m)
+            assert np.array_equal(got, expect), (off, m)
     ctx.trim()
 
 
