@@ -723,7 +723,9 @@ int sdice_scratch_region(sdice_ctx* ctx, int32_t index, const char** name, void*
 
 /* Test support.  The launch plan of this context's last sdice_ps_dev launch (sdice_ps goes through it), as int32
  * fields in this fixed order:
- *    0 kern           0 = register-staged kernel (ps_tile_v3_kernel), 2 = first-generation kernel (ps_tile_kernel)
+ *    0 kern           0 = register-staged kernel (ps_tile_v3_kernel), 2 = first-generation kernel (ps_tile_kernel),
+ *                     3 = register-staged kernel with a 16-bit count window (ps_tile_w16_kernel; the context profile
+ *                     books its launches under "ps_tile_v3_kernel")
  *    1 vec            columns per item: 4 or 1
  *    2 chunk_cols     columns per column chunk (= s: unchunked)
  *    3 tile_rows      4 halo          5 n_tiles       6 n_chunks

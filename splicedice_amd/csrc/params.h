@@ -20,7 +20,8 @@
     X(PS_NT_LOADS, "ps.nt_loads", 1, "1 = non-temporal window loads when the table is not cut into column chunks")      \
     X(PS_GEN1, "ps.gen1", 0, "1 = the first-generation tile kernel (any row width / tile shape) instead of the register-staged one") \
     X(PS_USE_REACH, "ps.use_reach", 1, "1 = size a tile's halo from the per-block reach the fast clustering recorded")  \
-    /* clustering (cluster.hip, cluster_fast.hip) */                                                                    \
+    X(PS_W16, "ps.w16", 1, "column-chunked tables at the default tile knobs: 1 = the 16-bit-window kernel from one whole tile of rows on, 2 = at any row count (tests), 0 = the register-staged kernel") \
+    /* clustering (cluster.hip, cluster_fast.hip) */                                                                   \
     X(CLUSTER_GENERIC, "cluster.generic", 0, "1 = the radix-sort path with unpacked keys")                              \
     X(CLUSTER_LEGACY, "cluster.legacy", 0, "1 = the radix-sort path")                                                   \
     X(CLUSTER_LDS_CAP, "cluster.lds_cap", 8192, "largest bucket sorted in LDS, 2 .. 8192 (0 = 8192); small values force the in-HBM sort: tests") \
