@@ -167,6 +167,68 @@ __device__ __forceinline__ v2f key_over_1000(v2f k) {
     return __builtin_elementwise_fma(__builtin_elementwise_fma(-q, th, k), m, q);
 }
 
+// LDS offsets of a batch of GB neighbours of an item, k .. k + GB - 1 of the tile's offset stage; a short last batch is
+// padded with the all-zero row kept behind the window.  Unconditional reads (a short last batch runs into the next
+// row's entries or the words behind the stage -- always inside the LDS allocation) and a select: predicated reads
+// compile to an exec-mask round trip per element.  CHECK: false = one of them is outside the window (a tile whose
+// staged neighbours all lie inside it skips the test)
+template <bool CHECK, int GB>
+__device__ __forceinline__ bool ps_batch_offsets(const int* colL, int k, int k1, int zero_off, int (&off)[GB]) {
+    int raw[GB];
+#pragma unroll
+    for (int u = 0; u < GB; ++u) raw[u] = colL[k + u];
+#pragma unroll
+    for (int u = 0; u < GB; ++u) off[u] = (k + u < k1) ? raw[u] : zero_off;
+    if (CHECK) {
+        int mn = off[0];
+#pragma unroll
+        for (int u = 1; u < GB; ++u) mn = min(mn, off[u]);
+        if (mn < 0) return false;
+    }
+    return true;
+}
+
+// PS of the four columns of an item whose totals are below 2^24: two packed float32 quotients per instruction
+template <bool Q3>
+__device__ __forceinline__ void ps_quotients32(const unsigned (&in)[4], const unsigned (&acc)[4], float (&o)[4]) {
+#pragma unroll
+    for (int q = 0; q < 4; q += 2) {
+        const v2f num = {(float)in[q], (float)in[q + 1]};
+        const v2f den = {(float)(in[q] + acc[q]), (float)(in[q + 1] + acc[q + 1])};
+        v2f ps2 = div_small_ints2(num, den);
+        if (Q3) ps2 = key_over_1000(thousandths2(ps2));     // fused K4: float32(f'{ps:.3f}')
+        o[q] = ps2.x; o[q + 1] = ps2.y;
+    }
+}
+
+// quotients and stores of a four-column item with 32-bit sums.  Non-temporal store: the PS matrix is written once and
+// not re-read by this kernel, keeping it out of the L2 leaves the halo rows of the count matrix there (-2.5 % at 1M x 100)
+template <bool WEXCL, bool WPS, bool Q3>
+__device__ __forceinline__ void ps_finish32(const PsArgs& a, const unsigned (&in)[4], const unsigned (&acc)[4], int64_t out_index) {
+    if (WPS) {
+        float o[4];
+        ps_quotients32<Q3>(in, acc, o);
+        store_f4_nt(a.ps + out_index, o);
+    }
+    if (WEXCL) store_excl<4, unsigned>(a.excl + out_index, acc);
+}
+
+// quotients and stores of an item with 64-bit sums: float64 division, exact for any counts (ABL 4 = no PS store)
+template <int VEC, bool WEXCL, bool WPS, bool Q3, int ABL>
+__device__ __forceinline__ void ps_finish64(const PsArgs& a, const typename Vt<VEC>::I& own, const unsigned long long (&acc)[VEC],
+                                            int64_t out_index) {
+    if (WPS) {
+        float o[VEC];
+#pragma unroll
+        for (int q = 0; q < VEC; ++q) {
+            o[q] = ps_value64(comp(own, q), acc[q]);
+            if (Q3) o[q] = (float)(rint((double)o[q] * 1000.0) / 1000.0);
+        }
+        if (!(ABL & 4)) store_f<VEC>(a.ps + out_index, o);
+    }
+    if (WEXCL) store_excl<VEC, unsigned long long>(a.excl + out_index, acc);
+}
+
 // Fast item: every neighbour offset comes from the LDS stage and lies inside the staged window,
 // the tile's bound keeps incl + excl < 2^24 -> 32-bit sums, float32 quotient.  Returns false
 // (nothing stored) as soon as a neighbour is outside the window; the caller then runs ps_item_slow.
@@ -178,24 +240,11 @@ __device__ __forceinline__ bool ps_item_fast(const PsArgs& a, const char* tileB,
 #pragma unroll
     for (int q = 0; q < VEC; ++q) acc[q] = 0;
     // batches of GB neighbours: all offset reads, then all row reads, then the adds -- two LDS
-    // round trips per batch instead of two per neighbour; short batches are padded with the
-    // all-zero row kept behind the window
+    // round trips per batch instead of two per neighbour
     constexpr int GB = 4;
     for (int k = k0; k < k1; k += GB) {
-        // unconditional reads (a short last batch runs into the next row's entries or the words
-        // behind the stage -- always inside the LDS allocation) and a select: predicated reads
-        // compile to an exec-mask round trip per element
-        int raw[GB], off[GB];
-#pragma unroll
-        for (int u = 0; u < GB; ++u) raw[u] = colL[k + u];
-#pragma unroll
-        for (int u = 0; u < GB; ++u) off[u] = (k + u < k1) ? raw[u] : zero_off;
-        if (CHECK) {      // (a tile whose staged neighbours all lie inside the window skips this)
-            int mn = off[0];
-#pragma unroll
-            for (int u = 1; u < GB; ++u) mn = min(mn, off[u]);
-            if (mn < 0) return false;
-        }
+        int off[GB];
+        if (!ps_batch_offsets<CHECK, GB>(colL, k, k1, zero_off, off)) return false;
         VI v[GB];
 #pragma unroll
         for (int u = 0; u < GB; ++u) v[u] = *reinterpret_cast<const VI*>(tileB + off[u] + cbytes);
@@ -203,33 +252,29 @@ __device__ __forceinline__ bool ps_item_fast(const PsArgs& a, const char* tileB,
         for (int u = 0; u < GB; ++u) acc_add(acc, v[u]);
     }
     const VI own = *reinterpret_cast<const VI*>(tileB + own_off + cbytes);
-    if (WPS) {
-        float o[VEC];
-        if (VEC == 4) {
-            // two packed quotients per instruction
+    if constexpr (VEC == 4 && ABL == 0) {
+        const unsigned in[4] = {comp(own, 0), comp(own, 1), comp(own, 2), comp(own, 3)};
+        ps_finish32<WEXCL, WPS, Q3>(a, in, acc, out_index);
+    } else {
+        if (WPS) {
+            float o[VEC];
+            if constexpr (VEC == 4) {
+                const unsigned in[4] = {comp(own, 0), comp(own, 1), comp(own, 2), comp(own, 3)};
+                ps_quotients32<Q3>(in, acc, o);
+            } else {
 #pragma unroll
-            for (int q = 0; q < VEC; q += 2) {
-                const unsigned i0 = comp(own, q), i1 = comp(own, q + 1);
-                const v2f num = {(float)i0, (float)i1};
-                const v2f den = {(float)(i0 + acc[q]), (float)(i1 + acc[q + 1])};
-                v2f ps2 = div_small_ints2(num, den);
-                if (Q3) ps2 = key_over_1000(thousandths2(ps2));     // fused K4: float32(f'{ps:.3f}')
-                o[q] = ps2.x; o[q + 1] = ps2.y;
+                for (int q = 0; q < VEC; ++q) {
+                    const unsigned in = comp(own, q);
+                    o[q] = div_small_ints((float)in, (float)(in + acc[q]));
+                    if (Q3) o[q] = div_small_ints((float)rint((double)o[q] * 1000.0), 1000.0f);
+                }
             }
-        } else {
-#pragma unroll
-            for (int q = 0; q < VEC; ++q) {
-                const unsigned in = comp(own, q);
-                o[q] = div_small_ints((float)in, (float)(in + acc[q]));
-                if (Q3) o[q] = div_small_ints((float)rint((double)o[q] * 1000.0), 1000.0f);
-            }
+            // (ABL 8 = plain store where the production kernel stores non-temporally, ABL 4 = none)
+            if (VEC == 4 && !(ABL & 8)) { if (!(ABL & 4)) store_f4_nt(a.ps + out_index, reinterpret_cast<const float (&)[4]>(o)); }
+            else if (!(ABL & 4)) store_f<VEC>(a.ps + out_index, o);
         }
-        // non-temporal store: the PS matrix is written once and not re-read by this kernel, keeping it
-        // out of the L2 leaves the halo rows of the count matrix there (-2.5 % at 1M x 100; ABL 8 = plain store)
-        if (VEC == 4 && !(ABL & 8)) { if (!(ABL & 4)) store_f4_nt(a.ps + out_index, reinterpret_cast<const float (&)[4]>(o)); }
-        else if (!(ABL & 4)) store_f<VEC>(a.ps + out_index, o);
+        if (WEXCL) store_excl<VEC, unsigned>(a.excl + out_index, acc);
     }
-    if (WEXCL) store_excl<VEC, unsigned>(a.excl + out_index, acc);
     return true;
 }
 
@@ -259,16 +304,23 @@ __device__ __forceinline__ void ps_item_slow(const PsArgs& a, const char* tileB,
         acc_add(acc, v);
     }
     const VI own = *reinterpret_cast<const VI*>(tileB + own_off + cbytes);
-    if (WPS) {
-        float o[VEC];
-#pragma unroll
-        for (int q = 0; q < VEC; ++q) {
-            o[q] = ps_value64(comp(own, q), acc[q]);
-            if (Q3) o[q] = (float)(rint((double)o[q] * 1000.0) / 1000.0);
-        }
-        if (!(ABL & 4)) store_f<VEC>(a.ps + out_index, o);
+    ps_finish64<VEC, WEXCL, WPS, Q3, ABL>(a, own, acc, out_index);
+}
+
+// workgroup id -> (row tile, column chunk) of a column-chunked launch.  1-D grid: the column chunks of one row tile are
+// CONSECUTIVE work on ONE XCD, so the cache lines that two chunks share at a chunk boundary (rows are not 128 B aligned
+// when 4*s is not) meet in that XCD's L2 and leave it as full lines instead of two masked partial writes.  With
+// tiles_per_xcd (blocks are dealt round-robin over the 8 XCDs) each XCD gets a contiguous run of tiles, so that
+// neighbouring tiles (which share halo rows) share one L2; the caller drops a workgroup whose tile >= n_tiles
+__device__ __forceinline__ void ps_tile_of_block(const PsArgs& a, int bid, int& tile, int& chunk) {
+    tile = bid / a.n_chunks;
+    chunk = bid - tile * a.n_chunks;
+    if (a.tiles_per_xcd) {
+        const int k = bid >> 3;
+        const int t_local = k / a.n_chunks;
+        chunk = k - t_local * a.n_chunks;
+        tile = (bid & 7) * a.tiles_per_xcd + t_local;
     }
-    if (WEXCL) store_excl<VEC, unsigned long long>(a.excl + out_index, acc);
 }
 
 // Q3: store the '.3f' text round trip of PS (K4 fused into the store, param ps.quantize3).
@@ -284,19 +336,8 @@ __device__ __forceinline__ void ps_tile_work(const PsArgs& a, const int bid, con
     unsigned* red = reinterpret_cast<unsigned*>(rpL + a.tile_rows + 1);  // [0] max count, [1] max degree
 
     const int T = blockDim.x;
-    // 1-D grid: the column chunks of one row tile are CONSECUTIVE work on ONE XCD, so the cache
-    // lines that two chunks share at a chunk boundary (rows are not 128 B aligned when 4*s is
-    // not) meet in that XCD's L2 and leave it as full lines instead of two masked partial writes
-    int tile = bid / a.n_chunks;
-    int chunk = bid - tile * a.n_chunks;
-    if (a.tiles_per_xcd) {
-        // blocks are dealt round-robin over the 8 XCDs: give each XCD a contiguous run of
-        // tiles so that neighbouring tiles (which share halo rows) share one L2.
-        const int k = bid >> 3;
-        const int t_local = k / a.n_chunks;
-        chunk = k - t_local * a.n_chunks;
-        tile = (bid & 7) * a.tiles_per_xcd + t_local;
-    }
+    int tile, chunk;
+    ps_tile_of_block(a, bid, tile, chunk);
     if (tile >= a.n_tiles) return;
     const int c0 = chunk * a.chunk_cols;
     const int cwc = min(a.chunk_cols, a.s - c0);
@@ -442,6 +483,101 @@ __device__ __forceinline__ unsigned wave_max_dpp(unsigned x) {
 }
 
 // ---------------------------------------------------------------------------------------------------
+// What the register-staged tile kernels (ps_tile_v3_kernel, ps_tile_w16_kernel) share.  The ORDER stays with the kernels:
+// the window loads are issued as (1) own vectors, (2) ps_tile_scalars, (3) low halo run, (4) neighbour indices, (5) row
+// pointers, a compiler barrier, (6) last own vector and high halo run, and are consumed in that order further down (own
+// vectors, low run, indices and pointers, last own vector, high run), so that hipcc's counted vmcnt waits retire them one
+// by one.  (Steps (4)/(5) and their retirement stand in each kernel: as helpers they moved the VGPR count of either the
+// chunked ps_tile_v3_kernel or ps_tile_w16_kernel by two -- EXPERIMENTS A.23.)
+
+// Step (2), the uniform scalars of a tile: first / last row pointer and the halo rows the lists really reach (nlo below,
+// nhi above the tile; `halo` without reach words).  Scalar loads: they return on lgkmcnt, the vector queue stays untouched
+__device__ __forceinline__ void ps_tile_scalars(const PsArgs& a, int r0, int nr, long long& kbase, long long& kend, int& nlo, int& nhi) {
+    nlo = a.halo; nhi = a.halo;
+    const int64_t* pf = a.row_ptr + r0;
+    const int64_t* pl = pf + nr;
+    if (a.reach) {
+        const int b0 = r0 >> 4, bl = (r0 + nr - 1) >> 4;
+        const uint32_t* q0 = a.reach + b0;
+        const uint32_t* q1 = a.reach + min(b0 + 1, bl);
+        const uint32_t* q2 = a.reach + max(bl - 1, b0);
+        const uint32_t* q3 = a.reach + bl;
+        unsigned w0, w1, w2, w3;
+        asm volatile("s_nop 4\n\ts_load_dwordx2 %0, %6, 0x0\n\ts_load_dwordx2 %1, %7, 0x0\n\t"
+                     "s_load_dword %2, %8, 0x0\n\ts_load_dword %3, %9, 0x0\n\t"
+                     "s_load_dword %4, %10, 0x0\n\ts_load_dword %5, %11, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&s"(kbase), "=&s"(kend), "=&s"(w0), "=&s"(w1), "=&s"(w2), "=&s"(w3)
+                     : "s"(pf), "s"(pl), "s"(q0), "s"(q1), "s"(q2), "s"(q3) : "memory");
+        // block b reaches (w & 255) rows below row 16 b and (w >> 8 & 255) rows beyond row 16 b + 15
+        const int e = r0 + nr - 1;
+        int lo_need = (int)(w0 & 255u);
+        if (b0 < bl) lo_need = max(lo_need, (int)(w1 & 255u) - 16);
+        int hi_need = ((bl << 4) + 15 + (int)((w3 >> 8) & 255u)) - e;
+        if (b0 < bl) hi_need = max(hi_need, (bl << 4) - 1 + (int)((w2 >> 8) & 255u) - e);
+        nlo = min(max(lo_need, 0), a.halo);
+        nhi = min(max(hi_need, 0), a.halo);
+    } else {
+        asm volatile("s_nop 4\n\ts_load_dwordx2 %0, %2, 0x0\n\ts_load_dwordx2 %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&s"(kbase), "=&s"(kend) : "s"(pf), "s"(pl) : "memory");
+    }
+}
+
+// The tile's ONE workgroup barrier and what goes through it: every wave's largest count and whether one of its staged
+// neighbours is outside the window.  One word per wave (the count saturating at 2^24: beyond that no item is fast, bit
+// 31 = outside); sixteen words are read back, wave 0 clears the unused ones.  Returns the tile's largest count
+// (uniform), all_in: no item needs the per-batch window check (uniform)
+__device__ __forceinline__ unsigned ps_tile_sync_bound(unsigned cmax, bool outside, unsigned* red, int lane, int wave, int NW, bool& all_in) {
+    cmax = wave_max_dpp(cmax);
+    const unsigned long long any_out = __ballot(outside);
+    if (lane == 63) red[wave] = min(cmax, 0x1000000u) | (any_out != 0ull ? 0x80000000u : 0u);
+    if (wave == 0 && lane >= NW && lane < 16) red[lane] = 0u;
+    __syncthreads();
+    const uint4* r4 = reinterpret_cast<const uint4*>(red);
+    const uint4 x0 = r4[0], x1 = r4[1], x2 = r4[2], x3 = r4[3];
+    const unsigned tile_or = (x0.x | x0.y | x0.z | x0.w) | (x1.x | x1.y | x1.z | x1.w) | (x2.x | x2.y | x2.z | x2.w) | (x3.x | x3.y | x3.z | x3.w);
+    const unsigned k = 0x7fffffffu;
+    const unsigned m0 = max(max(x0.x & k, x0.y & k), max(x0.z & k, x0.w & k)), m1 = max(max(x1.x & k, x1.y & k), max(x1.z & k, x1.w & k));
+    const unsigned m2 = max(max(x2.x & k, x2.y & k), max(x2.z & k, x2.w & k)), m3 = max(max(x3.x & k, x3.y & k), max(x3.z & k, x3.w & k));
+    const unsigned tile_cmax = (unsigned)__builtin_amdgcn_readfirstlane((int)max(max(m0, m1), max(m2, m3)));
+    all_in = __builtin_amdgcn_readfirstlane((int)tile_or) >= 0;
+    return tile_cmax;
+}
+
+// The arguments with the outputs rebased to the tile's first element, and the walk of one thread over the tile's (row,
+// 4-column vector) items tid, tid + T, ...: the outputs are addressed as (tile base: scalar) + (32-bit element offset
+// inside the tile: the host keeps a tile below 2^30 elements), and the offsets of successive items follow by additions:
+// no 64-bit multiply-add, no 32-bit multiplications (quarter-rate) per item -- the kernel runs at 3/4 of the VALU issue rate
+template <bool WEXCL, bool WPS>
+__device__ __forceinline__ PsArgs ps_tile_outputs(const PsArgs& a, int r0, int c0) {
+    PsArgs b = a;
+    const int64_t tile_base = (int64_t)r0 * a.s + c0;
+    if (WPS) b.ps = a.ps + tile_base;
+    if (WEXCL) b.excl = a.excl + tile_base;
+    return b;
+}
+struct PsItemWalk {
+    int ri, c;              // row of the tile, vector of the chunk
+    unsigned o32;           // element offset of the item's outputs from the tile's first
+    int own_off;            // LDS byte offset of the item's own window row
+    int V, rowb, dr, dc, d_own;
+    unsigned d_o, wrap_o;
+    // V vectors per row of the chunk, window rows of rowb bytes
+    __device__ __forceinline__ PsItemWalk(const PsArgs& a, int tid, int T, int V_, int rowb_) : V(V_), rowb(rowb_) {
+        ri = tid / V; c = tid - ri * V;
+        dr = T / V; dc = T - dr * V;
+        o32 = (unsigned)ri * (unsigned)a.s + (unsigned)(c * 4);
+        d_o = (unsigned)dr * (unsigned)a.s + (unsigned)(dc * 4); wrap_o = (unsigned)a.s - (unsigned)(V * 4);
+        own_off = (a.halo + ri) * rowb;
+        d_own = dr * rowb;
+    }
+    __device__ __forceinline__ int64_t out_index() const { return (int64_t)(uint64_t)o32; }
+    __device__ __forceinline__ void next() {
+        c += dc; ri += dr; o32 += d_o; own_off += d_own;
+        if (c >= V) { c -= V; ri += 1; o32 += wrap_o; own_off += rowb; }
+    }
+};
+
+// ---------------------------------------------------------------------------------------------------
 // Register-staged tile kernel, second generation (VEC = 4 tables).  The window passes through the VGPRs
 // (which gives the tile's count bound for free; an LDS-DMA staging, global_load_lds_dwordx4, was built in round 3,
 // bit-exact and slower -- DESIGN appendix A.3):
@@ -469,18 +605,8 @@ __global__ void __launch_bounds__(1024, 8) ps_tile_v3_kernel(PsArgs a) {
 
     const int bid = blockIdx.x;
     int tile, chunk = 0;
-    if (!CHUNKED) {
-        tile = a.tiles_per_xcd ? (bid & 7) * a.tiles_per_xcd + (bid >> 3) : bid;
-    } else {
-        tile = bid / a.n_chunks;
-        chunk = bid - tile * a.n_chunks;
-        if (a.tiles_per_xcd) {
-            const int k = bid >> 3;
-            const int t_local = k / a.n_chunks;
-            chunk = k - t_local * a.n_chunks;
-            tile = (bid & 7) * a.tiles_per_xcd + t_local;
-        }
-    }
+    if (!CHUNKED) tile = a.tiles_per_xcd ? (bid & 7) * a.tiles_per_xcd + (bid >> 3) : bid;
+    else ps_tile_of_block(a, bid, tile, chunk);
     if (tile >= a.n_tiles) return;
     const int c0 = chunk * a.chunk_cols;
     const int cwc = CHUNKED ? min(a.chunk_cols, a.s - c0) : a.s;
@@ -527,37 +653,10 @@ __global__ void __launch_bounds__(1024, 8) ps_tile_v3_kernel(PsArgs a) {
     if (!CHUNKED && a.nt) { cv[0] = nt_load(g[0]); cv[1] = nt_load(g[1]); if (grp4) cv[2] = nt_load(g[2]); }
     else                  { cv[0] = *g[0]; cv[1] = *g[1]; if (grp4) cv[2] = *g[2]; }
 
-    // ---- (2) uniform scalars of the tile (scalar loads: they return on lgkmcnt, the vector queue stays untouched)
+    // ---- (2) uniform scalars of the tile, one scalar-load round trip
     long long kbase, kend;
-    int nlo = a.halo, nhi = a.halo;
-    {
-        const int64_t* pf = a.row_ptr + r0;
-        const int64_t* pl = pf + nr;
-        if (a.reach) {
-            const int b0 = r0 >> 4, bl = (r0 + nr - 1) >> 4;
-            const uint32_t* q0 = a.reach + b0;
-            const uint32_t* q1 = a.reach + min(b0 + 1, bl);
-            const uint32_t* q2 = a.reach + max(bl - 1, b0);
-            const uint32_t* q3 = a.reach + bl;
-            unsigned w0, w1, w2, w3;
-            asm volatile("s_nop 4\n\ts_load_dwordx2 %0, %6, 0x0\n\ts_load_dwordx2 %1, %7, 0x0\n\t"
-                         "s_load_dword %2, %8, 0x0\n\ts_load_dword %3, %9, 0x0\n\t"
-                         "s_load_dword %4, %10, 0x0\n\ts_load_dword %5, %11, 0x0\n\ts_waitcnt lgkmcnt(0)"
-                         : "=&s"(kbase), "=&s"(kend), "=&s"(w0), "=&s"(w1), "=&s"(w2), "=&s"(w3)
-                         : "s"(pf), "s"(pl), "s"(q0), "s"(q1), "s"(q2), "s"(q3) : "memory");
-            // block b reaches (w & 255) rows below row 16 b and (w >> 8 & 255) rows beyond row 16 b + 15
-            const int e = r0 + nr - 1;
-            int lo_need = (int)(w0 & 255u);
-            if (b0 < bl) lo_need = max(lo_need, (int)(w1 & 255u) - 16);
-            int hi_need = ((bl << 4) + 15 + (int)((w3 >> 8) & 255u)) - e;
-            if (b0 < bl) hi_need = max(hi_need, (bl << 4) - 1 + (int)((w2 >> 8) & 255u) - e);
-            nlo = min(max(lo_need, 0), a.halo);
-            nhi = min(max(hi_need, 0), a.halo);
-        } else {
-            asm volatile("s_nop 4\n\ts_load_dwordx2 %0, %2, 0x0\n\ts_load_dwordx2 %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
-                         : "=&s"(kbase), "=&s"(kend) : "s"(pf), "s"(pl) : "memory");
-        }
-    }
+    int nlo, nhi;
+    ps_tile_scalars(a, r0, nr, kbase, kend, nlo, nhi);
     const int nk = (int)(kend - kbase);
     const int slo = max(0, r0 - nlo);
     const int shi = min((int)a.n, r0 + nr + nhi);
@@ -630,64 +729,30 @@ __global__ void __launch_bounds__(1024, 8) ps_tile_v3_kernel(PsArgs a) {
     // loop, whose registers these were, needs none -- a wait there would be a wait for its own stores)
     cmax = max(cmax, hdst[1] >= 0 ? vmax(hv[1]) : 0u);
     if (hdst[1] >= 0) win4[hdst[1]] = hv[1];
-    {
-        cmax = wave_max_dpp(cmax);
-        const unsigned long long any_out = __ballot(outside);
-        // one word per wave: its largest count (saturating at 2^24: beyond that no item is fast), bit 31 = one of its
-        // staged neighbours is outside the window; sixteen words are read back, wave 0 clears the unused ones
-        if (lane == 63) red[wave] = min(cmax, 0x1000000u) | (any_out != 0ull ? 0x80000000u : 0u);
-        if (wave == 0 && lane >= NW && lane < 16) red[lane] = 0u;
-    }
-    __syncthreads();
-    unsigned tile_cmax, tile_or;
-    {
-        const uint4* r4 = reinterpret_cast<const uint4*>(red);
-        const uint4 x0 = r4[0], x1 = r4[1], x2 = r4[2], x3 = r4[3];
-        tile_or = (x0.x | x0.y | x0.z | x0.w) | (x1.x | x1.y | x1.z | x1.w) | (x2.x | x2.y | x2.z | x2.w) | (x3.x | x3.y | x3.z | x3.w);
-        const unsigned k = 0x7fffffffu;
-        const unsigned m0 = max(max(x0.x & k, x0.y & k), max(x0.z & k, x0.w & k)), m1 = max(max(x1.x & k, x1.y & k), max(x1.z & k, x1.w & k));
-        const unsigned m2 = max(max(x2.x & k, x2.y & k), max(x2.z & k, x2.w & k)), m3 = max(max(x3.x & k, x3.y & k), max(x3.z & k, x3.w & k));
-        tile_cmax = max(max(m0, m1), max(m2, m3));
-    }
-    tile_cmax = (unsigned)__builtin_amdgcn_readfirstlane((int)tile_cmax);
+    bool all_in;                                                                         // block-uniform, as is tile_cmax
+    const unsigned tile_cmax = ps_tile_sync_bound(cmax, outside, red, lane, wave, NW, all_in);
     // an item is fast (32-bit sums, float32 quotient) iff (degree + 1) * (largest count of the tile) < 2^24
     const bool fast_tile = tile_cmax <= 0xFFFFFFu && col_in_lds;                         // block-uniform
-    const bool all_in = __builtin_amdgcn_readfirstlane((int)tile_or) >= 0;               // block-uniform: no per-batch window check needed
 
     // ---- per (row, vector) item: gather neighbours from LDS, divide, store
     {
         const char* tileB = reinterpret_cast<const char*>(tileL);
         const int items = nr * V;
-        int ri = tid / V, c = tid - ri * V;
-        const int dr = T / V, dc = T - dr * V;
-        // the outputs are addressed as (tile base: scalar) + (32-bit element offset inside the tile: the host keeps a tile
-        // below 2^30 elements), and the offsets of successive items follow by additions: no 64-bit multiply-add, no
-        // 32-bit multiplications (quarter-rate) per item -- the kernel runs at 3/4 of the VALU issue rate
-        PsArgs b = a;
-        {
-            const int64_t tile_base = (int64_t)r0 * a.s + c0;
-            if (WPS) b.ps = a.ps + tile_base;
-            if (WEXCL) b.excl = a.excl + tile_base;
-        }
-        unsigned o32 = (unsigned)ri * (unsigned)a.s + (unsigned)(c * VEC);
-        const unsigned d_o = (unsigned)dr * (unsigned)a.s + (unsigned)(dc * VEC), wrap_o = (unsigned)a.s - (unsigned)(V * VEC);
-        int own_off = (a.halo + ri) * rowb;
-        const int d_own = dr * rowb;
+        const PsArgs b = ps_tile_outputs<WEXCL, WPS>(a, r0, c0);
+        PsItemWalk w(a, tid, T, V, rowb);
         // (degree + 1) * (largest count of the tile) < 2^24  <=>  degree + 1 <= deg_lim
         const unsigned deg_lim = tile_cmax ? 0xFFFFFFu / tile_cmax : 0xFFFFFFFFu;
-        for (int it = tid; it < items; it += T) {
-            const int k0 = rpL[ri], k1 = rpL[ri + 1];
-            const int64_t o = (int64_t)(uint64_t)o32;
+        for (int it = tid; it < items; it += T, w.next()) {
+            const int k0 = rpL[w.ri], k1 = rpL[w.ri + 1];
+            const int64_t o = w.out_index();
             bool done = false;
             const unsigned deg = (unsigned)(k1 - k0);
             if (fast_tile && deg < 254u && deg + 1u <= deg_lim)
-                done = all_in ? ps_item_fast<VEC, WEXCL, WPS, false, Q3, 0>(b, tileB, colL, k0, k1, c * VEC * 4, own_off, o, zero_off)
-                              : ps_item_fast<VEC, WEXCL, WPS, true, Q3, 0>(b, tileB, colL, k0, k1, c * VEC * 4, own_off, o, zero_off);
+                done = all_in ? ps_item_fast<VEC, WEXCL, WPS, false, Q3, 0>(b, tileB, colL, k0, k1, w.c * VEC * 4, w.own_off, o, zero_off)
+                              : ps_item_fast<VEC, WEXCL, WPS, true, Q3, 0>(b, tileB, colL, k0, k1, w.c * VEC * 4, w.own_off, o, zero_off);
             if (!done)
-                ps_item_slow<VEC, WEXCL, WPS, Q3, 0>(b, tileB, colL, col_in_lds, kbase, k0, k1, slo, wrows, ldw, c0, c * VEC,
-                                                     own_off, o, wbase);
-            c += dc; ri += dr; o32 += d_o; own_off += d_own;
-            if (c >= V) { c -= V; ri += 1; o32 += wrap_o; own_off += rowb; }
+                ps_item_slow<VEC, WEXCL, WPS, Q3, 0>(b, tileB, colL, col_in_lds, kbase, k0, k1, slo, wrows, ldw, c0, w.c * VEC,
+                                                     w.own_off, o, wbase);
         }
     }
 }
@@ -696,8 +761,10 @@ __global__ void __launch_bounds__(1024, 8) ps_tile_v3_kernel(PsArgs a) {
 // Register-staged tile kernel with a 16-bit count window (column-chunked VEC = 4 tables, geometry: psplan.cpp).  The
 // window stands in LDS as saturated 16-bit words, min(count, 0xFFFF): a window row is chunk_cols x 2 bytes, a neighbour
 // is one 8-byte LDS read, and the same LDS holds twice the cells -- SIX items per thread share the per-tile fixed cost
-// that three share in ps_tile_v3_kernel.  Load order, reach-sized halo runs, the single barrier, the XCD remap and the
-// non-temporal stores are those of ps_tile_v3_kernel; the tile's count bound is taken from the 32-bit registers before
+// that three share in ps_tile_v3_kernel.  The two kernels share their steps through the helpers above: the XCD remap
+// (ps_tile_of_block), the reach-sized halo runs (ps_tile_scalars), the single
+// barrier (ps_tile_sync_bound), the item walk (PsItemWalk) and the batches and non-temporal stores of a 32-bit item
+// (ps_batch_offsets, ps_finish32), in one load order; the tile's count bound is taken from the 32-bit registers before
 // they are packed.  The row segments of a chunk divide the workgroup (T % LV == 0), so a thread keeps ONE column and
 // its vectors lie T / LV rows apart: the loads are addressed as (tile base: scalar) + (32-bit byte offset), offsets that
 // follow each other by additions.
@@ -721,41 +788,6 @@ __device__ __forceinline__ unsigned pk_max_u16(unsigned a, unsigned b) {
     return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(us2, a), __builtin_bit_cast(us2, b)));
 }
 
-// quotients and stores of a 32-bit item: the tail of ps_item_fast
-template <bool WEXCL, bool WPS, bool Q3>
-__device__ __forceinline__ void ps16_finish(const PsArgs& a, const unsigned (&in)[4], const unsigned (&acc)[4], int64_t out_index) {
-    if (WPS) {
-        float o[4];
-#pragma unroll
-        for (int q = 0; q < 4; q += 2) {
-            const v2f num = {(float)in[q], (float)in[q + 1]};
-            const v2f den = {(float)(in[q] + acc[q]), (float)(in[q + 1] + acc[q + 1])};
-            v2f ps2 = div_small_ints2(num, den);
-            if (Q3) ps2 = key_over_1000(thousandths2(ps2));
-            o[q] = ps2.x; o[q + 1] = ps2.y;
-        }
-        store_f4_nt(a.ps + out_index, o);
-    }
-    if (WEXCL) store_excl<4, unsigned>(a.excl + out_index, acc);
-}
-
-// offsets of a batch of GB neighbours (ps_item_fast): false = one of them is outside the window
-template <bool CHECK, int GB>
-__device__ __forceinline__ bool ps16_batch(const int* colL, int k, int k1, int zero_off, int (&off)[GB]) {
-    int raw[GB];
-#pragma unroll
-    for (int u = 0; u < GB; ++u) raw[u] = colL[k + u];
-#pragma unroll
-    for (int u = 0; u < GB; ++u) off[u] = (k + u < k1) ? raw[u] : zero_off;
-    if (CHECK) {
-        int mn = off[0];
-#pragma unroll
-        for (int u = 1; u < GB; ++u) mn = min(mn, off[u]);
-        if (mn < 0) return false;
-    }
-    return true;
-}
-
 // tier 1: packed sums
 template <bool WEXCL, bool WPS, bool CHECK, bool Q3>
 __device__ __forceinline__ bool ps16_item_packed(const PsArgs& a, const char* tileB, const int* colL, int k0, int k1,
@@ -764,7 +796,7 @@ __device__ __forceinline__ bool ps16_item_packed(const PsArgs& a, const char* ti
     unsigned s01 = 0, s23 = 0;
     for (int k = k0; k < k1; k += GB) {
         int off[GB];
-        if (!ps16_batch<CHECK, GB>(colL, k, k1, zero_off, off)) return false;
+        if (!ps_batch_offsets<CHECK, GB>(colL, k, k1, zero_off, off)) return false;
         uint2 v[GB];
 #pragma unroll
         for (int u = 0; u < GB; ++u) v[u] = *reinterpret_cast<const uint2*>(tileB + off[u] + cbytes);
@@ -774,7 +806,7 @@ __device__ __forceinline__ bool ps16_item_packed(const PsArgs& a, const char* ti
     const uint2 own = *reinterpret_cast<const uint2*>(tileB + own_off + cbytes);
     const unsigned in[4] = {own.x & 0xFFFFu, own.x >> 16, own.y & 0xFFFFu, own.y >> 16};
     const unsigned acc[4] = {s01 & 0xFFFFu, s01 >> 16, s23 & 0xFFFFu, s23 >> 16};
-    ps16_finish<WEXCL, WPS, Q3>(a, in, acc, out_index);
+    ps_finish32<WEXCL, WPS, Q3>(a, in, acc, out_index);
     return true;
 }
 
@@ -788,7 +820,7 @@ __device__ __forceinline__ bool ps16_item_wide(const PsArgs& a, const char* tile
     unsigned m01 = own.x, m23 = own.y;
     for (int k = k0; k < k1; k += GB) {
         int off[GB];
-        if (!ps16_batch<CHECK, GB>(colL, k, k1, zero_off, off)) return false;
+        if (!ps_batch_offsets<CHECK, GB>(colL, k, k1, zero_off, off)) return false;
         uint2 v[GB];
 #pragma unroll
         for (int u = 0; u < GB; ++u) v[u] = *reinterpret_cast<const uint2*>(tileB + off[u] + cbytes);
@@ -803,11 +835,11 @@ __device__ __forceinline__ bool ps16_item_wide(const PsArgs& a, const char* tile
         if ((m & 0xFFFFu) == 0xFFFFu || m >= 0xFFFF0000u) return false;
     }
     const unsigned in[4] = {own.x & 0xFFFFu, own.x >> 16, own.y & 0xFFFFu, own.y >> 16};
-    ps16_finish<WEXCL, WPS, Q3>(a, in, acc, out_index);
+    ps_finish32<WEXCL, WPS, Q3>(a, in, acc, out_index);
     return true;
 }
 
-// tier 3: every count from global memory, 64-bit sums, float64 division (the tail of ps_item_slow)
+// tier 3: every count from global memory, 64-bit sums, float64 division
 template <bool WEXCL, bool WPS, bool Q3>
 __device__ __forceinline__ void ps16_item_global(const PsArgs& a, int64_t kbase, int k0, int k1, int64_t row, int col0,
                                                  int64_t out_index) {
@@ -817,16 +849,7 @@ __device__ __forceinline__ void ps16_item_global(const PsArgs& a, int64_t kbase,
         acc_add(acc, *reinterpret_cast<const int4*>(a.counts + (int64_t)j * a.s + col0));
     }
     const int4 own = *reinterpret_cast<const int4*>(a.counts + row * a.s + col0);
-    if (WPS) {
-        float o[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            o[q] = ps_value64(comp(own, q), acc[q]);
-            if (Q3) o[q] = (float)(rint((double)o[q] * 1000.0) / 1000.0);
-        }
-        store_f<4>(a.ps + out_index, o);
-    }
-    if (WEXCL) store_excl<4, unsigned long long>(a.excl + out_index, acc);
+    ps_finish64<4, WEXCL, WPS, Q3, 0>(a, own, acc, out_index);
 }
 
 template <bool WEXCL, bool WPS, bool Q3>
@@ -844,15 +867,8 @@ __global__ void __launch_bounds__(1024, 8) ps_tile_w16_kernel(PsArgs a) {
     int* rpL = colL + a.col_cap;
     unsigned* red = reinterpret_cast<unsigned*>(rpL + ((a.tile_rows + 1 + 3) & ~3));   // one word per wave (16-byte aligned)
 
-    const int bid = blockIdx.x;
-    int tile = bid / a.n_chunks;
-    int chunk = bid - tile * a.n_chunks;
-    if (a.tiles_per_xcd) {
-        const int k = bid >> 3;
-        const int t_local = k / a.n_chunks;
-        chunk = k - t_local * a.n_chunks;
-        tile = (bid & 7) * a.tiles_per_xcd + t_local;
-    }
+    int tile, chunk;
+    ps_tile_of_block(a, blockIdx.x, tile, chunk);
     if (tile >= a.n_tiles) return;
     const int c0 = chunk * a.chunk_cols;
     const int cwc = min(a.chunk_cols, a.s - c0);
@@ -880,37 +896,10 @@ __global__ void __launch_bounds__(1024, 8) ps_tile_w16_kernel(PsArgs a) {
     for (int k = 0; k < NOWN - 1; ++k)
         cv[k] = *reinterpret_cast<const int4*>(gtile + (size_t)(min(rowoff + (unsigned)k * step, last_row) + ccb));
 
-    // ---- (2) uniform scalars of the tile (scalar loads: they return on lgkmcnt, the vector queue stays untouched)
+    // ---- (2) uniform scalars of the tile, one scalar-load round trip
     long long kbase, kend;
-    int nlo = a.halo, nhi = a.halo;
-    {
-        const int64_t* pf = a.row_ptr + r0;
-        const int64_t* pl = pf + nr;
-        if (a.reach) {
-            const int b0 = r0 >> 4, bl = (r0 + nr - 1) >> 4;
-            const uint32_t* q0 = a.reach + b0;
-            const uint32_t* q1 = a.reach + min(b0 + 1, bl);
-            const uint32_t* q2 = a.reach + max(bl - 1, b0);
-            const uint32_t* q3 = a.reach + bl;
-            unsigned w0, w1, w2, w3;
-            asm volatile("s_nop 4\n\ts_load_dwordx2 %0, %6, 0x0\n\ts_load_dwordx2 %1, %7, 0x0\n\t"
-                         "s_load_dword %2, %8, 0x0\n\ts_load_dword %3, %9, 0x0\n\t"
-                         "s_load_dword %4, %10, 0x0\n\ts_load_dword %5, %11, 0x0\n\ts_waitcnt lgkmcnt(0)"
-                         : "=&s"(kbase), "=&s"(kend), "=&s"(w0), "=&s"(w1), "=&s"(w2), "=&s"(w3)
-                         : "s"(pf), "s"(pl), "s"(q0), "s"(q1), "s"(q2), "s"(q3) : "memory");
-            // block b reaches (w & 255) rows below row 16 b and (w >> 8 & 255) rows beyond row 16 b + 15
-            const int e = r0 + nr - 1;
-            int lo_need = (int)(w0 & 255u);
-            if (b0 < bl) lo_need = max(lo_need, (int)(w1 & 255u) - 16);
-            int hi_need = ((bl << 4) + 15 + (int)((w3 >> 8) & 255u)) - e;
-            if (b0 < bl) hi_need = max(hi_need, (bl << 4) - 1 + (int)((w2 >> 8) & 255u) - e);
-            nlo = min(max(lo_need, 0), a.halo);
-            nhi = min(max(hi_need, 0), a.halo);
-        } else {
-            asm volatile("s_nop 4\n\ts_load_dwordx2 %0, %2, 0x0\n\ts_load_dwordx2 %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
-                         : "=&s"(kbase), "=&s"(kend) : "s"(pf), "s"(pl) : "memory");
-        }
-    }
+    int nlo, nhi;
+    ps_tile_scalars(a, r0, nr, kbase, kend, nlo, nhi);
     const int nk = (int)(kend - kbase);
     const int slo = max(0, r0 - nlo);
     const int shi = min((int)a.n, r0 + nr + nhi);
@@ -985,65 +974,34 @@ __global__ void __launch_bounds__(1024, 8) ps_tile_w16_kernel(PsArgs a) {
             win8[(a.halo + nr) * LV + tid + T] = pack_sat16(v); cmax = max(cmax, vmax(v));
         }
     }
-    {
-        cmax = wave_max_dpp(cmax);
-        const unsigned long long any_out = __ballot(outside);
-        // one word per wave: its largest count (saturating at 2^24), bit 31 = one of its staged neighbours is outside the
-        // window; sixteen words are read back, wave 0 clears the unused ones
-        if (lane == 63) red[wave] = min(cmax, 0x1000000u) | (any_out != 0ull ? 0x80000000u : 0u);
-        if (wave == 0 && lane >= NW && lane < 16) red[lane] = 0u;
-    }
-    __syncthreads();
-    unsigned tile_cmax, tile_or;
-    {
-        const uint4* r4 = reinterpret_cast<const uint4*>(red);
-        const uint4 x0 = r4[0], x1 = r4[1], x2 = r4[2], x3 = r4[3];
-        tile_or = (x0.x | x0.y | x0.z | x0.w) | (x1.x | x1.y | x1.z | x1.w) | (x2.x | x2.y | x2.z | x2.w) | (x3.x | x3.y | x3.z | x3.w);
-        const unsigned k = 0x7fffffffu;
-        const unsigned m0 = max(max(x0.x & k, x0.y & k), max(x0.z & k, x0.w & k)), m1 = max(max(x1.x & k, x1.y & k), max(x1.z & k, x1.w & k));
-        const unsigned m2 = max(max(x2.x & k, x2.y & k), max(x2.z & k, x2.w & k)), m3 = max(max(x3.x & k, x3.y & k), max(x3.z & k, x3.w & k));
-        tile_cmax = max(max(m0, m1), max(m2, m3));
-    }
-    tile_cmax = (unsigned)__builtin_amdgcn_readfirstlane((int)tile_cmax);
+    bool all_in;                                                                         // block-uniform, as is tile_cmax
+    const unsigned tile_cmax = ps_tile_sync_bound(cmax, outside, red, lane, wave, NW, all_in);
     const bool hi_tile = tile_cmax >= 0xFFFFu;                                           // block-uniform: halves may be saturated
-    const bool all_in = __builtin_amdgcn_readfirstlane((int)tile_or) >= 0;               // block-uniform: no per-batch window check needed
     // (degree + 1) * (largest count of the tile) <= 0xFFFF  <=>  degree + 1 <= lim16
     const unsigned lim16 = tile_cmax ? 0xFFFFu / tile_cmax : 0xFFFFFFFFu;
 
-    // ---- per (row, vector) item: gather neighbours from LDS, divide, store (addressing as in ps_tile_v3_kernel)
+    // ---- per (row, vector) item: gather neighbours from LDS, divide, store
     {
         const int items = nr * V;
-        int ri = tid / V, c = tid - ri * V;
-        const int dr = T / V, dc = T - dr * V;
-        PsArgs b = a;
-        {
-            const int64_t tile_base = (int64_t)r0 * a.s + c0;
-            if (WPS) b.ps = a.ps + tile_base;
-            if (WEXCL) b.excl = a.excl + tile_base;
-        }
-        unsigned o32 = (unsigned)ri * (unsigned)a.s + (unsigned)(c * VEC);
-        const unsigned d_o = (unsigned)dr * (unsigned)a.s + (unsigned)(dc * VEC), wrap_o = (unsigned)a.s - (unsigned)(V * VEC);
-        int own_off = (a.halo + ri) * rowb;
-        const int d_own = dr * rowb;
-        for (int it = tid; it < items; it += T) {
-            const int k0 = rpL[ri], k1 = rpL[ri + 1];
-            const int64_t o = (int64_t)(uint64_t)o32;
+        const PsArgs b = ps_tile_outputs<WEXCL, WPS>(a, r0, c0);
+        PsItemWalk w(a, tid, T, V, rowb);
+        for (int it = tid; it < items; it += T, w.next()) {
+            const int k0 = rpL[w.ri], k1 = rpL[w.ri + 1];
+            const int64_t o = w.out_index();
             bool done = false;
             const unsigned deg = (unsigned)(k1 - k0);
             if (col_in_lds && deg < 254u) {
                 if (hi_tile)
-                    done = ps16_item_wide<WEXCL, WPS, true, true, Q3>(b, tileB, colL, k0, k1, c * 8, own_off, o, zero_off);
+                    done = ps16_item_wide<WEXCL, WPS, true, true, Q3>(b, tileB, colL, k0, k1, w.c * 8, w.own_off, o, zero_off);
                 else if (deg + 1u <= lim16)
-                    done = all_in ? ps16_item_packed<WEXCL, WPS, false, Q3>(b, tileB, colL, k0, k1, c * 8, own_off, o, zero_off)
-                                  : ps16_item_packed<WEXCL, WPS, true, Q3>(b, tileB, colL, k0, k1, c * 8, own_off, o, zero_off);
+                    done = all_in ? ps16_item_packed<WEXCL, WPS, false, Q3>(b, tileB, colL, k0, k1, w.c * 8, w.own_off, o, zero_off)
+                                  : ps16_item_packed<WEXCL, WPS, true, Q3>(b, tileB, colL, k0, k1, w.c * 8, w.own_off, o, zero_off);
                 else
-                    done = all_in ? ps16_item_wide<WEXCL, WPS, false, false, Q3>(b, tileB, colL, k0, k1, c * 8, own_off, o, zero_off)
-                                  : ps16_item_wide<WEXCL, WPS, true, false, Q3>(b, tileB, colL, k0, k1, c * 8, own_off, o, zero_off);
+                    done = all_in ? ps16_item_wide<WEXCL, WPS, false, false, Q3>(b, tileB, colL, k0, k1, w.c * 8, w.own_off, o, zero_off)
+                                  : ps16_item_wide<WEXCL, WPS, true, false, Q3>(b, tileB, colL, k0, k1, w.c * 8, w.own_off, o, zero_off);
             }
             if (!done)
-                ps16_item_global<WEXCL, WPS, Q3>(b, kbase, k0, k1, (int64_t)(r0 + ri), c0 + c * VEC, o);
-            c += dc; ri += dr; o32 += d_o; own_off += d_own;
-            if (c >= V) { c -= V; ri += 1; o32 += wrap_o; own_off += rowb; }
+                ps16_item_global<WEXCL, WPS, Q3>(b, kbase, k0, k1, (int64_t)(r0 + w.ri), c0 + w.c * VEC, o);
         }
     }
 }
@@ -1081,6 +1039,17 @@ __global__ void mark_low_kernel(float* __restrict__ ps, const int64_t* __restric
     }
 }
 
+// (want_excl, want_ps, q3) -> one of the five <WE, WP, Q3> instantiations a tile kernel has: f is called with three
+// std::integral_constant<bool, ...> arguments.  Exclusion sums alone have nothing to quantise: q3 is ignored there
+template <typename F>
+int ps_with_flags(bool wexcl, bool wps, bool q3, F&& f) {
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if (wexcl && wps) return q3 ? f(yes, yes, yes) : f(yes, yes, no);
+    if (wexcl) return f(yes, no, no);
+    return q3 ? f(no, yes, yes) : f(no, yes, no);
+}
+
 template <int VEC, bool WE, bool WP, bool Q3, int ABL>
 int launch_ps_one(sdice_ctx* ctx, const PsArgs& a, int threads, size_t lds, dim3 grid) {
     SD_LAUNCH_LDS(ctx, "ps_tile_kernel", (ps_tile_kernel<VEC, WE, WP, Q3, ABL>), grid, dim3(threads), lds, a);
@@ -1094,11 +1063,9 @@ int launch_ps_v3_one(sdice_ctx* ctx, const PsArgs& a, int threads, size_t lds, d
 }
 template <bool CH>
 int launch_ps_v3(sdice_ctx* ctx, const PsArgs& a, int threads, size_t lds, dim3 grid, bool wexcl, bool wps, bool q3) {
-    if (wexcl && wps) return q3 ? launch_ps_v3_one<CH, true, true, true>(ctx, a, threads, lds, grid)
-                                : launch_ps_v3_one<CH, true, true, false>(ctx, a, threads, lds, grid);
-    if (wexcl) return launch_ps_v3_one<CH, true, false, false>(ctx, a, threads, lds, grid);
-    return q3 ? launch_ps_v3_one<CH, false, true, true>(ctx, a, threads, lds, grid)
-              : launch_ps_v3_one<CH, false, true, false>(ctx, a, threads, lds, grid);
+    return ps_with_flags(wexcl, wps, q3, [&](auto we, auto wp, auto q) {
+        return launch_ps_v3_one<CH, decltype(we)::value, decltype(wp)::value, decltype(q)::value>(ctx, a, threads, lds, grid);
+    });
 }
 
 template <bool WE, bool WP, bool Q3>
@@ -1109,11 +1076,9 @@ int launch_ps_w16_one(sdice_ctx* ctx, const PsArgs& a, int threads, size_t lds, 
     return SDICE_OK;
 }
 int launch_ps_w16(sdice_ctx* ctx, const PsArgs& a, int threads, size_t lds, dim3 grid, bool wexcl, bool wps, bool q3) {
-    if (wexcl && wps) return q3 ? launch_ps_w16_one<true, true, true>(ctx, a, threads, lds, grid)
-                                : launch_ps_w16_one<true, true, false>(ctx, a, threads, lds, grid);
-    if (wexcl) return launch_ps_w16_one<true, false, false>(ctx, a, threads, lds, grid);
-    return q3 ? launch_ps_w16_one<false, true, true>(ctx, a, threads, lds, grid)
-              : launch_ps_w16_one<false, true, false>(ctx, a, threads, lds, grid);
+    return ps_with_flags(wexcl, wps, q3, [&](auto we, auto wp, auto q) {
+        return launch_ps_w16_one<decltype(we)::value, decltype(wp)::value, decltype(q)::value>(ctx, a, threads, lds, grid);
+    });
 }
 
 template <int VEC>
@@ -1130,11 +1095,9 @@ int launch_ps(sdice_ctx* ctx, const PsArgs& a, int threads, size_t lds, dim3 gri
             default: return launch_ps_one<4, false, true, false, 7>(ctx, a, threads, lds, grid);
         }
     }
-    if (wexcl && wps) return q3 ? launch_ps_one<VEC, true, true, true, 0>(ctx, a, threads, lds, grid)
-                                : launch_ps_one<VEC, true, true, false, 0>(ctx, a, threads, lds, grid);
-    if (wexcl) return launch_ps_one<VEC, true, false, false, 0>(ctx, a, threads, lds, grid);
-    return q3 ? launch_ps_one<VEC, false, true, true, 0>(ctx, a, threads, lds, grid)
-              : launch_ps_one<VEC, false, true, false, 0>(ctx, a, threads, lds, grid);
+    return ps_with_flags(wexcl, wps, q3, [&](auto we, auto wp, auto q) {
+        return launch_ps_one<VEC, decltype(we)::value, decltype(wp)::value, decltype(q)::value, 0>(ctx, a, threads, lds, grid);
+    });
 }
 
 }  // namespace
