@@ -48,30 +48,6 @@ SIGNATURES = {
     "sdice_mark_low_dev": [ctxp, C.c_int64, vp, vp, C.c_int64],
     "sdice_quantize3": [ctxp, C.c_int64, vp],
     "sdice_quantize3_dev": [ctxp, C.c_int64, vp],
-    "sdice_ranksum": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32] + [vp] * 8,
-    "sdice_ranksum_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32] + [vp] * 8,
-    "sdice_kruskal": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 6,
-    "sdice_kruskal_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 6,
-    "sdice_kruskal_dunn": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 9,
-    "sdice_kruskal_dunn_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 9,
-    "sdice_jonckheere": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 7,
-    "sdice_jonckheere_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 7,
-    "sdice_signedrank": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 8,
-    "sdice_signedrank_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 8,
-    "sdice_ranksum_exact": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32] + [vp] * 9,
-    "sdice_ranksum_exact_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32] + [vp] * 9,
-    "sdice_signedrank_exact": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 9,
-    "sdice_signedrank_exact_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 9,
-    "sdice_ranksum_strata": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32] + [vp] * 8,
-    "sdice_ranksum_strata_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32] + [vp] * 8,
-    "sdice_ks": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32] + [vp] * 9,
-    "sdice_ks_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32] + [vp] * 9,
-    "sdice_shift": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_double] + [vp] * 5,
-    "sdice_shift_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_double] + [vp] * 5,
-    "sdice_spearman": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 6,
-    "sdice_spearman_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 6,
-    "sdice_sample_gram": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32] + [vp] * 4,
-    "sdice_sample_gram_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, C.c_int32] + [vp] * 4,
     "sdice_sample_matrix_finish": [C.c_int32, vp, vp, vp, vp, C.c_int64, vp, vp],
     "sdice_fisher_pairs": [ctxp, C.c_int64, C.c_int32, vp, vp, vp],
     "sdice_fisher_pairs_dev": [ctxp, C.c_int64, C.c_int32, vp, vp, vp],
@@ -138,6 +114,26 @@ SIGNATURES = {
     "sdice_scratch_region": [ctxp, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(vp), c_i64p],
     "sdice_ps_last_plan": [ctxp, c_i32p, C.c_int32, c_i32p],
 }
+# the row tests: sdice_<name> and sdice_<name>_dev take the same list -- the context, n, s, the table, the arguments of the
+# test, then one pointer per output field (engine.ROW_TESTS)
+_TABLE = [ctxp, C.c_int64, C.c_int32, vp]
+_TWO_GROUPS = [vp, C.c_int32, vp, C.c_int32]
+_TWO_LISTS = [vp, vp, C.c_int32]              # (k sets: cols, set_ptr, k; m pairs: a, b, m; spearman: cols, xg, m)
+for _name, _args, _outputs in (
+        ("ranksum", _TWO_GROUPS, 8),
+        ("ranksum_exact", _TWO_GROUPS, 9),
+        ("ranksum_strata", _TWO_GROUPS + [vp, vp, C.c_int32], 8),
+        ("ks", _TWO_GROUPS + [C.c_int32], 9),
+        ("shift", _TWO_GROUPS + [C.c_double], 5),
+        ("kruskal", _TWO_LISTS, 6),
+        ("kruskal_dunn", _TWO_LISTS, 9),
+        ("jonckheere", _TWO_LISTS, 7),
+        ("signedrank", _TWO_LISTS, 8),
+        ("signedrank_exact", _TWO_LISTS, 9),
+        ("spearman", _TWO_LISTS, 6),
+        ("sample_gram", [vp, C.c_int32], 4)):
+    for _form in ("", "_dev"):
+        SIGNATURES["sdice_" + _name + _form] = _TABLE + _args + [vp] * _outputs
 _RESTYPE = {"sdice_last_error": C.c_char_p}
 
 _lib = None

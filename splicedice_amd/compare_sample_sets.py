@@ -107,8 +107,8 @@ def compare(matrix, g1_idx, g2_idx, ctx, paired=False, exact=False, conf=None):
         def launch(d, out):
             test(d["ps"], d["g1"], d["g2"], out)
             if conf is not None:
-                ctx.shift_resident(d["ps"], d["g1"], d["g2"], {f[0]: out["shift" if f[0] == "shift" else "shift_" + f[0]]
-                                                          for f in SHIFT_FIELDS}, conf)
+                ctx.shift_dev(d["ps"], d["g1"], d["g2"], {f[0]: out["shift" if f[0] == "shift" else "shift_" + f[0]]
+                                                     for f in SHIFT_FIELDS}, conf)
 
         keep, r = tested(ctx, matrix, (RANKSUM_EXACT_FIELDS if exact else RANKSUM_FIELDS) + (SHIFT_RIDERS if conf is not None else []),
                          dict(g1=(g1_idx, np.int32), g2=(g2_idx, np.int32)), launch)
@@ -289,11 +289,10 @@ def _two_sets(sel):
     return dict(g1=(sel.g1_idx, np.int32), g2=(sel.g2_idx, np.int32))
 
 
-def _k_sets(test, resident=None):
-    """the rest of a row over k >= 3 sets; test: the engine's name of the call, resident: that of its form on resident
-    data where it is not `<test>_dev`"""
+def _k_sets(test):
+    """the rest of a row over k >= 3 sets; test: the engine's name of the call (`<test>_dev` on resident data)"""
     return dict(inputs=lambda sel: dict(cols=(sel.cols, np.int32)), k=lambda sel: len(sel.set_idx),
-                dev=lambda ctx, sel: lambda d, out: getattr(ctx, resident or test + "_dev")(d["ps"], d["cols"], sel.set_ptr, out),
+                dev=lambda ctx, sel: lambda d, out: getattr(ctx, test + "_dev")(d["ps"], d["cols"], sel.set_ptr, out),
                 host=lambda ctx, matrix, sel: getattr(ctx, test)(matrix, sel.set_idx))
 
 
@@ -347,7 +346,7 @@ TESTS = (
          conflicts=((TREND, "the trend test has one ordered alternative, not pairs"),),
          multi_rank=_multi_rank(POSTHOC, "the packed all-gather carries the two-set fields only"),
          fields=[f for f in KRUSKAL_DUNN_FIELDS if f[0] != "pair_p"],        # (the table prints z and padj: pair_p stays NULL)
-         stat=_dunn_columns, **_k_sets("kruskal_dunn", "kruskal_dunn_resident")),
+         stat=_dunn_columns, **_k_sets("kruskal_dunn")),
     # k >= 3 sets: Kruskal-Wallis per junction (--trend above: Jonckheere-Terpstra over the sets in this order)
     Test(MX, multi_rank=_multi_rank(MX, "the packed all-gather carries the two-set fields only"),
          fields=KRUSKAL_FIELDS, stat=(("H", "h"),), **_k_sets("kruskal")),

@@ -37,6 +37,22 @@ JONCKHEERE_FIELDS = [("tested", np.uint8), ("p", np.float64), ("z", np.float64),
 SPEARMAN_FIELDS = [("tested", np.uint8), ("p", np.float64), ("rho", np.float64), ("n_kept", np.int32), ("med", np.float32),
                    ("mean", np.float32)]
 GRAM_FIELDS = [("shared", np.int64), ("sum1", np.int64), ("sum2", np.int64), ("prod", np.int64)]
+# Every row test: the name of its pair of C entry points (sdice_<name>, sdice_<name>_dev) and of its pair of Context methods
+# (<name>, <name>_dev) -> (its field table, the fields a _dev call may leave out of `out`: the library is handed NULL)
+ROW_TESTS = {
+    "ranksum": (RANKSUM_FIELDS, ("z",)),
+    "ranksum_exact": (RANKSUM_EXACT_FIELDS, ("z",)),
+    "ranksum_strata": (RANKSUM_FIELDS, ("z",)),
+    "ks": (KS_FIELDS, ("d", "exact")),             # (ks_dev(exact=True) wants exact)
+    "shift": (SHIFT_FIELDS, ()),
+    "kruskal": (KRUSKAL_FIELDS, ("h",)),
+    "kruskal_dunn": (KRUSKAL_DUNN_FIELDS, ("h", "pair_p", "pair_padj")),
+    "jonckheere": (JONCKHEERE_FIELDS, ("j",)),
+    "signedrank": (RANKSUM_FIELDS, ("z",)),
+    "signedrank_exact": (RANKSUM_EXACT_FIELDS, ("z",)),
+    "spearman": (SPEARMAN_FIELDS, ("rho",)),
+    "sample_gram": (GRAM_FIELDS, ()),
+}
 
 
 def field_shapes(fields, shape, k=None):
@@ -55,10 +71,20 @@ def _zeros(fields, shape, k=None):
     return {name: np.zeros(sh, dt) for name, (sh, dt) in field_shapes(fields, shape, k).items()}
 
 
-def _dev_ptrs(fields, out, optional=()):
-    """the device pointers of a _dev call in the order of its field table; None for a field named in `optional` (a tuple)
-    when `out` lacks it"""
-    return [out[f[0]].ptr if f[0] not in optional or out.get(f[0]) else None for f in fields]
+def _arg(a):
+    """an argument between the table and the outputs of a row test as ctypes takes it: the address of a device or a host
+    array, anything else as it is"""
+    return a.ptr if isinstance(a, DeviceArray) else _ptr(a) if isinstance(a, np.ndarray) else a
+
+
+def _int_lists(*lists):
+    """column lists (or the ids that go with them) as int32 vectors"""
+    return [_c(v, np.int32).reshape(-1) for v in lists]
+
+
+def _with_lengths(*lists):
+    """(a, b) -> (a, len a, b, len b): the two column lists of a two-group call, host vectors or device arrays"""
+    return tuple(x for a in lists for x in (a, a.shape[0]))
 
 
 def pair_array(pairs):
@@ -348,34 +374,29 @@ class Context:
             return ps, excl
         return ps if want_ps else excl
 
-    def ps_f64(self, counts, row_ptr, col, n_out=None):
-        """-> ps float64[n_out,s] of a float64 count table, sums in list order (counts_to_ps.py:58-70).
-        Rows n_out.. of `counts` are sources only."""
+    def _listed_f64(self, name, counts, row_ptr, col, n_out):
+        """sdice_<name>: a float64 [n_out, s] result over the listed rows of a float64 table (ps_f64, excl_f64)"""
         counts = _c(counts, np.float64)
         n_rows, s = counts.shape
         n_out = n_rows if n_out is None else int(n_out)
         row_ptr, col = _c(row_ptr, np.int64), _c(col, np.int32)
         if row_ptr.size != n_out + 1:
-            raise ValueError("ps_f64: row_ptr must hold n_out + 1 entries")
-        ps = np.empty((n_out, s), dtype=np.float64)
-        check(self.lib.sdice_ps_f64(self.h, n_out, n_rows, s, _ptr(counts), _ptr(row_ptr), _ptr(col), _ptr(ps)),
-              "sdice_ps_f64")
-        return ps
+            raise ValueError(f"{name}: row_ptr must hold n_out + 1 entries")
+        out = np.empty((n_out, s), dtype=np.float64)
+        check(getattr(self.lib, "sdice_" + name)(self.h, n_out, n_rows, s, _ptr(counts), _ptr(row_ptr), _ptr(col), _ptr(out)),
+              "sdice_" + name)
+        return out
+
+    def ps_f64(self, counts, row_ptr, col, n_out=None):
+        """-> ps float64[n_out,s] of a float64 count table, sums in list order (counts_to_ps.py:58-70).
+        Rows n_out.. of `counts` are sources only."""
+        return self._listed_f64("ps_f64", counts, row_ptr, col, n_out)
 
     def excl_f64(self, counts, row_ptr, col, n_out=None):
         """-> float64[n_out,s]: for every row the sum of the listed rows of a float64 table, one addition per row in list
         order (np.sum(counts[mask], axis=0) of pairwise_fisher.py:158-160 when the lists are in table order).
         Rows n_out.. of `counts` are sources only."""
-        counts = _c(counts, np.float64)
-        n_rows, s = counts.shape
-        n_out = n_rows if n_out is None else int(n_out)
-        row_ptr, col = _c(row_ptr, np.int64), _c(col, np.int32)
-        if row_ptr.size != n_out + 1:
-            raise ValueError("excl_f64: row_ptr must hold n_out + 1 entries")
-        out = np.empty((n_out, s), dtype=np.float64)
-        check(self.lib.sdice_excl_f64(self.h, n_out, n_rows, s, _ptr(counts), _ptr(row_ptr), _ptr(col), _ptr(out)),
-              "sdice_excl_f64")
-        return out
+        return self._listed_f64("excl_f64", counts, row_ptr, col, n_out)
 
     def mark_low(self, ps, low_flat_idx):
         ps = _c(ps, np.float32)
@@ -388,150 +409,106 @@ class Context:
         check(self.lib.sdice_quantize3(self.h, out.size, _ptr(out)), "sdice_quantize3")
         return out
 
-    def _ranksum(self, name, fields, ps, g1, g2):
+    def _host_row(self, name, ps, mid, shape=None, k=None, skip=()):
+        """the host form of a row test of ROW_TESTS: sdice_<name>(ctx, n, s, ps, *mid, the outputs in field order) on zeroed
+        outputs of `shape` (default: [n]; k sets for the per-set and per-pair fields) -> {field: array}.  A field named in
+        `skip` is handed to the library as NULL and is not in the result."""
         ps = _c(ps, np.float32)
         n, s = ps.shape
-        g1, g2 = _c(g1, np.int32), _c(g2, np.int32)
-        out = _zeros(fields, n)
-        check(getattr(self.lib, "sdice_" + name)(self.h, n, s, _ptr(ps), _ptr(g1), g1.size, _ptr(g2), g2.size,
-                                                 *map(_ptr, out.values())), "sdice_" + name)
-        return out
+        out = _zeros(ROW_TESTS[name][0], n if shape is None else shape, k)
+        check(getattr(self.lib, "sdice_" + name)(self.h, n, s, _ptr(ps), *map(_arg, mid),
+                                                 *[None if f in skip else _ptr(a) for f, a in out.items()]), "sdice_" + name)
+        return {f: a for f, a in out.items() if f not in skip}
+
+    def _host_sets(self, name, ps, sets, skip=()):
+        """_host_row over k column sets (kruskal_sets checks them against the table's columns)"""
+        ps = _c(ps, np.float32)
+        _, s = ps.shape
+        cols, set_ptr = kruskal_sets(sets, s)
+        k = len(set_ptr) - 1
+        return self._host_row(name, ps, (cols, set_ptr, k), k=k, skip=skip)
+
+    def _host_pairs(self, name, ps, a, b):
+        """_host_row over matched column pairs"""
+        a, b = _c(a, np.int32), _c(b, np.int32)
+        if a.shape != b.shape or a.ndim != 1:
+            raise ValueError(f"{name}: the pair lists must be two vectors of one length, got {a.shape} and {b.shape}")
+        return self._host_row(name, ps, (a, b, a.size))
 
     def ranksum(self, ps, g1, g2):
         """compareSampleSets.py:216-232 for every row; un-compacted outputs + tested mask."""
-        return self._ranksum("ranksum", RANKSUM_FIELDS, ps, g1, g2)
+        return self._host_row("ranksum", ps, _with_lengths(*_int_lists(g1, g2)))
 
     def ranksum_exact(self, ps, g1, g2):
         """ranksum() with the exact conditional p-value on the rows that keep at most 32 values (include/sdice.h): the
         same outputs + exact (1 where p is the exact value); every other field is ranksum()'s bit for bit."""
-        return self._ranksum("ranksum_exact", RANKSUM_EXACT_FIELDS, ps, g1, g2)
+        return self._host_row("ranksum_exact", ps, _with_lengths(*_int_lists(g1, g2)))
 
     def ranksum_strata(self, ps, g1, g2, strat1, strat2):
         """van Elteren's stratified rank-sum test per row (include/sdice.h): strat1 / strat2 are the dense stratum ids
         (strata_ids) of the columns g1 / g2; the outputs of ranksum(), with medians and means that are ranksum()'s."""
-        ps = _c(ps, np.float32)
-        n, s = ps.shape
-        g1, g2, strat1, strat2 = (_c(v, np.int32).reshape(-1) for v in (g1, g2, strat1, strat2))
+        g1, g2, strat1, strat2 = _int_lists(g1, g2, strat1, strat2)
         if g1.size != strat1.size or g2.size != strat2.size:
             raise ValueError(f"ranksum_strata: one stratum id per listed column, got {g1.size} / {strat1.size} and "
                              f"{g2.size} / {strat2.size}")
         n_strata = int(max(strat1.max(initial=-1), strat2.max(initial=-1))) + 1
-        out = _zeros(RANKSUM_FIELDS, n)
-        check(self.lib.sdice_ranksum_strata(self.h, n, s, _ptr(ps), _ptr(g1), g1.size, _ptr(g2), g2.size, _ptr(strat1),
-                                            _ptr(strat2), n_strata, *map(_ptr, out.values())), "sdice_ranksum_strata")
-        return out
+        return self._host_row("ranksum_strata", ps, (*_with_lengths(g1, g2), strat1, strat2, n_strata))
 
     def ks(self, ps, g1, g2, exact=False):
         """the two-sample Kolmogorov-Smirnov test per row (include/sdice.h): un-compacted tested, p, d (the statistic D),
         the medians, means and delta of ranksum(), and exact (1 where p is the exact conditional value: with exact=True,
         on the tested rows that keep at most 32 values; all 0 otherwise)."""
-        ps = _c(ps, np.float32)
-        n, s = ps.shape
-        g1, g2 = _c(g1, np.int32).reshape(-1), _c(g2, np.int32).reshape(-1)
-        out = _zeros(KS_FIELDS, n)
-        check(self.lib.sdice_ks(self.h, n, s, _ptr(ps), _ptr(g1), g1.size, _ptr(g2), g2.size, int(bool(exact)),
-                                *map(_ptr, out.values())), "sdice_ks")
-        return out
+        return self._host_row("ks", ps, (*_with_lengths(*_int_lists(g1, g2)), int(bool(exact))))
 
     def shift(self, ps, g1, g2, conf=0.95):
         """the Hodges-Lehmann shift of group 1 against group 2 per row with its confidence interval at level conf
         (include/sdice.h): un-compacted tested (ranksum()'s), shift (the median of the pairwise differences), lo and hi (two
         order statistics of them) and rank (which ones; 1 = the whole range, the level is not reached)."""
-        ps = _c(ps, np.float32)
-        n, s = ps.shape
-        g1, g2 = _c(g1, np.int32).reshape(-1), _c(g2, np.int32).reshape(-1)
-        out = _zeros(SHIFT_FIELDS, n)
-        check(self.lib.sdice_shift(self.h, n, s, _ptr(ps), _ptr(g1), g1.size, _ptr(g2), g2.size, shift_quantile(conf),
-                                   *map(_ptr, out.values())), "sdice_shift")
-        return out
+        return self._host_row("shift", ps, (*_with_lengths(*_int_lists(g1, g2)), shift_quantile(conf)))
 
     def kruskal(self, ps, sets):
         """scipy.stats.kruskal per row across the k column sets under the row rules of ranksum(); un-compacted outputs:
         tested, p, h [n], med, mean [k, n] (set-major), delta [n] = largest minus smallest set median."""
-        ps = _c(ps, np.float32)
-        n, s = ps.shape
-        cols, set_ptr = kruskal_sets(sets, s)
-        k = len(set_ptr) - 1
-        out = _zeros(KRUSKAL_FIELDS, n, k)
-        check(self.lib.sdice_kruskal(self.h, n, s, _ptr(ps), _ptr(cols), _ptr(set_ptr), k, *map(_ptr, out.values())),
-              "sdice_kruskal")
-        return out
+        return self._host_sets("kruskal", ps, sets)
 
     def kruskal_dunn(self, ps, sets, pair_p=True, pair_padj=True):
         """kruskal() with Dunn's test for every pair of sets from the same joint ranking (include/sdice.h): kruskal()'s
         outputs bit for bit, and pair_z, pair_p, pair_padj float64 [k (k - 1) / 2, n] in the order of dunn_pairs(k): z > 0
-        where set i ranks above set j, p two-sided, padj Holm's step-down inside the row.  At most DUNN_MAX_SETS sets.
-        pair_p / pair_padj False: the library is handed NULL for that output and the result lacks it."""
-        ps = _c(ps, np.float32)
-        n, s = ps.shape
-        cols, set_ptr = kruskal_sets(sets, s)
-        k = len(set_ptr) - 1
-        out = _zeros(KRUSKAL_DUNN_FIELDS, n, k)          # (the library refuses k > DUNN_MAX_SETS)
-        skipped = [name for name, on in (("pair_p", pair_p), ("pair_padj", pair_padj)) if not on]
-        check(self.lib.sdice_kruskal_dunn(self.h, n, s, _ptr(ps), _ptr(cols), _ptr(set_ptr), k,
-                                          *[None if name in skipped else _ptr(a) for name, a in out.items()]),
-              "sdice_kruskal_dunn")
-        for name in skipped:
-            del out[name]
-        return out
+        where set i ranks above set j, p two-sided, padj Holm's step-down inside the row.  At most DUNN_MAX_SETS sets (the
+        library refuses more).  pair_p / pair_padj False: the library is handed NULL for that output and the result lacks
+        it."""
+        return self._host_sets("kruskal_dunn", ps, sets,
+                               skip=[name for name, on in (("pair_p", pair_p), ("pair_padj", pair_padj)) if not on])
 
     def jonckheere(self, ps, sets):
         """Jonckheere-Terpstra trend test per row across the k ORDERED column sets (set 0 < set 1 < ...) under the row rules
         of kruskal(); un-compacted outputs: tested, p, z (> 0: the values rise along the order), j = J [n], med, mean
         [k, n] and delta [n] as kruskal()'s."""
-        ps = _c(ps, np.float32)
-        n, s = ps.shape
-        cols, set_ptr = kruskal_sets(sets, s)
-        k = len(set_ptr) - 1
-        out = _zeros(JONCKHEERE_FIELDS, n, k)
-        check(self.lib.sdice_jonckheere(self.h, n, s, _ptr(ps), _ptr(cols), _ptr(set_ptr), k, *map(_ptr, out.values())),
-              "sdice_jonckheere")
-        return out
-
-    def _signedrank(self, name, fields, ps, a, b):
-        ps = _c(ps, np.float32)
-        n, s = ps.shape
-        a, b = _c(a, np.int32), _c(b, np.int32)
-        if a.shape != b.shape or a.ndim != 1:
-            raise ValueError(f"{name}: the pair lists must be two vectors of one length, got {a.shape} and {b.shape}")
-        out = _zeros(fields, n)
-        check(getattr(self.lib, "sdice_" + name)(self.h, n, s, _ptr(ps), _ptr(a), _ptr(b), a.size, *map(_ptr, out.values())),
-              "sdice_" + name)
-        return out
+        return self._host_sets("jonckheere", ps, sets)
 
     def signedrank(self, ps, a, b):
         """scipy.stats.wilcoxon (asymptotic, zero_method="wilcox") per row over the matched column pairs (a[q], b[q])
         under the row rules of ranksum(); same un-compacted outputs + tested mask (z > 0: side a is larger)."""
-        return self._signedrank("signedrank", RANKSUM_FIELDS, ps, a, b)
+        return self._host_pairs("signedrank", ps, a, b)
 
     def signedrank_exact(self, ps, a, b):
         """signedrank() with the exact p-value on the rows with at most 31 non-zero differences (include/sdice.h): the
         same outputs + exact; every other field is signedrank()'s bit for bit."""
-        return self._signedrank("signedrank_exact", RANKSUM_EXACT_FIELDS, ps, a, b)
+        return self._host_pairs("signedrank_exact", ps, a, b)
 
     def spearman(self, ps, cols, x):
         """scipy.stats.spearmanr(x_kept, ps_kept) per row between the PS values of the listed columns and the covariate x
         (one finite value per listed column) under the row rules of ranksum(); un-compacted outputs: tested, p, rho,
         n_kept (int32), med, mean of the kept PS values (in the order of spearman_order(cols, x))."""
-        ps = _c(ps, np.float32)
-        n, s = ps.shape
         cols, xg = spearman_order(cols, x)
-        out = _zeros(SPEARMAN_FIELDS, n)
-        check(self.lib.sdice_spearman(self.h, n, s, _ptr(ps), _ptr(cols), _ptr(xg), cols.size, *map(_ptr, out.values())),
-              "sdice_spearman")
-        return out
+        return self._host_row("spearman", ps, (cols, xg, cols.size))
 
     def sample_gram(self, ps, cols):
         """the exact integer sums of every pair of the listed columns over the rows both have a value in -> dict of int64
         [m, m]: shared (row count), sum1 / sum2 ([a, b]: a's sum of 3-decimal keys / squared keys over the rows shared
         with b), prod (sum of key products).  A value off the 3-decimal grid in a listed column raises SdiceError."""
-        ps = _c(ps, np.float32)
-        n, s = ps.shape
         cols = gram_columns(cols)
-        m = cols.size
-        out = _zeros(GRAM_FIELDS, (m, m))
-        check(self.lib.sdice_sample_gram(self.h, n, s, _ptr(ps), _ptr(cols), m, *map(_ptr, out.values())), "sdice_sample_gram")
-        return out
+        return self._host_row("sample_gram", ps, (cols, cols.size), shape=(cols.size, cols.size))
 
     def _pair_test(self, test, dev, incl, excl, pairs, p, *bad):
         """the C call behind the four pair methods: sdice_<test>_pair_list over a list, else sdice_<test>_pairs; dev: the _dev
@@ -646,93 +623,74 @@ class Context:
     def quantize3_dev(self, d_ps):
         check(self.lib.sdice_quantize3_dev(self.h, int(np.prod(d_ps.shape)), d_ps.ptr), "sdice_quantize3_dev")
 
-    def ranksum_dev(self, d_ps, d_g1, d_g2, out):
+    def _resident_row(self, name, d_ps, mid, out, optional=None):
+        """the resident form of a row test of ROW_TESTS: sdice_<name>_dev(ctx, n, s, d_ps, *mid, the device outputs of `out`
+        in field order).  A field of `optional` (default: the test's own) that `out` lacks is handed to the library as
+        NULL; any other field that `out` lacks raises ValueError."""
+        fields, may_omit = ROW_TESTS[name]
         n, s = d_ps.shape
-        check(self.lib.sdice_ranksum_dev(self.h, n, s, d_ps.ptr, d_g1.ptr, d_g1.shape[0], d_g2.ptr, d_g2.shape[0],
-                                         *_dev_ptrs(RANKSUM_FIELDS, out, ("z",))), "sdice_ranksum_dev")
+        ptrs = []
+        for f in fields:
+            d = out.get(f[0])
+            if d is None and f[0] not in (may_omit if optional is None else optional):
+                raise ValueError(f"{name}_dev: out lacks the required field {f[0]!r}")
+            ptrs.append(None if d is None else d.ptr)
+        check(getattr(self.lib, f"sdice_{name}_dev")(self.h, n, s, d_ps.ptr, *map(_arg, mid), *ptrs), f"sdice_{name}_dev")
+
+    def ranksum_dev(self, d_ps, d_g1, d_g2, out):
+        self._resident_row("ranksum", d_ps, _with_lengths(d_g1, d_g2), out)
 
     def ranksum_strata_dev(self, d_ps, d_g1, d_g2, d_strat1, d_strat2, n_strata, out):
         """d_strat1, d_strat2: the device copies of the stratum ids of d_g1, d_g2 (checked by the caller: the host call
         checks them, this one cannot); out: the device fields of RANKSUM_FIELDS (z optional)"""
-        n, s = d_ps.shape
-        check(self.lib.sdice_ranksum_strata_dev(self.h, n, s, d_ps.ptr, d_g1.ptr, d_g1.shape[0], d_g2.ptr, d_g2.shape[0],
-                                                d_strat1.ptr, d_strat2.ptr, int(n_strata),
-                                                *_dev_ptrs(RANKSUM_FIELDS, out, ("z",))), "sdice_ranksum_strata_dev")
+        self._resident_row("ranksum_strata", d_ps, (*_with_lengths(d_g1, d_g2), d_strat1, d_strat2, int(n_strata)), out)
 
     def ks_dev(self, d_ps, d_g1, d_g2, out, exact=False):
         """out: the device fields of KS_FIELDS (d optional; exact optional unless exact=True)"""
-        n, s = d_ps.shape
-        optional = ("d", "exact")
-        if any(not out.get(f[0]) for f in KS_FIELDS if f[0] not in optional):
-            raise ValueError("ks_dev: every field of KS_FIELDS but d and exact is required")
-        check(self.lib.sdice_ks_dev(self.h, n, s, d_ps.ptr, d_g1.ptr, d_g1.shape[0], d_g2.ptr, d_g2.shape[0],
-                                    int(bool(exact)), *_dev_ptrs(KS_FIELDS, out, optional)), "sdice_ks_dev")
+        self._resident_row("ks", d_ps, (*_with_lengths(d_g1, d_g2), int(bool(exact))), out, optional=("d",) if exact else None)
 
-    def shift_resident(self, d_ps, d_g1, d_g2, out, conf=0.95):
-        """sdice_shift_dev: shift() on a resident table and resident lists; out: the device fields of SHIFT_FIELDS, all of
-        them.  (Not named *_dev: tests/test_call_order_fixtures_cpu.py wants every method of that name in the catalogue of
-        tests/call_order_fixtures.py; this call has its own, tests/test_gpu_shift_call_order.py.)"""
-        n, s = d_ps.shape
-        if any(not out.get(f[0]) for f in SHIFT_FIELDS):
-            raise ValueError("shift_resident: every field of SHIFT_FIELDS is required")
-        check(self.lib.sdice_shift_dev(self.h, n, s, d_ps.ptr, d_g1.ptr, d_g1.shape[0], d_g2.ptr, d_g2.shape[0],
-                                       shift_quantile(conf), *_dev_ptrs(SHIFT_FIELDS, out)), "sdice_shift_dev")
+    def shift_dev(self, d_ps, d_g1, d_g2, out, conf=0.95):
+        """shift() on a resident table and resident lists; out: the device fields of SHIFT_FIELDS, all of them"""
+        self._resident_row("shift", d_ps, (*_with_lengths(d_g1, d_g2), shift_quantile(conf)), out)
 
     def signedrank_dev(self, d_ps, d_a, d_b, out):
-        n, s = d_ps.shape
-        check(self.lib.sdice_signedrank_dev(self.h, n, s, d_ps.ptr, d_a.ptr, d_b.ptr, d_a.shape[0],
-                                            *_dev_ptrs(RANKSUM_FIELDS, out, ("z",))), "sdice_signedrank_dev")
+        self._resident_row("signedrank", d_ps, (d_a, d_b, d_a.shape[0]), out)
 
     def ranksum_exact_dev(self, d_ps, d_g1, d_g2, out):
         """out: the device fields of RANKSUM_EXACT_FIELDS (z optional)"""
-        n, s = d_ps.shape
-        check(self.lib.sdice_ranksum_exact_dev(self.h, n, s, d_ps.ptr, d_g1.ptr, d_g1.shape[0], d_g2.ptr, d_g2.shape[0],
-                                               *_dev_ptrs(RANKSUM_EXACT_FIELDS, out, ("z",))), "sdice_ranksum_exact_dev")
+        self._resident_row("ranksum_exact", d_ps, _with_lengths(d_g1, d_g2), out)
 
     def signedrank_exact_dev(self, d_ps, d_a, d_b, out):
-        n, s = d_ps.shape
-        check(self.lib.sdice_signedrank_exact_dev(self.h, n, s, d_ps.ptr, d_a.ptr, d_b.ptr, d_a.shape[0],
-                                                  *_dev_ptrs(RANKSUM_EXACT_FIELDS, out, ("z",))), "sdice_signedrank_exact_dev")
+        self._resident_row("signedrank_exact", d_ps, (d_a, d_b, d_a.shape[0]), out)
 
     def spearman_dev(self, d_ps, d_cols, d_xg, out):
         """d_cols, d_xg: the device copies of spearman_order()'s pair; out: device tested, p, (rho), n_kept, med, mean"""
-        n, s = d_ps.shape
-        check(self.lib.sdice_spearman_dev(self.h, n, s, d_ps.ptr, d_cols.ptr, d_xg.ptr, d_cols.shape[0],
-                                          *_dev_ptrs(SPEARMAN_FIELDS, out, ("rho",))), "sdice_spearman_dev")
+        self._resident_row("spearman", d_ps, (d_cols, d_xg, d_cols.shape[0]), out)
 
     def sample_gram_dev(self, d_ps, d_cols, out):
         """d_cols: the device copy of gram_columns(); out: device shared, sum1, sum2, prod, int64 [m, m] each.  Synchronises
         once (the bad-value check of the pre-pass); the sums are queued."""
-        n, s = d_ps.shape
-        check(self.lib.sdice_sample_gram_dev(self.h, n, s, d_ps.ptr, d_cols.ptr, d_cols.shape[0],
-                                             *_dev_ptrs(GRAM_FIELDS, out)), "sdice_sample_gram_dev")
+        self._resident_row("sample_gram", d_ps, (d_cols, d_cols.shape[0]), out)
+
+    def _resident_sets(self, name, d_ps, d_cols, set_ptr, out):
+        """_resident_row over k column sets: the device copy of kruskal_sets()'s cols and its HOST offsets"""
+        set_ptr = _c(set_ptr, np.int32)
+        self._resident_row(name, d_ps, (d_cols, set_ptr, set_ptr.size - 1), out)
 
     def kruskal_dev(self, d_ps, d_cols, set_ptr, out):
         """d_cols: the device copy of kruskal_sets()'s cols; set_ptr: its HOST offsets; out: device tested, p, (h), med and
         mean [k, n], delta"""
-        n, s = d_ps.shape
-        set_ptr = _c(set_ptr, np.int32)
-        check(self.lib.sdice_kruskal_dev(self.h, n, s, d_ps.ptr, d_cols.ptr, _ptr(set_ptr), set_ptr.size - 1,
-                                         *_dev_ptrs(KRUSKAL_FIELDS, out, ("h",))), "sdice_kruskal_dev")
+        self._resident_sets("kruskal", d_ps, d_cols, set_ptr, out)
 
-    def kruskal_dunn_resident(self, d_ps, d_cols, set_ptr, out):
-        """sdice_kruskal_dunn_dev: kruskal_dunn() on a resident table; d_cols and set_ptr as kruskal_dev takes them; out: the
-        device fields of KRUSKAL_DUNN_FIELDS, h, pair_p and pair_padj optional, the pair fields [k (k - 1) / 2, n].  (Not
-        named *_dev: tests/test_call_order_fixtures_cpu.py wants every method of that name in the catalogue of
-        tests/call_order_fixtures.py; this call has its own, tests/test_gpu_dunn_call_order.py.)"""
-        n, s = d_ps.shape
-        set_ptr = _c(set_ptr, np.int32)
-        check(self.lib.sdice_kruskal_dunn_dev(self.h, n, s, d_ps.ptr, d_cols.ptr, _ptr(set_ptr), set_ptr.size - 1,
-                                              *_dev_ptrs(KRUSKAL_DUNN_FIELDS, out, ("h", "pair_p", "pair_padj"))),
-              "sdice_kruskal_dunn_dev")
+    def kruskal_dunn_dev(self, d_ps, d_cols, set_ptr, out):
+        """kruskal_dunn() on a resident table; d_cols and set_ptr as kruskal_dev takes them; out: the device fields of
+        KRUSKAL_DUNN_FIELDS, h, pair_p and pair_padj optional, the pair fields [k (k - 1) / 2, n]"""
+        self._resident_sets("kruskal_dunn", d_ps, d_cols, set_ptr, out)
 
     def jonckheere_dev(self, d_ps, d_cols, set_ptr, out):
         """d_cols: the device copy of kruskal_sets()'s cols; set_ptr: its HOST offsets; out: device tested, p, z, (j), med and
         mean [k, n], delta"""
-        n, s = d_ps.shape
-        set_ptr = _c(set_ptr, np.int32)
-        check(self.lib.sdice_jonckheere_dev(self.h, n, s, d_ps.ptr, d_cols.ptr, _ptr(set_ptr), set_ptr.size - 1,
-                                            *_dev_ptrs(JONCKHEERE_FIELDS, out, ("j",))), "sdice_jonckheere_dev")
+        self._resident_sets("jonckheere", d_ps, d_cols, set_ptr, out)
 
     def pair_table(self, s, pairs):
         """a pair list for the _dev calls: checked against s samples, packed and uploaded once -> DeviceArray uint32[m]

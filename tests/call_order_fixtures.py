@@ -28,6 +28,8 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import cluster_sort_fixtures as FX  # noqa: E402
+import dunn_fixtures as DF  # noqa: E402
+import dunn_referee as DR  # noqa: E402
 import exact_referee as ER  # noqa: E402
 import jonckheere_referee as JR  # noqa: E402
 import kruskal_referee as KR  # noqa: E402
@@ -37,14 +39,16 @@ import pair_fixtures as PF  # noqa: E402
 import rank_support as RS  # noqa: E402
 import sample_matrix_referee as SM  # noqa: E402
 import scoring_referee as SC  # noqa: E402
+import shift_referee as SH  # noqa: E402
 import signedrank_referee as SR  # noqa: E402
 import spearman_referee as SP  # noqa: E402
 import strata_referee as VR  # noqa: E402
 from bh_fixtures import bh_columns_values, bh_values  # noqa: E402
 from oracle import oracle_np as O  # noqa: E402
 from splicedice_amd import synth  # noqa: E402
-from splicedice_amd.engine import (GRAM_FIELDS, JONCKHEERE_FIELDS, KRUSKAL_FIELDS, KS_FIELDS, RANKSUM_EXACT_FIELDS,  # noqa: E402
-                                   RANKSUM_FIELDS, SPEARMAN_FIELDS, field_shapes, kruskal_sets, spearman_order)
+from splicedice_amd.engine import (GRAM_FIELDS, JONCKHEERE_FIELDS, KRUSKAL_DUNN_FIELDS, KRUSKAL_FIELDS, KS_FIELDS,  # noqa: E402
+                                   RANKSUM_EXACT_FIELDS, RANKSUM_FIELDS, SHIFT_FIELDS, SPEARMAN_FIELDS, field_shapes,
+                                   kruskal_sets, spearman_order)
 
 FILL = 0x5A
 F32 = ("med1", "med2", "mean1", "mean2", "delta")
@@ -481,6 +485,12 @@ _rows("ks exact", None, KS_FIELDS, (), lambda x: KS.table_reference(x["ps"], G1,
       run=functools.partial(_run_ks, True))
 
 
+SHIFT_CONF = 0.95      # (the default of shift_dev, which the case leaves in force)
+# (bit for bit on every field of shift_referee.OUTS, as test_gpu_shift.py:30, check, holds them)
+_rows("shift", "shift_dev", SHIFT_FIELDS, (G1, G2), lambda x: SH.table_reference(x["ps"], G1, G2, SH.zq_of(SHIFT_CONF)),
+      lambda got, want, label: _same(got, want, label, SH.OUTS))
+
+
 def _run_sets(entry, fields, ctx, x):
     cols, set_ptr = kruskal_sets(SETS, ROW_COLS)
     d_ps, d_cols = ctx.to_device(x["ps"]), ctx.to_device(cols)
@@ -520,6 +530,27 @@ _rows("kruskal", None, KRUSKAL_FIELDS, (), lambda x: KR.table_reference(x["ps"],
       run=functools.partial(_run_sets, "kruskal_dev", KRUSKAL_FIELDS))
 _rows("jonckheere", None, JONCKHEERE_FIELDS, (), lambda x: JR.table_reference(x["ps"], SETS, False), _check_jonckheere,
       run=functools.partial(_run_sets, "jonckheere_dev", JONCKHEERE_FIELDS))
+
+
+def _want_dunn(x):
+    """dunn_referee.table_reference, its per-row list `exact` (mpmath numbers and Fractions, for dunn_referee.close_pairs) as
+    an object vector: a reference is arrays throughout"""
+    want = DR.table_reference(x["ps"], SETS, False)
+    exact = np.empty(ROWS, dtype=object)
+    for r, e in enumerate(want["exact"]):
+        exact[r] = e
+    return dict(want, exact=exact)
+
+
+def _check_dunn(got, ref, label):
+    """test_gpu_dunn.py:34 (check): the Kruskal-Wallis fields by the bars of the kruskal case, the pair fields by
+    dunn_fixtures.check_pairs"""
+    _check_kruskal(got, ref, label)
+    DF.check_pairs(got, ref, label)
+
+
+_rows("kruskal_dunn", None, KRUSKAL_DUNN_FIELDS, (), _want_dunn, _check_dunn,
+      run=functools.partial(_run_sets, "kruskal_dunn_dev", KRUSKAL_DUNN_FIELDS))
 
 
 def _run_spearman(ctx, x):

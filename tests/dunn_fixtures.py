@@ -5,13 +5,16 @@ checks on the CPU that no fixture row has two pair p-values that only a rounding
 A fixture is (ps float32 [n, s], sets, label); FIXTURES maps a name to its maker, reference(name) to the referee's table
 (dense-rank keys, which serve rows on and off the 3-decimal grid alike).  FLAVOURS: `grid` rows take the histogram kernel,
 `off` rows (the same rows through rank_support.twin's map: same order, same ties) the sorting kernel, `mixed` interleaves the
-two, so the sorting kernel takes KW_REDO rows among grid rows."""
+two, so the sorting kernel takes KW_REDO rows among grid rows.
+
+check_pairs holds the pair outputs of a call to the bars of tests/test_gpu_dunn.py (its docstring) against such a reference."""
 import functools
 
 import numpy as np
 
 import dunn_referee as DR
 import kset_fixtures as KF
+import rank_support as RS
 from rank_support import twin
 
 FLAVOURS = ("grid", "off", "mixed")
@@ -19,6 +22,46 @@ KS = (2, 3, 4, 5, 10, 11)                      # m = 1, 3, 6, 10, 45, 55 pairs: 
 SHAPES = ("uniform", "shifted", "ties", "cluster")
 TOTALS = tuple(range(9, 67)) + (127, 128, 129)
 FIXTURES = {}
+Z_ROUNDINGS = 1
+PAIR = ("pair_z", "pair_p", "pair_padj")
+
+
+def ulps(a, b):
+    """the distance of two float64 arrays of one sign pattern in units of the last place"""
+    return np.abs(np.ascontiguousarray(a).view(np.int64) - np.ascontiguousarray(b).view(np.int64))
+
+
+def check_pairs(got, ref, label):
+    """the bars of the pair outputs on every row -> (tested rows, worst z distance in ulps, cells below the p floor)"""
+    assert np.array_equal(got["tested"], ref["tested"]), (label, "tested")
+    t = ref["tested"].astype(bool)
+    m = ref["pair_z"].shape[0]
+    for name in PAIR:
+        if name in got:
+            assert got[name].dtype == np.float64 and got[name].shape == (m, t.size), (label, name)
+            assert not RS.bits(got[name][:, ~t]).any(), (label, name, "a pair slot of a row that is not tested")
+    z, zr = got["pair_z"][:, t], ref["pair_z"][:, t]
+    zero = ref["zero_num"][:, t]
+    assert np.all(zr[zero] == 0) and np.all(zr[~zero] != 0)
+    assert np.all(z[zero] == 0), (label, "z where the referee's is 0")
+    assert np.array_equal(np.signbit(z[~zero]), np.signbit(zr[~zero])), (label, "sign of z")
+    dist = ulps(z[~zero], zr[~zero])
+    worst = int(dist.max()) if dist.size else 0
+    print(f"{label}: rows {t.size} tested {int(t.sum())} pairs {m} worst z distance {worst} ulp largest |z| "
+          f"{np.abs(zr).max() if zr.size else 0:.3g}", end=" ")
+    assert worst <= Z_ROUNDINGS <= 8, (label, "z", worst)
+    below = 0
+    for name in ("pair_p", "pair_padj"):
+        if name in got:
+            below += RS.check_p(got[name][:, t].ravel(), ref[name][:, t].ravel(), (label, name))[0]
+    if "pair_p" in got and "pair_padj" in got:
+        p, padj = got["pair_p"][:, t], got["pair_padj"][:, t]
+        assert np.all(padj >= p) and np.all(padj <= 1.0), (label, "padj against p and 1")
+        first = np.argmin(p, axis=0)
+        at = np.arange(p.shape[1])
+        assert np.array_equal(padj[first, at], np.minimum(1.0, m * p[first, at])), (label, "padj of the smallest p")
+        assert np.all(p[zero] == 1.0), (label, "p where z is 0")
+    return int(t.sum()), worst, below
 
 
 def _flavoured(grid_rows, sets, flavour):

@@ -9,8 +9,11 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import call_order_fixtures as CF  # noqa: E402
 import cluster_referee as CR  # noqa: E402
+import dunn_fixtures as DF  # noqa: E402
+import dunn_referee as DR  # noqa: E402
 import large_path_fixtures as LP  # noqa: E402
 import rank_support as RS  # noqa: E402
+import shift_referee as SH  # noqa: E402
 from splicedice_amd import engine  # noqa: E402
 
 
@@ -23,10 +26,10 @@ def test_case_has_a_reference_that_says_something(name):
         assert v.size > 0, field
         if v.dtype == np.uint8 and field not in case.constant:          # a boolean output takes both values
             assert set(np.unique(v).tolist()) == {0, 1}, (name, field)
-    # no output whose reference an all-zero array would satisfy (kruskal's h is the referee's hf)
+    # no output whose reference an all-zero array would satisfy (the h of kruskal and kruskal_dunn is the referee's hf)
     for field in case.outputs:
         if field not in case.constant:
-            assert np.any(want["hf" if name == "kruskal" and field == "h" else field] != 0), (name, field)
+            assert np.any(want["hf" if name in ("kruskal", "kruskal_dunn") and field == "h" else field] != 0), (name, field)
     assert case.want is want and case.inputs is case.inputs               # computed once, shared
 
 
@@ -116,8 +119,8 @@ def test_row_table_drives_both_kernels_of_every_test():
     grid_rows = RS.on_grid(ps).all(axis=1)
     some = ~np.isnan(ps).all(axis=1)
     assert (grid_rows & some).sum() > 100 and (~grid_rows).sum() >= 30
-    for name in ("ranksum", "ranksum_strata", "ranksum_exact", "signedrank", "signedrank_exact", "ks", "ks exact", "kruskal",
-                 "jonckheere", "spearman"):
+    for name in ("ranksum", "ranksum_strata", "ranksum_exact", "signedrank", "signedrank_exact", "ks", "ks exact", "shift",
+                 "kruskal", "kruskal_dunn", "jonckheere", "spearman"):
         t = CF.CASES[name].want["tested"].astype(bool)
         assert (t & grid_rows).sum() >= 50 and (t & ~grid_rows).sum() >= 15 and (~t).sum() >= 10, name
     assert len(CF.SETS) == 3 and np.unique(np.concatenate(CF.SETS)).size == sum(g.size for g in CF.SETS)
@@ -131,3 +134,21 @@ def test_row_table_drives_both_kernels_of_every_test():
     assert not CF.CASES["ks"].want["exact"].any()
     cols, x = CF.spearman_design()
     assert np.unique(cols).size == 30 and np.unique(x).size < 30
+
+
+def test_shift_and_dunn_cases_hang_on_no_rounding():
+    """shift: more than 10 distinct ranks among the tested rows, each far from a rounding, tested rows on the grid and off it,
+    no NaN triple (the table keeps no infinity); Dunn: no Holm order of a row hangs on a rounding, no pair output all zero
+    or NaN, and padj reaches 1 and falls below 0.05"""
+    want = CF.CASES["shift"].want
+    t = want["tested"].astype(bool)
+    assert all(not np.isnan(want[name]).any() for name in SH.OUTS)
+    assert want["grid"][t].any() and not want["grid"][t].all()
+    assert np.unique(want["rank"][t]).size > 10
+    for n1, n2 in {(int(a), int(b)) for a, b in zip(want["n1"][t], want["n2"][t])}:
+        assert SH.rank_and_margin(n1, n2, SH.zq_of(CF.SHIFT_CONF))[1] >= 1e-6, (n1, n2)
+    want = CF.CASES["kruskal_dunn"].want
+    t = want["tested"].astype(bool)
+    assert all(np.any(want[name] != 0) and not np.isnan(want[name]).any() for name in DF.PAIR)
+    assert DR.close_pairs(want, 1e-6) == []
+    assert (want["pair_padj"][:, t] == 1.0).any() and (want["pair_padj"][:, t] < 0.05).any()

@@ -265,7 +265,7 @@ def test_engine_field_table_and_pair_order():
     assert engine.field_shapes(engine.KRUSKAL_DUNN_FIELDS, 7, 11)["pair_padj"][0] == (55, 7)
     assert engine.dunn_pairs(4) == [(0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3)] == DR.pairs(4)
     assert engine.dunn_pairs(2) == [(0, 1)] and len(engine.dunn_pairs(11)) == 55
-    assert hasattr(engine.Context, "kruskal_dunn") and hasattr(engine.Context, "kruskal_dunn_resident")
+    assert hasattr(engine.Context, "kruskal_dunn") and hasattr(engine.Context, "kruskal_dunn_dev")
 
 
 def test_posthoc_flag_default_and_parse():

@@ -4,9 +4,10 @@ rounded from them, p and Holm's step-down from mpmath at 50 digits) and against 
 
 Bars, on every row of every fixture:
   tested, p, h, med, mean, delta   sdice_kruskal's on the same input, bit for bit
-  pair_z                           within Z_ROUNDINGS ulps of the referee's correctly rounded z -- the rounding count that the
-                                   header of csrc/kruskal.hip states for its z form (tests/test_dunn_cpu.py reads it there), and
-                                   never more than 8; exactly +-0 where the referee's z is 0
+  pair_z                           within Z_ROUNDINGS ulps (tests/dunn_fixtures.py) of the referee's correctly rounded z -- the
+                                   rounding count that the header of csrc/kruskal.hip states for its z form
+                                   (tests/test_dunn_cpu.py reads it there), and never more than 8; exactly +-0 where the
+                                   referee's z is 0
   pair_p, pair_padj                within 1e-9 relative of the referee where that is >= 1e-280, below 2e-280 under it
   pair_padj                        >= pair_p, <= 1, and exactly min(1, m * p) in float64 for the row's smallest p
   a row that is not tested         0 in every pair slot
@@ -22,52 +23,13 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dunn_fixtures as DF  # noqa: E402
 import dunn_referee as DR  # noqa: E402
 import rank_support as RS  # noqa: E402
+from dunn_fixtures import PAIR, check_pairs  # noqa: E402
 from oracle import oracle_np as O  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-Z_ROUNDINGS = 1
 K12 = ("tested", "p", "h", "med", "mean", "delta")
-PAIR = ("pair_z", "pair_p", "pair_padj")
 H_RTOL = 1e-12
-
-
-def ulps(a, b):
-    """the distance of two float64 arrays of one sign pattern in units of the last place"""
-    return np.abs(np.ascontiguousarray(a).view(np.int64) - np.ascontiguousarray(b).view(np.int64))
-
-
-def check_pairs(got, ref, label):
-    """the bars of the pair outputs on every row -> (tested rows, worst z distance in ulps, cells below the p floor)"""
-    assert np.array_equal(got["tested"], ref["tested"]), (label, "tested")
-    t = ref["tested"].astype(bool)
-    m = ref["pair_z"].shape[0]
-    for name in PAIR:
-        if name in got:
-            assert got[name].dtype == np.float64 and got[name].shape == (m, t.size), (label, name)
-            assert not RS.bits(got[name][:, ~t]).any(), (label, name, "a pair slot of a row that is not tested")
-    z, zr = got["pair_z"][:, t], ref["pair_z"][:, t]
-    zero = ref["zero_num"][:, t]
-    assert np.all(zr[zero] == 0) and np.all(zr[~zero] != 0)
-    assert np.all(z[zero] == 0), (label, "z where the referee's is 0")
-    assert np.array_equal(np.signbit(z[~zero]), np.signbit(zr[~zero])), (label, "sign of z")
-    dist = ulps(z[~zero], zr[~zero])
-    worst = int(dist.max()) if dist.size else 0
-    print(f"{label}: rows {t.size} tested {int(t.sum())} pairs {m} worst z distance {worst} ulp largest |z| "
-          f"{np.abs(zr).max() if zr.size else 0:.3g}", end=" ")
-    assert worst <= Z_ROUNDINGS <= 8, (label, "z", worst)
-    below = 0
-    for name in ("pair_p", "pair_padj"):
-        if name in got:
-            below += RS.check_p(got[name][:, t].ravel(), ref[name][:, t].ravel(), (label, name))[0]
-    if "pair_p" in got and "pair_padj" in got:
-        p, padj = got["pair_p"][:, t], got["pair_padj"][:, t]
-        assert np.all(padj >= p) and np.all(padj <= 1.0), (label, "padj against p and 1")
-        first = np.argmin(p, axis=0)
-        at = np.arange(p.shape[1])
-        assert np.array_equal(padj[first, at], np.minimum(1.0, m * p[first, at])), (label, "padj of the smallest p")
-        assert np.all(p[zero] == 1.0), (label, "p where z is 0")
-    return int(t.sum()), worst, below
 
 
 def check(ctx, ps, sets, ref, label):
@@ -174,7 +136,7 @@ def test_twelve_sets_and_a_null_pair_z_are_refused_by_both_entry_points(ctx):
             assert rc == -1 and b"NULL output" in ctx.lib.sdice_last_error()
         else:
             with pytest.raises(SdiceError):
-                ctx.kruskal_dunn_resident(d_ps, d_cols, set_ptr, handed)
+                ctx.kruskal_dunn_dev(d_ps, d_cols, set_ptr, handed)
         for name, d in out.items():
             assert np.all(d.to_host().view(np.uint8) == 0x5A), (len(sets), name)
             d.free()

@@ -57,7 +57,7 @@ def test_rows_per_wave(ctx, ch):
             out = {name: ctx.empty(shape, dtype).memset(0x5A) for name, (shape, dtype) in
                    field_shapes(KRUSKAL_DUNN_FIELDS, n, 3).items() if name not in absent}
             try:
-                ctx.kruskal_dunn_resident(d_ps, d_cols, set_ptr, out)
+                ctx.kruskal_dunn_dev(d_ps, d_cols, set_ptr, out)
                 for name, d in out.items():
                     RS.assert_same_bits(d.to_host(), got[name], ("sdice_kruskal_dunn_dev without", absent, name))
             finally:

@@ -53,7 +53,7 @@ def dev_call(ctx, d_ps, g1, g2, n, conf=0.95):
     held = [ctx.to_device(v, np.int32) for v in (g1, g2)]
     out = {name: ctx.empty(*sd).memset(0xA5) for name, sd in field_shapes(SHIFT_FIELDS, n).items()}
     try:
-        ctx.shift_resident(d_ps, *held, out, conf)
+        ctx.shift_dev(d_ps, *held, out, conf)
         ctx.sync()
         return {name: a.to_host() for name, a in out.items()}
     finally:

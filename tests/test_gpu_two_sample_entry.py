@@ -149,7 +149,7 @@ def _shift(n1, n2, ctx, n):
     g1, g2 = lists_of("shift", n1, n2, 0)
     host = ctx.shift(ps, g1, g2)
     held, out = _on_device(ctx, [ps, g1, g2], field_shapes(SHIFT_FIELDS, n))
-    ctx.shift_resident(*held, out)
+    ctx.shift_dev(*held, out)
     return host, out, held
 
 

@@ -365,7 +365,7 @@ def test_abi_of_the_two_calls():
         assert "double zq" in proto.group(1)
     assert [f[0] for f in SHIFT_FIELDS] == [name for name, _ in SR.FIELDS] == list(SR.OUTS)
     assert [np.dtype(f[1]) for f in SHIFT_FIELDS] == [np.dtype(dt) for _, dt in SR.FIELDS]
-    assert callable(Context.shift) and callable(Context.shift_resident)
+    assert callable(Context.shift) and callable(Context.shift_dev)
     assert shift_quantile(0.95) == SR.zq_of(0.95) and abs(shift_quantile(0.95) - ZQ95) <= 4.5e-16
     for bad in (0.0, 1.0, -1.0, 2.0, float("nan")):
         with pytest.raises(ValueError):

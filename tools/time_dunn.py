@@ -13,7 +13,7 @@ median of `reps`.
    with this build's (each child: every shape, its own table upload, its own warm-up).  Per shape the record holds every
    child's median, the median of those per build, and the parent's spread: the largest minus the smallest of the
    PARENT's own medians over its rounds -- the yardstick a difference between the builds has to exceed to mean anything.
-2. In this process: kruskal_dev, then kruskal_dunn_resident with every output, with pair_p absent (NULL), with pair_padj
+2. In this process: kruskal_dev, then kruskal_dunn_dev with every output, with pair_p absent (NULL), with pair_padj
    absent and with both absent, on the same resident table; the extra bytes written per row (8 m with z alone, 24 m with
    all three) beside the extra time.  `every output` minus `pair_p NULL` is the cost of m 8-byte stores per row and
    nothing else (p is computed for padj either way); `pair_p NULL` minus both NULL is erfc, Holm and the padj stores.
@@ -116,8 +116,8 @@ def main():
                                        ("pair_padj NULL", ("pair_padj",), 16 * m),
                                        ("pair_p and pair_padj NULL", ("pair_p", "pair_padj"), 8 * m)):
             handed = {x: d for x, d in out.items() if x not in absent}
-            med, lo, hi = timed(ctx, lambda: ctx.kruskal_dunn_resident(d_ps, d_cols, set_ptr, handed), args.reps)
-            results.append(dict(call="kruskal_dunn_resident, " + label, rows=ROWS, sets=k, set_size=size, pairs=m, reps=args.reps,
+            med, lo, hi = timed(ctx, lambda: ctx.kruskal_dunn_dev(d_ps, d_cols, set_ptr, handed), args.reps)
+            results.append(dict(call="kruskal_dunn_dev, " + label, rows=ROWS, sets=k, set_size=size, pairs=m, reps=args.reps,
                                 median_ms=med, min_ms=lo, max_ms=hi, ratio_to_kruskal=med / base[0], extra_ms=med - base[0],
                                 extra_bytes_per_row=per_row, extra_bytes_over_table_bytes=per_row * ROWS / table_bytes,
                                 tested_rows=int(out["tested"].to_host().sum())))

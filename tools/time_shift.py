@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time shift_resident (sdice_shift_dev: the Hodges-Lehmann shift with its confidence interval) beside ranksum_dev
+"""Time shift_dev (sdice_shift_dev: the Hodges-Lehmann shift with its confidence interval) beside ranksum_dev
 reading the same table, in one process:
 
     python tools/time_shift.py [--reps 21] [--out profiles/shift_times.json]
@@ -33,7 +33,7 @@ for n, m, blk in ((1_000_000, 8, 25_000), (1_000_000, 50, 25_000), (1_000_000, 5
         out = {x: ctx.empty(*sd) for x, sd in field_shapes(SHIFT_FIELDS, n).items()}
         row = dict(rows=n, samples=s, group=m, values="3-decimal" if grid else "off the grid", reps=args.reps)
         calls = dict(ranksum_dev=(lambda: ctx.ranksum_dev(d_ps, d_g1, d_g2, plain), plain),
-                     shift_dev=(lambda: ctx.shift_resident(d_ps, d_g1, d_g2, out), out))
+                     shift_dev=(lambda: ctx.shift_dev(d_ps, d_g1, d_g2, out), out))
         for name, (call, fields) in calls.items():
             med, lo, hi = timed(ctx, call, args.reps)
             row[name] = dict(median_ms=med, min_ms=lo, max_ms=hi, tested_rows=int(fields["tested"].to_host().sum()),
