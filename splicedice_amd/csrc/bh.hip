@@ -15,6 +15,7 @@
 // pass over the transposed table instead of one sort per column.
 #include "common.h"
 #include "bh.h"
+#include "wave.h"
 #include <algorithm>
 
 namespace {
@@ -124,18 +125,14 @@ __global__ void __launch_bounds__(256) seg_minscan_kernel(const uint64_t* __rest
         uint64_t x = v[7];
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
-            unsigned lo = (unsigned)(x & 0xffffffffu), hi = (unsigned)(x >> 32);
-            lo = __shfl_up(lo, o); hi = __shfl_up(hi, o);
-            const uint64_t y = ((uint64_t)hi << 32) | lo;
+            const uint64_t y = shfl_up_u64(x, o);
             if (lane >= o) x = y < x ? y : x;
         }
         if (lane == 63) wmin[w] = x;
         __syncthreads();
         uint64_t pre = carry_s;
         for (int k = 0; k < w; ++k) pre = wmin[k] < pre ? wmin[k] : pre;
-        unsigned lo = (unsigned)(x & 0xffffffffu), hi = (unsigned)(x >> 32);
-        lo = __shfl_up(lo, 1); hi = __shfl_up(hi, 1);
-        uint64_t prev = ((uint64_t)hi << 32) | lo;       // inclusive minimum of the lanes before this one
+        uint64_t prev = shfl_up_u64(x, 1);               // inclusive minimum of the lanes before this one
         if (lane == 0) prev = ~0ull;
         const uint64_t tpre = prev < pre ? prev : pre;
 #pragma unroll

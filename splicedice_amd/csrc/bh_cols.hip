@@ -29,8 +29,8 @@
 // algorithmic traffic per value; bit-identical to the generic path.
 #include "common.h"
 #include "bh.h"
+#include "wave.h"
 #include <algorithm>
-#include <stdio.h>
 
 namespace {
 
@@ -72,18 +72,98 @@ __device__ __forceinline__ unsigned hash32(unsigned x) {
     return x;
 }
 
-// c += (ka, ia) < (kb, ib) in composite order: the borrow of the 96-bit subtraction, added with carry -- four VALU
-// instructions (the compiler turns "ka < kb || (ka == kb && ia < ib)", and __builtin_subc chains too, into five compares
-// and their mask arithmetic)
-__device__ __forceinline__ void count_less96(unsigned& c, uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib) {
-    unsigned t;
-    asm("v_sub_co_u32 %0, vcc, %2, %3\n\t"
-        "v_subb_co_u32 %0, vcc, %4, %5, vcc\n\t"
-        "v_subb_co_u32 %0, vcc, %6, %7, vcc\n\t"
-        "v_addc_co_u32 %1, vcc, 0, %1, vcc"
-        : "=&v"(t), "+v"(c)
-        : "v"(ia), "v"(ib), "v"((unsigned)ka), "v"((unsigned)kb), "v"((unsigned)(ka >> 32)), "v"((unsigned)(kb >> 32))
-        : "vcc");
+// ---- steps of a workgroup of 64-lane waves (lane = tid & 63, wave = tid >> 6); the steps inside one wave: wave.h
+// exclusive prefix sum of v over the workgroup's threads; wtot[wave] holds each wave's total afterwards.  One barrier.
+__device__ __forceinline__ unsigned wg_excl_scan(unsigned v, unsigned* wtot, int lane, int wave) {
+    const unsigned x = wave_prefix_sum(v, lane);
+    if (lane == 63) wtot[wave] = x;
+    __syncthreads();
+    unsigned pre = x - v;
+    for (int w = 0; w < wave; ++w) pre += wtot[w];
+    return pre;
+}
+// minimum of `run` over the threads BEHIND this one (later lanes, then later waves; ~0 for the last thread) through
+// wred[NW]; `all` is the minimum over the whole workgroup, valid in thread 0.  One barrier.
+template <int NW>
+__device__ __forceinline__ uint64_t wg_later_min_u64(uint64_t run, uint64_t* wred, int lane, int wave, uint64_t& all) {
+    const uint64_t x = wave_suffix_min_u64(run, lane);
+    uint64_t ex = shfl_down_u64(x, 1);
+    if (lane == 63) ex = ~0ull;
+    if (lane == 0) wred[wave] = x;
+    __syncthreads();
+    uint64_t later = ~0ull;
+    for (int w = wave + 1; w < NW; ++w) later = wred[w] < later ? wred[w] : later;
+    all = x < later ? x : later;
+    return ex < later ? ex : later;
+}
+
+// ---- one wave works on n keys in HBM (the slow paths of both pipelines: a bucket beyond what LDS or registers hold)
+// sort ks[0, n) ascending in place, with IDX the indices is[] along with their keys: all-ascending bitonic network
+// (mirror partner in the first step of a merge), so that out-of-range partners count as +inf and never move
+template <bool IDX>
+__device__ void wave_sort_in_hbm(uint64_t* ks, uint32_t* is, int n, int lane) {
+    int P = 1;
+    while (P < n) P <<= 1;
+    for (int k2 = 2; k2 <= P; k2 <<= 1) {
+        for (int j = k2 >> 1; j >= 1; j >>= 1) {
+            for (int q = lane; q < (P >> 1); q += 64) {
+                int i, l;
+                if (j == (k2 >> 1)) {              // first step of a merge: mirror partner
+                    const int blk = q / j, r = q - blk * j;
+                    i = blk * k2 + r;
+                    l = blk * k2 + k2 - 1 - r;
+                } else {
+                    i = ((q & ~(j - 1)) << 1) | (q & (j - 1));
+                    l = i | j;
+                }
+                if (l < n) {
+                    const uint64_t ka = ks[i], kb = ks[l];
+                    if (kb < ka) {
+                        ks[i] = kb; ks[l] = ka;
+                        if (IDX) { const uint32_t ia = is[i], ib = is[l]; is[i] = ib; is[l] = ia; }
+                    }
+                }
+            }
+            __threadfence_block();
+        }
+    }
+}
+// t[p] = min over q >= p of raw(t[q], q), in place: chunks of 64 from the top, the minimum so far carried from chunk to
+// chunk; returns the minimum of all
+template <typename F>
+__device__ __forceinline__ uint64_t wave_suffix_min_in_hbm(uint64_t* t, int n, int lane, F raw) {
+    uint64_t carry = ~0ull;
+    for (int c = (n - 1) / 64; c >= 0; --c) {
+        const int p = c * 64 + lane;
+        uint64_t x = wave_suffix_min_u64(p < n ? raw(t[p], p) : ~0ull, lane);
+        x = carry < x ? carry : x;
+        if (p < n) t[p] = x;
+        carry = bcast_lane0_u64(x);
+    }
+    return carry;
+}
+
+// c += the entries j of [j0, j1) with (K[j], I[j]) below (km, im) in composite order: whole trips of eight reads in
+// flight without bound checks, then one guarded trip (beyond j1: a key above every key)
+__device__ __forceinline__ void count_below8(unsigned& c, const uint64_t* K, const uint32_t* I, int j0, int j1, uint64_t km, uint32_t im) {
+    uint64_t kj[8];
+    uint32_t ij[8];
+    for (; j0 + 8 <= j1; j0 += 8) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { kj[u] = K[j0 + u]; ij[u] = I[j0 + u]; }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) count_less96(c, kj[u], ij[u], km, im);
+    }
+    if (j0 < j1) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const bool in = j0 + u < j1;
+            const int j = min(j0 + u, j1 - 1);
+            kj[u] = in ? K[j] : ~0ull; ij[u] = in ? I[j] : ~0u;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) count_less96(c, kj[u], ij[u], km, im);
+    }
 }
 
 // number of splitters <= (k, i) in composite order
@@ -272,16 +352,7 @@ __global__ void __launch_bounds__(256) bhs_scan_kernel(BhsArgs a) {
         v[q] = b < a.B ? c[b] : 0u;
         s += v[q];
     }
-    unsigned x = s;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[w] = x;
-    __syncthreads();
-    unsigned pre = x - s;
-    for (int k = 0; k < w; ++k) pre += wsum[k];
+    unsigned pre = wg_excl_scan(s, wsum, lane, w);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int b = tid * 4 + q;
@@ -295,20 +366,6 @@ __global__ void __launch_bounds__(256) bhs_scan_kernel(BhsArgs a) {
 }
 
 // ---------------------------------------------------------------- 5. one wave per bucket
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int mask) {
-    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)(v & 0xffffffffu), mask);
-    const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), mask);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t shfl_down_u64(uint64_t v, int d) {
-    const unsigned lo = (unsigned)__shfl_down((int)(unsigned)(v & 0xffffffffu), d);
-    const unsigned hi = (unsigned)__shfl_down((int)(unsigned)(v >> 32), d);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t bcast_lane0_u64(uint64_t v) {
-    return ((uint64_t)(unsigned)__shfl((int)(unsigned)(v >> 32), 0) << 32) | (unsigned)__shfl((int)(unsigned)(v & 0xffffffffu), 0);
-}
-
 __device__ __forceinline__ uint64_t raw_bits(uint64_t key, int64_t rank1, int64_t m) {
     // p_(i) / (i / m), the arithmetic of the generic path (bh.hip bh_raw_kernel)
     const double ps = __longlong_as_double((long long)key);
@@ -327,17 +384,6 @@ __device__ __forceinline__ uint64_t raw_bits_inv(uint64_t key, int rank1, double
     return (uint64_t)__double_as_longlong(ps / ecdf);
 }
 
-__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const uint64_t y = shfl_xor_u64(v, o); v = y < v ? y : v; }
-    return v;
-}
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const uint64_t y = shfl_xor_u64(v, o); v = y > v ? y : v; }
-    return v;
-}
-
 // ---- ranking a bucket by a COUNTING SORT in LDS instead of a comparison network.  The bucket's keys lie between two
 // splitters, so (key - lo) >> sh -- sh the shift that brings the bucket's key range below the number of bins; integer
 // arithmetic on the bit patterns: monotone for ANY input, linear in the value inside a binade -- spreads them over the
@@ -354,36 +400,15 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
 // way: DESIGN.md appendix A.4.)
 
 // rare (adversarial input): more values in one bucket than the widest network holds -- its wave sorts a copy in HBM
-// (all-ascending bitonic network: out-of-range partners count as +inf and never move), ranks the bucket's values by
-// binary search in the copy, turns the copy into suffix minima and puts every value's result into its slot
+// (wave_sort_in_hbm), ranks the bucket's values by binary search in the copy, turns the copy into suffix minima
+// (wave_suffix_min_in_hbm) and puts every value's result into its slot
 __device__ void bucket_in_hbm(const BhsArgs& a, uint64_t* ks, int n_b, unsigned start, int lane, uint64_t* bmin_out) {
     unsigned long long so = 0;
     if (lane == 0) so = atomicAdd(a.spill_n, (unsigned long long)n_b);
     uint64_t* t = a.spill + bcast_lane0_u64(so);
     for (int p = lane; p < n_b; p += 64) t[p] = ks[p];
     __threadfence_block();
-    int P = 1;
-    while (P < n_b) P <<= 1;
-    for (int k2 = 2; k2 <= P; k2 <<= 1) {
-        for (int j = k2 >> 1; j >= 1; j >>= 1) {
-            for (int q = lane; q < (P >> 1); q += 64) {
-                int i, l;
-                if (j == (k2 >> 1)) {              // first step of a merge: mirror partner
-                    const int blk = q / j, r = q - blk * j;
-                    i = blk * k2 + r;
-                    l = blk * k2 + k2 - 1 - r;
-                } else {
-                    i = ((q & ~(j - 1)) << 1) | (q & (j - 1));
-                    l = i | j;
-                }
-                if (l < n_b) {
-                    const uint64_t ka = t[i], kb = t[l];
-                    if (kb < ka) { t[i] = kb; t[l] = ka; }
-                }
-            }
-            __threadfence_block();
-        }
-    }
+    wave_sort_in_hbm<false>(t, nullptr, n_b, lane);
     for (int p = lane; p < n_b; p += 64) {         // rank of value p: lower bound in the sorted copy
         const uint64_t k = ks[p];
         int lo = 0, hi = n_b;
@@ -391,22 +416,10 @@ __device__ void bucket_in_hbm(const BhsArgs& a, uint64_t* ks, int n_b, unsigned 
         ks[p] = (uint64_t)lo;
     }
     __threadfence_block();
-    uint64_t carry = ~0ull;
-    for (int c = (n_b - 1) / 64; c >= 0; --c) {
-        const int p = c * 64 + lane;
-        uint64_t x = p < n_b ? raw_bits(t[p], (int64_t)start + p + 1, a.m) : ~0ull;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint64_t y = shfl_down_u64(x, o);
-            if (lane + o < 64) x = y < x ? y : x;
-        }
-        x = carry < x ? carry : x;
-        if (p < n_b) t[p] = x;
-        carry = bcast_lane0_u64(x);
-    }
+    const uint64_t mn = wave_suffix_min_in_hbm(t, n_b, lane, [&](uint64_t key, int p) { return raw_bits(key, (int64_t)start + p + 1, a.m); });
     __threadfence_block();
     for (int p = lane; p < n_b; p += 64) ks[p] = t[ks[p]];
-    if (lane == 0) *bmin_out = carry;
+    if (lane == 0) *bmin_out = mn;
 }
 
 // what a wave needs to know about bucket g
@@ -533,13 +546,7 @@ __device__ __forceinline__ bool bucket_wg_rank(const BhsArgs& a, const BucketRef
 #pragma unroll
         for (int j = 0; j < 2 * K; ++j) { c[j] = CNT[tid * 2 * K + j]; tot += c[j]; cm = c[j] > cm ? c[j] : cm; }
         if (cm > (unsigned)HEAVY) hv[0] = 1u;
-        unsigned x = tot;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const unsigned y = __shfl_up(x, o); if (lane >= o) x += y; }
-        if (lane == 63) wtot[wave] = x;
-        __syncthreads();
-        unsigned pre = x - tot;
-        for (int w = 0; w < wave; ++w) pre += wtot[w];
+        unsigned pre = wg_excl_scan(tot, wtot, lane, wave);
 #pragma unroll
         for (int j = 0; j < 2 * K; ++j) { CNT[tid * 2 * K + j] = pre; pre += c[j]; }
         if (tid == T - 1) CNT[BINS] = pre;
@@ -651,13 +658,7 @@ __device__ __forceinline__ bool bucket_wg_rank(const BhsArgs& a, const BucketRef
                 unsigned c[K], tot = 0;
 #pragma unroll
                 for (int j = 0; j < K; ++j) { c[j] = SC[tid * K + j]; tot += c[j]; }
-                unsigned x = tot;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) { const unsigned y = __shfl_up(x, o); if (lane >= o) x += y; }
-                if (lane == 63) wtot[wave] = x;
-                __syncthreads();
-                unsigned pre = x - tot;
-                for (int w = 0; w < wave; ++w) pre += wtot[w];
+                unsigned pre = wg_excl_scan(tot, wtot, lane, wave);
 #pragma unroll
                 for (int j = 0; j < K; ++j) { SC[tid * K + j] = pre; pre += c[j]; }
                 if (tid == T - 1) SC[NS] = pre;
@@ -736,22 +737,9 @@ __device__ __forceinline__ bool bucket_wg_rank(const BhsArgs& a, const BucketRef
             run = v < run ? v : run;
             sfx[j] = run;
         }
-        uint64_t x = run;                          // inclusive suffix minimum over the lanes >= this one
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint64_t y = shfl_down_u64(x, o);
-            if (lane + o < 64) x = y < x ? y : x;
-        }
-        uint64_t ex = shfl_down_u64(x, 1);
-        if (lane == 63) ex = ~0ull;
-        if (lane == 0) wred[wave] = x;
-        __syncthreads();
-        for (int w = wave + 1; w < NW; ++w) ex = wred[w] < ex ? wred[w] : ex;     // (minima of the waves behind this one)
-        if (tid == 0) {
-            uint64_t all = wred[0];
-            for (int w = 1; w < NW; ++w) all = wred[w] < all ? wred[w] : all;
-            *r.bm = all;
-        }
+        uint64_t all;
+        const uint64_t ex = wg_later_min_u64<NW>(run, wred, lane, wave, all);
+        if (tid == 0) *r.bm = all;
 #pragma unroll
         for (int j = 0; j < K; ++j)
             if (tid * K + j < n_b) L[tid * K + j] = sfx[j] < ex ? sfx[j] : ex;
@@ -986,17 +974,9 @@ __global__ void __launch_bounds__(256) bhv_rank_kernel(BhvArgs a) {
 __device__ __forceinline__ void bhv_load_splitters(const BhvArgs& a, uint64_t* sk, uint32_t* si, int tid) {
     for (int b = tid; b < a.B - 1; b += BHV_T) { sk[b] = a.spl_k[b]; si[b] = a.spl_i[b]; }
 }
-// exclusive scan of up to 1024 counters held one per thread (BHV_T threads); returns this thread's prefix
-__device__ __forceinline__ unsigned bhv_block_excl_scan(unsigned v, unsigned* wsum /*[16]*/, int tid) {
-    const int lane = tid & 63, w = tid >> 6;
-    unsigned x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const unsigned y = __shfl_up(x, o); if (lane >= o) x += y; }
-    if (lane == 63) wsum[w] = x;
-    __syncthreads();
-    unsigned pre = x - v;
-    for (int k = 0; k < w; ++k) pre += wsum[k];
-    return pre;
+// p m_eff / rank of the entry at rank rank1 (from 1), the generic path's arithmetic; absent entries rank beyond m_eff: +inf
+__device__ __forceinline__ uint64_t bhv_raw_bits(uint64_t key, int64_t rank1, int64_t m_eff) {
+    return rank1 <= m_eff ? raw_bits(key, rank1, m_eff) : 0x7ff0000000000000ull;
 }
 
 // classify a tile against the splitters and move it straight into the buckets' SLOTS of `cap` elements each -- no
@@ -1061,44 +1041,6 @@ __global__ void __launch_bounds__(BHV_T) bhv_scatter_kernel(BhvArgs a) {
     }
 }
 
-// a bucket beyond the LDS capacity (practically never): in-place network in HBM by one wave
-__device__ uint64_t bhv_sub_in_lds(uint64_t* ks, uint32_t* is, int n_s, int64_t rank0, int64_t m_eff, int lane) {
-    int P = 1;
-    while (P < n_s) P <<= 1;
-    for (int k2 = 2; k2 <= P; k2 <<= 1) {
-        for (int j = k2 >> 1; j >= 1; j >>= 1) {
-            for (int t = lane; t < (P >> 1); t += 64) {
-                int i, l;
-                if (j == (k2 >> 1)) { const int blk = t / j, r = t - blk * j; i = blk * k2 + r; l = blk * k2 + k2 - 1 - r; }
-                else { i = ((t & ~(j - 1)) << 1) | (t & (j - 1)); l = i | j; }
-                if (l < n_s) {
-                    const uint64_t ka = ks[i], kb = ks[l];
-                    if (kb < ka) { const uint32_t ia = is[i], ib = is[l]; ks[i] = kb; ks[l] = ka; is[i] = ib; is[l] = ia; }
-                }
-            }
-            __threadfence_block();
-        }
-    }
-    uint64_t carry = ~0ull;
-    for (int c = (n_s - 1) / 64; c >= 0; --c) {
-        const int p = c * 64 + lane;
-        uint64_t x = ~0ull;
-        if (p < n_s) {
-            const int64_t rank1 = rank0 + p + 1;
-            x = rank1 <= m_eff ? raw_bits(ks[p], rank1, m_eff) : 0x7ff0000000000000ull;
-        }
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint64_t y = shfl_down_u64(x, o);
-            if (lane + o < 64) x = y < x ? y : x;
-        }
-        x = carry < x ? carry : x;
-        if (p < n_s) ks[p] = x;
-        carry = ((uint64_t)(unsigned)__shfl((int)(unsigned)(x >> 32), 0) << 32) | (unsigned)__shfl((int)(unsigned)(x & 0xffffffffu), 0);
-    }
-    return carry;
-}
-
 // LDS per value: key (8) + index (4) + sub-bucket (1) -- ONE copy of the bucket: a thread reads its values from HBM into
 // registers, scatters them into sub-bucket order, and after the ranking holds the finished (p m / rank, index, position)
 // in registers across a barrier before it overwrites the same arrays in sorted order.  5632 values = 73 KB, so that TWO
@@ -1138,7 +1080,7 @@ __global__ void __launch_bounds__(BHV_T, 8) bhv_bucket_kernel(BhvArgs a) {
         if (wave == 0) {
             unsigned long long so = 0;
             if (lane == 0) so = atomicAdd(a.spill_n, (unsigned long long)n_b);
-            so = ((unsigned long long)(unsigned)__shfl((int)(unsigned)(so >> 32), 0) << 32) | (unsigned)__shfl((int)(unsigned)(so & 0xffffffffu), 0);
+            so = bcast_lane0_u64(so);
             uint64_t* ks = a.spillK + so; uint32_t* is = a.spillI + so;
             for (int p = lane; p < a.cap; p += 64) { ks[p] = slotK[p]; is[p] = slotI[p]; }
             const long long n_o = (long long)*a.ovf_n;
@@ -1151,7 +1093,8 @@ __global__ void __launch_bounds__(BHV_T, 8) bhv_bucket_kernel(BhvArgs a) {
                 fill += __popcll(mm);
             }
             __threadfence_block();
-            const uint64_t mn = bhv_sub_in_lds(ks, is, n_b, (int64_t)start, m_eff, lane);
+            wave_sort_in_hbm<true>(ks, is, n_b, lane);
+            const uint64_t mn = wave_suffix_min_in_hbm(ks, n_b, lane, [&](uint64_t key, int p) { return bhv_raw_bits(key, (int64_t)start + p + 1, m_eff); });
             __threadfence();
             for (int p = lane; p < n_b; p += 64) { a.qpart[is[p]] = ks[p]; a.bid[is[p]] = (uint16_t)b; }
             if (lane == 0) a.bmin[b] = mn;
@@ -1183,20 +1126,8 @@ __global__ void __launch_bounds__(BHV_T, 8) bhv_bucket_kernel(BhvArgs a) {
         const int per = ns / slices;                                  // samples per slice (a power of two >= 1)
         {
             const int sm = tid & (ns - 1), sl = tid >> nsh;
-            const uint64_t km = samK[sm];
-            const uint32_t im = samI[sm];
             unsigned c = 0;
-            for (int j0 = sl * per; j0 < (sl + 1) * per; j0 += 8) {
-                uint64_t kj[8];
-                uint32_t ij[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) { const int pj = min(j0 + u, ns - 1); kj[u] = samK[pj]; ij[u] = samI[pj]; }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const bool in = j0 + u < (sl + 1) * per;
-                    count_less96(c, in ? kj[u] : ~0ull, in ? ij[u] : ~0u, km, im);
-                }
-            }
+            count_below8(c, samK, samI, sl * per, (sl + 1) * per, samK[sm], samI[sm]);
             if (c) atomicAdd(&srank[sm], c);
         }
         __syncthreads();
@@ -1225,9 +1156,7 @@ __global__ void __launch_bounds__(BHV_T, 8) bhv_bucket_kernel(BhvArgs a) {
             unsigned cq[PER], tot = 0;
 #pragma unroll
             for (int q = 0; q < PER; ++q) { const int sb = lane * PER + q; cq[q] = sb < nsb ? scount[sb] : 0u; tot += cq[q]; }
-            unsigned x = tot;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { const unsigned y = __shfl_up(x, o); if (lane >= o) x += y; }
+            const unsigned x = wave_prefix_sum(tot, lane);
             unsigned pre = x - tot;
 #pragma unroll
             for (int q = 0; q < PER; ++q) { const int sb = lane * PER + q; if (sb < BHV_NSB_MAX) sstart[sb] = pre; pre += cq[q]; }
@@ -1261,30 +1190,9 @@ __global__ void __launch_bounds__(BHV_T, 8) bhv_bucket_kernel(BhvArgs a) {
                 const uint64_t km = K2[d];
                 const uint32_t im = I2[d];
                 unsigned c = 0;
-                int j0 = 0;
-                for (; j0 + 8 <= n_s; j0 += 8) {              // whole trips: eight reads in flight, no bound checks
-                    uint64_t kj[8];
-                    uint32_t ij[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) { kj[u] = K2[s0 + j0 + u]; ij[u] = I2[s0 + j0 + u]; }
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) count_less96(c, kj[u], ij[u], km, im);
-                }
-                if (j0 < n_s) {
-                    uint64_t kj[8];
-                    uint32_t ij[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {             // (beyond the sub-bucket: a key above every key)
-                        const bool in = j0 + u < n_s;
-                        const int j = s0 + min(j0 + u, n_s - 1);
-                        kj[u] = in ? K2[j] : ~0ull; ij[u] = in ? I2[j] : ~0u;
-                    }
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) count_less96(c, kj[u], ij[u], km, im);
-                }
+                count_below8(c, K2, I2, s0, s0 + n_s, km, im);
                 const int pos = s0 + (int)c;
-                const int64_t rank1 = (int64_t)start + pos + 1;
-                ok[q] = rank1 <= m_eff ? raw_bits(km, rank1, m_eff) : 0x7ff0000000000000ull;     // absent entries: +inf
+                ok[q] = bhv_raw_bits(km, (int64_t)start + pos + 1, m_eff);
                 oi[q] = im;
                 op[q] = pos;
             }
@@ -1306,20 +1214,9 @@ __global__ void __launch_bounds__(BHV_T, 8) bhv_bucket_kernel(BhvArgs a) {
             run = r < run ? r : run;
             v[k] = run;
         }
-        uint64_t x = run;                       // inclusive suffix minimum over the lanes >= this one
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint64_t y = shfl_down_u64(x, o);
-            if (lane + o < 64) x = y < x ? y : x;
-        }
-        if (lane == 0) smin[wave] = x;          // (smin: one word per wave here)
-        __syncthreads();
-        uint64_t later = ~0ull;                 // minimum over the waves behind this one
-        for (int w = wave + 1; w < BHV_T / 64; ++w) later = smin[w] < later ? smin[w] : later;
-        uint64_t ex = shfl_down_u64(x, 1);      // ... and over the lanes behind this one
-        if (lane == 63) ex = ~0ull;
-        ex = ex < later ? ex : later;
-        if (tid == 0) a.bmin[b] = x < later ? x : later;
+        uint64_t all;
+        const uint64_t ex = wg_later_min_u64<BHV_T / 64>(run, smin, lane, wave, all);     // (smin: one word per wave here)
+        if (tid == 0) a.bmin[b] = all;
 #pragma unroll
         for (int k = 0; k < BHV_EPT; ++k) {
             const int pos = tid * BHV_EPT + k;
@@ -1337,22 +1234,9 @@ __global__ void __launch_bounds__(BHV_T) bhv_finish_kernel(BhvArgs a) {
     __shared__ uint64_t wmin[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // sfx[b] = minimum of the bucket minima behind b
-    uint64_t x = tid < a.B ? a.bmin[tid] : ~0ull;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t y = shfl_down_u64(x, o);
-        if (lane + o < 64) x = y < x ? y : x;
-    }
-    if (lane == 0) wmin[wave] = x;          // inclusive suffix minimum of the wave's 64 buckets
+    uint64_t all;
+    sfx[tid] = wg_later_min_u64<BHV_T / 64>(tid < a.B ? a.bmin[tid] : ~0ull, wmin, lane, wave, all);
     __syncthreads();
-    uint64_t later_waves = ~0ull;
-    for (int w = wave + 1; w < BHV_T / 64; ++w) later_waves = wmin[w] < later_waves ? wmin[w] : later_waves;
-    uint64_t ex = shfl_down_u64(x, 1);
-    if (lane == 63) ex = ~0ull;
-    sfx[tid] = ex < later_waves ? ex : later_waves;
-    __syncthreads();
-    const int64_t m_eff = (int64_t)*a.m_eff;
-    (void)m_eff;
     const int64_t e0 = (int64_t)blockIdx.x * (BHV_T * BHV_E);
 #pragma unroll
     for (int q = 0; q < BHV_E; ++q) {

@@ -42,6 +42,7 @@
 // dependent PS launch) and the failure is reported then.
 #include "common.h"
 #include "cluster.h"
+#include "wave.h"
 
 // Timing experiments (tools/ablate_cluster.py, param cluster.ablate) are compiled in only with
 // `make EXTRA=-DSDICE_CLUSTER_ABLATE=1`; the shipped kernels carry no trace of them.
@@ -101,19 +102,7 @@ __device__ __forceinline__ uint64_t sample_key(const FastArgs& a, int64_t i) {
     return ((uint64_t)(uint32_t)a.chrom[p] << 32) | (uint64_t)(uint32_t)a.left[p];
 }
 
-// c += (ka, ia) < (kb, ib) in composite order: the borrow of the 96-bit subtraction, added with carry (four VALU
-// instructions; the compiler makes five compares and their mask arithmetic of the || / && form)
-__device__ __forceinline__ void count_less96(unsigned& c, uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib) {
-    unsigned t;
-    asm("v_sub_co_u32 %0, vcc, %2, %3\n\t"
-        "v_subb_co_u32 %0, vcc, %4, %5, vcc\n\t"
-        "v_subb_co_u32 %0, vcc, %6, %7, vcc\n\t"
-        "v_addc_co_u32 %1, vcc, 0, %1, vcc"
-        : "=&v"(t), "+v"(c)
-        : "v"(ia), "v"(ib), "v"((unsigned)ka), "v"((unsigned)kb), "v"((unsigned)(ka >> 32)), "v"((unsigned)(kb >> 32))
-        : "vcc");
-}
-
+// (the count below uses count_less96, wave.h: the composite compare in four VALU instructions)
 __global__ void __launch_bounds__(256) sample_rank_kernel(FastArgs a) {
     __shared__ __align__(16) uint64_t jk[256];
     __shared__ unsigned last;

@@ -3,6 +3,7 @@
 // in between, 3 launches).  Used for row_ptr (sum), the segmented prefix maximum of the clustering
 // (max on composite keys) and the BH running minimum (min on IEEE bit patterns).
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
@@ -25,10 +26,7 @@ struct OpMinU64 {
 
 template <typename T>
 __device__ __forceinline__ T shfl_up64(T v, int o) {
-    unsigned lo = (unsigned)((uint64_t)v & 0xffffffffu), hi = (unsigned)((uint64_t)v >> 32);
-    lo = __shfl_up(lo, o);
-    hi = __shfl_up(hi, o);
-    return (T)(((uint64_t)hi << 32) | lo);
+    return (T)shfl_up_u64((uint64_t)v, o);
 }
 
 constexpr int SCAN_THREADS = 256;

@@ -747,7 +747,15 @@ def test_bh_columns_batched(ctx, n, cols):
 def test_bh_columns_samplesort_vs_generic(ctx, n, cols):
     """the sample-sort column path (bh_cols.hip) against the generic radix path, bit for bit, and the oracle:
     continuous values, heavy ties (p = 1, a few discrete levels as Fisher gives), one-value and two-value
-    columns, values a few ulps apart, NaN, crowds of distinct values far narrower than a bin (the second-level sort)"""
+    columns, values a few ulps apart, NaN, crowds of distinct values far narrower than a bin (the second-level sort).
+
+    The in-HBM bucket path (one wave sorts a copy of the bucket, then walks it in chunks of 64 from the top with a carry)
+    runs for every column of more than one bucket (n > 1024 at 256 threads; 1025 is the smallest) at mean buckets of 48,
+    64, 96 and 128 values.  Bucket sizes are not visible through the API, so nothing is asserted on them; the argument
+    that the edges are met: eight samples per bucket spread the sizes by about a third around the mean (Gamma(8)), so
+    every one of these means puts buckets on both sides of the 64-value chunk -- one chunk, two, three -- and on both
+    sides of bh.reg_cap 63 and 64, where the in-HBM and the LDS path mix in one launch; bh.reg_cap 0 sends every
+    bucket that holds a value through HBM."""
     rng = np.random.default_rng(n * 31 + cols)
     p = rng.random((n, cols)) ** 2
     p[rng.random((n, cols)) < 0.3] = 1.0
@@ -794,11 +802,15 @@ def test_bh_columns_samplesort_vs_generic(ctx, n, cols):
             d = ctx.to_device(p)
             ctx.bh_columns_dev(d)
             assert np.array_equal(generic, d.to_host(), equal_nan=True)
-        if n > 2000:
-            with ctx.params({"bh.reg_cap": 64}):                              # most buckets through the in-HBM path
-                d = ctx.to_device(p)
-                ctx.bh_columns_dev(d)
-                assert np.array_equal(generic, d.to_host(), equal_nan=True)
+        if n > 1024:
+            # buckets beyond bh.reg_cap values: one wave each, sorted and turned into suffix minima in HBM
+            knobs = [{"bh.reg_cap": 64}]                                      # default mean: most buckets
+            knobs += [{"bh.mean": mean, "bh.reg_cap": cap} for mean in (48, 64, 96, 128) for cap in (0, 63, 64)]
+            for kn in knobs:
+                with ctx.params(kn):
+                    d = ctx.to_device(p)
+                    ctx.bh_columns_dev(d)
+                    assert np.array_equal(generic, d.to_host(), equal_nan=True), kn
     ok = ~np.isnan(p).any(axis=0)
     np.testing.assert_allclose(fast[:, ok], O.bh_columns(p[:, ok]), rtol=1e-14, atol=0)
 
@@ -978,6 +990,7 @@ def test_bh_vector_samplesort_vs_radix(ctx, n):
             ctx.bh_dev(d_p, d_q)
             out[path] = d_q.to_host()
     assert np.array_equal(out[1].view(np.uint64), out[2].view(np.uint64))
+    ref_plain = out[1]
     if n <= 100_000:
         np.testing.assert_allclose(out[2], O.bh_fdr(p), rtol=1e-14, atol=0)
     # NaN sorts behind every number in both paths
@@ -998,6 +1011,7 @@ def test_bh_vector_samplesort_vs_radix(ctx, n):
             out[path] = d_q.to_host()
     assert np.array_equal(out[1].view(np.uint64), out[2].view(np.uint64))
     assert not out[2][tested == 0].any()
+    ref_flag = out[1]
     if n <= 100_000:
         np.testing.assert_allclose(out[2][tested != 0], O.bh_fdr(p[tested != 0]), rtol=1e-14, atol=0)
     pm = np.where(tested != 0, p, -1.0)                      # absent = negative p, no flag array
@@ -1008,11 +1022,24 @@ def test_bh_vector_samplesort_vs_radix(ctx, n):
             out[path] = d_q.to_host()
     assert np.array_equal(out[1].view(np.uint64), out[2].view(np.uint64))
     if n <= 100_000:
-        # buckets beyond the LDS capacity of a bucket workgroup (forced: every bucket) take the in-HBM network
-        with ctx.params({"bh.vector_path": 2, "bhv.cap": 512}):
-            d_p, d_q = ctx.to_device(pm), ctx.empty(n, np.float64)
-            ctx.bh_masked_dev(d_p, None, d_q)
-            assert np.array_equal(out[1].view(np.uint64), d_q.to_host().view(np.uint64))
+        # buckets beyond their slot take the slow path: one wave puts the bucket together from its slot and the overflow
+        # list and sorts it in HBM.  bhv.cap 512 at the default mean: every bucket.  Mean 512 (16384 values: 32 buckets of
+        # 512 +- 128): cap 448 ... 576 leave some buckets in LDS and give the others a few overflow entries, cap 64 puts
+        # most of every bucket into the overflow list.  Each for the plain vector, the flag mask and negative p.
+        ref = {"plain": ref_plain, "flag": ref_flag, "neg": out[1]}
+        knobs = [{"bhv.cap": 512}] + [{"bhv.mean": 512, "bhv.cap": cap} for cap in (64, 448, 512, 576)]
+        for kn in knobs:
+            with ctx.params({"bh.vector_path": 2, **kn}):
+                for form in ("plain", "flag", "neg"):
+                    d_p, d_t, d_q = ctx.to_device(pm if form == "neg" else p), ctx.to_device(tested), ctx.empty(n, np.float64)
+                    if form == "plain":
+                        ctx.bh_dev(d_p, d_q)
+                    else:
+                        ctx.bh_masked_dev(d_p, d_t if form == "flag" else None, d_q)
+                    got = d_q.to_host()
+                    assert np.array_equal(ref[form].view(np.uint64), got.view(np.uint64)), (kn, form)
+                    if form != "plain":
+                        assert not got[tested == 0].any(), (kn, form)
 
 
 def test_bh_high_word_runs(ctx):
