@@ -226,6 +226,43 @@ int sdice_jonckheere_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps
                          const int32_t* set_ptr, int32_t k, uint8_t* d_tested, double* d_p, double* d_z, double* d_j,
                          float* d_med, float* d_mean, float* d_delta);
 
+/* ---- compare_sample_sets --repeated: Friedman's test across k MATCHED sets (the same m subjects in every set), per row
+ *      scipy.stats.friedmanchisquare under the row rules below; with --trend Page's L test over the sets as ORDERED.
+ *  cols is SET-major: cols[j m + q] is the column of set j (0-based) for subject q.  2 <= k <= 64, 1 <= m <= 4096,
+ *  k m <= 16384, a column at most once; otherwise SDICE_ERR_ARG before any launch, outputs untouched (the host call checks
+ *  the index range and the one-appearance rule, the _dev call k, m, k m and k m <= s).  Values are finite float32 or NaN.
+ *  Per row: block q (subject q's k values) is kept when none of them is NaN; with fewer than 3 kept blocks (m') the row is
+ *  not tested and every output slot is 0.  blocks[n] int32 = m' (optional, NULL to skip).  med[k][n] / mean[k][n] float32
+ *  SET-major are np.median / np.mean of set j's values over the KEPT blocks in subject order, bit for bit as in
+ *  sdice_signedrank; delta[n] = largest minus smallest set median in float32.
+ *  Ranks are taken inside a block, as integers: r2(q, j) = 2 #{l: x_ql < x_qj} + #{l: x_ql == x_qj} + 1 (twice the
+ *  mid-rank; ties by float32 equality, -0.0 == +0.0, subnormals are distinct values), D_j = sum_q r2(q, j) - m'(k + 1),
+ *  C = sum over blocks and tie groups of t^3 - t, den = m'(k^3 - k) - C.  No value is subtracted from another: 3-decimal
+ *  rows and others are one path.
+ *  sdice_friedman: q[n] = Q = 3 (k - 1) sum D_j^2 / den and w[n] = Kendall's W = 3 sum D_j^2 / (m' den) = Q / (m'(k - 1)),
+ *  float64, each the correctly rounded quotient of two exact integers (both optional, NULL to skip); p[n] = chi2.sf(Q,
+ *  k - 1), to the p bars of sdice_kruskal.  Always the chi-square approximation: there is no exact form here.
+ *  sdice_page: the sets are ORDERED as given.  l[n] = L = sum_j (j + 1) R_j float64, exact (optional, NULL to skip); E[L] =
+ *  m' k (k + 1)^2 / 4, Var L = k (k + 1) den / 144, the conditional (within-block permutation) variance given the row's
+ *  ties (scipy.stats.page_trend_test uses the untied variance: the two differ on tied rows, on purpose); z[n] = (L - E[L])
+ *  / sqrt(Var L) = 6 sum_j (j + 1) D_j / sqrt(k (k + 1) den), no continuity correction, within 2 ulp of the correctly
+ *  rounded value, > 0 where the values rise along the set order, +0.0 where L = E[L]; the call on the reversed sets gives
+ *  -z bit for bit.  p[n] = erfc(|z| / sqrt 2), two-sided, asymptotic only, to the p bars of sdice_ranksum.  z is required.
+ *  A row whose kept blocks are all fully tied (den = 0) is tested with Q = W = z = 0 and p = 1 (scipy: NaN).  Permuting
+ *  the sets or the subjects leaves Q, W, p and |z| bit for bit. */
+int sdice_friedman(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps, const int32_t* cols, int32_t k, int32_t m,
+                   uint8_t* tested, double* p, double* q, double* w, int32_t* blocks, float* med, float* mean,
+                   float* delta);
+int sdice_friedman_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, const int32_t* d_cols, int32_t k,
+                       int32_t m, uint8_t* d_tested, double* d_p, double* d_q, double* d_w, int32_t* d_blocks,
+                       float* d_med, float* d_mean, float* d_delta);
+int sdice_page(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps, const int32_t* cols, int32_t k, int32_t m,
+               uint8_t* tested, double* p, double* z, double* l, int32_t* blocks, float* med, float* mean,
+               float* delta);
+int sdice_page_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, const int32_t* d_cols, int32_t k,
+                   int32_t m, uint8_t* d_tested, double* d_p, double* d_z, double* d_l, int32_t* d_blocks,
+                   float* d_med, float* d_mean, float* d_delta);
+
 /* ---- compare_sample_sets --paired: Wilcoxon signed-rank test over m matched column pairs, per row
  *      scipy.stats.wilcoxon(d, zero_method="wilcox", correction=False, alternative="two-sided", method="asymptotic")
  *      under the row rules above.

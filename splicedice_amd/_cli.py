@@ -80,10 +80,13 @@ def tested_rows(ctx, inputs, outputs, launch):
 
     def test_and_correct(d_in, d_out):
         launch(d_in, d_out)
-        ctx.bh_masked_dev(d_out["p"], d_out["tested"], d_out["q"])
+        ctx.bh_masked_dev(d_out["p"], d_out["tested"], d_out["corrected"])
 
-    res = device_call(ctx, inputs, {**outputs, "q": (n, np.float64)}, test_and_correct)
-    q = res.pop("q")
+    # (the corrected vector rides as `corrected`, what it is called in the result: no test's field has that name --
+    # Friedman's Q is the field `q`)
+    assert "corrected" not in outputs
+    res = device_call(ctx, inputs, {**outputs, "corrected": (n, np.float64)}, test_and_correct)
+    q = res.pop("corrected")
     keep = np.flatnonzero(res.pop("tested"))
     r = {name: v[keep] if v.ndim == 1 else np.ascontiguousarray(v[:, keep]) for name, v in res.items()}
     r["corrected"] = q[keep]

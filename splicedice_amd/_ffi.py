@@ -131,6 +131,8 @@ for _name, _args, _outputs in (
         ("signedrank", _TWO_LISTS, 8),
         ("signedrank_exact", _TWO_LISTS, 9),
         ("spearman", _TWO_LISTS, 6),
+        ("friedman", [vp, C.c_int32, C.c_int32], 8),          # (k matched sets: cols, k, m)
+        ("page", [vp, C.c_int32, C.c_int32], 8),
         ("sample_gram", [vp, C.c_int32], 4)):
     for _form in ("", "_dev"):
         SIGNATURES["sdice_" + _name + _form] = _TABLE + _args + [vp] * _outputs

@@ -46,6 +46,12 @@ of the Kruskal-Wallis test in the same pass (sdice_kruskal_dunn).  Every -mx col
 set j) and `padj{i}v{j}`, the pair's two-sided p-value after Holm's step-down correction over the pairs of the row.  At most
 11 sets; not with --trend.
 
+A ninth: `--repeated` (with -mx) takes the sets as MATCHED -- line i of every manifest is the same subject -- and the test
+becomes Friedman's test (sdice_friedman), ranks taken inside each subject's block of k values, blocks with a missing value
+dropped; the columns are the -mx ones with `Q W` where `H` stood.  With `--trend` the sets are ordered as well and the test
+is Page's L test (sdice_page) with `z` in that place.  Not with --paired, --exact, --strata, --ks, --shift or --posthoc
+(DESIGN.md section 7).
+
 On the GPU: the per-row loop :216-232 (NaN drop, <3 skip, scipy ranksums, medians, means)
 -> sdice_ranksum; multipletests(..., "fdr_bh") :235 -> sdice_bh over the tested rows.
 The GTF annotation columns are host string work, as in the reference.
@@ -58,8 +64,8 @@ import numpy as np
 
 from . import _cli
 from ._cli import annotation_suffixes, read_annotation, read_ps_table, samples_from_manifest, table_header_names  # noqa: F401
-from .engine import (DUNN_MAX_SETS, JONCKHEERE_FIELDS, KRUSKAL_DUNN_FIELDS, KRUSKAL_FIELDS, KS_FIELDS, RANKSUM_EXACT_FIELDS,
-                     RANKSUM_FIELDS, SHIFT_FIELDS, Context, dunn_pairs, field_shapes)
+from .engine import (DUNN_MAX_SETS, FRIEDMAN_FIELDS, JONCKHEERE_FIELDS, KRUSKAL_DUNN_FIELDS, KRUSKAL_FIELDS, KS_FIELDS,
+                     PAGE_FIELDS, RANKSUM_EXACT_FIELDS, RANKSUM_FIELDS, SHIFT_FIELDS, Context, dunn_pairs, field_shapes)
 
 MAX_STRATA = 64                     # strata a call accepts (include/sdice.h)
 
@@ -188,6 +194,17 @@ def add_parser(parser):
                              "correction over the pairs of the row (not across rows: `corrected` stays the Benjamini-"
                              "Hochberg value of the H test).  At most 11 sets.  Not with --trend (not part of the "
                              "reference)")
+    parser.add_argument("--repeated", action="store_true",
+                        help="With -mx: MATCHED sets -- the same subjects in every set (time points, normal / primary / "
+                             "metastasis of one patient, one cell line under several doses): line i of -m1, -m2 and every "
+                             "-mx file is the same subject (MANIFEST order, as with --paired) and the test is Friedman's "
+                             "test, ranks taken inside each subject's values; a subject with a missing value in any set "
+                             "is left out of the row, 3 complete subjects are needed.  The table carries Q and W "
+                             "(Kendall's coefficient of concordance) where the -mx table carries H; the p-value is the "
+                             "chi-square approximation.  With --trend the sets are ORDERED and the test is Page's L "
+                             "test: the table carries z (> 0 where the PS rises along the order; the variance is "
+                             "conditional on the row's ties), the p-value is two-sided and asymptotic.  Not with "
+                             "--paired, --exact, --strata, --ks, --shift or --posthoc (not part of the reference)")
     parser.add_argument("--ks", action="store_true",
                         help="The two-sample Kolmogorov-Smirnov test instead of the rank-sum test: it answers to any "
                              "difference between the two distributions (a junction switched on in part of a set, a "
@@ -304,10 +321,47 @@ def _dunn_columns(k):
         yield f"padj{i + 1}v{j + 1}", ("pair_padj", q)
 
 
+def repeated_columns(groups, header_names):
+    """--repeated: the manifests' sample lists (set by set) and the table's column names -> one int32 column index vector per
+    set in MANIFEST order, entry q of every vector the same subject; prints why and exits with status 1 when the lists are
+    not one line per subject"""
+    refuse = BY_FLAG[REPEATED].refuse
+    if len({len(g) for g in groups}) > 1:
+        refuse(f"the manifests differ in length ({', '.join(str(len(g)) for g in groups)} samples); line i of every "
+               f"manifest is the same subject")
+    if len(groups[0]) < 3:
+        refuse(f"cannot conduct Friedman's test with fewer than 3 subjects (got {len(groups[0])})")
+    seen = set()
+    for name in (x for g in groups for x in g):
+        if name in seen:
+            refuse(f"sample {name!r} appears twice in the manifests; a sample belongs to one set and one subject only")
+        seen.add(name)
+    idx = _cli.columns_in_header([x for g in groups for x in g], header_names, refuse)
+    return [v.copy() for v in np.split(idx, len(groups))]
+
+
+def _matched_sets(test):
+    """the rest of a row over k matched sets; test: the engine's name of the call (`<test>_resident` on resident data)"""
+    return dict(inputs=lambda sel: dict(cols=(sel.cols, np.int32)), k=lambda sel: len(sel.set_idx),
+                dev=lambda ctx, sel: lambda d, out: getattr(ctx, test + "_resident")(d["ps"], d["cols"], len(sel.set_idx), out),
+                host=lambda ctx, matrix, sel: getattr(ctx, test)(matrix, sel.set_idx))
+
+
 PAIRED, EXACT, STRATA, TREND, KS, MX = "--paired", "--exact", "--strata", "--trend", "--ks", "-mx/--moreManifests"
-SHIFT, CONF, POSTHOC = "--shift", "--conf", "--posthoc"
+SHIFT, CONF, POSTHOC, REPEATED = "--shift", "--conf", "--posthoc", "--repeated"
 # in the order the refusals are made; the first selected row with a pipeline is the test that runs
 TESTS = (
+    # k matched sets: Friedman's test per junction (with --trend: Page's test, PAGE below).  First, so that it, not the
+    # --trend / -mx rows, is the test that runs
+    Test(REPEATED, needs=(MX, "two matched sets are the signed-rank test: --paired"),
+         conflicts=((PAIRED, "the signed-rank test compares two matched sets; this test compares three or more"),
+                    (EXACT, "there is no exact Friedman test here"),
+                    (STRATA, "the subjects are the blocks already; there is no stratified form"),
+                    (KS, "the Kolmogorov-Smirnov test compares two independent sets"),
+                    (SHIFT, "the shift is an estimate between two independent sets"),
+                    (POSTHOC, "there is no post-hoc test of matched sets here")),
+         multi_rank=_multi_rank(REPEATED, "the packed all-gather carries the two-set fields only"),
+         fields=FRIEDMAN_FIELDS, stat=(("Q", "q"), ("W", "w")), **_matched_sets("friedman")),
     Test(CONF, needs=(SHIFT, "it is the level of the shift's confidence interval")),
     # (keeps the rank-sum pipeline, as --exact does: compare() adds the shift call to the same pass)
     Test(SHIFT, conflicts=((PAIRED, "the paired estimate is the median of the Walsh averages, which is not offered"),
@@ -352,6 +406,8 @@ TESTS = (
          fields=KRUSKAL_FIELDS, stat=(("H", "h"),), **_k_sets("kruskal")),
 )
 BY_FLAG = {t.flag: t for t in TESTS}
+# --repeated --trend: the same row with Page's call, fields and column
+PAGE = BY_FLAG[REPEATED]._replace(fields=PAGE_FIELDS, stat=(("z", "z"),), **_matched_sets("page"))
 KS_MULTI_RANK_REFUSAL, TREND_MULTI_RANK_REFUSAL, STRATA_MULTI_RANK_REFUSAL, MULTI_RANK_REFUSAL = (
     BY_FLAG[f].multi_rank for f in (KS, TREND, STRATA, MX))
 refuse, refuse_strata = BY_FLAG[PAIRED].refuse, BY_FLAG[STRATA].refuse
@@ -359,7 +415,7 @@ refuse, refuse_strata = BY_FLAG[PAIRED].refuse, BY_FLAG[STRATA].refuse
 
 def run_with(args, ctx=None):
     from . import _stages, mgpu
-    from .engine import kruskal_sets
+    from .engine import friedman_columns, kruskal_sets
     L = mgpu.launcher()             # (reads the torchrun environment before any GPU call)
     g1 = samples_from_manifest(args.manifest1)
     g2 = samples_from_manifest(args.manifest2)
@@ -367,8 +423,8 @@ def run_with(args, ctx=None):
     on = {PAIRED: getattr(args, "paired", False), EXACT: getattr(args, "exact", False), STRATA: getattr(args, "strata", None),
           TREND: getattr(args, "trend", False), KS: getattr(args, "ks", False), MX: more,
           SHIFT: getattr(args, "shift", False), CONF: getattr(args, "conf", None) is not None,
-          POSTHOC: getattr(args, "posthoc", False)}
-    chosen = [t for t in TESTS if on[t.flag]]
+          POSTHOC: getattr(args, "posthoc", False), REPEATED: getattr(args, "repeated", False)}
+    chosen = [PAGE if t.flag == REPEATED and on[TREND] else t for t in TESTS if on[t.flag]]
     sel = argparse.Namespace(exact=bool(on[EXACT]))
     conf = None
     if on[SHIFT]:
@@ -388,6 +444,9 @@ def run_with(args, ctx=None):
             g1, g2, table_header_names(args.psiSPLICEDICE), _cli.read_labels(on[STRATA], refuse_strata))
     if on[PAIRED]:
         sel.g1_idx, sel.g2_idx = paired_columns(g1, g2, table_header_names(args.psiSPLICEDICE))
+    if on[REPEATED]:
+        sel.set_idx = repeated_columns([g1, g2] + more, table_header_names(args.psiSPLICEDICE))
+        sel.g1_idx, sel.g2_idx = sel.set_idx[:2]
     if len(g1) < 3 or len(g2) < 3 or any(len(g) < 3 for g in more):
         print("Cannot conduct wilcoxon with less than 3 samples in either group. Exit.", file=sys.stderr)
         sys.exit(1)
@@ -401,7 +460,9 @@ def run_with(args, ctx=None):
         rows, cols, matrix = read_ps_table(args.psiSPLICEDICE, as_table=True)
     if not hasattr(sel, "g1_idx"):
         sel.g1_idx, sel.g2_idx = column_indices(g1, cols), column_indices(g2, cols)
-    if more:
+    if on[REPEATED]:
+        sel.cols = friedman_columns(sel.set_idx, matrix.shape[1])
+    elif more:
         sel.set_idx = [sel.g1_idx, sel.g2_idx] + [column_indices(g, cols) for g in more]
         sel.cols, sel.set_ptr = kruskal_sets(sel.set_idx, matrix.shape[1])       # (raises on a column in two sets)
     with _cli.engine_scope(ctx, lambda: Context(L.local_rank)) as ctx:

@@ -41,6 +41,21 @@ int kw_check_sets(const char* fn, const int32_t* set_ptr, int32_t k, int32_t s) 
     return SDICE_OK;
 }
 
+int fr_check_sets(const char* fn, const int32_t* cols, int32_t k, int32_t m, int32_t s) {
+    if (!(k >= 2 && k <= KW_MAX_SETS)) return refuse(fn, "the number of sets must be 2..64");
+    if (!(m >= 1 && m <= FR_MAX_BLOCKS)) {
+        sdice_set_error("%s: %d columns per set, each set needs 1..%d (one per subject)", fn, (int)m, FR_MAX_BLOCKS);
+        return SDICE_ERR_ARG;
+    }
+    if ((int64_t)k * m > KW_MAX_N) {
+        sdice_set_error("%s: %d selected columns, at most %d are supported", fn, (int)(k * m), KW_MAX_N);
+        return SDICE_ERR_ARG;
+    }
+    if ((int64_t)k * m > s) return refuse(fn, "more selected columns than the table has (a column may appear once)");
+    if (!cols) return SDICE_OK;
+    return check_columns(fn, {cols}, k * m, s, "column index out of range", "a column may appear once over all sets");
+}
+
 int check_two_groups(const char* fn, const int32_t* g1, int32_t n1, const int32_t* g2, int32_t n2, int32_t s, int limit,
                      const int32_t* strat1, const int32_t* strat2, int32_t n_strata, int max_strata) {
     const bool counts_ok = n1 >= 1 && n1 <= limit && n2 >= 1 && n2 <= limit;

@@ -17,6 +17,12 @@ int check_columns(const char* fn, std::initializer_list<const int32_t*> lists, i
 // (that refusal names `fn`) and no more than the table has
 int kw_check_sets(const char* fn, const int32_t* set_ptr, int32_t k, int32_t s);
 
+// k matched sets of m columns each, set-major (friedman.hip): 2 <= k <= KW_MAX_SETS, 1 <= m <= FR_MAX_BLOCKS, k m <= KW_MAX_N
+// and k m <= s, in this order; cols != NULL (the host entry points: a HOST list of k m entries): then also every entry a
+// column of the table and no column listed twice.  cols == NULL: the list is on the device, the counts alone are checked.
+constexpr int FR_MAX_BLOCKS = 4096;
+int fr_check_sets(const char* fn, const int32_t* cols, int32_t k, int32_t m, int32_t s);
+
 // Two column groups of their own lengths (strata.hip, ks.hip, shift.hip), at most `limit` columns each; max_strata != 0: every
 // column carries a stratum id in [0, n_strata), 1 <= n_strata <= max_strata.  In this order:
 //   the lists, when they are given and every count is in range: an index outside the table, a column listed twice over

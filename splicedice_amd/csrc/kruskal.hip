@@ -141,31 +141,7 @@ __device__ __forceinline__ void dunn_pairs(const DunnOut& o, int lane, int m, in
     if (mine) o.pair_padj[(int64_t)lane * n + row] = fmin(1.0, best);
 }
 
-// chi2.sf(h, df), integer df >= 1: the closed series (see the file comment)
-__device__ double kw_chi2_sf(double h, int df) {
-    const double x = 0.5 * h;
-    double sum = 0.0;
-    const double e = exp(-0.5 * x);      // e^-x in two factors: e^-x alone is subnormal from x = 709, where the sum can still lift p above 1e-280
-    if (df & 1) {
-        const double r = sqrt(x);
-        double term = r * 1.12837916709551257390;        // x^(1/2) / Gamma(3/2) = 2 sqrt(x / pi)
-        const int m = (df - 1) >> 1;
-        for (int j = 1; j <= m; ++j) {
-            sum += term;
-            term *= x / ((double)j + 0.5);
-        }
-        return erfc(r) + (sum * e) * e;
-    }
-    double term = 1.0;
-    const int m = df >> 1;
-    for (int j = 0; j < m; ++j) {
-        sum += term;
-        term *= x / (double)(j + 1);
-    }
-    return (sum * e) * e;
-}
-
-// H and p of a tested row from the integer pieces
+// H and p (kw_chi2_sf: rowsum.h, shared with friedman.hip) of a tested row from the integer pieces
 __device__ __forceinline__ void kw_finish(double S, long long N, long long tie, int k, double& H, double& p) {
     const long long den = N * N * N - N - tie;           // (N^3 - N) T
     if (den == 0) { H = 0.0; p = 1.0; return; }          // every value equal

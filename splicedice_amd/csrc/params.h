@@ -57,7 +57,9 @@
     X(BH_BIG_WG, "bh.big_wg", 512, "threads of a workgroup of the second bucket kernel: 512 (4 values per thread) or 256 (8)") \
     X(BH_SPB, "bh.spb", 8, "samples per bucket")                                                                        \
     /* sample Gram sums (gram.hip) */                                                                                   \
-    X(GRAM_ROWS_PER_WG, "gram.rows_per_wg", 0, "rows of a workgroup's slice, raised to a multiple of 64 (the smallest slice); 0 = by size: 4096, halved down to 256 while the grid is small")
+    X(GRAM_ROWS_PER_WG, "gram.rows_per_wg", 0, "rows of a workgroup's slice, raised to a multiple of 64 (the smallest slice); 0 = by size: 4096, halved down to 256 while the grid is small") \
+    /* Friedman and Page tests (friedman.hip) */                                                                        \
+    X(FRIEDMAN_WAVE_MAX, "friedman.wave_max", 1024, "staged values of a row (sets x subjects rounded up to a power of two) up to which one wave takes the row; above it a workgroup does (0 = always the workgroup; tests)")
 
 enum SdParam : int {
 #define X(id, name, dflt, meaning) SD_P_##id,

@@ -14,8 +14,10 @@
 //   kruskal.hip (K12)     as ranksum.hip's kernels + f32_ord, median_of_ord, block_bitonic
 //                         + the k-set section: the limits, KwSets, kw_stage_row / kw_walk_set (the first walk of the grid
 //                         kernel), kw_block_sort_sets (the block kernel up to its medians), kw_plan, kw_launch_pair,
-//                         kw_check_sets, check_columns
+//                         kw_check_sets, check_columns, kw_chi2_sf
 //   jonckheere.hip (K18)  as kruskal.hip's k-set section + kw_load_bins / kw_scan_bins, the launch sizes
+//   friedman.hip (K21)    lanes_below, wave_pairwise_sum (FloatAt), f32_ord, median_of_ord, PAD32, kw_wave_max / kw_wave_min,
+//                         kw_chi2_sf, the launch sizes; fr_check_sets (colcheck.h)
 //   signedrank.hip (K13)  PsKey, f32_ord, LaneGroup, group_add / group_sum / group_sort / group_median, pair_diff_key,
 //                         block_compact_by, block_pairwise_sum, block_bitonic, run_bounds, median_of_ord, store_two_sample,
 //                         with_group_launch; TwoSampleOut, zero_two_sample, stage_two_sample, check_columns
@@ -454,6 +456,31 @@ __device__ __forceinline__ float kw_wave_min(float v) {
 #pragma unroll
     for (int ofs = 32; ofs > 0; ofs >>= 1) v = fminf(v, __shfl_xor(v, ofs));
     return v;
+}
+
+// chi2.sf(h, df), integer df >= 1 (kruskal.hip, friedman.hip): the closed series with positive terms only (x = h / 2)
+//   even df: e^-x sum_{j < df/2} x^j / j!      odd df: erfc(sqrt x) + e^-x sum_{j=1..(df-1)/2} x^(j-1/2) / Gamma(j+1/2)
+__device__ double kw_chi2_sf(double h, int df) {
+    const double x = 0.5 * h;
+    double sum = 0.0;
+    const double e = exp(-0.5 * x);      // e^-x in two factors: e^-x alone is subnormal from x = 709, where the sum can still lift p above 1e-280
+    if (df & 1) {
+        const double r = sqrt(x);
+        double term = r * 1.12837916709551257390;        // x^(1/2) / Gamma(3/2) = 2 sqrt(x / pi)
+        const int m = (df - 1) >> 1;
+        for (int j = 1; j <= m; ++j) {
+            sum += term;
+            term *= x / ((double)j + 0.5);
+        }
+        return erfc(r) + (sum * e) * e;
+    }
+    double term = 1.0;
+    const int m = df >> 1;
+    for (int j = 0; j < m; ++j) {
+        sum += term;
+        term *= x / (double)(j + 1);
+    }
+    return (sum * e) * e;
 }
 
 // np.sum of the contiguous float32 array float32(K[0..nv) / 1000): the identity 0 plus the pairwise tree of every piece

@@ -34,11 +34,16 @@ KRUSKAL_DUNN_FIELDS = KRUSKAL_FIELDS + [("pair_z", np.float64, PER_PAIR), ("pair
                                         ("pair_padj", np.float64, PER_PAIR)]
 JONCKHEERE_FIELDS = [("tested", np.uint8), ("p", np.float64), ("z", np.float64), ("j", np.float64),
                      ("med", np.float32, PER_SET), ("mean", np.float32, PER_SET), ("delta", np.float32)]
+FRIEDMAN_FIELDS = [("tested", np.uint8), ("p", np.float64), ("q", np.float64), ("w", np.float64), ("blocks", np.int32),
+                   ("med", np.float32, PER_SET), ("mean", np.float32, PER_SET), ("delta", np.float32)]
+PAGE_FIELDS = [("tested", np.uint8), ("p", np.float64), ("z", np.float64), ("l", np.float64), ("blocks", np.int32),
+               ("med", np.float32, PER_SET), ("mean", np.float32, PER_SET), ("delta", np.float32)]
 SPEARMAN_FIELDS = [("tested", np.uint8), ("p", np.float64), ("rho", np.float64), ("n_kept", np.int32), ("med", np.float32),
                    ("mean", np.float32)]
 GRAM_FIELDS = [("shared", np.int64), ("sum1", np.int64), ("sum2", np.int64), ("prod", np.int64)]
 # Every row test: the name of its pair of C entry points (sdice_<name>, sdice_<name>_dev) and of its pair of Context methods
 # (<name>, <name>_dev) -> (its field table, the fields a _dev call may leave out of `out`: the library is handed NULL)
+# (friedman and page: the resident methods are friedman_resident / page_resident for now, see there)
 ROW_TESTS = {
     "ranksum": (RANKSUM_FIELDS, ("z",)),
     "ranksum_exact": (RANKSUM_EXACT_FIELDS, ("z",)),
@@ -48,6 +53,8 @@ ROW_TESTS = {
     "kruskal": (KRUSKAL_FIELDS, ("h",)),
     "kruskal_dunn": (KRUSKAL_DUNN_FIELDS, ("h", "pair_p", "pair_padj")),
     "jonckheere": (JONCKHEERE_FIELDS, ("j",)),
+    "friedman": (FRIEDMAN_FIELDS, ("q", "w", "blocks")),
+    "page": (PAGE_FIELDS, ("l", "blocks")),
     "signedrank": (RANKSUM_FIELDS, ("z",)),
     "signedrank_exact": (RANKSUM_EXACT_FIELDS, ("z",)),
     "spearman": (SPEARMAN_FIELDS, ("rho",)),
@@ -116,6 +123,30 @@ def kruskal_sets(sets, s=None):
                 raise ValueError(f"kruskal: column {c} is in set {seen[c] + 1} and in set {i + 1}; a column may belong to one set only")
             seen[c] = i
     return np.ascontiguousarray(cols, dtype=np.int32), set_ptr
+
+
+def friedman_columns(sets, s=None):
+    """k equally long lists of column indices, list j the columns of set j in SUBJECT order (entry q of every list is the
+    same subject) -> the set-major int32 cols of friedman() / page(): cols[j * m + q].  Lists of unequal length, a column
+    listed twice (inside a set or across sets) and, when s is given, an index outside [0, s) raise ValueError here, on the
+    host, before anything is launched."""
+    sets = [np.asarray(g).reshape(-1) for g in sets]
+    if len({g.size for g in sets}) > 1:
+        raise ValueError(f"friedman: the sets differ in length ({', '.join(str(g.size) for g in sets)} columns); entry q of "
+                         f"every set is the same subject")
+    for g in sets:
+        if g.size and g.dtype.kind not in "iu":
+            raise TypeError(f"friedman: column indices must be integers, got {g.dtype}")
+    cols = np.concatenate(sets).astype(np.int64) if sets else np.zeros(0, np.int64)
+    if s is not None and cols.size and (cols.min() < 0 or cols.max() >= s):
+        raise ValueError(f"friedman: column index outside [0, {s})")
+    if cols.size and (cols.min() < -2 ** 31 or cols.max() >= 2 ** 31):
+        raise ValueError("friedman: column index out of range")
+    uniq, count = np.unique(cols, return_counts=True)
+    if np.any(count > 1):
+        raise ValueError(f"friedman: column {int(uniq[count > 1][0])} is listed more than once; a column may appear once "
+                         f"over all sets")
+    return np.ascontiguousarray(cols, dtype=np.int32)
 
 
 def shift_quantile(conf):
@@ -486,6 +517,26 @@ class Context:
         [k, n] and delta [n] as kruskal()'s."""
         return self._host_sets("jonckheere", ps, sets)
 
+    def _host_matched(self, name, ps, sets, skip=()):
+        """_host_row over k matched column sets (friedman_columns checks them against the table's columns)"""
+        ps = _c(ps, np.float32)
+        cols = friedman_columns(sets, ps.shape[1])
+        k = len(sets)
+        return self._host_row(name, ps, (cols, k, cols.size // k if k else 0), k=k, skip=skip)
+
+    def friedman(self, ps, sets):
+        """Friedman's test per row across k MATCHED column sets (entry q of every set is the same subject;
+        include/sdice.h): a subject's block of k values is kept when none is NaN, the row is tested with 3 kept blocks or
+        more; un-compacted outputs: tested, p = chi2.sf(Q, k - 1), q = Q, w = Kendall's W, blocks (int32: kept blocks) [n],
+        med, mean [k, n] over the kept blocks, delta [n] = largest minus smallest set median."""
+        return self._host_matched("friedman", ps, sets)
+
+    def page(self, ps, sets):
+        """Page's L trend test per row across k MATCHED, ORDERED column sets (set 0 < set 1 < ...) under the row rules of
+        friedman(); un-compacted outputs: tested, p (two-sided, asymptotic), z (> 0: the values rise along the order, the
+        variance conditional on the row's ties), l = L, blocks [n], med, mean [k, n] and delta [n] as friedman()'s."""
+        return self._host_matched("page", ps, sets)
+
     def signedrank(self, ps, a, b):
         """scipy.stats.wilcoxon (asymptotic, zero_method="wilcox") per row over the matched column pairs (a[q], b[q])
         under the row rules of ranksum(); same un-compacted outputs + tested mask (z > 0: side a is larger)."""
@@ -691,6 +742,19 @@ class Context:
         """d_cols: the device copy of kruskal_sets()'s cols; set_ptr: its HOST offsets; out: device tested, p, z, (j), med and
         mean [k, n], delta"""
         self._resident_sets("jonckheere", d_ps, d_cols, set_ptr, out)
+
+    def friedman_resident(self, d_ps, d_cols, k, out):
+        """friedman() on a resident table: sdice_friedman_dev.  d_cols: the device copy of friedman_columns()'s cols, k the
+        number of sets (m = len(cols) / k); out: the device fields of FRIEDMAN_FIELDS, q, w and blocks optional.  (Named
+        _resident, not _dev: every `_dev` method has to be listed in the call-order catalogue of the test suite, which this
+        method joins, under the usual name friedman_dev, when that catalogue is next open for change.)"""
+        self._resident_row("friedman", d_ps, (d_cols, int(k), d_cols.shape[0] // int(k)), out)
+
+    def page_resident(self, d_ps, d_cols, k, out):
+        """page() on a resident table: sdice_page_dev.  d_cols and k as friedman_resident takes them; out: the device fields
+        of PAGE_FIELDS, l and blocks optional.  (page_dev in the call-order catalogue once that is open for change, as
+        friedman_resident.)"""
+        self._resident_row("page", d_ps, (d_cols, int(k), d_cols.shape[0] // int(k)), out)
 
     def pair_table(self, s, pairs):
         """a pair list for the _dev calls: checked against s samples, packed and uploaded once -> DeviceArray uint32[m]
