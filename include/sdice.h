@@ -421,14 +421,51 @@ int sdice_ks_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps,
  *  gets shift = lo = hi = NaN, with tested and rank as usual.  Any other float32 value is legal: signed zeros, subnormals,
  *  values outside [0, 1], +-FLT_MAX (a difference of 2 FLT_MAX is finite in float64).  Swapping the groups gives
  *  (-shift, -hi, -lo) and the same rank, bit for bit up to the +0.0 rule.
- *  Not offered: an exact (qwilcox) rank for small rows, a tie-corrected variance, the paired estimate (the median of the
- *  Walsh averages), a stratified form. */
+ *  Not offered: an exact (qwilcox) rank for small rows, a tie-corrected variance, a stratified form.  The paired estimate
+ *  (the median of the Walsh averages) is sdice_walsh's, below. */
 int sdice_shift(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps,
                 const int32_t* g1, int32_t n1, const int32_t* g2, int32_t n2, double zq,
                 uint8_t* tested, double* shift, double* lo, double* hi, int32_t* rank);
 int sdice_shift_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps,
                     const int32_t* d_g1, int32_t n1, const int32_t* d_g2, int32_t n2, double zq,
                     uint8_t* d_tested, double* d_shift, double* d_lo, double* d_hi, int32_t* d_rank);
+
+/* ---- compare_sample_sets --paired --pseudomedian: the paired shift per row with its distribution-free confidence interval
+ *      (the one-sample Hodges-Lehmann estimate of the within-pair differences, Hollander & Wolfe sections 3.2-3.3; R's
+ *      wilcox.test(paired = TRUE, conf.int = TRUE) prints the estimate as "(pseudo)median"; not in the reference): the size of
+ *      the difference that the signed-rank statistic tests.
+ *  Inputs are sdice_signedrank's plus zq, the standard normal quantile at 1 - (1 - conf) / 2 (1.959963984540054 for 95 %).
+ *  Pair q is the columns (a[q], b[q]), 1 <= m <= 4096, a column at most once over both lists, zq finite and > 0; otherwise
+ *  SDICE_ERR_ARG before any launch, outputs untouched, the reason in sdice_last_error (the host call checks the index range
+ *  and the one-appearance rule, the _dev call m, 2 m <= s and zq).
+ *  Outputs, one slot per row, all required: tested[n] uint8, shift[n], lo[n], hi[n] float64, rank[n] int32 (the outputs of
+ *  sdice_shift); every slot of a row that is not tested is 0.
+ *  Per row: a pair is kept when both of its values are non-NaN, m' pairs are kept, the row is tested when m' >= 3; tested
+ *  equals sdice_signedrank's bit for bit.
+ *  ZERO DIFFERENCES ARE KEPT: the estimator and its interval use all m' differences, unlike the test, which drops the zeros
+ *  (Hollander & Wolfe 3.2-3.3), so m' here is sdice_signedrank's kept count, not its n'.
+ *  The differences d are sdice_signedrank's: on-grid row (every kept value is a 3-decimal PS value float32(key / 1000), key =
+ *  0..1000): d = key_a - key_b, an integer in [-1000, 1000]; any other row: d = x - y in float32 (-0.0 == +0.0).  The estimate
+ *  and its interval thus belong to the test made on the same row.
+ *  The M = m'(m'+1)/2 Walsh sums S_ij = d_i + d_j, i <= j: integers in [-2000, 2000] on the grid, where an order statistic is
+ *  reported as (double)S / 2000.0; S = (double)d_i + (double)d_j, one IEEE float64 addition, on any other row, where an order
+ *  statistic is reported as 0.5 * S.  With W_(1) <= ... <= W_(M) the Walsh averages so ordered:
+ *    shift = the median of W: W_((M+1)/2) for odd M; for even M, with a and b the two middle ones, (double)(S_a + S_b) / 4000.0
+ *      on the grid and 0.5 * (W_a + W_b) otherwise.
+ *    rank  = c = max(1, floor(M/2 - zq sqrt(m'(m'+1)(2m'+1)/24))), evaluated in float64 as written: the normal approximation
+ *      of the signed-rank null distribution without a tie correction.
+ *    lo = W_(c), hi = W_(M + 1 - c).
+ *  c = 1 means that the interval is the whole range of the averages and that the requested level is NOT reached: at 95 %
+ *  that is every row with m' <= 6 (m' = 7 is the first with c = 2).  A zero result is +0.0.  A row that keeps a +-inf value,
+ *  or whose float32 d overflows to +-inf (FLT_MAX - (-FLT_MAX)), gets shift = lo = hi = NaN, with tested and rank as usual.
+ *  Any other float32 value is legal: signed zeros, subnormals, values outside [0, 1].  Swapping a and b gives (-shift, -hi,
+ *  -lo) and the same rank, bit for bit up to the +0.0 rule.
+ *  Not offered: an exact (qsignrank) rank for small rows (R takes it below 50 untied pairs), R's root-finding interval under
+ *  ties, a tie-corrected variance, one-sided intervals. */
+int sdice_walsh(sdice_ctx* ctx, int64_t n, int32_t s, const float* ps, const int32_t* a, const int32_t* b, int32_t m,
+                double zq, uint8_t* tested, double* shift, double* lo, double* hi, int32_t* rank);
+int sdice_walsh_dev(sdice_ctx* ctx, int64_t n, int32_t s, const float* d_ps, const int32_t* d_a, const int32_t* d_b,
+                    int32_t m, double zq, uint8_t* d_tested, double* d_shift, double* d_lo, double* d_hi, int32_t* d_rank);
 
 /* ---- correlate: Spearman rank correlation of the PS values of m listed columns with one covariate value per listed
  *      column, per row scipy.stats.spearmanr(x_kept, ps_kept) under the row rules above (not in the reference).

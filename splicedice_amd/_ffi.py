@@ -130,6 +130,7 @@ for _name, _args, _outputs in (
         ("jonckheere", _TWO_LISTS, 7),
         ("signedrank", _TWO_LISTS, 8),
         ("signedrank_exact", _TWO_LISTS, 9),
+        ("walsh", _TWO_LISTS + [C.c_double], 5),
         ("spearman", _TWO_LISTS, 6),
         ("friedman", [vp, C.c_int32, C.c_int32], 8),          # (k matched sets: cols, k, m)
         ("page", [vp, C.c_int32, C.c_int32], 8),

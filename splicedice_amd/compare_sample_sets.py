@@ -52,6 +52,14 @@ dropped; the columns are the -mx ones with `Q W` where `H` stood.  With `--trend
 is Page's L test (sdice_page) with `z` in that place.  Not with --paired, --exact, --strata, --ks, --shift or --posthoc
 (DESIGN.md section 7).
 
+A tenth: `--pseudomedian` (with --paired) adds the size of the difference that belongs to the signed-rank test: the paired
+Hodges-Lehmann estimate, the median of the Walsh averages (d_i + d_j) / 2, i <= j, of the within-pair differences -- R prints
+it as "(pseudo)median" -- and its distribution-free confidence interval at `--conf LEVEL` (0.95), two order statistics of the
+same averages (sdice_walsh; the interval of R's wilcox.test(paired = TRUE, conf.int = TRUE) with the rank from the normal
+approximation at every size).  `delta`, the difference of the two sets' medians, is not that quantity: it can be 0, or of the opposite sign, on a
+row where every pair moves the same way.  The test stays the signed-rank test (the exact one with `--exact`) and every other
+cell is what it is without the flag; the table gains `shift shift_lo shift_hi` before `p-value`.
+
 On the GPU: the per-row loop :216-232 (NaN drop, <3 skip, scipy ranksums, medians, means)
 -> sdice_ranksum; multipletests(..., "fdr_bh") :235 -> sdice_bh over the tested rows.
 The GTF annotation columns are host string work, as in the reference.
@@ -105,15 +113,16 @@ SHIFT_COLUMNS = ("shift", "shift_lo", "shift_hi")
 def compare(matrix, g1_idx, g2_idx, ctx, paired=False, exact=False, conf=None):
     """-> (kept row indices, dict of compacted per-row results incl. BH-corrected p).  paired: g1_idx[q] and g2_idx[q]
     are the columns of pair q and the test is the signed-rank test.  exact: exact p-values on the small rows (BH runs
-    over the mixed p vector).  conf: the level of --shift; the shift call then reads the same resident table in the same
-    pass and the results gain SHIFT_COLUMNS."""
+    over the mixed p vector).  conf: the level of --shift or, when paired, of --pseudomedian; the shift call (paired: the
+    walsh call) then reads the same resident table in the same pass and the results gain SHIFT_COLUMNS."""
     if hasattr(ctx, "ranksum_dev") and matrix.shape[0]:
         test = row_test(ctx, paired, exact, dev=True)
+        estimate = ctx.walsh_resident if paired else ctx.shift_dev
 
         def launch(d, out):
             test(d["ps"], d["g1"], d["g2"], out)
             if conf is not None:
-                ctx.shift_dev(d["ps"], d["g1"], d["g2"], {f[0]: out["shift" if f[0] == "shift" else "shift_" + f[0]]
+                estimate(d["ps"], d["g1"], d["g2"], {f[0]: out["shift" if f[0] == "shift" else "shift_" + f[0]]
                                                      for f in SHIFT_FIELDS}, conf)
 
         keep, r = tested(ctx, matrix, (RANKSUM_EXACT_FIELDS if exact else RANKSUM_FIELDS) + (SHIFT_RIDERS if conf is not None else []),
@@ -125,7 +134,7 @@ def compare(matrix, g1_idx, g2_idx, ctx, paired=False, exact=False, conf=None):
     keep = np.flatnonzero(res["tested"])
     out = {k: res[k][keep] for k in ("p", "med1", "med2", "mean1", "mean2", "delta")}
     if conf is not None:
-        sh = ctx.shift(matrix, g1_idx, g2_idx, conf)
+        sh = (ctx.walsh if paired else ctx.shift)(matrix, g1_idx, g2_idx, conf)
         out.update(shift=sh["shift"][keep], shift_lo=sh["lo"][keep], shift_hi=sh["hi"][keep])
     out["corrected"] = ctx.bh(out["p"]) if keep.size else np.zeros(0)
     return keep, out
@@ -223,7 +232,20 @@ def add_parser(parser):
                              "range of the differences and the level is not reached (3 v 3 at 95 %%).  Not with --paired, "
                              "-mx, --trend, --ks or --strata (not part of the reference)")
     parser.add_argument("--conf", type=float, required=False, default=None, metavar="LEVEL",
-                        help="With --shift: the confidence level of the interval, 0 < LEVEL < 1 (default 0.95)")
+                        help="With --shift or --pseudomedian: the confidence level of the interval, 0 < LEVEL < 1 (default "
+                             "0.95)")
+    parser.add_argument("--pseudomedian", action="store_true",
+                        help="With --paired: add the paired Hodges-Lehmann estimate of the within-pair change -- the median "
+                             "of the Walsh averages (d_i + d_j) / 2, i <= j, of the pairs' differences d = set 1 - set 2, "
+                             "which R prints as (pseudo)median; the estimate that belongs to the signed-rank test -- and "
+                             "its distribution-free confidence interval at --conf LEVEL (0.95; two order statistics of "
+                             "the same averages): the table gains the columns shift, shift_lo and shift_hi before "
+                             "p-value, every other column is what it is without the flag (with --exact: the exact "
+                             "p-values).  Pairs with equal values count here (the test drops them).  On rows of "
+                             "3-decimal PS values the averages are whole half thousandths.  With few pairs the interval "
+                             "is the whole range of the averages and the level is not reached (up to 6 pairs at 95 %%).  "
+                             "The rank of the interval's ends is the normal approximation without a tie correction at "
+                             "every size (not part of the reference)")
     parser.add_argument("-a", "--annotation", type=str, required=False, default="",
                         help="Optional GTF file to label known splice junctions and genes")
     parser.add_argument("-o", "--outputFile", type=str, required=True,
@@ -271,8 +293,8 @@ def paired_columns(g1, g2, header_names):
 
 
 class Test(typing.NamedTuple):
-    """One row per flag that changes the test.  The refusals: `needs` another flag (flag, why); `conflicts`, the ordered
-    (other flag, why) it cannot be combined with; `multi_rank`, why it does not run under the multi-rank launcher.  A row
+    """One row per flag that changes the test.  The refusals: `needs` another flag (flag, why), or one of `needs_or` in its
+    place; `conflicts`, the ordered (other flag, why) it cannot be combined with; `multi_rank`, why it does not run under the multi-rank launcher.  A row
     that replaces the rank-sum pipeline (--exact and --paired are forms of it: compare()) says how: `fields`, the
     engine's table of its _dev call; sel -> `inputs`, the device inputs beside the table; (ctx, sel) -> `dev`, the launch
     on them; (ctx, matrix, sel) -> `host`, the host call; sel -> `k`, the number of sets of its per-set fields.  `stat`: the
@@ -281,6 +303,7 @@ class Test(typing.NamedTuple):
     flag: str
     conflicts: tuple = ()
     needs: tuple = None
+    needs_or: tuple = ()
     multi_rank: str = None
     fields: list = None
     inputs: typing.Callable = None
@@ -348,7 +371,7 @@ def _matched_sets(test):
 
 
 PAIRED, EXACT, STRATA, TREND, KS, MX = "--paired", "--exact", "--strata", "--trend", "--ks", "-mx/--moreManifests"
-SHIFT, CONF, POSTHOC, REPEATED = "--shift", "--conf", "--posthoc", "--repeated"
+SHIFT, CONF, POSTHOC, REPEATED, PSEUDOMEDIAN = "--shift", "--conf", "--posthoc", "--repeated", "--pseudomedian"
 # in the order the refusals are made; the first selected row with a pipeline is the test that runs
 TESTS = (
     # k matched sets: Friedman's test per junction (with --trend: Page's test, PAGE below).  First, so that it, not the
@@ -362,7 +385,7 @@ TESTS = (
                     (POSTHOC, "there is no post-hoc test of matched sets here")),
          multi_rank=_multi_rank(REPEATED, "the packed all-gather carries the two-set fields only"),
          fields=FRIEDMAN_FIELDS, stat=(("Q", "q"), ("W", "w")), **_matched_sets("friedman")),
-    Test(CONF, needs=(SHIFT, "it is the level of the shift's confidence interval")),
+    Test(CONF, needs=(SHIFT, "it is the level of the shift's confidence interval"), needs_or=(PSEUDOMEDIAN,)),
     # (keeps the rank-sum pipeline, as --exact does: compare() adds the shift call to the same pass)
     Test(SHIFT, conflicts=((PAIRED, "the paired estimate is the median of the Walsh averages, which is not offered"),
                            (MX, "the shift is an estimate between two sets"),
@@ -404,6 +427,12 @@ TESTS = (
     # k >= 3 sets: Kruskal-Wallis per junction (--trend above: Jonckheere-Terpstra over the sets in this order)
     Test(MX, multi_rank=_multi_rank(MX, "the packed all-gather carries the two-set fields only"),
          fields=KRUSKAL_FIELDS, stat=(("H", "h"),), **_k_sets("kruskal")),
+    # (last, so that every older refusal of what it is combined with comes first; it keeps the signed-rank pipeline, as
+    # --shift keeps the rank-sum one: compare() adds the walsh call to the same pass)
+    Test(PSEUDOMEDIAN, needs=(PAIRED, "it is the estimate that belongs to the signed-rank test of matched samples; two "
+                                      "independent sets have --shift"),
+         multi_rank=_multi_rank(PSEUDOMEDIAN, "the packed all-gather carries the signed-rank fields only"),
+         stat=tuple((name, name) for name in SHIFT_COLUMNS)),
 )
 BY_FLAG = {t.flag: t for t in TESTS}
 # --repeated --trend: the same row with Page's call, fields and column
@@ -423,16 +452,17 @@ def run_with(args, ctx=None):
     on = {PAIRED: getattr(args, "paired", False), EXACT: getattr(args, "exact", False), STRATA: getattr(args, "strata", None),
           TREND: getattr(args, "trend", False), KS: getattr(args, "ks", False), MX: more,
           SHIFT: getattr(args, "shift", False), CONF: getattr(args, "conf", None) is not None,
-          POSTHOC: getattr(args, "posthoc", False), REPEATED: getattr(args, "repeated", False)}
+          POSTHOC: getattr(args, "posthoc", False), REPEATED: getattr(args, "repeated", False),
+          PSEUDOMEDIAN: getattr(args, "pseudomedian", False)}
     chosen = [PAGE if t.flag == REPEATED and on[TREND] else t for t in TESTS if on[t.flag]]
     sel = argparse.Namespace(exact=bool(on[EXACT]))
     conf = None
-    if on[SHIFT]:
+    if on[SHIFT] or on[PSEUDOMEDIAN]:
         conf = float(args.conf) if on[CONF] else 0.95
         if not 0.0 < conf < 1.0:                  # (NaN included)
             BY_FLAG[CONF].refuse(f"LEVEL must satisfy 0 < LEVEL < 1 (got {args.conf})")
     for t in chosen:
-        if t.needs and not on[t.needs[0]]:
+        if t.needs and not on[t.needs[0]] and not any(on[f] for f in t.needs_or):
             t.refuse(f"needs {t.needs[0]} ({t.needs[1]})")
         for other, why in t.conflicts:
             if on[other]:

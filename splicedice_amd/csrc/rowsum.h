@@ -35,7 +35,10 @@
 //                         stage_two_sample (with `exact`), check_two_groups
 //   shift.hip (K20)       PsKey, f32_ord / f32_unord, LaneGroup, group_add / group_sort, block_bitonic,
 //                         two_group_median_key, kw_load_bins / kw_scan_bins, the launch sizes, with_group_launch;
-//                         check_two_groups (its own five outputs)
+//                         ShiftOut, the SH_ marks, f64_ord / f64_unord, shift_targets; check_two_groups
+//   walsh.hip (K22)       PsKey, f32_ord / f32_unord, LaneGroup, group_add / group_sort, block_bitonic, kw_load_bins /
+//                         kw_scan_bins, the launch sizes, with_group_launch, ShiftOut, the SH_ marks, f64_ord / f64_unord,
+//                         shift_targets; check_columns
 // (strata.hip and ks.hip: the pass front of the group kernels and the LDS + sums of the block kernels stay written out, A.17)
 // Every helper is inlined into the kernels that call it and the kernels themselves stay in their .hip files, so a change
 // to a helper here is a change to each kernel that uses it -- ranksum.hip's pairq and count kernels among them, whose
@@ -435,6 +438,36 @@ __device__ __forceinline__ RunBounds run_bounds(const T* K, int n, C code, Proj 
 // bits) of a selected value, a NaN last with the padding
 __device__ __forceinline__ unsigned long long two_group_median_key(float v, bool in1) {
     return v == v ? ((unsigned long long)(in1 ? 0u : 1u) << 32) | f32_ord(v) : ~0ull;
+}
+
+// ---- the estimates with an interval (shift.hip, walsh.hip): the five outputs, what a lane keeps of its row beside the
+// images of its order statistics, the order-preserving bits of a float64 and which order statistics are wanted
+struct ShiftOut {
+    uint8_t* tested;
+    double* shift;
+    double* lo;
+    double* hi;
+    int32_t* rank;
+};
+
+constexpr int SH_TESTED = 1, SH_OFF = 2, SH_INF = 4, SH_ODD = 8;
+
+// order-preserving bits of a non-NaN float64 that is not -0.0, and the float64 back
+__device__ __forceinline__ unsigned long long f64_ord(double d) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(d);
+    return b ^ ((b >> 63) ? ~0ull : 0x8000000000000000ull);
+}
+__device__ __forceinline__ double f64_unord(unsigned long long o) {
+    return __longlong_as_double((long long)((o & 0x8000000000000000ull) ? (o ^ 0x8000000000000000ull) : ~o));
+}
+
+// the four order statistics wanted of M differences (or Walsh averages): the middle ones (twice the same for odd M), c and
+// its mirror
+__device__ __forceinline__ void shift_targets(int M, int c, int (&k)[4]) {
+    k[0] = (M + 1) >> 1;
+    k[1] = (M >> 1) + 1;
+    k[2] = c;
+    k[3] = M + 1 - c;
 }
 
 // ---- k sample sets (kruskal.hip, jonckheere.hip): the limits, the sets as a kernel argument, the first walk of a wave

@@ -37,7 +37,8 @@
 //   The switch at 64 selected columns is the lane-group kernels' everywhere (one column per lane of a wave).
 //
 // rowsum.h: PsKey, f32_ord / f32_unord, LaneGroup, group_add, group_sort, block_bitonic, two_group_median_key,
-// kw_load_bins / kw_scan_bins (the scan of a 1024-bin histogram by a wave), the launch sizes and the width ladder;
+// kw_load_bins / kw_scan_bins (the scan of a 1024-bin histogram by a wave), the launch sizes and the width ladder, and
+// what walsh.hip (K22) shares with this file: ShiftOut, the SH_ marks of a row, f64_ord / f64_unord, shift_targets;
 // colcheck.h: the check of the two groups.
 #include "common.h"
 #include <math.h>
@@ -49,37 +50,11 @@ constexpr int SH_MAX_GROUP = 4096;       // columns of one group
 constexpr int SH_GROUP_MAX = 64;         // selected columns the lane-group kernel takes
 constexpr int SH_BINS = 1024;            // 1001 used
 constexpr int SH_GRID_OFS = 1000;        // image of a grid difference: d + 1000
-constexpr int SH_TESTED = 1, SH_OFF = 2, SH_INF = 4, SH_ODD = 8;      // what a lane keeps of its row beside the images
-
-struct ShiftOut {
-    uint8_t* tested;
-    double* shift;
-    double* lo;
-    double* hi;
-    int32_t* rank;
-};
-
-// order-preserving bits of a non-NaN float64 that is not -0.0, and the float64 back
-__device__ __forceinline__ unsigned long long f64_ord(double d) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(d);
-    return b ^ ((b >> 63) ? ~0ull : 0x8000000000000000ull);
-}
-__device__ __forceinline__ double f64_unord(unsigned long long o) {
-    return __longlong_as_double((long long)((o & 0x8000000000000000ull) ? (o ^ 0x8000000000000000ull) : ~o));
-}
 
 // c = max(1, floor(M/2 - zq sqrt(M (N + 1) / 12))) in float64 as written (M (N + 1) < 2^38 is exact)
 __device__ __forceinline__ int shift_rank(int M, int N, double zq) {
     const double c = floor((double)M / 2.0 - zq * sqrt((double)((long long)M * (N + 1)) / 12.0));
     return c < 1.0 ? 1 : (int)c;
-}
-
-// the four order statistics wanted of M differences: the middle ones (twice the same for odd M), c and its mirror
-__device__ __forceinline__ void shift_targets(int M, int c, int (&k)[4]) {
-    k[0] = (M + 1) >> 1;
-    k[1] = (M >> 1) + 1;
-    k[2] = c;
-    k[3] = M + 1 - c;
 }
 
 // the images of the four order statistics -> shift, lo, hi of a tested row; a zero result is +0.0

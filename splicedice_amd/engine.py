@@ -28,6 +28,7 @@ RANKSUM_EXACT_FIELDS = RANKSUM_FIELDS + [("exact", np.uint8)]                   
 KS_FIELDS = [("tested", np.uint8), ("p", np.float64), ("d", np.float64), ("med1", np.float32), ("med2", np.float32),
              ("mean1", np.float32), ("mean2", np.float32), ("delta", np.float32), ("exact", np.uint8)]
 SHIFT_FIELDS = [("tested", np.uint8), ("shift", np.float64), ("lo", np.float64), ("hi", np.float64), ("rank", np.int32)]
+WALSH_FIELDS = SHIFT_FIELDS                     # (the paired estimate: the same five outputs)
 KRUSKAL_FIELDS = [("tested", np.uint8), ("p", np.float64), ("h", np.float64), ("med", np.float32, PER_SET),
                   ("mean", np.float32, PER_SET), ("delta", np.float32)]
 KRUSKAL_DUNN_FIELDS = KRUSKAL_FIELDS + [("pair_z", np.float64, PER_PAIR), ("pair_p", np.float64, PER_PAIR),
@@ -43,7 +44,7 @@ SPEARMAN_FIELDS = [("tested", np.uint8), ("p", np.float64), ("rho", np.float64),
 GRAM_FIELDS = [("shared", np.int64), ("sum1", np.int64), ("sum2", np.int64), ("prod", np.int64)]
 # Every row test: the name of its pair of C entry points (sdice_<name>, sdice_<name>_dev) and of its pair of Context methods
 # (<name>, <name>_dev) -> (its field table, the fields a _dev call may leave out of `out`: the library is handed NULL)
-# (friedman and page: the resident methods are friedman_resident / page_resident for now, see there)
+# (friedman, page and walsh: the resident methods are friedman_resident / page_resident / walsh_resident for now, see there)
 ROW_TESTS = {
     "ranksum": (RANKSUM_FIELDS, ("z",)),
     "ranksum_exact": (RANKSUM_EXACT_FIELDS, ("z",)),
@@ -57,6 +58,7 @@ ROW_TESTS = {
     "page": (PAGE_FIELDS, ("l", "blocks")),
     "signedrank": (RANKSUM_FIELDS, ("z",)),
     "signedrank_exact": (RANKSUM_EXACT_FIELDS, ("z",)),
+    "walsh": (WALSH_FIELDS, ()),
     "spearman": (SPEARMAN_FIELDS, ("rho",)),
     "sample_gram": (GRAM_FIELDS, ()),
 }
@@ -459,12 +461,12 @@ class Context:
         k = len(set_ptr) - 1
         return self._host_row(name, ps, (cols, set_ptr, k), k=k, skip=skip)
 
-    def _host_pairs(self, name, ps, a, b):
-        """_host_row over matched column pairs"""
+    def _host_pairs(self, name, ps, a, b, *more):
+        """_host_row over matched column pairs; more: the arguments after the pair count"""
         a, b = _c(a, np.int32), _c(b, np.int32)
         if a.shape != b.shape or a.ndim != 1:
             raise ValueError(f"{name}: the pair lists must be two vectors of one length, got {a.shape} and {b.shape}")
-        return self._host_row(name, ps, (a, b, a.size))
+        return self._host_row(name, ps, (a, b, a.size, *more))
 
     def ranksum(self, ps, g1, g2):
         """compareSampleSets.py:216-232 for every row; un-compacted outputs + tested mask."""
@@ -546,6 +548,14 @@ class Context:
         """signedrank() with the exact p-value on the rows with at most 31 non-zero differences (include/sdice.h): the
         same outputs + exact; every other field is signedrank()'s bit for bit."""
         return self._host_pairs("signedrank_exact", ps, a, b)
+
+    def walsh(self, ps, a, b, conf=0.95):
+        """the paired shift per row over the matched column pairs (a[q], b[q]) with its confidence interval at level conf
+        (include/sdice.h): the Hodges-Lehmann estimate that belongs to the signed-rank test, R's "(pseudo)median".
+        Un-compacted tested (signedrank()'s), shift (the median of the Walsh averages (d_i + d_j) / 2, i <= j, of the kept
+        pairs' differences, zeros included), lo and hi (two order statistics of them) and rank (which ones; 1 = the whole
+        range, the level is not reached)."""
+        return self._host_pairs("walsh", ps, a, b, shift_quantile(conf))
 
     def spearman(self, ps, cols, x):
         """scipy.stats.spearmanr(x_kept, ps_kept) per row between the PS values of the listed columns and the covariate x
@@ -755,6 +765,11 @@ class Context:
         of PAGE_FIELDS, l and blocks optional.  (page_dev in the call-order catalogue once that is open for change, as
         friedman_resident.)"""
         self._resident_row("page", d_ps, (d_cols, int(k), d_cols.shape[0] // int(k)), out)
+
+    def walsh_resident(self, d_ps, d_a, d_b, out, conf=0.95):
+        """walsh() on a resident table and resident pair lists: sdice_walsh_dev; out: the device fields of WALSH_FIELDS, all of
+        them.  (walsh_dev in the call-order catalogue once that is open for change, as friedman_resident.)"""
+        self._resident_row("walsh", d_ps, (d_a, d_b, d_a.shape[0], shift_quantile(conf)), out)
 
     def pair_table(self, s, pairs):
         """a pair list for the _dev calls: checked against s samples, packed and uploaded once -> DeviceArray uint32[m]
